@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the diffusion-denoiser hot path on MI355X (contract: see the task statement / DESIGN.md).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,10 @@ buffers allocated once (sharding.Exchange).  --ragged: BASELINE configs[3] as SU
 utterances' lengths are drawn from {512, 768, 1024, 1280, 1536} (seed 1234), partitioned longest-first over the
 ranks and run as ragged batches (dsd_set_lengths); frames = the VALID frames.
 
-value = mel-frames/s per denoise step = (valid frames of all N * B utterances) * NFE / seconds per step.
+value = mel-frames/s per denoise step = (valid frames of all N * B utterances) * NFE / seconds per step;
+ms_per_step = milliseconds per timed step (K timed steps after W untimed ones).  Inputs and weights are seeded, so
+the same arguments give the same inputs on every run; --dump-outputs DIR writes the last timed step's results as
+DIR/<name>.npy (float32) for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -56,7 +59,37 @@ def parse():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; at most 64 MB in all, else a fixed seeded sample of each array's flattened elements)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(arrays, out_dir):
+    """arrays: name -> host float32 ndarray.  Every array over its share of the 64 MB budget is replaced by a sample of
+    its flattened elements at indices drawn (sorted, without replacement) from a generator seeded with 0 - the same
+    indices for the same shape, so two builds' files compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)         # room for the .npy headers
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            if keep < a.size:
+                idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def cpu_baseline(kind, params, bargs, bsz, t_len, bins=128):
@@ -255,16 +288,19 @@ def main():
     tokens = (torch.arange(n_tok, device=device) % 59 + 1).to(torch.long)[None].expand(len(mine), n_tok).contiguous()
     f0 = torch.full((len(mine), T), 220.0, device=device)
     voc_ri = voc_noise = None
-    if args.workload == "acoustic_wav":          # SineGen's draws, resident like x_T
-        voc_ri = torch.rand(9, device=device)
-        voc_noise = torch.randn((len(mine), T * 512, 9), device=device)
+    if args.workload == "acoustic_wav":          # SineGen's draws, resident like x_T (seeded: the same inputs every run)
+        gen = torch.Generator(device=device)
+        gen.manual_seed(3)
+        voc_ri = torch.rand(9, generator=gen, device=device)
+        voc_noise = torch.randn((len(mine), T * 512, 9), generator=gen, device=device)
+    last_wav = {}        # acoustic_wav: the whole waveform of the latest step (the gather sees only a view of it)
 
     def run(c):
         if acoustic is not None:
             with torch.no_grad():       # as DiffSingerAcousticInfer.forward_model does (ds_acoustic.py:136)
                 if args.workload == "acoustic_wav":
                     mel = acoustic(tokens, mel2ph, f0, infer=True, noise=noise).diff_out
-                    wav = vocoder.spec2wav_torch(mel, f0=f0, rand_ini=voc_ri, noise=voc_noise)
+                    wav = last_wav["waveform"] = vocoder.spec2wav_torch(mel, f0=f0, rand_ini=voc_ri, noise=voc_noise)
                     return wav.view(len(mine), -1)[:, :T].unsqueeze(-1).expand(-1, -1, 128)   # gather-shaped view
                 if args.workload == "acoustic_e2e":     # the condition comes from the encoder on this GPU
                     return acoustic(tokens, mel2ph, f0, infer=True, noise=noise).diff_out
@@ -276,9 +312,12 @@ def main():
         return d(c, infer=True, noise=noise)
 
     def step(i):
+        # the two conditions alternate counted back from the last timed step, which always gets cond_bufs[0]: the
+        # dumped outputs do not depend on --steps / --warmup
+        k = (args.warmup + args.steps - 1 - i) & 1
         if not use_dist:
-            return run(cond_bufs[i & 1])
-        c = exchange.scatter(cond_bufs[i & 1] if rank == 0 else None)
+            return run(cond_bufs[k])
+        c = exchange.scatter(cond_bufs[k] if rank == 0 else None)
         return exchange.gather(run(c))
 
     def sync():
@@ -321,6 +360,21 @@ def main():
                      "utterances_by_rank": [len(sh) for sh in shards]}
     if rank == 0:
         assert out is not None and torch.isfinite(out).all()
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's results as its caller gets them (with N ranks: rank 0 after the gather), copied to the
+        # host before the roofline pass below runs the workload again
+        if args.workload == "acoustic_wav":
+            arrays = {"waveform": last_wav["waveform"].view(len(mine), -1)}
+        elif variance is not None:
+            arrays = {"pitch": out[..., 0], "energy": out[..., 1], "breathiness": out[..., 2]}
+        else:
+            arrays = {"mel": out}
+        arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+        if lengths:      # ragged: frames beyond an utterance's length are unspecified (GaussianDiffusion.forward) -> 0
+            for i, n in enumerate(lengths if use_dist else my_lens):
+                arrays["mel"][i, n:] = 0.0
+        dumped = dump_outputs(arrays, args.dump_outputs)
     sec_per_step = elapsed / max(args.steps, 1)
     utt_frames = sum(lengths) if lengths else n_utt * T
     frames = utt_frames * nfe
@@ -352,6 +406,8 @@ def main():
     }
     if dist_info is not None:
         result["distributed"] = dist_info
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
 
     if rank == 0 and not args.no_roofline:
         # The layer kernels of this workload (WaveNet: the fused layer kernel / the row-split or GEMM pair, per tile halo and per
