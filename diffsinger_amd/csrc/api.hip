@@ -10,7 +10,7 @@
 //                                      dsd_prepare_cond, dsd_denoise, dsd_sample (+ hipGraph cache), dsd_set_lengths
 //   acoustic encoder ................. dsd_encoder_create, enc_workspace, run_fs2_layers, dsd_encode
 //   variance-model encoders .......... dsd_token_encoder_create, dsd_token_encode, dsd_predict_dur, dsd_cond_assemble
-//   vocoder .......................... run_tconv, dsd_vocoder_create, dsd_vocode
+//   vocoder .......................... run_tconv, dsd_vocoder_create, dsd_vocode, dsd_vocode_ragged
 //   aux decoder ...................... dsd_aux_decode
 //   diagnostics ...................... dsd_get_stats, dsd_kernel_timing*
 #include <math.h>
@@ -108,6 +108,17 @@ struct GraphEntry {
 
 }  // namespace
 
+// dsd_vocode_ragged: one rate of the generator (stage i = after i upsamplings), all pointers into dsd_handle::vr_dev
+struct VocRagStage {
+    int T = 0;                          // padded length of the batch at this rate
+    const int* lens = nullptr;          // [B] item lengths at this rate
+    long valid = 0;                     // their sum
+    const int* cg[3] = {};              // GEMM column groups (item, frame tile) with valid frames, 16 / 32 / 64-frame tiles
+    int ncg[3] = {};
+    const int* tc = nullptr;            // tconv.hip's 256-frame tiles with valid frames
+    int ntc = 0;
+};
+
 struct dsd_handle {
     dsd_config cfg;
     std::string err;
@@ -148,6 +159,11 @@ struct dsd_handle {
     float* v_arena = nullptr;
     std::vector<float*> v_buf;                       // per stage: x, t1, r, acc
     float *v_mel = nullptr, *v_pre_out = nullptr, *v_har = nullptr, *v_phase = nullptr, *v_wav = nullptr;
+    // ragged vocoder batches: per-rate lengths and valid-tile lists (one device block, rebuilt when B, T or the lengths change)
+    std::vector<int> vr_key, vr_host;
+    int* vr_dev = nullptr;
+    size_t vr_cap = 0;
+    std::vector<VocRagStage> vr_st;
     // FastSpeech2 acoustic encoder
     dsd_encoder_config ecfg;
     std::vector<PackedGemm> g_qkv, g_oproj, g_ffn1, g_ffn2;
@@ -1257,8 +1273,10 @@ struct GemmCall {
     int stage, taps, epi, nb, batch, fast;
 };
 
+// vr: a ragged vocoder batch at this GEMM's rate (dsd_vocode_ragged): its lengths and valid tiles instead of dsd_set_lengths'
 GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b_bstride, int b_rstride, int batch,
-                   int T, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false) {
+                   int T, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false,
+                   const VocRagStage* vr = nullptr) {
     GemmCall c;
     memset(&c.p, 0, sizeof(c.p));
     GemmP& p = c.p;
@@ -1279,15 +1297,16 @@ GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b
     p.in_scale = 1.f;
     // ragged batches: only a convolution along time can carry an item's padded frames into its valid ones, so only the
     // k-tap GEMMs over the utterances' (B, T) frames mask their input (not the 1x1s, not the step-embedding MLPs)
-    const bool ragged = h->use_cg && !h->lens_host.empty() && batch == h->B && T == h->T;
-    p.lens = (ragged && g.taps > 1) ? h->lens_dev : nullptr;
+    const bool ragged = vr || (h->use_cg && !h->lens_host.empty() && batch == h->B && T == h->T);
+    p.lens = vr ? vr->lens : (ragged && g.taps > 1) ? h->lens_dev : nullptr;
     c.stage = stage;
     c.taps = g.taps;
     c.epi = epi;
     c.batch = batch;
     // tile width: 64 frames when that still fills the chip twice over, else 32
     const int mtiles = g.pairC > 0 ? (g.pairC + 31) / 32 : (g.M + 63) / 64;
-    const long wg64 = (long)batch * ((T + 63) / 64) * mtiles;
+    // (a ragged vocoder batch: counted over its valid tiles, the shape B lone calls of similar length would take)
+    const long wg64 = (vr ? (long)vr->ncg[2] : (long)batch * ((T + 63) / 64)) * mtiles;
     const long nb2_min = path_opts().nb2_min;          // (DSD_NB2_MIN_WG: diagnostic override)
     c.nb = wg64 >= nb2_min ? 2 : 1;
     // a conv on the generic path keeps all input channels resident: 64-frame tiles only while that fits in LDS
@@ -1316,8 +1335,8 @@ GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b
     const int BN = c.nb == 0 ? 16 : 32 * c.nb;
     p.tiles_per_b = (T + BN - 1) / BN;
     if (ragged) {       // the launch covers only the tiles that hold valid frames (lists built by prepare_ragged)
-        p.cgmap = h->cg_dev[c.nb];
-        p.ncg = h->cg_n[c.nb];
+        p.cgmap = vr ? vr->cg[c.nb] : h->cg_dev[c.nb];
+        p.ncg = vr ? vr->ncg[c.nb] : h->cg_n[c.nb];
     }
     int S = BN + 2 * p.HL;
     while (S % 32 != 16) S += 4;
@@ -2135,6 +2154,7 @@ void dsd_destroy(dsd_handle* h) {
         if (h->cg_dev[k]) (void)hipFree(h->cg_dev[k]);
     if (h->e_arena) (void)hipFree(h->e_arena);
     if (h->v_arena) (void)hipFree(h->v_arena);
+    if (h->vr_dev) (void)hipFree(h->vr_dev);
     delete h;
 }
 
@@ -2569,7 +2589,7 @@ int dsd_cond_assemble(const dsd_assemble_args* args, float* out, void* stream) {
 }
 
 static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float* out, const float* res, int B, int C,
-                     int T, int Ts, int dil, float slope_in, int act, hipStream_t st) {
+                     int T, int Ts, int dil, float slope_in, int act, hipStream_t st, const VocRagStage* vr = nullptr) {
     TConvP p;
     memset(&p, 0, sizeof(p));
     p.W = h->blob + pt.w_off;
@@ -2584,6 +2604,10 @@ static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float
     p.SP = SP;
     p.slope_in = slope_in; p.act = act; p.co_real = pt.co_real;
     p.lds_bytes = tconv_lds_bytes(pt.ci, pt.co, pt.taps, SP);
+    if (vr) {
+        p.lens = vr->lens; p.cgmap = vr->tc; p.ncg = vr->ntc;
+        p.tiles = (T + 255) / 256;
+    }
     if (p.lds_bytes > 160 * 1024) return fail(h, DSD_EINVAL, "few-channel conv needs %d bytes of LDS", p.lds_bytes);
     hipError_t e = launch_tconv(p, pt.ci, pt.co, B, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "tconv launch failed: %s", hipGetErrorString(e));
@@ -2639,23 +2663,93 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
     return DSD_OK;
 }
 
-int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m, int64_t stride_t,
-               const float* f0, const float* rand_ini, const float* noise, const float* pre_noise, float* wav_out,
-               void* stream) {
+namespace {
+
+// dsd_vocode_ragged's bookkeeping: item lengths at every rate and the lists of tiles that hold valid frames - for the GEMMs
+// at 32 / 64 frames (the vocoder's convolutions run on the generic path, never on 16-frame tiles) and for tconv.hip at 256 -
+// in one device block, copied on the caller's stream; kept while B, T and the lengths stay the same
+int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipStream_t st) {
+    const dsd_vocoder_config& v = h->vcfg;
+    std::vector<int> key = {B, T};
+    key.insert(key.end(), lengths, lengths + B);
+    if (h->vr_dev && key == h->vr_key) return DSD_OK;
+    const int NU = v.n_ups;
+    std::vector<VocRagStage> st_(NU + 1);
+    std::vector<int>& host = h->vr_host;
+    host.clear();
+    std::vector<size_t> off_lens(NU + 1), off_cg[2], off_tc(NU + 1);
+    off_cg[0].resize(NU + 1);
+    off_cg[1].resize(NU + 1);
+    long mul = 1;
+    for (int i = 0; i <= NU; ++i) {
+        VocRagStage& r = st_[i];
+        r.T = (int)(T * mul);
+        off_lens[i] = host.size();
+        for (int b = 0; b < B; ++b) {
+            host.push_back((int)(lengths[b] * mul));
+            r.valid += lengths[b] * mul;
+        }
+        for (int k = 0; k < 3; ++k) {       // tile counts at 16 / 32 / 64 frames (the GEMM's tile-width choice reads them)
+            const int BN = 16 << k;
+            for (int b = 0; b < B; ++b) r.ncg[k] += (int)((lengths[b] * mul + BN - 1) / BN);
+        }
+        for (int k = 1; k < 3; ++k) {
+            const int BN = 16 << k, tiles = (r.T + BN - 1) / BN;
+            off_cg[k - 1][i] = host.size();
+            for (int b = 0; b < B; ++b)
+                for (long ft = 0; ft * BN < lengths[b] * mul; ++ft) host.push_back(b * tiles + (int)ft);
+        }
+        off_tc[i] = host.size();
+        const int tiles = (r.T + 255) / 256;
+        for (int b = 0; b < B; ++b)
+            for (long ft = 0; ft * 256 < lengths[b] * mul; ++ft) host.push_back(b * tiles + (int)ft);
+        r.ntc = (int)(host.size() - off_tc[i]);
+        if (i < NU) mul *= v.upsample_rates[i];
+    }
+    if (host.size() > h->vr_cap) {
+        if (h->vr_dev) (void)hipFree(h->vr_dev);
+        h->vr_dev = nullptr;
+        h->vr_cap = 0;
+        if (hipMalloc(&h->vr_dev, sizeof(int) * host.size()) != hipSuccess)
+            return fail(h, DSD_ENOMEM, "dsd_vocode_ragged: hipMalloc of %zu tile indices failed", host.size());
+        h->vr_cap = host.size();
+    }
+    h->vr_key.clear();          // stale until the copy is queued
+    if (hipMemcpyAsync(h->vr_dev, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(h, DSD_EHIP, "dsd_vocode_ragged: copy of the tile lists failed");
+    for (int i = 0; i <= NU; ++i) {
+        st_[i].lens = h->vr_dev + off_lens[i];
+        st_[i].cg[1] = h->vr_dev + off_cg[0][i];
+        st_[i].cg[2] = h->vr_dev + off_cg[1][i];
+        st_[i].tc = h->vr_dev + off_tc[i];
+    }
+    h->vr_st = st_;
+    h->vr_key = key;
+    return DSD_OK;
+}
+
+// dsd_vocode and dsd_vocode_ragged (lengths != nullptr: item b is computed as if alone at T = lengths[b])
+int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
+                int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
+                const float* pre_noise, float* wav_out, void* stream) {
     refresh_path_opts();
-    if (!h || !mel || !f0 || !wav_out) return fail(h, DSD_EINVAL, "dsd_vocode: null argument");
-    if (!is_voc(h)) return fail(h, DSD_ESTATE, "dsd_vocode: this handle is not a vocoder");
+    if (!h || !mel || !f0 || !wav_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
+    if (!is_voc(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a vocoder", who);
     if (!h->vcfg.mini_nsf && (!rand_ini || !noise))
-        return fail(h, DSD_EINVAL, "dsd_vocode: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)");
+        return fail(h, DSD_EINVAL, "%s: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)", who);
     if (h->vcfg.noise_sigma > 0.f && !pre_noise)
-        return fail(h, DSD_EINVAL, "dsd_vocode: pre_noise is required when noise_sigma > 0 (models.py:272-273)");
-    if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_vocode: weights are not finalized");
-    if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_vocode: B and T must be positive (B=%d, T=%d)", B, T);
+        return fail(h, DSD_EINVAL, "%s: pre_noise is required when noise_sigma > 0 (models.py:272-273)", who);
+    if (!h->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
+    if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "%s: B and T must be positive (B=%d, T=%d)", who, B, T);
     if (stride_t != 1 && stride_m != 1)
-        return fail(h, DSD_EINVAL, "dsd_vocode: mel must be contiguous along T ([B,M,T]) or along M ([B,T,M])");
+        return fail(h, DSD_EINVAL, "%s: mel must be contiguous along T ([B,M,T]) or along M ([B,T,M])", who);
+    if (lengths)
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 1 || lengths[b] > T)
+                return fail(h, DSD_EINVAL, "%s: lengths[%d] = %d is outside [1, T = %d]", who, b, lengths[b], T);
     const dsd_vocoder_config& v = h->vcfg;
     const long upp = voc_upp(v, 0);
-    if ((long)T * upp > (1L << 28)) return fail(h, DSD_EINVAL, "dsd_vocode: %ld output samples per utterance is too long", (long)T * upp);
+    if ((long)T * upp > (1L << 28)) return fail(h, DSD_EINVAL, "%s: %ld output samples per utterance is too long", who, (long)T * upp);
     hipStream_t st = (hipStream_t)stream;
     HIP_OK(h, hipSetDevice(v.device));
     const int NU = v.n_ups, C0 = v.upsample_initial_channel, Ts0 = padded_ts(T);
@@ -2696,9 +2790,12 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
         h->v_buf.clear();
         for (size_t o : ob) h->v_buf.push_back(a + o);
     }
+    int rc;
+    if (lengths && (rc = prepare_voc_ragged(h, B, T, lengths, st))) return rc;
+    // per rate: nullptr (dense) or the ragged batch's lengths and tiles
+    auto rag = [&](int i) -> const VocRagStage* { return lengths ? &h->vr_st[i] : nullptr; };
     const float* blob = h->blob;
     hipError_t er;
-    int rc;
 #define VOC_OK(expr, what)                                                                        \
     if ((er = (expr)) != hipSuccess) return fail(h, DSD_EHIP, what " launch failed: %s", hipGetErrorString(er))
     // source: harmonic-plus-noise at the output rate (models.py:120-168, 200-203, 266), or - mini_nsf - one interpolated
@@ -2707,20 +2804,23 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
     if (v.mini_nsf) {
         const int src_upp = (int)(src_len / T);
         VOC_OK(launch_voc_fast_source(f0, B, T, src_upp, (float)v.sampling_rate / (float)voc_upp(v, 2), h->v_phase, lts[NU],
-                                      h->v_har, st), "source");
+                                      h->v_har, st, lengths ? rag(0)->lens : nullptr), "source");
     } else {
         VOC_OK(launch_voc_source(f0, rand_ini, noise, blob + h->v_linw, blob + h->v_linb, B, T, (int)upp, v.harmonic_num + 1,
-                                 (float)v.sampling_rate, 0.1f, 0.003f, h->v_phase, lts[NU], h->v_har, st), "source");
+                                 (float)v.sampling_rate, 0.1f, 0.003f, h->v_phase, lts[NU], h->v_har, st,
+                                 lengths ? rag(0)->lens : nullptr), "source");
     }
     // conv_pre  (models.py:227, 267)
     VOC_OK(launch_pack(mel, stride_b, stride_m, stride_t, h->v_mel, B, v.num_mels, T, Ts0, st), "pack(mel)");
     {
-        GemmCall g = make_gemm(h, h->v_pre, h->v_mel, (long)v.num_mels * Ts0, Ts0, B, T, ST_PLAIN, EP_BIAS_ACT, 1, true);
+        GemmCall g = make_gemm(h, h->v_pre, h->v_mel, (long)v.num_mels * Ts0, Ts0, B, T, ST_PLAIN, EP_BIAS_ACT, 1, true, false,
+                               rag(0));
         g.p.act = ACT_NONE; g.p.out = h->v_pre_out; g.p.o_bstride = (long)C0 * Ts0; g.p.o_rstride = Ts0;
         if ((rc = run_gemm(h, g, st))) return rc;
     }
     if (v.noise_sigma > 0.f)      // x += noise_sigma * randn_like(x)  (models.py:272-273)
-        VOC_OK(launch_voc_add_noise(h->v_pre_out, pre_noise, B, C0, T, Ts0, v.noise_sigma, st), "pre-noise");
+        VOC_OK(launch_voc_add_noise(h->v_pre_out, pre_noise, B, C0, T, Ts0, v.noise_sigma, st, lengths ? rag(0)->lens : nullptr),
+               "pre-noise");
     const float* cur = h->v_pre_out;
     int cur_c = C0;
     for (int i = 0; i < NU; ++i) {
@@ -2732,7 +2832,7 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
         float* acc = h->v_buf[4 * i + 3];
         const long xs = (long)ch * Tsq;
         {   // leaky_relu -> ConvTranspose1d  (models.py:271-272)
-            GemmCall g = make_gemm(h, h->v_ups[i], cur, (long)cur_c * Tsi, Tsi, B, Tin, ST_LRELU, EP_SCATTER, 1, true);
+            GemmCall g = make_gemm(h, h->v_ups[i], cur, (long)cur_c * Tsi, Tsi, B, Tin, ST_LRELU, EP_SCATTER, 1, true, false, rag(i));
             g.p.in_scale = 0.1f; g.p.C = ch; g.p.up = u;
             g.p.out = x; g.p.o_bstride = xs; g.p.o_rstride = Tsq;
             if ((rc = run_gemm(h, g, st))) return rc;
@@ -2741,10 +2841,12 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
             const int sf = (int)voc_upp(v, i + 1);
             const int ksz = i + 1 < NU ? 2 * sf : 1;
             VOC_OK(launch_voc_noise_conv(x, h->v_har, blob + h->v_nw[i], blob + h->v_nb[i], B, ch, Tq, Tsq, sf, ksz,
-                                         len[NU], lts[NU], st), "noise conv");
+                                         len[NU], lts[NU], st, lengths ? rag(i + 1)->lens : nullptr,
+                                         lengths ? rag(NU)->lens : nullptr), "noise conv");
         } else if (i == 1) {  // + source_conv(har_source): k = 1, same rate  (models.py:277-279)
             VOC_OK(launch_voc_noise_conv(x, h->v_har, blob + h->v_nw[i], blob + h->v_nb[i], B, ch, Tq, Tsq, 1, 1, src_len,
-                                         lts[NU], st), "source conv");
+                                         lts[NU], st, lengths ? rag(2)->lens : nullptr, lengths ? rag(2)->lens : nullptr),
+                   "source conv");
         }
         for (int j = 0; j < v.n_kernels; ++j) {     // residual blocks  (models.py:280-286; ResBlock1 :62-69, ResBlock2 :92-97)
             const auto& cv = h->v_res[(size_t)i * v.n_kernels + j];
@@ -2754,11 +2856,11 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
                 const int dil = v.resblock_dilation_sizes[j][d];
                 if (!tv.empty()) {          // 16 / 32 channels: time-major convolutions (tconv.hip)
                     if (v.resblock == 1) {
-                        if ((rc = run_tconv(h, tv[2 * d], src, t1, nullptr, B, ch, Tq, Tsq, dil, 0.1f, ACT_LRELU, st))) return rc;
-                        if ((rc = run_tconv(h, tv[2 * d + 1], t1, r, src, B, ch, Tq, Tsq, 1, 1.f, ACT_NONE, st))) return rc;
+                        if ((rc = run_tconv(h, tv[2 * d], src, t1, nullptr, B, ch, Tq, Tsq, dil, 0.1f, ACT_LRELU, st, rag(i + 1)))) return rc;
+                        if ((rc = run_tconv(h, tv[2 * d + 1], t1, r, src, B, ch, Tq, Tsq, 1, 1.f, ACT_NONE, st, rag(i + 1)))) return rc;
                     } else {
                         float* dst = src == x ? r : t1;
-                        if ((rc = run_tconv(h, tv[d], src, dst, src, B, ch, Tq, Tsq, dil, 0.1f, ACT_NONE, st))) return rc;
+                        if ((rc = run_tconv(h, tv[d], src, dst, src, B, ch, Tq, Tsq, dil, 0.1f, ACT_NONE, st, rag(i + 1)))) return rc;
                         if (dst == t1) {
                             float* tmp = r; r = t1; t1 = tmp;
                         }
@@ -2766,11 +2868,13 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
                     continue;
                 }
                 if (v.resblock == 1) {
-                    GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, dil, true);
+                    GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, dil, true, false,
+                                            rag(i + 1));
                     c1.p.in_scale = 0.1f; c1.p.act = ACT_LRELU;
                     c1.p.out = t1; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
                     if ((rc = run_gemm(h, c1, st))) return rc;
-                    GemmCall c2 = make_gemm(h, cv[2 * d + 1], t1, xs, Tsq, B, Tq, ST_PLAIN, EP_BIAS_RES, 1, true);
+                    GemmCall c2 = make_gemm(h, cv[2 * d + 1], t1, xs, Tsq, B, Tq, ST_PLAIN, EP_BIAS_RES, 1, true, false,
+                                            rag(i + 1));
                     c2.p.aux = src; c2.p.aux_bstride = xs; c2.p.aux_rstride = Tsq;
                     c2.p.out = r; c2.p.o_bstride = xs; c2.p.o_rstride = Tsq;
                     if ((rc = run_gemm(h, c2, st))) return rc;
@@ -2778,7 +2882,8 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
                     // xt + x with x read both as the (leaky-ReLU'd) conv input and as the residual: the output goes to
                     // the other buffer, the conv's halo reads must not see this launch's own stores
                     float* dst = (src == x || src == t1) ? r : t1;
-                    GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_RES, dil, true);
+                    GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_RES, dil, true, false,
+                                            rag(i + 1));
                     c1.p.in_scale = 0.1f;
                     c1.p.aux = src; c1.p.aux_bstride = xs; c1.p.aux_rstride = Tsq;
                     c1.p.out = dst; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
@@ -2796,9 +2901,9 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
     {   // leaky_relu (default slope 0.01) -> conv_post -> tanh  (models.py:287-289)
         const int ch = voc_stage_channels(v, NU - 1), Tq = (int)len[NU], Tsq = lts[NU];
         if (h->v_postt.valid()) {
-            if ((rc = run_tconv(h, h->v_postt, cur, h->v_wav, nullptr, B, ch, Tq, Tsq, 1, 0.01f, ACT_TANH, st))) return rc;
+            if ((rc = run_tconv(h, h->v_postt, cur, h->v_wav, nullptr, B, ch, Tq, Tsq, 1, 0.01f, ACT_TANH, st, rag(NU)))) return rc;
         } else {
-            GemmCall g = make_gemm(h, h->v_post, cur, (long)ch * Tsq, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, 1, true);
+            GemmCall g = make_gemm(h, h->v_post, cur, (long)ch * Tsq, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, 1, true, false, rag(NU));
             g.p.in_scale = 0.01f; g.p.act = ACT_TANH;
             g.p.out = h->v_wav; g.p.o_bstride = Tsq; g.p.o_rstride = Tsq;
             if ((rc = run_gemm(h, g, st))) return rc;
@@ -2807,6 +2912,23 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
     }
 #undef VOC_OK
     return DSD_OK;
+}
+
+}  // namespace
+
+int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m, int64_t stride_t,
+               const float* f0, const float* rand_ini, const float* noise, const float* pre_noise, float* wav_out,
+               void* stream) {
+    return vocode_impl("dsd_vocode", h, mel, B, T, stride_b, stride_m, stride_t, nullptr, f0, rand_ini, noise, pre_noise,
+                       wav_out, stream);
+}
+
+int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
+                      int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
+                      const float* pre_noise, float* wav_out, void* stream) {
+    if (!lengths) return fail(h, DSD_EINVAL, "dsd_vocode_ragged: null lengths");
+    return vocode_impl("dsd_vocode_ragged", h, mel, B, T, stride_b, stride_m, stride_t, lengths, f0, rand_ini, noise,
+                       pre_noise, wav_out, stream);
 }
 
 int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,

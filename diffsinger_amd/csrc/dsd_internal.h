@@ -373,6 +373,11 @@ struct TConvP {
     int act;                // ACT_NONE / ACT_LRELU / ACT_TANH on the output (before the residual)
     int co_real;            // output channels actually stored
     int lds_bytes;
+    // ragged batch (dsd_vocode_ragged; cgmap == nullptr: dense): the grid is the ncg (item, 256-frame tile) entries of cgmap,
+    // each b * tiles + tile, and item b's input frames t >= lens[b] are zero padding
+    const int* lens;
+    const int* cgmap;
+    int ncg, tiles;
 };
 int tconv_lds_bytes(int ci, int co, int taps, int SP);
 hipError_t tconv_init_all();
@@ -381,12 +386,15 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // vocoder_kernels.hip (NSF-HiFiGAN source, noise convs, residual-block average)
 hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w,
                              const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp, float noise_std,
-                             float* acc_tmp, int Tsu, float* har, hipStream_t st);
-hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int T, int Ts, float sigma, hipStream_t st);
+                             float* acc_tmp, int Tsu, float* har, hipStream_t st, const int* lens = nullptr);
+hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int T, int Ts, float sigma, hipStream_t st,
+                                const int* lens = nullptr);
 hipError_t launch_voc_fast_source(const float* f0, int B, int T, int upp, float source_sr, float* acc_tmp, int Tsu, float* har,
-                                  hipStream_t st);
+                                  hipStream_t st, const int* lens = nullptr);
+// lens_q / lens_up (ragged: per-item output frames / source samples) both or neither
 hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, const float* bias, int B, int C, int Tq,
-                                 int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st);
+                                 int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st, const int* lens_q = nullptr,
+                                 const int* lens_up = nullptr);
 hipError_t launch_voc_accum(float* acc, const float* r, long n, int first, float div, hipStream_t st);
 // encoder_kernels.hip (FastSpeech2 acoustic encoder glue)
 struct EncExpandArgs {

@@ -1017,6 +1017,15 @@ hipError_t gemm_init_all() {
     if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 2, 0>()) != hipSuccess) return e;
     if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 1, 0>()) != hipSuccess) return e;
     if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 2, 0>()) != hipSuccess) return e;
+    // ... and their ragged forms (dsd_vocode_ragged; conv_pre is the aux decoder's ST_PLAIN k-tap instantiation above)
+    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -1043,9 +1052,16 @@ hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int
             return (fast && p.S == 80) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, 1>(p, batch, st)
                                        : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, 1>(p, batch, st);
         }
-        if (stage == ST_PLAIN && epi == EP_BIAS_ACT && taps == p.taps && !fast && nb >= 1)       // aux decoder's k-tap convs
-            return nb == 1 ? launch_one<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>(p, batch, st)
-                           : launch_one<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>(p, batch, st);
+        // k-tap convs with the kernel size taken from the argument block: the aux decoder's, NSF-HiFiGAN's
+#define DSD_DENSE_R(ST, EP)                                                                                       \
+        if (stage == ST && epi == EP && taps == p.taps && !fast && nb >= 1)                                         \
+            return nb == 1 ? launch_one<ST, 0, EP, 1, 0, 0, 2, 1>(p, batch, st) : launch_one<ST, 0, EP, 2, 0, 0, 2, 1>(p, batch, st);
+        DSD_DENSE_R(ST_PLAIN, EP_BIAS_ACT)
+        DSD_DENSE_R(ST_LRELU, EP_BIAS_ACT)
+        DSD_DENSE_R(ST_PLAIN, EP_BIAS_RES)
+        DSD_DENSE_R(ST_LRELU, EP_BIAS_RES)
+        DSD_DENSE_R(ST_LRELU, EP_SCATTER)
+#undef DSD_DENSE_R
         return hipErrorInvalidValue;
     }
     DSD_CASE(ST_PLAIN, 1, EP_BIAS_ACT)

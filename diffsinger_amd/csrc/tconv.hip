@@ -19,34 +19,45 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TC_TT = 256;          // frames per workgroup (4 waves x 4 blocks of 16)
 
-template <int CI, int CO>
+// RAG = 1 (dsd_vocode_ragged): the grid covers only the (item, tile) entries of p.cgmap that hold valid frames, and item b's
+// input is zero from p.lens[b] on.  A separate instantiation: the dense kernel carries nothing new.
+template <int CI, int CO, int RAG>
 __global__ __launch_bounds__(256) void tconv_kernel(const TConvP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NBN = CO / 16;                   // 16-column output blocks
     constexpr int KC4 = CI / 4;                    // k4 steps per tap
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y;
-    const int t0 = blockIdx.x * TC_TT;
+    int b, t0, Tb;
+    if constexpr (RAG) {
+        const int e = p.cgmap[blockIdx.x];
+        b = e / p.tiles;
+        t0 = (e - b * p.tiles) * TC_TT;
+        Tb = p.lens[b];
+    } else {
+        b = blockIdx.y;
+        t0 = blockIdx.x * TC_TT;
+        Tb = p.T;
+    }
     const int HP = p.HP, SP = p.SP;                // halo (multiple of 4) and LDS row stride
     float* wfrag = lds;                            // [taps][KC4][NBN][64]
     float* tile = lds + p.taps * KC4 * NBN * 64;   // [CI][SP]
     // ---- weights: already in fragment order, straight copy ----
     const int nw = p.taps * KC4 * NBN * 64;
     for (int i = tid * 4; i < nw; i += 1024) *reinterpret_cast<f32x4*>(wfrag + i) = *reinterpret_cast<const f32x4*>(p.W + i);
-    // ---- input tile: frames [t0 - HP, t0 + TT + HP), leaky ReLU on load, zero outside [0, T) ----
+    // ---- input tile: frames [t0 - HP, t0 + TT + HP), leaky ReLU on load, zero outside [0, T) (ragged: [0, lens[b])) ----
     const float* xb = p.x + (long)b * p.x_bstride;
     const int w4 = (TC_TT + 2 * HP) / 4;
     for (int i = tid; i < CI * w4; i += 256) {
         const int c = i / w4, q = i - c * w4;
         const int t = t0 - HP + q * 4;
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (t >= -3 && t < p.T) {                  // some element of the float4 may be valid (rows are 16-byte aligned)
+        if (t >= -3 && t < Tb) {                  // some element of the float4 may be valid (rows are 16-byte aligned)
             const f32x4 g = *reinterpret_cast<const f32x4*>(xb + (long)c * p.x_rstride + t);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float y = g[e];
                 if (p.slope_in != 1.f) y = y >= 0.f ? y : y * p.slope_in;
-                v[e] = (t + e >= 0 && t + e < p.T) ? y : 0.f;
+                v[e] = (t + e >= 0 && t + e < Tb) ? y : 0.f;
             }
         }
         *reinterpret_cast<f32x4*>(tile + c * SP + q * 4) = v;
@@ -117,29 +128,41 @@ int tconv_lds_bytes(int ci, int co, int taps, int SP) {
     return (taps * ci * co + (in_tile > out_tile ? in_tile : out_tile)) * 4;
 }
 
-template <int CI, int CO>
+template <int CI, int CO, int RAG>
 static hipError_t tconv_go(const TConvP& p, int batch, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<CI, CO>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<CI, CO, RAG>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    hipLaunchKernelGGL((tconv_kernel<CI, CO>), dim3((p.T + TC_TT - 1) / TC_TT, batch), dim3(256), p.lds_bytes, st, p);
+    if (RAG) {
+        if (p.ncg == 0) return hipSuccess;
+        hipLaunchKernelGGL((tconv_kernel<CI, CO, RAG>), dim3(p.ncg), dim3(256), p.lds_bytes, st, p);
+    } else {
+        hipLaunchKernelGGL((tconv_kernel<CI, CO, RAG>), dim3((p.T + TC_TT - 1) / TC_TT, batch), dim3(256), p.lds_bytes, st, p);
+    }
     return hipGetLastError();
 }
 
 hipError_t tconv_init_all() {      // raise the dynamic-LDS limits once, outside any stream capture
     hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<16, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<32, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<16, 16, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<32, 32, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<16, 16, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<32, 32, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
     return hipSuccess;
 }
 
 hipError_t launch_tconv(const TConvP& p, int ci, int co, int batch, hipStream_t st) {
-    if (ci == 16 && co == 16) return tconv_go<16, 16>(p, batch, st);
-    if (ci == 32 && co == 32) return tconv_go<32, 32>(p, batch, st);
+    if (p.cgmap) {
+        if (ci == 16 && co == 16) return tconv_go<16, 16, 1>(p, batch, st);
+        if (ci == 32 && co == 32) return tconv_go<32, 32, 1>(p, batch, st);
+        return hipErrorInvalidValue;
+    }
+    if (ci == 16 && co == 16) return tconv_go<16, 16, 0>(p, batch, st);
+    if (ci == 32 && co == 32) return tconv_go<32, 32, 0>(p, batch, st);
     return hipErrorInvalidValue;
 }
 

@@ -3,6 +3,8 @@
 // with a scatter epilogue); what is here is the harmonic-plus-noise source (SineGen / SourceModuleHnNSF), the
 // single-input-channel strided "noise convs" that inject it at every resolution, and the residual-block average.
 // Internal layout [batch][channel][Ts], lanes along time.
+// RAG = 1 (dsd_vocode_ragged): item b of the batch is valid for lens[b] frames / samples of the launch's rate and is
+// computed as if it had been run alone at that length; separate instantiations, so the dense kernels carry nothing new.
 #include "dsd_internal.h"
 
 namespace dsd {
@@ -12,13 +14,15 @@ namespace dsd {
 // the per-frame phase advances wrapped into [-0.5, 0.5) - torch.cumsum's sequential order, one lane per utterance.
 //   rad_last = f0 / sr * upp;  rad2 = fmod(rad_last + 0.5, 1) - 0.5;  acc[t] = fmod(sum_{t' <= t} rad2[t'], 1)
 // ---------------------------------------------------------------------------------------------
+template <int RAG>
 __global__ __launch_bounds__(256) void voc_phase_kernel(const float* __restrict__ f0, int T, float sr, int upp,
-                                                        float* __restrict__ acc) {
+                                                        float* __restrict__ acc, const int* __restrict__ lens) {
     __shared__ float buf[2048];
     const int b = blockIdx.x;
+    const int Tb = RAG ? lens[b] : T;              // the running phase of an item stops at its own end
     float run = 0.f;                               // carried by thread 0 across the 2048-frame pieces
-    for (int base = 0; base < T; base += 2048) {
-        const int n = min(2048, T - base);
+    for (int base = 0; base < Tb; base += 2048) {
+        const int n = min(2048, Tb - base);
         for (int i = threadIdx.x; i < n; i += 256) {       // per-frame advance, in parallel
             const float rad_last = f0[(long)b * T + base + i] / sr * (float)upp;
             buf[i] = fmodf(rad_last + 0.5f, 1.0f) - 0.5f;
@@ -42,14 +46,19 @@ __global__ __launch_bounds__(256) void voc_phase_kernel(const float* __restrict_
 // rand_ini [dim] (element 0 is forced to 0, models.py:146) and noise [B, T*upp, dim] are inputs: the reference
 // draws them with torch.rand / torch.randn_like.
 // ---------------------------------------------------------------------------------------------
+// RAG = 1: rand_ini is [B][dim] (one draw per item, as B lone calls make them); samples past lens[b] * upp are not
+// written (the noise convs read them as zero).
 constexpr int VOC_MAXDIM = 16;
+template <int RAG>
 __global__ void voc_source_kernel(const float* __restrict__ f0, const float* __restrict__ acc,
                                   const float* __restrict__ rand_ini, const float* __restrict__ noise,
                                   const float* __restrict__ lin_w, const float* __restrict__ lin_b, int T, int upp,
-                                  int dim, float sr, float sine_amp, float noise_std, int Tsu, float* __restrict__ har) {
+                                  int dim, float sr, float sine_amp, float noise_std, int Tsu, float* __restrict__ har,
+                                  const int* __restrict__ lens) {
     const int b = blockIdx.y;
     const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;       // sample index within the utterance
-    if (s >= (long)T * upp) return;
+    if (s >= (long)(RAG ? lens[b] : T) * upp) return;
+    if (RAG) rand_ini += (long)b * dim;
     const int t = (int)(s / upp), n = (int)(s - (long)t * upp);
     const float f = f0[(long)b * T + t];
     float rad = f / sr * (float)(n + 1);
@@ -75,16 +84,24 @@ __global__ void voc_source_kernel(const float* __restrict__ f0, const float* __r
 // NQ consecutive frames of its channel, and the source window of the workgroup's frames sits in LDS, read as a
 // broadcast.  One workgroup = min(C, 256) channels x (256 / C) groups of NQ frames.
 // ---------------------------------------------------------------------------------------------
+// RAG = 1: item b has lens_q[b] output frames and lens_up[b] source samples; a workgroup past its item's end returns.
 constexpr int VOC_NQ = 16;
+template <int RAG>
 __global__ __launch_bounds__(256) void voc_noise_conv_kernel(float* __restrict__ x, const float* __restrict__ har,
                                                              const float* __restrict__ wt, const float* __restrict__ bias,
-                                                             int C, int Tq, int Tsq, int sf, int ksz, long Tup, int Tsu) {
+                                                             int C, int Tq, int Tsq, int sf, int ksz, long Tup, int Tsu,
+                                                             const int* __restrict__ lens_q, const int* __restrict__ lens_up) {
     extern __shared__ float win[];                  // (frames per workgroup - 1) * sf + ksz source samples
     const int b = blockIdx.z;
     const int cpb = C < 256 ? C : 256;              // channels per workgroup
     const int groups = 256 / cpb;                   // frame groups per workgroup
     const int fpb = groups * VOC_NQ;                // frames per workgroup
     const int q0 = blockIdx.x * fpb;
+    if (RAG) {
+        Tq = lens_q[b];
+        Tup = lens_up[b];
+        if (q0 >= Tq) return;                       // whole workgroup: before the barrier
+    }
     const int o = blockIdx.y * cpb + threadIdx.x % cpb, grp = threadIdx.x / cpb;
     const int pad = ksz > 1 ? sf / 2 : 0;
     const int nwin = (fpb - 1) * sf + ksz;
@@ -135,17 +152,19 @@ __device__ __forceinline__ float voc_fast_rad(float s0, float ds0, int n, int up
     return s0 * fn + 0.5f * ds0 * fn * (float)(n - 1) / (float)upp;
 }
 
+template <int RAG>
 __global__ __launch_bounds__(256) void voc_fast_phase_kernel(const float* __restrict__ f0, int T, float sr, int upp,
-                                                             float* __restrict__ acc) {
+                                                             float* __restrict__ acc, const int* __restrict__ lens) {
     __shared__ float buf[2048];
     const int b = blockIdx.x;
+    const int Tb = RAG ? lens[b] : T;              // ds0 = 0 at the item's own last frame
     float run = 0.f;
-    for (int base = 0; base < T; base += 2048) {
-        const int n = min(2048, T - base);
+    for (int base = 0; base < Tb; base += 2048) {
+        const int n = min(2048, Tb - base);
         for (int i = threadIdx.x; i < n; i += 256) {
             const int t = base + i;
             const float s0 = f0[(long)b * T + t] / sr;
-            const float ds0 = t + 1 < T ? f0[(long)b * T + t + 1] / sr - s0 : 0.f;
+            const float ds0 = t + 1 < Tb ? f0[(long)b * T + t + 1] / sr - s0 : 0.f;
             buf[i] = fmodf(voc_fast_rad(s0, ds0, upp, upp) + 0.5f, 1.0f) - 0.5f;
         }
         __syncthreads();
@@ -160,58 +179,85 @@ __global__ __launch_bounds__(256) void voc_fast_phase_kernel(const float* __rest
     }
 }
 
+template <int RAG>
 __global__ void voc_fast_source_kernel(const float* __restrict__ f0, const float* __restrict__ acc, int T, int upp, float sr,
-                                       int Tsu, float* __restrict__ har) {
+                                       int Tsu, float* __restrict__ har, const int* __restrict__ lens) {
     const int b = blockIdx.y;
     const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= (long)T * upp) return;
+    const int Tb = RAG ? lens[b] : T;
+    if (s >= (long)Tb * upp) return;
     const int t = (int)(s / upp), n = (int)(s - (long)t * upp) + 1;
     const float s0 = f0[(long)b * T + t] / sr;
-    const float ds0 = t + 1 < T ? f0[(long)b * T + t + 1] / sr - s0 : 0.f;
+    const float ds0 = t + 1 < Tb ? f0[(long)b * T + t + 1] / sr - s0 : 0.f;
     float rad = voc_fast_rad(s0, ds0, n, upp);
     if (t > 0) rad += acc[(long)b * T + t - 1];
     har[(long)b * Tsu + s] = sinf(6.283185307179586f * rad);
 }
 
 hipError_t launch_voc_fast_source(const float* f0, int B, int T, int upp, float source_sr, float* acc_tmp, int Tsu, float* har,
-                                  hipStream_t st) {
-    hipLaunchKernelGGL(voc_fast_phase_kernel, dim3(B), dim3(256), 0, st, f0, T, source_sr, upp, acc_tmp);
+                                  hipStream_t st, const int* lens) {
     const long n = (long)T * upp;
-    hipLaunchKernelGGL(voc_fast_source_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, T, upp,
-                       source_sr, Tsu, har);
+    if (lens) {
+        hipLaunchKernelGGL(voc_fast_phase_kernel<1>, dim3(B), dim3(256), 0, st, f0, T, source_sr, upp, acc_tmp, lens);
+        hipLaunchKernelGGL(voc_fast_source_kernel<1>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, T,
+                           upp, source_sr, Tsu, har, lens);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(voc_fast_phase_kernel<0>, dim3(B), dim3(256), 0, st, f0, T, source_sr, upp, acc_tmp, nullptr);
+    hipLaunchKernelGGL(voc_fast_source_kernel<0>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, T, upp,
+                       source_sr, Tsu, har, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w,
                              const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp, float noise_std,
-                             float* acc_tmp, int Tsu, float* har, hipStream_t st) {
+                             float* acc_tmp, int Tsu, float* har, hipStream_t st, const int* lens) {
     if (dim > VOC_MAXDIM) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(voc_phase_kernel, dim3(B), dim3(256), 0, st, f0, T, sr, upp, acc_tmp);
     const long n = (long)T * upp;
-    hipLaunchKernelGGL(voc_source_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, rand_ini, noise,
-                       lin_w, lin_b, T, upp, dim, sr, sine_amp, noise_std, Tsu, har);
+    if (lens) {
+        hipLaunchKernelGGL(voc_phase_kernel<1>, dim3(B), dim3(256), 0, st, f0, T, sr, upp, acc_tmp, lens);
+        hipLaunchKernelGGL(voc_source_kernel<1>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, rand_ini,
+                           noise, lin_w, lin_b, T, upp, dim, sr, sine_amp, noise_std, Tsu, har, lens);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(voc_phase_kernel<0>, dim3(B), dim3(256), 0, st, f0, T, sr, upp, acc_tmp, nullptr);
+    hipLaunchKernelGGL(voc_source_kernel<0>, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, f0, acc_tmp, rand_ini, noise,
+                       lin_w, lin_b, T, upp, dim, sr, sine_amp, noise_std, Tsu, har, nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, const float* bias, int B, int C, int Tq,
-                                 int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st) {
+                                 int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st, const int* lens_q,
+                                 const int* lens_up) {
     const int cpb = C < 256 ? C : 256, fpb = (256 / cpb) * VOC_NQ;
     const int nwin = (fpb - 1) * sf + ksz;
-    hipLaunchKernelGGL(voc_noise_conv_kernel, dim3((Tq + fpb - 1) / fpb, (C + cpb - 1) / cpb, B), dim3(256),
-                       nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf, ksz, Tup, Tsu);
+    const dim3 grid((Tq + fpb - 1) / fpb, (C + cpb - 1) / cpb, B);
+    if (lens_q)
+        hipLaunchKernelGGL(voc_noise_conv_kernel<1>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
+                           ksz, Tup, Tsu, lens_q, lens_up);
+    else
+        hipLaunchKernelGGL(voc_noise_conv_kernel<0>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
+                           ksz, Tup, Tsu, nullptr, nullptr);
     return hipGetLastError();
 }
 
 // x[row][t] += sigma * noise[row][t]  (models.py:272-273; x rows are padded to Ts, the caller's noise is dense)
-__global__ void voc_add_noise_kernel(float* __restrict__ x, const float* __restrict__ noise, int T, int Ts, float sigma) {
+// RAG = 1: item b (blockIdx.z) only over its lens[b] frames
+template <int RAG>
+__global__ void voc_add_noise_kernel(float* __restrict__ x, const float* __restrict__ noise, int T, int Ts, float sigma,
+                                     const int* __restrict__ lens) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= T) return;
+    if (t >= (RAG ? lens[blockIdx.z] : T)) return;
     const long row = (long)blockIdx.z * gridDim.y + blockIdx.y;
     x[row * Ts + t] += sigma * noise[row * T + t];
 }
 
-hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int T, int Ts, float sigma, hipStream_t st) {
-    hipLaunchKernelGGL(voc_add_noise_kernel, dim3((T + 255) / 256, C, B), dim3(256), 0, st, x, noise, T, Ts, sigma);
+hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int T, int Ts, float sigma, hipStream_t st,
+                                const int* lens) {
+    if (lens)
+        hipLaunchKernelGGL(voc_add_noise_kernel<1>, dim3((T + 255) / 256, C, B), dim3(256), 0, st, x, noise, T, Ts, sigma, lens);
+    else
+        hipLaunchKernelGGL(voc_add_noise_kernel<0>, dim3((T + 255) / 256, C, B), dim3(256), 0, st, x, noise, T, Ts, sigma, nullptr);
     return hipGetLastError();
 }
 

@@ -369,6 +369,26 @@ class AcousticHarness:
                          infer=True, noise=noise, lengths=lens, **kwargs).diff_out
         return [out[i:i + 1, :lens[i]] for i in range(n)]
 
+    @torch.no_grad()
+    def run_vocoder_batch(self, mels, f0s, draws):
+        """The vocoder over several segments in one ragged call (dsd_vocode_ragged): mels [1, T_i, M], f0s [1, T_i] and each
+        segment's (rand_ini, noise, pre_noise) as `Generator.draw` makes them -> list of [T_i * upp] waveforms, each the one
+        the segment gives alone with those draws."""
+        gen = self.vocoder.model
+        lens = [int(m.size(1)) for m in mels]
+        t_max, upp = max(lens), gen.upp
+        pad = lambda v, n: torch.nn.functional.pad(v, [0, n - v.size(-1)])      # noqa: E731  (along the last dim)
+        mel = torch.cat([torch.nn.functional.pad(m, [0, 0, 0, t_max - m.size(1)]) for m in mels])
+        f0 = torch.cat([pad(f.to(mel.device), t_max) for f in f0s])
+        kwargs = {}
+        if draws[0][0] is not None:
+            kwargs['rand_ini'] = torch.stack([d[0] for d in draws])
+            kwargs['noise'] = torch.cat([torch.nn.functional.pad(d[1], [0, 0, 0, t_max * upp - d[1].size(1)]) for d in draws])
+        if draws[0][2] is not None:
+            kwargs['pre_noise'] = torch.cat([pad(d[2], t_max) for d in draws])
+        wav = self.vocoder.spec2wav_torch(mel, f0=f0, lengths=lens, **kwargs).view(len(mels), -1)
+        return [wav[i, :n * upp] for i, n in enumerate(lens)]
+
     def _batchable(self):
         """A ragged batch reproduces the one-by-one results when x_T is the sampler's only random draw."""
         d = getattr(self.model, 'diffusion', None)
@@ -384,7 +404,9 @@ class AcousticHarness:
         `out_path` is given, writes it.  Each segment is placed at its `offset`; where it overlaps what is already
         there the two are cross-faded.  `batch_size` > 1 runs that many segments per launch of the acoustic model as
         a ragged batch (same mels as one by one - the reference's order of operations, `ds_acoustic.py:214-271`,
-        `batch_size` = 1, is the default); the vocoder still takes them one at a time.
+        `batch_size` = 1, is the default), and the vocoder then takes each such group in one ragged call, with every
+        segment's random draws made in the generator state a one-by-one run makes them in (same track up to the
+        vocoder's fp32 rounding).
         With `out_dir` and `title` the reference's own calling convention applies: `num_runs` passes, written to
         `out_dir/title[-NNN].wav` (or `.mel.pt` with `save_mel`); the last pass is returned."""
         if out_dir is not None:
@@ -397,20 +419,30 @@ class AcousticHarness:
                                             batch_size=batch_size)
             return result
         batches = [self.preprocess_input(param, idx=i) for i, param in enumerate(params)]
-        ready = {}
+        ready, wavs = {}, {}
         if batch_size > 1 and self._batchable():
             noises = [self._draw_noise(p, seed, int(b['mel2ph'].size(1))) for p, b in zip(params, batches)]
             order = sorted(range(len(params)), key=lambda i: -int(batches[i]['mel2ph'].size(1)))     # similar lengths together
-            for k in range(0, len(order), batch_size):
-                group = order[k:k + batch_size]
+            groups = [order[k:k + batch_size] for k in range(0, len(order), batch_size)]
+            for group in groups:
                 mels_g = self.forward_model_batch([batches[i] for i in group], [noises[i] for i in group])
                 ready.update(zip(group, mels_g))
+            if not save_mel:
+                # the vocoder's draws of every segment in the generator state a lone run of it makes them in: after its
+                # seed and its x_T draw; then each group in one ragged call
+                draws = []
+                for param, batch in zip(params, batches):
+                    t_len = int(batch['mel2ph'].size(1))
+                    self._draw_noise(param, seed, t_len)
+                    draws.append(self.vocoder.model.draw(t_len, self.device))
+                for group in groups:
+                    wav_g = self.run_vocoder_batch([ready[i] for i in group], [batches[i]['f0'] for i in group],
+                                                   [draws[i] for i in group])
+                    wavs.update(zip(group, wav_g))
         mels, track, cursor = [], np.zeros(0), 0
         for i, (param, batch) in enumerate(zip(params, batches)):
             if i in ready:
                 mel = ready[i]
-                if not save_mel:        # leave the generator where a lone run of this segment leaves it for the vocoder's draws
-                    self._draw_noise(param, seed, int(batch['mel2ph'].size(1)))
             else:
                 if 'seed' in param:
                     self._seed(param['seed'])
@@ -420,7 +452,7 @@ class AcousticHarness:
             if save_mel:
                 mels.append({'offset': param.get('offset', 0.), 'mel': mel.cpu(), 'f0': batch['f0'].cpu()})
                 continue
-            wav = self.run_vocoder(mel, f0=batch['f0'])[0].cpu().numpy()
+            wav = (wavs[i] if i in wavs else self.run_vocoder(mel, f0=batch['f0'])[0]).cpu().numpy()
             gap = round(param.get('offset', 0) * hparams['audio_sample_rate']) - cursor
             if gap >= 0:
                 track = np.concatenate((track, np.zeros(gap), wav))

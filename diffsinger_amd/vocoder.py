@@ -7,6 +7,8 @@ still carries `weight_g` / `weight_v` pairs is folded on load (`w = g * v / ||v|
 torch.nn.utils.weight_norm's default).  `forward(x, f0)` = models.py:262-290 with SineGen's two random draws
 (`torch.rand` initial phases, `torch.randn_like` noise) made on the caller's device, or passed in for
 reproducibility; `mini_nsf: true` generators (fastsinegen source, `source_conv`) have no random draws.
+`forward(x, f0, lengths=[...])` vocodes a zero-padded batch of segments in one ragged call (dsd_vocode_ragged): item b
+comes out as the segment alone at T = lengths[b] would, draws included.
 Inference only; no CPU path.
 """
 from __future__ import annotations
@@ -119,12 +121,20 @@ class Generator(_NativeBackbone):
     def prepare_cond(self, cond, layout="BHT"):
         raise RuntimeError("the vocoder has no conditioner; call forward(mel, f0)")
 
-    def forward(self, x, f0, *, rand_ini=None, noise=None, pre_noise=None):
-        """x: [B, num_mels, T] natural-log mel, f0: [B, T] -> [B, 1, T * prod(upsample_rates)]."""
+    def forward(self, x, f0, *, lengths=None, rand_ini=None, noise=None, pre_noise=None):
+        """x: [B, num_mels, T] natural-log mel, f0: [B, T] -> [B, 1, T * prod(upsample_rates)].
+
+        `lengths` (B ints in [1, T]): a ragged batch - item b holds `lengths[b]` valid frames and comes out as it would
+        alone at that length; the output past `lengths[b] * prod(upsample_rates)` is zero.  The draws are then per item:
+        `rand_ini` [B, harmonic_num + 1], `noise` [B, T * upp, harmonic_num + 1] (item b's first lengths[b] * upp rows),
+        `pre_noise` [B, C0, T] (item b's first lengths[b] frames); those not passed are drawn item by item in the order
+        and shapes B lone calls would draw them, so the generator state afterwards is the one those calls leave."""
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("diffsinger_amd.vocoder.Generator is inference-only: call it under torch.no_grad()")
         if x.dim() != 3 or x.shape[1] != self.num_mels or tuple(f0.shape) != (x.shape[0], x.shape[2]):
             raise ValueError(f"x [B, {self.num_mels}, T] and f0 [B, T] expected; got {tuple(x.shape)}, {tuple(f0.shape)}")
+        if lengths is not None:
+            return self._forward_ragged(x, f0, lengths, rand_ini, noise, pre_noise)
         dev = x.device
         handle = self.native_handle(dev)
         b, _, t = x.shape
@@ -173,6 +183,73 @@ class Generator(_NativeBackbone):
         return out
 
 
+    def draw(self, t_len, device):
+        """The random draws of a lone `forward` over `t_len` frames, made as it makes them (same calls, same order):
+        -> (rand_ini [dim] or None, noise [1, t_len * upp, dim] or None, pre_noise [1, C0, t_len] or None)."""
+        dim = self.harmonic_num + 1
+        rand_ini = None if self.mini_nsf else torch.rand(dim, device=device)
+        noise = None if self.mini_nsf else torch.randn((1, t_len * self.upp, dim), device=device)
+        pre = None
+        if self.noise_sigma is not None and self.noise_sigma > 0:
+            pre = torch.randn((1, self.upsample_initial_channel, t_len), device=device)
+        return rand_ini, noise, pre
+
+    def _forward_ragged(self, x, f0, lengths, rand_ini, noise, pre_noise):
+        lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        b, _, t = x.shape
+        if len(lens) != b or any(v < 1 or v > t for v in lens):
+            raise ValueError(f"lengths: {b} values in [1, {t}] expected; got {lens}")
+        dev = x.device
+        handle = self.native_handle(dev)
+        x = x.detach().to(torch.float32)
+        sb, sm, st_ = x.stride()
+        if st_ != 1 and sm != 1:
+            x = x.contiguous()
+            sb, sm, st_ = x.stride()
+        f0 = f0.detach().to(device=dev, dtype=torch.float32).contiguous()
+        dim, upp, c0 = self.harmonic_num + 1, self.upp, self.upsample_initial_channel
+        want_pre = self.noise_sigma is not None and self.noise_sigma > 0
+        draw_ini = not self.mini_nsf and rand_ini is None
+        draw_noise = not self.mini_nsf and noise is None
+        draw_pre = want_pre and pre_noise is None
+        if draw_ini:
+            rand_ini = torch.empty((b, dim), device=dev)
+        if draw_noise:
+            noise = torch.zeros((b, t * upp, dim), device=dev)
+        if draw_pre:
+            pre_noise = torch.zeros((b, c0, t), device=dev)
+        for i, n in enumerate(lens):        # per item, in item order: what a lone call at T = lengths[i] draws (see forward)
+            if draw_ini:
+                rand_ini[i] = torch.rand(dim, device=dev)
+            if draw_noise:
+                noise[i, :n * upp] = torch.randn((1, n * upp, dim), device=dev)[0]
+            if draw_pre:
+                pre_noise[i, :, :n] = torch.randn((1, c0, n), device=dev)[0]
+        pre_ptr = None
+        if want_pre:
+            pre_noise = pre_noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(pre_noise.shape) != (b, c0, t):
+                raise ValueError(f"pre_noise [{b}, {c0}, {t}] expected")
+            pre_ptr = C.c_void_p(pre_noise.data_ptr())
+        ini_ptr = noise_ptr = None
+        if not self.mini_nsf:
+            rand_ini = rand_ini.detach().to(device=dev, dtype=torch.float32).contiguous()
+            noise = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(rand_ini.shape) != (b, dim) or tuple(noise.shape) != (b, t * upp, dim):
+                raise ValueError(f"rand_ini [{b}, {dim}] and noise [{b}, {t * upp}, {dim}] expected")
+            ini_ptr, noise_ptr = C.c_void_p(rand_ini.data_ptr()), C.c_void_p(noise.data_ptr())
+        out = torch.empty((b, 1, t * upp), device=dev, dtype=torch.float32)
+        lens_c = (C.c_int32 * b)(*lens)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(handle, _lib.lib().dsd_vocode_ragged(handle, C.c_void_p(x.data_ptr()), b, t, sb, sm, st_, lens_c,
+                                                        C.c_void_p(f0.data_ptr()), ini_ptr, noise_ptr, pre_ptr,
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(stream)), "dsd_vocode_ragged")
+        for i, n in enumerate(lens):        # the library leaves the samples past an item's end unspecified
+            if n < t:
+                out[i, :, n * upp:] = 0
+        return out
+
+
 class NsfHifiGAN:
     """The `spec2wav_torch` half of modules/vocoders/nsf_hifigan.py:16-70 around a `Generator` (the checkpoint /
     config loading of `load_model`, models.py:18-33, is the caller's: pass the built generator and its config)."""
@@ -189,5 +266,5 @@ class NsfHifiGAN:
             f0 = kwargs.get('f0')
             if f0 is None:
                 raise ValueError("the NSF generator needs f0 (models.py:262)")
-            extra = {k: kwargs[k] for k in ("rand_ini", "noise", "pre_noise") if kwargs.get(k) is not None}
+            extra = {k: kwargs[k] for k in ("lengths", "rand_ini", "noise", "pre_noise") if kwargs.get(k) is not None}
             return self.model(c, f0, **extra).view(-1)

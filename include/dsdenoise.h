@@ -330,6 +330,20 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out);
 int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
                int64_t stride_t, const float* f0, const float* rand_ini, const float* noise, const float* pre_noise,
                float* wav_out, void* stream);
+/*
+ * Ragged vocoder batch: dsd_vocode over B segments zero-padded to T frames, where item b holds lengths[b] valid frames and
+ * comes out as if it had been vocoded alone at T = lengths[b] with its own draws (the frames past an item's end - at every
+ * rate, lengths[b] * prod(upsample_rates[:i]) after i upsamplings - are the zero padding of every convolution and of the
+ * source, and the tiles that hold only such frames are not computed).  lengths: HOST array of B values, 1 <= lengths[b] <= T.
+ *   rand_ini  [B][harmonic_num + 1]: one row per item (a lone call draws its own)
+ *   noise     [B, T * prod(upsample_rates), harmonic_num + 1]: item b's first lengths[b] * prod(upsample_rates) rows are used
+ *   pre_noise [B, upsample_initial_channel, T]: item b's [:, :lengths[b]] is used
+ * The null / mini_nsf / noise_sigma rules are dsd_vocode's; samples of wav_out at or past lengths[b] * prod(upsample_rates)
+ * are unspecified.  dsd_set_lengths does not apply to vocoder handles: this call takes the lengths explicitly.
+ */
+int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
+                      int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
+                      const float* pre_noise, float* wav_out, void* stream);
 
 /*
  * Ragged batches.  The reference runs one utterance per call (inference/ds_acoustic.py:214-271), because padding a batch

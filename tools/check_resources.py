@@ -5,7 +5,8 @@ register, scratch and occupancy figures of every instantiation (no GPU needed: h
 Why a check: these kernels keep whole operand sets in registers through fully unrolled loops; one loop that the compiler
 does not unroll turns a register array into scratch memory and a 63 us kernel into a 280 us one without any wrong result
 (it happened once: a barrier inside an unrolled K walk).  `python tools/check_resources.py` exits non-zero if any kernel
-of these files uses scratch or spills; tests/test_kernel_resources.py runs it."""
+of these files uses scratch or spills; tests/test_kernel_resources.py runs it.  `python tools/check_resources.py gemm.hip ...`
+checks the named files of diffsinger_amd/csrc instead."""
 import os
 import re
 import subprocess
@@ -43,7 +44,7 @@ def analyse(path):
 
 def main():
     bad = []
-    for f in FILES:
+    for f in sys.argv[1:] or FILES:
         for k in analyse(os.path.join(CSRC, f)):
             name = subprocess.run(["c++filt", k["name"]], capture_output=True, text=True).stdout.strip() or k["name"]
             scratch, spill = int(k.get("ScratchSize", 0)), int(k.get("VGPRs Spill", 0)) + int(k.get("SGPRs Spill", 0))
