@@ -32,40 +32,39 @@
 using namespace dsd;
 
 // ------------------------------------------------------------------------------------------
-// path switches: read from the environment once per C-ABI entry point (dsd_internal.h, PathOpts)
+// path switches: every C-ABI entry point that launches kernels takes a snapshot into its handle (dsd_internal.h, PathOpts)
 // ------------------------------------------------------------------------------------------
-namespace dsd {
-static PathOpts g_path_opts = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 512};
-const PathOpts& path_opts() { return g_path_opts; }
-void refresh_path_opts() {
-    auto geti = [](const char* name, int dflt) {
+namespace {
+PathOpts read_path_opts() {
+    auto geti = [](const char* name) {
         const char* v = getenv(name);
-        return v && *v ? atoi(v) : dflt;
+        return v && *v ? atoi(v) : -1;
     };
-    PathOpts& o = g_path_opts;
-    o.fused_layer = geti("DSD_FUSED_LAYER", -1);
-    o.wn_plan = geti("DSD_WN_PLAN", -1);
-    o.rowsplit = geti("DSD_ROWSPLIT", -1);
-    o.rs_bn48 = geti("DSD_RS_BN48", -1);
-    o.rs_conv_q = geti("DSD_RS_CONV_Q", -1);
-    o.rs_rows = geti("DSD_RS_ROWS", -1);
-    o.rs_rows_out = geti("DSD_RS_ROWS_OUT", -1);
-    o.edge = geti("DSD_EDGE", -1);
-    o.lynx_resident = geti("DSD_LYNX_RESIDENT", -1);
-    o.lynx_pw1p = geti("DSD_LYNX_PW1P", -1);
-    o.lynx_pw2d = geti("DSD_LYNX_PW2D", -1);
-    o.lynx_pw2q = geti("DSD_LYNX_PW2Q", -1);
-    o.narrow = geti("DSD_NARROW", -1);
-    o.gm_shift = geti("DSD_GM_SHIFT", -1);
-    o.film_t = geti("DSD_FILM_T", -1);
-    o.dwconv_rows = geti("DSD_DWCONV_ROWS", -1);
-    o.precision = geti("DSD_PRECISION", -1);
-    o.fused16 = geti("DSD_FUSED16", -1);
-    o.x3_wide = geti("DSD_X3_WIDE", -1);
+    PathOpts o;
+    o.fused_layer = geti("DSD_FUSED_LAYER");
+    o.wn_plan = geti("DSD_WN_PLAN");
+    o.rowsplit = geti("DSD_ROWSPLIT");
+    o.rs_bn48 = geti("DSD_RS_BN48");
+    o.rs_conv_q = geti("DSD_RS_CONV_Q");
+    o.rs_rows = geti("DSD_RS_ROWS");
+    o.rs_rows_out = geti("DSD_RS_ROWS_OUT");
+    o.edge = geti("DSD_EDGE");
+    o.lynx_resident = geti("DSD_LYNX_RESIDENT");
+    o.lynx_pw1p = geti("DSD_LYNX_PW1P");
+    o.lynx_pw2d = geti("DSD_LYNX_PW2D");
+    o.lynx_pw2q = geti("DSD_LYNX_PW2Q");
+    o.narrow = geti("DSD_NARROW");
+    o.gm_shift = geti("DSD_GM_SHIFT");
+    o.film_t = geti("DSD_FILM_T");
+    o.dwconv_rows = geti("DSD_DWCONV_ROWS");
+    o.precision = geti("DSD_PRECISION");
+    o.fused16 = geti("DSD_FUSED16");
+    o.x3_wide = geti("DSD_X3_WIDE");
     const char* nb = getenv("DSD_NB2_MIN_WG");
-    o.nb2_min = nb && *nb ? atol(nb) : 512;
+    if (nb && *nb) o.nb2_min = atol(nb);
+    return o;
 }
-}  // namespace dsd
+}  // namespace
 
 namespace dsd {
 TimingSlot& timing_slot() {
@@ -130,6 +129,7 @@ struct dsd_handle {
     // wn_edge.hip: the state buffer whose input projection the previous evaluation's edge kernel already wrote into xh
     const float* edge_xh_src = nullptr;
     bool finalized = false;
+    PathOpts opts;                  // path switches: the snapshot of the last entry point that launches kernels (read_path_opts)
 
     // packed weights
     std::vector<float> blob_host;
@@ -1274,7 +1274,7 @@ struct GemmCall {
 };
 
 // vr: a ragged vocoder batch at this GEMM's rate (dsd_vocode_ragged): its lengths and valid tiles instead of dsd_set_lengths'
-GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b_bstride, int b_rstride, int batch,
+GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b_bstride, int b_rstride, int batch,
                    int T, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false,
                    const VocRagStage* vr = nullptr) {
     GemmCall c;
@@ -1307,7 +1307,7 @@ GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b
     const int mtiles = g.pairC > 0 ? (g.pairC + 31) / 32 : (g.M + 63) / 64;
     // (a ragged vocoder batch: counted over its valid tiles, the shape B lone calls of similar length would take)
     const long wg64 = (vr ? (long)vr->ncg[2] : (long)batch * ((T + 63) / 64)) * mtiles;
-    const long nb2_min = path_opts().nb2_min;          // (DSD_NB2_MIN_WG: diagnostic override)
+    const long nb2_min = h->opts.nb2_min;          // (DSD_NB2_MIN_WG: diagnostic override)
     c.nb = wg64 >= nb2_min ? 2 : 1;
     // a conv on the generic path keeps all input channels resident: 64-frame tiles only while that fits in LDS
     if ((g.taps > 3 || (generic_only && g.taps > 1)) &&
@@ -1315,7 +1315,7 @@ GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b
     // narrow tiles (64 rows x 16 frames, c.nb == 0): when 32-frame tiles would put at most ~1.5 workgroups on a CU,
     // twice as many half-size workgroups share each SIMD between two waves and halve the latency of a lone one
     if (c.nb == 1) {
-        const int force = path_opts().narrow;          // (DSD_NARROW: diagnostic override)
+        const int force = h->opts.narrow;          // (DSD_NARROW: diagnostic override)
         const long wg32 = (long)batch * ((T + 31) / 32) * mtiles;
         int s16 = 16 + 2 * p.HL;
         while (s16 % 32 != 16) s16 += 4;
@@ -1349,7 +1349,7 @@ GemmCall make_gemm(dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b
     p.lpr_shift = 3;
     while ((1 << p.lpr_shift) < w4) ++p.lpr_shift;
     {   // L2 blocking of the work order for GEMMs with many row tiles (GemmP::gm_shift): groups of 8 row tiles
-        const int gm_env = path_opts().gm_shift;       // (DSD_GM_SHIFT: diagnostic override)
+        const int gm_env = h->opts.gm_shift;       // (DSD_GM_SHIFT: diagnostic override)
         const int shift = gm_env >= 0 ? gm_env : 3;
         const long nft = ragged ? (long)p.ncg : (long)batch * p.tiles_per_b;
         if (shift > 0 && mtiles >= (2 << shift) && mtiles % (1 << shift) == 0 && nft * mtiles >= 2048 && (nft << shift) < (1L << 22)) {
@@ -1383,6 +1383,11 @@ int run_gemm(dsd_handle* h, const GemmCall& c, hipStream_t st) {
     return DSD_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// denoiser launch plan: every launch choice of one backbone evaluation, made once per dsd_denoise / dsd_sample call
+// (plan_denoise) from the handle's config, (B, T, Ts), lengths, CU count, precision and path switches; run_backbone executes
+// it and dsd_get_stats reports it
+// ------------------------------------------------------------------------------------------
 // WaveNet: how one residual layer runs on this (B, T) / these lengths.  Three launch shapes exist:
 //   * wn_layer.hip, ONE launch per layer, a workgroup per 32-frame tile with all 2C rows: a launch is ceil(tiles / 256) rounds
 //     of one tile per CU and a round takes the same time whether 1 or 256 of its tiles exist (at C = 256 ~67 us, 63 us of it
@@ -1398,25 +1403,42 @@ int run_gemm(dsd_handle* h, const GemmCall& c, hipStream_t st) {
 // Mixed plans: the whole rounds on the fused kernel, the remainder on the row-split pair (B = 9: 67 + 14 us instead of
 // 2 x 67 fused or ~92 split).  Costs below are in units of one fused round; they are RATIOS measured on one box
 // (profiles/r03_plan_sweep.txt), not absolute times.  DSD_FUSED_LAYER=0/1 forces no / only fused segments, DSD_WN_PLAN=0
-// keeps one launch shape per layer (round 2's rule).  An empty plan = the per-layer choice between the row-split pair
-// and the GEMM pair in run_backbone.
+// keeps one launch shape per layer: no mixed plans and no wide row tiles (whole-layer 16-frame fused tiles stay allowed).
+// No segments = the per-layer choice between the row-split pair and the GEMM pair (DenoisePlan::layer).
 enum { WN_FUSED = 0, WN_ROWSPLIT = 1, WN_FUSED_X3 = 2 };
 struct WnSeg {
     int kind, bn;       // launch shape, frames per tile
     int t0, nt;         // tiles [t0, t0 + nt) of the (item, frame tile) order at this width (ragged: of the valid-tile list)
     int rows;           // WN_ROWSPLIT: rows per workgroup - 64 (wn_rowsplit.hip), 128 or 256 (wn_rows.hip)
+    int rows_out;       // ... of the out-proj launch alone (DSD_RS_ROWS_OUT)
+};
+// LYNXNet's pointwise GEMMs: gemm.hip, lynx_layer.hip with the whole K extent resident (pw2: 512 rows per workgroup; LX_PW2Q:
+// 128 rows), lynx_x3.hip (split-bf16)
+enum { LX_GEMM = 0, LX_RESIDENT = 1, LX_X3 = 2, LX_PW2Q = 3 };
+struct DenoisePlan {
+    // WaveNet
+    std::vector<WnSeg> segs;    // the segments of every residual layer (empty: `layer`)
+    struct {
+        int rs_bn = 0;          // > 0: the row-split pair on tiles of this many frames (32 / 48); 0: the two GEMMs
+        bool rs_pair = false;   // the row-split pair was an option (the conv GEMM's tile width depends on it: make_gemm)
+    } layer[8];                 // ... by position in the dilation cycle (dilation_cycle_length <= 8)
+    bool edge = false;          // the edge kernel (wn_edge.hip) - unless the sampler program does not fit it (run_wavenet)
+    // LYNXNet
+    int pw1 = LX_GEMM, pw2 = LX_GEMM;
+    bool ln_merge = true;       // a separate LayerNorm-merge launch in front of pw1
+    int x3_ncb1 = 2, x3_ncb2 = 2;   // LX_X3 tiles in 16-frame blocks: 2 = 32 frames, 4 = 64 frames
+    bool bf16x3() const {
+        for (const WnSeg& sg : segs)
+            if (sg.kind == WN_FUSED_X3) return true;
+        return pw1 == LX_X3;
+    }
 };
 
-inline long wn_tiles32(const dsd_handle* h) {
-    if (h->lens_host.empty()) return (long)h->B * ((h->T + 31) / 32);
+// valid frame tiles of `bn` frames in the batch (ragged: tiles that hold valid frames, = the length of the valid-tile list)
+inline long tiles_at(const dsd_handle* h, int bn) {
+    if (h->lens_host.empty()) return (long)h->B * ((h->T + bn - 1) / bn);
     long tiles = 0;
-    for (int v : h->lens_host) tiles += (v + 31) / 32;
-    return tiles;
-}
-inline long wn_tiles16(const dsd_handle* h) {
-    if (h->lens_host.empty()) return (long)h->B * ((h->T + 15) / 16);
-    long tiles = 0;
-    for (int v : h->lens_host) tiles += (v + 15) / 16;
+    for (int v : h->lens_host) tiles += (v + bn - 1) / bn;
     return tiles;
 }
 
@@ -1435,9 +1457,8 @@ inline double wn_split_cost(long tiles, int rows, bool segment) {
     // (above ~110 tiles: the GEMM pair's 64-frame tiles fill the chip two utterances of ~1000 frames at a time)
     return tiles <= 110 ? 0.067 + (double)tiles / 223.0 : 0.04 + 0.30 * (double)((tiles + 63) / 64);
 }
-// ... and the rows per workgroup that minimise it.  DSD_RS_ROWS forces.
-inline int wn_rows_for(long tiles, bool segment) {
-    const int force = path_opts().rs_rows;
+// ... and the rows per workgroup that minimise it.  DSD_RS_ROWS (`force`) forces.
+inline int wn_rows_for(long tiles, bool segment, int force) {
     if (force == 64 || force == 128 || force == 256) return force;
     int best = 64;
     for (int rows : {128, 256})
@@ -1445,14 +1466,13 @@ inline int wn_rows_for(long tiles, bool segment) {
     return best;
 }
 
-bool wn_plan_for(const dsd_handle* h, std::vector<WnSeg>& segs) {
-    segs.clear();
-    if (!is_wavenet(h)) return false;
+// WaveNet's segments (plan_denoise); false: none, the per-layer choice
+bool wn_segments(const dsd_handle* h, std::vector<WnSeg>& segs) {
     const int C = C_of(h);
     const int max_dil = 1 << (std::min(h->cfg.dilation_cycle_length, L_of(h)) - 1);
     if (h->cfg.dilation_cycle_length < 1 || !wn_layer_supported(C, max_dil)) return false;
-    const PathOpts& o = path_opts();
-    const long tiles = wn_tiles32(h);
+    const PathOpts& o = h->opts;
+    const long tiles = tiles_at(h, 32);
     if (tiles == 0 || tiles >= (1L << 22)) return false;
     const bool rs_ok = o.rowsplit != 0 && wn_rowsplit_supported(C, max_dil, h->Ts) && wn_rows_supported(C, max_dil, h->Ts);
     // split-bf16 mode: the fused segments run wn_layer_x3.hip, whose round takes ~0.55 of an fp32 round (bound by the weight
@@ -1466,66 +1486,12 @@ bool wn_plan_for(const dsd_handle* h, std::vector<WnSeg>& segs) {
     }
     // the fused kernel on 16-frame tiles (wn_layer16_kernel): a round of one tile per CU takes kRound16 of a 32-frame round (half the
     // MFMAs against the same 2 MB of weights per workgroup: profiles/r03_plan_sweep.txt); fp32 only, whole layers only
-    const long tiles16 = wn_tiles16(h);
+    const long tiles16 = tiles_at(h, 16);
     const bool f16_ok = !x3 && wn_layer16_supported(C, max_dil) && tiles16 < (1L << 22);
     if (o.fused16 == 1 && f16_ok) {                // forced
         segs.push_back({WN_FUSED, 16, 0, (int)tiles16, 0});
         return true;
     }
-    if (o.wn_plan == 2 && rs_ok && o.fused_layer != 0) {
-        // test hook: a mixed plan at any size - the first half of the tiles fused, the rest on the two-launch path
-        const int nfh = (int)(tiles / 2);
-        if (nfh > 0) segs.push_back({fused_kind, 32, 0, nfh, 0});
-        segs.push_back({WN_ROWSPLIT, 32, nfh, (int)tiles - nfh, wn_rows_for(tiles - nfh, true)});
-        return true;
-    }
-    if ((o.wn_plan == 3 || o.wn_plan == 4) && f16_ok && rs_ok && o.fused_layer != 0) {
-        // test hooks: plans with a 16-frame fused segment at any size - 3: the first half of the 32-frame tiles on 16-frame fused
-        // tiles, the rest on the two-launch path; 4: the first half on the 32-frame fused kernel, the rest on 16-frame tiles
-        const long nfh = tiles / 2;
-        auto m16 = [h](long n) -> long {
-            if (h->lens_host.empty()) {
-                const long tpb32 = (h->T + 31) / 32, tpb16 = (h->T + 15) / 16;
-                return (n / tpb32) * tpb16 + 2 * (n % tpb32);
-            }
-            long n32 = 0, n16 = 0;
-            for (int v : h->lens_host) {
-                const long t32 = (v + 31) / 32, t16 = (v + 15) / 16;
-                if (n < n32 + t32) return n16 + 2 * (n - n32);
-                n32 += t32; n16 += t16;
-            }
-            return n16;
-        };
-        if (o.wn_plan == 3) {
-            if (nfh > 0) segs.push_back({WN_FUSED, 16, 0, (int)m16(nfh), 0});
-            segs.push_back({WN_ROWSPLIT, 32, (int)nfh, (int)(tiles - nfh), wn_rows_for(tiles - nfh, true)});
-        } else {
-            if (nfh > 0) segs.push_back({WN_FUSED, 32, 0, (int)nfh, 0});
-            segs.push_back({WN_FUSED, 16, (int)m16(nfh), (int)(tiles16 - m16(nfh)), 0});
-        }
-        return true;
-    }
-    const bool rows_forced = rs_ok && (o.rs_rows == 128 || o.rs_rows == 256);
-    if (rows_forced && o.fused_layer == 0) {       // forced: the whole layer on wide row tiles
-        segs.push_back({WN_ROWSPLIT, 32, 0, (int)tiles, o.rs_rows});
-        return true;
-    }
-    if (o.fused_layer == 0) return false;
-    const bool plans = rs_ok && o.wn_plan != 0;     // DSD_WN_PLAN=0: one launch shape per layer, no wide row tiles (round 2's rule)
-    // one fused round = one tile per CU; the two-launch costs were measured on 256 CUs, so their tile counts are taken in
-    // 256ths of the chip (`eq`): a part with fewer CUs sees proportionally "more" tiles
-    const long cus = h->cus;
-    const long rounds = (tiles + cus - 1) / cus, nf = tiles / cus * cus, rem = tiles - nf;
-    auto eq = [cus](long t) { return (t * 256 + cus - 1) / cus; };
-    const double fused_all = 2 * tiles >= cus ? round_cost * (double)rounds : 1e30;
-    const int rows_all = plans ? wn_rows_for(eq(tiles), false) : 64;
-    const double split_all = wn_split_cost(eq(tiles), rows_all, false);
-    double mixed = 1e30;
-    if (plans && nf > 0 && rem > 0) mixed = round_cost * (double)(nf / cus) + wn_split_cost(eq(rem), wn_rows_for(eq(rem), true), true);
-    // ... and the 16-frame fused kernel as a whole layer, as the FIRST segment of a layer of up to ~1.5 rounds (one full round of
-    // 16-frame tiles, the rest on the two-launch path: B = 5 at T = 1000), or as the remainder behind whole 32-frame rounds
-    constexpr double kRound16 = 0.53;               // a round of 16-frame tiles / a round of 32-frame tiles (35.3 / 67.1 ms per loop)
-    const bool use16 = f16_ok && o.fused16 != 0;
     // index in the 16-frame tile order of the first 16-frame tile of 32-frame tile n (of the dense order / the valid-tile list)
     auto map16 = [h](long n) -> long {
         if (h->lens_host.empty()) {
@@ -1540,6 +1506,48 @@ bool wn_plan_for(const dsd_handle* h, std::vector<WnSeg>& segs) {
         }
         return n16;
     };
+    if (o.wn_plan == 2 && rs_ok && o.fused_layer != 0) {
+        // test hook: a mixed plan at any size - the first half of the tiles fused, the rest on the two-launch path
+        const int nfh = (int)(tiles / 2);
+        if (nfh > 0) segs.push_back({fused_kind, 32, 0, nfh, 0});
+        segs.push_back({WN_ROWSPLIT, 32, nfh, (int)tiles - nfh, wn_rows_for(tiles - nfh, true, o.rs_rows)});
+        return true;
+    }
+    if ((o.wn_plan == 3 || o.wn_plan == 4) && f16_ok && rs_ok && o.fused_layer != 0) {
+        // test hooks: plans with a 16-frame fused segment at any size - 3: the first half of the 32-frame tiles on 16-frame fused
+        // tiles, the rest on the two-launch path; 4: the first half on the 32-frame fused kernel, the rest on 16-frame tiles
+        const long nfh = tiles / 2;
+        if (o.wn_plan == 3) {
+            if (nfh > 0) segs.push_back({WN_FUSED, 16, 0, (int)map16(nfh), 0});
+            segs.push_back({WN_ROWSPLIT, 32, (int)nfh, (int)(tiles - nfh), wn_rows_for(tiles - nfh, true, o.rs_rows)});
+        } else {
+            if (nfh > 0) segs.push_back({WN_FUSED, 32, 0, (int)nfh, 0});
+            segs.push_back({WN_FUSED, 16, (int)map16(nfh), (int)(tiles16 - map16(nfh)), 0});
+        }
+        return true;
+    }
+    const bool rows_forced = rs_ok && (o.rs_rows == 128 || o.rs_rows == 256);
+    if (rows_forced && o.fused_layer == 0) {       // forced: the whole layer on wide row tiles
+        segs.push_back({WN_ROWSPLIT, 32, 0, (int)tiles, o.rs_rows});
+        return true;
+    }
+    if (o.fused_layer == 0) return false;
+    const bool plans = rs_ok && o.wn_plan != 0;     // DSD_WN_PLAN=0: one launch shape per layer, no wide row tiles
+    // one fused round = one tile per CU; the two-launch costs were measured on 256 CUs, so their tile counts are taken in
+    // 256ths of the chip (`eq`): a part with fewer CUs sees proportionally "more" tiles
+    const long cus = h->cus;
+    const long rounds = (tiles + cus - 1) / cus, nf = tiles / cus * cus, rem = tiles - nf;
+    auto eq = [cus](long t) { return (t * 256 + cus - 1) / cus; };
+    auto rows_seg = [&](long t) { return wn_rows_for(eq(t), true, o.rs_rows); };
+    const double fused_all = 2 * tiles >= cus ? round_cost * (double)rounds : 1e30;
+    const int rows_all = plans ? wn_rows_for(eq(tiles), false, o.rs_rows) : 64;
+    const double split_all = wn_split_cost(eq(tiles), rows_all, false);
+    double mixed = 1e30;
+    if (plans && nf > 0 && rem > 0) mixed = round_cost * (double)(nf / cus) + wn_split_cost(eq(rem), rows_seg(rem), true);
+    // ... and the 16-frame fused kernel as a whole layer, as the FIRST segment of a layer of up to ~1.5 rounds (one full round of
+    // 16-frame tiles, the rest on the two-launch path: B = 5 at T = 1000), or as the remainder behind whole 32-frame rounds
+    constexpr double kRound16 = 0.53;               // a round of 16-frame tiles / a round of 32-frame tiles (35.3 / 67.1 ms per loop)
+    const bool use16 = f16_ok && o.fused16 != 0;
     const double fused16_all = (use16 && 2 * tiles16 >= cus) ? kRound16 * (double)((tiles16 + cus - 1) / cus) : 1e30;
     double head16 = 1e30, tail16 = 1e30;
     long head_n32 = 0;
@@ -1551,7 +1559,7 @@ bool wn_plan_for(const dsd_handle* h, std::vector<WnSeg>& segs) {
         }
         head_n32 = lo;
         if (head_n32 > 0 && head_n32 < tiles)
-            head16 = kRound16 + wn_split_cost(eq(tiles - head_n32), wn_rows_for(eq(tiles - head_n32), true), true);
+            head16 = kRound16 + wn_split_cost(eq(tiles - head_n32), rows_seg(tiles - head_n32), true);
     }
     if (use16 && nf > 0 && rem > 0) {               // whole 32-frame rounds, the remainder as one round of 16-frame tiles
         const long rem16 = tiles16 - map16(nf);
@@ -1560,42 +1568,99 @@ bool wn_plan_for(const dsd_handle* h, std::vector<WnSeg>& segs) {
     const double best_other = std::min(std::min(mixed, fused_all), split_all);
     if (fused16_all < best_other && fused16_all <= head16 && fused16_all <= tail16) {
         segs.push_back({WN_FUSED, 16, 0, (int)tiles16, 0});
-        return true;
-    }
-    if (head16 < best_other && head16 <= tail16) {
+    } else if (head16 < best_other && head16 <= tail16) {
         segs.push_back({WN_FUSED, 16, 0, (int)map16(head_n32), 0});
-        segs.push_back({WN_ROWSPLIT, 32, (int)head_n32, (int)(tiles - head_n32), wn_rows_for(eq(tiles - head_n32), true)});
-        return true;
-    }
-    if (tail16 < best_other) {
+        segs.push_back({WN_ROWSPLIT, 32, (int)head_n32, (int)(tiles - head_n32), rows_seg(tiles - head_n32)});
+    } else if (tail16 < best_other) {
         segs.push_back({fused_kind, 32, 0, (int)nf, 0});
         segs.push_back({WN_FUSED, 16, (int)map16(nf), (int)(tiles16 - map16(nf)), 0});
-        return true;
-    }
-    if (mixed < fused_all && mixed < split_all) {
+    } else if (mixed < fused_all && mixed < split_all) {
         segs.push_back({fused_kind, 32, 0, (int)nf, 0});
-        segs.push_back({WN_ROWSPLIT, 32, (int)nf, (int)rem, wn_rows_for(eq(rem), true)});
-        return true;
-    }
-    if (fused_all < split_all) {
+        segs.push_back({WN_ROWSPLIT, 32, (int)nf, (int)rem, rows_seg(rem)});
+    } else if (fused_all < split_all) {
         segs.push_back({fused_kind, 32, 0, (int)tiles, 0});
-        return true;
-    }
-    if (rows_all > 64) {
+    } else if (rows_all > 64) {
         segs.push_back({WN_ROWSPLIT, 32, 0, (int)tiles, rows_all});
-        return true;
     }
-    return false;                                   // 64 rows per workgroup: the per-layer choice in run_backbone
+    return !segs.empty();                           // (none: 64 rows per workgroup, the per-layer choice)
 }
 
-// DSD_EDGE: 0 = never the edge kernel (wn_edge.hip), 1 = on every grid, unset = by grid size.  Read per call: tests/
-// test_gpu_edge.py switches it between two handles of one process.
-inline int edge_choice() { return path_opts().edge; }
+DenoisePlan plan_denoise(const dsd_handle* h) {
+    DenoisePlan pl;
+    const PathOpts& o = h->opts;
+    const int B = h->B, T = h->T, C = C_of(h);
+    if (is_wavenet(h)) {
+        if (wn_segments(h, pl.segs)) {
+            for (WnSeg& sg : pl.segs) sg.rows_out = sg.rows > 64 && o.rs_rows_out > 64 ? o.rs_rows_out : sg.rows;
+        } else {
+            const bool ragged = !h->lens_host.empty();
+            for (int c = 0; c < std::min(h->cfg.dilation_cycle_length, L_of(h)); ++c) {
+                const int dil = 1 << c;
+                // 32-frame tiles on a grid of about one workgroup per CU (one utterance of ~1000 frames): the row-split pair
+                // of wn_rowsplit.hip - every weight block loaded once, compiler-counted waits - instead of the two GEMMs
+                const bool rs_ok = o.rowsplit != 0 && wn_rowsplit_supported(C, dil, h->Ts);
+                const GemmCall g = make_gemm(h, h->g_conv[c], nullptr, 0, h->Ts, B, T, ST_FILM, EP_GATE, dil, false, rs_ok);
+                // 48-frame tiles where they make a dense launch ONE round of workgroups and 32-frame tiles do not (T in
+                // (1024, 1536] at B = 1: 35-48 tiles of 32 frames = 280-384 workgroups for 256 CUs): 21.9 -> see DESIGN 4.2.
+                // DSD_RS_BN48=0: off
+                const bool bn48 = rs_ok && o.rs_bn48 != 0 && !ragged && (long)B * ((T + 31) / 32) * 8 > 256 &&
+                                  (long)B * ((T + 47) / 48) * 8 <= 256;
+                pl.layer[c].rs_bn = rs_ok && ((g.nb == 1 && g.fast) || bn48) ? (bn48 ? 48 : 32) : 0;
+                pl.layer[c].rs_pair = rs_ok;
+            }
+        }
+        // skip projection -> output projection + solver update (-> the next evaluation's input projection) in one launch with
+        // one workgroup per 32-frame tile.  DSD_EDGE: 0 = never (the three GEMMs of gemm.hip), 1 = on every grid, unset = by
+        // grid size (tests/test_gpu_edge.py switches it between two handles of one process)
+        pl.edge = o.edge != 0 && wn_edge_supported(C, FM_of(h)) && (o.edge == 1 || tiles_at(h, 32) >= 128);
+        return pl;
+    }
+    // LYNXNet.  Batched grids: the two pointwise GEMMs with the whole K extent of a 32-frame tile resident in LDS
+    // (lynx_layer.hip); pw1 launches 2 inner / 512 workgroups per frame tile (8 at C = 1024: one utterance of ~1000 frames
+    // already fills the chip), pw2 only C / 512 (measured at C = 1024: slower at B = 2, +4 % at 3, +12 % at 4, +10 % at 8), so a
+    // single utterance stays on the GEMM family
+    const int inner = inner_of(h);
+    const long t32 = tiles_at(h, 32), t64 = tiles_at(h, 64);
+    const bool lx_ok = o.lynx_resident != 0 && lx_layer_supported(C, inner);
+    const bool res1 = lx_ok && (o.lynx_resident == 1 || t32 * (2 * inner / 512) >= 192);
+    const bool res2 = lx_ok && (o.lynx_resident == 1 || t32 * (C / 512) >= 192);
+    if (!res1) return pl;
+    // split-bf16 mode (lynx_x3.hip): both pointwise GEMMs as weight-stream-bound bf16x3 kernels; pw2 only where its C / 512
+    // workgroups per frame tile fill at least half the chip (one utterance: the fp32 128-row kernel is faster) ... on 64-frame
+    // tiles where those still fill the chip: the same weight stream then serves twice the frames.  Both fp32 forms of pw1 and
+    // the bf16x3 one merge their own frames' LayerNorm partials (lx_pw1_merges_stats).
+    const bool x3 = h->precision == 1 && !h->x3_conv.empty();
+    const int xw = o.x3_wide;
+    if (x3) {
+        pl.pw1 = LX_X3;
+        pl.ln_merge = false;
+        pl.x3_ncb1 = xw != 0 && (xw == 1 || t64 * (2 * inner / 512) >= h->cus) ? 4 : 2;
+    } else {
+        pl.pw1 = LX_RESIDENT;
+        pl.ln_merge = !lx_pw1_merges_stats(C, inner, (int)t32, o.lynx_pw1p, h->cus);
+    }
+    if (x3 && t32 * (C / 512) >= h->cus / 2) {
+        pl.pw2 = LX_X3;
+        pl.x3_ncb2 = xw != 0 && (xw == 1 || t64 * (C / 512) >= h->cus) ? 4 : 2;
+        return pl;
+    }
+    // pw2, fp32: 512-row workgroups (lx_pw2d_kernel, ~130 us per round of one per CU) or 128-row ones (lx_pw2q_kernel, ~40 us
+    // per round) - by rounds: between whole rounds of the wide form the narrow one wins (B = 3, 5, 6 at T = 1000: 192 / 320 /
+    // 384 wide workgroups for 256 CUs); one-utterance grids: the 128-row form or gemm.hip.  DSD_LYNX_PW2Q=0/1 forces.
+    const bool q_ok = lx_pw2q_supported(C, inner);
+    bool q_over_d = o.lynx_pw2q == 1;
+    if (res2 && o.lynx_pw2q < 0 && q_ok) {
+        const long rq = (t32 * (C / 128) + h->cus - 1) / h->cus, rd = (t32 * (C / 512) + h->cus - 1) / h->cus;
+        q_over_d = 10 * rq < 33 * rd;
+    }
+    pl.pw2 = res2 && !q_over_d ? LX_RESIDENT : o.lynx_pw2q != 0 && q_ok ? LX_PW2Q : LX_GEMM;
+    return pl;
+}
 
 // Layer `layer`'s FiLM vector d[c] for step column col0 (+ colb per batch item): kernels read film[c * cstride + c0 + b * cb].
 // From the transposed table Dt [step][L * C] that is C contiguous floats (DSD_FILM_T=0: from D [L * C][Ns], one line per row - A/B)
 inline void film_of(const dsd_handle* h, int layer, int col0, int colb, const float*& film, int& cstride, int& c0, int& cb) {
-    const int transposed = path_opts().film_t != 0;
+    const int transposed = h->opts.film_t != 0;
     const int C = C_of(h), LC = L_of(h) * C;
     if (transposed) {
         film = h->Dt + (long)layer * C; cstride = 1; c0 = col0 * LC; cb = colb * LC;
@@ -1629,20 +1694,20 @@ int run_step_tables(dsd_handle* h, int ncols, hipStream_t st) {
     return DSD_OK;
 }
 
-// One backbone evaluation on the internal-layout input `xin_state` ([B][F*M][Ts]); the last GEMM's
-// epilogue writes the `nout` linear combinations `lo` (LinTerm.ptr == nullptr = model output).
-int run_backbone(dsd_handle* h, const float* xin_state, int film_col0, int film_colb, const LinOut* lo, int nout,
-                 hipStream_t st, const float* next_xin = nullptr) {
-    const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h), L = L_of(h), Ns = h->Ns;
-    const long xs = (long)C * Ts;
-    int rc;
-    RaggedScope ragged_scope(h);
-    // timing pass: per kernel class (launch site + variant) every timing_stride-th launch carries events (a dispatch with
-    // profiling events costs the command processor more than a plain one; sampling keeps the pass close to the untimed pace)
+// A launch's result as a DSD code: hipError_t -> "<what> launch failed: ..."; run_gemm's code is already one
+inline int launch_rc(dsd_handle* h, hipError_t e, const char* what) {
+    return e == hipSuccess ? DSD_OK : fail(h, DSD_EHIP, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+inline int launch_rc(dsd_handle*, int rc, const char*) { return rc; }
+
+// One launch of kernel class `key` (a launch site of run_backbone and the variant of it that ran; bench.py groups by it) with
+// its algorithmic FLOPs / bytes.  Timing pass (dsd_kernel_timing): every timing_stride-th launch of a class carries events (a
+// dispatch with profiling events costs the command processor more than a plain one; sampling keeps the pass close to the
+// untimed pace).
+template <typename Launch>
+int timed_launch(dsd_handle* h, int key, double flops, double bytes, const char* what, Launch&& launch) {
     dsd_handle::TimedClass* tcls = nullptr;
-    auto timed_begin = [&](int key, double flops, double bytes) {
-        tcls = nullptr;
-        if (!h->timing) return;
+    if (h->timing) {
         for (auto& c : h->tclasses)
             if (c.key == key) tcls = &c;
         if (!tcls) {
@@ -1652,20 +1717,23 @@ int run_backbone(dsd_handle* h, const float* xin_state, int film_col0, int film_
         }
         tcls->flops = flops;
         tcls->bytes = bytes;
-        if (tcls->launches++ % h->timing_stride != 0) { tcls = nullptr; return; }
-        if (h->ev_used == h->ev_pool.size()) {
-            hipEvent_t a, b;
-            (void)hipEventCreate(&a);
-            (void)hipEventCreate(&b);
-            h->ev_pool.emplace_back(a, b);
+        if (tcls->launches++ % h->timing_stride != 0) {
+            tcls = nullptr;
+        } else {
+            if (h->ev_used == h->ev_pool.size()) {
+                hipEvent_t a, b;
+                (void)hipEventCreate(&a);
+                (void)hipEventCreate(&b);
+                h->ev_pool.emplace_back(a, b);
+            }
+            TimingSlot& ts = timing_slot();
+            ts.e0 = h->ev_pool[h->ev_used].first;
+            ts.e1 = h->ev_pool[h->ev_used].second;
+            ts.taken = false;
         }
-        TimingSlot& ts = timing_slot();
-        ts.e0 = h->ev_pool[h->ev_used].first;
-        ts.e1 = h->ev_pool[h->ev_used].second;
-        ts.taken = false;
-    };
-    auto timed_end = [&]() {
-        if (!tcls) return;
+    }
+    const auto r = launch();
+    if (tcls) {
         TimingSlot& ts = timing_slot();
         if (ts.taken) {
             if (tcls->name.empty()) tcls->name = ts.name;
@@ -1673,10 +1741,282 @@ int run_backbone(dsd_handle* h, const float* xin_state, int film_col0, int film_
         }
         ts.e0 = ts.e1 = nullptr;
         ts.taken = false;
-        tcls = nullptr;
+    }
+    return launch_rc(h, r, what);
+}
+
+// LYNXNet layer transition, fused into the producing GEMM's epilogue (lynxnet.py:76-84): `next` = the layer whose conditioner /
+// step projections are added (L = none: only the final LayerNorm follows)
+void lynx_next(const dsd_handle* h, GemmP& p, int next, int film_col0, int film_colb) {
+    const int C = C_of(h), L = L_of(h), Ts = h->Ts;
+    p.out = h->xh; p.o_bstride = (long)C * Ts; p.o_rstride = Ts;
+    p.out2 = next < L ? h->xin : nullptr;
+    p.lnpart = h->lnpart; p.lnpart_ts = Ts;
+    p.strong = h->cfg.strong_cond;
+    if (next < L) {
+        p.cpn = h->cp + (long)next * C * Ts; p.cpn_bstride = (long)L * C * Ts; p.cpn_rstride = Ts;
+        film_of(h, next, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
+    }
+}
+
+// WaveNet's residual layers and what follows them (run_backbone)
+int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_colb, const LinOut* lo, int nout, hipStream_t st,
+                const float* next_xin) {
+    const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h), L = L_of(h);
+    const long xs = (long)C * Ts, cps = (long)L * 2 * C * Ts;
+    const bool ragged = !h->lens_host.empty();
+    int rc;
+    // algorithmic work of the layer kernels per VALID frame: conv 3*C*2C MACs, out-proj C*2C;
+    // bytes: the conv launch reads x and the hoisted conditioner projection and writes z (16 C), the out-proj launch
+    // reads z, updates x and the skip sum (20 C); fused: x r/w, conditioner projection, skip r/w (24 C)
+    const double fl_conv = 2.0 * 3 * C * 2 * C, fl_out = 2.0 * C * 2 * C;
+    auto seg_frames = [&](int bn, int t0, int nt) -> double {       // valid frames in tiles [t0, t0 + nt) at width bn
+        const int tpb = (T + bn - 1) / bn;
+        double fr = 0;
+        if (!ragged) {
+            for (int i = t0; i < t0 + nt; ++i) fr += std::min(bn, T - (i % tpb) * bn);
+        } else {
+            const int k = bn == 16 ? 0 : bn / 32;
+            for (int i = t0; i < t0 + nt; ++i) {
+                const int e = h->cg_host[k][i], b = e / tpb, ft = e - b * tpb;
+                fr += std::min(bn, h->lens_host[b] - ft * bn);
+            }
+        }
+        return fr;
     };
-    if (h->timing) ++h->timing_evals;
+    auto layer_params = [&](WnLayerP& p, int l, int bn) {
+        memset(&p, 0, sizeof(p));
+        p.Aconv = h->blob + h->g_conv[l].a_off;
+        p.Aout = h->blob + h->g_outp[l].a_off;
+        p.bias_out = h->blob + h->g_outp[l].bias_off;
+        p.skip = h->skip;
+        p.x_bstride = xs; p.Ts = Ts;
+        p.cp = h->cp + (long)l * 2 * C * Ts; p.cp_bstride = cps;
+        film_of(h, l, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
+        p.dil = 1 << (l % h->cfg.dilation_cycle_length);
+        p.T = T; p.tiles_per_b = (T + bn - 1) / bn; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        p.first_layer = (l == 0);
+    };
+    // the row-split pair (rows per workgroup: 64 = wn_rowsplit.hip, else wn_rows.hip) on the tiles of `p`; class keys 200 + v / 300 + v
+    auto rowsplit = [&](const WnLayerP& p, int bn, int rows, int rows_out, int v, double fr) {
+        const int q = h->opts.rs_conv_q;
+        int r = timed_launch(h, 200 + v, fl_conv * fr, 16.0 * C * fr, "row-split WaveNet layer", [&] {
+            return rows > 64 ? launch_wn_rows(p, 0, C, B, rows, st) : launch_wn_rowsplit(p, 0, C, B, bn, q, st);
+        });
+        if (r) return r;
+        return timed_launch(h, 300 + v, fl_out * fr, 20.0 * C * fr, "row-split WaveNet layer", [&] {
+            return rows > 64 ? launch_wn_rows(p, 1, C, B, rows_out, st) : launch_wn_rowsplit(p, 1, C, B, bn, q, st);
+        });
+    };
+    if (!pl.segs.empty()) {
+        // the residual stream ping-pongs between xh and z (a tile's halo columns must come from the layer's INPUT, which
+        // a neighbouring tile - of this or another segment - may already have replaced); row-split segments gate into hbuf
+        const float* xi = h->xh;
+        float* xo = h->z;
+        std::vector<double> seg_fr(pl.segs.size());
+        for (size_t k = 0; k < pl.segs.size(); ++k) seg_fr[k] = seg_frames(pl.segs[k].bn, pl.segs[k].t0, pl.segs[k].nt);
+        for (int l = 0; l < L; ++l) {
+            for (size_t k = 0; k < pl.segs.size(); ++k) {
+                const WnSeg& sg = pl.segs[k];
+                const double fr = seg_fr[k];
+                WnLayerP p;
+                layer_params(p, l, sg.bn);
+                p.xin = xi; p.xout = xo; p.z = h->hbuf;
+                p.tile0 = sg.t0; p.ntiles = sg.nt;
+                if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[sg.bn == 16 ? 0 : 1] + sg.t0; p.ncg = sg.nt; }
+                const int vkey = (int)k * 4 + (p.dil > 8 ? 2 : 0) + (sg.bn == 16 ? 1 : 0);
+                if (sg.kind == WN_FUSED_X3) {
+                    p.Aconv = h->blob + h->x3_conv[l];
+                    p.Aout = h->blob + h->x3_out[l];
+                    rc = timed_launch(h, 150 + vkey, (fl_conv + fl_out) * fr, 24.0 * C * fr, "bf16x3 fused WaveNet layer",
+                                      [&] { return launch_wn_layer_x3(p, C, B, st); });
+                } else if (sg.kind == WN_FUSED) {
+                    rc = timed_launch(h, 100 + vkey, (fl_conv + fl_out) * fr, 24.0 * C * fr, "fused WaveNet layer",
+                                      [&] { return launch_wn_layer(p, C, B, st, sg.bn); });
+                } else {
+                    rc = rowsplit(p, sg.bn, sg.rows, sg.rows_out, vkey, fr);
+                }
+                if (rc) return rc;
+            }
+            xi = xo;
+            xo = (xo == h->z) ? h->xh : h->z;
+        }
+    } else {
+        const double fr_all = ragged ? seg_frames(32, 0, h->cg_n[1]) : (double)B * T;
+        for (int l = 0; l < L; ++l) {
+            const int dil = 1 << (l % h->cfg.dilation_cycle_length);
+            const auto& form = pl.layer[l % h->cfg.dilation_cycle_length];
+            if (form.rs_bn) {
+                WnLayerP p;
+                layer_params(p, l, form.rs_bn);
+                p.xin = h->xh; p.xout = h->xh; p.z = h->z;
+                if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
+                if ((rc = rowsplit(p, form.rs_bn, 64, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
+                continue;
+            }
+            GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, ST_FILM, EP_GATE, dil, false, form.rs_pair);
+            film_of(h, l, film_col0, film_colb, g.p.film, g.p.film_cstride, g.p.film_col0, g.p.film_colb);
+            g.p.aux = h->cp + (long)l * 2 * C * Ts; g.p.aux_bstride = cps; g.p.aux_rstride = Ts;
+            g.p.out = h->z; g.p.o_bstride = xs; g.p.o_rstride = Ts;
+            if ((rc = timed_launch(h, 400 + (dil > 8 ? 2 : 0), fl_conv * fr_all, 16.0 * C * fr_all, "WaveNet conv GEMM", [&] { return run_gemm(h, g, st); })))
+                return rc;
+            GemmCall o = make_gemm(h, h->g_outp[l], h->z, xs, Ts, B, T, ST_PLAIN, EP_RESSKIP, 0);
+            o.p.C = C; o.p.x = h->xh; o.p.skip = h->skip; o.p.first_layer = (l == 0);
+            o.p.o_bstride = xs; o.p.o_rstride = Ts;
+            if ((rc = timed_launch(h, 500, fl_out * fr_all, 20.0 * C * fr_all, "WaveNet out-proj GEMM", [&] { return run_gemm(h, o, st); }))) return rc;
+        }
+    }
+    if (pl.edge && nout >= 1 && nout <= kMaxOut) {      // the edge kernel (wn_edge.hip), one workgroup per 32-frame tile
+        const int ncb = 2;
+        const int bnw = 16 * ncb;
+        WnEdgeP p;
+        memset(&p, 0, sizeof(p));
+        p.A1 = h->blob + h->g_tail1.a_off; p.b1 = h->blob + h->g_tail1.bias_off;
+        p.A2 = h->blob + h->g_out.a_off; p.b2 = h->blob + h->g_out.bias_off;
+        p.A3 = h->blob + h->g_inproj.a_off; p.b3 = h->blob + h->g_inproj.bias_off;
+        p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
+        p.in_scale = sqrtf((float)L);
+        p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        p.nout = nout;
+        bool fits = true;
+        for (int i = 0; i < nout; ++i) {
+            p.dst[i] = lo[i].dst;
+            for (int k = 0; k < lo[i].nterms; ++k) {
+                const LinTerm& tm = lo[i].t[k];
+                if (tm.ptr == nullptr) { p.cm[i] += tm.coef; continue; }
+                if (p.nq == kEdgeMaxTerms || tm.ext) { fits = false; break; }      // (caller-noise terms: the GEMM path)
+                EdgeTerm& q = p.q[p.nq++];
+                q.ptr = tm.ptr; q.bstride = tm.bstride; q.rstride = tm.rstride; q.ext = tm.ext; q.coef = tm.coef; q.out = i;
+            }
+        }
+        p.o_bstride = (long)FM * Ts; p.o_rstride = Ts;
+        p.next_src = -1;
+        if (next_xin)
+            for (int i = 0; i < nout; ++i)
+                if (lo[i].dst == next_xin) p.next_src = i;
+        int nwg = B * p.tiles_per_b;
+        if (ragged) { p.cgmap = h->cg_dev[ncb == 2 ? 1 : 0]; p.ncg = h->cg_n[ncb == 2 ? 1 : 0]; nwg = p.ncg; }
+        if (fits) {      // (more state terms than the kernel holds at once: the three GEMMs below)
+            double fr_all = (double)B * T;
+            if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
+            if ((rc = timed_launch(h, 700, 2.0 * (C * C + 2.0 * C * FM) * fr_all, 4.0 * (2 * C + 3 * FM) * fr_all, "WaveNet edge-kernel",
+                                   [&] { return launch_wn_edge(p, C, ncb, nwg, st); })))
+                return rc;
+            if (p.next_src >= 0) h->edge_xh_src = next_xin;
+            return DSD_OK;
+        }
+    }
+    GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, ST_SCALE, EP_BIAS_ACT, 0);
+    t1.p.in_scale = sqrtf((float)L);      // staged value is DIVIDED by in_scale (wavenet.py:96)
+    t1.p.act = ACT_RELU; t1.p.out = h->hbuf; t1.p.o_bstride = xs; t1.p.o_rstride = Ts;
+    if ((rc = run_gemm(h, t1, st))) return rc;
+    GemmCall t2 = make_gemm(h, h->g_out, h->hbuf, xs, Ts, B, T, ST_PLAIN, EP_LINCOMB, 0);
+    t2.p.nout = nout;
+    for (int i = 0; i < nout; ++i) t2.p.lo[i] = lo[i];
+    t2.p.o_bstride = (long)FM * Ts; t2.p.o_rstride = Ts;
+    return run_gemm(h, t2, st);
+}
+
+// LYNXNet's layers and the output projection (lynxnet.py:76-87, 145-154; run_backbone)
+int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_colb, const LinOut* lo, int nout, hipStream_t st) {
+    const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h), L = L_of(h), inner = inner_of(h);
+    const long xs = (long)C * Ts, us = (long)inner * Ts;
+    const bool ragged = !h->lens_host.empty();
+    const int ln_tiles = (C + 63) / 64;
+    int rc;
+    // LayerNorm statistics of the next GEMM's input: merged from the producer's per-tile partials by a small kernel
+    // (merging inside the consuming GEMM's prologue was measured slower: every one of its ~1 k workgroups repeats it)
+    auto ln_merge = [&] { return launch_rc(h, launch_ln_merge(h->lnpart, ln_tiles, C, B, T, Ts, 1e-5f, h->stats, st), "LayerNorm merge"); };
+    // algorithmic work per valid frame of the two pointwise GEMMs (SURVEY 8(a) a12): pw1 C -> 2 inner (reads x_in, writes the
+    // SwiGLU product), pw2 inner -> C (reads the depthwise conv's output, the residual stream and the next layer's hoisted
+    // conditioner projection, writes x and x_in)
+    double fr = (double)B * T;
+    if (ragged) { fr = 0; for (int v : h->lens_host) fr += v; }
+    const double fl1 = 2.0 * C * 2 * inner * fr, by1 = 4.0 * (C + inner) * fr, fl2 = 2.0 * inner * C * fr, by2 = 4.0 * (inner + 4 * C) * fr;
+    auto widen = [&](LxLayerP& q, int ncb) {              // the tile bookkeeping of a launch on 64-frame tiles
+        if (ncb != 4) return;
+        q.tiles_per_b = (T + 63) / 64;
+        q.inv_tiles_per_b = 1.0f / (float)q.tiles_per_b;
+        q.nft = B * q.tiles_per_b;
+        if (ragged) { q.cgmap = h->cg_dev[2]; q.ncg = h->cg_n[2]; }
+        q.inv_nft = 1.0f / (float)std::max(1, ragged ? q.ncg : q.nft);
+    };
+    const PathOpts& o = h->opts;
+    for (int l = 0; l < L; ++l) {
+        // the resident and bf16x3 kernels' parameters (lynx_layer.hip, lynx_x3.hip)
+        LxLayerP p;
+        memset(&p, 0, sizeof(p));
+        p.A1 = h->blob + h->g_pw1[l].a_off; p.bias1 = h->blob + h->g_pw1[l].bias_off;
+        p.A2 = h->blob + h->g_pw2[l].a_off; p.bias2 = h->blob + h->g_pw2[l].bias_off;
+        p.xin = h->xin; p.stats = h->stats; p.u = h->ubuf; p.v = h->vbuf; p.x = h->xh;
+        p.x_bstride = xs; p.u_bstride = us; p.inner = inner; p.Ts = Ts; p.T = T;
+        p.tiles_per_b = (T + 31) / 32; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        p.nft = B * p.tiles_per_b;
+        if (ragged) { p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
+        p.inv_nft = 1.0f / (float)std::max(1, ragged ? p.ncg : p.nft);
+        p.strong = h->cfg.strong_cond;
+        p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles;
+        p.lnpart_in = h->lnpart;        // (read by pw1 before pw2 of this layer replaces it with the next layer's partials)
+        const int next = l + 1;
+        p.xin_out = next < L ? h->xin : nullptr;
+        if (next < L) {
+            p.cpn = h->cp + (long)next * C * Ts; p.cpn_bstride = (long)L * C * Ts;
+            film_of(h, next, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
+        }
+        if (pl.ln_merge && (rc = ln_merge())) return rc;
+        if (pl.pw1 == LX_X3) {
+            LxLayerP q = p;
+            q.A1 = h->blob + h->x3_conv[l];
+            widen(q, pl.x3_ncb1);
+            rc = timed_launch(h, 650 + (pl.x3_ncb1 == 4 ? 1 : 0), fl1, by1, "LYNXNet pw1", [&] { return launch_lx_x3(q, 0, C, pl.x3_ncb1, st); });
+        } else if (pl.pw1 == LX_RESIDENT) {
+            rc = timed_launch(h, 600, fl1, by1, "LYNXNet pw1", [&] { return launch_lx_layer(p, 0, C, o.lynx_pw1p, o.lynx_pw2d, h->cus, st); });
+        } else {
+            GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_SWIGLU, 0);
+            g.p.ln_stats = h->stats; g.p.ln_ts = Ts;
+            g.p.out = h->ubuf; g.p.o_bstride = us; g.p.o_rstride = Ts;
+            rc = timed_launch(h, 630, fl1, by1, "LYNXNet pw1 GEMM", [&] { return run_gemm(h, g, st); });
+        }
+        if (rc) return rc;
+        rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, ragged ? h->lens_dev : nullptr, h->blob + h->dw_w[l],
+                                        h->blob + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
+                                        h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], o.dwconv_rows, st), "dwconv");
+        if (rc) return rc;
+        if (pl.pw2 == LX_X3) {
+            LxLayerP q = p;
+            q.A2 = h->blob + h->x3_out[l];
+            widen(q, pl.x3_ncb2);
+            rc = timed_launch(h, 660 + (pl.x3_ncb2 == 4 ? 1 : 0), fl2, by2, "LYNXNet pw2 (bf16x3)", [&] { return launch_lx_x3(q, 1, C, pl.x3_ncb2, st); });
+        } else if (pl.pw2 == LX_RESIDENT) {
+            rc = timed_launch(h, 610, fl2, by2, "LYNXNet pw2", [&] { return launch_lx_layer(p, 1, C, o.lynx_pw1p, o.lynx_pw2d, h->cus, st); });
+        } else if (pl.pw2 == LX_PW2Q) {     // 128 rows per workgroup, C / 128 workgroups per frame tile (lynx_layer.hip, lx_pw2q_kernel)
+            rc = timed_launch(h, 615, fl2, by2, "LYNXNet pw2 (128-row)", [&] { return launch_lx_pw2q(p, C, st); });
+        } else {
+            GemmCall g = make_gemm(h, h->g_pw2[l], h->vbuf, us, Ts, B, T, ST_PLAIN, EP_LYNX_NEXT, 0);
+            g.p.act = ACT_NONE;
+            g.p.aux = h->xh; g.p.aux_bstride = xs; g.p.aux_rstride = Ts;
+            lynx_next(h, g.p, next, film_col0, film_colb);
+            rc = timed_launch(h, 620, fl2, by2, "LYNXNet pw2 GEMM", [&] { return run_gemm(h, g, st); });
+        }
+        if (rc) return rc;
+    }
+    GemmCall f = make_gemm(h, h->g_out, h->xh, xs, Ts, B, T, ST_LN, EP_LINCOMB, 0);
+    if ((rc = ln_merge())) return rc;
+    f.p.ln_stats = h->stats; f.p.ln_ts = Ts;
+    f.p.nout = nout;
+    for (int i = 0; i < nout; ++i) f.p.lo[i] = lo[i];
+    f.p.o_bstride = (long)FM * Ts; f.p.o_rstride = Ts;
+    return run_gemm(h, f, st);
+}
+
+// One backbone evaluation on the internal-layout input `xin_state` ([B][F*M][Ts]) by the plan of this call (plan_denoise); the
+// last GEMM's epilogue writes the `nout` linear combinations `lo` (LinTerm.ptr == nullptr = model output).
+int run_backbone(dsd_handle* h, const DenoisePlan& pl, const float* xin_state, int film_col0, int film_colb, const LinOut* lo,
+                 int nout, hipStream_t st, const float* next_xin = nullptr) {
+    const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h);
+    RaggedScope ragged_scope(h);
     if (h->timing) {      // one empty bracket per evaluation calibrates what a hipEvent pair itself costs
+        ++h->timing_evals;
         if (h->cal_used == h->cal_pool.size()) {
             hipEvent_t a, b;
             (void)hipEventCreate(&a);
@@ -1688,366 +2028,19 @@ int run_backbone(dsd_handle* h, const float* xin_state, int film_col0, int film_
         ++h->cal_used;
     }
     const bool lynx = !is_wavenet(h);
-    const int ln_tiles = (C + 63) / 64;
-    // LYNXNet layer transition, fused into the producing GEMM's epilogue (lynxnet.py:76-84): `next` = the layer whose
-    // conditioner / step projections are added (L = none: only the final LayerNorm follows)
-    auto lynx_next = [&](GemmCall& g, int next) {
-        g.p.out = h->xh; g.p.o_bstride = xs; g.p.o_rstride = Ts;
-        g.p.out2 = next < L ? h->xin : nullptr;
-        g.p.lnpart = h->lnpart; g.p.lnpart_ts = Ts;
-        g.p.strong = h->cfg.strong_cond;
-        if (next < L) {
-            g.p.cpn = h->cp + (long)next * C * Ts; g.p.cpn_bstride = (long)L * C * Ts; g.p.cpn_rstride = Ts;
-            film_of(h, next, film_col0, film_colb, g.p.film, g.p.film_cstride, g.p.film_col0, g.p.film_colb);
-        }
-    };
     // WaveNet: the previous evaluation's edge kernel (wn_edge.hip) may already have projected this very input into xh
     const bool inproj_done = !lynx && h->edge_xh_src != nullptr && h->edge_xh_src == xin_state;
     h->edge_xh_src = nullptr;
     if (!inproj_done) {   // input projection (+ReLU for WaveNet, wavenet.py:86-88; GELU unless strong_cond for LYNXNet, lynxnet.py:141-143)
-        GemmCall g = make_gemm(h, h->g_inproj, xin_state, (long)FM * Ts, Ts, B, T, ST_PLAIN,
-                               lynx ? EP_LYNX_NEXT : EP_BIAS_ACT, 0);
-        g.p.act = is_wavenet(h) ? ACT_RELU : (h->cfg.strong_cond ? ACT_NONE : ACT_GELU);
-        g.p.out = h->xh; g.p.o_bstride = xs; g.p.o_rstride = Ts;
-        if (lynx) lynx_next(g, 0);
-        if ((rc = run_gemm(h, g, st))) return rc;
-    }
-    if (is_wavenet(h)) {
-        const long cps = (long)L * 2 * C * Ts;
-        const bool ragged = h->use_cg && !h->lens_host.empty();
-        // algorithmic work of the layer kernels per VALID frame: conv 3*C*2C MACs, out-proj C*2C;
-        // bytes: the conv launch reads x and the hoisted conditioner projection and writes z (16 C), the out-proj launch
-        // reads z, updates x and the skip sum (20 C); fused: x r/w, conditioner projection, skip r/w (24 C)
-        const double fl_conv = 2.0 * 3 * C * 2 * C, fl_out = 2.0 * C * 2 * C;
-        auto seg_frames = [&](int bn, int t0, int nt) -> double {       // valid frames in tiles [t0, t0 + nt) at width bn
-            const int tpb = (T + bn - 1) / bn;
-            double fr = 0;
-            if (!ragged) {
-                for (int i = t0; i < t0 + nt; ++i) fr += std::min(bn, T - (i % tpb) * bn);
-            } else {
-                const int k = bn == 16 ? 0 : bn / 32;
-                for (int i = t0; i < t0 + nt; ++i) {
-                    const int e = h->cg_host[k][i], b = e / tpb, ft = e - b * tpb;
-                    fr += std::min(bn, h->lens_host[b] - ft * bn);
-                }
-            }
-            return fr;
-        };
-        auto layer_params = [&](WnLayerP& p, int l, int bn) {
-            memset(&p, 0, sizeof(p));
-            p.Aconv = h->blob + h->g_conv[l].a_off;
-            p.Aout = h->blob + h->g_outp[l].a_off;
-            p.bias_out = h->blob + h->g_outp[l].bias_off;
-            p.skip = h->skip;
-            p.x_bstride = xs; p.Ts = Ts;
-            p.cp = h->cp + (long)l * 2 * C * Ts; p.cp_bstride = cps;
-            film_of(h, l, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
-            p.dil = 1 << (l % h->cfg.dilation_cycle_length);
-            p.T = T; p.tiles_per_b = (T + bn - 1) / bn; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-            p.first_layer = (l == 0);
-        };
-        std::vector<WnSeg> plan;
-        if (wn_plan_for(h, plan)) {
-            // the residual stream ping-pongs between xh and z (a tile's halo columns must come from the layer's INPUT, which
-            // a neighbouring tile - of this or another segment - may already have replaced); row-split segments gate into hbuf
-            const float* xi = h->xh;
-            float* xo = h->z;
-            std::vector<double> seg_fr(plan.size());
-            for (size_t k = 0; k < plan.size(); ++k) seg_fr[k] = seg_frames(plan[k].bn, plan[k].t0, plan[k].nt);
-            for (int l = 0; l < L; ++l) {
-                for (size_t k = 0; k < plan.size(); ++k) {
-                    const WnSeg& sg = plan[k];
-                    WnLayerP p;
-                    layer_params(p, l, sg.bn);
-                    p.xin = xi; p.xout = xo; p.z = h->hbuf;
-                    p.tile0 = sg.t0; p.ntiles = sg.nt;
-                    if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[sg.bn == 16 ? 0 : 1] + sg.t0; p.ncg = sg.nt; }
-                    const int vkey = (int)k * 4 + (p.dil > 8 ? 2 : 0) + (sg.bn == 16 ? 1 : 0);
-                    hipError_t le;
-                    if (sg.kind == WN_FUSED_X3) {
-                        p.Aconv = h->blob + h->x3_conv[l];
-                        p.Aout = h->blob + h->x3_out[l];
-                        timed_begin(150 + vkey, (fl_conv + fl_out) * seg_fr[k], 24.0 * C * seg_fr[k]);
-                        le = launch_wn_layer_x3(p, C, B, st);
-                        timed_end();
-                        if (le != hipSuccess) return fail(h, DSD_EHIP, "bf16x3 fused WaveNet layer launch failed: %s", hipGetErrorString(le));
-                    } else if (sg.kind == WN_FUSED) {
-                        timed_begin(100 + vkey, (fl_conv + fl_out) * seg_fr[k], 24.0 * C * seg_fr[k]);
-                        le = launch_wn_layer(p, C, B, st, sg.bn);
-                        timed_end();
-                        if (le != hipSuccess) return fail(h, DSD_EHIP, "fused WaveNet layer launch failed: %s", hipGetErrorString(le));
-                    } else {
-                        const bool wide = sg.rows > 64;
-                        timed_begin(200 + vkey, fl_conv * seg_fr[k], 16.0 * C * seg_fr[k]);
-                        le = wide ? launch_wn_rows(p, 0, C, B, sg.rows, st) : launch_wn_rowsplit(p, 0, C, B, sg.bn, st);
-                        timed_end();
-                        if (le == hipSuccess) {
-                            timed_begin(300 + vkey, fl_out * seg_fr[k], 20.0 * C * seg_fr[k]);
-                            le = wide ? launch_wn_rows(p, 1, C, B, path_opts().rs_rows_out > 64 ? path_opts().rs_rows_out : sg.rows, st)
-                                      : launch_wn_rowsplit(p, 1, C, B, sg.bn, st);
-                            timed_end();
-                        }
-                        if (le != hipSuccess) return fail(h, DSD_EHIP, "row-split WaveNet layer launch failed: %s", hipGetErrorString(le));
-                    }
-                }
-                xi = xo;
-                xo = (xo == h->z) ? h->xh : h->z;
-            }
-        } else
-        for (int l = 0; l < L; ++l) {
-            const int dil = 1 << (l % h->cfg.dilation_cycle_length);
-            // 32-frame tiles on a grid of about one workgroup per CU (one utterance of ~1000 frames): the row-split pair
-            // of wn_rowsplit.hip - every weight block loaded once, compiler-counted waits - instead of the two GEMMs
-            const bool rs_ok = path_opts().rowsplit != 0 && wn_rowsplit_supported(C, dil, Ts);
-            GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, ST_FILM, EP_GATE, dil, false, rs_ok);
-            // 48-frame tiles where they make a dense launch ONE round of workgroups and 32-frame tiles do not (T in (1024, 1536]
-            // at B = 1: 35-48 tiles of 32 frames = 280-384 workgroups for 256 CUs): 21.9 -> see DESIGN 4.2.  DSD_RS_BN48=0: off
-            const bool bn48 = rs_ok && path_opts().rs_bn48 != 0 && !ragged && (long)B * ((T + 31) / 32) * 8 > 256 &&
-                              (long)B * ((T + 47) / 48) * 8 <= 256;
-            const double fr_all = ragged ? seg_frames(32, 0, h->cg_n[1]) : (double)B * T;
-            if (rs_ok && ((g.nb == 1 && g.fast) || bn48)) {
-                const int bn = bn48 ? 48 : 32;
-                WnLayerP p;
-                layer_params(p, l, bn);
-                p.xin = h->xh; p.xout = h->xh; p.z = h->z;
-                if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
-                timed_begin(200 + (bn48 ? 1 : 0) + (dil > 8 ? 2 : 0), fl_conv * fr_all, 16.0 * C * fr_all);
-                hipError_t le = launch_wn_rowsplit(p, 0, C, B, bn, st);
-                timed_end();
-                if (le == hipSuccess) {
-                    timed_begin(300 + (bn48 ? 1 : 0) + (dil > 8 ? 2 : 0), fl_out * fr_all, 20.0 * C * fr_all);
-                    le = launch_wn_rowsplit(p, 1, C, B, bn, st);
-                    timed_end();
-                }
-                if (le != hipSuccess) return fail(h, DSD_EHIP, "row-split WaveNet layer launch failed: %s", hipGetErrorString(le));
-                continue;
-            }
-            film_of(h, l, film_col0, film_colb, g.p.film, g.p.film_cstride, g.p.film_col0, g.p.film_colb);
-            g.p.aux = h->cp + (long)l * 2 * C * Ts; g.p.aux_bstride = cps; g.p.aux_rstride = Ts;
-            g.p.out = h->z; g.p.o_bstride = xs; g.p.o_rstride = Ts;
-            timed_begin(400 + (dil > 8 ? 2 : 0), fl_conv * fr_all, 16.0 * C * fr_all);
-            rc = run_gemm(h, g, st);
-            timed_end();
-            if (rc) return rc;
-            GemmCall o = make_gemm(h, h->g_outp[l], h->z, xs, Ts, B, T, ST_PLAIN, EP_RESSKIP, 0);
-            o.p.C = C; o.p.x = h->xh; o.p.skip = h->skip; o.p.first_layer = (l == 0);
-            o.p.o_bstride = xs; o.p.o_rstride = Ts;
-            timed_begin(500, fl_out * fr_all, 20.0 * C * fr_all);
-            rc = run_gemm(h, o, st);
-            timed_end();
-            if (rc) return rc;
-        }
-        // skip projection -> output projection + solver update (-> the next evaluation's input projection) in one launch with
-        // one workgroup per frame tile (wn_edge.hip); DSD_EDGE=0: the three GEMMs of gemm.hip
-        const int edge_env = edge_choice();
-        const bool e_ragged = h->use_cg && !h->lens_host.empty();
-        const long e_t32 = e_ragged ? (long)h->cg_n[1] : (long)B * ((T + 31) / 32);       // 32-frame tiles = workgroups
-        if (edge_env != 0 && wn_edge_supported(C, FM) && nout >= 1 && nout <= kMaxOut && (edge_env == 1 || e_t32 >= 128)) {
-            const bool ragged = e_ragged;
-            const int ncb = 2;
-            const int bnw = 16 * ncb;
-            WnEdgeP p;
-            memset(&p, 0, sizeof(p));
-            p.A1 = h->blob + h->g_tail1.a_off; p.b1 = h->blob + h->g_tail1.bias_off;
-            p.A2 = h->blob + h->g_out.a_off; p.b2 = h->blob + h->g_out.bias_off;
-            p.A3 = h->blob + h->g_inproj.a_off; p.b3 = h->blob + h->g_inproj.bias_off;
-            p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
-            p.in_scale = sqrtf((float)L);
-            p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-            p.nout = nout;
-            bool fits = true;
-            for (int i = 0; i < nout; ++i) {
-                p.dst[i] = lo[i].dst;
-                for (int k = 0; k < lo[i].nterms; ++k) {
-                    const LinTerm& tm = lo[i].t[k];
-                    if (tm.ptr == nullptr) { p.cm[i] += tm.coef; continue; }
-                    if (p.nq == kEdgeMaxTerms || tm.ext) { fits = false; break; }      // (caller-noise terms: the GEMM path)
-                    EdgeTerm& q = p.q[p.nq++];
-                    q.ptr = tm.ptr; q.bstride = tm.bstride; q.rstride = tm.rstride; q.ext = tm.ext; q.coef = tm.coef; q.out = i;
-                }
-            }
-            p.o_bstride = (long)FM * Ts; p.o_rstride = Ts;
-            p.next_src = -1;
-            if (next_xin)
-                for (int i = 0; i < nout; ++i)
-                    if (lo[i].dst == next_xin) p.next_src = i;
-            int nwg = B * p.tiles_per_b;
-            if (ragged) { p.cgmap = h->cg_dev[ncb == 2 ? 1 : 0]; p.ncg = h->cg_n[ncb == 2 ? 1 : 0]; nwg = p.ncg; }
-            if (fits) {      // (more state terms than the kernel holds at once: the three GEMMs below)
-                double fr_all = (double)B * T;
-                if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
-                timed_begin(700, 2.0 * (C * C + 2.0 * C * FM) * fr_all, 4.0 * (2 * C + 3 * FM) * fr_all);
-                hipError_t ee = launch_wn_edge(p, C, ncb, nwg, st);
-                timed_end();
-                if (ee != hipSuccess) return fail(h, DSD_EHIP, "WaveNet edge-kernel launch failed: %s", hipGetErrorString(ee));
-                if (p.next_src >= 0) h->edge_xh_src = next_xin;
-                return DSD_OK;
-            }
-        }
-        GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, ST_SCALE, EP_BIAS_ACT, 0);
-        t1.p.in_scale = sqrtf((float)L);      // staged value is DIVIDED by in_scale (wavenet.py:96)
-        t1.p.act = ACT_RELU; t1.p.out = h->hbuf; t1.p.o_bstride = xs; t1.p.o_rstride = Ts;
-        if ((rc = run_gemm(h, t1, st))) return rc;
-        GemmCall t2 = make_gemm(h, h->g_out, h->hbuf, xs, Ts, B, T, ST_PLAIN, EP_LINCOMB, 0);
-        t2.p.nout = nout;
-        for (int i = 0; i < nout; ++i) t2.p.lo[i] = lo[i];
-        t2.p.o_bstride = (long)FM * Ts; t2.p.o_rstride = Ts;
-        return run_gemm(h, t2, st);
-    }
-    // ---- LYNXNet (lynxnet.py:76-87, 145-154) ----
-    const int inner = inner_of(h);
-    const long us = (long)inner * Ts;
-    hipError_t e;
-    // LayerNorm statistics of the next GEMM's input: merged from the producer's per-tile partials by a small kernel
-    // (merging inside the consuming GEMM's prologue was measured slower: every one of its ~1 k workgroups repeats it)
-    auto ln_input = [&](GemmCall& g) -> int {
-        hipError_t me = launch_ln_merge(h->lnpart, ln_tiles, C, B, T, Ts, 1e-5f, h->stats, st);
-        if (me != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm merge launch failed: %s", hipGetErrorString(me));
-        g.p.ln_stats = h->stats; g.p.ln_ts = Ts;
-        return DSD_OK;
-    };
-    // Batched grids: the two pointwise GEMMs with the whole K extent of a 32-frame tile resident in LDS (lynx_layer.hip);
-    // pw2 launches only C / 512 workgroups per frame tile, so a single utterance stays on the GEMM family
-    const bool lx_ragged = h->use_cg && !h->lens_host.empty();
-    const long lx_tiles = lx_ragged ? (long)h->cg_n[1] : (long)B * ((T + 31) / 32);
-    const int lx_env = path_opts().lynx_resident;
-    const bool lx_ok = lx_env != 0 && lx_layer_supported(C, inner);
-    // pw1 launches 2 inner / 512 workgroups per frame tile (8 at C = 1024: one utterance of ~1000 frames already fills the
-    // chip), pw2 only C / 512 (measured at C = 1024: slower at B = 2, +4 % at 3, +12 % at 4, +10 % at 8)
-    const bool lx_res1 = lx_ok && (lx_env == 1 || lx_tiles * (2 * inner / 512) >= 192);
-    const bool lx_res2 = lx_ok && (lx_env == 1 || lx_tiles * (C / 512) >= 192);
-    const bool lx_res = lx_res1;
-    // algorithmic work per valid frame of the two pointwise GEMMs (SURVEY 8(a) a12): pw1 C -> 2 inner (reads x_in, writes the
-    // SwiGLU product), pw2 inner -> C (reads the depthwise conv's output, the residual stream and the next layer's hoisted
-    // conditioner projection, writes x and x_in)
-    double lx_fr = (double)B * T;
-    if (lx_ragged) { lx_fr = 0; for (int v : h->lens_host) lx_fr += v; }
-    const double lx_fl1 = 2.0 * C * 2 * inner, lx_by1 = 4.0 * (C + inner), lx_fl2 = 2.0 * inner * C, lx_by2 = 4.0 * (inner + 4 * C);
-    for (int l = 0; l < L; ++l) {
-        if (lx_res) {
-            LxLayerP p;
-            memset(&p, 0, sizeof(p));
-            p.A1 = h->blob + h->g_pw1[l].a_off; p.bias1 = h->blob + h->g_pw1[l].bias_off;
-            p.A2 = h->blob + h->g_pw2[l].a_off; p.bias2 = h->blob + h->g_pw2[l].bias_off;
-            p.xin = h->xin; p.stats = h->stats; p.u = h->ubuf; p.v = h->vbuf; p.x = h->xh;
-            p.x_bstride = xs; p.u_bstride = us; p.inner = inner; p.Ts = Ts; p.T = T;
-            p.tiles_per_b = (T + 31) / 32; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-            p.nft = B * p.tiles_per_b;
-            if (lx_ragged) { p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
-            p.inv_nft = 1.0f / (float)std::max(1, lx_ragged ? p.ncg : p.nft);
-            p.strong = h->cfg.strong_cond;
-            p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles;
-            p.lnpart_in = h->lnpart;        // (read by pw1 before pw2 of this layer replaces it with the next layer's partials)
-            if (!(h->precision == 1 && !h->x3_conv.empty()) && !lx_pw1_merges_stats(p, C)) {      // (both fp32 forms and the bf16x3 one merge their own frames' partials)
-                hipError_t me = launch_ln_merge(h->lnpart, ln_tiles, C, B, T, Ts, 1e-5f, h->stats, st);
-                if (me != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm merge launch failed: %s", hipGetErrorString(me));
-            }
-            const int next = l + 1;
-            p.xin_out = next < L ? h->xin : nullptr;
-            if (next < L) {
-                p.cpn = h->cp + (long)next * C * Ts; p.cpn_bstride = (long)L * C * Ts;
-                film_of(h, next, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
-            }
-            // split-bf16 mode (lynx_x3.hip): both pointwise GEMMs as weight-stream-bound bf16x3 kernels; pw2 only where its C / 512
-            // workgroups per frame tile fill at least half the chip (one utterance: the fp32 128-row kernel is faster)
-            const bool x3 = h->precision == 1 && !h->x3_conv.empty();
-            const bool x3_pw2 = x3 && lx_tiles * (C / 512) >= h->cus / 2;
-            // ... on 64-frame tiles where those still fill the chip: the same weight stream then serves twice the frames
-            const long lx_t64 = lx_ragged ? (long)h->cg_n[2] : (long)B * ((T + 63) / 64);
-            const int xw = path_opts().x3_wide;
-            const bool wide1 = x3 && xw != 0 && (xw == 1 || lx_t64 * (2 * inner / 512) >= h->cus);
-            const bool wide2 = x3_pw2 && xw != 0 && (xw == 1 || lx_t64 * (C / 512) >= h->cus);
-            auto widen = [&](LxLayerP& q) {                      // the tile bookkeeping of a launch on 64-frame tiles
-                q.tiles_per_b = (T + 63) / 64;
-                q.inv_tiles_per_b = 1.0f / (float)q.tiles_per_b;
-                q.nft = B * q.tiles_per_b;
-                if (lx_ragged) { q.cgmap = h->cg_dev[2]; q.ncg = h->cg_n[2]; }
-                q.inv_nft = 1.0f / (float)std::max(1, lx_ragged ? q.ncg : q.nft);
-            };
-            // pw2, fp32: 512-row workgroups (lx_pw2d_kernel, ~130 us per round of one per CU) or 128-row ones (lx_pw2q_kernel, ~40 us
-            // per round) - by rounds: between whole rounds of the wide form the narrow one wins (B = 3, 5, 6 at T = 1000: 192 / 320 /
-            // 384 wide workgroups for 256 CUs).  DSD_LYNX_PW2Q=0/1 forces.
-            bool lx_q_over_d = path_opts().lynx_pw2q == 1;
-            if (lx_res2 && path_opts().lynx_pw2q < 0 && lx_pw2q_supported(C, inner)) {
-                const long rq = (lx_tiles * (C / 128) + h->cus - 1) / h->cus, rd = (lx_tiles * (C / 512) + h->cus - 1) / h->cus;
-                lx_q_over_d = 10 * rq < 33 * rd;
-            }
-            hipError_t le;
-            if (x3) {
-                LxLayerP q = p;
-                q.A1 = h->blob + h->x3_conv[l];
-                if (wide1) widen(q);
-                timed_begin(650 + (wide1 ? 1 : 0), lx_fl1 * lx_fr, lx_by1 * lx_fr);
-                le = launch_lx_x3(q, 0, C, wide1 ? 4 : 2, st);
-                timed_end();
-            } else {
-                timed_begin(600, lx_fl1 * lx_fr, lx_by1 * lx_fr);
-                le = launch_lx_layer(p, 0, C, st);
-                timed_end();
-            }
-            if (le != hipSuccess) return fail(h, DSD_EHIP, "LYNXNet pw1 launch failed: %s", hipGetErrorString(le));
-            e = launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, h->lens_host.empty() ? nullptr : h->lens_dev,
-                              h->blob + h->dw_w[l], h->blob + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
-                              h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], st);
-            if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
-            if (x3_pw2) {
-                LxLayerP q = p;
-                q.A2 = h->blob + h->x3_out[l];
-                if (wide2) widen(q);
-                timed_begin(660 + (wide2 ? 1 : 0), lx_fl2 * lx_fr, lx_by2 * lx_fr);
-                le = launch_lx_x3(q, 1, C, wide2 ? 4 : 2, st);
-                timed_end();
-                if (le != hipSuccess) return fail(h, DSD_EHIP, "LYNXNet pw2 (bf16x3) launch failed: %s", hipGetErrorString(le));
-            } else if (lx_res2 && !lx_q_over_d) {
-                timed_begin(610, lx_fl2 * lx_fr, lx_by2 * lx_fr);
-                le = launch_lx_layer(p, 1, C, st);
-                timed_end();
-                if (le != hipSuccess) return fail(h, DSD_EHIP, "LYNXNet pw2 launch failed: %s", hipGetErrorString(le));
-            } else if (path_opts().lynx_pw2q != 0 && lx_pw2q_supported(C, inner)) {
-                // one-utterance grids: 128 rows per workgroup, C / 128 workgroups per frame tile (lynx_layer.hip, lx_pw2q_kernel)
-                timed_begin(615, lx_fl2 * lx_fr, lx_by2 * lx_fr);
-                le = launch_lx_pw2q(p, C, st);
-                timed_end();
-                if (le != hipSuccess) return fail(h, DSD_EHIP, "LYNXNet pw2 (128-row) launch failed: %s", hipGetErrorString(le));
-            } else {
-                GemmCall o = make_gemm(h, h->g_pw2[l], h->vbuf, us, Ts, B, T, ST_PLAIN, EP_LYNX_NEXT, 0);
-                o.p.act = ACT_NONE;
-                o.p.aux = h->xh; o.p.aux_bstride = xs; o.p.aux_rstride = Ts;
-                lynx_next(o, l + 1);
-                timed_begin(620, lx_fl2 * lx_fr, lx_by2 * lx_fr);
-                rc = run_gemm(h, o, st);
-                timed_end();
-                if (rc) return rc;
-            }
-            continue;
-        }
-        GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_SWIGLU, 0);
-        if ((rc = ln_input(g))) return rc;
-        g.p.out = h->ubuf; g.p.o_bstride = us; g.p.o_rstride = Ts;
-        timed_begin(630, lx_fl1 * lx_fr, lx_by1 * lx_fr);
-        rc = run_gemm(h, g, st);
-        timed_end();
-        if (rc) return rc;
-        e = launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, h->lens_host.empty() ? nullptr : h->lens_dev,
-                          h->blob + h->dw_w[l], h->blob + h->dw_b[l],
-                          h->cfg.kernel_size, h->cfg.activation,
-                          h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], st);
-        if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
-        GemmCall o = make_gemm(h, h->g_pw2[l], h->vbuf, us, Ts, B, T, ST_PLAIN, EP_LYNX_NEXT, 0);
-        o.p.act = ACT_NONE;
-        o.p.aux = h->xh; o.p.aux_bstride = xs; o.p.aux_rstride = Ts;
-        lynx_next(o, l + 1);
-        timed_begin(620, lx_fl2 * lx_fr, lx_by2 * lx_fr);
-        rc = run_gemm(h, o, st);
-        timed_end();
+        GemmCall g = make_gemm(h, h->g_inproj, xin_state, (long)FM * Ts, Ts, B, T, ST_PLAIN, lynx ? EP_LYNX_NEXT : EP_BIAS_ACT, 0);
+        g.p.act = lynx ? (h->cfg.strong_cond ? ACT_NONE : ACT_GELU) : ACT_RELU;
+        g.p.out = h->xh; g.p.o_bstride = (long)C * Ts; g.p.o_rstride = Ts;
+        if (lynx) lynx_next(h, g.p, 0, film_col0, film_colb);
+        const int rc = run_gemm(h, g, st);
         if (rc) return rc;
     }
-    GemmCall f = make_gemm(h, h->g_out, h->xh, xs, Ts, B, T, ST_LN, EP_LINCOMB, 0);
-    if ((rc = ln_input(f))) return rc;
-    f.p.nout = nout;
-    for (int i = 0; i < nout; ++i) f.p.lo[i] = lo[i];
-    f.p.o_bstride = (long)FM * Ts; f.p.o_rstride = Ts;
-    return run_gemm(h, f, st);
+    return lynx ? run_lynxnet(h, pl, film_col0, film_colb, lo, nout, st)
+                : run_wavenet(h, pl, film_col0, film_colb, lo, nout, st, next_xin);
 }
 
 void destroy_graphs(dsd_handle* h) {
@@ -2119,8 +2112,8 @@ int dsd_create(const dsd_config* cfg, dsd_handle** out) {
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
     dsd_handle* h = new dsd_handle();
     h->cfg = *cfg;
-    refresh_path_opts();
-    h->precision = path_opts().precision == 1 ? 1 : 0;       // DSD_PRECISION=1: split-bf16 layer kernels (dsd_set_precision)
+    h->opts = read_path_opts();
+    h->precision = h->opts.precision == 1 ? 1 : 0;       // DSD_PRECISION=1: split-bf16 layer kernels (dsd_set_precision)
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
@@ -2226,8 +2219,8 @@ int dsd_finalize_weights(dsd_handle* h) {
 
 int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,
                      int64_t stride_t, void* stream) {
-    refresh_path_opts();
     if (!h || !cond) return fail(h, DSD_EINVAL, "dsd_prepare_cond: null argument");
+    h->opts = read_path_opts();
     if (is_aux(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an aux decoder (use dsd_aux_decode)");
     if (is_enc(h) || is_tok(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an encoder (use dsd_encode / dsd_token_encode)");
     if (is_voc(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is a vocoder (use dsd_vocode)");
@@ -2374,8 +2367,8 @@ static int run_fs2_layers(dsd_handle* h, int H, int NL, int heads, int ffn_ks, i
 
 int dsd_encode(dsd_handle* h, const int64_t* txt_tokens, const int64_t* mel2ph, const float* f0, int32_t B, int32_t L,
                int32_t T, const dsd_encode_extras* ex, float* cond_out, void* stream) {
-    refresh_path_opts();
     if (!h || !txt_tokens || !mel2ph || !f0 || !cond_out) return fail(h, DSD_EINVAL, "dsd_encode: null argument");
+    h->opts = read_path_opts();
     if (!is_enc(h)) return fail(h, DSD_ESTATE, "dsd_encode: this handle is not an encoder");
     if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_encode: weights are not finalized");
     if (B < 1 || L < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_encode: B, T_txt and T must be positive (%d, %d, %d)", B, L, T);
@@ -2489,9 +2482,9 @@ static int tok_common(dsd_handle* h, const char* who, const void* a, const void*
 
 int dsd_token_encode(dsd_handle* h, const float* embed, const uint8_t* padding_mask, int32_t B, int32_t L, float* enc_out,
                      void* stream) {
-    refresh_path_opts();
     int rc = tok_common(h, "dsd_token_encode", embed, padding_mask, enc_out, B, L);
     if (rc) return rc;
+    h->opts = read_path_opts();
     const dsd_token_encoder_config& t = h->tcfg;
     hipStream_t st = (hipStream_t)stream;
     HIP_OK(h, hipSetDevice(t.device));
@@ -2524,9 +2517,9 @@ int dsd_token_encode(dsd_handle* h, const float* embed, const uint8_t* padding_m
 
 int dsd_predict_dur(dsd_handle* h, const float* dur_cond, const uint8_t* padding_mask, int32_t B, int32_t L, float* dur_out,
                     void* stream) {
-    refresh_path_opts();
     int rc = tok_common(h, "dsd_predict_dur", dur_cond, padding_mask, dur_out, B, L);
     if (rc) return rc;
+    h->opts = read_path_opts();
     const dsd_token_encoder_config& t = h->tcfg;
     if (t.dur_layers < 1) return fail(h, DSD_ESTATE, "dsd_predict_dur: this encoder was created without a duration predictor");
     hipStream_t st = (hipStream_t)stream;
@@ -2732,8 +2725,8 @@ int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipS
 int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
                 int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
                 const float* pre_noise, float* wav_out, void* stream) {
-    refresh_path_opts();
     if (!h || !mel || !f0 || !wav_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
+    h->opts = read_path_opts();
     if (!is_voc(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a vocoder", who);
     if (!h->vcfg.mini_nsf && (!rand_ini || !noise))
         return fail(h, DSD_EINVAL, "%s: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)", who);
@@ -2933,8 +2926,8 @@ int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int
 
 int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,
                    int64_t stride_t, float* out, const float* out_scale, const float* out_shift, void* stream) {
-    refresh_path_opts();
     if (!h || !cond || !out) return fail(h, DSD_EINVAL, "dsd_aux_decode: null argument");
+    h->opts = read_path_opts();
     if (!is_aux(h)) return fail(h, DSD_ESTATE, "dsd_aux_decode: this handle is a denoiser backbone");
     if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_aux_decode: weights are not finalized");
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_aux_decode: B and T must be positive (B=%d, T=%d)", B, T);
@@ -2957,7 +2950,7 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
     }
     for (int l = 0; l < L; ++l) {      // ConvNeXtBlock.forward   convnext.py:40-56
         e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev,
-                          h->blob + h->dw_w[l], h->blob + h->dw_b[l], 7, 3, nullptr, st);
+                          h->blob + h->dw_w[l], h->blob + h->dw_b[l], 7, 3, nullptr, h->opts.dwconv_rows, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
         e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, C, B, T, 0, h->stats, Ts, 1e-6f, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm stats launch failed: %s", hipGetErrorString(e));
@@ -2982,8 +2975,8 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
 }
 
 int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, float* out, void* stream) {
-    refresh_path_opts();
     if (!h || !x || !t || !out) return fail(h, DSD_EINVAL, "dsd_denoise: null argument");
+    h->opts = read_path_opts();
     if (!h->cond_ready) return fail(h, DSD_ESTATE, "dsd_denoise: call dsd_prepare_cond first");
     if (x == out) return fail(h, DSD_EINVAL, "dsd_denoise: out must not alias x");
     if (t_len != 1 && t_len != h->B) return fail(h, DSD_EINVAL, "dsd_denoise: t_len must be 1 or B=%d (got %d)", h->B, t_len);
@@ -2992,6 +2985,7 @@ int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, fl
     const int B = h->B, T = h->T, Ts = h->Ts, FM = FM_of(h);
     int rc = check_lens(h, "dsd_denoise", B, T, st);
     if (rc) return rc;
+    const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_emb(h, t_len))) return rc;
     HIP_OK(h, hipMemcpyAsync(h->t_dev, t, sizeof(float) * t_len, hipMemcpyDeviceToDevice, st));
     if ((rc = run_step_tables(h, t_len, st))) return rc;
@@ -3003,7 +2997,7 @@ int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, fl
     lo.nterms = 1;
     lo.t[0].ptr = nullptr;
     lo.t[0].coef = 1.f;
-    rc = run_backbone(h, h->io_in, 0, t_len == 1 ? 0 : 1, &lo, 1, st);
+    rc = run_backbone(h, pl, h->io_in, 0, t_len == 1 ? 0 : 1, &lo, 1, st);
     if (rc) return rc;
     e = launch_unpack(h->io_out, Ts, out, B, h->cfg.n_feats, h->cfg.in_dims, T, 0, nullptr, nullptr, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "unpack launch failed: %s", hipGetErrorString(e));
@@ -3012,8 +3006,8 @@ int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, fl
 
 int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, const float* noise, float* out,
                const float* out_scale, const float* out_shift, uint32_t flags, void* stream) {
-    refresh_path_opts();
     if (!h || !prog || !x_init || !out) return fail(h, DSD_EINVAL, "dsd_sample: null argument");
+    h->opts = read_path_opts();
     if (!h->cond_ready) return fail(h, DSD_ESTATE, "dsd_sample: call dsd_prepare_cond first");
     if (prog->n_bufs < 1 || prog->n_bufs > 64 || prog->n_evals < 0 || (prog->n_evals > 0 && !prog->evals))
         return fail(h, DSD_EINVAL, "dsd_sample: malformed program");
@@ -3041,6 +3035,7 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
     }
     int rc = check_lens(h, "dsd_sample", B, T, st);
     if (rc) return rc;
+    const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_state(h, prog->n_bufs, st))) return rc;
     if (prog->n_evals > 0 && (rc = ensure_emb(h, prog->n_evals))) return rc;
 
@@ -3085,7 +3080,7 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
                 }
             }
             const float* next_xin = i + 1 < prog->n_evals ? state_buf(h, prog->evals[i + 1].x_buf) : nullptr;
-            if ((r = run_backbone(h, state_buf(h, ev.x_buf), i, 0, lo, ev.n_out, s, next_xin))) return r;
+            if ((r = run_backbone(h, pl, state_buf(h, ev.x_buf), i, 0, lo, ev.n_out, s, next_xin))) return r;
         }
         return r;
     };
@@ -3100,7 +3095,7 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
         key.append((const char*)&noise, sizeof(noise));
         key.append((const char*)&B, sizeof(B));             // batch shape: grids and strides are baked into the launches
         key.append((const char*)&T, sizeof(T));
-        key.append((const char*)&path_opts(), sizeof(PathOpts));   // the path switches: a graph is ONE set of launch choices
+        key.append((const char*)&h->opts, sizeof(PathOpts));      // the path switches: a graph is ONE set of launch choices
         key.append((const char*)&h->precision, sizeof(int));
         key.push_back(h->lens_host.empty() ? 'd' : 'r');       // dense / ragged: other kernels, and grids that follow
         for (int v : h->lens_host) key.append((const char*)&v, sizeof(v));      // the lengths (baked into the launches)
@@ -3194,7 +3189,6 @@ int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stre
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
     if (!h || !out) return DSD_EINVAL;
     memset(out, 0, sizeof(*out));
-    refresh_path_opts();
     const int64_t C = h->c_user ? h->c_user : C_of(h), M = FM_of(h), L = L_of(h);
     out->weight_bytes = (int64_t)h->blob_floats * 4;
     out->workspace_bytes = (int64_t)h->arena_floats * 4;
@@ -3212,33 +3206,24 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         // 2*(M*C + L*(3*C*2C + C*2C) + C*C + C*M); bytes L*24C + 2*4*M
         out->flops_per_frame_nfe = 2 * (M * C + L * (3 * C * 2 * C + C * 2 * C) + C * C + C * M);
         out->bytes_per_frame_nfe = L * 24 * C + 8 * M;
-        // around the layers: the edge kernel (skip projection, output projection + solver update, the next evaluation's input
-        // projection; wn_edge.hip) or the three GEMMs of gemm.hip
-        const int edge_env = edge_choice();
-        long t32 = (long)h->B * ((h->T + 31) / 32);
-        if (!h->lens_host.empty()) { t32 = 0; for (int v : h->lens_host) t32 += (v + 31) / 32; }
-        const bool edge = edge_env != 0 && wn_edge_supported(C_of(h), FM_of(h)) && h->arena && (edge_env == 1 || t32 >= 128);
-        std::vector<WnSeg> plan;
-        int per_layer = 2;                          // the row-split pair or the two GEMMs
-        const long tiles = wn_tiles32(h);
-        out->split_tiles = (int32_t)tiles;
-        if (h->arena && wn_plan_for(h, plan)) {
-            per_layer = 0;
-            out->split_tiles = 0;
-            for (const WnSeg& sg : plan) {
-                per_layer += sg.kind == WN_ROWSPLIT ? 2 : 1;
-                (sg.kind == WN_ROWSPLIT ? out->split_tiles : out->fused_tiles) += sg.nt;
-                if (sg.kind == WN_FUSED_X3) out->precision = DSD_PRECISION_BF16X3;
-            }
+        // the plan of the handle's last call (plan_denoise): segments, or the row-split pair / the two GEMMs per layer; around the
+        // layers the edge kernel (skip projection, output projection + solver update, the next evaluation's input projection;
+        // wn_edge.hip) or the three GEMMs of gemm.hip
+        const DenoisePlan pl = h->arena ? plan_denoise(h) : DenoisePlan();
+        out->layer_launches = pl.segs.empty() ? 2 : 0;
+        if (pl.segs.empty()) out->split_tiles = (int32_t)tiles_at(h, 32);
+        for (const WnSeg& sg : pl.segs) {
+            out->layer_launches += sg.kind == WN_ROWSPLIT ? 2 : 1;
+            (sg.kind == WN_ROWSPLIT ? out->split_tiles : out->fused_tiles) += sg.nt;
         }
-        out->layer_launches = per_layer;
-        out->kernels_per_nfe = per_layer * (int)L + (edge ? 1 : 3);
+        out->kernels_per_nfe = out->layer_launches * (int)L + (pl.edge ? 1 : 3);
+        if (pl.bf16x3()) out->precision = DSD_PRECISION_BF16X3;
     } else {
         const int64_t inner = inner_of(h), ks = h->cfg.kernel_size;
         out->flops_per_frame_nfe = 2 * (M * C + L * (C * 2 * inner + ks * inner + inner * C) + C * M);
         out->bytes_per_frame_nfe = L * 12 * C + 8 * M;
         out->kernels_per_nfe = 1 + 4 * (int)L + 2;
-        if (h->precision == 1 && !h->x3_conv.empty()) out->precision = DSD_PRECISION_BF16X3;
+        if (h->arena && plan_denoise(h).bf16x3()) out->precision = DSD_PRECISION_BF16X3;
     }
     out->graphs_cached = (int)h->graphs.size();
     return DSD_OK;

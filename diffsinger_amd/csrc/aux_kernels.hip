@@ -433,11 +433,10 @@ __global__ __launch_bounds__(256) void dwconv_rows_kernel(const float* __restric
 }
 
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
-                         const float* w, const float* bias, int ksz, int act, const float* prelu,
+                         const float* w, const float* bias, int ksz, int act, const float* prelu, int rows_form,
                          hipStream_t stream) {
     if (ksz > DW_MAXK || ksz < 1 || ksz % 2 == 0) return hipErrorInvalidValue;
-    const int rows_env = path_opts().dwconv_rows;      // 0: the first form (A/B)
-    if (rows_env != 0 && (ksz == 31 || ksz == 7)) {
+    if (rows_form != 0 && (ksz == 31 || ksz == 7)) {      // (rows_form = 0: the first form, A/B)
         const int nrows = B * C;
         if (ksz == 31)
             hipLaunchKernelGGL(dwconv_rows_kernel<31>, dim3((nrows + 3) / 4), dim3(256), 0, stream, src, dst, bstride, rstride, C, T,

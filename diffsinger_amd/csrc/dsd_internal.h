@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 namespace dsd {
 
 // ---------------------------------------------------------------------------------------------
@@ -36,34 +38,37 @@ enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_MISH = 2, ACT_GELU = 3, ACT_LRELU = 4
 #define DSD_ST_AUX 16
 #endif
 
-// Path switches (diagnostics, A/B runs, tests).  Every entry point of the C ABI that launches kernels re-reads them from the
-// environment ONCE (refresh_path_opts), so one process can drive either side of a switch through consecutive calls - this is
-// how tests/test_gpu_fused.py puts every instantiation of the layer kernels under oracle parity - and the values are part of
-// the hipGraph cache key (a captured graph is the launch sequence of ONE set of choices).  -1 = unset: the library's own rule.
+// Path switches (diagnostics, A/B runs, tests).  Each handle keeps its own snapshot (dsd_handle::opts): every entry point of the
+// C ABI that launches kernels takes a fresh one from the environment, so one process can drive either side of a switch through
+// consecutive calls - this is how tests/test_gpu_fused.py puts every instantiation of the layer kernels under oracle parity - and
+// dsd_get_stats reports from the snapshot of the handle's last call.  The snapshot is part of the hipGraph cache key (a captured
+// graph is the launch sequence of ONE set of choices).  -1 = unset: the library's own rule.  Launchers outside api.hip get the
+// switch they need as an argument.
 struct PathOpts {
-    int fused_layer;        // DSD_FUSED_LAYER     0: never wn_layer.hip, 1: on every supported grid
-    int fused16;            // DSD_FUSED16         0: never wn_layer16_kernel (16-frame tiles of the fused layer), 1: every layer on it
-    int wn_plan;            // DSD_WN_PLAN         0: one launch shape per layer (round 2), 1/unset: mixed plans (wn_plan_for)
-    int rowsplit;           // DSD_ROWSPLIT        0: never wn_rowsplit.hip
-    int rs_bn48;            // DSD_RS_BN48         0: no 48-frame tiles of the row-split pair
-    int rs_conv_q;          // DSD_RS_CONV_Q       0 / 1: K-half / K-quarter layout of the row-split conv
-    int rs_rows;            // DSD_RS_ROWS         64 / 128 / 256: rows per workgroup of the row-split pair
-    int rs_rows_out;        // DSD_RS_ROWS_OUT     128 / 256: ... of its out-proj launch alone (diagnostic: the two launches are independent)
-    int edge;               // DSD_EDGE            0: never wn_edge.hip, 1: on every grid
-    int lynx_resident;      // DSD_LYNX_RESIDENT   0: never lynx_layer.hip, 1: on every supported grid
-    int lynx_pw1p;          // DSD_LYNX_PW1P
-    int lynx_pw2d;          // DSD_LYNX_PW2D
-    int lynx_pw2q;          // DSD_LYNX_PW2Q       0: never the 128-row pw2 of one-utterance grids (gemm.hip instead), 1: on every grid
-    int narrow;             // DSD_NARROW          gemm.hip: 16-frame tiles off / on
-    int gm_shift;           // DSD_GM_SHIFT        gemm.hip: L2 blocking of the work order
-    int film_t;             // DSD_FILM_T          0: FiLM vectors from D [L*C][Ns] instead of the transposed table
-    int dwconv_rows;        // DSD_DWCONV_ROWS     0: the first depthwise-convolution kernel
-    int precision;          // DSD_PRECISION       1: split-bf16 (bf16x3) layer kernels where they exist (opt-in, own tolerance)
-    int x3_wide;            // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet kernels, 1: wherever they exist
-    long nb2_min;           // DSD_NB2_MIN_WG      gemm.hip: workgroups from which 64-frame tiles are used (default 512)
+    int fused_layer = -1;   // DSD_FUSED_LAYER     0: never wn_layer.hip, 1: on every supported grid
+    int fused16 = -1;       // DSD_FUSED16         0: never wn_layer16_kernel (16-frame tiles of the fused layer), 1: every layer on it
+    int wn_plan = -1;       // DSD_WN_PLAN         0: one launch shape per layer (no mixed plans, no wide row tiles; whole-layer 16-frame
+                            //                     fused tiles stay allowed), 1/unset: mixed plans (plan_denoise)
+    int rowsplit = -1;      // DSD_ROWSPLIT        0: never wn_rowsplit.hip
+    int rs_bn48 = -1;       // DSD_RS_BN48         0: no 48-frame tiles of the row-split pair
+    int rs_conv_q = -1;     // DSD_RS_CONV_Q       0 / 1: K-half / K-quarter layout of the row-split conv (launch_wn_rowsplit)
+    int rs_rows = -1;       // DSD_RS_ROWS         64 / 128 / 256: rows per workgroup of the row-split pair
+    int rs_rows_out = -1;   // DSD_RS_ROWS_OUT     128 / 256: ... of its out-proj launch alone (diagnostic: the two launches are independent)
+    int edge = -1;          // DSD_EDGE            0: never wn_edge.hip, 1: on every grid
+    int lynx_resident = -1; // DSD_LYNX_RESIDENT   0: never lynx_layer.hip, 1: on every supported grid
+    int lynx_pw1p = -1;     // DSD_LYNX_PW1P       0 / 1: pw1 with one workgroup per (frame tile, row tile) / per frame tile
+    int lynx_pw2d = -1;     // DSD_LYNX_PW2D       0: never the double-buffered pw2
+    int lynx_pw2q = -1;     // DSD_LYNX_PW2Q       0: never the 128-row pw2 of one-utterance grids (gemm.hip instead), 1: on every grid
+    int narrow = -1;        // DSD_NARROW          gemm.hip: 16-frame tiles off / on
+    int gm_shift = -1;      // DSD_GM_SHIFT        gemm.hip: L2 blocking of the work order
+    int film_t = -1;        // DSD_FILM_T          0: FiLM vectors from D [L*C][Ns] instead of the transposed table
+    int dwconv_rows = -1;   // DSD_DWCONV_ROWS     0: the first depthwise-convolution kernel (launch_dwconv)
+    int precision = -1;     // DSD_PRECISION       1: split-bf16 (bf16x3) layer kernels where they exist (opt-in, own tolerance)
+    int x3_wide = -1;       // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet kernels, 1: wherever they exist
+    int pad_ = 0;           // (explicit: no padding bytes - the struct's bytes are part of the hipGraph cache key)
+    long nb2_min = 512;     // DSD_NB2_MIN_WG      gemm.hip: workgroups from which 64-frame tiles are used (default 512)
 };
-const PathOpts& path_opts();
-void refresh_path_opts();
+static_assert(std::has_unique_object_representations<PathOpts>::value, "PathOpts has padding bytes (it is hashed as raw bytes)");
 
 // Timing hook of bench.py (dsd_kernel_timing): api.hip arms the slot with a start / stop event pair before a launch it wants
 // timed; the launcher that finds it armed goes through hipExtLaunchKernelGGL, which ties the two events to the dispatch
@@ -251,7 +256,7 @@ hipError_t wn_layer_init_all();
 // wn_rowsplit.hip: the same layer as two launches with the 2C rows split over 2C / 64 workgroups per 32-frame tile, for
 // grids too small for full-row tiles.  which = 0: conv + FiLM + gate (xin -> z); 1: out-proj + residual / skip (in place
 // when xout == xin)
-hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, hipStream_t st);
+hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, int conv_q, hipStream_t st);   // conv_q: DSD_RS_CONV_Q
 hipError_t wn_rowsplit_init_all();
 bool wn_rowsplit_supported(int C, int dil, long Ts);
 
@@ -331,12 +336,13 @@ struct LxLayerP {
     int ncg;
     int rt_groups;          // lx_pw1p_kernel: workgroups per frame tile, each looping over (2 inner / 512) / rt_groups row tiles (0 / 1: one)
 };
-hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, hipStream_t st);      // which: 0 = pw1, 1 = pw2
+// which: 0 = pw1, 1 = pw2;  pw1p / pw2d: DSD_LYNX_PW1P / DSD_LYNX_PW2D;  cus: compute units of the device (pw1's row-tile groups)
+hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw2d, int cus, hipStream_t st);
 bool lx_layer_supported(int C, int inner);
 hipError_t launch_lx_pw2q(const LxLayerP& p, int C, hipStream_t st);      // pw2 with 128 rows per workgroup: one-utterance grids
 bool lx_pw2q_supported(int C, int inner);
 hipError_t lx_layer_init_all();
-bool lx_pw1_merges_stats(const LxLayerP& p, int C);
+bool lx_pw1_merges_stats(int C, int inner, int nft, int pw1p, int cus);      // nft: frame tiles of the launch
 
 // lynx_x3.hip: the two pointwise GEMMs in split-bf16 arithmetic (opt-in precision mode); p.A1 / p.A2 = the layer's bf16x3 weight
 // streams [row tile][wave][k32 step][row block][hi | lo][lane][8 bf16]
@@ -440,6 +446,6 @@ hipError_t launch_enc_expand(const float* enc, const long long* mel2ph, const En
 hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T, int ts, float eps, float* stats,
                            hipStream_t stream);
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
-                         const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream);
+                         const float* w, const float* bias, int ksz, int act, const float* prelu, int rows_form, hipStream_t stream);  // rows_form: DSD_DWCONV_ROWS
 
 }  // namespace dsd

@@ -1115,16 +1115,9 @@ static hipError_t lx_launch_pw1p(const LxLayerP& p, int nwg, hipStream_t st) {
 // frame tile) - 1: all row tiles in one workgroup (lx_pw1p_kernel as in round 2), 2 / 4: half / a quarter of them, 0: one
 // workgroup per (frame tile, row tile) = lx_pw1_kernel.  By rounds of the chip: a workgroup takes ~11 us of prologue (statistics
 // merge, 128 KiB staging, launch ramp) + ~60 us per row tile (484 us at B = 8 for 8 row tiles, 254 for 4, 132 for 2); the
-// groups that fill whole rounds win - B = 2 / 4 / 6 at T = 1000: 4 / 2 / 4 groups.  DSD_LYNX_PW1P=0/1 forces none / one group.
-static int lx_pw1p_groups(int nft, int mtiles) {
-    const int force = path_opts().lynx_pw1p;
+// groups that fill whole rounds win - B = 2 / 4 / 6 at T = 1000: 4 / 2 / 4 groups.  force (DSD_LYNX_PW1P) = 0/1: none / one group.
+static int lx_pw1p_groups(int nft, int mtiles, int force, int cus) {
     if (force >= 0) return force != 0 ? 1 : 0;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
     int best = 0;
     double best_t = 1e30;
     for (int g = 1; g <= mtiles; g *= 2) {
@@ -1136,7 +1129,6 @@ static int lx_pw1p_groups(int nft, int mtiles) {
     }
     return best == mtiles ? 0 : best;                            // one row tile per workgroup: lx_pw1_kernel
 }
-static bool lx_use_pw1p(int nft, int mtiles) { return lx_pw1p_groups(nft, mtiles) > 0; }
 
 template <int KT, int RAG>
 static hipError_t lx_launch(const LxLayerP& p, int which, int nwg, hipStream_t st) {
@@ -1170,21 +1162,21 @@ static hipError_t lx_launch_pw2d(const LxLayerP& p, int nwg, hipStream_t st) {
 }
 
 // which = 0: pw1 (LayerNorm -> C -> 2 inner -> SwiGLU);  1: pw2 (inner -> C + residual + next-layer transition)
-hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, hipStream_t st) {
+hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw2d, int cus, hipStream_t st) {
     const int nft = p.cgmap ? p.ncg : p.nft;
     const int mtiles = which == 0 ? (2 * p.inner) / 512 : C / 512;
     const int nwg = nft * mtiles;
-    if (which == 0 && (nft == 0 || lx_use_pw1p(nft, mtiles))) {      // (nft == 0: attribute set-up of both forms at create)
+    const int groups = which == 0 && nft > 0 ? lx_pw1p_groups(nft, mtiles, pw1p, cus) : 0;
+    if (which == 0 && (nft == 0 || groups > 0)) {      // (nft == 0: attribute set-up of both forms at create)
         LxLayerP q = p;
-        q.rt_groups = nft == 0 ? 1 : lx_pw1p_groups(nft, mtiles);
+        q.rt_groups = nft == 0 ? 1 : groups;
         const int nwg1 = nft * q.rt_groups;
         hipError_t e = C == 1024 ? (q.cgmap ? lx_launch_pw1p<1024, 1>(q, nwg1, st) : lx_launch_pw1p<1024, 0>(q, nwg1, st))
                      : C == 512 ? (q.cgmap ? lx_launch_pw1p<512, 1>(q, nwg1, st) : lx_launch_pw1p<512, 0>(q, nwg1, st))
                                 : hipErrorInvalidValue;
         if (nft != 0 || e != hipSuccess) return e;
     }
-    // pw2 with double-buffered 512-channel half-phases (inner = 1024 or 2048); DSD_LYNX_PW2D=0: the two-phase form
-    const int pw2d = path_opts().lynx_pw2d;
+    // pw2 with double-buffered 512-channel half-phases (inner = 1024 or 2048); pw2d (DSD_LYNX_PW2D) = 0: the two-phase form
     if (which == 1 && pw2d != 0 && (p.inner == 2048 || p.inner == 1024) && (C == 1024 || C == 512)) {
         hipError_t e = p.inner == 2048 ? (p.cgmap ? lx_launch_pw2d<4, 1>(p, nwg, st) : lx_launch_pw2d<4, 0>(p, nwg, st))
                                        : (p.cgmap ? lx_launch_pw2d<2, 1>(p, nwg, st) : lx_launch_pw2d<2, 0>(p, nwg, st));
@@ -1197,10 +1189,9 @@ hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, hipStream_t st) 
 
 // true: launch_lx_layer(p, 0, ...) will take lx_pw1p_kernel, which merges the LayerNorm partials itself (p.lnpart_in): the
 // caller skips the ln_merge launch for this layer
-bool lx_pw1_merges_stats(const LxLayerP& p, int C) {
-    const int nft = p.cgmap ? p.ncg : p.nft;
+bool lx_pw1_merges_stats(int C, int inner, int nft, int pw1p, int cus) {
     if (DSD_LX_PW1_MERGE) return C == 512 || C == 1024;          // both forms of pw1 merge the partials in their prologue
-    return nft > 0 && (C == 512 || C == 1024) && lx_use_pw1p(nft, (2 * p.inner) / 512);
+    return nft > 0 && (C == 512 || C == 1024) && lx_pw1p_groups(nft, (2 * inner) / 512, pw1p, cus) > 0;
 }
 
 hipError_t lx_layer_init_all() {
@@ -1212,8 +1203,8 @@ hipError_t lx_layer_init_all() {
             p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
             p.ncg = 0;
             p.nft = 0;
-            if ((e = launch_lx_layer(p, 0, C, nullptr)) != hipSuccess) return e;
-            if ((e = launch_lx_layer(p, 1, C, nullptr)) != hipSuccess) return e;
+            if ((e = launch_lx_layer(p, 0, C, -1, -1, 256, nullptr)) != hipSuccess) return e;
+            if ((e = launch_lx_layer(p, 1, C, -1, -1, 256, nullptr)) != hipSuccess) return e;
             if ((e = launch_lx_pw2q(p, C, nullptr)) != hipSuccess) return e;
         }
     return hipSuccess;

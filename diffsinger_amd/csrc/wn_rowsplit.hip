@@ -772,7 +772,7 @@ int wn_rs_out_lds_bytes(int bn) { return (256 * 48 + 2 * 64 * (bn + 4)) * 4; }
 bool wn_rowsplit_supported(int C, int dil, long Ts) { return C == 256 && dil >= 1 && dil <= 16 && Ts < (1L << 22); }
 
 template <int SW, int RAG>
-static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, hipStream_t st) {
+static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int conv_q, hipStream_t st) {
     constexpr int HL = SW == 48 ? 8 : 16;
     static bool attr_done = false;
     if (!attr_done) {
@@ -788,10 +788,9 @@ static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, hipStream_t
         return launch_timed(wn_conv_rq_kernel<3, 80, HL, 0>, dim3(nwg), dim3(512), wn_rs_conv_lds_bytes(80, 48, true), st, p,
                             "wn_conv_rq_kernel<3, 80, %d, 0>", HL);
     }
-    // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two.  DSD_RS_CONV_Q=0/1
-    // forces the choice (A/B, tests).
-    const int q_ev = path_opts().rs_conv_q;                      // (tests/test_gpu_rowsplit.py switches it between handles)
-    const bool quarters = q_ev >= 0 ? q_ev != 0 : nwg <= 256;
+    // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two.  conv_q
+    // (DSD_RS_CONV_Q) = 0 / 1 forces the choice (A/B, tests).
+    const bool quarters = conv_q >= 0 ? conv_q != 0 : nwg <= 256;
     const int ldsb = wn_rs_conv_lds_bytes(SW, 32, quarters);
     if (quarters)
         return launch_timed(wn_conv_rq_kernel<2, SW, HL, RAG>, dim3(nwg), dim3(512), ldsb, st, p, "wn_conv_rq_kernel<2, %d, %d, %d>",
@@ -817,8 +816,8 @@ static hipError_t rs_launch_out(const WnLayerP& p, int nwg, int bn, hipStream_t 
 }
 
 // which = 0: conv + FiLM + gate (p.xin -> p.z);  which = 1: out-proj + residual / skip (p.z, p.xin -> p.xout, p.skip);
-// bn = frames per tile (32, or 48 on dense batches): p.tiles_per_b counts tiles of that width
-hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, int bn, hipStream_t st) {
+// bn = frames per tile (32, or 48 on dense batches): p.tiles_per_b counts tiles of that width;  conv_q: DSD_RS_CONV_Q (-1: by grid)
+hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, int bn, int conv_q, hipStream_t st) {
     if (C_ != 256 || (bn != 32 && bn != 48)) return hipErrorInvalidValue;
     // every store of a tile stays inside its row: the last tile of an item reaches column tiles_per_b * bn (48-frame tiles: up to
     // 47 past T), and rows are Ts = padded_ts(T) floats apart - holds for every T with the present padded_ts, checked here so that
@@ -827,8 +826,8 @@ hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, i
     const int nt = p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b);
     const int nwg = nt * 8;
     if (which == 1) return p.cgmap ? rs_launch_out<1>(p, nwg, bn, st) : rs_launch_out<0>(p, nwg, bn, st);
-    if (p.dil <= 8) return p.cgmap ? rs_launch_conv<48, 1>(p, nwg, bn, st) : rs_launch_conv<48, 0>(p, nwg, bn, st);
-    return p.cgmap ? rs_launch_conv<80, 1>(p, nwg, bn, st) : rs_launch_conv<80, 0>(p, nwg, bn, st);
+    if (p.dil <= 8) return p.cgmap ? rs_launch_conv<48, 1>(p, nwg, bn, conv_q, st) : rs_launch_conv<48, 0>(p, nwg, bn, conv_q, st);
+    return p.cgmap ? rs_launch_conv<80, 1>(p, nwg, bn, conv_q, st) : rs_launch_conv<80, 0>(p, nwg, bn, conv_q, st);
 }
 
 hipError_t wn_rowsplit_init_all() {
@@ -840,8 +839,8 @@ hipError_t wn_rowsplit_init_all() {
             p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;      // (no launch: the grid is empty)
             p.ncg = 0;
             p.tiles_per_b = 0;
-            if ((e = launch_wn_rowsplit(p, 0, 256, 0, 32, nullptr)) != hipSuccess) return e;
-            if ((e = launch_wn_rowsplit(p, 1, 256, 0, 32, nullptr)) != hipSuccess) return e;
+            if ((e = launch_wn_rowsplit(p, 0, 256, 0, 32, -1, nullptr)) != hipSuccess) return e;
+            if ((e = launch_wn_rowsplit(p, 1, 256, 0, 32, -1, nullptr)) != hipSuccess) return e;
         }
     return hipSuccess;
 }

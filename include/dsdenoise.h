@@ -443,13 +443,14 @@ typedef struct dsd_stats {
     int64_t bytes_per_frame_nfe; /* algorithmic HBM bytes per mel frame per NFE         */
     int32_t kernels_per_nfe;     /* kernel launches per backbone evaluation             */
     int32_t graphs_cached;
-    /* WaveNet, how a residual layer runs on the current batch shape (API v10): launches per layer (1 = the fused layer
-       kernel over every tile, 2 = the row-split pair or the two GEMMs, 3 = a mixed plan: the whole rounds of tiles on the
-       fused kernel, the remainder on the row-split pair) and how many 32-frame tiles each form covers */
+    /* The launch plan of the handle's last call, under the path switches of that call.  WaveNet, how a residual layer runs
+       on the current batch shape (API v10): launches per layer (1 = the fused layer kernel over every tile, 2 = the row-split
+       pair or the two GEMMs, 3 = a mixed plan: the whole rounds of tiles on the fused kernel, the remainder on the row-split
+       pair) and how many tiles each form covers - tiles of their segment's own width (16 or 32 frames) */
     int32_t layer_launches;
     int32_t fused_tiles;
     int32_t split_tiles;
-    int32_t precision;           /* DSD_PRECISION_* of the fused segments that ran (dsd_set_precision) */
+    int32_t precision;           /* DSD_PRECISION_BF16X3: the plan has a split-bf16 launch (dsd_set_precision), else F32 */
 } dsd_stats;
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out);
 

@@ -8,9 +8,6 @@
 #include <vector>
 #include "dsd_internal.h"
 namespace dsd {
-static PathOpts g_o = {};
-const PathOpts& path_opts() { return g_o; }
-void refresh_path_opts() {}
 TimingSlot& timing_slot() { static thread_local TimingSlot s; return s; }
 }
 using namespace dsd;
