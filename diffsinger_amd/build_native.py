@@ -18,7 +18,7 @@ HEADERS = [os.path.join(CSRC, "dsd_internal.h"), os.path.join(os.path.dirname(HE
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 FILE_FLAGS = {}           # per-file extra flags (none needed today; tools/check_resources.py and the stamp tools honour them)
-FLAGS += os.environ.get("DSD_EXTRA_HIPCC_FLAGS", "").split()      # diagnostic A/B builds (e.g. -DDSD_ST_AUX=0)
+FLAGS += os.environ.get("DSD_EXTRA_HIPCC_FLAGS", "").split()      # diagnostic builds (e.g. -DDSD_STAMPS)
 
 
 def _stale(target, deps):

@@ -44,24 +44,15 @@ PathOpts read_path_opts() {
     o.fused_layer = geti("DSD_FUSED_LAYER");
     o.wn_plan = geti("DSD_WN_PLAN");
     o.rowsplit = geti("DSD_ROWSPLIT");
-    o.rs_bn48 = geti("DSD_RS_BN48");
     o.rs_conv_q = geti("DSD_RS_CONV_Q");
     o.rs_rows = geti("DSD_RS_ROWS");
-    o.rs_rows_out = geti("DSD_RS_ROWS_OUT");
     o.edge = geti("DSD_EDGE");
     o.lynx_resident = geti("DSD_LYNX_RESIDENT");
     o.lynx_pw1p = geti("DSD_LYNX_PW1P");
-    o.lynx_pw2d = geti("DSD_LYNX_PW2D");
     o.lynx_pw2q = geti("DSD_LYNX_PW2Q");
-    o.narrow = geti("DSD_NARROW");
-    o.gm_shift = geti("DSD_GM_SHIFT");
-    o.film_t = geti("DSD_FILM_T");
-    o.dwconv_rows = geti("DSD_DWCONV_ROWS");
     o.precision = geti("DSD_PRECISION");
     o.fused16 = geti("DSD_FUSED16");
     o.x3_wide = geti("DSD_X3_WIDE");
-    const char* nb = getenv("DSD_NB2_MIN_WG");
-    if (nb && *nb) o.nb2_min = atol(nb);
     return o;
 }
 }  // namespace
@@ -1307,15 +1298,13 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     const int mtiles = g.pairC > 0 ? (g.pairC + 31) / 32 : (g.M + 63) / 64;
     // (a ragged vocoder batch: counted over its valid tiles, the shape B lone calls of similar length would take)
     const long wg64 = (vr ? (long)vr->ncg[2] : (long)batch * ((T + 63) / 64)) * mtiles;
-    const long nb2_min = h->opts.nb2_min;          // (DSD_NB2_MIN_WG: diagnostic override)
-    c.nb = wg64 >= nb2_min ? 2 : 1;
+    c.nb = wg64 >= 512 ? 2 : 1;
     // a conv on the generic path keeps all input channels resident: 64-frame tiles only while that fits in LDS
     if ((g.taps > 3 || (generic_only && g.taps > 1)) &&
         (size_t)g.K * (64 + 2 * round_up((g.taps / 2) * dil, 4) + 16) * 4 > 150 * 1024) c.nb = 1;
     // narrow tiles (64 rows x 16 frames, c.nb == 0): when 32-frame tiles would put at most ~1.5 workgroups on a CU,
     // twice as many half-size workgroups share each SIMD between two waves and halve the latency of a lone one
     if (c.nb == 1) {
-        const int force = h->opts.narrow;          // (DSD_NARROW: diagnostic override)
         const long wg32 = (long)batch * ((T + 31) / 32) * mtiles;
         int s16 = 16 + 2 * p.HL;
         while (s16 % 32 != 16) s16 += 4;
@@ -1330,7 +1319,7 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
         // <= 256 workgroups; narrow tiles beat that only while they too are one round (T <= 512 at B = 1: 13.0 ms; T = 768 took
         // 16.9 ms as 384 narrow workgroups)
         const bool small = rs_pair ? wg16 <= 256 : wg32 <= 192;
-        if (ok && !generic_only && (force == 1 || (force != 0 && (small || (wg32 <= 768 && load16 < load32))))) c.nb = 0;
+        if (ok && !generic_only && (small || (wg32 <= 768 && load16 < load32))) c.nb = 0;
     }
     const int BN = c.nb == 0 ? 16 : 32 * c.nb;
     p.tiles_per_b = (T + BN - 1) / BN;
@@ -1349,10 +1338,9 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     p.lpr_shift = 3;
     while ((1 << p.lpr_shift) < w4) ++p.lpr_shift;
     {   // L2 blocking of the work order for GEMMs with many row tiles (GemmP::gm_shift): groups of 8 row tiles
-        const int gm_env = h->opts.gm_shift;       // (DSD_GM_SHIFT: diagnostic override)
-        const int shift = gm_env >= 0 ? gm_env : 3;
+        constexpr int shift = 3;
         const long nft = ragged ? (long)p.ncg : (long)batch * p.tiles_per_b;
-        if (shift > 0 && mtiles >= (2 << shift) && mtiles % (1 << shift) == 0 && nft * mtiles >= 2048 && (nft << shift) < (1L << 22)) {
+        if (mtiles >= (2 << shift) && mtiles % (1 << shift) == 0 && nft * mtiles >= 2048 && (nft << shift) < (1L << 22)) {
             p.gm_shift = shift;
             p.per_group = (int)(nft << shift);
             p.inv_per_group = 1.0f / (float)p.per_group;
@@ -1410,7 +1398,6 @@ struct WnSeg {
     int kind, bn;       // launch shape, frames per tile
     int t0, nt;         // tiles [t0, t0 + nt) of the (item, frame tile) order at this width (ragged: of the valid-tile list)
     int rows;           // WN_ROWSPLIT: rows per workgroup - 64 (wn_rowsplit.hip), 128 or 256 (wn_rows.hip)
-    int rows_out;       // ... of the out-proj launch alone (DSD_RS_ROWS_OUT)
 };
 // LYNXNet's pointwise GEMMs: gemm.hip, lynx_layer.hip with the whole K extent resident (pw2: 512 rows per workgroup; LX_PW2Q:
 // 128 rows), lynx_x3.hip (split-bf16)
@@ -1590,9 +1577,7 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
     const PathOpts& o = h->opts;
     const int B = h->B, T = h->T, C = C_of(h);
     if (is_wavenet(h)) {
-        if (wn_segments(h, pl.segs)) {
-            for (WnSeg& sg : pl.segs) sg.rows_out = sg.rows > 64 && o.rs_rows_out > 64 ? o.rs_rows_out : sg.rows;
-        } else {
+        if (!wn_segments(h, pl.segs)) {
             const bool ragged = !h->lens_host.empty();
             for (int c = 0; c < std::min(h->cfg.dilation_cycle_length, L_of(h)); ++c) {
                 const int dil = 1 << c;
@@ -1601,9 +1586,8 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
                 const bool rs_ok = o.rowsplit != 0 && wn_rowsplit_supported(C, dil, h->Ts);
                 const GemmCall g = make_gemm(h, h->g_conv[c], nullptr, 0, h->Ts, B, T, ST_FILM, EP_GATE, dil, false, rs_ok);
                 // 48-frame tiles where they make a dense launch ONE round of workgroups and 32-frame tiles do not (T in
-                // (1024, 1536] at B = 1: 35-48 tiles of 32 frames = 280-384 workgroups for 256 CUs): 21.9 -> see DESIGN 4.2.
-                // DSD_RS_BN48=0: off
-                const bool bn48 = rs_ok && o.rs_bn48 != 0 && !ragged && (long)B * ((T + 31) / 32) * 8 > 256 &&
+                // (1024, 1536] at B = 1: 35-48 tiles of 32 frames = 280-384 workgroups for 256 CUs): 21.9 -> see DESIGN 4.2
+                const bool bn48 = rs_ok && !ragged && (long)B * ((T + 31) / 32) * 8 > 256 &&
                                   (long)B * ((T + 47) / 48) * 8 <= 256;
                 pl.layer[c].rs_bn = rs_ok && ((g.nb == 1 && g.fast) || bn48) ? (bn48 ? 48 : 32) : 0;
                 pl.layer[c].rs_pair = rs_ok;
@@ -1628,17 +1612,12 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
     // split-bf16 mode (lynx_x3.hip): both pointwise GEMMs as weight-stream-bound bf16x3 kernels; pw2 only where its C / 512
     // workgroups per frame tile fill at least half the chip (one utterance: the fp32 128-row kernel is faster) ... on 64-frame
     // tiles where those still fill the chip: the same weight stream then serves twice the frames.  Both fp32 forms of pw1 and
-    // the bf16x3 one merge their own frames' LayerNorm partials (lx_pw1_merges_stats).
+    // the bf16x3 one merge their own frames' LayerNorm partials: no LayerNorm-merge launch.
     const bool x3 = h->precision == 1 && !h->x3_conv.empty();
     const int xw = o.x3_wide;
-    if (x3) {
-        pl.pw1 = LX_X3;
-        pl.ln_merge = false;
-        pl.x3_ncb1 = xw != 0 && (xw == 1 || t64 * (2 * inner / 512) >= h->cus) ? 4 : 2;
-    } else {
-        pl.pw1 = LX_RESIDENT;
-        pl.ln_merge = !lx_pw1_merges_stats(C, inner, (int)t32, o.lynx_pw1p, h->cus);
-    }
+    pl.pw1 = x3 ? LX_X3 : LX_RESIDENT;
+    pl.ln_merge = false;
+    if (x3) pl.x3_ncb1 = xw != 0 && (xw == 1 || t64 * (2 * inner / 512) >= h->cus) ? 4 : 2;
     if (x3 && t32 * (C / 512) >= h->cus / 2) {
         pl.pw2 = LX_X3;
         pl.x3_ncb2 = xw != 0 && (xw == 1 || t64 * (C / 512) >= h->cus) ? 4 : 2;
@@ -1658,15 +1637,11 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
 }
 
 // Layer `layer`'s FiLM vector d[c] for step column col0 (+ colb per batch item): kernels read film[c * cstride + c0 + b * cb].
-// From the transposed table Dt [step][L * C] that is C contiguous floats (DSD_FILM_T=0: from D [L * C][Ns], one line per row - A/B)
+// From the transposed table Dt [step][L * C] that is C contiguous floats (run_step_tables: reading D [L * C][Ns] directly, one
+// cache line per row, was measured and removed)
 inline void film_of(const dsd_handle* h, int layer, int col0, int colb, const float*& film, int& cstride, int& c0, int& cb) {
-    const int transposed = h->opts.film_t != 0;
     const int C = C_of(h), LC = L_of(h) * C;
-    if (transposed) {
-        film = h->Dt + (long)layer * C; cstride = 1; c0 = col0 * LC; cb = colb * LC;
-    } else {
-        film = h->D + (long)layer * C * h->Ns; cstride = h->Ns; c0 = col0; cb = colb;
-    }
+    film = h->Dt + (long)layer * C; cstride = 1; c0 = col0 * LC; cb = colb * LC;
 }
 
 // step tables: E = sinemb(t) -> Hd = act(W0 E + b0) -> E2 = W1 Hd + b1 -> D[l*C + c][col] = Wd_l E2 + bd_l
@@ -1798,14 +1773,14 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         p.first_layer = (l == 0);
     };
     // the row-split pair (rows per workgroup: 64 = wn_rowsplit.hip, else wn_rows.hip) on the tiles of `p`; class keys 200 + v / 300 + v
-    auto rowsplit = [&](const WnLayerP& p, int bn, int rows, int rows_out, int v, double fr) {
+    auto rowsplit = [&](const WnLayerP& p, int bn, int rows, int v, double fr) {
         const int q = h->opts.rs_conv_q;
         int r = timed_launch(h, 200 + v, fl_conv * fr, 16.0 * C * fr, "row-split WaveNet layer", [&] {
             return rows > 64 ? launch_wn_rows(p, 0, C, B, rows, st) : launch_wn_rowsplit(p, 0, C, B, bn, q, st);
         });
         if (r) return r;
         return timed_launch(h, 300 + v, fl_out * fr, 20.0 * C * fr, "row-split WaveNet layer", [&] {
-            return rows > 64 ? launch_wn_rows(p, 1, C, B, rows_out, st) : launch_wn_rowsplit(p, 1, C, B, bn, q, st);
+            return rows > 64 ? launch_wn_rows(p, 1, C, B, rows, st) : launch_wn_rowsplit(p, 1, C, B, bn, q, st);
         });
     };
     if (!pl.segs.empty()) {
@@ -1834,7 +1809,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                     rc = timed_launch(h, 100 + vkey, (fl_conv + fl_out) * fr, 24.0 * C * fr, "fused WaveNet layer",
                                       [&] { return launch_wn_layer(p, C, B, st, sg.bn); });
                 } else {
-                    rc = rowsplit(p, sg.bn, sg.rows, sg.rows_out, vkey, fr);
+                    rc = rowsplit(p, sg.bn, sg.rows, vkey, fr);
                 }
                 if (rc) return rc;
             }
@@ -1851,7 +1826,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 layer_params(p, l, form.rs_bn);
                 p.xin = h->xh; p.xout = h->xh; p.z = h->z;
                 if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
-                if ((rc = rowsplit(p, form.rs_bn, 64, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
+                if ((rc = rowsplit(p, form.rs_bn, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
                 continue;
             }
             GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, ST_FILM, EP_GATE, dil, false, form.rs_pair);
@@ -1970,7 +1945,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             widen(q, pl.x3_ncb1);
             rc = timed_launch(h, 650 + (pl.x3_ncb1 == 4 ? 1 : 0), fl1, by1, "LYNXNet pw1", [&] { return launch_lx_x3(q, 0, C, pl.x3_ncb1, st); });
         } else if (pl.pw1 == LX_RESIDENT) {
-            rc = timed_launch(h, 600, fl1, by1, "LYNXNet pw1", [&] { return launch_lx_layer(p, 0, C, o.lynx_pw1p, o.lynx_pw2d, h->cus, st); });
+            rc = timed_launch(h, 600, fl1, by1, "LYNXNet pw1", [&] { return launch_lx_layer(p, 0, C, o.lynx_pw1p, h->cus, st); });
         } else {
             GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_SWIGLU, 0);
             g.p.ln_stats = h->stats; g.p.ln_ts = Ts;
@@ -1980,7 +1955,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         if (rc) return rc;
         rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, ragged ? h->lens_dev : nullptr, h->blob + h->dw_w[l],
                                         h->blob + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
-                                        h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], o.dwconv_rows, st), "dwconv");
+                                        h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], st), "dwconv");
         if (rc) return rc;
         if (pl.pw2 == LX_X3) {
             LxLayerP q = p;
@@ -1988,7 +1963,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             widen(q, pl.x3_ncb2);
             rc = timed_launch(h, 660 + (pl.x3_ncb2 == 4 ? 1 : 0), fl2, by2, "LYNXNet pw2 (bf16x3)", [&] { return launch_lx_x3(q, 1, C, pl.x3_ncb2, st); });
         } else if (pl.pw2 == LX_RESIDENT) {
-            rc = timed_launch(h, 610, fl2, by2, "LYNXNet pw2", [&] { return launch_lx_layer(p, 1, C, o.lynx_pw1p, o.lynx_pw2d, h->cus, st); });
+            rc = timed_launch(h, 610, fl2, by2, "LYNXNet pw2", [&] { return launch_lx_layer(p, 1, C, o.lynx_pw1p, h->cus, st); });
         } else if (pl.pw2 == LX_PW2Q) {     // 128 rows per workgroup, C / 128 workgroups per frame tile (lynx_layer.hip, lx_pw2q_kernel)
             rc = timed_launch(h, 615, fl2, by2, "LYNXNet pw2 (128-row)", [&] { return launch_lx_pw2q(p, C, st); });
         } else {
@@ -2950,7 +2925,7 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
     }
     for (int l = 0; l < L; ++l) {      // ConvNeXtBlock.forward   convnext.py:40-56
         e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev,
-                          h->blob + h->dw_w[l], h->blob + h->dw_b[l], 7, 3, nullptr, h->opts.dwconv_rows, st);
+                          h->blob + h->dw_w[l], h->blob + h->dw_b[l], 7, 3, nullptr, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
         e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, C, B, T, 0, h->stats, Ts, 1e-6f, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm stats launch failed: %s", hipGetErrorString(e));

@@ -288,9 +288,9 @@ hipError_t launch_lynx_pre(float* x, float* xin, const float* cp, long cp_bstrid
 // ---------------------------------------------------------------------------------------------
 constexpr int DW_TT = 256;
 constexpr int DW_MAXK = 63;
-// KS > 0: kernel size known at compile time - the lane's (KS + 3)-float input window is pulled from LDS with
-// aligned 16-byte reads into registers once and the taps run on registers (k = 31: 9 LDS reads per lane instead
-// of 124); KS == 0: any odd k <= 63, taps read from LDS one by one.
+// Any odd k <= 63, taps read from LDS one by one; the sizes the models use (31, 7) run dwconv_rows_kernel below.  KS is always
+// 0: the instantiations with a compile-time KS > 0 (the lane's input window in registers) were the first form of those sizes
+// and went when dwconv_rows_kernel replaced it.
 template <int KS>
 __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                      long bstride, int rstride, int C, int T, const int* __restrict__ lens,
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ s
     const int Tb = lens ? lens[b] : T;                   // ragged batch: zero padding starts at this item's own length
     const int c = blockIdx.y * 4 + wave;                 // wave-uniform: weights and bias are scalar loads
     const int t0 = blockIdx.x * DW_TT;
-    const int ksz = KS > 0 ? KS : ksz_rt;
+    const int ksz = ksz_rt;
     const int pad = ksz >> 1;
     if (c < C) {
         const float* s = src + (long)b * bstride + (long)c * rstride;
@@ -320,26 +320,10 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ s
     for (int e = 0; e < 4; ++e) acc[e] = bv;
     const float* wc = w + (long)c * ksz;
     const float* r = &row[wave][lane * 4];
-    if constexpr (KS > 0) {
-        constexpr int NW = (KS + 3 + 3) / 4 * 4;         // window, rounded up to whole float4s (stays inside the row)
-        float win[NW];
+    for (int j = 0; j < ksz; ++j) {
+        const float wj = wc[j];
 #pragma unroll
-        for (int i = 0; i < NW; i += 4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(&r[i]);
-            win[i] = v[0]; win[i + 1] = v[1]; win[i + 2] = v[2]; win[i + 3] = v[3];
-        }
-#pragma unroll
-        for (int j = 0; j < KS; ++j) {
-            const float wj = wc[j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] += wj * win[j + e];
-        }
-    } else {
-        for (int j = 0; j < ksz; ++j) {
-            const float wj = wc[j];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] += wj * r[j + e];
-        }
+        for (int e = 0; e < 4; ++e) acc[e] += wj * r[j + e];
     }
     float* d = dst + (long)b * bstride + (long)c * rstride + t0 + lane * 4;
     const float slope = (act == 0) ? prelu[c] : 0.f;
@@ -361,8 +345,9 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ s
 // range check IS the zero padding (the descriptor covers exactly the item's valid frames: offsets before 0 wrap around and
 // offsets from Tb on read as 0, per dword), goes into the wave's own LDS row (two rows in turn: no workgroup barrier, the
 // four waves of a workgroup never meet), and the NEXT segment's loads are in flight while this one's taps run from
-// registers.  The first form above launches 16 k four-row workgroups of one segment each, stages with 4-byte loads and
-// meets at a barrier: 36.9 us per LYNXNet layer at B = 8 (131 MB at 3.5 TB/s) against this one's.
+// registers.  The first form (dwconv_kernel<31>, since removed) launched 16 k four-row workgroups of one segment each, staged
+// with 4-byte loads and met at a barrier: 36.9 us per LYNXNet layer at B = 8 (131 MB at 3.5 TB/s) against this one's (see
+// DESIGN.md section 6).
 template <int KS>
 __global__ __launch_bounds__(256) void dwconv_rows_kernel(const float* __restrict__ src, float* __restrict__ dst,
                                                           long bstride, int rstride, int C, int T, int nrows,
@@ -433,10 +418,9 @@ __global__ __launch_bounds__(256) void dwconv_rows_kernel(const float* __restric
 }
 
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
-                         const float* w, const float* bias, int ksz, int act, const float* prelu, int rows_form,
-                         hipStream_t stream) {
+                         const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream) {
     if (ksz > DW_MAXK || ksz < 1 || ksz % 2 == 0) return hipErrorInvalidValue;
-    if (rows_form != 0 && (ksz == 31 || ksz == 7)) {      // (rows_form = 0: the first form, A/B)
+    if (ksz == 31 || ksz == 7) {
         const int nrows = B * C;
         if (ksz == 31)
             hipLaunchKernelGGL(dwconv_rows_kernel<31>, dim3((nrows + 3) / 4), dim3(256), 0, stream, src, dst, bstride, rstride, C, T,
@@ -447,15 +431,8 @@ hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride
         return hipGetLastError();
     }
     dim3 grid((T + DW_TT - 1) / DW_TT, (C + 3) / 4, B);
-    if (ksz == 31)
-        hipLaunchKernelGGL(dwconv_kernel<31>, grid, dim3(256), 0, stream, src, dst, bstride, rstride, C, T, lens, w, bias, ksz,
-                           act, prelu);
-    else if (ksz == 7)
-        hipLaunchKernelGGL(dwconv_kernel<7>, grid, dim3(256), 0, stream, src, dst, bstride, rstride, C, T, lens, w, bias, ksz,
-                           act, prelu);
-    else
-        hipLaunchKernelGGL(dwconv_kernel<0>, grid, dim3(256), 0, stream, src, dst, bstride, rstride, C, T, lens, w, bias, ksz,
-                           act, prelu);
+    hipLaunchKernelGGL(dwconv_kernel<0>, grid, dim3(256), 0, stream, src, dst, bstride, rstride, C, T, lens, w, bias, ksz, act,
+                       prelu);
     return hipGetLastError();
 }
 

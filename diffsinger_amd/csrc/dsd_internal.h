@@ -23,50 +23,34 @@ enum Stage { ST_PLAIN = 0, ST_FILM = 1, ST_LN = 2, ST_SCALE = 3, ST_LRELU = 4 };
 enum Epi { EP_BIAS_ACT = 0, EP_GATE = 1, EP_RESSKIP = 2, EP_LINCOMB = 3, EP_SWIGLU = 4, EP_BIAS_RES = 5, EP_SCATTER = 6, EP_LYNX_NEXT = 7 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_MISH = 2, ACT_GELU = 3, ACT_LRELU = 4, ACT_TANH = 5, ACT_SILU = 6 };
 
-// lx_pw1_kernel (LYNXNet pw1, one workgroup per (frame tile, row tile)) merges the LayerNorm partials in its prologue like
-// lx_pw1p_kernel does (1) or reads ln_merge_kernel's statistics (0: A/B builds)
-#ifndef DSD_LX_PW1_MERGE
-#define DSD_LX_PW1_MERGE 1
-#endif
-
 // Cache policy of the WaveNet layer kernels' 16-byte result stores (raw buffer intrinsics: bit 4 = sc1 = write-through).
 // A kernel boundary costs the bytes its predecessor left dirty in the L2s / ~6 TB/s (MI355X_MICROARCH.md, "boundary":
 // x + skip of a fused layer at B = 8 are 16 MB); write-through stores spread that over the kernel's own epilogues.
-// A/B on fresh boxes (tools/ab_bench.sh; -DDSD_ST_AUX=0 builds the plain form): 50-NFE loop 16.68 -> 16.55 ms at B = 1,
+// Measured against plain stores on fresh boxes (the plain form has since been removed): 50-NFE loop 16.68 -> 16.55 ms at B = 1,
 // 26.21 -> 25.79 at B = 2, 70.07 -> 69.00 at B = 8, the variance pair 37.54 -> 36.92; LYNXNet's kernels keep plain stores.
-#ifndef DSD_ST_AUX
-#define DSD_ST_AUX 16
-#endif
+constexpr int kStAux = 16;
 
-// Path switches (diagnostics, A/B runs, tests).  Each handle keeps its own snapshot (dsd_handle::opts): every entry point of the
-// C ABI that launches kernels takes a fresh one from the environment, so one process can drive either side of a switch through
-// consecutive calls - this is how tests/test_gpu_fused.py puts every instantiation of the layer kernels under oracle parity - and
-// dsd_get_stats reports from the snapshot of the handle's last call.  The snapshot is part of the hipGraph cache key (a captured
-// graph is the launch sequence of ONE set of choices).  -1 = unset: the library's own rule.  Launchers outside api.hip get the
-// switch they need as an argument.
+// Path switches (tests, diagnostics): each forces a form the library's own rule also chooses (DSD_PRECISION selects an
+// arithmetic mode).  Each handle keeps its own snapshot (dsd_handle::opts): every entry point of the C ABI that launches kernels
+// takes a fresh one from the environment, so one process can drive either side of a switch through consecutive calls - this is
+// how tests/test_gpu_fused.py puts every instantiation of the layer kernels under oracle parity - and dsd_get_stats reports
+// from the snapshot of the handle's last call.  The snapshot is part of the hipGraph cache key (a captured graph is the launch
+// sequence of ONE set of choices).  -1 = unset: the library's own rule.  Launchers outside api.hip get the switch they need as
+// an argument.
 struct PathOpts {
     int fused_layer = -1;   // DSD_FUSED_LAYER     0: never wn_layer.hip, 1: on every supported grid
     int fused16 = -1;       // DSD_FUSED16         0: never wn_layer16_kernel (16-frame tiles of the fused layer), 1: every layer on it
     int wn_plan = -1;       // DSD_WN_PLAN         0: one launch shape per layer (no mixed plans, no wide row tiles; whole-layer 16-frame
                             //                     fused tiles stay allowed), 1/unset: mixed plans (plan_denoise)
     int rowsplit = -1;      // DSD_ROWSPLIT        0: never wn_rowsplit.hip
-    int rs_bn48 = -1;       // DSD_RS_BN48         0: no 48-frame tiles of the row-split pair
     int rs_conv_q = -1;     // DSD_RS_CONV_Q       0 / 1: K-half / K-quarter layout of the row-split conv (launch_wn_rowsplit)
     int rs_rows = -1;       // DSD_RS_ROWS         64 / 128 / 256: rows per workgroup of the row-split pair
-    int rs_rows_out = -1;   // DSD_RS_ROWS_OUT     128 / 256: ... of its out-proj launch alone (diagnostic: the two launches are independent)
     int edge = -1;          // DSD_EDGE            0: never wn_edge.hip, 1: on every grid
     int lynx_resident = -1; // DSD_LYNX_RESIDENT   0: never lynx_layer.hip, 1: on every supported grid
     int lynx_pw1p = -1;     // DSD_LYNX_PW1P       0 / 1: pw1 with one workgroup per (frame tile, row tile) / per frame tile
-    int lynx_pw2d = -1;     // DSD_LYNX_PW2D       0: never the double-buffered pw2
     int lynx_pw2q = -1;     // DSD_LYNX_PW2Q       0: never the 128-row pw2 of one-utterance grids (gemm.hip instead), 1: on every grid
-    int narrow = -1;        // DSD_NARROW          gemm.hip: 16-frame tiles off / on
-    int gm_shift = -1;      // DSD_GM_SHIFT        gemm.hip: L2 blocking of the work order
-    int film_t = -1;        // DSD_FILM_T          0: FiLM vectors from D [L*C][Ns] instead of the transposed table
-    int dwconv_rows = -1;   // DSD_DWCONV_ROWS     0: the first depthwise-convolution kernel (launch_dwconv)
     int precision = -1;     // DSD_PRECISION       1: split-bf16 (bf16x3) layer kernels where they exist (opt-in, own tolerance)
     int x3_wide = -1;       // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet kernels, 1: wherever they exist
-    int pad_ = 0;           // (explicit: no padding bytes - the struct's bytes are part of the hipGraph cache key)
-    long nb2_min = 512;     // DSD_NB2_MIN_WG      gemm.hip: workgroups from which 64-frame tiles are used (default 512)
 };
 static_assert(std::has_unique_object_representations<PathOpts>::value, "PathOpts has padding bytes (it is hashed as raw bytes)");
 
@@ -317,8 +301,9 @@ struct LxLayerP {
     const float* A2;        // packed pw2 weights
     const float* bias2;     // [C]
     const float* xin;       // pw1 input: the layer's pre-LayerNorm activations [B][C][Ts]
-    const float* stats;     // [B][2][Ts]: mean, rstd per frame (ln_merge_kernel) - lx_pw1_kernel
-    const float* lnpart_in; // the producer's LayerNorm partials of xin (same layout as lnpart) - lx_pw1p_kernel merges them itself
+    const float* stats;     // [B][2][Ts]: mean, rstd per frame (ln_merge_kernel) - read by no kernel since both pw1 forms merge
+    const float* lnpart_in; // the producer's LayerNorm partials of xin (same layout as lnpart) - lx_pw1_kernel / lx_pw1p_kernel
+                            // merge them themselves
     float* u;               // pw1 output [B][inner][Ts]
     const float* v;         // pw2 input (depthwise conv output) [B][inner][Ts]
     float* x;               // residual stream [B][C][Ts]: read and replaced by pw2
@@ -336,13 +321,12 @@ struct LxLayerP {
     int ncg;
     int rt_groups;          // lx_pw1p_kernel: workgroups per frame tile, each looping over (2 inner / 512) / rt_groups row tiles (0 / 1: one)
 };
-// which: 0 = pw1, 1 = pw2;  pw1p / pw2d: DSD_LYNX_PW1P / DSD_LYNX_PW2D;  cus: compute units of the device (pw1's row-tile groups)
-hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw2d, int cus, hipStream_t st);
+// which: 0 = pw1, 1 = pw2;  pw1p: DSD_LYNX_PW1P;  cus: compute units of the device (pw1's row-tile groups)
+hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int cus, hipStream_t st);
 bool lx_layer_supported(int C, int inner);
 hipError_t launch_lx_pw2q(const LxLayerP& p, int C, hipStream_t st);      // pw2 with 128 rows per workgroup: one-utterance grids
 bool lx_pw2q_supported(int C, int inner);
 hipError_t lx_layer_init_all();
-bool lx_pw1_merges_stats(int C, int inner, int nft, int pw1p, int cus);      // nft: frame tiles of the launch
 
 // lynx_x3.hip: the two pointwise GEMMs in split-bf16 arithmetic (opt-in precision mode); p.A1 / p.A2 = the layer's bf16x3 weight
 // streams [row tile][wave][k32 step][row block][hi | lo][lane][8 bf16]
@@ -446,6 +430,6 @@ hipError_t launch_enc_expand(const float* enc, const long long* mel2ph, const En
 hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T, int ts, float eps, float* stats,
                            hipStream_t stream);
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
-                         const float* w, const float* bias, int ksz, int act, const float* prelu, int rows_form, hipStream_t stream);  // rows_form: DSD_DWCONV_ROWS
+                         const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream);
 
 }  // namespace dsd

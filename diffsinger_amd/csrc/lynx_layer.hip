@@ -6,7 +6,7 @@
 // MFMA peak on these shapes; the resident walk of wn_layer.hip runs at 33 cycles per MFMA.)
 //
 //   lx_pw1_kernel : u = out * silu(gate),  [out; gate] = W1 LayerNorm(xin) + b1      (LN affine folded into W1 / b1;
-//                   per-frame (mean, rstd) from ln_merge_kernel applied while the tile is staged)
+//                   per-frame (mean, rstd) merged from the producer's LayerNorm partials, applied while the tile is staged)
 //   lx_pw2_kernel : v = W2 u' + b2 + x  (residual), then the NEXT layer's transition exactly as gemm.hip's EP_LYNX_NEXT:
 //                   strong: x = v + cpn, xin = x + d;  else: x = v, xin = v + cpn + d;  no next layer: x = xin = v;
 //                   plus the LayerNorm partials (mean, sum of squared deviations) of xin per 64-row tile and frame.
@@ -49,14 +49,9 @@ __device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int sof
 __device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {
     dsd_store_b128<0>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);      // plain: the next kernel re-reads these lines from L2 (write-through measured +0.5 %)
 }
-#ifndef DSD_LX_RCP
-#define DSD_LX_RCP 1
-#endif
 // SiLU's sigmoid: expf as the library computes it; the reciprocal as v_rcp_f32 (<= 1 ulp) instead of an IEEE division
 // sequence (~10 VALU instructions per element, 64 elements per lane and row tile in the SwiGLU epilogue)
-__device__ __forceinline__ float sigmoid_f(float v) {
-    return DSD_LX_RCP ? __builtin_amdgcn_rcpf(1.f + expf(-v)) : 1.f / (1.f + expf(-v));
-}
+__device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.f + expf(-v)); }
 
 constexpr int BN = 32;          // frames per tile
 constexpr int MBW = 8;          // 16-row blocks per wave: 128 rows, 512 per workgroup
@@ -189,15 +184,7 @@ __global__ __launch_bounds__(256, 1) void lx_pw1_kernel(const LxLayerP p) {
     const int c4 = tid & 7;                                      // the thread's frames 4 c4 .. 4 c4 + 3, for every staged row
     // (the 2 * inner / 512 row-tile workgroups of a frame tile each repeat this small merge: cheaper than a launch of its own)
     f32x4 mean, rstd;
-#if DSD_LX_PW1_MERGE
     lx_merge_stats<KT>(p, bu, t0u, c4, mean, rstd);
-#else
-    {
-        const __amdgpu_buffer_rsrc_t r_s = rsrc(p.stats + (long)bu * 2 * Ts + t0u);
-        mean = ld4(r_s, c4 * 16, 0);
-        rstd = ld4(r_s, c4 * 16, Ts * 4);
-    }
-#endif
     const __amdgpu_buffer_rsrc_t r_x = rsrc(p.xin + (long)bu * p.x_bstride + t0u);
     const __amdgpu_buffer_rsrc_t r_w = rsrc(p.A1 + (long)(MBW * 4 * mu + MBW * wave) * NS * 256);
     int wk[MBW];
@@ -816,10 +803,6 @@ __global__ __launch_bounds__(256, 1) void lx_pw2d_kernel(const LxLayerP p) {
 // quarters' partial sums meet in LDS over the dead buffers; the transition (bias, residual, the next layer's conditioner /
 // step projections; LayerNorm partials per 64-row tile) is lx_pw2d_kernel's, on 2 items per thread.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef DSD_LXQ_SPREAD
-#define DSD_LXQ_SPREAD 1
-#endif
-#if DSD_LXQ_SPREAD == 1
 #define LXQ_SPREAD()                                                                 \
     _Pragma("unroll") for (int g_ = 0; g_ < 8; ++g_) {                               \
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                           \
@@ -827,19 +810,6 @@ __global__ __launch_bounds__(256, 1) void lx_pw2d_kernel(const LxLayerP p) {
         __builtin_amdgcn_sched_group_barrier(0x080, 2, 0);                           \
     }                                                                                \
     __builtin_amdgcn_sched_barrier(0);
-#elif DSD_LXQ_SPREAD == 2
-#define LXQ_SPREAD()                                                                 \
-    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                               \
-    __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);                               \
-    _Pragma("unroll") for (int g_ = 0; g_ < 7; ++g_) {                               \
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);                           \
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                           \
-        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                           \
-    }                                                                                \
-    __builtin_amdgcn_sched_barrier(0);
-#else
-#define LXQ_SPREAD() __builtin_amdgcn_sched_barrier(0);
-#endif
 
 template <int KQ, int RAG>
 __global__ __launch_bounds__(512, 1) void lx_pw2q_kernel(const LxLayerP p) {
@@ -1162,7 +1132,7 @@ static hipError_t lx_launch_pw2d(const LxLayerP& p, int nwg, hipStream_t st) {
 }
 
 // which = 0: pw1 (LayerNorm -> C -> 2 inner -> SwiGLU);  1: pw2 (inner -> C + residual + next-layer transition)
-hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw2d, int cus, hipStream_t st) {
+hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int cus, hipStream_t st) {
     const int nft = p.cgmap ? p.ncg : p.nft;
     const int mtiles = which == 0 ? (2 * p.inner) / 512 : C / 512;
     const int nwg = nft * mtiles;
@@ -1176,8 +1146,8 @@ hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw
                                 : hipErrorInvalidValue;
         if (nft != 0 || e != hipSuccess) return e;
     }
-    // pw2 with double-buffered 512-channel half-phases (inner = 1024 or 2048); pw2d (DSD_LYNX_PW2D) = 0: the two-phase form
-    if (which == 1 && pw2d != 0 && (p.inner == 2048 || p.inner == 1024) && (C == 1024 || C == 512)) {
+    // pw2 with double-buffered 512-channel half-phases (inner = 1024 or 2048); lx_pw2_kernel's two-phase form for inner = 512
+    if (which == 1 && (p.inner == 2048 || p.inner == 1024) && (C == 1024 || C == 512)) {
         hipError_t e = p.inner == 2048 ? (p.cgmap ? lx_launch_pw2d<4, 1>(p, nwg, st) : lx_launch_pw2d<4, 0>(p, nwg, st))
                                        : (p.cgmap ? lx_launch_pw2d<2, 1>(p, nwg, st) : lx_launch_pw2d<2, 0>(p, nwg, st));
         if (nwg != 0 || e != hipSuccess) return e;
@@ -1185,13 +1155,6 @@ hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int pw
     if (C == 1024) return p.cgmap ? lx_launch<1024, 1>(p, which, nwg, st) : lx_launch<1024, 0>(p, which, nwg, st);
     if (C == 512) return p.cgmap ? lx_launch<512, 1>(p, which, nwg, st) : lx_launch<512, 0>(p, which, nwg, st);
     return hipErrorInvalidValue;
-}
-
-// true: launch_lx_layer(p, 0, ...) will take lx_pw1p_kernel, which merges the LayerNorm partials itself (p.lnpart_in): the
-// caller skips the ln_merge launch for this layer
-bool lx_pw1_merges_stats(int C, int inner, int nft, int pw1p, int cus) {
-    if (DSD_LX_PW1_MERGE) return C == 512 || C == 1024;          // both forms of pw1 merge the partials in their prologue
-    return nft > 0 && (C == 512 || C == 1024) && lx_pw1p_groups(nft, (2 * inner) / 512, pw1p, cus) > 0;
 }
 
 hipError_t lx_layer_init_all() {
@@ -1203,8 +1166,8 @@ hipError_t lx_layer_init_all() {
             p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
             p.ncg = 0;
             p.nft = 0;
-            if ((e = launch_lx_layer(p, 0, C, -1, -1, 256, nullptr)) != hipSuccess) return e;
-            if ((e = launch_lx_layer(p, 1, C, -1, -1, 256, nullptr)) != hipSuccess) return e;
+            if ((e = launch_lx_layer(p, 0, C, -1, 256, nullptr)) != hipSuccess) return e;
+            if ((e = launch_lx_layer(p, 1, C, -1, 256, nullptr)) != hipSuccess) return e;
             if ((e = launch_lx_pw2q(p, C, nullptr)) != hipSuccess) return e;
         }
     return hipSuccess;

@@ -49,7 +49,7 @@ __device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int sof
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
 }
 __device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {      // write-through: dsd_internal.h
-    dsd_store_b128<DSD_ST_AUX>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
+    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
 }
 
 // acc[k][n] += W[block k][:, K] * tile[K, column block n]: NS k16 steps, the wave's MB row blocks (1 KiB fragment blocks at

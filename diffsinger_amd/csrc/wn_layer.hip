@@ -37,17 +37,6 @@ __device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn
 __device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
 __device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
 
-// 1: the FiLM values of a thread's staging rows read from LDS in one batch, the late chunks written after step 9 and the barrier
-// taken after step 10 (as in wn_rowsplit.hip, finding (7) of DESIGN 4.2).  0: first version (A/B build).
-#ifndef DSD_WN_LATE
-#define DSD_WN_LATE 1
-#endif
-// 1: only step 0's weight blocks are part of the prologue's burst of loads (a CU issues one vector-memory wave-instruction per
-// ~50 cycles and the burst is the prologue's critical path); step 0 issues steps 1 and 2.  0: steps 0 and 1 in the prologue.
-#ifndef DSD_WN_RAMP
-#define DSD_WN_RAMP 1
-#endif
-
 #ifdef DSD_STAMPS
 // [workgroup][0..7]: s_memtime at the phase boundaries; [8], [9]: s_memrealtime (100 MHz) at the first and last stamp
 __device__ unsigned long long g_wn_stamps[4096][10];
@@ -142,7 +131,6 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
     // the late chunks' loads are all issued by step 8: one per step, or (the 80-float tile at C = 256: 12 late float4 per
     // thread) two on steps 1 .. 3 - which the step's schedule below gives a second slot
     constexpr int NLATE = NU - NU0;
-    constexpr bool EARLY_LATE = DSD_WN_LATE && NLATE <= 12;
     constexpr int NDBL = NLATE > 9 ? NLATE - 9 : 0;              // steps 1 .. NDBL carry two late loads
     static_assert(NDBL <= 3, "late loads: at most two on steps 1 .. 3, one on the others up to step 8");
     f32x4 sv[NU];
@@ -173,28 +161,22 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
 #pragma unroll
         for (int k = 0; k < MBW; ++k) dst[k] = ld4(r_w2, wk2[k] + (s & 3) * 1024, (s >> 2) * 4096);
     };
+    // Only step 0's weight blocks are part of the prologue's burst of loads (a CU issues one vector-memory wave-instruction per
+    // ~50 cycles and the burst is the prologue's critical path); step 0 issues steps 1 and 2.  (Steps 0 and 1 in the prologue
+    // were measured against this and removed.)
     load_w1(W[0], 0);
-#if !DSD_WN_RAMP
-    load_w1(W[1], 1);
-#endif
     WN_STAMP(1);
     // FiLM vector -> LDS (the staging region is free until the gate), so each thread can pick the scalars of its rows
     es[tid] = fmine;                                             // (threads beyond C: a copy of the last channel's, unused)
     __syncthreads();
     // FiLM add, then the zero padding (wavenet.py:36-38: the pad is applied to x + d), then LDS
-#if DSD_WN_LATE
     float fav[NU];                                               // one batch of LDS reads, not one round trip per float4 staged
 #pragma unroll
     for (int u = 0; u < NU; ++u) fav[u] = es[(tid + 256 * u) / W4];
-#endif
     auto stage_write = [&](int u) {
         const int idx = tid + 256 * u;
         const int row = idx / W4, c4 = idx - row * W4;
-#if DSD_WN_LATE
         const float fa = fav[u];
-#else
-        const float fa = es[row];
-#endif
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -251,7 +233,7 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                           \
     }                                                                                \
     __builtin_amdgcn_sched_barrier(0);
-    // step 0 of a ramped ring issues TWO steps' weights (DSD_WN_RAMP): two loads behind every 8 MFMAs
+    // step 0 issues TWO steps' weights (the prologue holds step 0's alone): two loads behind every 8 MFMAs
 #define WN_SPREAD2()                                                                 \
     __builtin_amdgcn_sched_group_barrier(0x008, 2 * NCB, 0);                               \
     __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                               \
@@ -293,58 +275,47 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
     __builtin_amdgcn_sched_barrier(0);
     auto conv_step = [&](int s) {
         // step s + 2: a conv step, or one of the out-proj's first two blocks behind the last conv steps
-        if (DSD_WN_RAMP && s == 0) load_w1(W[1], 1);           // (only step 0's weights are in the prologue burst)
+        if (s == 0) load_w1(W[1], 1);                           // (only step 0's weights are in the prologue burst)
         if (s + 2 < NS1) load_w1(W[(s + 2) % 3], s + 2);
         else load_w2(W[(s + 2) % 3], s + 2 - NS1);
         // the step's one extra operand load: the rest of the x tile first, then the conditioner projection (filter rows sit
         // C rows below the gate rows), then the out-proj bias
-        if (EARLY_LATE && NDBL > 0 && s <= 8) {
+        if (NDBL > 0 && s <= 8) {
             // late slot index of step s: 0 at step 0, then two per step on steps 1 .. NDBL, one per step after
             const int first = s == 0 ? 0 : (s <= NDBL ? 2 * s - 1 : s + NDBL);
             const int cnt = s == 0 ? 1 : (s <= NDBL ? 2 : 1);
             if (first < NLATE) sv[NU0 + first] = ld4(r_x, x_voff(NU0 + first), 0);
             if (cnt == 2 && first + 1 < NLATE) sv[NU0 + first + 1] = ld4(r_x, x_voff(NU0 + first + 1), 0);
-        } else if (!(EARLY_LATE && NDBL > 0) && s < NLATE)
+        } else if (NDBL == 0 && s < NLATE)
             sv[NU0 + s] = ld4(r_x, x_voff(NU0 + s), 0);
         else if (s >= 12 && s < 12 + NE)          // (one chain of else-ifs: as separate ifs hipcc no longer folds the register arrays' indices)
             cpv[s - 12] = ld4(r_c, ev0, (((s - 12) % (NE / 2)) * RPM + (s - 12 >= NE / 2 ? C : 0)) * Ts * 4);
         else if (s >= 12 + NE && s < 12 + NE + MBW)
             bo[s - 12 - NE] = ld4(r_b, rq * 4, (s - 12 - NE) * 64);
-        if (EARLY_LATE || s != 11) read_b1(bq[(s + 1) & 1], s + 1 < NS1 ? s + 1 : 0);      // (after the last step: unused)
+        read_b1(bq[(s + 1) & 1], s + 1 < NS1 ? s + 1 : 0);      // (after the last step: unused)
         mfma_step(W[s % 3], bq[s & 1]);
-        if (DSD_WN_RAMP && s == 0) {
+        if (s == 0) {
             WN_SPREAD2()
-        } else if (EARLY_LATE && NDBL > 0 && s >= 1 && s <= NDBL) {
+        } else if (NDBL > 0 && s >= 1 && s <= NDBL) {
             WN_SPREAD3()
         } else {
             WN_SPREAD()
         }
     };
-    if constexpr (EARLY_LATE) {
-        // chunks 1.. of the x tile are read from step 12 on and their loads ride behind steps 0 .. 8: written after step 9, the
-        // workgroup meets after step 10, step 11 fetches step 12's operands in its normal slot
+    // chunks 1.. of the x tile are read from step 12 on and their loads ride behind steps 0 .. 8: written after step 9, the
+    // workgroup meets after step 10, step 11 fetches step 12's operands in its normal slot (as in wn_rowsplit.hip, finding (7)
+    // of DESIGN 4.2; the first version - late chunks written right before step 12, FiLM values read from LDS one round trip per
+    // staged float4 - was measured against this and removed)
 #pragma unroll
-        for (int s = 0; s < 10; ++s) conv_step(s);
+    for (int s = 0; s < 10; ++s) conv_step(s);
 #pragma unroll
-        for (int u = NU0; u < NU; ++u) stage_write(u);
-        __builtin_amdgcn_sched_barrier(0);
-        conv_step(10);
-        __syncthreads();
-        __builtin_amdgcn_sched_barrier(0);
+    for (int u = NU0; u < NU; ++u) stage_write(u);
+    __builtin_amdgcn_sched_barrier(0);
+    conv_step(10);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int s = 11; s < NS1; ++s) conv_step(s);
-    } else {
-        // (the 80-float tile's late loads ride behind steps 0 .. 11: written right before they are read)
-#pragma unroll
-        for (int s = 0; s < 12; ++s) conv_step(s);
-#pragma unroll
-        for (int u = NU0; u < NU; ++u) stage_write(u);
-        __syncthreads();
-        read_b1(bq[0], 12);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 12; s < NS1; ++s) conv_step(s);
-    }
+    for (int s = 11; s < NS1; ++s) conv_step(s);
     static_assert(12 + NE + MBW <= NS1, "one extra operand load per step");
     WN_STAMP(3);
 
@@ -446,7 +417,7 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[m][e] : 0.f) + a4[e]) * scale;
-            dsd_store_b128<DSD_ST_AUX>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * RPM * Ts * 4);
+            dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * RPM * Ts * 4);
         }
     }
     WN_STAMP(6);

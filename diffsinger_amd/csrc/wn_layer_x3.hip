@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void wn_layer_x3_kernel(const WnLayerP p) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[m][e] : 0.f) + a4[e]) * scale;
-            dsd_store_b128<DSD_ST_AUX>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * 8 * Ts * 4);
+            dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * 8 * Ts * 4);
         }
     }
 }

@@ -43,7 +43,7 @@ __device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int sof
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {       // x / skip: write-through
-    dsd_store_b128<DSD_ST_AUX>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
+    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
 }
 __device__ __forceinline__ void st4z(f32x4 v, dsd_i32x4 r, int voff, int soff) {      // z: read back by the next launch
     dsd_store_b128<0>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
@@ -74,10 +74,7 @@ __device__ __forceinline__ f32x4 rw_mfma(float wfrag, float xfrag, f32x4 acc) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag, xfrag, acc, 0, 0, 0);
 }
 
-#ifndef DSD_RW_ES
-#define DSD_RW_ES 36
-#endif
-constexpr int NCH = 4, C = 256, BN = 32, ES = DSD_RW_ES, B4 = 8;
+constexpr int NCH = 4, C = 256, BN = 32, ES = 36, B4 = 8;
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 }  // namespace
@@ -104,10 +101,7 @@ __global__ __launch_bounds__(512, 1) void wn_conv_rw_kernel(const WnLayerP p) {
     static_assert(128 * W4 % 512 == 0 && NE <= 6, "whole float4 slots per thread; late rows: two per step during steps 0 .. 2");
     constexpr int NS = NCH * 12;                    // weight blocks per packed row block: [chunk][tap][k16 in chunk]
     constexpr int NQ = 12;                          // steps per wave (one chunk)
-#ifndef DSD_RW_DW4
-#define DSD_RW_DW4 2
-#endif
-    constexpr int DW = MP == 4 ? DSD_RW_DW4 : 3;    // weight ring depth (step sets)
+    constexpr int DW = MP == 4 ? 2 : 3;             // weight ring depth (step sets)
     constexpr int LW = 3, LB = 4;                   // late rows: written after step LW, barrier after step LB, read from step 6 on
     constexpr int CPS = 7;                          // the conditioner projection's loads: steps CPS (gate rows), CPS + 1 (filter rows)
     constexpr int NG = MP / 2;                      // gate items (channel, float4) per thread: 32 MP channels x 8 / 512

@@ -48,16 +48,14 @@ __device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int sof
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
 }
 __device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<DSD_ST_AUX>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
+    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
 }
 // The conv's z is read back by the very next launch: kept in L2 (plain).  Same-box A/B of the 50-NFE loop at B = 1, three runs
-// each (tools/ab_store.sh): x / skip write-through + z plain 16.52 ms, both write-through 16.55, x / skip plain + z
-// write-through 16.70, both plain 16.67.
-#ifndef DSD_ST_AUX_Z
-#define DSD_ST_AUX_Z 0
-#endif
+// each: x / skip write-through + z plain 16.52 ms, both write-through 16.55, x / skip plain + z write-through 16.70, both
+// plain 16.67.
+constexpr int kStAuxZ = 0;
 __device__ __forceinline__ void st4z(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<DSD_ST_AUX_Z>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
+    dsd_store_b128<kStAuxZ>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
 }
 
 #ifdef DSD_STAMPS
@@ -79,88 +77,42 @@ __device__ unsigned long long g_rs_stamps[2][4096][40];      // [10 + s]: after 
 
 // Every field of the argument block in SGPRs behind ONE batch of scalar loads at the top of the kernel: left to itself the
 // compiler fetches them in two or three dependent batches (each a cold scalar-cache round trip) before the first vector load
-// can issue - on kernels whose whole life is 8-20 k cycles.  -DDSD_RS_PIN_ARGS=0: A/B build.
-#ifndef DSD_RS_FILM4
-#define DSD_RS_FILM4 1
-#endif
-#ifndef DSD_RS_PIN_ARGS
-#define DSD_RS_PIN_ARGS 1
-#endif
+// can issue - on kernels whose whole life is 8-20 k cycles.  (The unpinned form was measured against this and removed.)
 __device__ __forceinline__ void rs_pin_args(const WnLayerP& p) {
-#if DSD_RS_PIN_ARGS
     asm volatile("" ::"s"(p.Aconv), "s"(p.Aout), "s"(p.bias_out), "s"(p.xin), "s"(p.xout), "s"(p.skip), "s"(p.z), "s"(p.x_bstride),
                  "s"(p.Ts), "s"(p.cp), "s"(p.cp_bstride), "s"(p.film), "s"(p.film_cstride), "s"(p.film_col0), "s"(p.film_colb),
                  "s"(p.dil), "s"(p.T), "s"(p.tiles_per_b), "s"(p.first_layer), "s"(p.inv_tiles_per_b), "s"(p.tile0),
                  "s"((int)gridDim.x));                           // (the grid size is an implicit argument: same segment)
-#endif
 }
 
 // Weight fragments in rotation: step s runs from W[s % DEPTH], step s + DEPTH - 1 is in flight.  The prologue of these short
 // kernels is bound by how many wave-level loads a CU can issue before the walk starts, and DEPTH - 1 blocks per wave are part of
 // that burst: same-box scan of the 50-NFE loop at the headline (tools/ab_flags.sh) - depth 8: 16.08 ms, 6: 15.73, 5: 15.73,
 // 4: 15.37, 3: 15.28, 2: 15.55; with separate depths for the two kernels (3, 3) 15.29, (3, 2) 15.36, (4, 3) 15.31, (3, 4) 15.33;
-// depth 3 also wins at B = 2 (24.72 -> 24.02), T = 2048 (24.69 -> 23.96), T = 900 and on the pitch network (tools/ab_depth.sh).
-#ifndef DSD_RS_DEPTH
-#define DSD_RS_DEPTH 3
-#endif
+// depth 3 also wins at B = 2 (24.72 -> 24.02), T = 2048 (24.69 -> 23.96), T = 900 and on the pitch network.
+constexpr int DEPTH = 3;                      // ... of the conv kernel (24 steps per wave)
+constexpr int DEPTH_OUT = DEPTH;              // ... of the out-proj kernel (8 steps per wave)
 // (Tried: the two MFMA operand registers swapped - they have the same lane pattern, so D^T = X^T W^T needs no other change and a
 // lane's four accumulator values become four consecutive FRAMES of one row: the tails' LDS transposes are then one
 // ds_write_b128 per accumulator instead of four ds_write_b32, bit-identical results.  No effect on the loop time, here
 // (14.76 = 14.75 ms) or in the fused kernel's gate / epilogue (67.3 = 67.3 ms at B = 8): those phases are not LDS-issue bound.)
-#ifndef DSD_RS_DEPTH_OUT
-#define DSD_RS_DEPTH_OUT DSD_RS_DEPTH
-#endif
-// Conv: the late chunks go to LDS after local step DSD_RS_LATE_W and the workgroup meets after step DSD_RS_LATE_B; step 12 is
-// the first to read them and its operands are fetched during step 11 like any other step's.  (11, 11) is the first version:
-// write, barrier and step 12's LDS reads back to back, all of it exposed.  DSD_RS_FA_BATCH: the FiLM values of a thread's
-// staging rows are read from LDS in one batch (left inline, every ds_write_b128 waited for its own ds_read_b32 round trip).
-// Same-box A/B at the headline (tools/ab_flags.sh, ms per 50-NFE loop): first version 15.08; batch alone 14.99; batch +
-// (W, B) = (5, 10) 14.96, (8, 10) 14.97, (6, 7) 14.97, (4, 5) 14.97, (8, 8) 15.00.
-#ifndef DSD_RS_LATE_W
-#define DSD_RS_LATE_W 5
-#endif
-#ifndef DSD_RS_LATE_B
-#define DSD_RS_LATE_B 10
-#endif
-#ifndef DSD_RS_FA_BATCH
-#define DSD_RS_FA_BATCH 1
-#endif
+// Conv: the late chunks go to LDS after local step LATE_W and the workgroup meets after step LATE_B; step 12 is the first to
+// read them and its operands are fetched during step 11 like any other step's.  The FiLM values of a thread's staging rows
+// are read from LDS in one batch.  Measured and removed: the first version, (W, B) = (11, 11) - write, barrier and step 12's
+// LDS reads back to back, all of it exposed - with the FiLM values read inline (every ds_write_b128 waited for its own
+// ds_read_b32 round trip).  Same-box A/B at the headline (ms per 50-NFE loop): first version 15.08; batch alone 14.99; batch
+// + (W, B) = (5, 10) 14.96, (8, 10) 14.97, (6, 7) 14.97, (4, 5) 14.97, (8, 8) 15.00.
+constexpr int LATE_W = 5, LATE_B = 10;
 // (Measured and removed.  Out-proj: only the two 64-channel chunks that the first four steps of either K half read staged before
 // the walk, the other two written after step 1 behind a barrier after step 2 - the walk is 8 steps and the extra barrier costs
 // what the earlier start gains, 14.99 against 14.97 ms.  Both kernels: the loads spread over the walk's first steps - late x
 // chunks, conditioner projection, residual / skip operand - issued in the prologue right behind the first weight blocks:
 // 15.44 against 14.98 ms per loop, ten more wave-level loads per wave in the burst before the walk.)
-// The K-half conv's ring can RAMP: DEPTH - 1 blocks per wave in the prologue burst, then two blocks per step until
-// DSD_RS_DEPTH_MAX - 1 are in flight (= DEPTH: no ramp; measured equal for 4 .. 8).
-// Out-proj: 1 = one weight block less in the prologue's burst (DEPTH_OUT - 2), step 0 issues two (as the K-quarter conv does)
-#ifndef DSD_RS_OUT_RAMP
-#define DSD_RS_OUT_RAMP 1
-#endif
-#ifndef DSD_RS_DEPTH_MAX
-#define DSD_RS_DEPTH_MAX DSD_RS_DEPTH
-#endif
-// TIMING-ONLY diagnostic builds of the conv walk (wrong results): bit 0 no weight loads inside the walk, bit 1 no B-fragment
-// LDS reads inside the walk, bit 2 no late chunks (loads, LDS writes, barrier), bit 3 no conditioner-projection loads
-#ifndef DSD_RS_DIAG
-#define DSD_RS_DIAG 0
-#endif
-constexpr int DEPTH_OUT = DSD_RS_DEPTH_OUT;   // ... of the out-proj kernel (8 steps per wave)
-constexpr int DEPTH = DSD_RS_DEPTH;           // ... of the conv kernel (24 steps per wave)
-constexpr int DMAX = DSD_RS_DEPTH_MAX;
-static_assert(DMAX >= DEPTH, "the ring ramps up, not down");
-// blocks issued before local step s of an n-step walk: DEPTH - 1 in the prologue, then at most two per step and never past
-// block s + DMAX - 1 (whose slot the step before freed)
-constexpr int rs_issued_before(int s, int n) {
-    int c = DEPTH - 1;
-    for (int i = 0; i < s; ++i) {
-        int lim = i + DMAX;
-        if (lim > n) lim = n;
-        c = c + 2 < lim ? c + 2 : lim;
-    }
-    return c < n ? c : n;
-}
+// (Measured and removed: a K-half conv ring that RAMPS - DEPTH - 1 blocks per wave in the prologue burst, then two blocks per
+// step until more are in flight - equal for 4 .. 8 blocks.)
+// Out-proj: one weight block less in the prologue's burst (DEPTH_OUT - 2), step 0 issues two (as the K-quarter conv does).
 
-// the walk's steps with their index a constant expression (ring slots, the issue plan above)
+// the walk's steps with their index a constant expression (ring slots, the block each step issues)
 template <int I, int N, typename F>
 __device__ __forceinline__ void rs_static_for(F&& f) {
     if constexpr (I < N) {
@@ -241,12 +193,8 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
     // ---------------- prologue: the chunks the first 12 steps of either half read (0 and 2), FiLM vector, weights ----------------
     const __amdgpu_buffer_rsrc_t r_x = rsrc(p.xin + (long)bu * p.x_bstride + (t0u - HL));
     const __amdgpu_buffer_rsrc_t r_f = rsrc(p.film + p.film_col0 + bu * p.film_colb);
-#if DSD_RS_FILM4
     float fmine = 0.f;                                           // 256 values: the first four waves fetch them (wave-uniform branch)
     if (wave < 4) fmine = ld1(r_f, tid * p.film_cstride * 4, 0);
-#else
-    const float fmine = ld1(r_f, (tid & 255) * p.film_cstride * 4, 0);
-#endif
     // staging slot u of a thread: float4 (row, c4) of a 128-row set; `late` = 0: chunks 0 and 2 (rows [0,64) + [128,192)),
     // 1: chunks 1 and 3 - fetched one float4 per step behind the first steps' MFMAs, written to LDS after step 11
     auto x_row = [&](int u, int late) {
@@ -265,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
     // this wave's row block: packed block 4 * mtile + w (even: gate rows, odd: filter rows of 16 channels), steps [NH kh, +NH)
     const __amdgpu_buffer_rsrc_t r_w = rsrc(p.Aconv + ((long)(4 * mtile + w) * NS + NH * kh) * 256);
     const int wl = lane * 16;
-    f32x4 W[DMAX];
+    f32x4 W[DEPTH];
 #pragma unroll
     for (int s = 0; s < DEPTH - 1; ++s) W[s] = ld4(r_w, wl + (s & 3) * 1024, (s >> 2) * 4096);
     RS_PIN();
@@ -275,27 +223,17 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
     const __amdgpu_buffer_rsrc_t r_c = rsrc(p.cp + (long)bu * p.cp_bstride + t0u);
     f32x4 cpg = f32x4{0.f, 0.f, 0.f, 0.f}, cpf = cpg;
     RS_STAMP(0, 1);
-#if DSD_RS_FILM4
     if (wave < 4) et[tid] = fmine;
-#else
-    et[tid & 255] = fmine;
-#endif
     __syncthreads();
-#if DSD_RS_FA_BATCH
     float fa0[NE], fa1[NE];
 #pragma unroll
     for (int u = 0; u < NE; ++u) {
         fa0[u] = et[x_row(u, 0)];
         fa1[u] = et[x_row(u, 1)];
     }
-#endif
     auto stage_write = [&](const f32x4& v, int u, int late) {    // FiLM add, then the zero padding (wavenet.py:36-38), then LDS
         const int row = x_row(u, late), c4 = x_c4(u);
-#if DSD_RS_FA_BATCH
         const float fa = late ? fa1[u] : fa0[u];
-#else
-        const float fa = et[row];
-#endif
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -326,41 +264,38 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
     RS_PIN();
     rs_static_for<0, NH>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
-        const f32x4 wv = W[(DSD_RS_DIAG & 1) ? s % (DEPTH - 1) : s % DMAX];
-        float (&bc)[4][2] = bq[(DSD_RS_DIAG & 2) ? 0 : s & 1];
+        const f32x4 wv = W[s % DEPTH];
+        float (&bc)[4][2] = bq[s & 1];
         float (&bn)[4][2] = bq[(s + 1) & 1];
-        constexpr int nb0 = rs_issued_before(s, NH), nb1 = rs_issued_before(s + 1, NH);     // this step issues blocks [nb0, nb1)
+        constexpr int nb = s + DEPTH - 1;                        // this step issues block nb (its slot the step before freed)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc[0] = rs_mfma(wv[j], bc[j][0], acc[0]);
-            if (!(DSD_RS_DIAG & 1) && j < 2 && nb0 + j < nb1) W[(nb0 + j) % DMAX] = ld4(r_w, wl + ((nb0 + j) & 3) * 1024, ((nb0 + j) >> 2) * 4096);
-            if (!(DSD_RS_DIAG & 2) && j == 0 && !(DSD_RS_LATE_B == 11 && s == 11) && s + 1 < NH) {      // the next step's 4 LDS read pairs in one burst
+            if (j == 0 && nb < NH) W[nb % DEPTH] = ld4(r_w, wl + (nb & 3) * 1024, (nb >> 2) * 4096);
+            if (j == 0 && s + 1 < NH) {                          // the next step's 4 LDS read pairs in one burst
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) read_b1(bn, s + 1, jj);
             }
             RS_PIN();
             acc[1] = rs_mfma(wv[j], bc[j][1], acc[1]);
-            if (!(DSD_RS_DIAG & 4) && j == 0 && s < NE) svl[s] = ld4(r_x, row_ts(x_row(s, 1), Ts) + x_c4(s) * 16, 0);
-            if (!(DSD_RS_DIAG & 8) && j == 0 && s == 12) cpg = ld4(r_c, row_ts(gch, Ts) + (tid & 7) * 16, 0);
-            if (!(DSD_RS_DIAG & 8) && j == 0 && s == 13) cpf = ld4(r_c, row_ts(gch + C, Ts) + (tid & 7) * 16, 0);
+            if constexpr (s < NE)
+                if (j == 0) svl[s] = ld4(r_x, row_ts(x_row(s, 1), Ts) + x_c4(s) * 16, 0);
+            if (j == 0 && s == 12) cpg = ld4(r_c, row_ts(gch, Ts) + (tid & 7) * 16, 0);
+            if (j == 0 && s == 13) cpf = ld4(r_c, row_ts(gch + C, Ts) + (tid & 7) * 16, 0);
             RS_PIN();
         }
-        if (!(DSD_RS_DIAG & 4) && s == DSD_RS_LATE_W) {
+        if (s == LATE_W) {
 #pragma unroll
             for (int u = 0; u < NE; ++u) stage_write(svl[u], u, 1);
             RS_PIN();
         }
-        if (!(DSD_RS_DIAG & 4) && s == DSD_RS_LATE_B) {
+        if (s == LATE_B) {
             __syncthreads();
-            if (DSD_RS_LATE_B == 11) {                           // (first version: step 12's operands behind the barrier)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) read_b1(bn, 12, j);
-            }
             RS_PIN();
         }
         RS_STAMP(0, 10 + s);
     });
-    static_assert(DSD_RS_LATE_W >= 3 && DSD_RS_LATE_W <= DSD_RS_LATE_B && DSD_RS_LATE_B <= 11, "late chunks: read from step 12 on");
+    static_assert(LATE_W >= 3 && LATE_W <= LATE_B && LATE_B <= 10, "late chunks: read from step 12 on, fetched during step 11");
     RS_STAMP(0, 3);
 
     // ---------------- the two K halves' sums; accumulators -> LDS tile (rows [0, 32): gate, [32, 64): filter) ----------------
@@ -417,19 +352,10 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
     static_assert(128 * W4 % 512 == 0, "whole float4 slots per thread");
     constexpr int NS = NCH * 12;                    // weight blocks per packed row block: [chunk][tap][k16 in chunk]
     constexpr int NQ = 12;                          // steps per wave (one chunk)
-#ifndef DSD_RQ_LW
-#define DSD_RQ_LW 3
-#endif
-#ifndef DSD_RQ_LB
-#define DSD_RQ_LB 4
-#endif
-#ifndef DSD_RQ_CP
-#define DSD_RQ_CP 7
-#endif
-    constexpr int LW = DSD_RQ_LW, LB = DSD_RQ_LB;   // late rows: written after step LW, barrier after step LB, read from step 6 on
-    constexpr int CPS = DSD_RQ_CP;                  // the conditioner projection's two loads: steps CPS and CPS + 1
+    constexpr int LW = 3, LB = 4;                   // late rows: written after step LW, barrier after step LB, read from step 6 on
+    constexpr int CPS = 7;                          // the conditioner projection's two loads: steps CPS and CPS + 1
     static_assert(LW >= 2 && LW <= LB && LB <= 4 && CPS >= 2 && CPS <= 10, "step 5 fetches step 6's operands");
-    static_assert(NE <= 6 && DSD_RQ_LW >= 2, "the late rows are fetched two per step during steps 0 .. 2");
+    static_assert(NE <= 6, "the late rows are fetched two per step during steps 0 .. 2");
     float* xs = lds;                                 // [C][SW]
     float* et = lds + C * SW;                        // [4 quarters][64][ES]: FiLM vector first, the quarters' accumulators last
 
@@ -653,13 +579,10 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
     const __amdgpu_buffer_rsrc_t r_w = rsrc(p.Aout + ((long)(4 * mtile + w) * NS + NH * kh) * 256);
     const int wl = lane * 16;
     f32x4 W[DEPTH_OUT];
-#ifndef DSD_RS_BIAS_KH0
-#define DSD_RS_BIAS_KH0 1
-#endif
     f32x4 bo = f32x4{0.f, 0.f, 0.f, 0.f};                        // the bias rides in the first K half: only its waves fetch it
-    if (!DSD_RS_BIAS_KH0 || kh == 0) bo = ld4(rsrc(p.bias_out + orow), rq * 4, 0);
+    if (kh == 0) bo = ld4(rsrc(p.bias_out + orow), rq * 4, 0);
 #pragma unroll
-    for (int s = 0; s < DEPTH_OUT - 1 - DSD_RS_OUT_RAMP; ++s) W[s] = ld4(r_w, wl + (s & 3) * 1024, (s >> 2) * 4096);
+    for (int s = 0; s < DEPTH_OUT - 2; ++s) W[s] = ld4(r_w, wl + (s & 3) * 1024, (s >> 2) * 4096);
     RS_PIN();
     // residual stream (row tiles of the first C rows) or running skip sum (the other half), row-major float4:
     // thread (of the first 256) -> rows (tid >> 3) and 32 + (tid >> 3) of the tile, frames 4 * (tid & 7)
@@ -669,10 +592,7 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
     const __amdgpu_buffer_rsrc_t r_e = rsrc((const float*)(is_res ? xa : sa) + eoff);
     // (threads beyond the tile's 32 x B4 float4 per half: a copy of the last row's, unused)
     // 32-frame tiles: 64 rows x 8 float4 = one item per thread, all eight waves; 48-frame tiles: rows r and r + 32 per thread
-#ifndef DSD_RS_OUT_ITEMS1
-#define DSD_RS_OUT_ITEMS1 1
-#endif
-    constexpr int ITEMS = (DSD_RS_OUT_ITEMS1 && NCB == 2) ? 1 : 2, RP = 64 / ITEMS;
+    constexpr int ITEMS = NCB == 2 ? 1 : 2, RP = 64 / ITEMS;
     const int erow = min(div_b4<B4>(tid), RP - 1), ec4 = tid - div_b4<B4>(tid) * B4;
     const int ev0 = row_ts(erow, Ts) + ec4 * 16;
     f32x4 pre[2];
@@ -687,7 +607,7 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
 #pragma unroll
     for (int n = 0; n < NCB; ++n)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[n][r] = DSD_RS_BIAS_KH0 ? bo[r] : (kh == 0 ? bo[r] : 0.f);
+        for (int r = 0; r < 4; ++r) acc[n][r] = bo[r];
     const float* zt = zs + (kh * 128 + lrow) * SZ + lcol;
     float bq[2][4][NCB];
 #pragma unroll
@@ -703,9 +623,9 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc[0] = rs_mfma(wv[j], bc[j][0], acc[0]);
-            if (DSD_RS_OUT_RAMP && s == 0 && j == 0)             // (the prologue's burst holds one block less: step 0 issues two)
+            if (s == 0 && j == 0)                                // (the prologue's burst holds one block less: step 0 issues two)
                 W[DEPTH_OUT - 2] = ld4(r_w, wl + ((DEPTH_OUT - 2) & 3) * 1024, ((DEPTH_OUT - 2) >> 2) * 4096);
-            if (j == (DSD_RS_OUT_RAMP && s == 0 ? 1 : 0) && s + DEPTH_OUT - 1 < NH)
+            if (j == (s == 0 ? 1 : 0) && s + DEPTH_OUT - 1 < NH)
                 W[(s + DEPTH_OUT - 1) % DEPTH_OUT] = ld4(r_w, wl + ((s + DEPTH_OUT - 1) & 3) * 1024, ((s + DEPTH_OUT - 1) >> 2) * 4096);
             if (j == 0 && s + 1 < NH) {          // the next step's 4 LDS read pairs in one burst: spread one per MFMA pair
 #pragma unroll                                   // they cost the walk 12 % more (measured 5.0 k vs 4.45 k cycles)
