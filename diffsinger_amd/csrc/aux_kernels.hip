@@ -3,10 +3,9 @@
 // All of them are HBM/L2-bound streaming kernels: 64-wide wavefronts run along the time axis so
 // that every global access is a contiguous 256-B row segment.
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // pack: caller tensor (element (b, r, t) at src[b*sb + r*sr + t*st]) -> internal [B][R][Ts].

@@ -23,13 +23,6 @@ enum Stage { ST_PLAIN = 0, ST_FILM = 1, ST_LN = 2, ST_SCALE = 3, ST_LRELU = 4 };
 enum Epi { EP_BIAS_ACT = 0, EP_GATE = 1, EP_RESSKIP = 2, EP_LINCOMB = 3, EP_SWIGLU = 4, EP_BIAS_RES = 5, EP_SCATTER = 6, EP_LYNX_NEXT = 7 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_MISH = 2, ACT_GELU = 3, ACT_LRELU = 4, ACT_TANH = 5, ACT_SILU = 6 };
 
-// Cache policy of the WaveNet layer kernels' 16-byte result stores (raw buffer intrinsics: bit 4 = sc1 = write-through).
-// A kernel boundary costs the bytes its predecessor left dirty in the L2s / ~6 TB/s (MI355X_MICROARCH.md, "boundary":
-// x + skip of a fused layer at B = 8 are 16 MB); write-through stores spread that over the kernel's own epilogues.
-// Measured against plain stores on fresh boxes (the plain form has since been removed): 50-NFE loop 16.68 -> 16.55 ms at B = 1,
-// 26.21 -> 25.79 at B = 2, 70.07 -> 69.00 at B = 8, the variance pair 37.54 -> 36.92; LYNXNet's kernels keep plain stores.
-constexpr int kStAux = 16;
-
 // Path switches (tests, diagnostics): each forces a form the library's own rule also chooses (DSD_PRECISION selects an
 // arithmetic mode).  Each handle keeps its own snapshot (dsd_handle::opts): every entry point of the C ABI that launches kernels
 // takes a fresh one from the environment, so one process can drive either side of a switch through consecutive calls - this is
@@ -83,31 +76,12 @@ inline hipError_t launch_timed(K kern, dim3 grid, dim3 block, int lds, hipStream
     return hipGetLastError();
 }
 
-// 16-byte raw buffer store followed by two wait states, as ONE inline-asm statement.  A store of more than 8 bytes reads its
-// data registers over several cycles after issue, and a VALU write to one of them in the next issue slot can land first.
-// hipcc (ROCm 7.2) inserts the required wait state for the immediate-soffset form but not when soffset is a register - LLVM's
-// hazard model calls that form safe - and on gfx950 it is not: wn_out_rw_kernel<4, *> stored, nondeterministically and in
-// ~0.4 % of the elements, the NEXT item's operand as the first element of a vector (found with tools/harness/
-// rows_harness.hip; tools/check_store_hazard.py scans the ISA of every kernel file for the pattern, tests/
-// test_kernel_resources.py runs it).  A separate `s_nop` (builtin or asm) behind the builtin store does not stay there -
-// neither scheduling barriers nor a memory clobber kept the post-RA scheduler from moving VALU instructions in between -
-// so the store itself is asm.  `rsrc` = the four descriptor words (dsd_rsrc_words), wave-uniform.
-typedef unsigned dsd_u32x4 __attribute__((ext_vector_type(4)));
-typedef int dsd_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ dsd_i32x4 dsd_rsrc_words(const void* ptr) {
-    // (readfirstlane: the words must be in SGPRs for the asm's "s" operand - when the compiler cannot prove the pointer
-    // wave-uniform, or has spilled it to a VGPR, it would otherwise print a VGPR range into the descriptor slot)
-    const unsigned long long a = (unsigned long long)ptr;
-    return dsd_i32x4{__builtin_amdgcn_readfirstlane((int)(unsigned)a), __builtin_amdgcn_readfirstlane((int)(unsigned)((a >> 32) & 0xffffu)),
-                     (int)0x7FFFFFF0u, 0x00020000};
-}
-template <int AUX>
-__device__ __forceinline__ void dsd_store_b128(dsd_u32x4 data, dsd_i32x4 rsrc, int voff, int soff) {
-    static_assert(AUX == 0 || AUX == 16, "plain or sc1 (write-through)");
-    if (AUX == 16)
-        asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen sc1\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    else
-        asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" ::"v"(data), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+// The dynamic-LDS limit of every kernel instantiation is raised to all of gfx950's 160 KiB per CU, once per instantiation
+// and outside any stream capture (the *_init_all() functions; the launchers' attr_done flags).
+constexpr int kMaxDynLds = 160 * 1024;
+template <typename K>
+inline hipError_t allow_max_lds(K kern) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
 }
 
 constexpr int kMaxTerms = 8;
@@ -372,7 +346,6 @@ struct TConvP {
 int tconv_lds_bytes(int ci, int co, int taps, int SP);
 hipError_t tconv_init_all();
 hipError_t launch_tconv(const TConvP& p, int ci, int co, int batch, hipStream_t st);
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // vocoder_kernels.hip (NSF-HiFiGAN source, noise convs, residual-block average)
 hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w,
                              const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp, float noise_std,

@@ -5,10 +5,9 @@
 // length-regulator gather that expands token states to mel frames.  Activations use the internal layout
 // [batch][channel][Ls] (time innermost), lanes run along tokens / frames.
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // mel2ph_to_dur (tts_modules.py:344-350): dur[b][k] = #{t : mel2ph[b][t] == k + 1}.  Integer atomics: exact.

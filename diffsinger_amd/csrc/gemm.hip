@@ -27,13 +27,10 @@
 //     (gate, residual/skip), or straight from registers (bias+activation, SwiGLU, solver update).
 #include <hip/hip_ext.h>
 
-#include <type_traits>
-
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
@@ -46,35 +43,17 @@ __device__ __forceinline__ float act_apply(float v, int act) {
         default: return v;
     }
 }
-__device__ __forceinline__ float sigmoid_f(float v) { return 1.f / (1.f + expf(-v)); }
-// Gate nonlinearities on the hardware exp / rcp units (v_exp_f32, v_rcp_f32: ~1 ulp each).  Absolute error of
-// sigmoid(g) * tanh(f) stays below 3e-7 - far inside the 2e-5 per-evaluation parity tolerance - at a fifth of
-// the instruction count of libm's expf / tanhf (the gate is ~1 k cycles of a 23 k-cycle workgroup at B = 1).
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-__device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
+// SwiGLU's sigmoid on this path: an IEEE division (lynx_layer.hip / lynx_x3.hip use sigmoid_rcp, which rounds differently)
+__device__ __forceinline__ float sigmoid_ieee(float v) { return 1.f / (1.f + expf(-v)); }
 
 #ifdef DSD_STAMPS
 // Diagnostic build only (tools/stamp_profile.py): wave 0 of every workgroup records s_memtime at phase
 // boundaries into a buffer of its own; no output value depends on a stamp.
 __device__ unsigned long long g_stamps[8][4096][8];
-#define DSD_STAMP(i)                                                                              \
-    do {                                                                                          \
-        if (threadIdx.x == 0 && blockIdx.x < 4096) {                                              \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            g_stamps[EPI][blockIdx.x][i] = __builtin_amdgcn_s_memtime();                          \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-        }                                                                                         \
-    } while (0)
+#define DSD_STAMP(i) DSD_STAMP_AT(g_stamps[EPI][blockIdx.x][i])
 // finer stamps inside the first chunk pair of the pipelined K loop
 __device__ unsigned long long g_stamps2[8][4096][16];
-#define DSD_STAMP2(i)                                                                             \
-    do {                                                                                          \
-        if (threadIdx.x == 0 && blockIdx.x < 4096 && c == 0) {                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            g_stamps2[EPI][blockIdx.x][i] = __builtin_amdgcn_s_memtime();                         \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-        }                                                                                         \
-    } while (0)
+#define DSD_STAMP2(i) do { if (c == 0) DSD_STAMP_AT(g_stamps2[EPI][blockIdx.x][i]); } while (0)
 extern "C" int dsd_dbg_read_stamps(unsigned long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps), sizeof(g_stamps));
 }
@@ -85,10 +64,6 @@ extern "C" int dsd_dbg_read_stamps2(unsigned long long* host_out) {
 #define DSD_STAMP(i)
 #define DSD_STAMP2(i)
 #endif
-
-// floor(x / d) for 0 <= x < 2^22 with inv = 1.0f / d: one cvt + mul + cvt instead of the ~40-instruction
-// integer-division expansion (the kernel prologue is on the latency-critical path at B = 1)
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
 
 constexpr int PF = 8;   // A-fragment prefetch distance in k16 iterations (2 x 1 KiB loads each)
 
@@ -130,7 +105,7 @@ __device__ __forceinline__ void ring_load_s(f32x4& dst, unsigned voff, unsigned 
 template <int STAGE, int TAPS, int EPI, int NB, int SW, int RES = 0, int WN = 2, int RAG = 0>
 __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_kernel(const GemmP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // the header of the ~1 KB argument block in SGPRs behind ONE batch of scalar loads (as wn_rowsplit.hip's rs_pin_args: left
+    // the header of the ~1 KB argument block in SGPRs behind ONE batch of scalar loads (as wn_pin_args in dsd_device.h: left
     // alone the fields arrive in several dependent, cold round trips before the first vector load - on 5 us kernels)
     asm volatile("" ::"s"(p.A), "s"(p.bias), "s"(p.M), "s"(p.C), "s"(p.B), "s"(p.b_bstride), "s"(p.b_rstride), "s"(p.K), "s"(p.T),
                  "s"(p.tiles_per_b), "s"(p.mtiles), "s"(p.inv_mtiles), "s"(p.inv_tiles_per_b), "s"(p.inv_w4), "s"(p.gm_shift),
@@ -149,16 +124,11 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform (SGPR)
     const int wm = wave / WN, wn = wave % WN;
-    // 1-D grid with an XCD-aware remap (speed only, bijective for any grid size): the dispatcher deals
-    // workgroups round-robin over the 8 XCDs, so blocks b and b+8 share an L2.  Work items are numbered with the
-    // row tile fastest, and XCD k takes a CONTIGUOUS range of them: the workgroups that stage the SAME activation
-    // tile (same frames, all row tiles) share an XCD, so each L2 pulls 1/8 of the activations through the fabric
+    // XCD-aware remap (xcd_work).  Work items are numbered with the row tile fastest, so the workgroups that stage the SAME
+    // activation tile (same frames, all row tiles) share an XCD, and each L2 pulls 1/8 of the activations through the fabric
     // instead of all of them (measured: the staging phase was bound by 8 XCDs each re-reading the whole x).
     // Weights are then read by every XCD, but they stream during the K loop, off the latency-critical path.
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    const int work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const int work = xcd_work();
     int rest0, mtile;
     if (p.gm_shift > 0) {           // grouped order: work = (row group * frame tiles + frame tile) << gm_shift | row tile in group
         const int mg = fdiv_floor(work, p.inv_per_group);
@@ -795,7 +765,7 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
                 if (ch < p.C) {
                     const float u0 = acc[0][n][r] + p.bias[ch];
                     const float u1 = acc[MB - 1][n][r] + p.bias[ch + p.C];
-                    p.out[(long)b * p.o_bstride + (long)ch * p.o_rstride + t] = u0 * (u1 * sigmoid_f(u1));   // out * silu(gate)
+                    p.out[(long)b * p.o_bstride + (long)ch * p.o_rstride + t] = u0 * (u1 * sigmoid_ieee(u1));   // out * silu(gate)
                 }
             }
         } else {
@@ -893,12 +863,6 @@ int gemm_lds_bytes_fast(int S, int stage, int taps, int K, int nb, int resident)
 }
 
 template <int STAGE, int TAPS, int EPI, int NB, int SW, int RES = 0, int WN = 2, int RAG = 0>
-static hipError_t set_attr() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<STAGE, TAPS, EPI, NB, SW, RES, WN, RAG>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <int STAGE, int TAPS, int EPI, int NB, int SW, int RES = 0, int WN = 2, int RAG = 0>
 static hipError_t launch_one(const GemmP& p, int batch, hipStream_t st) {
     const int lds = p.lds_bytes;
     dim3 grid((RAG ? p.ncg : batch * p.tiles_per_b) * p.mtiles, 1, 1);
@@ -947,21 +911,21 @@ static hipError_t attr_all() {
     hipError_t e;
     if constexpr (STAGE != ST_LN && EPI != EP_SWIGLU) {
         if constexpr (TAPS == 1) {
-            if ((e = set_attr<STAGE, TAPS, EPI, 1, 16, 1, 1, RAG>()) != hipSuccess) return e;
-            if ((e = set_attr<STAGE, TAPS, EPI, 1, 16, 0, 1, RAG>()) != hipSuccess) return e;
+            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 16, 1, 1, RAG>)) != hipSuccess) return e;
+            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 16, 0, 1, RAG>)) != hipSuccess) return e;
         } else {
-            if ((e = set_attr<STAGE, TAPS, EPI, 1, 48, 0, 1, RAG>()) != hipSuccess) return e;
+            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 0, 1, RAG>)) != hipSuccess) return e;
         }
     }
-    if ((e = set_attr<STAGE, TAPS, EPI, 1, 0, 0, 2, RAG>()) != hipSuccess) return e;
-    if ((e = set_attr<STAGE, TAPS, EPI, 2, 0, 0, 2, RAG>()) != hipSuccess) return e;
-    if ((e = set_attr<STAGE, TAPS, EPI, 1, 48, 0, 2, RAG>()) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 0, 0, 2, RAG>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 0, 0, 2, RAG>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 0, 2, RAG>)) != hipSuccess) return e;
     if constexpr (TAPS == 1)
-        if ((e = set_attr<STAGE, TAPS, EPI, 1, 48, 1, 2, RAG>()) != hipSuccess) return e;
-    if ((e = set_attr<STAGE, TAPS, EPI, 2, 80, 0, 2, RAG>()) != hipSuccess) return e;
+        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 1, 2, RAG>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 80, 0, 2, RAG>)) != hipSuccess) return e;
     if constexpr (TAPS == 3) {
-        if ((e = set_attr<STAGE, TAPS, EPI, 1, 80, 0, 2, RAG>()) != hipSuccess) return e;
-        if ((e = set_attr<STAGE, TAPS, EPI, 2, 112, 0, 2, RAG>()) != hipSuccess) return e;
+        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 80, 0, 2, RAG>)) != hipSuccess) return e;
+        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 112, 0, 2, RAG>)) != hipSuccess) return e;
     }
     return hipSuccess;
 }
@@ -978,12 +942,12 @@ hipError_t gemm_init_all() {
     if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_LINCOMB>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_BIAS_ACT>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0>()) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0>)) != hipSuccess) return e;
     // ragged batches (RAG = 1): every GEMM of the denoisers and of the aux decoder
     if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_SCALE, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
@@ -994,30 +958,30 @@ hipError_t gemm_init_all() {
     if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
     // NSF-HiFiGAN: leaky-ReLU staged k-tap convs, residual epilogue, transposed-conv scatter (generic path only)
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 2, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 2, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 2, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 1, 0>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 2, 0>()) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 2, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 2, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 2, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 1, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 2, 0>)) != hipSuccess) return e;
     // ... and their ragged forms (dsd_vocode_ragged; conv_pre is the aux decoder's ST_PLAIN k-tap instantiation above)
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_PLAIN, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 1, 0, 0, 2, 1>()) != hipSuccess) return e;
-    if ((e = set_attr<ST_LRELU, 0, EP_SCATTER, 2, 0, 0, 2, 1>()) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
     return hipSuccess;
 }
 

@@ -18,10 +18,9 @@
 #include <hip/hip_ext.h>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef DSD_STAMPS
 // lx_pw1p_kernel, wave 0 of each workgroup: [0] start, [1] activation tile staged (after the barrier), [2] sum over the row
@@ -35,36 +34,12 @@ extern "C" int dsd_dbg_read_lx_stamps(unsigned long long* host_out) {
 
 namespace {
 
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
-constexpr unsigned kRange = 0x7FFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* ptr) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<0>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);      // plain: the next kernel re-reads these lines from L2 (write-through measured +0.5 %)
-}
-// SiLU's sigmoid: expf as the library computes it; the reciprocal as v_rcp_f32 (<= 1 ulp) instead of an IEEE division
-// sequence (~10 VALU instructions per element, 64 elements per lane and row tile in the SwiGLU epilogue)
-__device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.f + expf(-v)); }
-
 constexpr int BN = 32;          // frames per tile
 constexpr int MBW = 8;          // 16-row blocks per wave: 128 rows, 512 per workgroup
 constexpr int ES = BN + 4;      // row stride of the epilogue transpose tiles
 
-// XCD-aware remap (speed only): an XCD takes a contiguous range of work items; with the row tile SLOWEST an XCD walks all
-// frame tiles of (about) one row tile, whose 2 MiB of weights then stay in its L2 while the activation tiles stream
-__device__ __forceinline__ int xcd_work() {
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
+// Work order under the XCD-aware remap (xcd_work): with the row tile SLOWEST an XCD walks all frame tiles of (about) one row
+// tile, whose 2 MiB of weights then stay in its L2 while the activation tiles stream
 
 // 64 MFMAs of a k16 step with the step's MBW weight loads (for step s + 2), one optional operand load and the 8 LDS reads
 // of step s + 1 between them
@@ -242,7 +217,7 @@ __global__ __launch_bounds__(256, 1) void lx_pw1_kernel(const LxLayerP p) {
             for (int r = 0; r < 4; ++r) {
                 const float u0 = acc[2 * i][n][r] + bo[2 * i][r];
                 const float u1 = acc[2 * i + 1][n][r] + bo[2 * i + 1][r];
-                ew[(i * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_f(u1));
+                ew[(i * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_rcp(u1));
             }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -253,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void lx_pw1_kernel(const LxLayerP p) {
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int idx = lane + 64 * m;
-            st4(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, m * 8 * Ts * 4);
+            st4_l2(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, m * 8 * Ts * 4);
         }
     }
 }
@@ -384,7 +359,7 @@ __global__ __launch_bounds__(256, 1) void lx_pw1p_kernel(const LxLayerP p) {
                     for (int r = 0; r < 4; ++r) {
                         const float u0 = acc[2 * i][n][r] + bo[2 * i][r];
                         const float u1 = acc[2 * i + 1][n][r] + bo[2 * i + 1][r];
-                        ew[(ii * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_f(u1));
+                        ew[(ii * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_rcp(u1));
                     }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -393,7 +368,7 @@ __global__ __launch_bounds__(256, 1) void lx_pw1p_kernel(const LxLayerP p) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 const int idx = lane + 64 * m;
-                st4(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, (hf * 32 + m * 8) * Ts * 4);
+                st4_l2(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, (hf * 32 + m * 8) * Ts * 4);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();                     // the tile is read before the next half overwrites it
@@ -554,8 +529,8 @@ __global__ __launch_bounds__(256, 1) void lx_pw2_kernel(const LxLayerP p) {
             xo[e] = o;
             xi[m][e] = in;
         }
-        st4(xo, w_xo, ev0, m * 8 * Ts * 4);
-        if (p.xin_out) st4(xi[m], w_xi, ev0, m * 8 * Ts * 4);
+        st4_l2(xo, w_xo, ev0, m * 8 * Ts * 4);
+        if (p.xin_out) st4_l2(xi[m], w_xi, ev0, m * 8 * Ts * 4);
     }
     // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers.
     // A frame's 64 rows sit in 8 slots m of the 8 lanes with equal (lane & 7): sum over m, then over lanes 8, 16, 32 apart.
@@ -750,8 +725,8 @@ __global__ __launch_bounds__(256, 1) void lx_pw2d_kernel(const LxLayerP p) {
             xo[e] = o;
             xi[m][e] = in;
         }
-        st4(xo, w_xo, ev0, m * 8 * Ts * 4);
-        if (p.xin_out) st4(xi[m], w_xi, ev0, m * 8 * Ts * 4);
+        st4_l2(xo, w_xo, ev0, m * 8 * Ts * 4);
+        if (p.xin_out) st4_l2(xi[m], w_xi, ev0, m * 8 * Ts * 4);
     }
     // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers.
     // A frame's 64 rows sit in 8 slots m of the 8 lanes with equal (lane & 7): sum over m, then over lanes 8, 16, 32 apart.
@@ -981,8 +956,8 @@ __global__ __launch_bounds__(512, 1) void lx_pw2q_kernel(const LxLayerP p) {
             xo[e] = o;
             xi[k][e] = in;
         }
-        st4(xo, w_xo, ev0, k * 64 * Ts * 4);
-        if (p.xin_out) st4(xi[k], w_xi, ev0, k * 64 * Ts * 4);
+        st4_l2(xo, w_xo, ev0, k * 64 * Ts * 4);
+        if (p.xin_out) st4_l2(xi[k], w_xi, ev0, k * 64 * Ts * 4);
     }
     // LayerNorm partials of xin per 64-row tile (item k of every thread = tile k of this workgroup): two passes.  A frame quad's 64
     // rows sit in the 8 lanes with equal (lane & 7) of each of the 8 waves: lanes 8, 16, 32 apart, then the waves through LDS.
@@ -1037,7 +1012,7 @@ template <int KQ, int RAG>
 static hipError_t lx_launch_pw2q(const LxLayerP& p, int nwg, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lx_pw2q_kernel<KQ, RAG>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(lx_pw2q_kernel<KQ, RAG>);
         if (e != hipSuccess) return e;
         attr = true;
     }
@@ -1063,16 +1038,11 @@ bool lx_layer_supported(int C, int inner) {
     return (C == 512 || C == 1024) && (2 * inner) % 512 == 0 && C % 512 == 0 && inner % C == 0 && inner / C <= 2;
 }
 
-template <typename K>
-static hipError_t lx_attr(K kern) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 template <int KT, int RAG>
 static hipError_t lx_launch_pw1p(const LxLayerP& p, int nwg, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = lx_attr(lx_pw1p_kernel<KT, RAG>);
+        hipError_t e = allow_max_lds(lx_pw1p_kernel<KT, RAG>);
         if (e != hipSuccess) return e;
         attr = true;
     }
@@ -1104,12 +1074,12 @@ template <int KT, int RAG>
 static hipError_t lx_launch(const LxLayerP& p, int which, int nwg, hipStream_t st) {
     static bool attr1 = false, attr2 = false;
     if (which == 0 && !attr1) {
-        hipError_t e = lx_attr(lx_pw1_kernel<KT, RAG>);
+        hipError_t e = allow_max_lds(lx_pw1_kernel<KT, RAG>);
         if (e != hipSuccess) return e;
         attr1 = true;
     }
     if (which == 1 && !attr2) {
-        hipError_t e = lx_attr(lx_pw2_kernel<KT, RAG>);
+        hipError_t e = allow_max_lds(lx_pw2_kernel<KT, RAG>);
         if (e != hipSuccess) return e;
         attr2 = true;
     }
@@ -1123,7 +1093,7 @@ template <int NP, int RAG>
 static hipError_t lx_launch_pw2d(const LxLayerP& p, int nwg, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = lx_attr(lx_pw2d_kernel<NP, RAG>);
+        hipError_t e = allow_max_lds(lx_pw2d_kernel<NP, RAG>);
         if (e != hipSuccess) return e;
         attr = true;
     }

@@ -16,20 +16,14 @@
 #include <hip/hip_ext.h>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
 #ifdef DSD_STAMPS
 // [pw1 / pw2][workgroup][0..7]: s_memtime at the phase boundaries of wave 0 (tools/stamp_lynx_x3.py)
 __device__ unsigned long long g_x3_stamps[2][4096][8];
-#define X3_STAMP(i)                                                                     \
-    do {                                                                                \
-        if (threadIdx.x == 0 && blockIdx.x < 4096) {                                    \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-            g_x3_stamps[MODE][blockIdx.x][i] = __builtin_amdgcn_s_memtime();            \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-        }                                                                               \
-    } while (0)
+#define X3_STAMP(i) DSD_STAMP_AT(g_x3_stamps[MODE][blockIdx.x][i])
 extern "C" int dsd_dbg_read_x3_stamps(unsigned long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_x3_stamps), sizeof(g_x3_stamps));
 }
@@ -37,49 +31,9 @@ extern "C" int dsd_dbg_read_x3_stamps(unsigned long long* host_out) {
 #define X3_STAMP(i)
 #endif
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
-constexpr unsigned kRange = 0x7FFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* ptr) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ bf16x8 ldw(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<0>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
-}
-__device__ __forceinline__ float sigmoid_f(float v) { return __builtin_amdgcn_rcpf(1.f + expf(-v)); }
-
 constexpr int BN = 32, MBW = 8, ES = BN + 4;
-
-__device__ __forceinline__ int xcd_work() {
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
-
-// one row block x all NCB column blocks of a k32 step: lo.hi, hi.lo, hi.hi, the accumulators alternating
-template <int NCB>
-__device__ __forceinline__ void x3_products(f32x4 (&a)[NCB], bf16x8 wh, bf16x8 wl, const bf16x8 (&bh)[NCB], const bf16x8 (&bl)[NCB]) {
-#pragma unroll
-    for (int n = 0; n < NCB; ++n) a[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, bh[n], a[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NCB; ++n) a[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bl[n], a[n], 0, 0, 0);
-#pragma unroll
-    for (int n = 0; n < NCB; ++n) a[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bh[n], a[n], 0, 0, 0);
-}
 
 }  // namespace
 
@@ -268,7 +222,7 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
                     for (int r = 0; r < 4; ++r) {
                         const float u0 = acc[2 * i][2 * hf + n][r] + bo[2 * i][r];
                         const float u1 = acc[2 * i + 1][2 * hf + n][r] + bo[2 * i + 1][r];
-                        ew[(i * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_f(u1));
+                        ew[(i * 16 + rq + r) * ES + n * 16 + lcol] = u0 * (u1 * sigmoid_rcp(u1));
                     }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -277,7 +231,7 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const int idx = lane + 64 * m;
-                st4(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, m * 8 * Ts * 4);
+                st4_l2(*reinterpret_cast<const f32x4*>(&ew[(idx >> 3) * ES + (idx & 7) * 4]), w_o, ev0, m * 8 * Ts * 4);
             }
         } else {
             // transition (gemm.hip EP_LYNX_NEXT; lynxnet.py:76-84 of the next layer), row-major
@@ -323,8 +277,8 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
                     xo[e] = o;
                     xi[m][e] = in;
                 }
-                st4(xo, w_xo, ev0, m * 8 * Ts * 4);
-                if (p.xin_out) st4(xi[m], w_xi, ev0, m * 8 * Ts * 4);
+                st4_l2(xo, w_xo, ev0, m * 8 * Ts * 4);
+                if (p.xin_out) st4_l2(xi[m], w_xi, ev0, m * 8 * Ts * 4);
             }
             // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers
             if (p.lnpart) {
@@ -382,7 +336,7 @@ template <int MODE, int KT, int RAG, int NCB>
 static hipError_t lx_x3_launch(const LxLayerP& p, int nwg, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lx_x3_kernel<MODE, KT, RAG, NCB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(lx_x3_kernel<MODE, KT, RAG, NCB>);
         if (e != hipSuccess) return e;
         attr = true;
     }

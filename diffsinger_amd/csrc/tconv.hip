@@ -12,10 +12,9 @@
 //   D (row = (lane >> 4) * 4 + reg, column = lane & 15) goes through an LDS [CO][256] tile so that the global
 //     stores are 16-byte pieces of a channel row, with bias / leaky-ReLU / tanh / residual applied row-major.
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TC_TT = 256;          // frames per workgroup (4 waves x 4 blocks of 16)
 
@@ -132,8 +131,7 @@ template <int CI, int CO, int RAG>
 static hipError_t tconv_go(const TConvP& p, int batch, hipStream_t st) {
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<CI, CO, RAG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(tconv_kernel<CI, CO, RAG>);
         if (e != hipSuccess) return e;
         attr_set = true;
     }
@@ -148,10 +146,10 @@ static hipError_t tconv_go(const TConvP& p, int batch, hipStream_t st) {
 
 hipError_t tconv_init_all() {      // raise the dynamic-LDS limits once, outside any stream capture
     hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<16, 16, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<32, 32, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<16, 16, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(tconv_kernel<32, 32, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
+    if ((e = allow_max_lds(tconv_kernel<16, 16, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(tconv_kernel<32, 32, 0>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(tconv_kernel<16, 16, 1>)) != hipSuccess) return e;
+    if ((e = allow_max_lds(tconv_kernel<32, 32, 1>)) != hipSuccess) return e;
     return hipSuccess;
 }
 

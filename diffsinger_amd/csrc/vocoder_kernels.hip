@@ -6,6 +6,7 @@
 // RAG = 1 (dsd_vocode_ragged): item b of the batch is valid for lens[b] frames / samples of the launch's rate and is
 // computed as if it had been run alone at that length; separate instantiations, so the dense kernels carry nothing new.
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
@@ -132,13 +133,13 @@ __global__ __launch_bounds__(256) void voc_noise_conv_kernel(float* __restrict__
 __global__ void voc_accum_kernel(float* __restrict__ acc, const float* __restrict__ r, long n, int first, float div) {
     const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
-    f32x4_t a = *reinterpret_cast<const f32x4_t*>(r + i);
+    f32x4 a = *reinterpret_cast<const f32x4*>(r + i);
     if (!first) {
-        const f32x4_t c = *reinterpret_cast<const f32x4_t*>(acc + i);
+        const f32x4 c = *reinterpret_cast<const f32x4*>(acc + i);
         a = c + a;
     }
     if (div != 1.f) a = a / div;
-    *reinterpret_cast<f32x4_t*>(acc + i) = a;
+    *reinterpret_cast<f32x4*>(acc + i) = a;
 }
 
 // ---------------------------------------------------------------------------------------------

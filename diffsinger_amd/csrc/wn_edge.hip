@@ -15,22 +15,14 @@
 #include <hip/hip_ext.h>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef DSD_STAMPS
 // [launch with / without a fused input projection][workgroup][0..9]: s_memtime at the phase boundaries (wave 0)
 __device__ unsigned long long g_edge_stamps[2][4096][16];
-#define EDGE_STAMP(i)                                                                          \
-    do {                                                                                       \
-        if (threadIdx.x == 0 && blockIdx.x < 4096) {                                           \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-            g_edge_stamps[p.next_src >= 0 ? 1 : 0][blockIdx.x][i] = __builtin_amdgcn_s_memtime(); \
-            __builtin_amdgcn_sched_barrier(0);                                                 \
-        }                                                                                      \
-    } while (0)
+#define EDGE_STAMP(i) DSD_STAMP_AT(g_edge_stamps[p.next_src >= 0 ? 1 : 0][blockIdx.x][i])
 extern "C" int dsd_dbg_read_edge_stamps(unsigned long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_edge_stamps), sizeof(g_edge_stamps));
 }
@@ -39,18 +31,6 @@ extern "C" int dsd_dbg_read_edge_stamps(unsigned long long* host_out) {
 #endif
 
 namespace {
-
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
-constexpr unsigned kRange = 0x7FFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* ptr) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {      // write-through: dsd_internal.h
-    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
-}
 
 // acc[k][n] += W[block k][:, K] * tile[K, column block n]: NS k16 steps, the wave's MB row blocks (1 KiB fragment blocks at
 // wk[k] + 1024 * step), the B fragments from an LDS tile of row stride 16 * NCB floats (NCB = 2: odd rows are stored with
@@ -347,7 +327,7 @@ __global__ __launch_bounds__(256, 1) void wn_edge_kernel(const WnEdgeP p) {
                     const int idx = lane + 64 * m;
                     const int row = idx / W4, cc = (idx % W4) * 4;
                     if (wave * MB2 * 16 + row < p.FM)
-                        st4(*reinterpret_cast<const f32x4*>(&po[row * PS + cc]), w_d, (row * p.o_rstride + cc) * 4, 0);
+                        st4_wt(*reinterpret_cast<const f32x4*>(&po[row * PS + cc]), w_d, (row * p.o_rstride + cc) * 4, 0);
                 }
             }
         }
@@ -390,7 +370,7 @@ __global__ __launch_bounds__(256, 1) void wn_edge_kernel(const WnEdgeP p) {
         for (int m = 0; m < NE; ++m) {
             const int idx = lane + 64 * m;
             const int row = idx / W4, cc = (idx % W4) * 4;
-            st4(*reinterpret_cast<const f32x4*>(&ew[row * PS + cc]), w_xo, (row * Ts + cc) * 4, 0);
+            st4_wt(*reinterpret_cast<const f32x4*>(&ew[row * PS + cc]), w_xo, (row * Ts + cc) * 4, 0);
         }
     }
     EDGE_STAMP(9);
@@ -408,8 +388,7 @@ template <int NCH, int FMB, int NCB, int RAG>
 static hipError_t edge_launch(const WnEdgeP& p, int nwg, hipStream_t st) {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wn_edge_kernel<NCH, FMB, NCB, RAG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(wn_edge_kernel<NCH, FMB, NCB, RAG>);
         if (e != hipSuccess) return e;
         attr = true;
     }

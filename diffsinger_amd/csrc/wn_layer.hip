@@ -26,29 +26,20 @@
 #include <hip/hip_ext.h>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-__device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
 
 #ifdef DSD_STAMPS
 // [workgroup][0..7]: s_memtime at the phase boundaries; [8], [9]: s_memrealtime (100 MHz) at the first and last stamp
 __device__ unsigned long long g_wn_stamps[4096][10];
-#define WN_STAMP(i)                                                                     \
-    do {                                                                                \
-        if (threadIdx.x == 0 && blockIdx.x < 4096) {                                    \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-            g_wn_stamps[blockIdx.x][i] = __builtin_amdgcn_s_memtime();                  \
-            if ((i) == 0) g_wn_stamps[blockIdx.x][8] = __builtin_amdgcn_s_memrealtime(); \
-            if ((i) == 6) g_wn_stamps[blockIdx.x][9] = __builtin_amdgcn_s_memrealtime(); \
-            __builtin_amdgcn_sched_barrier(0);                                          \
-        }                                                                               \
+#define WN_STAMP(i)                                                                               \
+    do {                                                                                          \
+        DSD_STAMP_AT(g_wn_stamps[blockIdx.x][i]);                                                 \
+        if ((i) == 0) DSD_STAMP_WITH(g_wn_stamps[blockIdx.x][8], __builtin_amdgcn_s_memrealtime); \
+        if ((i) == 6) DSD_STAMP_WITH(g_wn_stamps[blockIdx.x][9], __builtin_amdgcn_s_memrealtime); \
     } while (0)
 #else
 #define WN_STAMP(i)
@@ -92,12 +83,7 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane >> 4, lcol = lane & 15, rq = lrow * 4;
-    // XCD-aware bijective remap (speed only): XCD k takes a contiguous range of tiles, so the tiles that share halo
-    // columns share an L2
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    const int work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const int work = xcd_work();                     // (XCD k takes a contiguous range of tiles: those that share halo columns share an L2)
     const int rest = RAG ? p.cgmap[work] : work + p.tile0;
     const int b = fdiv_floor(rest, p.inv_tiles_per_b);
     const int t0 = (rest - b * p.tiles_per_b) * BN;
@@ -111,14 +97,6 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
     // only what GEMM 1 cannot start without (x tile, FiLM vector, two weight steps: 30 instructions per wave); every
     // other operand (conditioner projection, biases, residual / skip) is fetched between the MFMAs of the K walks.
     const int bu = __builtin_amdgcn_readfirstlane(b), t0u = __builtin_amdgcn_readfirstlane(t0);
-    constexpr unsigned kRange = 0x7FFFFFF0u;
-    auto rsrc = [](const void* ptr) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000); };
-    auto ld4 = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto ld1 = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-    };
 
     // ---------------- prologue: x tile, FiLM vector, first two weight steps ----------------
     const __amdgpu_buffer_rsrc_t r_x = rsrc(p.xin + (long)bu * p.x_bstride + (t0u - HL));       // inside the arena's guard at t0 = 0
@@ -417,7 +395,7 @@ __device__ __forceinline__ void wn_layer_body(const WnLayerP& p, float* lds) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[m][e] : 0.f) + a4[e]) * scale;
-            dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * RPM * Ts * 4);
+            st4_wt(o, w_o, ev0, m * RPM * Ts * 4);
         }
     }
     WN_STAMP(6);
@@ -446,7 +424,7 @@ static hipError_t wn_launch(const WnLayerP& p, int ntiles, hipStream_t st) {
     if constexpr (NCB == 2) kern = wn_layer_kernel<NCH, SW, RAG>;
     else kern = wn_layer16_kernel<NCH, SW, RAG>;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(kern);
         if (e != hipSuccess) return e;
         attr_done = true;
     }

@@ -22,34 +22,18 @@
 #include <hip/hip_ext.h>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-__device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
 
 constexpr int C = 256, BN = 32, RS = C + 8;          // LDS image row stride in bf16 elements: 528 bytes
 constexpr int MBW = 8;                               // 16-row blocks per wave (2C rows / 4 waves / 16), both GEMMs
 constexpr int NS1 = 3 * C / 32, NS2 = C / 32;        // k32 steps: conv [tap][32-channel chunk], out-proj
 constexpr int ES = BN + 4;                           // epilogue tile row stride (floats)
-
-// one row block x both column blocks of a k32 step: lo.hi, hi.lo, hi.hi (smallest terms first), the two accumulators alternating
-__device__ __forceinline__ void x3_products(f32x4 (&a)[2], bf16x8 wh, bf16x8 wl, const bf16x8 (&bh)[2], const bf16x8 (&bl)[2]) {
-    a[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, bh[0], a[0], 0, 0, 0);
-    a[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, bh[1], a[1], 0, 0, 0);
-    a[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bl[0], a[0], 0, 0, 0);
-    a[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bl[1], a[1], 0, 0, 0);
-    a[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bh[0], a[0], 0, 0, 0);
-    a[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, bh[1], a[1], 0, 0, 0);
-}
 
 }  // namespace
 
@@ -71,28 +55,13 @@ __global__ __launch_bounds__(256, 1) void wn_layer_x3_kernel(const WnLayerP p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane >> 4, lcol = lane & 15, rq = lrow * 4;
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    const int work = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+    const int work = xcd_work();
     const int rest = RAG ? p.cgmap[work] : work + p.tile0;
     const int b = fdiv_floor(rest, p.inv_tiles_per_b);
     const int t0 = (rest - b * p.tiles_per_b) * BN;
     const int Tb = (RAG && p.lens) ? p.lens[b] : p.T;
     const int Ts = p.Ts;
     const int bu = __builtin_amdgcn_readfirstlane(b), t0u = __builtin_amdgcn_readfirstlane(t0);
-
-    constexpr unsigned kRange = 0x7FFFFFF0u;
-    auto rsrc = [](const void* ptr) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000); };
-    auto ld4 = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto ldw = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-    };
-    auto ld1 = [](__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-    };
 
     // ---------------- prologue: FiLM vector, x tile (transposed to [frame][channel], split hi / lo), first weight blocks ----------------
     const __amdgpu_buffer_rsrc_t r_x = rsrc(p.xin + (long)bu * p.x_bstride + (t0u - HL));       // inside the arena's guard at t0 = 0
@@ -189,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void wn_layer_x3_kernel(const WnLayerP p) {
         for (int k = 0; k < MBW; ++k) {
             const int i = s * MBW + k;
             const bf16x8 wh = Whi[i % RB], wl = Wlo[i % RB];
-            x3_products(acc[k], wh, wl, bh, bl);
+            x3_products<2>(acc[k], wh, wl, bh, bl);
             w_issue(i + RB);                                     // the slot is free again: next block of the stream
             // (pinned: left to itself the scheduler sinks every weight load to just before its use - the ring collapses to two
             // registers and the walk runs at one L2 round trip per row block, 102 us per tile instead of ~35)
@@ -269,7 +238,7 @@ __global__ __launch_bounds__(256, 1) void wn_layer_x3_kernel(const WnLayerP p) {
         for (int k = 0; k < MBW; ++k) {
             const int i = NB1 + s * MBW + k;
             const bf16x8 wh = Whi[i % RB], wl = Wlo[i % RB];
-            x3_products(acc[k], wh, wl, bh, bl);
+            x3_products<2>(acc[k], wh, wl, bh, bl);
             w_issue(i + RB);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -298,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void wn_layer_x3_kernel(const WnLayerP p) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[m][e] : 0.f) + a4[e]) * scale;
-            dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, o), w_o, ev0, m * 8 * Ts * 4);
+            st4_wt(o, w_o, ev0, m * 8 * Ts * 4);
         }
     }
 }
@@ -311,8 +280,7 @@ template <int HL, int RAG>
 static hipError_t x3_launch(const WnLayerP& p, int ntiles, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wn_layer_x3_kernel<HL, RAG>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = allow_max_lds(wn_layer_x3_kernel<HL, RAG>);
         if (e != hipSuccess) return e;
         attr_done = true;
     }

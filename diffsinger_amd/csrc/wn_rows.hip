@@ -16,63 +16,15 @@
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
-#include <type_traits>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-__device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
-// byte offset of a row as a 24-bit multiply (see wn_rowsplit.hip: a 32-bit mad's undefined high half)
-__device__ __forceinline__ int row_ts(int row, int Ts) { return (int)__umul24((unsigned)row, (unsigned)(Ts * 4)); }
-
-constexpr unsigned kRange = 0x7FFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* ptr) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {       // x / skip: write-through
-    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
-}
-__device__ __forceinline__ void st4z(f32x4 v, dsd_i32x4 r, int voff, int soff) {      // z: read back by the next launch
-    dsd_store_b128<0>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
-}
-__device__ __forceinline__ void rw_pin_args(const WnLayerP& p) {     // every argument in SGPRs behind ONE batch of scalar loads
-    asm volatile("" ::"s"(p.Aconv), "s"(p.Aout), "s"(p.bias_out), "s"(p.xin), "s"(p.xout), "s"(p.skip), "s"(p.z), "s"(p.x_bstride),
-                 "s"(p.Ts), "s"(p.cp), "s"(p.cp_bstride), "s"(p.film), "s"(p.film_cstride), "s"(p.film_col0), "s"(p.film_colb),
-                 "s"(p.dil), "s"(p.T), "s"(p.tiles_per_b), "s"(p.first_layer), "s"(p.inv_tiles_per_b), "s"(p.tile0),
-                 "s"((int)gridDim.x));
-}
-template <int I, int N, typename F>
-__device__ __forceinline__ void rw_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rw_static_for<I + 1, N>(f);
-    }
-}
-// XCD-aware bijective remap (speed only): an XCD takes a contiguous range of work items, row tile fastest, so the row tiles
-// of a frame tile - which stage the same activations - share an L2
-__device__ __forceinline__ int xcd_work() {
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
 #define RW_PIN() __builtin_amdgcn_sched_barrier(0)
-__device__ __forceinline__ f32x4 rw_mfma(float wfrag, float xfrag, f32x4 acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag, xfrag, acc, 0, 0, 0);
-}
 
 constexpr int NCH = 4, C = 256, BN = 32, ES = 36, B4 = 8;
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -93,7 +45,7 @@ __global__ __launch_bounds__(512, 1) void wn_conv_rw_kernel(const WnLayerP p) {
     static_assert(MP == 2 || MP == 4, "128 or 256 rows per workgroup");
     static_assert(SW >= BN + 2 * HL && (SW % 64 == 16 || SW % 64 == 48), "x tile row stride");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    rw_pin_args(p);
+    wn_pin_args(p);
     constexpr int MT = 8 / MP;                      // row tiles (workgroups) per frame tile
     constexpr int NB2 = 2 * MP;                     // row blocks per wave
     constexpr int W4 = (BN + 2 * HL) / 4;
@@ -205,7 +157,7 @@ __global__ __launch_bounds__(512, 1) void wn_conv_rw_kernel(const WnLayerP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) read_b1(bq[0], 0, j);
     RW_PIN();
-    rw_static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
+    static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
         constexpr int t = decltype(tc)::value;
         float (&bc)[4][2] = bq[t & 1];
         float (&bn)[4][2] = bq[(t + 1) & 1];
@@ -222,7 +174,7 @@ __global__ __launch_bounds__(512, 1) void wn_conv_rw_kernel(const WnLayerP p) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const int m = (j * NB2 + rb) * 2 + n;
-                    acc[rb][n] = rw_mfma(W[t % DW][rb][j], bc[j][n], acc[rb][n]);
+                    acc[rb][n] = mfma_16x16x4(W[t % DW][rb][j], bc[j][n], acc[rb][n]);
                     if (t == 0) {
                         if (DW == 3 && m % 4 == 0 && m / 4 < 2 * NB2) w_load(1 + (m / 4) / NB2, (m / 4) % NB2);
                         if (DW == 2 && m % 8 == 0 && m / 8 < NB2) w_load(1, m / 8);
@@ -291,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void wn_conv_rw_kernel(const WnLayerP p) {
             f32x4 z;
 #pragma unroll
             for (int e = 0; e < 4; ++e) z[e] = sigmoid_fast(g[e] + cpg[k][e]) * tanh_fast(f[e] + cpf[k][e]);      // wavenet.py:41-42
-            st4z(z, w_z, row_ts(gch0 + 64 * k, Ts) + gc4 * 16, 0);
+            st4_l2(z, w_z, row_ts(gch0 + 64 * k, Ts) + gc4 * 16, 0);
         }
     }
 }
@@ -305,7 +257,7 @@ template <int MP, int RAG>
 __global__ __launch_bounds__(512, 1) void wn_out_rw_kernel(const WnLayerP p) {
     static_assert(MP == 2 || MP == 4, "128 or 256 rows per workgroup");
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    rw_pin_args(p);
+    wn_pin_args(p);
     constexpr int MT = 8 / MP;
     constexpr int SZ = 48;
     constexpr int NZ = C * B4 / 512;                // staged float4 per thread: 4
@@ -388,7 +340,7 @@ __global__ __launch_bounds__(512, 1) void wn_out_rw_kernel(const WnLayerP p) {
         bq[0][j][1] = zt[(j * 4) * SZ + 16];
     }
     RW_PIN();
-    rw_static_for<0, NH>([&](auto sc) __attribute__((always_inline)) {
+    static_for<0, NH>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         float (&bc)[4][2] = bq[s & 1];
         float (&bn)[4][2] = bq[(s + 1) & 1];
@@ -399,7 +351,7 @@ __global__ __launch_bounds__(512, 1) void wn_out_rw_kernel(const WnLayerP p) {
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
                     const int m = (j * MP + k) * 2 + n;          // MFMA of the step, 8 MP of them
-                    acc[k][n] = rw_mfma(W[s % DO][k][j], bc[j][n], acc[k][n]);
+                    acc[k][n] = mfma_16x16x4(W[s % DO][k][j], bc[j][n], acc[k][n]);
                     if (s == 0) {                                // step 0 issues the sets of steps 1 and 2
                         if (m % 2 == 0 && m / 2 < 2 * MP) w_load(1 + (m / 2) / MP, (m / 2) % MP);
                     } else if (s + DO - 1 < NH && m % 2 == 0 && m / 2 < MP) {
@@ -439,7 +391,7 @@ __global__ __launch_bounds__(512, 1) void wn_out_rw_kernel(const WnLayerP p) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[k][e] : 0.f) + a4[e]) * scale;
-            st4(o, w_o, ev0, k * 64 * Ts * 4);
+            st4_wt(o, w_o, ev0, k * 64 * Ts * 4);
         }
     }
 }
@@ -450,17 +402,12 @@ int wn_rw_out_lds_bytes(int mp) { return (C * 48 + 2 * 64 * mp * ES) * 4; }
 
 bool wn_rows_supported(int C_, int dil, long Ts) { return C_ == 256 && dil >= 1 && dil <= 16 && Ts < (1L << 22); }
 
-template <typename K>
-static hipError_t rw_attr(K kern) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 template <int MP, int SW, int RAG>
 static hipError_t rw_launch_conv(const WnLayerP& p, int nwg, hipStream_t st) {
     constexpr int HL = SW == 48 ? 8 : 16;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = rw_attr(wn_conv_rw_kernel<MP, SW, HL, RAG>);
+        hipError_t e = allow_max_lds(wn_conv_rw_kernel<MP, SW, HL, RAG>);
         if (e != hipSuccess) return e;
         attr_done = true;
     }
@@ -473,7 +420,7 @@ template <int MP, int RAG>
 static hipError_t rw_launch_out(const WnLayerP& p, int nwg, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = rw_attr(wn_out_rw_kernel<MP, RAG>);
+        hipError_t e = allow_max_lds(wn_out_rw_kernel<MP, RAG>);
         if (e != hipSuccess) return e;
         attr_done = true;
     }

@@ -17,73 +17,31 @@
 #include <hip/hip_ext.h>
 
 #include <cstdlib>
-#include <type_traits>
 
 #include "dsd_internal.h"
+#include "dsd_device.h"
 
 namespace dsd {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-__device__ __forceinline__ float sigmoid_fast(float v) { return __builtin_amdgcn_rcpf(1.f + __expf(-v)); }
-__device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * v)); }
-__device__ __forceinline__ int fdiv_floor(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }
-// byte offset of a row as a 24-bit multiply (rows < 512; the host keeps Ts below 2^22): a 32-bit `row * Ts + c` compiles to
-// v_mad_u64_u32, whose 64-bit addend has an undefined high half - the register allocator parked it on a register with a load
-// in flight (the FiLM value) and the hardware dependency put an s_waitcnt vmcnt(0) in front of the x-tile loads.
 template <int B4>
-__device__ __forceinline__ int div_b4(int x) { return B4 == 8 ? x >> 3 : fdiv_floor(x, 1.0f / B4); }     // x / B4, x < 2^16
-__device__ __forceinline__ int row_ts(int row, int Ts) { return (int)__umul24((unsigned)row, (unsigned)(Ts * 4)); }   // BYTES
-
-constexpr unsigned kRange = 0x7FFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* ptr) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(ptr), 0, kRange, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld4(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ void st4(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<kStAux>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
-}
-// The conv's z is read back by the very next launch: kept in L2 (plain).  Same-box A/B of the 50-NFE loop at B = 1, three runs
-// each: x / skip write-through + z plain 16.52 ms, both write-through 16.55, x / skip plain + z write-through 16.70, both
-// plain 16.67.
-constexpr int kStAuxZ = 0;
-__device__ __forceinline__ void st4z(f32x4 v, dsd_i32x4 r, int voff, int soff) {
-    dsd_store_b128<kStAuxZ>(__builtin_bit_cast(dsd_u32x4, v), r, voff, soff);
+__device__ __forceinline__ int div_b4(int x) {     // x / B4, x < 2^16
+    return B4 == 8 ? x >> 3 : fdiv_floor(x, 1.0f / B4);
 }
 
 #ifdef DSD_STAMPS
 // [kernel 0 = conv, 1 = out][workgroup][0..6]: s_memtime at the phase boundaries; [8], [9]: s_memrealtime at the first / last
 __device__ unsigned long long g_rs_stamps[2][4096][40];      // [10 + s]: after local step s of the conv walk
-#define RS_STAMP(K, i)                                                                          \
-    do {                                                                                        \
-        if (threadIdx.x == 0 && blockIdx.x < 4096) {                                            \
-            __builtin_amdgcn_sched_barrier(0);                                                  \
-            g_rs_stamps[K][blockIdx.x][i] = __builtin_amdgcn_s_memtime();                       \
-            if ((i) == 0) g_rs_stamps[K][blockIdx.x][8] = __builtin_amdgcn_s_memrealtime();     \
-            if ((i) == 5) g_rs_stamps[K][blockIdx.x][9] = __builtin_amdgcn_s_memrealtime();     \
-            __builtin_amdgcn_sched_barrier(0);                                                  \
-        }                                                                                       \
+#define RS_STAMP(K, i)                                                                               \
+    do {                                                                                             \
+        DSD_STAMP_AT(g_rs_stamps[K][blockIdx.x][i]);                                                 \
+        if ((i) == 0) DSD_STAMP_WITH(g_rs_stamps[K][blockIdx.x][8], __builtin_amdgcn_s_memrealtime); \
+        if ((i) == 5) DSD_STAMP_WITH(g_rs_stamps[K][blockIdx.x][9], __builtin_amdgcn_s_memrealtime); \
     } while (0)
 #else
 #define RS_STAMP(K, i)
 #endif
-
-// Every field of the argument block in SGPRs behind ONE batch of scalar loads at the top of the kernel: left to itself the
-// compiler fetches them in two or three dependent batches (each a cold scalar-cache round trip) before the first vector load
-// can issue - on kernels whose whole life is 8-20 k cycles.  (The unpinned form was measured against this and removed.)
-__device__ __forceinline__ void rs_pin_args(const WnLayerP& p) {
-    asm volatile("" ::"s"(p.Aconv), "s"(p.Aout), "s"(p.bias_out), "s"(p.xin), "s"(p.xout), "s"(p.skip), "s"(p.z), "s"(p.x_bstride),
-                 "s"(p.Ts), "s"(p.cp), "s"(p.cp_bstride), "s"(p.film), "s"(p.film_cstride), "s"(p.film_col0), "s"(p.film_colb),
-                 "s"(p.dil), "s"(p.T), "s"(p.tiles_per_b), "s"(p.first_layer), "s"(p.inv_tiles_per_b), "s"(p.tile0),
-                 "s"((int)gridDim.x));                           // (the grid size is an implicit argument: same segment)
-}
 
 // Weight fragments in rotation: step s runs from W[s % DEPTH], step s + DEPTH - 1 is in flight.  The prologue of these short
 // kernels is bound by how many wave-level loads a CU can issue before the walk starts, and DEPTH - 1 blocks per wave are part of
@@ -112,24 +70,6 @@ constexpr int LATE_W = 5, LATE_B = 10;
 // step until more are in flight - equal for 4 .. 8 blocks.)
 // Out-proj: one weight block less in the prologue's burst (DEPTH_OUT - 2), step 0 issues two (as the K-quarter conv does).
 
-// the walk's steps with their index a constant expression (ring slots, the block each step issues)
-template <int I, int N, typename F>
-__device__ __forceinline__ void rs_static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rs_static_for<I + 1, N>(f);
-    }
-}
-
-// XCD-aware bijective remap (speed only): an XCD takes a contiguous range of work items, row tile fastest, so the row
-// tiles of a frame tile - which stage the same activations - share an L2
-__device__ __forceinline__ int xcd_work() {
-    const int nwg = gridDim.x;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int q8 = nwg >> 3, r8 = nwg & 7;
-    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
-}
-
 }  // namespace
 
 #ifdef DSD_STAMPS
@@ -145,9 +85,6 @@ extern "C" int dsd_dbg_read_rs_stamps(unsigned long long* host_out) {
 // weight load for step s + 5 and an operand load behind the first two, one LDS read pair of step s + 1 behind each of
 // the first four.
 #define RS_PIN() __builtin_amdgcn_sched_barrier(0)
-__device__ __forceinline__ f32x4 rs_mfma(float wfrag, float xfrag, f32x4 acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag, xfrag, acc, 0, 0, 0);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Both kernels: C = 256 (NCH = 4 chunks of 64 channels), 512 threads = 8 waves = two K HALVES of four row waves: wave
@@ -164,7 +101,7 @@ template <int SW, int RAG>
 __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     RS_STAMP(0, 6);                                              // (diagnostic builds: before any argument is touched ...
-    rs_pin_args(p);
+    wn_pin_args(p);
     RS_STAMP(0, 7);                                              //  ... and with all of them in SGPRs)
     constexpr int HL = SW == 48 ? 8 : 16;
     constexpr int W4 = (BN + 2 * HL) / 4;
@@ -262,7 +199,7 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) read_b1(bq[0], 0, j);
     RS_PIN();
-    rs_static_for<0, NH>([&](auto sc) __attribute__((always_inline)) {
+    static_for<0, NH>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         const f32x4 wv = W[s % DEPTH];
         float (&bc)[4][2] = bq[s & 1];
@@ -270,14 +207,14 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
         constexpr int nb = s + DEPTH - 1;                        // this step issues block nb (its slot the step before freed)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            acc[0] = rs_mfma(wv[j], bc[j][0], acc[0]);
+            acc[0] = mfma_16x16x4(wv[j], bc[j][0], acc[0]);
             if (j == 0 && nb < NH) W[nb % DEPTH] = ld4(r_w, wl + (nb & 3) * 1024, (nb >> 2) * 4096);
             if (j == 0 && s + 1 < NH) {                          // the next step's 4 LDS read pairs in one burst
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) read_b1(bn, s + 1, jj);
             }
             RS_PIN();
-            acc[1] = rs_mfma(wv[j], bc[j][1], acc[1]);
+            acc[1] = mfma_16x16x4(wv[j], bc[j][1], acc[1]);
             if constexpr (s < NE)
                 if (j == 0) svl[s] = ld4(r_x, row_ts(x_row(s, 1), Ts) + x_c4(s) * 16, 0);
             if (j == 0 && s == 12) cpg = ld4(r_c, row_ts(gch, Ts) + (tid & 7) * 16, 0);
@@ -320,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rs_kernel(const WnLayerP p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[e] = sigmoid_fast(g[e] + cpg[e]) * tanh_fast(f[e] + cpf[e]);      // wavenet.py:41-42
         const dsd_i32x4 w_z = dsd_rsrc_words(p.z + (long)bu * p.x_bstride + t0u);
-        st4z(z, w_z, row_ts(gch, Ts) + c4 * 16, 0);
+        st4_l2(z, w_z, row_ts(gch, Ts) + c4 * 16, 0);
     }
     RS_STAMP(0, 4);
     RS_STAMP(0, 5);
@@ -345,7 +282,7 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
     static_assert(SW >= BN + 2 * HL && (SW % 64 == 16 || SW % 64 == 48), "x tile row stride");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     RS_STAMP(0, 6);
-    rs_pin_args(p);
+    wn_pin_args(p);
     RS_STAMP(0, 7);
     constexpr int W4 = (BN + 2 * HL) / 4;
     constexpr int NE = 128 * W4 / 512;              // float4 per thread of 128 rows: 3 - 5
@@ -458,14 +395,14 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) read_b1(bq[0], 0, j);
     RS_PIN();
-    rs_static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
+    static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
         constexpr int t = decltype(tc)::value;
         const f32x4 wv0 = W[t % 3][0], wv1 = W[t % 3][1];
         float (&bc)[4][NCB] = bq[t & 1];
         float (&bn)[4][NCB] = bq[(t + 1) & 1];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            acc[0][0] = rs_mfma(wv0[j], bc[j][0], acc[0][0]);
+            acc[0][0] = mfma_16x16x4(wv0[j], bc[j][0], acc[0][0]);
             if (t == 0) w_load(1 + j / 2, j & 1);                // step 0 issues steps 1 and 2 ...
             else if (j < 2 && t + 2 < NQ) w_load(t + 2, j);      // ... step t >= 1 issues step t + 2
             if (j == 0 && t + 1 < NQ) {                          // the next step's LDS reads in one burst
@@ -473,19 +410,19 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
                 for (int jj = 0; jj < 4; ++jj) read_b1(bn, t + 1, jj);
             }
             RS_PIN();
-            acc[0][1] = rs_mfma(wv0[j], bc[j][1], acc[0][1]);
+            acc[0][1] = mfma_16x16x4(wv0[j], bc[j][1], acc[0][1]);
             if (j < 2 && t < 3 && 2 * t + j < NE) svl[2 * t + j] = ld4(r_x, row_ts(x_row(2 * t + j, 1), Ts) + x_c4(2 * t + j) * 16, 0);
             if (j == 0 && t == CPS) cpg = ld4(r_c, row_ts(gch, Ts) + gc4 * 16, 0);
             if (j == 0 && t == CPS + 1) cpf = ld4(r_c, row_ts(gch + C, Ts) + gc4 * 16, 0);
             RS_PIN();
 #pragma unroll
             for (int n = 2; n < NCB; ++n) {
-                acc[0][n] = rs_mfma(wv0[j], bc[j][n], acc[0][n]);
+                acc[0][n] = mfma_16x16x4(wv0[j], bc[j][n], acc[0][n]);
                 RS_PIN();
             }
 #pragma unroll
             for (int n = 0; n < NCB; ++n) {
-                acc[1][n] = rs_mfma(wv1[j], bc[j][n], acc[1][n]);
+                acc[1][n] = mfma_16x16x4(wv1[j], bc[j][n], acc[1][n]);
                 RS_PIN();
             }
         }
@@ -526,7 +463,7 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[e] = sigmoid_fast(g[e] + cpg[e]) * tanh_fast(f[e] + cpf[e]);      // wavenet.py:41-42
         const dsd_i32x4 w_z = dsd_rsrc_words(p.z + (long)bu * p.x_bstride + t0u);
-        st4z(z, w_z, row_ts(gch, Ts) + c4 * 16, 0);
+        st4_l2(z, w_z, row_ts(gch, Ts) + c4 * 16, 0);
     }
     RS_STAMP(0, 4);
     RS_STAMP(0, 5);
@@ -536,7 +473,7 @@ template <int NCB, int RAG>
 __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
     constexpr int BN = 16 * NCB, ES = BN + 4, B4 = BN / 4;      // (shadow the 32-frame constants)
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    rs_pin_args(p);
+    wn_pin_args(p);
     constexpr int SZ = 48;
     constexpr int NZ = C * B4 / 512;                // staged float4 per thread: 4 / 6
     static_assert(SZ >= BN && NCB <= 3, "z tile row stride");
@@ -622,7 +559,7 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
         float (&bn)[4][NCB] = bq[(s + 1) & 1];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            acc[0] = rs_mfma(wv[j], bc[j][0], acc[0]);
+            acc[0] = mfma_16x16x4(wv[j], bc[j][0], acc[0]);
             if (s == 0 && j == 0)                                // (the prologue's burst holds one block less: step 0 issues two)
                 W[DEPTH_OUT - 2] = ld4(r_w, wl + ((DEPTH_OUT - 2) & 3) * 1024, ((DEPTH_OUT - 2) >> 2) * 4096);
             if (j == (s == 0 ? 1 : 0) && s + DEPTH_OUT - 1 < NH)
@@ -634,13 +571,13 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
                     for (int n = 0; n < NCB; ++n) bn[jj][n] = zt[((s + 1) * 16 + jj * 4) * SZ + 16 * n];
             }
             RS_PIN();
-            acc[1] = rs_mfma(wv[j], bc[j][1], acc[1]);
+            acc[1] = mfma_16x16x4(wv[j], bc[j][1], acc[1]);
             if (j == 0 && s == 1) pre[0] = ld4(r_e, ev0, 0);
             if (ITEMS == 2 && j == 0 && s == 2) pre[1] = ld4(r_e, ev0, 32 * Ts * 4);
             RS_PIN();
 #pragma unroll
             for (int n = 2; n < NCB; ++n) {
-                acc[n] = rs_mfma(wv[j], bc[j][n], acc[n]);
+                acc[n] = mfma_16x16x4(wv[j], bc[j][n], acc[n]);
                 RS_PIN();
             }
         }
@@ -668,7 +605,7 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
             f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = ((add_pre ? pre[k][e] : 0.f) + a4[e]) * scale;
-            st4(o, w_o, ev0, k * 32 * Ts * 4);
+            st4_wt(o, w_o, ev0, k * 32 * Ts * 4);
         }
     }
     RS_STAMP(1, 4);
@@ -677,11 +614,6 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
 // (The out-proj in the same K-quarter layout - 4 steps of 16 MFMAs per wave, four partial tiles - was built and measured: 14.76
 // against 14.75 ms per loop; its walk is too short for the halved LDS reads to pay for the wider reduction.  Not kept.)
 #undef RS_PIN
-
-template <typename K>
-static hipError_t rs_attr(K kern) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
 
 // x tile + the K parts' transpose tiles
 int wn_rs_conv_lds_bytes(int sw, int bn, bool quarters) { return (256 * sw + (quarters ? 4 : 2) * 64 * (bn + 4)) * 4; }
@@ -696,9 +628,9 @@ static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int conv_q,
     constexpr int HL = SW == 48 ? 8 : 16;
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = rs_attr(wn_conv_rq_kernel<2, SW, HL, RAG>);
-        if (e == hipSuccess) e = rs_attr(wn_conv_rs_kernel<SW, RAG>);
-        if (e == hipSuccess && !RAG) e = rs_attr(wn_conv_rq_kernel<3, 80, HL, 0>);
+        hipError_t e = allow_max_lds(wn_conv_rq_kernel<2, SW, HL, RAG>);
+        if (e == hipSuccess) e = allow_max_lds(wn_conv_rs_kernel<SW, RAG>);
+        if (e == hipSuccess && !RAG) e = allow_max_lds(wn_conv_rq_kernel<3, 80, HL, 0>);
         if (e != hipSuccess) return e;
         attr_done = true;
     }
@@ -722,8 +654,8 @@ template <int RAG>
 static hipError_t rs_launch_out(const WnLayerP& p, int nwg, int bn, hipStream_t st) {
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = rs_attr(wn_out_rs_kernel<2, RAG>);
-        if (e == hipSuccess && !RAG) e = rs_attr(wn_out_rs_kernel<3, 0>);
+        hipError_t e = allow_max_lds(wn_out_rs_kernel<2, RAG>);
+        if (e == hipSuccess && !RAG) e = allow_max_lds(wn_out_rs_kernel<3, 0>);
         if (e != hipSuccess) return e;
         attr_done = true;
     }

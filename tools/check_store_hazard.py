@@ -9,7 +9,7 @@ one or two issue slots can land first (seen on MI355X in wn_out_rw_kernel<4, *>:
 NEXT item's operand, nondeterministically, in ~0.4 % of the elements).  The ISA manuals list the case (VMEM store of > 64
 bits of data followed by a write of its data VGPRs: 1-2 wait states); the compiler inserts the s_nop for stores without an
 SGPR offset but not for the `soffset` form the raw-buffer builtins produce.  The kernels therefore issue `s_nop 1` behind
-every 16-byte raw buffer store (st4 helpers); this script verifies that no such pair is left.
+every 16-byte raw buffer store (dsd_store_b128 in dsd_device.h); this script verifies that no such pair is left.
 
 Usage: python tools/check_store_hazard.py            (exit 1 if a hazard pair is found; no GPU needed)"""
 import os
@@ -20,8 +20,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "diffsinger_amd", "csrc")
-FILES = ["gemm.hip", "wn_layer.hip", "wn_rowsplit.hip", "wn_rows.hip", "wn_edge.hip", "lynx_layer.hip", "aux_kernels.hip", "tconv.hip",
-         "encoder_kernels.hip", "vocoder_kernels.hip"]
+FILES = ["gemm.hip", "wn_layer.hip", "wn_layer_x3.hip", "wn_rowsplit.hip", "wn_rows.hip", "wn_edge.hip", "lynx_layer.hip", "lynx_x3.hip",
+         "aux_kernels.hip", "tconv.hip", "encoder_kernels.hip", "vocoder_kernels.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 WAIT_STATES = 2
 
