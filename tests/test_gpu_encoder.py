@@ -10,7 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from diffsinger_amd import synth  # noqa: E402
-from gpu_util import dev, rel_err, set_hp  # noqa: E402
+from gpu_util import check, dev, rel_err, set_hp  # noqa: E402
 from oracle import encoder as oe  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -95,6 +95,65 @@ def test_encoder_vs_oracle_sizes(bsz, t_txt, t_mel):
         got32 = m(dev(tokens).int(), dev(mel2ph).int(), dev(f0))          # int32 indices are widened
     assert rel_err(got, want) < TOL
     assert torch.equal(got, got32)
+    m.release_native()
+
+
+def padded_inputs(n_tok, n_fr, t_txt, t_mel, seed, vocab=50):
+    """A zero-padded batch: item b has n_tok[b] tokens (ids in [1, vocab)) spread over its first n_fr[b] frames."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    bsz = len(n_tok)
+    tokens = np.zeros((bsz, t_txt), np.int64)
+    mel2ph = np.zeros((bsz, t_mel), np.int64)
+    for b in range(bsz):
+        tokens[b, :n_tok[b]] = rng.integers(1, vocab, n_tok[b])
+        durs = 1 + rng.multinomial(n_fr[b] - n_tok[b], np.ones(n_tok[b]) / n_tok[b])
+        mel2ph[b, :n_fr[b]] = np.repeat(np.arange(1, n_tok[b] + 1), durs)
+    f0 = (200.0 * 2.0 ** rng.uniform(-1, 1, (bsz, t_mel))).astype(np.float32)
+    return tokens, mel2ph, f0
+
+
+@pytest.mark.parametrize("heads", [1, 16, 32])
+def test_encoder_head_dims_vs_oracle(heads):
+    """enc_attention_kernel at head dimensions D = 256 / 16 / 8 (hidden 256): D = 256 takes four passes of the P.V loop,
+    D = 16 / 8 leave lanes idle there and fill `qs` partly, RoPE rotates 8 / 4 pairs per head.  L = 130 is three key
+    chunks, the last one partial; item 1 (100 tokens) ends inside chunk 1 and has chunk 2 all padding."""
+    m, params, _ = build(50, dict(num_heads=heads), dict(), 93)
+    tokens, mel2ph, f0 = padded_inputs([130, 100], [260, 190], 130, 260, 94)
+    want = oe.fs2_acoustic_forward(params, tokens, mel2ph, f0, num_heads=heads)
+    with torch.no_grad():
+        got = m(dev(tokens), dev(mel2ph), dev(f0))
+    check(got, want, TOL, what=("heads", heads))
+    m.release_native()
+
+
+@pytest.mark.parametrize("t_txt", [1985, 2048])
+def test_encoder_longest_inputs_vs_oracle(t_txt):
+    """The last of the 32 key chunks holds 1 (L = 1985) or 64 (L = 2048) keys; the P.V walk reads V rows up to
+    nch * 64 = 2048, past L into the rows' padding.  Item 1 is shorter (padding from inside chunk 19)."""
+    m, params, _ = build(50, dict(), dict(), 95)
+    t_mel = t_txt * 3 // 2
+    tokens, mel2ph, f0 = padded_inputs([t_txt, 1234], [t_mel, 1900], t_txt, t_mel, t_txt)
+    want = oe.fs2_acoustic_forward(params, tokens, mel2ph, f0, num_heads=2)
+    with torch.no_grad():
+        got = m(dev(tokens), dev(mel2ph), dev(f0))
+    check(got, want, TOL, what=("L", t_txt))
+    m.release_native()
+
+
+def test_encoder_rejects_2049_tokens_and_recovers():
+    """dsd_encode accepts at most 2048 tokens (ATT_MAXCH = 32 key chunks of 64); one more is an error naming the limit,
+    and the handle stays usable."""
+    from diffsinger_amd._lib import NativeLibraryError
+    m, params, _ = build(50, dict(), dict(), 96)
+    tokens, mel2ph, f0 = padded_inputs([2049], [2049], 2049, 2049, 97)
+    with torch.no_grad():
+        with pytest.raises(NativeLibraryError, match="2049 tokens exceeds the supported 2048"):
+            m(dev(tokens), dev(mel2ph), dev(f0))
+    tokens, mel2ph, f0 = padded_inputs([70, 41], [150, 90], 70, 150, 98)
+    want = oe.fs2_acoustic_forward(params, tokens, mel2ph, f0, num_heads=2)
+    with torch.no_grad():
+        got = m(dev(tokens), dev(mel2ph), dev(f0))
+    check(got, want, TOL, what="after the rejection")
     m.release_native()
 
 

@@ -178,6 +178,55 @@ def test_token_encoders_other_ffn_activations_vs_oracle(act):
     model.melody_encoder.release_native()
 
 
+def test_token_encoder_head_dim_8_at_2048_tokens_and_2049_rejected():
+    """dsd_token_encode at its limits: 32 heads of D = 8 (RoPE on 4 pairs, 56 of 64 lanes idle in the P.V loop) over
+    L = 2048 tokens (all 32 key chunks, the last one ending in padding: 2000 real tokens), FastSpeech2Variance and its
+    duration predictor against the oracle; then L = 2049 is an error naming the limit, and the handle still works."""
+    from diffsinger_amd._lib import NativeLibraryError
+    from diffsinger_amd.variance import DiffSingerVariance
+    from gpu_util import check
+    tag = "word_reflow"
+    hp = vc.case_hparams(tag)
+    hp.update(num_heads=32)
+    hparams.clear()
+    hparams.update(hp, infer=True)
+    c = vc.CASES[tag]
+    model = DiffSingerVariance(c["vocab"])
+    shapes = vc.sorted_param_shapes(model.named_parameters())
+    assert shapes["fs2.encoder.layers.0.op.self_attn.rotary_embed.freqs"] == (4,)
+    params = vc.synth_weights(shapes, c["seed"] + 3)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=False)
+    fs2 = model.fs2.cuda().eval()
+    rng = np.random.Generator(np.random.PCG64(19))
+
+    def inputs(n_ph, n_real):
+        tokens = rng.integers(1, c["vocab"], (1, n_ph)).astype(np.int64)
+        tokens[:, n_real:] = 0
+        ph2word = np.zeros((1, n_ph), np.int64)
+        ph2word[0, :n_real] = np.cumsum(rng.random(n_real) < 0.4) + 1
+        ph2word[0, 0] = 1
+        midi = rng.integers(30, 90, (1, n_ph)).astype(np.int64) * (tokens > 0)
+        word_dur = rng.integers(1, 40, (1, int(ph2word.max()))).astype(np.int64)
+        return tokens, midi, ph2word, word_dur
+
+    def run(tokens, midi, ph2word, word_dur):
+        with torch.no_grad():
+            return fs2(dev(tokens), midi=dev(midi), ph2word=dev(ph2word), word_dur=dev(word_dur))
+
+    ok = inputs(2048, 2000)
+    tokens, midi, ph2word, word_dur = ok
+    want_enc, want_dur = ovar.fs2_variance_forward(ovar.sub(params, "fs2."), hp, tokens, midi, ph2word, word_dur=word_dur)
+    enc, dur = run(*ok)
+    check(enc, want_enc, 2e-4, what="enc")
+    assert np.abs(dur.cpu().numpy() - want_dur).max() < 2e-4 * max(1.0, np.abs(want_dur).max())
+    with pytest.raises(NativeLibraryError, match="L = 2049 tokens exceeds the supported 2048"):
+        run(*inputs(2049, 2049))
+    enc, dur = run(*ok)
+    check(enc, want_enc, 2e-4, what="enc after the rejection")
+    assert np.abs(dur.cpu().numpy() - want_dur).max() < 2e-4 * max(1.0, np.abs(want_dur).max())
+    fs2.release_native()
+
+
 def test_cond_assemble_matches_torch_and_rejects_bad_arguments():
     from diffsinger_amd import _lib
     from diffsinger_amd.variance import assemble
