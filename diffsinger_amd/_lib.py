@@ -27,6 +27,7 @@ EXPORTS = [
     "dsd_finalize_weights", "dsd_prepare_cond", "dsd_denoise", "dsd_sample", "dsd_get_stats",
     "dsd_kernel_timing", "dsd_kernel_timing_read", "dsd_kernel_timing_classes", "dsd_set_precision", "dsd_aux_decode", "dsd_encoder_create", "dsd_encode", "dsd_vocoder_create", "dsd_vocode", "dsd_vocode_ragged",
     "dsd_token_encoder_create", "dsd_token_encode", "dsd_predict_dur", "dsd_cond_assemble", "dsd_set_lengths",
+    "dsd_mel_create", "dsd_mel_filterbank", "dsd_mel_num_frames", "dsd_mel_analyze",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -53,6 +54,12 @@ class DsdVocoderConfig(C.Structure):
                 ("resblock_kernel_sizes", C.c_int32 * 8), ("n_dilations", C.c_int32 * 8),
                 ("resblock_dilation_sizes", (C.c_int32 * 4) * 8), ("harmonic_num", C.c_int32), ("mini_nsf", C.c_int32),
                 ("noise_sigma", C.c_float), ("device", C.c_int32)]
+
+
+class DsdMelConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("sampling_rate", C.c_int32), ("n_fft", C.c_int32), ("win_size", C.c_int32),
+                ("hop_size", C.c_int32), ("num_mels", C.c_int32), ("fmin", C.c_double), ("fmax", C.c_double),
+                ("clip_val", C.c_double), ("device", C.c_int32)]
 
 
 class DsdTokenEncoderConfig(C.Structure):
@@ -153,6 +160,11 @@ def _load():
     lib.dsd_cond_assemble.argtypes = [C.POINTER(DsdAssembleArgs), vp, vp]
     lib.dsd_set_lengths.argtypes = [vp, C.POINTER(C.c_int32), i32, vp]
     lib.dsd_encode.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(DsdEncodeExtras), vp, vp]
+    lib.dsd_mel_create.argtypes = [C.POINTER(DsdMelConfig), C.POINTER(vp)]
+    lib.dsd_mel_filterbank.argtypes = [C.POINTER(DsdMelConfig), C.POINTER(C.c_float)]
+    lib.dsd_mel_num_frames.argtypes = [C.POINTER(DsdMelConfig), i64, C.c_double, C.c_double]
+    lib.dsd_mel_num_frames.restype = i64
+    lib.dsd_mel_analyze.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), C.c_double, C.c_double, vp, i64, i64, i64, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

@@ -12,6 +12,7 @@
 //   variance-model encoders .......... dsd_token_encoder_create, dsd_token_encode, dsd_predict_dur, dsd_cond_assemble
 //   vocoder .......................... run_tconv, dsd_vocoder_create, dsd_vocode, dsd_vocode_ragged
 //   aux decoder ...................... dsd_aux_decode
+//   mel analysis ..................... dsd_mel_create, dsd_mel_filterbank, dsd_mel_num_frames, dsd_mel_analyze (mel_kernels.hip)
 //   diagnostics ...................... dsd_get_stats, dsd_kernel_timing*
 #include <math.h>
 #include <stdarg.h>
@@ -109,6 +110,25 @@ struct VocRagStage {
     int ntc = 0;
 };
 
+// dsd_mel_analyze: per handle, the filterbank on the device and the DFT bases of the (N', W') sizes met so far
+struct MelBasis {
+    int N = 0, W = 0;
+    float* dev = nullptr;
+};
+struct MelState {
+    dsd_mel_config cfg;
+    int k_lo = 0, k_hi = -1;            // the bins any filter reads (k_hi < k_lo: none)
+    std::vector<int> range_host;        // [M][2] bins [lo, hi) relative to k_lo
+    int *range = nullptr, *woff = nullptr;
+    float* fw = nullptr;                // packed non-zero runs
+    std::vector<MelBasis> bases;        // most recent last
+    std::vector<int> work_host;
+    int* work = nullptr;
+    size_t work_cap = 0;
+    float* mags = nullptr;
+    size_t mags_cap = 0;
+};
+
 struct dsd_handle {
     dsd_config cfg;
     std::string err;
@@ -155,6 +175,8 @@ struct dsd_handle {
     int* vr_dev = nullptr;
     size_t vr_cap = 0;
     std::vector<VocRagStage> vr_st;
+    // mel analysis (dsd_mel_create): the config, the filterbank's packed non-zero runs and the device blocks of dsd_mel_analyze
+    MelState* mel = nullptr;
     // FastSpeech2 acoustic encoder
     dsd_encoder_config ecfg;
     std::vector<PackedGemm> g_qkv, g_oproj, g_ffn1, g_ffn2;
@@ -298,6 +320,9 @@ inline bool is_aux(const dsd_handle* h) { return h->cfg.backbone == DSD_AUX_CONV
 inline bool is_enc(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_ACOUSTIC; }
 inline bool is_tok(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_TOKENS; }
 inline bool is_voc(const dsd_handle* h) { return h->cfg.backbone == DSD_VOC_NSF_HIFIGAN; }
+inline bool is_mel(const dsd_handle* h) { return h->cfg.backbone == DSD_MEL_ANALYSIS; }
+#define MEL_HANDLE_REJECT(h, who) \
+    if (is_mel(h)) return fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is a mel analysis handle (use dsd_mel_analyze)", who)
 
 inline int voc_stage_channels(const dsd_vocoder_config& v, int i) { return v.upsample_initial_channel >> (i + 1); }
 inline long voc_upp(const dsd_vocoder_config& v, int from) {     // product of upsample_rates[from:]
@@ -2123,12 +2148,19 @@ void dsd_destroy(dsd_handle* h) {
     if (h->e_arena) (void)hipFree(h->e_arena);
     if (h->v_arena) (void)hipFree(h->v_arena);
     if (h->vr_dev) (void)hipFree(h->vr_dev);
+    if (MelState* m = h->mel) {
+        for (auto& bs : m->bases) (void)hipFree(bs.dev);
+        for (void* p : {(void*)m->range, (void*)m->woff, (void*)m->fw, (void*)m->work, (void*)m->mags})
+            if (p) (void)hipFree(p);
+        delete m;
+    }
     delete h;
 }
 
 int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim,
                     int32_t on_device) {
     if (!h || !name || !data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
+    MEL_HANDLE_REJECT(h, "dsd_load_weight");
     const std::string n(name);
     std::vector<int64_t> shp(shape, shape + ndim);
     bool found = false;
@@ -2171,6 +2203,7 @@ int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const in
 
 int dsd_finalize_weights(dsd_handle* h) {
     if (!h) return DSD_EINVAL;
+    MEL_HANDLE_REJECT(h, "dsd_finalize_weights");
     std::string missing;
     for (auto& e : expected_for(h))
         if (!h->raw.count(e.first)) missing += (missing.empty() ? "" : ", ") + e.first;
@@ -2199,6 +2232,7 @@ int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int
     if (is_aux(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an aux decoder (use dsd_aux_decode)");
     if (is_enc(h) || is_tok(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an encoder (use dsd_encode / dsd_token_encode)");
     if (is_voc(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is a vocoder (use dsd_vocode)");
+    MEL_HANDLE_REJECT(h, "dsd_prepare_cond");
     if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_prepare_cond: weights are not finalized");
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_prepare_cond: B and T must be positive (B=%d, T=%d)", B, T);
     if (stride_t != 1 && stride_h != 1)
@@ -3135,7 +3169,7 @@ int dsd_set_precision(dsd_handle* h, int32_t mode) {
 
 int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stream) {
     if (!h) return DSD_EINVAL;
-    if (is_enc(h) || is_tok(h) || is_voc(h))
+    if (is_enc(h) || is_tok(h) || is_voc(h) || is_mel(h))
         return fail(h, DSD_ESTATE, "dsd_set_lengths: only denoiser and aux-decoder handles take ragged batches");
     if (!lengths) {             // back to dense batches
         h->lens_host.clear();
@@ -3163,6 +3197,7 @@ int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stre
 
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
     if (!h || !out) return DSD_EINVAL;
+    MEL_HANDLE_REJECT(h, "dsd_get_stats");
     memset(out, 0, sizeof(*out));
     const int64_t C = h->c_user ? h->c_user : C_of(h), M = FM_of(h), L = L_of(h);
     out->weight_bytes = (int64_t)h->blob_floats * 4;
@@ -3206,6 +3241,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
 
 int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
     if (!h) return DSD_EINVAL;
+    MEL_HANDLE_REJECT(h, "dsd_kernel_timing");
     h->timing = enable != 0;
     h->tclasses.clear();
     h->timing_evals = 0;
@@ -3218,6 +3254,7 @@ int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
 int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_classes, int32_t* n_classes,
                               double* empty_pair_ms) {
     if (!h || !out || !n_classes || max_classes < 1) return DSD_EINVAL;
+    MEL_HANDLE_REJECT(h, "dsd_kernel_timing_classes");
     HIP_OK(h, hipSetDevice(h->cfg.device));
     int n = 0;
     // largest share of the evaluation first
@@ -3266,6 +3303,7 @@ int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_c
 
 int dsd_kernel_timing_read(dsd_handle* h, double* mean_ms, double* empty_pair_ms, int64_t* launches) {
     if (!h || !mean_ms || !empty_pair_ms || !launches) return DSD_EINVAL;
+    MEL_HANDLE_REJECT(h, "dsd_kernel_timing_read");
     dsd_kernel_time top;
     int32_t n = 0;
     int rc = dsd_kernel_timing_classes(h, &top, 1, &n, empty_pair_ms);      // the class with the largest share of the pass
@@ -3276,6 +3314,297 @@ int dsd_kernel_timing_read(dsd_handle* h, double* mean_ms, double* empty_pair_ms
     h->timing_evals = 0;
     h->ev_used = 0;
     h->cal_used = 0;
+    return DSD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Mel analysis (dsd_mel_*): STFT.get_mel, modules/nsf_hifigan/nvSTFT.py:50-87
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int mel_check_config(const dsd_mel_config* c, const char* who) {
+    if (!c) return fail(nullptr, DSD_EINVAL, "%s: null config", who);
+    if (c->struct_size != (int32_t)sizeof(dsd_mel_config))
+        return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, c->struct_size, sizeof(dsd_mel_config));
+    if (c->sampling_rate < 1 || c->n_fft < 2 || c->n_fft > 16384 || c->win_size < 1 || c->win_size > c->n_fft ||
+        c->hop_size < 1 || c->num_mels < 1 || c->num_mels > 1024)
+        return fail(nullptr, DSD_EINVAL, "%s: need sampling_rate >= 1, 2 <= n_fft <= 16384, 1 <= win_size <= n_fft, hop_size >= 1 "
+                    "and 1 <= num_mels <= 1024", who);
+    if (!(c->fmin >= 0.0) || !(c->fmax > c->fmin) || !std::isfinite(c->fmax))
+        return fail(nullptr, DSD_EINVAL, "%s: need 0 <= fmin < fmax (got %g, %g)", who, c->fmin, c->fmax);
+    if (!(c->clip_val > 0.0) || !std::isfinite(c->clip_val)) return fail(nullptr, DSD_EINVAL, "%s: clip_val must be > 0", who);
+    return DSD_OK;
+}
+
+// librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) with its defaults (htk=False, norm="slaney", dtype=float32), restated
+// step by step in float64 as librosa computes it: Slaney scale (linear at 200/3 Hz per mel below 1000 Hz = 15 mel,
+// logarithmic above with step ln(6.4) / 27), np.linspace of the mel points, np.fft.rfftfreq bin centres, triangles stored
+// into the float32 array, then the area normalisation 2 / (f[i+2] - f[i]) multiplied in place (a float32 result).
+double slaney_hz_to_mel(double f) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+    return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
+}
+double slaney_mel_to_hz(double m) {
+    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+    return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
+}
+void mel_filterbank_host(const dsd_mel_config& c, std::vector<float>& w) {
+    const int M = c.num_mels, K = c.n_fft / 2 + 1, n = M + 2;
+    const double lo = slaney_hz_to_mel(c.fmin), hi = slaney_hz_to_mel(c.fmax), step = (hi - lo) / (double)(n - 1);
+    std::vector<double> mel_f(n), fft_f(K);
+    for (int i = 0; i < n; ++i) {
+        const double m = (double)i * step;      // np.linspace: arange * step + start, the end point set to stop
+        mel_f[i] = slaney_mel_to_hz(i == n - 1 ? hi : m + lo);
+    }
+    const double val = 1.0 / ((double)c.n_fft * (1.0 / (double)c.sampling_rate));      // np.fft.rfftfreq(n_fft, 1 / sr)
+    for (int k = 0; k < K; ++k) fft_f[k] = (double)k * val;
+    w.assign((size_t)M * K, 0.f);
+    for (int i = 0; i < M; ++i) {
+        const double d0 = mel_f[i + 1] - mel_f[i], d1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
+        for (int k = 0; k < K; ++k) {
+            const double lower = -(mel_f[i] - fft_f[k]) / d0, upper = (mel_f[i + 2] - fft_f[k]) / d1;
+            const float tri = (float)std::max(0.0, std::min(lower, upper));
+            w[(size_t)i * K + k] = (float)((double)tri * enorm);
+        }
+    }
+}
+
+// The STFT geometry of one (keyshift, speed) (nvSTFT.py:52-66): np.round is round-half-even, as nearbyint
+struct MelGeom {
+    int N, W, H, off, padL, padR;
+    bool rescale;
+};
+bool mel_geometry(const dsd_mel_config& c, double keyshift, double speed, MelGeom& g) {
+    if (!std::isfinite(keyshift) || !std::isfinite(speed) || !(speed > 0.0)) return false;
+    const double factor = pow(2.0, keyshift / 12.0);
+    const double N = nearbyint(c.n_fft * factor), W = nearbyint(c.win_size * factor), H = nearbyint(c.hop_size * speed);
+    if (!(N >= 1 && N <= 32768 && W >= 1 && W <= N && H >= 1 && H <= (1 << 24))) return false;
+    g.N = (int)N;
+    g.W = (int)W;
+    g.H = (int)H;
+    g.off = (g.N - g.W) / 2;                               // torch.stft centres a shorter window in the frame
+    const int d = g.W - g.H;                               // Python floor division of d and d + 1 by 2
+    g.padL = d >= 0 ? d / 2 : -((-d + 1) / 2);
+    g.padR = d + 1 >= 0 ? (d + 1) / 2 : -((-(d + 1) + 1) / 2);
+    g.rescale = keyshift != 0.0;
+    return true;
+}
+// T of an item of L samples, or -1 where torch raises (reflect pad >= L, padded signal shorter than N')
+int64_t mel_frames(const MelGeom& g, int64_t L) {
+    if (L < 1 || g.padL >= L || g.padR >= L) return -1;
+    const int64_t Lp = L + g.padL + g.padR;
+    if (Lp < g.N) return -1;
+    return 1 + (Lp - g.N) / g.H;
+}
+
+}  // namespace
+
+int dsd_mel_filterbank(const dsd_mel_config* cfg, float* out) {
+    int rc = mel_check_config(cfg, "dsd_mel_filterbank");
+    if (rc) return rc;
+    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_mel_filterbank: null output");
+    std::vector<float> w;
+    mel_filterbank_host(*cfg, w);
+    memcpy(out, w.data(), w.size() * sizeof(float));
+    return DSD_OK;
+}
+
+int64_t dsd_mel_num_frames(const dsd_mel_config* cfg, int64_t n_samples, double keyshift, double speed) {
+    if (mel_check_config(cfg, "dsd_mel_num_frames")) return DSD_EINVAL;
+    MelGeom g;
+    if (!mel_geometry(*cfg, keyshift, speed, g)) return fail(nullptr, DSD_EINVAL, "dsd_mel_num_frames: bad keyshift / speed");
+    const int64_t T = mel_frames(g, n_samples);
+    if (T < 1) return fail(nullptr, DSD_EINVAL, "dsd_mel_num_frames: %lld samples are too short (torch.stft / reflect pad raise)",
+                           (long long)n_samples);
+    return T;
+}
+
+int dsd_mel_create(const dsd_mel_config* cfg, dsd_handle** out) {
+    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_mel_create: null argument");
+    int rc = mel_check_config(cfg, "dsd_mel_create");
+    if (rc) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, DSD_EHIP, "dsd_mel_create: no HIP device is visible (this library has no CPU path)");
+    if (cfg->device < 0 || cfg->device >= ndev)
+        return fail(nullptr, DSD_EINVAL, "dsd_mel_create: device %d out of range [0, %d)", cfg->device, ndev);
+    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_mel_create: hipSetDevice failed");
+    // the non-zero run of every filter (librosa's triangles are contiguous), packed
+    std::vector<float> w;
+    mel_filterbank_host(*cfg, w);
+    const int M = cfg->num_mels, K = cfg->n_fft / 2 + 1;
+    std::vector<int> first(M, -1), last(M, -2);
+    int k_lo = K, k_hi = -1;
+    for (int m = 0; m < M; ++m) {
+        for (int k = 0; k < K; ++k)
+            if (w[(size_t)m * K + k] != 0.f) {
+                if (first[m] < 0) first[m] = k;
+                last[m] = k;
+            }
+        if (first[m] >= 0) {
+            k_lo = std::min(k_lo, first[m]);
+            k_hi = std::max(k_hi, last[m]);
+        }
+    }
+    if (k_hi < 0) k_lo = 0;
+    std::vector<int> range(2 * M), woff(M);
+    std::vector<float> fw;
+    for (int m = 0; m < M; ++m) {
+        woff[m] = (int)fw.size();
+        if (first[m] < 0) {
+            range[2 * m] = range[2 * m + 1] = 0;
+            continue;
+        }
+        range[2 * m] = first[m] - k_lo;
+        range[2 * m + 1] = last[m] + 1 - k_lo;
+        for (int k = first[m]; k <= last[m]; ++k) fw.push_back(w[(size_t)m * K + k]);
+    }
+    fw.push_back(0.f);       // never empty
+    dsd_handle* h = new dsd_handle();
+    memset(&h->cfg, 0, sizeof(h->cfg));
+    h->cfg.struct_size = sizeof(dsd_config);
+    h->cfg.backbone = DSD_MEL_ANALYSIS;
+    h->cfg.in_dims = M;
+    h->cfg.n_feats = 1;
+    h->cfg.device = cfg->device;
+    MelState* ms = h->mel = new MelState();
+    ms->cfg = *cfg;
+    ms->k_lo = k_lo;
+    ms->k_hi = k_hi;
+    ms->range_host = range;
+    if (hipMalloc(&ms->range, sizeof(int) * range.size()) != hipSuccess || hipMalloc(&ms->woff, sizeof(int) * M) != hipSuccess ||
+        hipMalloc(&ms->fw, sizeof(float) * fw.size()) != hipSuccess) {
+        dsd_destroy(h);
+        return fail(nullptr, DSD_ENOMEM, "dsd_mel_create: hipMalloc of the filterbank failed");
+    }
+    if (hipMemcpy(ms->range, range.data(), sizeof(int) * range.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ms->woff, woff.data(), sizeof(int) * M, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(ms->fw, fw.data(), sizeof(float) * fw.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        dsd_destroy(h);
+        return fail(nullptr, DSD_EHIP, "dsd_mel_create: upload of the filterbank failed");
+    }
+    *out = h;
+    return DSD_OK;
+}
+
+int dsd_mel_analyze(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
+                    const int64_t* lengths, double keyshift, double speed, float* mel_out, int64_t stride_b,
+                    int64_t stride_m, int64_t stride_t, void* stream) {
+    if (!h || !wav || !mel_out) return fail(h, DSD_EINVAL, "dsd_mel_analyze: null argument");
+    if (!is_mel(h)) return fail(h, DSD_ESTATE, "dsd_mel_analyze: this handle is not a mel analysis handle (dsd_mel_create)");
+    MelState& ms = *h->mel;
+    const dsd_mel_config& c = ms.cfg;
+    if (B < 1 || n_samples < 1) return fail(h, DSD_EINVAL, "dsd_mel_analyze: B and n_samples must be positive (%d, %lld)", B,
+                                            (long long)n_samples);
+    if (n_samples > ((int64_t)1 << 31) - 1 || (B > 1 && wav_stride_b < n_samples))
+        return fail(h, DSD_EINVAL, "dsd_mel_analyze: n_samples must be < 2^31 and wav_stride_b >= n_samples");
+    MelGeom g;
+    if (!mel_geometry(c, keyshift, speed, g))
+        return fail(h, DSD_EINVAL, "dsd_mel_analyze: keyshift %g / speed %g give no valid STFT size", keyshift, speed);
+    // work list: (item, 64-frame tile) entries over the frames each item has
+    std::vector<int>& work = ms.work_host;
+    work.clear();
+    int64_t G = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t L = lengths ? lengths[b] : n_samples;
+        if (L < 1 || L > n_samples) return fail(h, DSD_EINVAL, "dsd_mel_analyze: lengths[%d] = %lld outside [1, %lld]", b,
+                                                (long long)L, (long long)n_samples);
+        const int64_t T = mel_frames(g, L);
+        if (T < 1)
+            return fail(h, DSD_EINVAL, "dsd_mel_analyze: item %d (%lld samples) is too short for N' = %d, W' = %d, H' = %d "
+                        "(torch.stft / reflect pad raise)", b, (long long)L, g.N, g.W, g.H);
+        for (int64_t t0 = 0; t0 < T; t0 += 64) {
+            const int e[5] = {b, (int)t0, (int)L, (int)T, (int)(G + t0)};
+            work.insert(work.end(), e, e + 5);
+        }
+        G += T;
+        if (G > ((int64_t)1 << 30)) return fail(h, DSD_EINVAL, "dsd_mel_analyze: too many frames in one call");
+    }
+    const int n_entries = (int)(work.size() / 5);
+    // bins the filterbank reads that this N' has: nvSTFT.py:76-80 zero-pads the bins past N'/2
+    const int k_hi = std::min(ms.k_hi, g.N / 2), nb = std::max(0, k_hi - ms.k_lo + 1);
+    const int row_tiles = (2 * nb + 63) / 64, Kpad = (g.W + 31) / 32 * 32;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    float* basis = nullptr;
+    if (nb > 0) {
+        for (size_t i = 0; i < ms.bases.size(); ++i)
+            if (ms.bases[i].N == g.N && ms.bases[i].W == g.W) {
+                std::rotate(ms.bases.begin() + i, ms.bases.begin() + i + 1, ms.bases.end());      // most recent last
+                basis = ms.bases.back().dev;
+                break;
+            }
+        if (!basis) {
+            if (ms.bases.size() == 4) {       // continuous keyshift draws: keep the four most recent sizes
+                (void)hipFree(ms.bases.front().dev);
+                ms.bases.erase(ms.bases.begin());
+            }
+            const size_t n = (size_t)row_tiles * 64 * Kpad;
+            if (hipMalloc(&basis, n * sizeof(float)) != hipSuccess)
+                return fail(h, DSD_ENOMEM, "dsd_mel_analyze: hipMalloc of the %d x %d DFT basis failed", row_tiles * 64, Kpad);
+            MelBasis mb;
+            mb.N = g.N;
+            mb.W = g.W;
+            mb.dev = basis;
+            ms.bases.push_back(mb);
+            hipError_t e = launch_mel_basis(basis, row_tiles * 64, Kpad, ms.k_lo, nb, g.N, g.W, g.off, st);
+            if (e != hipSuccess) return fail(h, DSD_EHIP, "mel basis launch failed: %s", hipGetErrorString(e));
+        }
+    }
+    if (work.size() > ms.work_cap) {
+        if (ms.work) (void)hipFree(ms.work);
+        ms.work = nullptr;
+        ms.work_cap = 0;
+        if (hipMalloc(&ms.work, sizeof(int) * work.size()) != hipSuccess)
+            return fail(h, DSD_ENOMEM, "dsd_mel_analyze: hipMalloc of the work list failed");
+        ms.work_cap = work.size();
+    }
+    HIP_OK(h, hipMemcpyAsync(ms.work, work.data(), sizeof(int) * work.size(), hipMemcpyHostToDevice, st));
+    const size_t mags_n = std::max<size_t>(1, (size_t)nb * (size_t)G);
+    if (mags_n > ms.mags_cap) {
+        if (ms.mags) (void)hipFree(ms.mags);
+        ms.mags = nullptr;
+        ms.mags_cap = 0;
+        if (hipMalloc(&ms.mags, sizeof(float) * mags_n) != hipSuccess)
+            return fail(h, DSD_ENOMEM, "dsd_mel_analyze: hipMalloc of %zu magnitudes failed", mags_n);
+        ms.mags_cap = mags_n;
+    }
+    if (nb > 0) {
+        MelDftP p;
+        p.wav = wav;
+        p.wav_bstride = (long)wav_stride_b;
+        p.work = ms.work;
+        p.basis = basis;
+        p.Kpad = Kpad;
+        p.W = g.W;
+        p.H = g.H;
+        p.off = g.off;
+        p.padL = g.padL;
+        p.nb = nb;
+        p.rescale = g.rescale ? 1 : 0;
+        p.win_size = (float)c.win_size;
+        p.win_new = (float)g.W;
+        p.mags = ms.mags;
+        p.G = (long)G;
+        hipError_t e = launch_mel_dft(p, n_entries, row_tiles, st);
+        if (e != hipSuccess) return fail(h, DSD_EHIP, "mel DFT launch failed: %s", hipGetErrorString(e));
+    }
+    MelProjP q;
+    q.work = ms.work;
+    q.mags = ms.mags;
+    q.G = (long)G;
+    q.nb = nb;
+    q.M = c.num_mels;
+    q.range = ms.range;
+    q.woff = ms.woff;
+    q.fw = ms.fw;
+    q.clip = (float)c.clip_val;
+    q.out = mel_out;
+    q.o_sb = (long)stride_b;
+    q.o_sm = (long)stride_m;
+    q.o_st = (long)stride_t;
+    hipError_t e = launch_mel_project(q, n_entries, st);
+    if (e != hipSuccess) return fail(h, DSD_EHIP, "mel projection launch failed: %s", hipGetErrorString(e));
     return DSD_OK;
 }
 

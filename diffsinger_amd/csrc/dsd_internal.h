@@ -405,4 +405,34 @@ hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T,
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
                          const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream);
 
+// mel_kernels.hip: waveform -> log-mel (dsd_mel_analyze).  work: 5 ints per (item, 64-frame tile) entry = item b, first
+// frame t0, item length L in samples, item frame count T_b, index of the entry's first frame in the magnitude buffer
+struct MelDftP {
+    const float* wav;
+    long wav_bstride;
+    const int* work;
+    const float* basis;     // [row tiles * 64][Kpad] (mel_basis_kernel)
+    int Kpad, W, H, off, padL;
+    int nb;                 // bins computed: k_lo .. k_lo + nb - 1
+    int rescale;            // keyshift != 0: |X| * win_size / W'
+    float win_size, win_new;
+    float* mags;            // [nb][G]
+    long G;                 // frames of the whole call
+};
+struct MelProjP {
+    const int* work;
+    const float* mags;
+    long G;
+    int nb, M;
+    const int* range;       // [M][2]: bins [lo, hi) relative to k_lo
+    const int* woff;        // [M]: offset of filter m's packed weights in fw
+    const float* fw;
+    float clip;
+    float* out;
+    long o_sb, o_sm, o_st;
+};
+hipError_t launch_mel_basis(float* basis, int Rpad, int Kpad, int k_lo, int nb, int N, int W, int off, hipStream_t st);
+hipError_t launch_mel_dft(const MelDftP& p, int n_entries, int row_tiles, hipStream_t st);
+hipError_t launch_mel_project(const MelProjP& p, int n_entries, hipStream_t st);
+
 }  // namespace dsd

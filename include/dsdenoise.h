@@ -49,7 +49,10 @@ enum { DSD_BACKBONE_WAVENET = 0, DSD_BACKBONE_LYNXNET = 1,
        DSD_VOC_NSF_HIFIGAN = 4,
        /* modules/fastspeech/tts_modules.py:353  FastSpeech2Encoder on caller-assembled embeddings (+ DurationPredictor /
           out_proj): the encoders of the variance model; created with dsd_token_encoder_create */
-       DSD_ENC_FS2_TOKENS = 5 };
+       DSD_ENC_FS2_TOKENS = 5,
+       /* modules/nsf_hifigan/nvSTFT.py:26  STFT (waveform -> log-mel analysis, no weights; see dsd_mel_analyze);
+          created with dsd_mel_create */
+       DSD_MEL_ANALYSIS = 6 };
 /* modules/backbones/lynxnet.py:38-42  activation_classes */
 enum { DSD_ACT_PRELU = 0, DSD_ACT_SILU = 1, DSD_ACT_RELU = 2 };
 
@@ -356,6 +359,56 @@ int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int
  * / dsd_sample / dsd_aux_decode calls at batch size B until changed; NULL restores dense batches.
  */
 int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Mel analysis: waveform -> natural-log mel, the analysis front end the reference pairs with its vocoder (resynthesis
+ * inference/val_nsf_hifigan.py:65, the binarizer's mel preprocessing/acoustic_binarizer.py:103 through get_mel_torch
+ * utils/binarizer_utils.py:13-26, key-shift / speed augmentation augmentation/spec_stretch.py:31).  The output is what
+ * dsd_vocode takes.  A mel handle has no weights: every other entry point returns DSD_ESTATE on it, and the mel entry
+ * points return DSD_ESTATE on any other handle.
+ * ------------------------------------------------------------------------------------------ */
+/* STFT.__init__(sr, n_mels, n_fft, win_size, hop_length, fmin, fmax, clip_val)  (nvSTFT.py:27-48) */
+typedef struct dsd_mel_config {
+    int32_t struct_size;      /* sizeof(dsd_mel_config)                                      */
+    int32_t sampling_rate;    /* sr                                                          */
+    int32_t n_fft;
+    int32_t win_size;         /* <= n_fft                                                    */
+    int32_t hop_size;         /* hop_length                                                  */
+    int32_t num_mels;         /* n_mels                                                      */
+    double fmin, fmax;        /* Hz, 0 <= fmin < fmax                                        */
+    double clip_val;          /* dynamic_range_compression_torch's clamp (nvSTFT.py:19-20)   */
+    int32_t device;
+} dsd_mel_config;
+
+int dsd_mel_create(const dsd_mel_config* cfg, dsd_handle** out);
+/*
+ * Replaces: librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) as nvSTFT.py:47-48 calls it: Slaney mel scale, Slaney area
+ * normalisation, float32 weights (the library's one definition of the filterbank).  Host only, no device needed.
+ * out: [num_mels][n_fft / 2 + 1] host floats.
+ */
+int dsd_mel_filterbank(const dsd_mel_config* cfg, float* out);
+/*
+ * Frame count of STFT.get_mel(y, keyshift, speed, center=False) on n_samples samples (nvSTFT.py:52-75):
+ *   N' = round(n_fft 2^(keyshift/12)), W' = round(win_size 2^(keyshift/12)), H' = round(hop_size speed) (ties to even),
+ *   reflect pads (W'-H')//2 and (W'-H'+1)//2 (floor division: negative pads crop),  T = 1 + (L + pads - N') // H'.
+ * Returns T >= 1, or DSD_EINVAL where torch raises (a reflect pad >= n_samples, a padded signal shorter than N') or the
+ * configuration / keyshift / speed is invalid.  Host only.
+ */
+int64_t dsd_mel_num_frames(const dsd_mel_config* cfg, int64_t n_samples, double keyshift, double speed);
+/*
+ * Replaces: STFT.get_mel(y, keyshift, speed, center=False)  (nvSTFT.py:50-87): reflect pad, torch.stft with the periodic
+ * Hann window centred in the N'-sample frame, |X|, with keyshift != 0 the bins zero-padded / truncated to n_fft/2 + 1 and
+ * scaled by win_size / W', the mel projection, log(clamp(., clip_val)).
+ *   wav      item b's sample s at wav[b * wav_stride_b + s], s < n_samples (device fp32)
+ *   lengths  HOST array of B sample counts (1 <= lengths[b] <= n_samples) or NULL (every item n_samples long).  Item b is
+ *            computed exactly as a lone call on its own lengths[b] samples: reflected at its own end, nothing past it read.
+ *   mel_out  element (b, m, t) at mel_out[b * stride_b + m * stride_m + t * stride_t], t < T_b = dsd_mel_num_frames(cfg,
+ *            lengths[b], keyshift, speed) ([B, num_mels, T] or [B, T, num_mels] views); frames at or past T_b are not written.
+ * One (keyshift, speed) per call.  The DFT basis of each (N', W') is built on the device at its first use and cached.
+ */
+int dsd_mel_analyze(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
+                    const int64_t* lengths, double keyshift, double speed, float* mel_out, int64_t stride_b,
+                    int64_t stride_m, int64_t stride_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sampling programs.  Every sampler of the reference (ddpm.py:149-204,221-351 p_sample /
