@@ -1661,6 +1661,17 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
     return pl;
 }
 
+// A path switch whose value no launch form matches fails the call before it launches anything (never another form in its place):
+// DSD_LYNX_PW1P = g row-tile groups must divide LYNXNet's 2 inner / 512 row tiles and be below their count - on every grid, not
+// only on those where plan_denoise picks the resident pw1
+int check_path_opts(dsd_handle* h) {
+    const int pw1p = h->opts.lynx_pw1p, C = C_of(h), inner = inner_of(h);
+    if (!is_wavenet(h) && !is_aux(h) && lx_layer_supported(C, inner) && !lx_pw1p_force_ok(inner, pw1p))
+        return fail(h, DSD_EINVAL, "DSD_LYNX_PW1P=%d: not a pw1 form of this network (-1: by rounds, 0: one row tile per workgroup, "
+                    "or a row-tile group count that divides the %d row tiles of inner = %d and is below it)", pw1p, 2 * inner / 512, inner);
+    return DSD_OK;
+}
+
 // Layer `layer`'s FiLM vector d[c] for step column col0 (+ colb per batch item): kernels read film[c * cstride + c0 + b * cb].
 // From the transposed table Dt [step][L * C] that is C contiguous floats (run_step_tables: reading D [L * C][Ns] directly, one
 // cache line per row, was measured and removed)
@@ -2992,8 +3003,8 @@ int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, fl
     hipStream_t st = (hipStream_t)stream;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, T = h->T, Ts = h->Ts, FM = FM_of(h);
-    int rc = check_lens(h, "dsd_denoise", B, T, st);
-    if (rc) return rc;
+    int rc = check_path_opts(h);
+    if (rc || (rc = check_lens(h, "dsd_denoise", B, T, st))) return rc;
     const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_emb(h, t_len))) return rc;
     HIP_OK(h, hipMemcpyAsync(h->t_dev, t, sizeof(float) * t_len, hipMemcpyDeviceToDevice, st));
@@ -3042,8 +3053,8 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
             }
         }
     }
-    int rc = check_lens(h, "dsd_sample", B, T, st);
-    if (rc) return rc;
+    int rc = check_path_opts(h);
+    if (rc || (rc = check_lens(h, "dsd_sample", B, T, st))) return rc;
     const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_state(h, prog->n_bufs, st))) return rc;
     if (prog->n_evals > 0 && (rc = ensure_emb(h, prog->n_evals))) return rc;

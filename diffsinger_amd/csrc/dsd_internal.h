@@ -40,7 +40,7 @@ struct PathOpts {
     int rs_rows = -1;       // DSD_RS_ROWS         64 / 128 / 256: rows per workgroup of the row-split pair
     int edge = -1;          // DSD_EDGE            0: never wn_edge.hip, 1: on every grid
     int lynx_resident = -1; // DSD_LYNX_RESIDENT   0: never lynx_layer.hip, 1: on every supported grid
-    int lynx_pw1p = -1;     // DSD_LYNX_PW1P       0 / 1: pw1 with one workgroup per (frame tile, row tile) / per frame tile
+    int lynx_pw1p = -1;     // DSD_LYNX_PW1P       0: pw1 with one workgroup per (frame tile, row tile), g >= 1: g per frame tile
     int lynx_pw2q = -1;     // DSD_LYNX_PW2Q       0: never the 128-row pw2 of one-utterance grids (gemm.hip instead), 1: on every grid
     int precision = -1;     // DSD_PRECISION       1: split-bf16 (bf16x3) layer kernels where they exist (opt-in, own tolerance)
     int x3_wide = -1;       // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet kernels, 1: wherever they exist
@@ -298,6 +298,8 @@ struct LxLayerP {
 // which: 0 = pw1, 1 = pw2;  pw1p: DSD_LYNX_PW1P;  cus: compute units of the device (pw1's row-tile groups)
 hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int cus, hipStream_t st);
 bool lx_layer_supported(int C, int inner);
+// DSD_LYNX_PW1P = force: -1 (by rounds), 0 (lx_pw1_kernel) or a row-tile group count g that divides 2 inner / 512 and is below it
+bool lx_pw1p_force_ok(int inner, int force);
 hipError_t launch_lx_pw2q(const LxLayerP& p, int C, hipStream_t st);      // pw2 with 128 rows per workgroup: one-utterance grids
 bool lx_pw2q_supported(int C, int inner);
 hipError_t lx_layer_init_all();

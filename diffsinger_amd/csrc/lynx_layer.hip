@@ -1055,9 +1055,10 @@ static hipError_t lx_launch_pw1p(const LxLayerP& p, int nwg, hipStream_t st) {
 // frame tile) - 1: all row tiles in one workgroup (lx_pw1p_kernel as in round 2), 2 / 4: half / a quarter of them, 0: one
 // workgroup per (frame tile, row tile) = lx_pw1_kernel.  By rounds of the chip: a workgroup takes ~11 us of prologue (statistics
 // merge, 128 KiB staging, launch ramp) + ~60 us per row tile (484 us at B = 8 for 8 row tiles, 254 for 4, 132 for 2); the
-// groups that fill whole rounds win - B = 2 / 4 / 6 at T = 1000: 4 / 2 / 4 groups.  force (DSD_LYNX_PW1P) = 0/1: none / one group.
+// groups that fill whole rounds win - B = 2 / 4 / 6 at T = 1000: 4 / 2 / 4 groups.  force (DSD_LYNX_PW1P) = 0: lx_pw1_kernel,
+// g >= 1: exactly g groups (lx_pw1p_force_ok: checked before the call launches anything).
 static int lx_pw1p_groups(int nft, int mtiles, int force, int cus) {
-    if (force >= 0) return force != 0 ? 1 : 0;
+    if (force >= 0) return force;
     int best = 0;
     double best_t = 1e30;
     for (int g = 1; g <= mtiles; g *= 2) {
@@ -1068,6 +1069,11 @@ static int lx_pw1p_groups(int nft, int mtiles, int force, int cus) {
         if (t < best_t * 0.995) { best_t = t; best = g; }       // (ties: fewer, longer workgroups)
     }
     return best == mtiles ? 0 : best;                            // one row tile per workgroup: lx_pw1_kernel
+}
+
+bool lx_pw1p_force_ok(int inner, int force) {
+    const int mtiles = (2 * inner) / 512;
+    return force >= -1 && (force <= 0 || (force < mtiles && mtiles % force == 0));
 }
 
 template <int KT, int RAG>
