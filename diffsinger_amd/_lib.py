@@ -28,6 +28,8 @@ EXPORTS = [
     "dsd_kernel_timing", "dsd_kernel_timing_read", "dsd_kernel_timing_classes", "dsd_set_precision", "dsd_aux_decode", "dsd_encoder_create", "dsd_encode", "dsd_vocoder_create", "dsd_vocode", "dsd_vocode_ragged",
     "dsd_token_encoder_create", "dsd_token_encode", "dsd_predict_dur", "dsd_cond_assemble", "dsd_set_lengths",
     "dsd_mel_create", "dsd_mel_filterbank", "dsd_mel_num_frames", "dsd_mel_analyze",
+    "dsd_rmvpe_create", "dsd_rmvpe_num_frames", "dsd_rmvpe_filterbank", "dsd_rmvpe_mel_to_hidden", "dsd_rmvpe_decode",
+    "dsd_rmvpe_infer",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -60,6 +62,11 @@ class DsdMelConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("sampling_rate", C.c_int32), ("n_fft", C.c_int32), ("win_size", C.c_int32),
                 ("hop_size", C.c_int32), ("num_mels", C.c_int32), ("fmin", C.c_double), ("fmax", C.c_double),
                 ("clip_val", C.c_double), ("device", C.c_int32)]
+
+
+class DsdRmvpeConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_blocks", C.c_int32), ("n_gru", C.c_int32), ("en_de_layers", C.c_int32),
+                ("inter_layers", C.c_int32), ("en_out_channels", C.c_int32), ("device", C.c_int32)]
 
 
 class DsdTokenEncoderConfig(C.Structure):
@@ -165,6 +172,13 @@ def _load():
     lib.dsd_mel_num_frames.argtypes = [C.POINTER(DsdMelConfig), i64, C.c_double, C.c_double]
     lib.dsd_mel_num_frames.restype = i64
     lib.dsd_mel_analyze.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), C.c_double, C.c_double, vp, i64, i64, i64, vp]
+    lib.dsd_rmvpe_create.argtypes = [C.POINTER(DsdRmvpeConfig), C.POINTER(vp)]
+    lib.dsd_rmvpe_num_frames.argtypes = [i64, i32]
+    lib.dsd_rmvpe_num_frames.restype = i64
+    lib.dsd_rmvpe_filterbank.argtypes = [C.POINTER(C.c_float)]
+    lib.dsd_rmvpe_mel_to_hidden.argtypes = [vp, vp, i32, i32, i64, i64, i64, C.POINTER(i64), vp, i64, i64, vp]
+    lib.dsd_rmvpe_decode.argtypes = [vp, vp, i32, i32, i64, i64, C.c_float, vp, i64, vp]
+    lib.dsd_rmvpe_infer.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), i32, C.c_float, vp, i64, vp, i64, i64, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

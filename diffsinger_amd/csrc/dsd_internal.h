@@ -437,4 +437,74 @@ hipError_t launch_mel_basis(float* basis, int Rpad, int Kpad, int k_lo, int nb, 
 hipError_t launch_mel_dft(const MelDftP& p, int n_entries, int row_tiles, hipStream_t st);
 hipError_t launch_mel_project(const MelProjP& p, int n_entries, hipStream_t st);
 
+// rmvpe_kernels.hip: RMVPE pitch extraction (dsd_rmvpe_*).  work lists: 3 ints per (item, tile) entry = item b, first
+// quad / position / frame of the tile, the item's extent at that level (frames; Tin for the transposed conv).
+// Activations: [b][t < Tal][F][C] floats, Tal = the call's largest padded frame count at that level.
+struct RmResampleP {
+    const float* x;
+    long x_sb;
+    const int *len_in, *len_out;    // [B] samples in / out per item
+    const float* kern;              // [nw][K]
+    int K, orig, nw, width;
+    float* y;
+    long y_sb;
+};
+struct RmPrepP {
+    const float* mel;               // element (b, m, t) at mel[b sb + m sm + t st]
+    long sb, sm, st;
+    const int *T, *Tp;              // [B] frames, padded frames
+    float scale, shift;             // unet.encoder.bn
+    float* x;                       // [b][Tal][128]
+    int Tal;
+};
+struct RmConvP {
+    const float *x0, *x1;           // conv input: x0 (c0 channels) then x1 (c1 channels, 0 = none): torch.cat(dim=1)
+    int c0, c1;
+    const float *r0, *r1;           // residual input (the ConvBlockRes input), rc0 + rc1 channels
+    int rc0, rc1;
+    int res_mode;                   // 0 none, 1 identity (rc0 == cout), 2 shortcut conv ws / bs
+    const float* w;                 // [tap][c0 + c1][cout_pad], BN scale folded in
+    const float* shift;             // [cout_pad]: BN shift or the conv bias
+    const float *ws, *bs;           // [rc0 + rc1][cout_pad], [cout_pad]
+    int cout, cout_pad, relu;
+    int F, Tal;                     // bins and allocated frames of the INPUT level
+    float* y;                       // [b][Tal][F][cout] (the transposed conv: [b][2 Tal][2 F][cout])
+    float* pool;                    // optional AvgPool2d(2) of y: [b][Tal / 2][F / 2][cout]
+    const int* work;
+};
+struct RmLinearP {
+    const float* x;                 // [b][Tal][K]
+    const float* w;                 // [K][N]
+    const float* bias;              // [N]
+    int K, N, act, Tal;
+    float* y;                       // [b][Tal][N]
+    const int* work;                // (b, t0, Tp_b)
+};
+struct RmGruP {
+    const float* gi;                // [b][Tal][1536]
+    const float* whh;               // [2][256][768]: W_hh transposed per direction
+    const float* bhh;               // [2][768]
+    const int* Tp;
+    int Tal;
+    float* y;                       // [b][Tal][512]
+};
+struct RmDecodeP {
+    const float* hidden;            // frame (b, t) at hidden + b h_sb + t h_st, 360 contiguous classes
+    long h_sb, h_st;
+    const int* T;
+    int B, Tmax;
+    float thred;
+    float* f0;                      // optional: f0[b f_sb + t]
+    long f_sb;
+    float* out_hidden;              // optional copy, [b o_sb + t o_st + class]
+    long o_sb, o_st;
+};
+hipError_t launch_rm_resample(const RmResampleP& p, int B, long max_blocks, int nw, hipStream_t st);
+hipError_t launch_rm_prep(const RmPrepP& p, int B, int Tal, hipStream_t st);
+hipError_t launch_rm_conv3(const RmConvP& p, int n_entries, hipStream_t st);
+hipError_t launch_rm_tconv(const RmConvP& p, int n_entries, hipStream_t st);
+hipError_t launch_rm_linear(const RmLinearP& p, int n_entries, hipStream_t st);
+hipError_t launch_rm_gru(const RmGruP& p, int B, hipStream_t st);
+hipError_t launch_rm_decode(const RmDecodeP& p, hipStream_t st);
+
 }  // namespace dsd

@@ -1,0 +1,420 @@
+// RMVPE pitch extraction (modules/pe/rmvpe/, E2E0 + MelSpectrogram + to_local_average_f0), fp32 throughout:
+//   rm_resample_kernel  torchaudio's sinc_interp_hann Resample(sr, 16000, lowpass_filter_width=128) as a polyphase FIR
+//   rm_prep_kernel      log-mel [b][m][t] (caller strides) -> unet.encoder.bn(pad(mel)) in the [b][t][f] layout
+//   rm_conv3_kernel     3x3 conv (BN folded into the weights) + ReLU, then the ConvBlockRes residual (identity or the 1x1
+//                       shortcut conv), optionally the AvgPool2d(2) of the result; reads two sources as one concat
+//   rm_tconv_kernel     ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1) + folded BN + ReLU
+//   rm_linear_kernel    frames x weights (+ bias, optional sigmoid): the GRU input projections and the Linear heads
+//   rm_gru_kernel       one GRU direction of one item per workgroup; W_hh split over registers, LDS and L2
+//   rm_decode_kernel    argmax, the local weighted average of the cents, f0, the threshold
+// Activations are [item][frame][bin][channel] (channels innermost): the K walk of a conv is contiguous in the channels,
+// and the head's [frame][bin][3] output is the GRU's input row as it stands.
+// Work is listed per (item, tile) with the item's own frame count, so a ragged item computes exactly as its lone call.
+#include "dsd_internal.h"
+#include "dsd_device.h"
+
+namespace dsd {
+
+constexpr int RM_CO = 8;            // output channels per thread (conv / tconv), outputs per thread (linear)
+
+// ---------------------------------------------------------------------------------------------
+// out[b][blk * nw + ph] = sum_k kern[ph][k] xpad[blk * orig + k], xpad = the item's samples behind `width` zeros, zeros past
+// its end (_apply_sinc_resample_kernel: pad (width, width + orig), conv1d stride orig, phases interleaved).  blockIdx.y =
+// phase: the kernel row is wave-uniform.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rm_resample_kernel(const RmResampleP p) {
+    const int b = blockIdx.z, ph = blockIdx.y;
+    const long blk = (long)blockIdx.x * 256 + threadIdx.x;
+    const long i = blk * p.nw + ph, L = p.len_in[b];
+    if (i >= p.len_out[b]) return;
+    const float* __restrict__ x = p.x + (long)b * p.x_sb;
+    const float* __restrict__ kr = p.kern + (long)ph * p.K;
+    const long j0 = blk * p.orig - p.width;
+    float s = 0.f;
+    for (int k = 0; k < p.K; ++k) {
+        const long j = j0 + k;
+        if (j >= 0 && j < L) s = fmaf(kr[k], x[j], s);
+    }
+    p.y[(long)b * p.y_sb + i] = s;
+}
+
+// x0[b][t][f] = scale * mel[b][f][t] + shift for t < T_b, the BatchNorm of the zero padding (shift) for T_b <= t < Tp_b
+__global__ __launch_bounds__(256) void rm_prep_kernel(const RmPrepP p) {
+    const int b = blockIdx.y;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int t = (int)(idx / 128), f = (int)(idx % 128);
+    if (t >= p.Tp[b]) return;
+    const float v = t < p.T[b] ? p.mel[(long)b * p.sb + (long)f * p.sm + (long)t * p.st] : 0.f;
+    p.x[((long)b * p.Tal + t) * 128 + f] = fmaf(p.scale, v, p.shift);
+}
+
+// 8 consecutive floats at a 16-byte aligned byte offset through the store primitive of dsd_device.h
+__device__ __forceinline__ void st8(const dsd_i32x4& r, int off, const float (&v)[RM_CO]) {
+    st4_l2(f32x4{v[0], v[1], v[2], v[3]}, r, off, 0);
+    st4_l2(f32x4{v[4], v[5], v[6], v[7]}, r, off + 16, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One thread = one 2x2 quad of (frame, bin) positions x 8 output channels; blockIdx.y = the channel group, so every weight
+// read is wave-uniform.  The K walk is tap-major, then channels in vectors of CIV (one 16-byte load per
+// position when the channel counts allow); each weight vector serves 4 positions.  Positions outside [0, Tl) x [0, F) of
+// the item are the conv's zero padding.  work: (b, first quad, Tl).
+// ---------------------------------------------------------------------------------------------
+template <int CIV>
+__global__ __launch_bounds__(256) void rm_conv3_kernel(const RmConvP p) {
+    const int* e = p.work + 3 * blockIdx.x;
+    const int b = e[0], Tl = e[2], F = p.F, FQ = F >> 1;
+    const int q = e[1] + threadIdx.x;
+    if (q >= ((Tl + 1) >> 1) * FQ) return;
+    const int t0 = 2 * (q / FQ), f0 = 2 * (q % FQ), co0 = blockIdx.y * RM_CO;
+    const int cin = p.c0 + p.c1;
+    float acc[4][RM_CO];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) acc[i][o] = 0.f;
+    for (int s = 0; s < 2; ++s) {
+        const int cs = s ? p.c1 : p.c0, cb = s ? p.c0 : 0;
+        if (cs == 0) continue;
+        const float* __restrict__ src = (s ? p.x1 : p.x0) + (long)b * p.Tal * F * cs;
+#pragma unroll 1
+        for (int kt = 0; kt < 3; ++kt)
+#pragma unroll 1
+            for (int kf = 0; kf < 3; ++kf) {
+                bool in[2][2];
+                long off[2][2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int t = t0 + i + kt - 1, f = f0 + j + kf - 1;
+                        in[i][j] = t >= 0 && t < Tl && f >= 0 && f < F;
+                        off[i][j] = in[i][j] ? ((long)t * F + f) * cs : 0;
+                    }
+                const float* wt = p.w + ((long)(kt * 3 + kf) * cin + cb) * p.cout_pad + co0;
+                // weights through vector loads (all lanes one address): as scalar loads, four vectors of 8 next to the kernel
+                // arguments spill SGPRs
+                asm volatile("" : "+v"(wt));
+#pragma unroll 1
+                for (int ci = 0; ci < cs; ci += CIV) {
+                    float v[2][2][CIV];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            if constexpr (CIV == 4) {
+                                const f32x4 x4 = in[i][j] ? *(const f32x4*)(src + off[i][j] + ci) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) v[i][j][c] = x4[c];
+                            } else {
+                                v[i][j][0] = in[i][j] ? src[off[i][j] + ci] : 0.f;
+                            }
+                        }
+#pragma unroll
+                    for (int c = 0; c < CIV; ++c) {
+                        const float* __restrict__ w = wt + (long)(ci + c) * p.cout_pad;
+                        float wv[RM_CO];
+#pragma unroll
+                        for (int o = 0; o < RM_CO; ++o) wv[o] = w[o];
+#pragma unroll
+                        for (int i = 0; i < 2; ++i)
+#pragma unroll
+                            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                                for (int o = 0; o < RM_CO; ++o)
+                                    acc[2 * i + j][o] = fmaf(v[i][j][c], wv[o], acc[2 * i + j][o]);
+                    }
+                }
+            }
+    }
+    // epilogue: folded BN shift (or the conv bias), ReLU, residual
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) {
+            const float y = acc[i][o] + p.shift[co0 + o];
+            acc[i][o] = p.relu ? fmaxf(y, 0.f) : y;
+        }
+    if (p.res_mode == 1) {              // identity: the block input, cout channels
+        const float* __restrict__ r = p.r0 + (long)b * p.Tal * F * p.rc0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = t0 + (i >> 1), f = f0 + (i & 1);
+            if (t >= Tl) continue;
+#pragma unroll
+            for (int o = 0; o < RM_CO; ++o)
+                if (co0 + o < p.cout) acc[i][o] += r[((long)t * F + f) * p.rc0 + co0 + o];
+        }
+    } else if (p.res_mode == 2) {       // shortcut: Conv2d(cin, cout, 1) with bias over the block input (concat or not)
+        float sc[4][RM_CO];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int o = 0; o < RM_CO; ++o) sc[i][o] = 0.f;
+        for (int s = 0; s < 2; ++s) {
+            const int cs = s ? p.rc1 : p.rc0, cb = s ? p.rc0 : 0;
+            if (cs == 0) continue;
+            const float* __restrict__ src = (s ? p.r1 : p.r0) + (long)b * p.Tal * F * cs;
+#pragma unroll 1
+            for (int ci = 0; ci < cs; ++ci) {
+                const float* __restrict__ w = p.ws + (long)(cb + ci) * p.cout_pad + co0;
+                float wv[RM_CO];
+#pragma unroll
+                for (int o = 0; o < RM_CO; ++o) wv[o] = w[o];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int t = min(t0 + (i >> 1), Tl - 1), f = f0 + (i & 1);
+                    const float xv = src[((long)t * F + f) * cs + ci];
+#pragma unroll
+                    for (int o = 0; o < RM_CO; ++o) sc[i][o] = fmaf(xv, wv[o], sc[i][o]);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int o = 0; o < RM_CO; ++o) acc[i][o] += sc[i][o] + p.bs[co0 + o];
+    }
+    const dsd_i32x4 ry = dsd_rsrc_words(p.y);
+    const long ybase = (long)b * p.Tal * F;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = t0 + (i >> 1), f = f0 + (i & 1);
+        if (t >= Tl) continue;
+        const long pos = ybase + (long)t * F + f;
+        if ((p.cout & 7) == 0) {
+            st8(ry, (int)((pos * p.cout + co0) * 4), acc[i]);
+        } else {
+#pragma unroll
+            for (int o = 0; o < RM_CO; ++o)
+                if (co0 + o < p.cout) p.y[pos * p.cout + co0 + o] = acc[i][o];
+        }
+    }
+    if (p.pool) {                        // AvgPool2d(2): ((x00 + x01) + x10) + x11, / 4, as torch's CPU kernel sums
+        float pv[RM_CO];
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) pv[o] = (((acc[0][o] + acc[1][o]) + acc[2][o]) + acc[3][o]) / 4.f;
+        const long pos = ((long)b * (p.Tal >> 1) + (t0 >> 1)) * (F >> 1) + (f0 >> 1);
+        st8(dsd_rsrc_words(p.pool), (int)((pos * p.cout + co0) * 4), pv);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1): one thread = input position (i, j) -> the output quad
+// (2i + a, 2j + c), the four parity sub-convolutions.  Output row 2i reads input i with tap 1; row 2i + 1 reads input i with
+// tap 2 and input i + 1 with tap 0 (zero past the item's Tin frames / the F bins).  w: [kt * 3 + kf][cin][cout_pad], BN folded.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rm_tconv_kernel(const RmConvP p) {
+    const int* e = p.work + 3 * blockIdx.x;
+    const int b = e[0], Tin = e[2], F = p.F;
+    const int q = e[1] + threadIdx.x;
+    if (q >= Tin * F) return;
+    const int ti = q / F, fi = q % F, co0 = blockIdx.y * RM_CO, cin = p.c0;
+    const float* __restrict__ src = p.x0 + (long)b * p.Tal * F * cin;
+    const bool tn = ti + 1 < Tin, fn = fi + 1 < F;
+    float acc[4][RM_CO];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) acc[i][o] = 0.f;
+    for (int ci = 0; ci < cin; ++ci) {
+        const float x00 = src[((long)ti * F + fi) * cin + ci];
+        const float x01 = fn ? src[((long)ti * F + fi + 1) * cin + ci] : 0.f;
+        const float x10 = tn ? src[((long)(ti + 1) * F + fi) * cin + ci] : 0.f;
+        const float x11 = tn && fn ? src[((long)(ti + 1) * F + fi + 1) * cin + ci] : 0.f;
+        const float* __restrict__ w = p.w + (long)ci * p.cout_pad + co0;
+        const long tap = (long)cin * p.cout_pad;
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) {
+            const float w00 = w[0 * tap + o], w01 = w[1 * tap + o], w02 = w[2 * tap + o];
+            const float w10 = w[3 * tap + o], w11 = w[4 * tap + o], w12 = w[5 * tap + o];
+            const float w20 = w[6 * tap + o], w21 = w[7 * tap + o], w22 = w[8 * tap + o];
+            acc[0][o] = fmaf(x00, w11, acc[0][o]);
+            acc[1][o] = fmaf(x01, w10, fmaf(x00, w12, acc[1][o]));
+            acc[2][o] = fmaf(x10, w01, fmaf(x00, w21, acc[2][o]));
+            acc[3][o] = fmaf(x11, w00, fmaf(x10, w02, fmaf(x01, w20, fmaf(x00, w22, acc[3][o]))));
+        }
+    }
+    const int Fo = 2 * F;
+    const dsd_i32x4 ry = dsd_rsrc_words(p.y);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float v[RM_CO];
+#pragma unroll
+        for (int o = 0; o < RM_CO; ++o) v[o] = fmaxf(acc[i][o] + p.shift[co0 + o], 0.f);
+        const long pos = ((long)b * p.Tal * 2 + 2 * ti + (i >> 1)) * Fo + 2 * fi + (i & 1);
+        st8(ry, (int)((pos * p.cout + co0) * 4), v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// y[row][n] = act(sum_k x[row][k] W[k][n] + bias[n]) for the rows (b, t < Tp_b); one thread = one row x 8 outputs,
+// blockIdx.y = the output group (uniform weight reads).  work: (b, first frame, Tp_b).  act 1 = sigmoid.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rm_linear_kernel(const RmLinearP p) {
+    const int* e = p.work + 3 * blockIdx.x;
+    const int b = e[0], t = e[1] + threadIdx.x;
+    if (t >= e[2]) return;
+    const long row = (long)b * p.Tal + t;
+    const int n0 = blockIdx.y * RM_CO;
+    const float* __restrict__ x = p.x + row * p.K;
+    float acc[RM_CO];
+#pragma unroll
+    for (int o = 0; o < RM_CO; ++o) acc[o] = 0.f;
+    for (int k = 0; k < p.K; k += 4) {
+        const f32x4 xv = *(const f32x4*)(x + k);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float* __restrict__ w = p.w + (long)(k + c) * p.N + n0;
+#pragma unroll
+            for (int o = 0; o < RM_CO; ++o) acc[o] = fmaf(xv[c], w[o], acc[o]);
+        }
+    }
+#pragma unroll
+    for (int o = 0; o < RM_CO; ++o) {
+        const float v = acc[o] + p.bias[n0 + o];
+        acc[o] = p.act ? 1.f / (1.f + expf(-v)) : v;
+    }
+    st8(dsd_rsrc_words(p.y), (int)((row * p.N + n0) * 4), acc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// One GRU direction of one item: blockIdx = (item, direction).  Thread r < 768 owns row r of W_hh (gate r / z / n of unit
+// r % 256): columns [0, RM_KR) in registers, [RM_KR, RM_KR + RM_KL) in LDS, the rest read from L2 each step in the
+// [k][768] layout (coalesced).  Per step: gh = W_hh h + b_hh through LDS, then unit j < 256 applies
+//   r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h      (torch.nn.GRU)
+// The item runs over its own Tp_b frames; the reverse direction starts at Tp_b - 1.  gi: [b][t][1536] (forward | reverse
+// gates with b_ih), y: [b][t][512] (forward | reverse h).
+// ---------------------------------------------------------------------------------------------
+constexpr int RM_H = 256, RM_G = 768, RM_KR = 112, RM_KL = 48, RM_KG = RM_H - RM_KR - RM_KL;
+__global__ __launch_bounds__(768) void rm_gru_kernel(const RmGruP p) {
+    __shared__ __attribute__((aligned(16))) float sW[RM_KL * RM_G];
+    __shared__ __attribute__((aligned(16))) float sh[RM_H];
+    __shared__ float sg[RM_G];
+    const int b = blockIdx.x, d = blockIdx.y, r = threadIdx.x, Tp = p.Tp[b];
+    const float* __restrict__ whh = p.whh + (long)d * RM_H * RM_G;      // [k][768]
+    float wr[RM_KR];
+#pragma unroll
+    for (int k = 0; k < RM_KR; ++k) wr[k] = whh[(long)k * RM_G + r];
+    for (int k = 0; k < RM_KL; ++k) sW[k * RM_G + r] = whh[(long)(RM_KR + k) * RM_G + r];
+    const float* __restrict__ wg = whh + (long)(RM_KR + RM_KL) * RM_G + r;
+    const float bh = p.bhh[d * RM_G + r];
+    if (r < RM_H) sh[r] = 0.f;
+    __syncthreads();
+    for (int s = 0; s < Tp; ++s) {
+        const int t = d ? Tp - 1 - s : s;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+        for (int k = 0; k < RM_KR; k += 4) {
+            const f32x4 hv = *(const f32x4*)(sh + k);
+            a0 = fmaf(wr[k], hv[0], a0);
+            a1 = fmaf(wr[k + 1], hv[1], a1);
+            a2 = fmaf(wr[k + 2], hv[2], a2);
+            a3 = fmaf(wr[k + 3], hv[3], a3);
+        }
+#pragma unroll 4
+        for (int k = 0; k < RM_KL; k += 4) {
+            const f32x4 hv = *(const f32x4*)(sh + RM_KR + k);
+            a0 = fmaf(sW[k * RM_G + r], hv[0], a0);
+            a1 = fmaf(sW[(k + 1) * RM_G + r], hv[1], a1);
+            a2 = fmaf(sW[(k + 2) * RM_G + r], hv[2], a2);
+            a3 = fmaf(sW[(k + 3) * RM_G + r], hv[3], a3);
+        }
+#pragma unroll 4
+        for (int k = 0; k < RM_KG; k += 4) {
+            const f32x4 hv = *(const f32x4*)(sh + RM_KR + RM_KL + k);
+            a0 = fmaf(wg[(long)k * RM_G], hv[0], a0);
+            a1 = fmaf(wg[(long)(k + 1) * RM_G], hv[1], a1);
+            a2 = fmaf(wg[(long)(k + 2) * RM_G], hv[2], a2);
+            a3 = fmaf(wg[(long)(k + 3) * RM_G], hv[3], a3);
+        }
+        sg[r] = ((a0 + a1) + (a2 + a3)) + bh;
+        __syncthreads();
+        if (r < RM_H) {
+            const float* __restrict__ gi = p.gi + ((long)b * p.Tal + t) * (2 * RM_G) + d * RM_G;
+            const float rg = 1.f / (1.f + expf(-(gi[r] + sg[r])));
+            const float zg = 1.f / (1.f + expf(-(gi[RM_H + r] + sg[RM_H + r])));
+            const float ng = tanhf(fmaf(rg, sg[2 * RM_H + r], gi[2 * RM_H + r]));
+            const float hn = fmaf(zg, sh[r] - ng, ng);       // (1 - z) n + z h
+            sh[r] = hn;
+            p.y[((long)b * p.Tal + t) * (2 * RM_H) + d * RM_H + r] = hn;
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// to_local_average_f0 (utils.py:8-23): one wave per frame (b, t < T_b).  argmax over the 360 classes (first index on ties),
+// the weighted mean of 20 i + CONST over [c - 4, c + 5) clipped to [0, 360), f0 = 10 * 2^(cents / 1200), 0 where max < thred.
+// Optionally copies the frame's 360 values to hidden_out.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rm_decode_kernel(const RmDecodeP p) {
+    const int lane = threadIdx.x & 63;
+    const long fr = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = (int)(fr / p.Tmax), t = (int)(fr % p.Tmax);
+    if (b >= p.B || t >= p.T[b]) return;
+    const float* __restrict__ hv = p.hidden + (long)b * p.h_sb + (long)t * p.h_st;
+    float best = -INFINITY;
+    int bi = 360;
+    for (int i = lane; i < 360; i += 64) {
+        const float v = hv[i];
+        if (v > best || bi == 360) {
+            best = v;
+            bi = i;
+        }
+        if (p.out_hidden) p.out_hidden[(long)b * p.o_sb + (long)t * p.o_st + i] = v;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ob > best || (ob == best && oi < bi)) {
+            best = ob;
+            bi = oi;
+        }
+    }
+    if (lane != 0 || !p.f0) return;
+    const int lo = max(bi - 4, 0), hi = min(bi + 5, 360);
+    float ps = 0.f, ws = 0.f;
+    for (int i = lo; i < hi; ++i) {
+        ps = fmaf(hv[i], 20.f * (float)i + 1997.3794084376191f, ps);
+        ws += hv[i];
+    }
+    const float cents = ps / (ws + (ws == 0.f ? 1.f : 0.f));
+    const float f0 = 10.f * exp2f(cents / 1200.f);
+    p.f0[(long)b * p.f_sb + t] = best < p.thred ? 0.f : f0;
+}
+
+hipError_t launch_rm_resample(const RmResampleP& p, int B, long max_blocks, int nw, hipStream_t st) {
+    hipLaunchKernelGGL(rm_resample_kernel, dim3((unsigned)((max_blocks + 255) / 256), (unsigned)nw, (unsigned)B), dim3(256), 0,
+                       st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_prep(const RmPrepP& p, int B, int Tal, hipStream_t st) {
+    hipLaunchKernelGGL(rm_prep_kernel, dim3((unsigned)((Tal * 128 + 255) / 256), (unsigned)B), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_conv3(const RmConvP& p, int n_entries, hipStream_t st) {
+    const dim3 grid((unsigned)n_entries, (unsigned)(p.cout_pad / RM_CO));
+    if (p.c0 % 4 == 0 && p.c1 % 4 == 0) hipLaunchKernelGGL(rm_conv3_kernel<4>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(rm_conv3_kernel<1>, grid, dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_tconv(const RmConvP& p, int n_entries, hipStream_t st) {
+    hipLaunchKernelGGL(rm_tconv_kernel, dim3((unsigned)n_entries, (unsigned)(p.cout_pad / RM_CO)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_linear(const RmLinearP& p, int n_entries, hipStream_t st) {
+    hipLaunchKernelGGL(rm_linear_kernel, dim3((unsigned)n_entries, (unsigned)(p.N / RM_CO)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_gru(const RmGruP& p, int B, hipStream_t st) {
+    hipLaunchKernelGGL(rm_gru_kernel, dim3((unsigned)B, 2), dim3(RM_G), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_decode(const RmDecodeP& p, hipStream_t st) {
+    const long frames = (long)p.B * p.Tmax;
+    hipLaunchKernelGGL(rm_decode_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace dsd

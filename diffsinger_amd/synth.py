@@ -268,3 +268,106 @@ def state_dict_digest(sd):
 def synth_normal(shape, seed):
     rng = np.random.Generator(np.random.PCG64(seed))
     return rng.standard_normal(shape, dtype=np.float32)
+
+
+def rmvpe_param_shapes(n_blocks=4, n_gru=1, en_de_layers=5, inter_layers=4, en_out_channels=16, with_tf=False):
+    """The state_dict of E2E0(n_blocks, n_gru, (2, 2), en_de_layers, inter_layers, 1, en_out_channels)
+    (modules/pe/rmvpe/model.py): name -> shape, `num_batches_tracked` as () and, with `with_tf`, the TimbreFilter
+    (`unet.tf.*`) the checkpoint carries but forward never calls.  The defaults are the production RMVPE."""
+    shapes = OrderedDict()
+
+    def bn(p, c):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            shapes[f"{p}.{leaf}"] = (c,)
+        shapes[f"{p}.num_batches_tracked"] = ()
+
+    def block(p, cin, cout):
+        shapes[f"{p}.conv.0.weight"] = (cout, cin, 3, 3)
+        bn(f"{p}.conv.1", cout)
+        shapes[f"{p}.conv.3.weight"] = (cout, cout, 3, 3)
+        bn(f"{p}.conv.4", cout)
+        if cin != cout:
+            shapes[f"{p}.shortcut.weight"] = (cout, cin, 1, 1)
+            shapes[f"{p}.shortcut.bias"] = (cout,)
+
+    E, C = en_de_layers, en_out_channels
+    bn("unet.encoder.bn", 1)
+    for l in range(E):
+        cin, cout = (1 if l == 0 else C << (l - 1)), C << l
+        for k in range(n_blocks):
+            block(f"unet.encoder.layers.{l}.conv.{k}", cout if k else cin, cout)
+    for i in range(inter_layers):
+        cin, cout = (C << (E - 1) if i == 0 else C << E), C << E
+        for k in range(n_blocks):
+            block(f"unet.intermediate.layers.{i}.conv.{k}", cout if k else cin, cout)
+    if with_tf:
+        for l in range(E):
+            block(f"unet.tf.layers.{l}", C << l, C << l)
+    for i in range(E):
+        cin = C << (E - i)
+        cout = cin // 2
+        shapes[f"unet.decoder.layers.{i}.conv1.0.weight"] = (cin, cout, 3, 3)
+        bn(f"unet.decoder.layers.{i}.conv1.1", cout)
+        for k in range(n_blocks):
+            block(f"unet.decoder.layers.{i}.conv2.{k}", cout if k else 2 * cout, cout)
+    shapes["cnn.weight"] = (3, C, 3, 3)
+    shapes["cnn.bias"] = (3,)
+    if n_gru:
+        for sfx in ("", "_reverse"):
+            shapes[f"fc.0.gru.weight_ih_l0{sfx}"] = (768, 384)
+            shapes[f"fc.0.gru.weight_hh_l0{sfx}"] = (768, 256)
+            shapes[f"fc.0.gru.bias_ih_l0{sfx}"] = (768,)
+            shapes[f"fc.0.gru.bias_hh_l0{sfx}"] = (768,)
+        shapes["fc.1.weight"] = (360, 512)
+        shapes["fc.1.bias"] = (360,)
+    else:
+        shapes["fc.0.weight"] = (360, 384)
+        shapes["fc.0.bias"] = (360,)
+    return shapes
+
+
+RMVPE_SMALL = dict(n_blocks=1, n_gru=1, en_de_layers=5, inter_layers=1, en_out_channels=16)
+
+
+def rmvpe_state_dict(seed=1800, with_tf=False, **cfg):
+    """Seeded synthetic RMVPE weights (float32; num_batches_tracked int64 0) whose sigmoid output is non-degenerate on the
+    test signals: voiced and unvoiced frames, the frame maximum on both sides of thred = 0.03, argmax spread over the 360
+    classes.  Statistics:
+      conv weights         N(0, 2 / fan_in) (He), the second conv of every ConvBlockRes and the shortcut times 0.5
+      BatchNorm            weight 1 + 0.1 N, bias 0.1 N, running_mean 0.1 N, running_var 1 + 0.25 U(0, 1); the input
+                           BatchNorm: running_mean -5, running_var 9 (log-mel values of -11.5 .. 2 come out as O(1))
+      cnn                  N(0, 1 / fan_in), bias 0.1 N
+      GRU                  weights U(-1, 1) / 16 (torch's init: U(-1 / sqrt(256), 1 / sqrt(256))), biases the same
+      fc (Linear -> 360)   N(0, 9 / fan_in), bias -6 + 0.5 N (sigmoid(-6) = 0.0025 < 0.03)"""
+    shapes = rmvpe_param_shapes(with_tf=with_tf, **cfg)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "num_batches_tracked":
+            out[name] = np.zeros((), dtype=np.int64)
+            continue
+        z = rng.standard_normal(shape)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
+        is_bn = len(shape) == 1 and leaf in ("weight", "bias", "running_mean", "running_var") and not name.startswith(("cnn", "fc"))
+        is_bn = is_bn and not name.endswith(("shortcut.bias",))
+        if name.startswith("unet.encoder.bn."):
+            w = {"weight": 1.0 + 0.1 * z, "bias": 0.1 * z, "running_mean": np.full(shape, -5.0),
+                 "running_var": np.full(shape, 9.0)}[leaf]
+        elif is_bn:
+            w = {"weight": 1.0 + 0.1 * z, "bias": 0.1 * z, "running_mean": 0.1 * z,
+                 "running_var": 1.0 + 0.25 * rng.uniform(0, 1, shape)}[leaf]
+        elif name.startswith("fc.0.gru."):
+            w = rng.uniform(-1, 1, shape) / 16.0
+        elif name.startswith("fc."):
+            w = (-6.0 + 0.5 * z) if leaf == "bias" else 3.0 * z / np.sqrt(fan_in)
+        elif name.startswith("cnn."):
+            w = 0.1 * z if leaf == "bias" else z / np.sqrt(fan_in)
+        elif leaf == "bias":
+            w = 0.1 * z
+        else:
+            w = np.sqrt(2.0 / fan_in) * z
+            if ".conv.3." in name or ".shortcut." in name:
+                w = 0.5 * w
+        out[name] = np.ascontiguousarray(w, dtype=np.float32)
+    return out

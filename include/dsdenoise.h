@@ -52,7 +52,10 @@ enum { DSD_BACKBONE_WAVENET = 0, DSD_BACKBONE_LYNXNET = 1,
        DSD_ENC_FS2_TOKENS = 5,
        /* modules/nsf_hifigan/nvSTFT.py:26  STFT (waveform -> log-mel analysis, no weights; see dsd_mel_analyze);
           created with dsd_mel_create */
-       DSD_MEL_ANALYSIS = 6 };
+       DSD_MEL_ANALYSIS = 6,
+       /* modules/pe/rmvpe/inference.py:14  RMVPE pitch extractor (E2E0 + MelSpectrogram + to_local_average_f0);
+          created with dsd_rmvpe_create */
+       DSD_PE_RMVPE = 7 };
 /* modules/backbones/lynxnet.py:38-42  activation_classes */
 enum { DSD_ACT_PRELU = 0, DSD_ACT_SILU = 1, DSD_ACT_RELU = 2 };
 
@@ -409,6 +412,71 @@ int64_t dsd_mel_num_frames(const dsd_mel_config* cfg, int64_t n_samples, double 
 int dsd_mel_analyze(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
                     const int64_t* lengths, double keyshift, double speed, float* mel_out, int64_t stride_b,
                     int64_t stride_m, int64_t stride_t, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * RMVPE pitch extraction: waveform -> f0 at 16 kHz / hop 160 (100 frames per second), the extractor the reference's
+ * binarizers and augmentation select with `pe: rmvpe` (modules/pe/rmvpe/inference.py).  fp32 throughout.  Weights load
+ * through dsd_load_weight / dsd_finalize_weights under the reference's state_dict names; `unet.tf.*` (TimbreFilter, never
+ * called in forward) and `*.num_batches_tracked` are accepted and ignored, any other unknown name is DSD_ENOTFOUND.  An
+ * RMVPE handle returns DSD_ESTATE on every entry point but these and the weight loading; the dsd_rmvpe_* calls return
+ * DSD_ESTATE on any other handle.
+ * ------------------------------------------------------------------------------------------ */
+/* E2E0(n_blocks, n_gru, (2, 2), en_de_layers, inter_layers, 1, en_out_channels)  (modules/pe/rmvpe/model.py:8-31);
+   the reference's RMVPE builds E2E0(4, 1, (2, 2)) with en_de_layers 5, inter_layers 4, en_out_channels 16 */
+typedef struct dsd_rmvpe_config {
+    int32_t struct_size;        /* sizeof(dsd_rmvpe_config)                                        */
+    int32_t n_blocks;           /* ConvBlockRes per encoder / intermediate / decoder block, >= 1   */
+    int32_t n_gru;              /* 1: BiGRU(384, 256) + Linear(512, 360); 0: Linear(384, 360)      */
+    int32_t en_de_layers;       /* 1 .. 5                                                          */
+    int32_t inter_layers;       /* >= 1                                                            */
+    int32_t en_out_channels;    /* a positive multiple of 8                                        */
+    int32_t device;
+} dsd_rmvpe_config;
+
+int dsd_rmvpe_create(const dsd_rmvpe_config* cfg, dsd_handle** out);
+/*
+ * Frame count of RMVPE.infer_from_audio on n_samples samples at sample_rate: L16 = n_samples, or ceil(16000 n_samples /
+ * sample_rate) after the resampler; T = 1 + L16 // 160.  DSD_EINVAL where torch.stft's reflect pad raises (L16 <= 512) or
+ * sample_rate < 1.  Host only.
+ */
+int64_t dsd_rmvpe_num_frames(int64_t n_samples, int32_t sample_rate);
+/*
+ * The mel filterbank MelSpectrogram stores (spec.py:22-29): librosa.filters.mel(sr=16000, n_fft=1024, n_mels=128, fmin=30,
+ * fmax=8000, htk=True) - HTK mel scale, Slaney area normalisation, float32.  out: [128][513] host floats.  Host only.
+ */
+int dsd_rmvpe_filterbank(float* out);
+/*
+ * Replaces: RMVPE.mel2hidden(mel)  (inference.py:24-29): zero pad to Tp = 32 ceil(T / 32) frames, E2E0.forward over the
+ * padded frames (the reverse GRU starts at frame Tp - 1), crop to T.
+ *   mel         element (b, m, t) of the natural-log mel [B, 128, T] at mel[b * stride_b + m * stride_m + t * stride_t]
+ *               (device fp32)
+ *   lengths     HOST array of B frame counts (1 <= lengths[b] <= T) or NULL; item b is computed exactly as a lone call on
+ *               its own lengths[b] frames
+ *   hidden_out  element (b, t, c) of [B, T, 360] at hidden_out[b * h_stride_b + t * h_stride_t + c]; frames at or past
+ *               T_b are not written
+ */
+int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
+                         int64_t stride_t, const int64_t* lengths, float* hidden_out, int64_t h_stride_b,
+                         int64_t h_stride_t, void* stream);
+/*
+ * Replaces: RMVPE.decode(hidden, thred, use_viterbi=False) = to_local_average_f0  (utils.py:8-23) on a device [B, T, 360]
+ * hidden (classes contiguous): f0_out[b * f0_stride_b + t] (device fp32), 0 where max < thred.
+ */
+int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
+                     float thred, float* f0_out, int64_t f0_stride_b, void* stream);
+/*
+ * Replaces: RMVPE.infer_from_audio(audio, sample_rate, thred, use_viterbi=False)  (inference.py:38-51): resample to 16 kHz
+ * unless sample_rate == 16000 (torchaudio Resample(sr, 16000, lowpass_filter_width=128): Hann-windowed sinc, rolloff
+ * 0.99), MelSpectrogram(center=True), mel2hidden, decode.
+ *   wav         item b's sample s at wav[b * wav_stride_b + s], s < n_samples (device fp32)
+ *   lengths     HOST array of B sample counts (1 <= lengths[b] <= n_samples) or NULL; item b is computed exactly as a lone
+ *               call on its own samples (its own resampled length, frames and padding)
+ *   f0_out      f0 of frame t < T_b = dsd_rmvpe_num_frames(lengths[b], sample_rate) at f0_out[b * f0_stride_b + t]
+ *   hidden_out  NULL, or the sigmoid output as in dsd_rmvpe_mel_to_hidden
+ */
+int dsd_rmvpe_infer(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
+                    const int64_t* lengths, int32_t sample_rate, float thred, float* f0_out, int64_t f0_stride_b,
+                    float* hidden_out, int64_t h_stride_b, int64_t h_stride_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Sampling programs.  Every sampler of the reference (ddpm.py:149-204,221-351 p_sample /
