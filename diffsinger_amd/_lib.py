@@ -30,6 +30,8 @@ EXPORTS = [
     "dsd_mel_create", "dsd_mel_filterbank", "dsd_mel_num_frames", "dsd_mel_analyze",
     "dsd_rmvpe_create", "dsd_rmvpe_num_frames", "dsd_rmvpe_filterbank", "dsd_rmvpe_mel_to_hidden", "dsd_rmvpe_decode",
     "dsd_rmvpe_infer",
+    "dsd_hnsep_create", "dsd_hnsep_num_frames", "dsd_hnsep_mask", "dsd_hnsep_separate", "dsd_base_harmonic",
+    "dsd_variance_curves",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -67,6 +69,11 @@ class DsdMelConfig(C.Structure):
 class DsdRmvpeConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_blocks", C.c_int32), ("n_gru", C.c_int32), ("en_de_layers", C.c_int32),
                 ("inter_layers", C.c_int32), ("en_out_channels", C.c_int32), ("device", C.c_int32)]
+
+
+class DsdHnsepConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_fft", C.c_int32), ("hop_length", C.c_int32), ("nout", C.c_int32),
+                ("nout_lstm", C.c_int32), ("is_mono", C.c_int32), ("device", C.c_int32)]
 
 
 class DsdTokenEncoderConfig(C.Structure):
@@ -179,6 +186,14 @@ def _load():
     lib.dsd_rmvpe_mel_to_hidden.argtypes = [vp, vp, i32, i32, i64, i64, i64, C.POINTER(i64), vp, i64, i64, vp]
     lib.dsd_rmvpe_decode.argtypes = [vp, vp, i32, i32, i64, i64, C.c_float, vp, i64, vp]
     lib.dsd_rmvpe_infer.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), i32, C.c_float, vp, i64, vp, i64, i64, vp]
+    lib.dsd_hnsep_create.argtypes = [C.POINTER(DsdHnsepConfig), C.POINTER(vp)]
+    lib.dsd_hnsep_num_frames.argtypes = [i64, i32]
+    lib.dsd_hnsep_num_frames.restype = i64
+    lib.dsd_hnsep_mask.argtypes = [vp, vp, i32, i32, i64, i64, i64, i64, C.POINTER(i64), vp, i64, i64, i64, i64, vp]
+    lib.dsd_hnsep_separate.argtypes = [vp, vp, i32, i64, i64, i64, C.POINTER(i64), vp, i64, i64, vp]
+    lib.dsd_base_harmonic.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), i32, i32, i32, vp, i64, vp]
+    lib.dsd_variance_curves.argtypes = [vp, vp, vp, vp, i32, i64, C.POINTER(i64), i32, i32, C.POINTER(i64), i32, i32, vp, vp, vp,
+                                        vp, i64, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

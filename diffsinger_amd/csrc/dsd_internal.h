@@ -507,4 +507,112 @@ hipError_t launch_rm_linear(const RmLinearP& p, int n_entries, hipStream_t st);
 hipError_t launch_rm_gru(const RmGruP& p, int B, hipStream_t st);
 hipError_t launch_rm_decode(const RmDecodeP& p, hipStream_t st);
 
+// ---------------------------------------------------------------------------------------------
+// hnsep_kernels.hip: VR harmonic-noise separation and the variance curves
+// ---------------------------------------------------------------------------------------------
+struct HsView {                     // element (b, f, t, c) at p + b bs + f fs + t ts + c cs
+    float* p;
+    long bs, fs, ts, cs;
+};
+struct HsSrc {                      // a conv source: C channels (Cp = C rounded up to 4) at p + b bs + f fs + t ts + c cs
+    const float* p;
+    long bs, fs, ts, cs;
+    int C, Cp;
+    int mode;                       // 0 plain, 1 bilinear x2 upsample (align_corners), 2 one bin broadcast over bins
+};
+struct HsConvP {
+    HsSrc src[4];
+    int nsrc;
+    const float* w;                 // [(source, tap kf * ks + kt, channel < Cp)][cout_pad], BN scale folded
+    const float* shift;             // [cout_pad]
+    HsView y;
+    int cout, cout_pad;
+    int F, Fin;                     // output / input bins
+    int ks, stride, dil_f, dil_t;
+    int act;                        // 0 none, 1 ReLU, 2 LeakyReLU(0.01)
+    const int* work;                // (b, q0, T_l out, T_l in)
+};
+struct HsBinMeanP {
+    HsView x, y;
+    int F, C;
+    const int* T;
+};
+struct HsLstmNet {
+    const float* gi;                // [b][t][2][4H]
+    long gi_bs;
+    const float* whh;               // [2][4H][H]
+    float* y;                       // [b][t][2][H]
+    long y_bs;
+    int H;
+};
+struct HsLstmP {
+    HsLstmNet net[2];
+    const int* T;
+};
+struct HsMaskP {
+    HsView x, y;                    // the out conv (channels re 0..C-1, im C..2C-1) -> the mask (re at c cs, im at y_im + c cs)
+    long y_im;
+    int F, Fx, C;                   // mask bins, conv bins (the last one replicated)
+    const int* T;
+};
+struct HsDftP {
+    const float* basis;
+    int Kpad, K, N, nb, inv;
+    // forward
+    const float* wav;               // channel ch of item b at wav + b wav_sb + ch wav_sc
+    long wav_sb, wav_sc;
+    int H, reflect;                 // (padL per work entry)
+    // inverse: spectrum (b, bin, t) at spec + b s_sb + bin s_sf + t s_st, re / im at channel s_cre / s_cim + ch
+    const float* spec;
+    long s_sb, s_sf, s_st;
+    int s_cre, s_cim;
+    const float* mask;              // the network's mask (NULL: the f0 bin mask)
+    long m_sb, m_sf, m_st;
+    int m_cim, mask_F;
+    const float* f0;                // [b f0_sb + t], f0_len[b] frames
+    long f0_sb;
+    const int* f0_len;
+    float sr, half_width;
+    // output: forward spectrum view, inverse frames [(b nch + ch) o_sb + t N + j]
+    float* out;
+    long o_sb, o_sf, o_st;
+    int o_cre, o_cim, nrep, nch;
+    const int* work;                // (b, t0, L, T_b, ch, padL)
+};
+struct HsOlaP {
+    const float* frames;            // [(b nch + c) f_sb + t N + j]
+    long f_sb;
+    const float* win;
+    int N, H, nch;
+    const int* T;                   // frames per item
+    const long* len;                // output samples per item
+    const long* off0;               // padded position of output sample 0
+    float* out;
+    long o_sb, o_sc;                // o_sc 0: the mean of the channels at out + b o_sb; else channel c at + c o_sc
+};
+struct HsRmsP {
+    const float *wav, *harm, *base; // any may be NULL
+    long sb;
+    const long* len;
+    const int* nfr;                 // librosa frames per item: 1 + L // hop
+    int hop, win, B, Tmax;
+    float* rms;                     // [4][B][Tmax]
+};
+struct HsCurvesP {
+    const float* rms;
+    const int *nfr, *length;
+    int B, Tmax, domain, db;        // db 0: energy / breathiness / voicing stay RMS
+    float* out[4];                  // energy, breathiness, voicing, tension (any may be NULL): [b o_sb + t]
+    long o_sb;
+};
+hipError_t launch_hs_basis(float* basis, const float* win, int Rpad, int Kpad, int nb, int N, int inv, hipStream_t st);
+hipError_t launch_hs_dft(const HsDftP& p, int n_entries, int row_tiles, hipStream_t st);
+hipError_t launch_hs_ola(const HsOlaP& p, int B, long max_len, hipStream_t st);
+hipError_t launch_hs_conv(const HsConvP& p, int n_entries, hipStream_t st);
+hipError_t launch_hs_binmean(const HsBinMeanP& p, int B, int Tmax, hipStream_t st);
+hipError_t launch_hs_lstm(const HsLstmP& p, int B, int nnet, hipStream_t st);
+hipError_t launch_hs_mask(const HsMaskP& p, int B, int Tmax, hipStream_t st);
+hipError_t launch_hs_rms(const HsRmsP& p, hipStream_t st);
+hipError_t launch_hs_curves(const HsCurvesP& p, hipStream_t st);
+
 }  // namespace dsd

@@ -371,3 +371,46 @@ def rmvpe_state_dict(seed=1800, with_tf=False, **cfg):
                 w = 0.5 * w
         out[name] = np.ascontiguousarray(w, dtype=np.float32)
     return out
+
+
+HNSEP_SMALL = dict(n_fft=512, hop_length=128, nout=8, nout_lstm=16, is_mono=True)
+HNSEP_PROD = dict(n_fft=2048, hop_length=512, nout=32, nout_lstm=128, is_mono=True)
+
+
+def hnsep_state_dict(cfg=None, seed=1900, out_scale=0.5):
+    """Seeded synthetic CascadedNet weights (float32; num_batches_tracked int64 0) for the layout `cfg` (CascadedNet's
+    arguments).  Statistics:
+      conv weights   N(0, 2 / fan_in) (He)
+      BatchNorm      weight 1 + 0.1 N, bias 0.1 N, running_mean 0.1 N, running_var 1 + 0.25 U(0, 1) (non-trivial, so the
+                     folding into the conv weights is exercised)
+      LSTM           U(-1, 1) / sqrt(hidden) (torch's init), Linear N(0, 1 / fan_in), bias 0.1 N
+      out            N(0, 1 / fan_in) times out_scale: the bounded mask's magnitudes spread over (0, 1) instead of
+                     saturating at tanh's ceiling on the test signals"""
+    from .hnsep import CascadedNet
+    cfg = dict(HNSEP_SMALL if cfg is None else cfg)
+    shapes = OrderedDict((k, tuple(v.shape)) for k, v in CascadedNet(**cfg).state_dict().items())
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "num_batches_tracked":
+            out[name] = np.zeros((), dtype=np.int64)
+            continue
+        z = rng.standard_normal(shape)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
+        if ".lstm." in name:
+            hid = shapes[name.replace("ih", "hh").replace("bias_hh", "weight_hh").replace("bias_ih", "weight_hh")][1]
+            w = rng.uniform(-1, 1, shape) / np.sqrt(hid)
+        elif len(shape) == 1 and ".dense.0." in name:
+            w = 0.1 * z
+        elif len(shape) == 1:
+            w = {"weight": 1.0 + 0.1 * z, "bias": 0.1 * z, "running_mean": 0.1 * z,
+                 "running_var": 1.0 + 0.25 * rng.uniform(0, 1, shape)}[leaf]
+        elif ".dense.0." in name:
+            w = z / np.sqrt(fan_in)
+        elif name in ("out.weight", "aux_out.weight"):
+            w = out_scale * z / np.sqrt(fan_in)
+        else:
+            w = np.sqrt(2.0 / fan_in) * z
+        out[name] = np.ascontiguousarray(w, dtype=np.float32)
+    return out

@@ -55,7 +55,10 @@ enum { DSD_BACKBONE_WAVENET = 0, DSD_BACKBONE_LYNXNET = 1,
        DSD_MEL_ANALYSIS = 6,
        /* modules/pe/rmvpe/inference.py:14  RMVPE pitch extractor (E2E0 + MelSpectrogram + to_local_average_f0);
           created with dsd_rmvpe_create */
-       DSD_PE_RMVPE = 7 };
+       DSD_PE_RMVPE = 7,
+       /* modules/hnsep/vr/nets.py:72  CascadedNet (VR harmonic-noise separator, is_complex=True) and the variance curves
+          built on it; created with dsd_hnsep_create */
+       DSD_HNSEP_VR = 8 };
 /* modules/backbones/lynxnet.py:38-42  activation_classes */
 enum { DSD_ACT_PRELU = 0, DSD_ACT_SILU = 1, DSD_ACT_RELU = 2 };
 
@@ -606,6 +609,93 @@ typedef struct dsd_kernel_time {
 } dsd_kernel_time;
 int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_classes, int32_t* n_classes,
                               double* empty_pair_ms);
+
+/*
+ * VR harmonic-noise separation and the variance curves (utils/decomposed_waveform.py: DecomposedWaveformVocalRemover,
+ * utils/binarizer_utils.py: get_energy_librosa, get_breathiness, get_voicing, get_tension_base_harmonic).  fp32 throughout.
+ * Weights load through dsd_load_weight under CascadedNet's state_dict names (aux_out.weight and num_batches_tracked are
+ * accepted and unused), then dsd_finalize_weights.  A separator handle returns DSD_ESTATE on every entry point but these
+ * and the weight loading.
+ */
+/* CascadedNet(n_fft, hop_length, nout, nout_lstm, is_complex=True, is_mono)  (modules/hnsep/vr/nets.py:72-117) */
+typedef struct dsd_hnsep_config {
+    int32_t struct_size;        /* sizeof(dsd_hnsep_config)                                                          */
+    int32_t n_fft;              /* a multiple of 64, 128 .. 4096                                                     */
+    int32_t hop_length;         /* 1 .. n_fft / 2                                                                    */
+    int32_t nout;               /* a multiple of 4, 4 .. 64                                                          */
+    int32_t nout_lstm;          /* a multiple of 8, 8 .. 128                                                         */
+    int32_t is_mono;            /* 1: nin = 2 (one complex channel); 0: nin = 4 (stereo; a mono clip is repeated to two
+                                   channels and the outputs averaged, as DecomposedWaveformVocalRemover._infer)      */
+    int32_t device;
+} dsd_hnsep_config;
+
+int dsd_hnsep_create(const dsd_hnsep_config* cfg, dsd_handle** out);
+/*
+ * Frame count of predict_from_audio's padded spectrogram for a clip of n_samples: 32 (n // 32 + 1), n = n_samples //
+ * hop_length + 1 (always a multiple of 32).  DSD_EINVAL for n_samples < 1 or hop_length < 1.  Host only.
+ */
+int64_t dsd_hnsep_num_frames(int64_t n_samples, int32_t hop_length);
+/*
+ * Replaces: CascadedNet.forward(spec) in eval mode: complex spectrogram [B, C, n_fft / 2 + 1, T] -> bounded complex mask of the
+ * same shape (bins past n_fft / 2 replicate the last one).  C = 1 (mono model) or 2.
+ *   spec        re of element (b, c, f, t) at spec[b * s_stride_b + c * s_stride_c + f * s_stride_f + t * s_stride_t], im at
+ *               the next float (torch.view_as_real) (device fp32)
+ *   lengths     HOST array of B frame counts (multiples of 16, 16 <= lengths[b] <= T) or NULL (T, a multiple of 16); item
+ *               b is computed exactly as a lone call on its own frames
+ *   mask_out    same layout with the m_stride_* strides; frames at or past lengths[b] are not written
+ */
+int dsd_hnsep_mask(dsd_handle* h, const float* spec, int32_t B, int32_t T, int64_t s_stride_b, int64_t s_stride_c,
+                   int64_t s_stride_f, int64_t s_stride_t, const int64_t* lengths, float* mask_out, int64_t m_stride_b,
+                   int64_t m_stride_c, int64_t m_stride_f, int64_t m_stride_t, void* stream);
+/*
+ * Replaces: CascadedNet.predict_from_audio (nets.py:148-166): zero pad to dsd_hnsep_num_frames frames, STFT (periodic Hann,
+ * center=True, pad_mode 'constant') of each channel, spec * forward(spec), iSTFT, crop to the clip.
+ *   wav           channel c of item b: sample s at wav[b * wav_stride_b + c * wav_stride_c + s], s < n_samples (device
+ *                 fp32); a stereo model with wav_stride_c == 0 sees one clip on both channels (DecomposedWaveformVocalRemover.
+ *                 _infer's repeat; one STFT serves both); a mono model ignores wav_stride_c
+ *   lengths       HOST array of B sample counts (1 <= lengths[b] <= n_samples) or NULL; item b is computed exactly as a lone
+ *                 call on its own samples
+ *   harmonic_out  the harmonic part: sample s < lengths[b] of channel c of item b at harmonic_out[b * out_stride_b +
+ *                 c * out_stride_c + s]; a stereo model with out_stride_c == 0 writes the mean of its two channels
+ *                 (_infer's torch.mean over channels) at harmonic_out[b * out_stride_b + s]
+ */
+int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
+                       int64_t wav_stride_c, const int64_t* lengths, float* harmonic_out, int64_t out_stride_b,
+                       int64_t out_stride_c, void* stream);
+/*
+ * Replaces: DecomposedWaveformPyWorld._kth_harmonic(0)  (decomposed_waveform.py:132-193) after its host part: STFT of the
+ * harmonic part (Nuttall window of win_size, n_fft = win_size, hop_size, center=True, pad_mode 'reflect'), the per-frame bin
+ * mask center = f0 win_size / sample_rate, [max(center - 3.5, 0), min(center + 3.5, win_size / 2 + 1)), center >= 1 (frames
+ * at or past f0_lengths[b]: 0), iSTFT with length = the clip's samples.  Needs lengths[b] > win_size / 2 (torch's reflect pad)
+ * and hop_size <= win_size / 2 (a larger hop lets the window-square envelope reach 0, where torch.istft raises).
+ *   harmonic      item b's sample s at harmonic[b * stride_b + s], s < lengths[b] (device fp32)
+ *   f0            the interpolated, edge-padded f0 (fp32, Hz) of frame t < f0_lengths[b] at f0[b * f0_stride_b + t]
+ *   out           the base harmonic at out[b * out_stride_b + s], s < lengths[b]
+ * Any separator handle serves (no weights are used).
+ */
+int dsd_base_harmonic(dsd_handle* h, const float* harmonic, int32_t B, int64_t n_samples, int64_t stride_b,
+                      const int64_t* lengths, const float* f0, int64_t f0_stride_b, const int64_t* f0_lengths,
+                      int32_t sample_rate, int32_t hop_size, int32_t win_size, float* out, int64_t out_stride_b,
+                      void* stream);
+/* tension domains of get_tension_base_harmonic */
+enum { DSD_TENSION_RATIO = 0, DSD_TENSION_DB = 1, DSD_TENSION_LOGIT = 2 };
+/*
+ * Replaces: get_energy_librosa (binarizer_utils.py:82-102) on the waveform (energy), the aperiodic part = waveform - harmonic
+ * (get_breathiness), the harmonic part (get_voicing), and get_tension_base_harmonic from the harmonic part and the base
+ * harmonic.  The RMS is librosa 0.9.2's feature.rms(frame_length=win_size, hop_length=hop_size, center=True,
+ * pad_mode="constant"); it is padded with zeros or cropped to frames[b]; dB is amplitude_to_db(amin=1e-5, top_db=80) against
+ * the item's own maximum.
+ *   wav, harmonic, base   item b's sample s < lengths[b] at ptr[b * stride_b + s] (device fp32); each may be NULL when no
+ *                         requested curve needs it (energy: wav; breathiness: wav, harmonic; voicing: harmonic; tension:
+ *                         harmonic, base)
+ *   frames                HOST array of B curve lengths (`length` of the reference)
+ *   energy_db             1: energy, breathiness and voicing in dB ('db'); 0: the padded RMS itself ('amplitude')
+ *   energy, breathiness, voicing, tension   frame t < frames[b] of item b at ptr[b * out_stride_b + t], or NULL (not computed)
+ */
+int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, const float* base, int32_t B,
+                        int64_t stride_b, const int64_t* lengths, int32_t hop_size, int32_t win_size, const int64_t* frames,
+                        int32_t tension_domain, int32_t energy_db, float* energy, float* breathiness, float* voicing,
+                        float* tension, int64_t out_stride_b, void* stream);
 
 #ifdef __cplusplus
 }
