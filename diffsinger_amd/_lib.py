@@ -223,6 +223,17 @@ def check(handle, rc, what):
     raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
 
 
+def load_state_dict(handle, sd):
+    """Every tensor of `sd` (torch tensors or arrays, copied through host float32) into the handle, then finalize."""
+    import numpy as np
+    for name, v in sd.items():
+        a = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v), dtype=np.float32)
+        shape = (C.c_int64 * max(1, a.ndim))(*(a.shape or (1,)))
+        check(handle, lib().dsd_load_weight(handle, name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), shape, a.ndim, 0),
+              f"dsd_load_weight({name})")
+    check(handle, lib().dsd_finalize_weights(handle), "dsd_finalize_weights")
+
+
 def program_to_c(prog):
     """schedule.Program -> (DsdProgram, keepalive)."""
     n = len(prog.evals)

@@ -1,8 +1,10 @@
 // libdsdenoise C-ABI (include/dsdenoise.h): handle, weight re-layout, workspace, backbone launch
 // sequences (WaveNet / LYNXNet), sampling-program executor and hipGraph cache.  gfx950 only.
 //
-// Map of this file (one translation unit: every entry point shares the handle, the packed-weight blob and make_gemm):
-//   handle + host tensors ............ struct dsd_handle, expected_params*(): the state-dict layouts the library accepts
+// Map of this file (one translation unit: these entry points share the packed-weight blob and make_gemm; the handle itself,
+// struct dsd_handle, is in api_host.h):
+//   shared with the other host files . fail, select_device, store_weight / check_missing / upload_blob, bn_scale_shift
+//   state-dict layouts ............... expected_params*(): the names and shapes the library accepts
 //   weight re-layout ................. pack_gemm (MFMA fragment order), build_packed{,_aux,_enc,_tok,_voc}
 //   workspaces ....................... ensure_workspace / ensure_state / ensure_emb (kept across shape changes)
 //   GEMM launch decisions ............ make_gemm (tile width, fast / generic path, ragged lengths), run_gemm
@@ -12,26 +14,13 @@
 //   variance-model encoders .......... dsd_token_encoder_create, dsd_token_encode, dsd_predict_dur, dsd_cond_assemble
 //   vocoder .......................... run_tconv, dsd_vocoder_create, dsd_vocode, dsd_vocode_ragged
 //   aux decoder ...................... dsd_aux_decode
-//   mel analysis ..................... dsd_mel_create, dsd_mel_filterbank, dsd_mel_num_frames, dsd_mel_analyze (mel_kernels.hip)
 //   diagnostics ...................... dsd_get_stats, dsd_kernel_timing*
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <functional>
-#include <map>
-#include <numeric>
-#include <set>
-#include <string>
-#include <vector>
-
-#include "../../include/dsdenoise.h"
-#include "dsd_internal.h"
-
-using namespace dsd;
+// The analysis families use none of the above but the handle and have host files of their own:
+//   mel analysis ..................... mel_api.hip    dsd_mel_*
+//   RMVPE pitch extraction ........... rmvpe_api.hip  dsd_rmvpe_*  (its front end is mel_api.hip's mel_run)
+//   VR harmonic-noise separation ..... hnsep_api.hip  dsd_hnsep_*, dsd_base_harmonic, dsd_variance_curves
+// dsd_load_weight, dsd_finalize_weights and dsd_destroy hand an RMVPE or separator handle on to them.
+#include "api_host.h"
 
 // ------------------------------------------------------------------------------------------
 // path switches: every C-ABI entry point that launches kernels takes a snapshot into its handle (dsd_internal.h, PathOpts)
@@ -67,233 +56,13 @@ TimingSlot& timing_slot() {
 }  // namespace dsd
 
 namespace {
-
 std::string g_create_error = "";
-
-struct HostTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-};
-
-// one packed GEMM operand set on the device
-struct PackedGemm {
-    size_t a_off = 0;     // float offset into the weight blob
-    size_t bias_off = 0;  // float offset, or SIZE_MAX
-    int M = 0;            // real rows
-    int K = 0;            // padded input channels
-    int Kreal = 0;
-    int taps = 1;
-    int pairC = 0;        // > 0: paired packing with this many pairs
-};
-
-// weights of a few-channel convolution in tconv.hip's B-fragment order
-struct PackedTConv {
-    size_t w_off = SIZE_MAX, b_off = 0;
-    int ci = 0, co = 0, co_real = 0, taps = 0;
-    bool valid() const { return w_off != SIZE_MAX; }
-};
-
-struct GraphEntry {
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-};
-
 }  // namespace
 
-// dsd_vocode_ragged: one rate of the generator (stage i = after i upsamplings), all pointers into dsd_handle::vr_dev
-struct VocRagStage {
-    int T = 0;                          // padded length of the batch at this rate
-    const int* lens = nullptr;          // [B] item lengths at this rate
-    long valid = 0;                     // their sum
-    const int* cg[3] = {};              // GEMM column groups (item, frame tile) with valid frames, 16 / 32 / 64-frame tiles
-    int ncg[3] = {};
-    const int* tc = nullptr;            // tconv.hip's 256-frame tiles with valid frames
-    int ntc = 0;
-};
-
-// dsd_mel_analyze: per handle, the filterbank on the device and the DFT bases of the (N', W') sizes met so far
-struct MelBasis {
-    int N = 0, W = 0;
-    float* dev = nullptr;
-};
-struct MelState {
-    dsd_mel_config cfg;
-    int k_lo = 0, k_hi = -1;            // the bins any filter reads (k_hi < k_lo: none)
-    std::vector<int> range_host;        // [M][2] bins [lo, hi) relative to k_lo
-    int *range = nullptr, *woff = nullptr;
-    float* fw = nullptr;                // packed non-zero runs
-    std::vector<MelBasis> bases;        // most recent last
-    std::vector<int> work_host;
-    int* work = nullptr;
-    size_t work_cap = 0;
-    float* mags = nullptr;
-    size_t mags_cap = 0;
-};
-
-// dsd_rmvpe_*: the offsets of a conv's packed parts in the weight blob (floats)
-struct RmConvW {
-    size_t w = 0, shift = 0, ws = 0, bs = 0;
-    int cin = 0, cout = 0, cout_pad = 0;
-    bool sc = false;            // a 1x1 shortcut conv (ws / bs): ConvBlockRes with in != out
-};
-struct RmBlockW {
-    RmConvW c1, c2;             // c2 carries the residual
-};
-struct RmvpeState {
-    dsd_rmvpe_config cfg;
-    std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
-    bool finalized = false;
-    float* blob = nullptr;
-    float bn0_scale = 1.f, bn0_shift = 0.f;                  // unet.encoder.bn (1 channel)
-    std::vector<std::vector<RmBlockW>> enc, inter, dec;     // [layer][block]
-    std::vector<RmConvW> up;                                 // decoder ConvTranspose2d per layer
-    RmConvW head;                                            // cnn
-    size_t wih = 0, bih = 0, whh = 0, bhh = 0, fcw = 0, fcb = 0;
-    MelState* mel = nullptr;                                 // MelSpectrogram(128, 16000, 1024, 160, None, 30, 8000)
-    struct Resampler {
-        int sr = 0, orig = 0, nw = 0, width = 0, K = 0;
-        float* dev = nullptr;
-    };
-    std::vector<Resampler> rs;                               // per input sample rate met so far
-    float* ws = nullptr;                                     // workspace
-    size_t ws_cap = 0;
-    int* iws = nullptr;                                      // per-item counts and work lists
-    size_t iws_cap = 0;
-    std::vector<int> iw_host, lens_host;
-    float* fe = nullptr;                                     // front end: log-mel, resampled audio
-    size_t fe_cap = 0;
-    int* lens = nullptr;                                     // resampler: samples in / out per item
-    size_t lens_cap = 0;
-};
-
-struct HnsepState;
-
-struct dsd_handle {
-    dsd_config cfg;
-    std::string err;
-    std::map<std::string, HostTensor> raw;
-    // WaveNet with a channel count that is not a multiple of 32: cfg.num_channels is the count the kernels run with
-    // (rounded up), c_user the caller's; `padded` holds the zero-extended tensors build_packed reads (pad_wavenet_weights)
-    std::map<std::string, HostTensor> padded;
-    int c_user = 0;
-    // wn_edge.hip: the state buffer whose input projection the previous evaluation's edge kernel already wrote into xh
-    const float* edge_xh_src = nullptr;
-    bool finalized = false;
-    PathOpts opts;                  // path switches: the snapshot of the last entry point that launches kernels (read_path_opts)
-
-    // packed weights
-    std::vector<float> blob_host;
-    float* blob = nullptr;
-    size_t blob_floats = 0;
-    PackedGemm g_inproj, g_emb0, g_emb1, g_dproj, g_cp, g_tail1, g_out;
-    std::vector<PackedGemm> g_conv, g_outp;          // WaveNet per layer
-    // split-bf16 precision mode (wn_layer_x3.hip): 0 = fp32 (default), 1 = bf16x3 where a kernel exists; the layers' weight
-    // streams (float offsets into the blob; empty: not built)
-    int precision = 0;
-    std::vector<size_t> x3_conv, x3_out;
-    int cus = 256;                  // compute units of the device (hipDeviceProp_t::multiProcessorCount): one fused round = `cus` tiles
-    std::vector<PackedGemm> g_pw1, g_pw2;            // LYNXNet per layer
-    std::vector<size_t> dw_w, dw_b, dw_prelu;        // LYNXNet / ConvNeXt depthwise params (float offsets)
-    PackedGemm g_ain, g_aout;                        // ConvNeXt aux decoder: dense k-tap in/out convs
-    // NSF-HiFiGAN generator
-    dsd_vocoder_config vcfg;
-    PackedGemm v_pre, v_post;
-    std::vector<PackedGemm> v_ups;                   // transposed convs as phase-row GEMMs
-    std::vector<std::vector<PackedGemm>> v_res;      // [stage * n_kernels + j][2 * n_dil (ResBlock1) or n_dil]
-    std::vector<std::vector<PackedTConv>> v_rest;    // same indexing: the 16- / 32-channel stages (tconv.hip)
-    PackedTConv v_postt;
-    std::vector<size_t> v_nw, v_nb;                  // noise conv weights / biases
-    std::vector<int> v_uptaps;
-    size_t v_linw = 0, v_linb = 0;
-    int vB = 0, vT = 0;
-    float* v_arena = nullptr;
-    std::vector<float*> v_buf;                       // per stage: x, t1, r, acc
-    float *v_mel = nullptr, *v_pre_out = nullptr, *v_har = nullptr, *v_phase = nullptr, *v_wav = nullptr;
-    // ragged vocoder batches: per-rate lengths and valid-tile lists (one device block, rebuilt when B, T or the lengths change)
-    std::vector<int> vr_key, vr_host;
-    int* vr_dev = nullptr;
-    size_t vr_cap = 0;
-    std::vector<VocRagStage> vr_st;
-    // mel analysis (dsd_mel_create): the config, the filterbank's packed non-zero runs and the device blocks of dsd_mel_analyze
-    MelState* mel = nullptr;
-    // RMVPE pitch extraction (dsd_rmvpe_create): config, packed weights, its own mel front end, workspace
-    RmvpeState* pe = nullptr;
-    // VR harmonic-noise separation (dsd_hnsep_create): config, packed weights, DFT bases, workspace
-    HnsepState* hs = nullptr;
-    // FastSpeech2 acoustic encoder
-    dsd_encoder_config ecfg;
-    std::vector<PackedGemm> g_qkv, g_oproj, g_ffn1, g_ffn2;
-    std::vector<size_t> e_ln1g, e_ln1b, e_ln2g, e_ln2b;
-    size_t e_lng = 0, e_lnb = 0, e_txt = 0, e_lang = SIZE_MAX, e_durw = 0, e_durb = 0, e_freqs = 0, e_spk = SIZE_MAX;
-    size_t e_linw[7], e_linb[7];                     // pitch, energy, breathiness, voicing, tension, key shift, speed
-    int eL = 0, eLs = 0, eB = 0, e_pos = 0;
-    int e_ffn_act = DSD_FFN_GELU;                    // TransformerFFNLayer's activation (DSD_FFN_*)
-    float *e_x = nullptr, *e_y = nullptr, *e_qkv = nullptr, *e_mid = nullptr, *e_nonpad = nullptr;
-    int* e_dur = nullptr;
-    float* e_arena = nullptr;
-    // token encoder (variance model): FastSpeech2Encoder + out_proj / DurationPredictor
-    dsd_token_encoder_config tcfg;
-    PackedGemm g_tout;
-    std::vector<PackedGemm> g_dconv;
-    std::vector<size_t> d_lng, d_lnb;
-    size_t d_linw = 0, d_linb = 0;
-    float *d_a = nullptr, *d_b = nullptr, *d_in = nullptr;
-    int dC = 0;
-    size_t freqs_off = 0;
-    int emb_act = ACT_MISH;
-
-    // workspace for (B, T)
-    int B = 0, T = 0, Ts = 0;
-    float* arena = nullptr;
-    size_t arena_floats = 0, arena_cap = 0, state_cap = 0, e_cap = 0, v_cap = 0;
-    float *cond_i = nullptr, *cp = nullptr, *xh = nullptr, *z = nullptr, *skip = nullptr, *hbuf = nullptr;
-    float *xin = nullptr, *ubuf = nullptr, *vbuf = nullptr, *stats = nullptr, *lnpart = nullptr;
-    float *io_in = nullptr, *io_out = nullptr;
-    bool cond_ready = false;
-    // ragged batches (dsd_set_lengths): per-item valid lengths on the device, nullptr = dense
-    int* lens_dev = nullptr;
-    int lens_cap = 0;
-    std::vector<int> lens_host;
-    // ... and, per tile width (16 / 32 / 64 frames), the list of column groups (item, frame tile) with valid frames
-    int* cg_dev[3] = {nullptr, nullptr, nullptr};
-    int cg_cap[3] = {0, 0, 0}, cg_n[3] = {0, 0, 0};
-    std::vector<int> cg_host[3];
-    int cg_T = -1;                  // the T the lists were built for (-1: stale)
-    bool use_cg = false;            // set around the launch sequences that may skip padded tiles
-    // sampler state buffers
-    float* state = nullptr;
-    int state_nbufs = 0;
-    size_t state_buf_floats = 0;
-    // step-embedding tables (columns = steps or batch items)
-    float* emb_arena = nullptr;
-    int emb_cols = 0, Ns = 0;
-    float *t_dev = nullptr, *E = nullptr, *Hd = nullptr, *E2 = nullptr, *D = nullptr;
-    float* Dt = nullptr;            // D transposed: [step column][L * C rows] - what the layer kernels read their FiLM vectors from
-    std::vector<float> t_host;
-
-    std::map<std::string, GraphEntry> graphs;
-    std::set<std::string> graph_seen;      // programs run once eagerly: a graph is captured when one comes back
-
-    // timing of the layer kernels (dsd_kernel_timing): per kernel CLASS - a launch site of run_backbone and the variant of
-    // it that ran (tile width, halo, segment of a mixed plan) - every timing_stride-th launch carries an event pair
-    struct TimedClass {
-        int key = 0;
-        std::string name;           // the instantiation, as rocprofv3 prints it (filled in by the launcher that took the slot)
-        double flops = 0, bytes = 0;    // algorithmic work of one launch (valid frames)
-        long launches = 0;          // all launches of the class since timing was switched on
-        std::vector<size_t> evs;    // indices into ev_pool
-    };
-    bool timing = false;
-    std::vector<TimedClass> tclasses;
-    long timing_evals = 0;         // backbone evaluations since timing was switched on
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
-    size_t ev_used = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> cal_pool;   // back-to-back pairs: the cost of the bracket itself
-    size_t cal_used = 0;
-    int timing_stride = 7;         // coprime with the layer count: every layer is sampled over a pass
-};
-
-namespace {
+// ------------------------------------------------------------------------------------------
+// shared with the analysis families' host files (declared in api_host.h)
+// ------------------------------------------------------------------------------------------
+namespace dsd {
 
 int fail(dsd_handle* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -306,11 +75,79 @@ int fail(dsd_handle* h, int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_OK(h, expr)                                                                          \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return fail(h, DSD_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+int select_device(const char* who, int device, bool say_range) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(nullptr, DSD_EHIP, "%s: no HIP device is visible (this library has no CPU path)", who);
+    if (device < 0 || device >= ndev)
+        return say_range ? fail(nullptr, DSD_EINVAL, "%s: device %d out of range [0, %d)", who, device, ndev)
+                         : fail(nullptr, DSD_EINVAL, "%s: device %d out of range", who, device);
+    if (hipSetDevice(device) != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: hipSetDevice failed", who);
+    return DSD_OK;
+}
+
+int store_weight(dsd_handle* h, const ParamList* expected, const char* name, const float* data, const int64_t* shape,
+                 int32_t ndim, int32_t on_device) {
+    const std::string n(name);
+    std::vector<int64_t> shp(shape, shape + ndim);
+    if (expected) {
+        const std::vector<int64_t>* want = nullptr;
+        for (auto& e : *expected)
+            if (e.first == n) want = &e.second;
+        if (!want) return fail(h, DSD_ENOTFOUND, "unexpected key in state_dict: %s", name);
+        if (*want != shp) {
+            std::string a, b;
+            for (auto v : *want) a += std::to_string(v) + ",";
+            for (auto v : shp) b += std::to_string(v) + ",";
+            return fail(h, DSD_EINVAL, "size mismatch for %s: expected [%s] got [%s]", name, a.c_str(), b.c_str());
+        }
+    }
+    size_t numel = 1;
+    for (auto v : shp) numel *= (size_t)v;
+    HostTensor t;
+    t.shape = shp;
+    t.data.resize(numel);
+    if (on_device) {
+        HIP_OK(h, hipSetDevice(h->cfg.device));
+        HIP_OK(h, hipMemcpy(t.data.data(), data, numel * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+        memcpy(t.data.data(), data, numel * sizeof(float));
+    }
+    h->raw[n] = std::move(t);
+    return DSD_OK;
+}
+
+int check_missing(dsd_handle* h, const ParamList& expected) {
+    std::string missing;
+    for (auto& e : expected)
+        if (!h->raw.count(e.first)) missing += (missing.empty() ? "" : ", ") + e.first;
+    if (!missing.empty()) return fail(h, DSD_ESTATE, "missing keys in state_dict: %s", missing.c_str());
+    return DSD_OK;
+}
+
+int upload_blob(dsd_handle* h, DevBuf<float>& dev, const std::vector<float>& host, size_t tail) {
+    dev = DevBuf<float>();      // free the old blob first: two sets of weights need not fit side by side
+    const int rc = dev.reserve(h, host.size() + tail, "dsd_finalize_weights");
+    if (rc) return rc;
+    if (tail) HIP_OK(h, hipMemset(dev.p, 0, dev.cap * sizeof(float)));
+    HIP_OK(h, hipMemcpy(dev.p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    return DSD_OK;
+}
+
+void bn_scale_shift(const dsd_handle* h, const std::string& p, int C, std::vector<double>& sc, std::vector<double>& sh) {
+    const auto &g = h->raw.at(p + ".weight").data, &b = h->raw.at(p + ".bias").data;
+    const auto &m = h->raw.at(p + ".running_mean").data, &v = h->raw.at(p + ".running_var").data;
+    sc.resize(C);
+    sh.resize(C);
+    for (int c = 0; c < C; ++c) {
+        sc[c] = (double)g[c] / sqrt((double)v[c] + 1e-5);
+        sh[c] = (double)b[c] - (double)m[c] * sc[c];
+    }
+}
+
+}  // namespace dsd
+
+namespace {
 
 void destroy_graphs(dsd_handle* h);
 
@@ -337,17 +174,11 @@ inline int check_lens(dsd_handle* h, const char* who, int B, int T, hipStream_t 
         for (int b = 0; b < B; ++b)
             for (int ft = 0; ft * BN < h->lens_host[b]; ++ft) v.push_back(b * tiles + ft);
         h->cg_n[k] = (int)v.size();
-        if ((int)v.size() > h->cg_cap[k]) {
-            if (h->cg_dev[k]) (void)hipFree(h->cg_dev[k]);
-            h->cg_dev[k] = nullptr;
-            h->cg_cap[k] = 0;
-            const size_t cap = (size_t)B * tiles;
-            if (hipMalloc(&h->cg_dev[k], sizeof(int) * cap) != hipSuccess)
-                return fail(h, DSD_ENOMEM, "%s: hipMalloc of %zu tile indices failed", who, cap);
-            h->cg_cap[k] = (int)cap;
+        if (v.size() > h->cg_dev[k].cap) {
+            if (int rc = h->cg_dev[k].reserve(h, (size_t)B * tiles, who)) return rc;
             destroy_graphs(h);      // cached graphs captured the old pointer
         }
-        if (!v.empty() && hipMemcpyAsync(h->cg_dev[k], v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+        if (!v.empty() && hipMemcpyAsync(h->cg_dev[k].p, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, st) != hipSuccess)
             return fail(h, DSD_EHIP, "%s: upload of the valid-tile list failed", who);
     }
     h->cg_T = T;
@@ -358,18 +189,14 @@ inline int C_of(const dsd_handle* h) { return h->cfg.num_channels; }
 inline int FM_of(const dsd_handle* h) { return h->cfg.in_dims * h->cfg.n_feats; }
 inline int L_of(const dsd_handle* h) { return h->cfg.num_layers; }
 inline int inner_of(const dsd_handle* h) { return h->cfg.num_channels * h->cfg.expansion_factor; }
-inline bool is_wavenet(const dsd_handle* h) { return h->cfg.backbone == DSD_BACKBONE_WAVENET; }
-inline bool is_aux(const dsd_handle* h) { return h->cfg.backbone == DSD_AUX_CONVNEXT; }
-inline bool is_enc(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_ACOUSTIC; }
-inline bool is_tok(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_TOKENS; }
-inline bool is_voc(const dsd_handle* h) { return h->cfg.backbone == DSD_VOC_NSF_HIFIGAN; }
-inline bool is_mel(const dsd_handle* h) { return h->cfg.backbone == DSD_MEL_ANALYSIS; }
-inline bool is_pe(const dsd_handle* h) { return h->cfg.backbone == DSD_PE_RMVPE; }
-inline bool is_hs(const dsd_handle* h) { return h->cfg.backbone == DSD_HNSEP_VR; }
-#define MEL_HANDLE_REJECT(h, who)                                                                                              \
-    if (is_mel(h)) return fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is a mel analysis handle (use dsd_mel_analyze)", who); \
-    if (is_pe(h)) return fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is an RMVPE pitch extractor (use dsd_rmvpe_*)", who); \
-    if (is_hs(h)) return fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is a harmonic-noise separator (use dsd_hnsep_*)", who)
+// the entry points of the model families refuse an analysis handle, which has entry points of its own
+int reject_analysis_handle(const dsd_handle* h, const char* who) {
+    const char* is = is_mel(h)  ? "a mel analysis handle (use dsd_mel_analyze)"
+                     : is_pe(h) ? "an RMVPE pitch extractor (use dsd_rmvpe_*)"
+                     : is_hs(h) ? "a harmonic-noise separator (use dsd_hnsep_*)"
+                                : nullptr;
+    return is ? fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is %s", who, is) : DSD_OK;
+}
 
 inline int voc_stage_channels(const dsd_vocoder_config& v, int i) { return v.upsample_initial_channel >> (i + 1); }
 inline long voc_upp(const dsd_vocoder_config& v, int from) {     // product of upsample_rates[from:]
@@ -1207,7 +1034,7 @@ int build_packed(dsd_handle* h) {
 constexpr size_t kGuard = 256;
 
 int ensure_workspace(dsd_handle* h, int B, int T, hipStream_t st) {
-    if (h->arena && h->B == B && h->T == T) return DSD_OK;
+    if (h->arena.p && h->B == B && h->T == T) return DSD_OK;
     // shape change: drop everything that depends on it
     for (auto& kv : h->graphs) {
         if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
@@ -1247,18 +1074,10 @@ int ensure_workspace(dsd_handle* h, int B, int T, hipStream_t st) {
     off += kGuard;
     // A project's segments all differ in length: keep the allocation while the new shape fits (hipFree + hipMalloc per
     // segment is a device-wide synchronisation each), re-carve it, and clear it on the caller's stream.
-    float* a = h->arena;
-    if (!a || off > h->arena_cap) {
-        if (h->arena) (void)hipFree(h->arena);
-        h->arena = a = nullptr;
-        h->arena_cap = 0;
-        if (hipMalloc(&a, off * sizeof(float)) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "hipMalloc of %zu bytes for the (B=%d, T=%d) workspace failed", off * 4, B, T);
-        h->arena_cap = off;
-    }
+    if (int rc = h->arena.reserve(h, off, "denoiser workspace")) return rc;
+    float* a = h->arena.p;
     // padding frames and guards are masked by every consumer, but start from finite values
     if (hipMemsetAsync(a, 0, off * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(workspace) failed");
-    h->arena = a;
     h->arena_floats = off;
     h->B = B; h->T = T; h->Ts = Ts;
     h->cond_i = a + o_cond; h->cp = a + o_cp; h->xh = a + o_xh; h->io_in = a + o_in; h->io_out = a + o_out;
@@ -1268,43 +1087,21 @@ int ensure_workspace(dsd_handle* h, int B, int T, hipStream_t st) {
 }
 
 int ensure_state(dsd_handle* h, int nbufs, hipStream_t st) {
-    if (h->state && h->state_nbufs >= nbufs) return DSD_OK;
+    if (h->state.p && h->state_nbufs >= nbufs) return DSD_OK;
     const size_t per = ((size_t)h->B * FM_of(h) * h->Ts + 63) / 64 * 64 + 64;
     const size_t total = kGuard * 2 + per * nbufs;
-    float* s = h->state;
-    if (!s || total > h->state_cap) {
-        if (h->state) (void)hipFree(h->state);
-        h->state = s = nullptr;
-        h->state_cap = 0;
-        if (hipMalloc(&s, total * sizeof(float)) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "hipMalloc of %zu bytes for %d sampler state buffers failed", total * 4, nbufs);
-        h->state_cap = total;
-    }
-    if (hipMemsetAsync(s, 0, total * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(state) failed");
-    h->state = s;
+    if (int rc = h->state.reserve(h, total, "sampler state buffers")) return rc;
+    if (hipMemsetAsync(h->state.p, 0, total * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(state) failed");
     h->state_nbufs = nbufs;
     h->state_buf_floats = per;
-    // cached graphs captured the old pointers
-    for (auto& kv : h->graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
-    h->graphs.clear();
-    h->graph_seen.clear();
+    destroy_graphs(h);      // cached graphs captured the old pointers
     return DSD_OK;
 }
-inline float* state_buf(dsd_handle* h, int i) { return h->state + kGuard + h->state_buf_floats * i; }
+inline float* state_buf(dsd_handle* h, int i) { return h->state.p + kGuard + h->state_buf_floats * i; }
 
 int ensure_emb(dsd_handle* h, int ncols) {
-    if (h->emb_arena && h->emb_cols >= ncols) return DSD_OK;
-    if (h->emb_arena) (void)hipFree(h->emb_arena);
-    h->emb_arena = nullptr;
-    for (auto& kv : h->graphs) {
-        if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-    }
-    h->graphs.clear();
-    h->graph_seen.clear();
+    if (h->emb_arena.p && h->emb_cols >= ncols) return DSD_OK;
+    destroy_graphs(h);      // cached graphs captured the old pointers
     const int cap = round_up(ncols, 64);
     const int Ns = padded_ts(cap);
     const size_t C = C_of(h), L = L_of(h);
@@ -1317,10 +1114,9 @@ int ensure_emb(dsd_handle* h, int ncols) {
     const size_t o_t = take(Ns), o_E = take(C * Ns), o_H = take(4 * C * Ns), o_E2 = take(C * Ns), o_D = take(L * C * Ns);
     const size_t o_Dt = take(L * C * Ns);
     off += kGuard;
-    float* a = nullptr;
-    if (hipMalloc(&a, off * sizeof(float)) != hipSuccess) return fail(h, DSD_ENOMEM, "hipMalloc(step tables) failed");
+    if (int rc = h->emb_arena.reserve(h, off, "step tables")) return rc;      // more columns: larger than the last
+    float* a = h->emb_arena.p;
     if (hipMemset(a, 0, off * sizeof(float)) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(step tables) failed");
-    h->emb_arena = a;
     h->emb_cols = cap;
     h->Ns = Ns;
     h->t_dev = a + o_t; h->E = a + o_E; h->Hd = a + o_H; h->E2 = a + o_E2; h->D = a + o_D;
@@ -1343,8 +1139,8 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     GemmCall c;
     memset(&c.p, 0, sizeof(c.p));
     GemmP& p = c.p;
-    p.A = h->blob + g.a_off;
-    p.bias = g.bias_off == SIZE_MAX ? nullptr : h->blob + g.bias_off;
+    p.A = h->blob.p + g.a_off;
+    p.bias = g.bias_off == SIZE_MAX ? nullptr : h->blob.p + g.bias_off;
     p.M = g.M;
     p.C = g.pairC;
     p.B = Bsrc;
@@ -1361,7 +1157,7 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     // ragged batches: only a convolution along time can carry an item's padded frames into its valid ones, so only the
     // k-tap GEMMs over the utterances' (B, T) frames mask their input (not the 1x1s, not the step-embedding MLPs)
     const bool ragged = vr || (h->use_cg && !h->lens_host.empty() && batch == h->B && T == h->T);
-    p.lens = vr ? vr->lens : (ragged && g.taps > 1) ? h->lens_dev : nullptr;
+    p.lens = vr ? vr->lens : (ragged && g.taps > 1) ? h->lens_dev.p : nullptr;
     c.stage = stage;
     c.taps = g.taps;
     c.epi = epi;
@@ -1396,7 +1192,7 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     const int BN = c.nb == 0 ? 16 : 32 * c.nb;
     p.tiles_per_b = (T + BN - 1) / BN;
     if (ragged) {       // the launch covers only the tiles that hold valid frames (lists built by prepare_ragged)
-        p.cgmap = vr ? vr->cg[c.nb] : h->cg_dev[c.nb];
+        p.cgmap = vr ? vr->cg[c.nb] : h->cg_dev[c.nb].p;
         p.ncg = vr ? vr->ncg[c.nb] : h->cg_n[c.nb];
     }
     int S = BN + 2 * p.HL;
@@ -1730,7 +1526,7 @@ inline void film_of(const dsd_handle* h, int layer, int col0, int colb, const fl
 // step tables: E = sinemb(t) -> Hd = act(W0 E + b0) -> E2 = W1 Hd + b1 -> D[l*C + c][col] = Wd_l E2 + bd_l
 int run_step_tables(dsd_handle* h, int ncols, hipStream_t st) {
     const int C = C_of(h), Ns = h->Ns;
-    hipError_t e = launch_sinemb(h->t_dev, ncols, Ns, h->blob + h->freqs_off, C, h->E, st);
+    hipError_t e = launch_sinemb(h->t_dev, ncols, Ns, h->blob.p + h->freqs_off, C, h->E, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "sinemb launch failed: %s", hipGetErrorString(e));
     GemmCall g0 = make_gemm(h, h->g_emb0, h->E, 0, Ns, 1, ncols, ST_PLAIN, EP_BIAS_ACT, 0);
     g0.p.act = h->emb_act; g0.p.out = h->Hd; g0.p.o_bstride = 0; g0.p.o_rstride = Ns;
@@ -1844,9 +1640,9 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     };
     auto layer_params = [&](WnLayerP& p, int l, int bn) {
         memset(&p, 0, sizeof(p));
-        p.Aconv = h->blob + h->g_conv[l].a_off;
-        p.Aout = h->blob + h->g_outp[l].a_off;
-        p.bias_out = h->blob + h->g_outp[l].bias_off;
+        p.Aconv = h->blob.p + h->g_conv[l].a_off;
+        p.Aout = h->blob.p + h->g_outp[l].a_off;
+        p.bias_out = h->blob.p + h->g_outp[l].bias_off;
         p.skip = h->skip;
         p.x_bstride = xs; p.Ts = Ts;
         p.cp = h->cp + (long)l * 2 * C * Ts; p.cp_bstride = cps;
@@ -1881,11 +1677,11 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 layer_params(p, l, sg.bn);
                 p.xin = xi; p.xout = xo; p.z = h->hbuf;
                 p.tile0 = sg.t0; p.ntiles = sg.nt;
-                if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[sg.bn == 16 ? 0 : 1] + sg.t0; p.ncg = sg.nt; }
+                if (ragged) { p.lens = h->lens_dev.p; p.cgmap = h->cg_dev[sg.bn == 16 ? 0 : 1].p + sg.t0; p.ncg = sg.nt; }
                 const int vkey = (int)k * 4 + (p.dil > 8 ? 2 : 0) + (sg.bn == 16 ? 1 : 0);
                 if (sg.kind == WN_FUSED_X3) {
-                    p.Aconv = h->blob + h->x3_conv[l];
-                    p.Aout = h->blob + h->x3_out[l];
+                    p.Aconv = h->blob.p + h->x3_conv[l];
+                    p.Aout = h->blob.p + h->x3_out[l];
                     rc = timed_launch(h, 150 + vkey, (fl_conv + fl_out) * fr, 24.0 * C * fr, "bf16x3 fused WaveNet layer",
                                       [&] { return launch_wn_layer_x3(p, C, B, st); });
                 } else if (sg.kind == WN_FUSED) {
@@ -1908,7 +1704,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 WnLayerP p;
                 layer_params(p, l, form.rs_bn);
                 p.xin = h->xh; p.xout = h->xh; p.z = h->z;
-                if (ragged) { p.lens = h->lens_dev; p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
+                if (ragged) { p.lens = h->lens_dev.p; p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
                 if ((rc = rowsplit(p, form.rs_bn, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
                 continue;
             }
@@ -1929,9 +1725,9 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         const int bnw = 16 * ncb;
         WnEdgeP p;
         memset(&p, 0, sizeof(p));
-        p.A1 = h->blob + h->g_tail1.a_off; p.b1 = h->blob + h->g_tail1.bias_off;
-        p.A2 = h->blob + h->g_out.a_off; p.b2 = h->blob + h->g_out.bias_off;
-        p.A3 = h->blob + h->g_inproj.a_off; p.b3 = h->blob + h->g_inproj.bias_off;
+        p.A1 = h->blob.p + h->g_tail1.a_off; p.b1 = h->blob.p + h->g_tail1.bias_off;
+        p.A2 = h->blob.p + h->g_out.a_off; p.b2 = h->blob.p + h->g_out.bias_off;
+        p.A3 = h->blob.p + h->g_inproj.a_off; p.b3 = h->blob.p + h->g_inproj.bias_off;
         p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
         p.in_scale = sqrtf((float)L);
         p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
@@ -1953,7 +1749,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             for (int i = 0; i < nout; ++i)
                 if (lo[i].dst == next_xin) p.next_src = i;
         int nwg = B * p.tiles_per_b;
-        if (ragged) { p.cgmap = h->cg_dev[ncb == 2 ? 1 : 0]; p.ncg = h->cg_n[ncb == 2 ? 1 : 0]; nwg = p.ncg; }
+        if (ragged) { p.cgmap = h->cg_dev[ncb == 2 ? 1 : 0].p; p.ncg = h->cg_n[ncb == 2 ? 1 : 0]; nwg = p.ncg; }
         if (fits) {      // (more state terms than the kernel holds at once: the three GEMMs below)
             double fr_all = (double)B * T;
             if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
@@ -1996,7 +1792,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         q.tiles_per_b = (T + 63) / 64;
         q.inv_tiles_per_b = 1.0f / (float)q.tiles_per_b;
         q.nft = B * q.tiles_per_b;
-        if (ragged) { q.cgmap = h->cg_dev[2]; q.ncg = h->cg_n[2]; }
+        if (ragged) { q.cgmap = h->cg_dev[2].p; q.ncg = h->cg_n[2]; }
         q.inv_nft = 1.0f / (float)std::max(1, ragged ? q.ncg : q.nft);
     };
     const PathOpts& o = h->opts;
@@ -2004,13 +1800,13 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         // the resident and bf16x3 kernels' parameters (lynx_layer.hip, lynx_x3.hip)
         LxLayerP p;
         memset(&p, 0, sizeof(p));
-        p.A1 = h->blob + h->g_pw1[l].a_off; p.bias1 = h->blob + h->g_pw1[l].bias_off;
-        p.A2 = h->blob + h->g_pw2[l].a_off; p.bias2 = h->blob + h->g_pw2[l].bias_off;
+        p.A1 = h->blob.p + h->g_pw1[l].a_off; p.bias1 = h->blob.p + h->g_pw1[l].bias_off;
+        p.A2 = h->blob.p + h->g_pw2[l].a_off; p.bias2 = h->blob.p + h->g_pw2[l].bias_off;
         p.xin = h->xin; p.stats = h->stats; p.u = h->ubuf; p.v = h->vbuf; p.x = h->xh;
         p.x_bstride = xs; p.u_bstride = us; p.inner = inner; p.Ts = Ts; p.T = T;
         p.tiles_per_b = (T + 31) / 32; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
         p.nft = B * p.tiles_per_b;
-        if (ragged) { p.cgmap = h->cg_dev[1]; p.ncg = h->cg_n[1]; }
+        if (ragged) { p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
         p.inv_nft = 1.0f / (float)std::max(1, ragged ? p.ncg : p.nft);
         p.strong = h->cfg.strong_cond;
         p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles;
@@ -2024,7 +1820,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         if (pl.ln_merge && (rc = ln_merge())) return rc;
         if (pl.pw1 == LX_X3) {
             LxLayerP q = p;
-            q.A1 = h->blob + h->x3_conv[l];
+            q.A1 = h->blob.p + h->x3_conv[l];
             widen(q, pl.x3_ncb1);
             rc = timed_launch(h, 650 + (pl.x3_ncb1 == 4 ? 1 : 0), fl1, by1, "LYNXNet pw1", [&] { return launch_lx_x3(q, 0, C, pl.x3_ncb1, st); });
         } else if (pl.pw1 == LX_RESIDENT) {
@@ -2036,13 +1832,13 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             rc = timed_launch(h, 630, fl1, by1, "LYNXNet pw1 GEMM", [&] { return run_gemm(h, g, st); });
         }
         if (rc) return rc;
-        rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, ragged ? h->lens_dev : nullptr, h->blob + h->dw_w[l],
-                                        h->blob + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
-                                        h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob + h->dw_prelu[l], st), "dwconv");
+        rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, ragged ? h->lens_dev.p : nullptr, h->blob.p + h->dw_w[l],
+                                        h->blob.p + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
+                                        h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob.p + h->dw_prelu[l], st), "dwconv");
         if (rc) return rc;
         if (pl.pw2 == LX_X3) {
             LxLayerP q = p;
-            q.A2 = h->blob + h->x3_out[l];
+            q.A2 = h->blob.p + h->x3_out[l];
             widen(q, pl.x3_ncb2);
             rc = timed_launch(h, 660 + (pl.x3_ncb2 == 4 ? 1 : 0), fl2, by2, "LYNXNet pw2 (bf16x3)", [&] { return launch_lx_x3(q, 1, C, pl.x3_ncb2, st); });
         } else if (pl.pw2 == LX_RESIDENT) {
@@ -2110,12 +1906,6 @@ void destroy_graphs(dsd_handle* h) {
     h->graph_seen.clear();
 }
 
-void mel_state_free(MelState* m);
-int rmvpe_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim, int32_t on_device);
-int rmvpe_finalize(dsd_handle* h);
-int hnsep_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim, int32_t on_device);
-int hnsep_finalize(dsd_handle* h);
-void hnsep_free(HnsepState* s);
 
 }  // namespace
 
@@ -2160,12 +1950,7 @@ int dsd_create(const dsd_config* cfg, dsd_handle** out) {
         if (cfg->activation < DSD_ACT_PRELU || cfg->activation > DSD_ACT_RELU)
             return fail(nullptr, DSD_EINVAL, "dsd_create: %d is not a valid activation", cfg->activation);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_create: hipSetDevice failed");
+    if (int rc = select_device("dsd_create", cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_layer_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_rowsplit_init_all();
@@ -2203,26 +1988,10 @@ void dsd_destroy(dsd_handle* h) {
         (void)hipEventDestroy(ev.first);
         (void)hipEventDestroy(ev.second);
     }
-    if (h->blob) (void)hipFree(h->blob);
-    if (h->arena) (void)hipFree(h->arena);
-    if (h->state) (void)hipFree(h->state);
-    if (h->emb_arena) (void)hipFree(h->emb_arena);
-    if (h->lens_dev) (void)hipFree(h->lens_dev);
-    for (int k = 0; k < 3; ++k)
-        if (h->cg_dev[k]) (void)hipFree(h->cg_dev[k]);
-    if (h->e_arena) (void)hipFree(h->e_arena);
-    if (h->v_arena) (void)hipFree(h->v_arena);
-    if (h->vr_dev) (void)hipFree(h->vr_dev);
     mel_state_free(h->mel);
-    if (RmvpeState* r = h->pe) {
-        mel_state_free(r->mel);
-        for (auto& x : r->rs) (void)hipFree(x.dev);
-        for (void* p : {(void*)r->blob, (void*)r->ws, (void*)r->iws, (void*)r->fe, (void*)r->lens})
-            if (p) (void)hipFree(p);
-        delete r;
-    }
+    rmvpe_free(h->pe);
     hnsep_free(h->hs);
-    delete h;
+    delete h;       // the device buffers go with their owners
 }
 
 int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim,
@@ -2230,67 +1999,36 @@ int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const in
     if (h && is_pe(h)) return rmvpe_load_weight(h, name, data, shape, ndim, on_device);
     if (h && is_hs(h)) return hnsep_load_weight(h, name, data, shape, ndim, on_device);
     if (!h || !name || !data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    MEL_HANDLE_REJECT(h, "dsd_load_weight");
+    if (int rc = reject_analysis_handle(h, "dsd_load_weight")) return rc;
     const std::string n(name);
-    std::vector<int64_t> shp(shape, shape + ndim);
-    bool found = false;
     if ((is_enc(h) || is_tok(h)) && n == "encoder.embed_positions._float_tensor")
         return DSD_OK;       // SinusoidalPositionalEmbedding's device/dtype marker buffer (common_layers.py:59): carries no value
+    int rc;
     if (n == "diffusion_embedding.freqs" && !is_enc(h) && !is_voc(h) && !is_tok(h)) {
         const int cu = h->c_user ? h->c_user : h->cfg.num_channels;
-        if (ndim != 1 || shp[0] != cu / 2)
+        if (ndim != 1 || shape[0] != cu / 2)
             return fail(h, DSD_EINVAL, "diffusion_embedding.freqs must have shape [%d]", cu / 2);
-        found = true;
+        rc = store_weight(h, nullptr, name, data, shape, ndim, on_device);      // a buffer: in no parameter list
     } else {
-        for (auto& e : expected_for(h)) {
-            if (e.first != n) continue;
-            if (e.second != shp) {
-                std::string want, got;
-                for (auto v : e.second) want += std::to_string(v) + ",";
-                for (auto v : shp) got += std::to_string(v) + ",";
-                return fail(h, DSD_EINVAL, "size mismatch for %s: expected [%s] got [%s]", name, want.c_str(), got.c_str());
-            }
-            found = true;
-            break;
-        }
+        const ParamList expected = expected_for(h);
+        rc = store_weight(h, &expected, name, data, shape, ndim, on_device);
     }
-    if (!found) return fail(h, DSD_ENOTFOUND, "unexpected key in state_dict: %s", name);
-    size_t numel = 1;
-    for (auto v : shp) numel *= (size_t)v;
-    HostTensor t;
-    t.shape = shp;
-    t.data.resize(numel);
-    if (on_device) {
-        HIP_OK(h, hipSetDevice(h->cfg.device));
-        HIP_OK(h, hipMemcpy(t.data.data(), data, numel * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(t.data.data(), data, numel * sizeof(float));
-    }
-    h->raw[n] = std::move(t);
-    h->finalized = false;
-    return DSD_OK;
+    if (rc == DSD_OK) h->finalized = false;
+    return rc;
 }
 
 int dsd_finalize_weights(dsd_handle* h) {
     if (!h) return DSD_EINVAL;
     if (is_pe(h)) return rmvpe_finalize(h);
     if (is_hs(h)) return hnsep_finalize(h);
-    MEL_HANDLE_REJECT(h, "dsd_finalize_weights");
-    std::string missing;
-    for (auto& e : expected_for(h))
-        if (!h->raw.count(e.first)) missing += (missing.empty() ? "" : ", ") + e.first;
-    if (!missing.empty()) return fail(h, DSD_ESTATE, "missing keys in state_dict: %s", missing.c_str());
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    int rc = build_packed(h);
+    if (int rc = reject_analysis_handle(h, "dsd_finalize_weights")) return rc;
+    int rc = check_missing(h, expected_for(h));
     if (rc) return rc;
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    if ((rc = build_packed(h))) return rc;
     destroy_graphs(h);
-    if (h->blob) (void)hipFree(h->blob);
-    h->blob = nullptr;
-    h->blob_floats = h->blob_host.size() + 8192;     // tail guard: the fragment ring reads up to one group (2 x 8 KiB) past the end
-    if (hipMalloc(&h->blob, h->blob_floats * sizeof(float)) != hipSuccess)
-        return fail(h, DSD_ENOMEM, "hipMalloc(%zu bytes of packed weights) failed", h->blob_floats * 4);
-    HIP_OK(h, hipMemset(h->blob, 0, h->blob_floats * sizeof(float)));
-    HIP_OK(h, hipMemcpy(h->blob, h->blob_host.data(), h->blob_host.size() * sizeof(float), hipMemcpyHostToDevice));
+    // tail guard: the fragment ring reads up to one group (2 x 8 KiB) past the end
+    if ((rc = upload_blob(h, h->blob, h->blob_host, 8192))) return rc;
     std::vector<float>().swap(h->blob_host);
     h->finalized = true;
     h->cond_ready = false;
@@ -2304,7 +2042,7 @@ int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int
     if (is_aux(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an aux decoder (use dsd_aux_decode)");
     if (is_enc(h) || is_tok(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an encoder (use dsd_encode / dsd_token_encode)");
     if (is_voc(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is a vocoder (use dsd_vocode)");
-    MEL_HANDLE_REJECT(h, "dsd_prepare_cond");
+    if (int rc = reject_analysis_handle(h, "dsd_prepare_cond")) return rc;
     if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_prepare_cond: weights are not finalized");
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_prepare_cond: B and T must be positive (B=%d, T=%d)", B, T);
     if (stride_t != 1 && stride_h != 1)
@@ -2340,12 +2078,7 @@ int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
     if (cfg->num_spk < 0 || cfg->num_lang < 0) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: negative table size");
     if (cfg->pos_mode < DSD_POS_ROPE || cfg->pos_mode > DSD_POS_SIN) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: pos_mode must be one of DSD_POS_*");
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: ffn_act must be one of DSD_FFN_*");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_encoder_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_encoder_create: hipSetDevice failed");
+    if (int rc = select_device("dsd_encoder_create", cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
     dsd_handle* h = new dsd_handle();
@@ -2369,7 +2102,7 @@ int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
 // input buffer for the duration predictor)
 static int enc_workspace(dsd_handle* h, int B, int L, int H, int Cd, hipStream_t st) {
     const int Ls = padded_ts(L);
-    if (h->e_arena && h->eB == B && h->eL == L && h->dC == Cd) return DSD_OK;
+    if (h->e_arena.p && h->eB == B && h->eL == L && h->dC == Cd) return DSD_OK;
     const size_t per = (size_t)B * Ls;
     size_t off = kGuard;
     auto take = [&](size_t n) {
@@ -2382,17 +2115,10 @@ static int enc_workspace(dsd_handle* h, int B, int L, int H, int Cd, hipStream_t
     const size_t o_np = take(per), o_dur = take((size_t)B * L);
     const size_t o_da = take(per * Cd), o_db = take(per * Cd), o_di = take(Cd > 0 ? per * H : 0);
     off += kGuard;
-    float* a = h->e_arena;      // kept while the new shape fits (every segment of a project has its own token count)
-    if (!a || off > h->e_cap) {
-        if (h->e_arena) (void)hipFree(h->e_arena);
-        h->e_arena = a = nullptr;
-        h->e_cap = 0;
-        if (hipMalloc(&a, off * sizeof(float)) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "hipMalloc of %zu bytes for the encoder workspace failed", off * 4);
-        h->e_cap = off;
-    }
+    // kept while the new shape fits (every segment of a project has its own token count)
+    if (int rc = h->e_arena.reserve(h, off, "encoder workspace")) return rc;
+    float* a = h->e_arena.p;
     if (hipMemsetAsync(a, 0, off * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(encoder workspace) failed");
-    h->e_arena = a;
     h->eB = B; h->eL = L; h->eLs = Ls; h->dC = Cd;
     h->e_x = a + o_x; h->e_y = a + o_y; h->e_qkv = a + o_qkv; h->e_mid = a + o_mid; h->e_nonpad = a + o_np;
     h->e_dur = reinterpret_cast<int*>(a + o_dur);
@@ -2403,7 +2129,7 @@ static int enc_workspace(dsd_handle* h, int B, int L, int H, int Cd, hipStream_t
 // FastSpeech2Encoder.forward after the embedding (tts_modules.py:412-424): e_x (already masked) -> e_y = LN(x) * nonpad
 static int run_fs2_layers(dsd_handle* h, int H, int NL, int heads, int ffn_ks, int B, int L, hipStream_t st) {
     const int Ls = h->eLs;
-    const float* blob = h->blob;
+    const float* blob = h->blob.p;
     const long xs = (long)H * Ls;
     hipError_t er;
     int rc;
@@ -2469,7 +2195,7 @@ int dsd_encode(dsd_handle* h, const int64_t* txt_tokens, const int64_t* mel2ph, 
     const int H = e.hidden_size, Ls = padded_ts(L);
     int rc = enc_workspace(h, B, L, H, 0, st);
     if (rc) return rc;
-    const float* blob = h->blob;
+    const float* blob = h->blob.p;
     hipError_t er;
 #define ENC_OK(expr, what)                                                                        \
     if ((er = (expr)) != hipSuccess) return fail(h, DSD_EHIP, what " launch failed: %s", hipGetErrorString(er))
@@ -2527,12 +2253,7 @@ int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** o
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: duration predictor needs channels >= 1 and an odd kernel size <= 15");
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU)
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: ffn_act must be one of DSD_FFN_*");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_token_encoder_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_token_encoder_create: hipSetDevice failed");
+    if (int rc = select_device("dsd_token_encoder_create", cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_token_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
     dsd_handle* h = new dsd_handle();
@@ -2578,8 +2299,8 @@ int dsd_token_encode(dsd_handle* h, const float* embed, const uint8_t* padding_m
     // x = (embed_scale * main + extra) * nonpadding  (tts_modules.py:401-412), [B, L, H] -> [B][H][Ls]
     ENC_OK(launch_enc_nonpad(padding_mask, B, L, Ls, h->e_nonpad, st), "nonpad");
     ENC_OK(launch_pack(embed, (long)L * H, 1, H, h->e_x, B, H, L, Ls, st), "pack(embed)");
-    if (t.pos_mode == DSD_POS_REL) ENC_OK(launch_enc_relpos(h->e_x, h->blob + h->e_freqs, H, B, L, Ls, st), "relpos");
-    if (t.pos_mode == DSD_POS_SIN) ENC_OK(launch_enc_sinpos(h->e_x, h->e_nonpad, h->blob + h->e_freqs, H, B, L, Ls, st), "sinpos");
+    if (t.pos_mode == DSD_POS_REL) ENC_OK(launch_enc_relpos(h->e_x, h->blob.p + h->e_freqs, H, B, L, Ls, st), "relpos");
+    if (t.pos_mode == DSD_POS_SIN) ENC_OK(launch_enc_sinpos(h->e_x, h->e_nonpad, h->blob.p + h->e_freqs, H, B, L, Ls, st), "sinpos");
     ENC_OK(launch_enc_mask(h->e_x, h->e_nonpad, H, B, L, Ls, st), "mask");
     if ((rc = run_fs2_layers(h, H, t.enc_layers, t.num_heads, t.ffn_kernel_size, B, L, st))) return rc;
     const float* res = h->e_y;
@@ -2608,7 +2329,7 @@ int dsd_predict_dur(dsd_handle* h, const float* dur_cond, const uint8_t* padding
     const int H = t.hidden_size, Cd = t.dur_chans;
     if ((rc = enc_workspace(h, B, L, H, Cd, st))) return rc;
     const int Ls = h->eLs;
-    const float* blob = h->blob;
+    const float* blob = h->blob.p;
     hipError_t er;
 #define ENC_OK(expr, what)                                                                        \
     if ((er = (expr)) != hipSuccess) return fail(h, DSD_EHIP, what " launch failed: %s", hipGetErrorString(er))
@@ -2652,11 +2373,7 @@ int dsd_cond_assemble(const dsd_assemble_args* args, float* out, void* stream) {
         if (!args->term[k].v) return fail(nullptr, DSD_EINVAL, "dsd_cond_assemble: term %d has no vector", k);
         a.t_s[k] = args->term[k].s; a.t_v[k] = args->term[k].v;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_cond_assemble: no HIP device is visible (this library has no CPU path)");
-    if (args->device < 0 || args->device >= ndev) return fail(nullptr, DSD_EINVAL, "dsd_cond_assemble: device %d out of range", args->device);
-    if (hipSetDevice(args->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_cond_assemble: hipSetDevice failed");
+    if (int rc = select_device("dsd_cond_assemble", args->device, false)) return rc;
     hipError_t er = launch_assemble(a, out, (hipStream_t)stream);
     if (er != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_cond_assemble: launch failed: %s", hipGetErrorString(er));
     return DSD_OK;
@@ -2666,8 +2383,8 @@ static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float
                      int T, int Ts, int dil, float slope_in, int act, hipStream_t st, const VocRagStage* vr = nullptr) {
     TConvP p;
     memset(&p, 0, sizeof(p));
-    p.W = h->blob + pt.w_off;
-    p.bias = h->blob + pt.b_off;
+    p.W = h->blob.p + pt.w_off;
+    p.bias = h->blob.p + pt.b_off;
     p.x = x; p.x_bstride = (long)C * Ts; p.x_rstride = Ts;
     p.out = out; p.res = res; p.o_bstride = (long)pt.co_real * Ts; p.o_rstride = Ts;
     p.T = T; p.Ts_out = Ts;
@@ -2713,12 +2430,7 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
             if (cfg->resblock_dilation_sizes[j][d] < 1 || cfg->resblock_dilation_sizes[j][d] * (cfg->resblock_kernel_sizes[j] / 2) > 48)
                 return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: residual block %d dilation %d reaches beyond 48 frames", j, d);
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: hipSetDevice failed");
+    if (int rc = select_device("dsd_vocoder_create", cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess) ie = tconv_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
@@ -2746,7 +2458,7 @@ int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipS
     const dsd_vocoder_config& v = h->vcfg;
     std::vector<int> key = {B, T};
     key.insert(key.end(), lengths, lengths + B);
-    if (h->vr_dev && key == h->vr_key) return DSD_OK;
+    if (h->vr_dev.p && key == h->vr_key) return DSD_OK;
     const int NU = v.n_ups;
     std::vector<VocRagStage> st_(NU + 1);
     std::vector<int>& host = h->vr_host;
@@ -2780,22 +2492,15 @@ int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipS
         r.ntc = (int)(host.size() - off_tc[i]);
         if (i < NU) mul *= v.upsample_rates[i];
     }
-    if (host.size() > h->vr_cap) {
-        if (h->vr_dev) (void)hipFree(h->vr_dev);
-        h->vr_dev = nullptr;
-        h->vr_cap = 0;
-        if (hipMalloc(&h->vr_dev, sizeof(int) * host.size()) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "dsd_vocode_ragged: hipMalloc of %zu tile indices failed", host.size());
-        h->vr_cap = host.size();
-    }
+    if (int rc = h->vr_dev.reserve(h, host.size(), "dsd_vocode_ragged")) return rc;
     h->vr_key.clear();          // stale until the copy is queued
-    if (hipMemcpyAsync(h->vr_dev, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(h->vr_dev.p, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(h, DSD_EHIP, "dsd_vocode_ragged: copy of the tile lists failed");
     for (int i = 0; i <= NU; ++i) {
-        st_[i].lens = h->vr_dev + off_lens[i];
-        st_[i].cg[1] = h->vr_dev + off_cg[0][i];
-        st_[i].cg[2] = h->vr_dev + off_cg[1][i];
-        st_[i].tc = h->vr_dev + off_tc[i];
+        st_[i].lens = h->vr_dev.p + off_lens[i];
+        st_[i].cg[1] = h->vr_dev.p + off_cg[0][i];
+        st_[i].cg[2] = h->vr_dev.p + off_cg[1][i];
+        st_[i].tc = h->vr_dev.p + off_tc[i];
     }
     h->vr_st = st_;
     h->vr_key = key;
@@ -2833,7 +2538,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     len[0] = T;
     for (int i = 0; i < NU; ++i) len[i + 1] = len[i] * v.upsample_rates[i];
     for (int i = 0; i <= NU; ++i) lts[i] = padded_ts((int)len[i]);
-    if (!h->v_arena || h->vB != B || h->vT != T) {
+    if (!h->v_arena.p || h->vB != B || h->vT != T) {
         size_t off = kGuard;
         auto take = [&](size_t n) {
             size_t o = off;
@@ -2848,17 +2553,10 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
             for (int k = 0; k < 4; ++k) ob.push_back(take(n));
         }
         off += kGuard;
-        float* a = h->v_arena;      // kept while the new shape fits: half a gigabyte per 1000 frames is not re-made per segment
-        if (!a || off > h->v_cap) {
-            if (h->v_arena) (void)hipFree(h->v_arena);
-            h->v_arena = a = nullptr;
-            h->v_cap = 0;
-            if (hipMalloc(&a, off * sizeof(float)) != hipSuccess)
-                return fail(h, DSD_ENOMEM, "hipMalloc of %zu bytes for the vocoder workspace failed", off * 4);
-            h->v_cap = off;
-        }
+        // kept while the new shape fits: half a gigabyte per 1000 frames is not re-made per segment
+        if (int rc = h->v_arena.reserve(h, off, "vocoder workspace")) return rc;
+        float* a = h->v_arena.p;
         if (hipMemsetAsync(a, 0, off * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(vocoder workspace) failed");
-        h->v_arena = a;
         h->vB = B; h->vT = T;
         h->v_mel = a + o_mel; h->v_pre_out = a + o_pre; h->v_har = a + o_har; h->v_phase = a + o_ph; h->v_wav = a + o_wav;
         h->v_buf.clear();
@@ -2868,7 +2566,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     if (lengths && (rc = prepare_voc_ragged(h, B, T, lengths, st))) return rc;
     // per rate: nullptr (dense) or the ragged batch's lengths and tiles
     auto rag = [&](int i) -> const VocRagStage* { return lengths ? &h->vr_st[i] : nullptr; };
-    const float* blob = h->blob;
+    const float* blob = h->blob.p;
     hipError_t er;
 #define VOC_OK(expr, what)                                                                        \
     if ((er = (expr)) != hipSuccess) return fail(h, DSD_EHIP, what " launch failed: %s", hipGetErrorString(er))
@@ -3030,8 +2728,8 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
         if ((rc = run_gemm(h, g, st))) return rc;
     }
     for (int l = 0; l < L; ++l) {      // ConvNeXtBlock.forward   convnext.py:40-56
-        e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev,
-                          h->blob + h->dw_w[l], h->blob + h->dw_b[l], 7, 3, nullptr, st);
+        e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev.p,
+                          h->blob.p + h->dw_w[l], h->blob.p + h->dw_b[l], 7, 3, nullptr, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
         e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, C, B, T, 0, h->stats, Ts, 1e-6f, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm stats launch failed: %s", hipGetErrorString(e));
@@ -3251,28 +2949,23 @@ int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stre
     for (int b = 0; b < B; ++b)
         if (lengths[b] < 0) return fail(h, DSD_EINVAL, "dsd_set_lengths: lengths[%d] = %d is negative", b, lengths[b]);
     HIP_OK(h, hipSetDevice(h->cfg.device));
-    if (h->lens_cap < B) {
-        if (h->lens_dev) (void)hipFree(h->lens_dev);
-        h->lens_dev = nullptr;
-        h->lens_cap = 0;
-        if (hipMalloc(&h->lens_dev, sizeof(int) * (size_t)B) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "hipMalloc of %d lengths failed", B);
-        h->lens_cap = B;
+    if ((size_t)B > h->lens_dev.cap) {
+        if (int rc = h->lens_dev.reserve(h, (size_t)B, "dsd_set_lengths")) return rc;
         destroy_graphs(h);      // cached graphs captured the old pointer
     }
     h->lens_host.assign(lengths, lengths + B);
     h->cg_T = -1;               // the valid-tile lists follow the lengths
     // stream-ordered behind earlier launches that still read the old values
-    HIP_OK(h, hipMemcpyAsync(h->lens_dev, h->lens_host.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_OK(h, hipMemcpyAsync(h->lens_dev.p, h->lens_host.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, (hipStream_t)stream));
     return DSD_OK;
 }
 
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
     if (!h || !out) return DSD_EINVAL;
-    MEL_HANDLE_REJECT(h, "dsd_get_stats");
+    if (int rc = reject_analysis_handle(h, "dsd_get_stats")) return rc;
     memset(out, 0, sizeof(*out));
     const int64_t C = h->c_user ? h->c_user : C_of(h), M = FM_of(h), L = L_of(h);
-    out->weight_bytes = (int64_t)h->blob_floats * 4;
+    out->weight_bytes = (int64_t)h->blob.cap * 4;
     out->workspace_bytes = (int64_t)h->arena_floats * 4;
     if (is_enc(h) || is_tok(h)) {        // per TOKEN per encoder pass (attention excluded: it depends on the sequence length)
         const int64_t H = h->cfg.hidden_size, ks = h->cfg.kernel_size, NL = h->cfg.num_layers;
@@ -3291,7 +2984,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         // the plan of the handle's last call (plan_denoise): segments, or the row-split pair / the two GEMMs per layer; around the
         // layers the edge kernel (skip projection, output projection + solver update, the next evaluation's input projection;
         // wn_edge.hip) or the three GEMMs of gemm.hip
-        const DenoisePlan pl = h->arena ? plan_denoise(h) : DenoisePlan();
+        const DenoisePlan pl = h->arena.p ? plan_denoise(h) : DenoisePlan();
         out->layer_launches = pl.segs.empty() ? 2 : 0;
         if (pl.segs.empty()) out->split_tiles = (int32_t)tiles_at(h, 32);
         for (const WnSeg& sg : pl.segs) {
@@ -3305,7 +2998,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         out->flops_per_frame_nfe = 2 * (M * C + L * (C * 2 * inner + ks * inner + inner * C) + C * M);
         out->bytes_per_frame_nfe = L * 12 * C + 8 * M;
         out->kernels_per_nfe = 1 + 4 * (int)L + 2;
-        if (h->arena && plan_denoise(h).bf16x3()) out->precision = DSD_PRECISION_BF16X3;
+        if (h->arena.p && plan_denoise(h).bf16x3()) out->precision = DSD_PRECISION_BF16X3;
     }
     out->graphs_cached = (int)h->graphs.size();
     return DSD_OK;
@@ -3313,7 +3006,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
 
 int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
     if (!h) return DSD_EINVAL;
-    MEL_HANDLE_REJECT(h, "dsd_kernel_timing");
+    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing")) return rc;
     h->timing = enable != 0;
     h->tclasses.clear();
     h->timing_evals = 0;
@@ -3326,7 +3019,7 @@ int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
 int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_classes, int32_t* n_classes,
                               double* empty_pair_ms) {
     if (!h || !out || !n_classes || max_classes < 1) return DSD_EINVAL;
-    MEL_HANDLE_REJECT(h, "dsd_kernel_timing_classes");
+    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing_classes")) return rc;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     int n = 0;
     // largest share of the evaluation first
@@ -3375,7 +3068,7 @@ int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_c
 
 int dsd_kernel_timing_read(dsd_handle* h, double* mean_ms, double* empty_pair_ms, int64_t* launches) {
     if (!h || !mean_ms || !empty_pair_ms || !launches) return DSD_EINVAL;
-    MEL_HANDLE_REJECT(h, "dsd_kernel_timing_read");
+    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing_read")) return rc;
     dsd_kernel_time top;
     int32_t n = 0;
     int rc = dsd_kernel_timing_classes(h, &top, 1, &n, empty_pair_ms);      // the class with the largest share of the pass
@@ -3386,2103 +3079,6 @@ int dsd_kernel_timing_read(dsd_handle* h, double* mean_ms, double* empty_pair_ms
     h->timing_evals = 0;
     h->ev_used = 0;
     h->cal_used = 0;
-    return DSD_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// Mel analysis (dsd_mel_*): STFT.get_mel, modules/nsf_hifigan/nvSTFT.py:50-87
-// ------------------------------------------------------------------------------------------------------------------------------
-namespace {
-
-int mel_check_config(const dsd_mel_config* c, const char* who) {
-    if (!c) return fail(nullptr, DSD_EINVAL, "%s: null config", who);
-    if (c->struct_size != (int32_t)sizeof(dsd_mel_config))
-        return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, c->struct_size, sizeof(dsd_mel_config));
-    if (c->sampling_rate < 1 || c->n_fft < 2 || c->n_fft > 16384 || c->win_size < 1 || c->win_size > c->n_fft ||
-        c->hop_size < 1 || c->num_mels < 1 || c->num_mels > 1024)
-        return fail(nullptr, DSD_EINVAL, "%s: need sampling_rate >= 1, 2 <= n_fft <= 16384, 1 <= win_size <= n_fft, hop_size >= 1 "
-                    "and 1 <= num_mels <= 1024", who);
-    if (!(c->fmin >= 0.0) || !(c->fmax > c->fmin) || !std::isfinite(c->fmax))
-        return fail(nullptr, DSD_EINVAL, "%s: need 0 <= fmin < fmax (got %g, %g)", who, c->fmin, c->fmax);
-    if (!(c->clip_val > 0.0) || !std::isfinite(c->clip_val)) return fail(nullptr, DSD_EINVAL, "%s: clip_val must be > 0", who);
-    return DSD_OK;
-}
-
-// librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) with its defaults (htk=False, norm="slaney", dtype=float32), restated
-// step by step in float64 as librosa computes it: Slaney scale (linear at 200/3 Hz per mel below 1000 Hz = 15 mel,
-// logarithmic above with step ln(6.4) / 27), np.linspace of the mel points, np.fft.rfftfreq bin centres, triangles stored
-// into the float32 array, then the area normalisation 2 / (f[i+2] - f[i]) multiplied in place (a float32 result).
-double slaney_hz_to_mel(double f) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-}
-double slaney_mel_to_hz(double m) {
-    const double f_sp = 200.0 / 3, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-    return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
-}
-// htk = true: librosa's HTK scale instead (mel = 2595 log10(1 + f / 700)), the same triangles and Slaney area norm
-double htk_hz_to_mel(double f) { return 2595.0 * log10(1.0 + f / 700.0); }
-double htk_mel_to_hz(double m) { return 700.0 * (pow(10.0, m / 2595.0) - 1.0); }
-void mel_filterbank_host(const dsd_mel_config& c, std::vector<float>& w, bool htk = false) {
-    const int M = c.num_mels, K = c.n_fft / 2 + 1, n = M + 2;
-    double (*to_mel)(double) = htk ? htk_hz_to_mel : slaney_hz_to_mel;
-    double (*to_hz)(double) = htk ? htk_mel_to_hz : slaney_mel_to_hz;
-    const double lo = to_mel(c.fmin), hi = to_mel(c.fmax), step = (hi - lo) / (double)(n - 1);
-    std::vector<double> mel_f(n), fft_f(K);
-    for (int i = 0; i < n; ++i) {
-        const double m = (double)i * step;      // np.linspace: arange * step + start, the end point set to stop
-        mel_f[i] = to_hz(i == n - 1 ? hi : m + lo);
-    }
-    const double val = 1.0 / ((double)c.n_fft * (1.0 / (double)c.sampling_rate));      // np.fft.rfftfreq(n_fft, 1 / sr)
-    for (int k = 0; k < K; ++k) fft_f[k] = (double)k * val;
-    w.assign((size_t)M * K, 0.f);
-    for (int i = 0; i < M; ++i) {
-        const double d0 = mel_f[i + 1] - mel_f[i], d1 = mel_f[i + 2] - mel_f[i + 1], enorm = 2.0 / (mel_f[i + 2] - mel_f[i]);
-        for (int k = 0; k < K; ++k) {
-            const double lower = -(mel_f[i] - fft_f[k]) / d0, upper = (mel_f[i + 2] - fft_f[k]) / d1;
-            const float tri = (float)std::max(0.0, std::min(lower, upper));
-            w[(size_t)i * K + k] = (float)((double)tri * enorm);
-        }
-    }
-}
-
-// The STFT geometry of one (keyshift, speed) (nvSTFT.py:52-66): np.round is round-half-even, as nearbyint
-struct MelGeom {
-    int N, W, H, off, padL, padR;
-    bool rescale;
-};
-bool mel_geometry(const dsd_mel_config& c, double keyshift, double speed, MelGeom& g) {
-    if (!std::isfinite(keyshift) || !std::isfinite(speed) || !(speed > 0.0)) return false;
-    const double factor = pow(2.0, keyshift / 12.0);
-    const double N = nearbyint(c.n_fft * factor), W = nearbyint(c.win_size * factor), H = nearbyint(c.hop_size * speed);
-    if (!(N >= 1 && N <= 32768 && W >= 1 && W <= N && H >= 1 && H <= (1 << 24))) return false;
-    g.N = (int)N;
-    g.W = (int)W;
-    g.H = (int)H;
-    g.off = (g.N - g.W) / 2;                               // torch.stft centres a shorter window in the frame
-    const int d = g.W - g.H;                               // Python floor division of d and d + 1 by 2
-    g.padL = d >= 0 ? d / 2 : -((-d + 1) / 2);
-    g.padR = d + 1 >= 0 ? (d + 1) / 2 : -((-(d + 1) + 1) / 2);
-    g.rescale = keyshift != 0.0;
-    return true;
-}
-// T of an item of L samples, or -1 where torch raises (reflect pad >= L, padded signal shorter than N')
-int64_t mel_frames(const MelGeom& g, int64_t L) {
-    if (L < 1 || g.padL >= L || g.padR >= L) return -1;
-    const int64_t Lp = L + g.padL + g.padR;
-    if (Lp < g.N) return -1;
-    return 1 + (Lp - g.N) / g.H;
-}
-
-// the packed non-zero runs of the filterbank w [num_mels][n_fft / 2 + 1] on the device
-int mel_state_build(MelState& mst, const dsd_mel_config* cfg, const std::vector<float>& w, const char* who) {
-    // the non-zero run of every filter (librosa's triangles are contiguous), packed
-    const int M = cfg->num_mels, K = cfg->n_fft / 2 + 1;
-    std::vector<int> first(M, -1), last(M, -2);
-    int k_lo = K, k_hi = -1;
-    for (int m = 0; m < M; ++m) {
-        for (int k = 0; k < K; ++k)
-            if (w[(size_t)m * K + k] != 0.f) {
-                if (first[m] < 0) first[m] = k;
-                last[m] = k;
-            }
-        if (first[m] >= 0) {
-            k_lo = std::min(k_lo, first[m]);
-            k_hi = std::max(k_hi, last[m]);
-        }
-    }
-    if (k_hi < 0) k_lo = 0;
-    std::vector<int> range(2 * M), woff(M);
-    std::vector<float> fw;
-    for (int m = 0; m < M; ++m) {
-        woff[m] = (int)fw.size();
-        if (first[m] < 0) {
-            range[2 * m] = range[2 * m + 1] = 0;
-            continue;
-        }
-        range[2 * m] = first[m] - k_lo;
-        range[2 * m + 1] = last[m] + 1 - k_lo;
-        for (int k = first[m]; k <= last[m]; ++k) fw.push_back(w[(size_t)m * K + k]);
-    }
-    fw.push_back(0.f);       // never empty
-    MelState* ms = &mst;
-    ms->cfg = *cfg;
-    ms->k_lo = k_lo;
-    ms->k_hi = k_hi;
-    ms->range_host = range;
-    if (hipMalloc(&ms->range, sizeof(int) * range.size()) != hipSuccess || hipMalloc(&ms->woff, sizeof(int) * M) != hipSuccess ||
-        hipMalloc(&ms->fw, sizeof(float) * fw.size()) != hipSuccess) {
-        return fail(nullptr, DSD_ENOMEM, "%s: hipMalloc of the filterbank failed", who);
-    }
-    if (hipMemcpy(ms->range, range.data(), sizeof(int) * range.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ms->woff, woff.data(), sizeof(int) * M, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ms->fw, fw.data(), sizeof(float) * fw.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        return fail(nullptr, DSD_EHIP, "%s: upload of the filterbank failed", who);
-    }
-    return DSD_OK;
-}
-
-void mel_state_free(MelState* m) {
-    if (!m) return;
-    for (auto& bs : m->bases) (void)hipFree(bs.dev);
-    for (void* p : {(void*)m->range, (void*)m->woff, (void*)m->fw, (void*)m->work, (void*)m->mags})
-        if (p) (void)hipFree(p);
-    delete m;
-}
-
-}  // namespace
-
-int dsd_mel_filterbank(const dsd_mel_config* cfg, float* out) {
-    int rc = mel_check_config(cfg, "dsd_mel_filterbank");
-    if (rc) return rc;
-    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_mel_filterbank: null output");
-    std::vector<float> w;
-    mel_filterbank_host(*cfg, w);
-    memcpy(out, w.data(), w.size() * sizeof(float));
-    return DSD_OK;
-}
-
-int64_t dsd_mel_num_frames(const dsd_mel_config* cfg, int64_t n_samples, double keyshift, double speed) {
-    if (mel_check_config(cfg, "dsd_mel_num_frames")) return DSD_EINVAL;
-    MelGeom g;
-    if (!mel_geometry(*cfg, keyshift, speed, g)) return fail(nullptr, DSD_EINVAL, "dsd_mel_num_frames: bad keyshift / speed");
-    const int64_t T = mel_frames(g, n_samples);
-    if (T < 1) return fail(nullptr, DSD_EINVAL, "dsd_mel_num_frames: %lld samples are too short (torch.stft / reflect pad raise)",
-                           (long long)n_samples);
-    return T;
-}
-
-int dsd_mel_create(const dsd_mel_config* cfg, dsd_handle** out) {
-    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_mel_create: null argument");
-    int rc = mel_check_config(cfg, "dsd_mel_create");
-    if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_mel_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_mel_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_mel_create: hipSetDevice failed");
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_MEL_ANALYSIS;
-    h->cfg.in_dims = cfg->num_mels;
-    h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
-    std::vector<float> w;
-    mel_filterbank_host(*cfg, w);
-    h->mel = new MelState();
-    rc = mel_state_build(*h->mel, cfg, w, "dsd_mel_create");
-    if (rc) {
-        dsd_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return DSD_OK;
-}
-
-namespace {
-
-// the analysis of dsd_mel_analyze after its argument checks, for one STFT geometry (RMVPE's front end calls it too)
-int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
-            const int64_t* lengths, float* mel_out, int64_t stride_b, int64_t stride_m, int64_t stride_t, void* stream,
-            const char* who) {
-    const dsd_mel_config& c = ms.cfg;
-    // work list: (item, 64-frame tile) entries over the frames each item has
-    std::vector<int>& work = ms.work_host;
-    work.clear();
-    int64_t G = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t L = lengths ? lengths[b] : n_samples;
-        if (L < 1 || L > n_samples) return fail(h, DSD_EINVAL, "%s: lengths[%d] = %lld outside [1, %lld]", who, b,
-                                                (long long)L, (long long)n_samples);
-        const int64_t T = mel_frames(g, L);
-        if (T < 1)
-            return fail(h, DSD_EINVAL, "%s: item %d (%lld samples) is too short for N' = %d, W' = %d, H' = %d "
-                        "(torch.stft / reflect pad raise)", who, b, (long long)L, g.N, g.W, g.H);
-        for (int64_t t0 = 0; t0 < T; t0 += 64) {
-            const int e[5] = {b, (int)t0, (int)L, (int)T, (int)(G + t0)};
-            work.insert(work.end(), e, e + 5);
-        }
-        G += T;
-        if (G > ((int64_t)1 << 30)) return fail(h, DSD_EINVAL, "%s: too many frames in one call", who);
-    }
-    const int n_entries = (int)(work.size() / 5);
-    // bins the filterbank reads that this N' has: nvSTFT.py:76-80 zero-pads the bins past N'/2
-    const int k_hi = std::min(ms.k_hi, g.N / 2), nb = std::max(0, k_hi - ms.k_lo + 1);
-    const int row_tiles = (2 * nb + 63) / 64, Kpad = (g.W + 31) / 32 * 32;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    float* basis = nullptr;
-    if (nb > 0) {
-        for (size_t i = 0; i < ms.bases.size(); ++i)
-            if (ms.bases[i].N == g.N && ms.bases[i].W == g.W) {
-                std::rotate(ms.bases.begin() + i, ms.bases.begin() + i + 1, ms.bases.end());      // most recent last
-                basis = ms.bases.back().dev;
-                break;
-            }
-        if (!basis) {
-            if (ms.bases.size() == 4) {       // continuous keyshift draws: keep the four most recent sizes
-                (void)hipFree(ms.bases.front().dev);
-                ms.bases.erase(ms.bases.begin());
-            }
-            const size_t n = (size_t)row_tiles * 64 * Kpad;
-            if (hipMalloc(&basis, n * sizeof(float)) != hipSuccess)
-                return fail(h, DSD_ENOMEM, "%s: hipMalloc of the %d x %d DFT basis failed", who, row_tiles * 64, Kpad);
-            MelBasis mb;
-            mb.N = g.N;
-            mb.W = g.W;
-            mb.dev = basis;
-            ms.bases.push_back(mb);
-            hipError_t e = launch_mel_basis(basis, row_tiles * 64, Kpad, ms.k_lo, nb, g.N, g.W, g.off, st);
-            if (e != hipSuccess) return fail(h, DSD_EHIP, "mel basis launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    if (work.size() > ms.work_cap) {
-        if (ms.work) (void)hipFree(ms.work);
-        ms.work = nullptr;
-        ms.work_cap = 0;
-        if (hipMalloc(&ms.work, sizeof(int) * work.size()) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "%s: hipMalloc of the work list failed", who);
-        ms.work_cap = work.size();
-    }
-    HIP_OK(h, hipMemcpyAsync(ms.work, work.data(), sizeof(int) * work.size(), hipMemcpyHostToDevice, st));
-    const size_t mags_n = std::max<size_t>(1, (size_t)nb * (size_t)G);
-    if (mags_n > ms.mags_cap) {
-        if (ms.mags) (void)hipFree(ms.mags);
-        ms.mags = nullptr;
-        ms.mags_cap = 0;
-        if (hipMalloc(&ms.mags, sizeof(float) * mags_n) != hipSuccess)
-            return fail(h, DSD_ENOMEM, "%s: hipMalloc of %zu magnitudes failed", who, mags_n);
-        ms.mags_cap = mags_n;
-    }
-    if (nb > 0) {
-        MelDftP p;
-        p.wav = wav;
-        p.wav_bstride = (long)wav_stride_b;
-        p.work = ms.work;
-        p.basis = basis;
-        p.Kpad = Kpad;
-        p.W = g.W;
-        p.H = g.H;
-        p.off = g.off;
-        p.padL = g.padL;
-        p.nb = nb;
-        p.rescale = g.rescale ? 1 : 0;
-        p.win_size = (float)c.win_size;
-        p.win_new = (float)g.W;
-        p.mags = ms.mags;
-        p.G = (long)G;
-        hipError_t e = launch_mel_dft(p, n_entries, row_tiles, st);
-        if (e != hipSuccess) return fail(h, DSD_EHIP, "mel DFT launch failed: %s", hipGetErrorString(e));
-    }
-    MelProjP q;
-    q.work = ms.work;
-    q.mags = ms.mags;
-    q.G = (long)G;
-    q.nb = nb;
-    q.M = c.num_mels;
-    q.range = ms.range;
-    q.woff = ms.woff;
-    q.fw = ms.fw;
-    q.clip = (float)c.clip_val;
-    q.out = mel_out;
-    q.o_sb = (long)stride_b;
-    q.o_sm = (long)stride_m;
-    q.o_st = (long)stride_t;
-    hipError_t e = launch_mel_project(q, n_entries, st);
-    if (e != hipSuccess) return fail(h, DSD_EHIP, "mel projection launch failed: %s", hipGetErrorString(e));
-    return DSD_OK;
-}
-
-}  // namespace
-
-int dsd_mel_analyze(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
-                    const int64_t* lengths, double keyshift, double speed, float* mel_out, int64_t stride_b,
-                    int64_t stride_m, int64_t stride_t, void* stream) {
-    if (!h || !wav || !mel_out) return fail(h, DSD_EINVAL, "dsd_mel_analyze: null argument");
-    if (!is_mel(h)) return fail(h, DSD_ESTATE, "dsd_mel_analyze: this handle is not a mel analysis handle (dsd_mel_create)");
-    MelState& ms = *h->mel;
-    const dsd_mel_config& c = ms.cfg;
-    if (B < 1 || n_samples < 1) return fail(h, DSD_EINVAL, "dsd_mel_analyze: B and n_samples must be positive (%d, %lld)", B,
-                                            (long long)n_samples);
-    if (n_samples > ((int64_t)1 << 31) - 1 || (B > 1 && wav_stride_b < n_samples))
-        return fail(h, DSD_EINVAL, "dsd_mel_analyze: n_samples must be < 2^31 and wav_stride_b >= n_samples");
-    MelGeom g;
-    if (!mel_geometry(c, keyshift, speed, g))
-        return fail(h, DSD_EINVAL, "dsd_mel_analyze: keyshift %g / speed %g give no valid STFT size", keyshift, speed);
-    return mel_run(h, ms, g, wav, B, n_samples, wav_stride_b, lengths, mel_out, stride_b, stride_m, stride_t, stream,
-                   "dsd_mel_analyze");
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// RMVPE pitch extraction (dsd_rmvpe_*): modules/pe/rmvpe/ (inference.py, model.py, deepunet.py, seq.py, spec.py, utils.py)
-// ------------------------------------------------------------------------------------------------------------------------------
-extern "C++" {     // the helpers return C++ types
-namespace {
-
-constexpr int RM_MELS = 128, RM_CLASSES = 360, RM_HOP = 160, RM_NFFT = 1024;
-
-dsd_mel_config rmvpe_mel_config(int device) {
-    dsd_mel_config c;
-    memset(&c, 0, sizeof(c));
-    c.struct_size = sizeof(dsd_mel_config);
-    c.sampling_rate = 16000;
-    c.n_fft = RM_NFFT;
-    c.win_size = RM_NFFT;
-    c.hop_size = RM_HOP;
-    c.num_mels = RM_MELS;
-    c.fmin = 30.0;
-    c.fmax = 8000.0;
-    c.clip_val = 1e-5;
-    c.device = device;
-    return c;
-}
-
-// torch.stft(center=True): reflect pads n_fft / 2 on both sides, T = 1 + L // 160
-MelGeom rmvpe_geometry() {
-    MelGeom g;
-    g.N = g.W = RM_NFFT;
-    g.H = RM_HOP;
-    g.off = 0;
-    g.padL = g.padR = RM_NFFT / 2;
-    g.rescale = false;
-    return g;
-}
-
-int64_t rmvpe_resampled_length(int64_t L, int sr) {
-    if (sr == 16000) return L;
-    const int g = std::gcd(sr, 16000), orig = sr / g, nw = 16000 / g;
-    return ((int64_t)nw * L + orig - 1) / orig;       // ceil(new L / orig)
-}
-
-// ConvBlockRes(cin, cout) under `prefix`: conv.0 / conv.3 (3x3, no bias), conv.1 / conv.4 (BatchNorm2d), shortcut when cin != cout
-void rmvpe_block_names(std::vector<std::pair<std::string, std::vector<int64_t>>>& e, const std::string& prefix, int cin, int cout) {
-    const char* bn[4] = {"weight", "bias", "running_mean", "running_var"};
-    e.push_back({prefix + ".conv.0.weight", {cout, cin, 3, 3}});
-    for (auto n : bn) e.push_back({prefix + ".conv.1." + n, {cout}});
-    e.push_back({prefix + ".conv.3.weight", {cout, cout, 3, 3}});
-    for (auto n : bn) e.push_back({prefix + ".conv.4." + n, {cout}});
-    if (cin != cout) {
-        e.push_back({prefix + ".shortcut.weight", {cout, cin, 1, 1}});
-        e.push_back({prefix + ".shortcut.bias", {cout}});
-    }
-}
-
-std::vector<std::pair<std::string, std::vector<int64_t>>> rmvpe_expected(const dsd_rmvpe_config& c) {
-    std::vector<std::pair<std::string, std::vector<int64_t>>> e;
-    const char* bn[4] = {"weight", "bias", "running_mean", "running_var"};
-    const int E = c.en_de_layers, C = c.en_out_channels, nb = c.n_blocks;
-    for (auto n : bn) e.push_back({std::string("unet.encoder.bn.") + n, {1}});
-    for (int l = 0; l < E; ++l) {
-        const int cin = l == 0 ? 1 : C << (l - 1), cout = C << l;
-        for (int k = 0; k < nb; ++k)
-            rmvpe_block_names(e, "unet.encoder.layers." + std::to_string(l) + ".conv." + std::to_string(k), k ? cout : cin, cout);
-    }
-    for (int i = 0; i < c.inter_layers; ++i) {
-        const int cin = i == 0 ? C << (E - 1) : C << E, cout = C << E;
-        for (int k = 0; k < nb; ++k)
-            rmvpe_block_names(e, "unet.intermediate.layers." + std::to_string(i) + ".conv." + std::to_string(k), k ? cout : cin, cout);
-    }
-    for (int i = 0; i < E; ++i) {
-        const int cin = C << (E - i), cout = cin / 2;
-        const std::string p = "unet.decoder.layers." + std::to_string(i);
-        e.push_back({p + ".conv1.0.weight", {cin, cout, 3, 3}});
-        for (auto n : bn) e.push_back({p + ".conv1.1." + n, {cout}});
-        for (int k = 0; k < nb; ++k) rmvpe_block_names(e, p + ".conv2." + std::to_string(k), k ? cout : 2 * cout, cout);
-    }
-    e.push_back({"cnn.weight", {3, C, 3, 3}});
-    e.push_back({"cnn.bias", {3}});
-    if (c.n_gru) {
-        for (std::string sfx : {"", "_reverse"}) {
-            e.push_back({"fc.0.gru.weight_ih_l0" + sfx, {768, 3 * RM_MELS}});
-            e.push_back({"fc.0.gru.weight_hh_l0" + sfx, {768, 256}});
-            e.push_back({"fc.0.gru.bias_ih_l0" + sfx, {768}});
-            e.push_back({"fc.0.gru.bias_hh_l0" + sfx, {768}});
-        }
-        e.push_back({"fc.1.weight", {RM_CLASSES, 512}});
-        e.push_back({"fc.1.bias", {RM_CLASSES}});
-    } else {
-        e.push_back({"fc.0.weight", {RM_CLASSES, 3 * RM_MELS}});
-        e.push_back({"fc.0.bias", {RM_CLASSES}});
-    }
-    return e;
-}
-
-bool ends_with(const std::string& s, const char* suffix) {
-    const size_t n = strlen(suffix);
-    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
-}
-
-int rmvpe_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim,
-                      int32_t on_device) {
-    if (!name) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    const std::string n(name);
-    // strict=False in the reference's RMVPE: TimbreFilter is never called in forward; BatchNorm's step counter carries no value
-    if (n.rfind("unet.tf.", 0) == 0 || ends_with(n, ".num_batches_tracked")) return DSD_OK;
-    if (!data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    RmvpeState& r = *h->pe;
-    std::vector<int64_t> shp(shape, shape + ndim);
-    const std::vector<int64_t>* want = nullptr;
-    for (auto& e : r.expected)
-        if (e.first == n) want = &e.second;
-    if (!want) return fail(h, DSD_ENOTFOUND, "unexpected key in state_dict: %s", name);
-    if (*want != shp) {
-        std::string a, b;
-        for (auto v : *want) a += std::to_string(v) + ",";
-        for (auto v : shp) b += std::to_string(v) + ",";
-        return fail(h, DSD_EINVAL, "size mismatch for %s: expected [%s] got [%s]", name, a.c_str(), b.c_str());
-    }
-    size_t numel = 1;
-    for (auto v : shp) numel *= (size_t)v;
-    HostTensor t;
-    t.shape = shp;
-    t.data.resize(numel);
-    if (on_device) {
-        HIP_OK(h, hipSetDevice(h->cfg.device));
-        HIP_OK(h, hipMemcpy(t.data.data(), data, numel * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(t.data.data(), data, numel * sizeof(float));
-    }
-    h->raw[n] = std::move(t);
-    r.finalized = false;
-    return DSD_OK;
-}
-
-// eval-mode BatchNorm2d (eps 1e-5) as scale / shift, in double
-void rmvpe_bn(const dsd_handle* h, const std::string& p, int C, std::vector<double>& sc, std::vector<double>& sh) {
-    const auto &g = h->raw.at(p + ".weight").data, &b = h->raw.at(p + ".bias").data;
-    const auto &m = h->raw.at(p + ".running_mean").data, &v = h->raw.at(p + ".running_var").data;
-    sc.resize(C);
-    sh.resize(C);
-    for (int c = 0; c < C; ++c) {
-        sc[c] = (double)g[c] / sqrt((double)v[c] + 1e-5);
-        sh[c] = (double)b[c] - (double)m[c] * sc[c];
-    }
-}
-
-// a 3x3 conv [cout][cin][3][3] (transposed: [cin][cout][3][3]) with the BN scale folded in -> [tap][cin][cout_pad]
-RmConvW rmvpe_pack_conv(std::vector<float>& blob, const std::vector<float>& w, int cin, int cout, bool transposed,
-                        const std::vector<double>& sc, const std::vector<double>& sh) {
-    RmConvW c;
-    c.cin = cin;
-    c.cout = cout;
-    c.cout_pad = (cout + 7) / 8 * 8;
-    c.w = blob.size();
-    blob.resize(blob.size() + (size_t)9 * cin * c.cout_pad, 0.f);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int tap = 0; tap < 9; ++tap) {
-                const float v = transposed ? w[((size_t)ci * cout + co) * 9 + tap] : w[((size_t)co * cin + ci) * 9 + tap];
-                blob[c.w + ((size_t)tap * cin + ci) * c.cout_pad + co] = (float)((double)v * sc[co]);
-            }
-    c.shift = blob.size();
-    blob.resize(blob.size() + c.cout_pad, 0.f);
-    for (int co = 0; co < cout; ++co) blob[c.shift + co] = (float)sh[co];
-    return c;
-}
-
-RmBlockW rmvpe_pack_block(const dsd_handle* h, std::vector<float>& blob, const std::string& p, int cin, int cout) {
-    std::vector<double> sc, sh;
-    RmBlockW b;
-    rmvpe_bn(h, p + ".conv.1", cout, sc, sh);
-    b.c1 = rmvpe_pack_conv(blob, h->raw.at(p + ".conv.0.weight").data, cin, cout, false, sc, sh);
-    rmvpe_bn(h, p + ".conv.4", cout, sc, sh);
-    b.c2 = rmvpe_pack_conv(blob, h->raw.at(p + ".conv.3.weight").data, cout, cout, false, sc, sh);
-    if (cin != cout) {
-        const auto &ws = h->raw.at(p + ".shortcut.weight").data, &bs = h->raw.at(p + ".shortcut.bias").data;
-        const int cp = b.c2.cout_pad;
-        b.c2.sc = true;
-        b.c2.ws = blob.size();
-        blob.resize(blob.size() + (size_t)cin * cp, 0.f);
-        for (int co = 0; co < cout; ++co)
-            for (int ci = 0; ci < cin; ++ci) blob[b.c2.ws + (size_t)ci * cp + co] = ws[(size_t)co * cin + ci];
-        b.c2.bs = blob.size();
-        blob.resize(blob.size() + cp, 0.f);
-        for (int co = 0; co < cout; ++co) blob[b.c2.bs + co] = bs[co];
-    }
-    return b;
-}
-
-// W [N][K] with K indexed c * 128 + f (transpose(1, 2).flatten(-2) of the head's [3][T][128]) -> rows f * 3 + c, the
-// head's [frame][bin][channel] order; columns n0 .. n0 + N of a [K][ld] block
-void rmvpe_pack_fc(std::vector<float>& blob, size_t at, const std::vector<float>& w, int N, int K, int ld, int n0, bool head_order) {
-    for (int n = 0; n < N; ++n)
-        for (int k = 0; k < K; ++k) {
-            const int kk = head_order ? (k % RM_MELS) * 3 + k / RM_MELS : k;
-            blob[at + (size_t)kk * ld + n0 + n] = w[(size_t)n * K + k];
-        }
-}
-
-int rmvpe_finalize(dsd_handle* h) {
-    RmvpeState& r = *h->pe;
-    const dsd_rmvpe_config& c = r.cfg;
-    std::string missing;
-    for (auto& e : r.expected)
-        if (!h->raw.count(e.first)) missing += (missing.empty() ? "" : ", ") + e.first;
-    if (!missing.empty()) return fail(h, DSD_ESTATE, "missing keys in state_dict: %s", missing.c_str());
-    const int E = c.en_de_layers, C = c.en_out_channels, nb = c.n_blocks;
-    std::vector<float> blob;
-    std::vector<double> sc, sh;
-    rmvpe_bn(h, "unet.encoder.bn", 1, sc, sh);
-    r.bn0_scale = (float)sc[0];
-    r.bn0_shift = (float)sh[0];
-    r.enc.assign(E, {});
-    for (int l = 0; l < E; ++l) {
-        const int cin = l == 0 ? 1 : C << (l - 1), cout = C << l;
-        for (int k = 0; k < nb; ++k)
-            r.enc[l].push_back(rmvpe_pack_block(h, blob, "unet.encoder.layers." + std::to_string(l) + ".conv." + std::to_string(k),
-                                                k ? cout : cin, cout));
-    }
-    r.inter.assign(c.inter_layers, {});
-    for (int i = 0; i < c.inter_layers; ++i) {
-        const int cin = i == 0 ? C << (E - 1) : C << E, cout = C << E;
-        for (int k = 0; k < nb; ++k)
-            r.inter[i].push_back(rmvpe_pack_block(h, blob, "unet.intermediate.layers." + std::to_string(i) + ".conv." +
-                                                  std::to_string(k), k ? cout : cin, cout));
-    }
-    r.dec.assign(E, {});
-    r.up.clear();
-    for (int i = 0; i < E; ++i) {
-        const int cin = C << (E - i), cout = cin / 2;
-        const std::string p = "unet.decoder.layers." + std::to_string(i);
-        rmvpe_bn(h, p + ".conv1.1", cout, sc, sh);
-        r.up.push_back(rmvpe_pack_conv(blob, h->raw.at(p + ".conv1.0.weight").data, cin, cout, true, sc, sh));
-        for (int k = 0; k < nb; ++k)
-            r.dec[i].push_back(rmvpe_pack_block(h, blob, p + ".conv2." + std::to_string(k), k ? cout : 2 * cout, cout));
-    }
-    {
-        std::vector<double> one(3, 1.0), bias(3);
-        for (int k = 0; k < 3; ++k) bias[k] = h->raw.at("cnn.bias").data[k];
-        r.head = rmvpe_pack_conv(blob, h->raw.at("cnn.weight").data, C, 3, false, one, bias);
-    }
-    const int KH = 3 * RM_MELS;
-    if (c.n_gru) {
-        r.wih = blob.size();
-        blob.resize(blob.size() + (size_t)KH * 1536, 0.f);
-        r.bih = blob.size();
-        blob.resize(blob.size() + 1536, 0.f);
-        r.whh = blob.size();
-        blob.resize(blob.size() + (size_t)2 * 256 * 768, 0.f);
-        r.bhh = blob.size();
-        blob.resize(blob.size() + 2 * 768, 0.f);
-        for (int d = 0; d < 2; ++d) {
-            const std::string sfx = d ? "_reverse" : "";
-            rmvpe_pack_fc(blob, r.wih, h->raw.at("fc.0.gru.weight_ih_l0" + sfx).data, 768, KH, 1536, 768 * d, true);
-            const auto& bi = h->raw.at("fc.0.gru.bias_ih_l0" + sfx).data;
-            const auto& bh = h->raw.at("fc.0.gru.bias_hh_l0" + sfx).data;
-            const auto& wh = h->raw.at("fc.0.gru.weight_hh_l0" + sfx).data;
-            for (int n = 0; n < 768; ++n) {
-                blob[r.bih + 768 * d + n] = bi[n];
-                blob[r.bhh + 768 * d + n] = bh[n];
-                for (int k = 0; k < 256; ++k) blob[r.whh + ((size_t)d * 256 + k) * 768 + n] = wh[(size_t)n * 256 + k];
-            }
-        }
-        r.fcw = blob.size();
-        blob.resize(blob.size() + (size_t)512 * RM_CLASSES, 0.f);
-        rmvpe_pack_fc(blob, r.fcw, h->raw.at("fc.1.weight").data, RM_CLASSES, 512, RM_CLASSES, 0, false);
-        r.fcb = blob.size();
-        blob.insert(blob.end(), h->raw.at("fc.1.bias").data.begin(), h->raw.at("fc.1.bias").data.end());
-    } else {
-        r.fcw = blob.size();
-        blob.resize(blob.size() + (size_t)KH * RM_CLASSES, 0.f);
-        rmvpe_pack_fc(blob, r.fcw, h->raw.at("fc.0.weight").data, RM_CLASSES, KH, RM_CLASSES, 0, true);
-        r.fcb = blob.size();
-        blob.insert(blob.end(), h->raw.at("fc.0.bias").data.begin(), h->raw.at("fc.0.bias").data.end());
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    if (r.blob) (void)hipFree(r.blob);
-    r.blob = nullptr;
-    if (hipMalloc(&r.blob, blob.size() * sizeof(float)) != hipSuccess)
-        return fail(h, DSD_ENOMEM, "hipMalloc(%zu bytes of packed RMVPE weights) failed", blob.size() * 4);
-    HIP_OK(h, hipMemcpy(r.blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    r.finalized = true;
-    return DSD_OK;
-}
-
-int rmvpe_check(dsd_handle* h, const char* who) {
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
-    if (!h->pe->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
-    return DSD_OK;
-}
-
-// grow-only device blocks of the handle
-template <typename T>
-int rmvpe_reserve(dsd_handle* h, T*& p, size_t& cap, size_t n, const char* who) {
-    if (n <= cap) return DSD_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return fail(h, DSD_ENOMEM, "%s: hipMalloc of %zu bytes failed", who, n * sizeof(T));
-    cap = n;
-    return DSD_OK;
-}
-
-#define RM_LAUNCH(expr, what)                                                                            \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail(h, DSD_EHIP, "%s launch failed: %s", what, hipGetErrorString(e_)); \
-    } while (0)
-
-// E2E0.forward over each item's Tp_b = 32 ceil(T_b / 32) frames of the log-mel (element (b, m, t) at mel + b sb + m sm + t st),
-// then decode.  f0 / hidden_out may be NULL.  `extra` floats at the end of the workspace are left to the caller (front end).
-int rmvpe_run(dsd_handle* h, const float* mel, int64_t sb, int64_t sm, int64_t st_, int B, const std::vector<int>& T,
-              float thred, float* f0, int64_t f_sb, float* hidden_out, int64_t o_sb, int64_t o_st, hipStream_t st,
-              const char* who) {
-    RmvpeState& r = *h->pe;
-    const dsd_rmvpe_config& c = r.cfg;
-    const int E = c.en_de_layers, C = c.en_out_channels;
-    std::vector<int> Tp(B);
-    int Tpmax = 0, Tmax = 0;
-    for (int b = 0; b < B; ++b) {
-        Tp[b] = (T[b] + 31) / 32 * 32;
-        Tpmax = std::max(Tpmax, Tp[b]);
-        Tmax = std::max(Tmax, T[b]);
-    }
-    // workspace: the prepared input, one skip tensor per encoder level, three rotating tensors, the sigmoid output
-    auto level_size = [&](int l, int ch) { return (size_t)B * (size_t)(Tpmax >> l) * (size_t)(RM_MELS >> l) * (size_t)ch; };
-    size_t S = (size_t)B * Tpmax * 1536;
-    for (int l = 0; l <= E; ++l) S = std::max(S, level_size(l, C << l));
-    if (S * 4 >= ((size_t)1 << 31)) return fail(h, DSD_EINVAL, "%s: batch too large for one call (%zu floats per tensor)", who, S);
-    std::vector<size_t> skip_off(E);
-    size_t n = level_size(0, 1);
-    for (int l = 0; l < E; ++l) {
-        skip_off[l] = n;
-        n += level_size(l, C << l);
-    }
-    const size_t scr_off = n;
-    n += 3 * S;
-    const size_t hid_off = n;
-    n += (size_t)B * Tpmax * RM_CLASSES;
-    int rc = rmvpe_reserve(h, r.ws, r.ws_cap, n, who);
-    if (rc) return rc;
-    float* ws = r.ws;
-    // per-item counts and work lists: conv (quads) and tconv (positions) per level, linear (frames)
-    std::vector<int>& iw = r.iw_host;       // kept on the handle: the upload is asynchronous
-    iw.assign(2 * B, 0);
-    for (int b = 0; b < B; ++b) {
-        iw[b] = T[b];
-        iw[B + b] = Tp[b];
-    }
-    std::vector<size_t> conv_wl(E + 1), conv_n(E + 1), tc_wl(E + 1), tc_n(E + 1);
-    for (int l = 0; l <= E; ++l) {
-        const int F = RM_MELS >> l;
-        conv_wl[l] = iw.size();
-        for (int b = 0; b < B; ++b) {
-            const int Tl = Tp[b] >> l, nq = ((Tl + 1) / 2) * (F / 2);
-            for (int q0 = 0; q0 < nq; q0 += 256) iw.insert(iw.end(), {b, q0, Tl});
-        }
-        conv_n[l] = (iw.size() - conv_wl[l]) / 3;
-        tc_wl[l] = iw.size();
-        for (int b = 0; b < B; ++b) {
-            const int Tl = Tp[b] >> l, np_ = Tl * F;
-            for (int q0 = 0; q0 < np_; q0 += 256) iw.insert(iw.end(), {b, q0, Tl});
-        }
-        tc_n[l] = (iw.size() - tc_wl[l]) / 3;
-    }
-    const size_t lin_wl = iw.size();
-    for (int b = 0; b < B; ++b)
-        for (int t0 = 0; t0 < Tp[b]; t0 += 256) iw.insert(iw.end(), {b, t0, Tp[b]});
-    const size_t lin_n = (iw.size() - lin_wl) / 3;
-    if ((rc = rmvpe_reserve(h, r.iws, r.iws_cap, iw.size(), who))) return rc;
-    HIP_OK(h, hipMemcpyAsync(r.iws, iw.data(), iw.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    const int *dT = r.iws, *dTp = r.iws + B;
-    const float* wb = r.blob;
-
-    RmPrepP pp;
-    pp.mel = mel;
-    pp.sb = (long)sb;
-    pp.sm = (long)sm;
-    pp.st = (long)st_;
-    pp.T = dT;
-    pp.Tp = dTp;
-    pp.scale = r.bn0_scale;
-    pp.shift = r.bn0_shift;
-    pp.x = ws;
-    pp.Tal = Tpmax;
-    RM_LAUNCH(launch_rm_prep(pp, B, Tpmax, st), "rmvpe prep");
-
-    float* scr[3] = {ws + scr_off, ws + scr_off + S, ws + scr_off + 2 * S};
-    auto other = [&](const float* a, const float* b, const float* c = nullptr) -> float* {     // a scratch tensor not a, b, c
-        for (float* p : scr)
-            if (p != a && p != b && p != c) return p;
-        return nullptr;
-    };
-    auto conv = [&](const RmConvW& cw, int l, const float* x0, int c0, const float* x1, int c1, const float* r0, int rc0,
-                    const float* r1, int rc1, int res_mode, bool relu, float* y, float* pool) -> int {
-        RmConvP p;
-        p.x0 = x0;
-        p.x1 = x1;
-        p.c0 = c0;
-        p.c1 = c1;
-        p.r0 = r0;
-        p.r1 = r1;
-        p.rc0 = rc0;
-        p.rc1 = rc1;
-        p.res_mode = res_mode;
-        p.w = wb + cw.w;
-        p.shift = wb + cw.shift;
-        p.ws = cw.sc ? wb + cw.ws : nullptr;
-        p.bs = cw.sc ? wb + cw.bs : nullptr;
-        p.cout = cw.cout;
-        p.cout_pad = cw.cout_pad;
-        p.relu = relu ? 1 : 0;
-        p.F = RM_MELS >> l;
-        p.Tal = Tpmax >> l;
-        p.y = y;
-        p.pool = pool;
-        p.work = r.iws + conv_wl[l];
-        RM_LAUNCH(launch_rm_conv3(p, (int)conv_n[l], st), "rmvpe conv");
-        return DSD_OK;
-    };
-    // ConvBlockRes on x (x0 | x1) at level l -> y; the last block of an encoder layer also writes the pooled tensor
-    auto block = [&](const RmBlockW& bw, int l, const float* x0, int c0, const float* x1, int c1, float* y, float* pool) -> int {
-        float* h1 = other(x0, y, pool);      // x1 is a skip tensor, never scratch
-        int rc2 = conv(bw.c1, l, x0, c0, x1, c1, nullptr, 0, nullptr, 0, 0, true, h1, nullptr);
-        if (rc2) return rc2;
-        return conv(bw.c2, l, h1, bw.c2.cout, nullptr, 0, x0, c0, x1, c1, bw.c2.sc ? 2 : 1, true, y, pool);
-    };
-    const float* cur = ws;
-    int cc = 1;
-    for (int l = 0; l < E; ++l) {
-        const int nbk = (int)r.enc[l].size();
-        for (int k = 0; k < nbk; ++k) {
-            const bool last = k == nbk - 1;
-            float* y = last ? ws + skip_off[l] : other(cur, nullptr);
-            float* pool = last ? other(cur, nullptr) : nullptr;
-            if ((rc = block(r.enc[l][k], l, cur, cc, nullptr, 0, y, pool))) return rc;
-            cur = last ? pool : y;
-            cc = C << l;
-        }
-    }
-    for (auto& layer : r.inter)
-        for (auto& bw : layer) {
-            float* y = other(cur, nullptr);
-            if ((rc = block(bw, E, cur, cc, nullptr, 0, y, nullptr))) return rc;
-            cur = y;
-            cc = bw.c2.cout;
-        }
-    for (int i = 0; i < E; ++i) {
-        const int lin = E - i, lo = lin - 1;
-        const RmConvW& uw = r.up[i];
-        float* u = other(cur, nullptr);
-        RmConvP p;
-        memset(&p, 0, sizeof(p));
-        p.x0 = cur;
-        p.c0 = cc;
-        p.w = wb + uw.w;
-        p.shift = wb + uw.shift;
-        p.cout = uw.cout;
-        p.cout_pad = uw.cout_pad;
-        p.relu = 1;
-        p.F = RM_MELS >> lin;
-        p.Tal = Tpmax >> lin;
-        p.y = u;
-        p.work = r.iws + tc_wl[lin];
-        RM_LAUNCH(launch_rm_tconv(p, (int)tc_n[lin], st), "rmvpe tconv");
-        const float* x0 = u;
-        const float* x1 = ws + skip_off[lo];
-        int c0 = uw.cout, c1 = uw.cout;
-        for (auto& bw : r.dec[i]) {
-            float* y = other(x0, nullptr);
-            if ((rc = block(bw, lo, x0, c0, x1, c1, y, nullptr))) return rc;
-            x0 = y;
-            x1 = nullptr;
-            c0 = bw.c2.cout;
-            c1 = 0;
-        }
-        cur = x0;
-        cc = c0;
-    }
-    float* hd = other(cur, nullptr);
-    if ((rc = conv(r.head, 0, cur, cc, nullptr, 0, nullptr, 0, nullptr, 0, 0, false, hd, nullptr))) return rc;
-    float* hid = ws + hid_off;
-    RmLinearP lp;
-    lp.Tal = Tpmax;
-    lp.work = r.iws + lin_wl;
-    if (c.n_gru) {
-        float* gi = other(hd, nullptr);
-        lp.x = hd;
-        lp.w = wb + r.wih;
-        lp.bias = wb + r.bih;
-        lp.K = 3 * RM_MELS;
-        lp.N = 1536;
-        lp.act = 0;
-        lp.y = gi;
-        RM_LAUNCH(launch_rm_linear(lp, (int)lin_n, st), "rmvpe gru input");
-        float* gy = other(hd, gi);
-        RmGruP gp;
-        gp.gi = gi;
-        gp.whh = wb + r.whh;
-        gp.bhh = wb + r.bhh;
-        gp.Tp = dTp;
-        gp.Tal = Tpmax;
-        gp.y = gy;
-        RM_LAUNCH(launch_rm_gru(gp, B, st), "rmvpe gru");
-        lp.x = gy;
-        lp.K = 512;
-    } else {
-        lp.x = hd;
-        lp.K = 3 * RM_MELS;
-    }
-    lp.w = wb + r.fcw;
-    lp.bias = wb + r.fcb;
-    lp.N = RM_CLASSES;
-    lp.act = 1;
-    lp.y = hid;
-    RM_LAUNCH(launch_rm_linear(lp, (int)lin_n, st), "rmvpe fc");
-    RmDecodeP dp;
-    dp.hidden = hid;
-    dp.h_sb = (long)Tpmax * RM_CLASSES;
-    dp.h_st = RM_CLASSES;
-    dp.T = dT;
-    dp.B = B;
-    dp.Tmax = Tmax;
-    dp.thred = thred;
-    dp.f0 = f0;
-    dp.f_sb = (long)f_sb;
-    dp.out_hidden = hidden_out;
-    dp.o_sb = (long)o_sb;
-    dp.o_st = (long)o_st;
-    RM_LAUNCH(launch_rm_decode(dp, st), "rmvpe decode");
-    return DSD_OK;
-}
-
-// torchaudio.functional._get_sinc_resample_kernel(sr, 16000, gcd, lowpass_filter_width=128, rolloff=0.99,
-// "sinc_interp_hann") restated: float64 except the phase term, which torch computes as an int64 arange / new_freq (a
-// float32 tensor) before adding the float64 tap index; stored as float32.
-const RmvpeState::Resampler* rmvpe_resampler(dsd_handle* h, int sr) {
-    RmvpeState& r = *h->pe;
-    for (auto& x : r.rs)
-        if (x.sr == sr) return &x;
-    const int g = std::gcd(sr, 16000), orig = sr / g, nw = 16000 / g;
-    const double lpw = 128.0, base = std::min(orig, nw) * 0.99;
-    const int width = (int)ceil(lpw * orig / base), K = 2 * width + orig;
-    std::vector<float> kern((size_t)nw * K);
-    for (int p = 0; p < nw; ++p)
-        for (int k = 0; k < K; ++k) {
-            const double idx = (double)(k - width) / orig;
-            double t = ((double)((float)(-p) / (float)nw) + idx) * base;
-            t = std::min(lpw, std::max(-lpw, t));
-            const double cw = cos(t * M_PI / lpw / 2);
-            const double window = cw * cw;
-            t *= M_PI;
-            const double v = t == 0.0 ? 1.0 : sin(t) / t;
-            kern[(size_t)p * K + k] = (float)(v * (window * (base / orig)));
-        }
-    RmvpeState::Resampler x;
-    x.sr = sr;
-    x.orig = orig;
-    x.nw = nw;
-    x.width = width;
-    x.K = K;
-    if (hipMalloc(&x.dev, kern.size() * sizeof(float)) != hipSuccess) return nullptr;
-    if (hipMemcpy(x.dev, kern.data(), kern.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(x.dev);
-        return nullptr;
-    }
-    r.rs.push_back(x);
-    return &r.rs.back();
-}
-
-}  // namespace
-}  // extern "C++"
-
-int dsd_rmvpe_create(const dsd_rmvpe_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_rmvpe_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_rmvpe_config));
-    if (cfg->n_blocks < 1 || (cfg->n_gru != 0 && cfg->n_gru != 1) || cfg->en_de_layers < 1 || cfg->en_de_layers > 5 ||
-        cfg->inter_layers < 1 || cfg->en_out_channels < 8 || cfg->en_out_channels % 8 != 0 || cfg->en_out_channels > 64)
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: need n_blocks >= 1, n_gru in {0, 1}, 1 <= en_de_layers <= 5, "
-                    "inter_layers >= 1 and en_out_channels a multiple of 8 in [8, 64]");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_rmvpe_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_rmvpe_create: hipSetDevice failed");
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_PE_RMVPE;
-    h->cfg.in_dims = RM_MELS;
-    h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
-    h->pe = new RmvpeState();
-    h->pe->cfg = *cfg;
-    h->pe->expected = rmvpe_expected(*cfg);
-    const dsd_mel_config mc = rmvpe_mel_config(cfg->device);
-    std::vector<float> w;
-    mel_filterbank_host(mc, w, true);
-    h->pe->mel = new MelState();
-    int rc = mel_state_build(*h->pe->mel, &mc, w, "dsd_rmvpe_create");
-    if (rc) {
-        dsd_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return DSD_OK;
-}
-
-int64_t dsd_rmvpe_num_frames(int64_t n_samples, int32_t sample_rate) {
-    if (sample_rate < 1 || n_samples < 1) return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_num_frames: need n_samples, sample_rate >= 1");
-    const int64_t L16 = rmvpe_resampled_length(n_samples, sample_rate);
-    const int64_t T = mel_frames(rmvpe_geometry(), L16);
-    if (T < 1)
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_num_frames: %lld samples at 16 kHz are too short (torch.stft's reflect pad "
-                    "of 512 raises)", (long long)L16);
-    return T;
-}
-
-int dsd_rmvpe_filterbank(float* out) {
-    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_filterbank: null output");
-    std::vector<float> w;
-    mel_filterbank_host(rmvpe_mel_config(0), w, true);
-    memcpy(out, w.data(), w.size() * sizeof(float));
-    return DSD_OK;
-}
-
-int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
-                         int64_t stride_t, const int64_t* lengths, float* hidden_out, int64_t h_stride_b,
-                         int64_t h_stride_t, void* stream) {
-    if (!h || !mel || !hidden_out) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: null argument");
-    int rc = rmvpe_check(h, "dsd_rmvpe_mel_to_hidden");
-    if (rc) return rc;
-    if (B < 1 || T < 1 || T > (1 << 24)) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: need B >= 1 and 1 <= T <= 2^24");
-    std::vector<int> Tb(B);
-    for (int b = 0; b < B; ++b) {
-        const int64_t v = lengths ? lengths[b] : T;
-        if (v < 1 || v > T) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: lengths[%d] = %lld outside [1, %d]", b, (long long)v, T);
-        Tb[b] = (int)v;
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    return rmvpe_run(h, mel, stride_b, stride_m, stride_t, B, Tb, 0.f, nullptr, 0, hidden_out, h_stride_b, h_stride_t,
-                     (hipStream_t)stream, "dsd_rmvpe_mel_to_hidden");
-}
-
-int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
-                     float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
-    if (!h || !hidden || !f0_out) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: null argument");
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "dsd_rmvpe_decode: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)");
-    if (B < 1 || T < 1 || T > (1 << 24)) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: need B >= 1 and 1 <= T <= 2^24");
-    RmvpeState& r = *h->pe;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    std::vector<int>& iw = r.iw_host;
-    iw.assign(B, T);
-    int rc = rmvpe_reserve(h, r.iws, r.iws_cap, iw.size(), "dsd_rmvpe_decode");
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipMemcpyAsync(r.iws, iw.data(), iw.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    RmDecodeP dp;
-    dp.hidden = hidden;
-    dp.h_sb = (long)h_stride_b;
-    dp.h_st = (long)h_stride_t;
-    dp.T = r.iws;
-    dp.B = B;
-    dp.Tmax = T;
-    dp.thred = thred;
-    dp.f0 = f0_out;
-    dp.f_sb = (long)f0_stride_b;
-    dp.out_hidden = nullptr;
-    dp.o_sb = dp.o_st = 0;
-    RM_LAUNCH(launch_rm_decode(dp, st), "rmvpe decode");
-    return DSD_OK;
-}
-
-int dsd_rmvpe_infer(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
-                    const int64_t* lengths, int32_t sample_rate, float thred, float* f0_out, int64_t f0_stride_b,
-                    float* hidden_out, int64_t h_stride_b, int64_t h_stride_t, void* stream) {
-    const char* who = "dsd_rmvpe_infer";
-    if (!h || !wav || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    int rc = rmvpe_check(h, who);
-    if (rc) return rc;
-    RmvpeState& r = *h->pe;
-    if (B < 1 || n_samples < 1 || sample_rate < 1) return fail(h, DSD_EINVAL, "%s: B, n_samples and sample_rate must be positive", who);
-    if (n_samples > ((int64_t)1 << 30) || (B > 1 && wav_stride_b < n_samples))
-        return fail(h, DSD_EINVAL, "%s: n_samples must be <= 2^30 and wav_stride_b >= n_samples", who);
-    std::vector<int64_t> L(B), L16(B);
-    std::vector<int> T(B);
-    int64_t L16max = 0;
-    int Tmax = 0;
-    for (int b = 0; b < B; ++b) {
-        L[b] = lengths ? lengths[b] : n_samples;
-        if (L[b] < 1 || L[b] > n_samples)
-            return fail(h, DSD_EINVAL, "%s: lengths[%d] = %lld outside [1, %lld]", who, b, (long long)L[b], (long long)n_samples);
-        L16[b] = rmvpe_resampled_length(L[b], sample_rate);
-        const int64_t t = mel_frames(rmvpe_geometry(), L16[b]);
-        if (t < 1)
-            return fail(h, DSD_EINVAL, "%s: item %d has %lld samples at 16 kHz; torch.stft's reflect pad of 512 needs more", who, b,
-                        (long long)L16[b]);
-        T[b] = (int)t;
-        L16max = std::max(L16max, L16[b]);
-        Tmax = std::max(Tmax, T[b]);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    // the front end's log-mel and resampled audio live in a block of their own: rmvpe_run reuses the workspace
-    const float* w16 = wav;
-    int64_t w16_sb = wav_stride_b;
-    const size_t mel_n = (size_t)B * RM_MELS * Tmax, wav_n = sample_rate == 16000 ? 0 : (size_t)B * L16max;
-    if ((rc = rmvpe_reserve(h, r.fe, r.fe_cap, mel_n + wav_n, who))) return rc;
-    float* front = r.fe;
-    if (sample_rate != 16000) {
-        const RmvpeState::Resampler* rs = rmvpe_resampler(h, sample_rate);
-        if (!rs) return fail(h, DSD_ENOMEM, "%s: the resampling kernel for %d Hz could not be placed on the device", who, sample_rate);
-        std::vector<int>& lens = r.lens_host;
-        lens.resize(2 * B);
-        for (int b = 0; b < B; ++b) {
-            lens[b] = (int)L[b];
-            lens[B + b] = (int)L16[b];
-        }
-        if ((rc = rmvpe_reserve(h, r.lens, r.lens_cap, lens.size(), who))) return rc;
-        HIP_OK(h, hipMemcpyAsync(r.lens, lens.data(), lens.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        RmResampleP p;
-        p.x = wav;
-        p.x_sb = (long)wav_stride_b;
-        p.len_in = r.lens;
-        p.len_out = r.lens + B;
-        p.kern = rs->dev;
-        p.K = rs->K;
-        p.orig = rs->orig;
-        p.nw = rs->nw;
-        p.width = rs->width;
-        p.y = front + mel_n;
-        p.y_sb = (long)L16max;
-        RM_LAUNCH(launch_rm_resample(p, B, (L16max + rs->nw - 1) / rs->nw, rs->nw, st), "rmvpe resample");
-        w16 = front + mel_n;
-        w16_sb = L16max;
-    }
-    rc = mel_run(h, *r.mel, rmvpe_geometry(), w16, B, L16max, w16_sb, L16.data(), front, (int64_t)RM_MELS * Tmax, Tmax, 1,
-                 stream, who);
-    if (rc) return rc;
-    rc = rmvpe_run(h, front, (int64_t)RM_MELS * Tmax, Tmax, 1, B, T, thred, f0_out, f0_stride_b, hidden_out, h_stride_b,
-                   h_stride_t, st, who);
-    return rc;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// VR harmonic-noise separation and the variance curves (dsd_hnsep_*, dsd_base_harmonic, dsd_variance_curves):
-// modules/hnsep/vr/ (nets.py, layers.py), utils/decomposed_waveform.py, utils/binarizer_utils.py
-// ------------------------------------------------------------------------------------------------------------------------------
-struct HsConvW {
-    size_t w = 0, shift = 0;
-    int cout = 0, cout_pad = 0, ks = 1, stride = 1, dil_f = 1, dil_t = 1, act = 0;
-    std::vector<int> cin;                   // channels per source, in concat order
-};
-struct HsNetW {                             // one BaseNet
-    int nin = 0, nout = 0, nin_lstm = 0, H = 0;
-    HsConvW enc1, enc[4][2], aspp[5], bott, dec4, dec3, dec2, dec1, lconv, lproj, ldense;
-    size_t whh = 0;
-};
-constexpr int HS_ROWS = 64;                 // hs_dft_kernel's basis rows per tile
-struct HsBasis {
-    int N = 0, kind = 0;                    // kind 0: periodic Hann (VR), 1: Nuttall (_kth_harmonic)
-    float *win = nullptr, *fwd = nullptr, *inv = nullptr;
-    int fRpad = 0, fKpad = 0, iRpad = 0, iKpad = 0;
-};
-struct HnsepState {
-    dsd_hnsep_config cfg;
-    std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
-    bool finalized = false;
-    float* blob = nullptr;
-    HsNetW net[5];                          // stg1 low, stg1 high, stg2 low, stg2 high, stg3 full
-    HsConvW tail1, tail2, out;              // stg1_low_band_net.1, stg2_low_band_net.1, out
-    std::vector<HsBasis> bases;
-    float* ws = nullptr;
-    size_t ws_cap = 0;
-    void* iws = nullptr;                    // per-item counts and work lists
-    size_t iws_cap = 0;
-    std::vector<char> iw_host;
-};
-
-extern "C++" {
-namespace {
-
-void hnsep_free(HnsepState* s) {
-    if (!s) return;
-    for (auto& b : s->bases)
-        for (void* p : {(void*)b.win, (void*)b.fwd, (void*)b.inv})
-            if (p) (void)hipFree(p);
-    for (void* p : {(void*)s->blob, (void*)s->ws, s->iws})
-        if (p) (void)hipFree(p);
-    delete s;
-}
-
-void hs_names_cba(std::vector<std::pair<std::string, std::vector<int64_t>>>& e, const std::string& p, int cin, int cout, int k) {
-    e.push_back({p + ".conv.0.weight", {cout, cin, k, k}});
-    for (const char* n : {"weight", "bias", "running_mean", "running_var"}) e.push_back({p + ".conv.1." + n, {cout}});
-}
-
-// BaseNet(nin, nout, nin_lstm, nout_lstm)  (nets.py:8-42)
-void hs_names_net(std::vector<std::pair<std::string, std::vector<int64_t>>>& e, const std::string& p, int nin, int n,
-                  int nin_lstm, int nout_lstm) {
-    hs_names_cba(e, p + ".enc1", nin, n, 3);
-    const int ch[5] = {1, 2, 4, 6, 8};
-    for (int l = 1; l < 5; ++l) {
-        hs_names_cba(e, p + ".enc" + std::to_string(l + 1) + ".conv1", n * ch[l - 1], n * ch[l], 3);
-        hs_names_cba(e, p + ".enc" + std::to_string(l + 1) + ".conv2", n * ch[l], n * ch[l], 3);
-    }
-    hs_names_cba(e, p + ".aspp.conv1.1", 8 * n, 8 * n, 1);
-    hs_names_cba(e, p + ".aspp.conv2", 8 * n, 8 * n, 1);
-    for (int k = 3; k <= 5; ++k) hs_names_cba(e, p + ".aspp.conv" + std::to_string(k), 8 * n, 8 * n, 3);
-    hs_names_cba(e, p + ".aspp.bottleneck", 40 * n, 8 * n, 1);
-    hs_names_cba(e, p + ".dec4.conv1", 14 * n, 6 * n, 3);
-    hs_names_cba(e, p + ".dec3.conv1", 10 * n, 4 * n, 3);
-    hs_names_cba(e, p + ".dec2.conv1", 6 * n, 2 * n, 3);
-    hs_names_cba(e, p + ".lstm_dec2.conv", 2 * n, 1, 1);
-    const int H = nout_lstm / 2;
-    for (const char* sfx : {"", "_reverse"}) {
-        const std::string l = p + ".lstm_dec2.lstm.";
-        e.push_back({l + "weight_ih_l0" + sfx, {4 * H, nin_lstm}});
-        e.push_back({l + "weight_hh_l0" + sfx, {4 * H, H}});
-        e.push_back({l + "bias_ih_l0" + sfx, {4 * H}});
-        e.push_back({l + "bias_hh_l0" + sfx, {4 * H}});
-    }
-    e.push_back({p + ".lstm_dec2.dense.0.weight", {nin_lstm, nout_lstm}});
-    e.push_back({p + ".lstm_dec2.dense.0.bias", {nin_lstm}});
-    for (const char* nm : {"weight", "bias", "running_mean", "running_var"}) e.push_back({p + ".lstm_dec2.dense.1." + nm, {nin_lstm}});
-    hs_names_cba(e, p + ".dec1.conv1", 3 * n + 1, n, 3);
-}
-
-const char* const HS_NET[5] = {"stg1_low_band_net.0", "stg1_high_band_net", "stg2_low_band_net.0", "stg2_high_band_net",
-                               "stg3_full_band_net"};
-
-struct HsNetDims {
-    int nin, nout, nin_lstm, nout_lstm;
-};
-void hs_net_dims(const dsd_hnsep_config& c, HsNetDims d[5]) {
-    const int nin = c.is_mono ? 2 : 4, nl = c.n_fft / 4, n = c.nout, L = c.nout_lstm;   // nin_lstm = max_bin / 2
-    d[0] = {nin, n / 2, nl / 2, L};
-    d[1] = {nin, n / 4, nl / 2, L / 2};
-    d[2] = {n / 4 + nin, n, nl / 2, L};
-    d[3] = {n / 4 + nin, n / 2, nl / 2, L / 2};
-    d[4] = {3 * n / 4 + nin, n, nl, L};
-}
-
-std::vector<std::pair<std::string, std::vector<int64_t>>> hnsep_expected(const dsd_hnsep_config& c) {
-    std::vector<std::pair<std::string, std::vector<int64_t>>> e;
-    HsNetDims d[5];
-    hs_net_dims(c, d);
-    const int nin = c.is_mono ? 2 : 4, n = c.nout;
-    for (int i = 0; i < 5; ++i) hs_names_net(e, HS_NET[i], d[i].nin, d[i].nout, d[i].nin_lstm, d[i].nout_lstm);
-    hs_names_cba(e, "stg1_low_band_net.1", n / 2, n / 4, 1);
-    hs_names_cba(e, "stg2_low_band_net.1", n, n / 2, 1);
-    e.push_back({"out.weight", {nin, n, 1, 1}});
-    e.push_back({"aux_out.weight", {nin, 3 * n / 4, 1, 1}});
-    return e;
-}
-
-int hnsep_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim, int32_t on_device) {
-    if (!name) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    const std::string n(name);
-    if (ends_with(n, ".num_batches_tracked")) return DSD_OK;       // BatchNorm's step counter carries no value
-    if (!data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    HnsepState& r = *h->hs;
-    std::vector<int64_t> shp(shape, shape + ndim);
-    const std::vector<int64_t>* want = nullptr;
-    for (auto& e : r.expected)
-        if (e.first == n) want = &e.second;
-    if (!want) return fail(h, DSD_ENOTFOUND, "unexpected key in state_dict: %s", name);
-    if (*want != shp) {
-        std::string a, b;
-        for (auto v : *want) a += std::to_string(v) + ",";
-        for (auto v : shp) b += std::to_string(v) + ",";
-        return fail(h, DSD_EINVAL, "size mismatch for %s: expected [%s] got [%s]", name, a.c_str(), b.c_str());
-    }
-    size_t numel = 1;
-    for (auto v : shp) numel *= (size_t)v;
-    HostTensor t;
-    t.shape = shp;
-    t.data.resize(numel);
-    if (on_device) {
-        HIP_OK(h, hipSetDevice(h->cfg.device));
-        HIP_OK(h, hipMemcpy(t.data.data(), data, numel * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-        memcpy(t.data.data(), data, numel * sizeof(float));
-    }
-    h->raw[n] = std::move(t);
-    r.finalized = false;
-    return DSD_OK;
-}
-
-// eval-mode BatchNorm (eps 1e-5) as scale / shift, in double
-void hs_bn(const dsd_handle* h, const std::string& p, int C, std::vector<double>& sc, std::vector<double>& sh) {
-    const auto &g = h->raw.at(p + ".weight").data, &b = h->raw.at(p + ".bias").data;
-    const auto &m = h->raw.at(p + ".running_mean").data, &v = h->raw.at(p + ".running_var").data;
-    sc.resize(C);
-    sh.resize(C);
-    for (int c = 0; c < C; ++c) {
-        sc[c] = (double)g[c] / sqrt((double)v[c] + 1e-5);
-        sh[c] = (double)b[c] - (double)m[c] * sc[c];
-    }
-}
-
-// w(co, ci, kf, kt) of a conv over the concat `cin` (sources in order) -> [(source, kf ks + kt, channel < Cp)][cout_pad],
-// times sc[co]; shift -> [cout_pad]
-template <typename W>
-HsConvW hs_pack(std::vector<float>& blob, W&& w, int cout, std::vector<int> cin, int ks, const std::vector<double>& sc,
-                const std::vector<double>& sh) {
-    HsConvW c;
-    c.cout = cout;
-    c.cout_pad = (cout + 15) / 16 * 16;
-    c.ks = ks;
-    c.cin = cin;
-    size_t rows = 0;
-    for (int cs : cin) rows += (size_t)ks * ks * ((cs + 3) / 4 * 4);
-    c.w = blob.size();
-    blob.resize(blob.size() + rows * c.cout_pad, 0.f);
-    size_t row = 0;
-    int cb = 0;
-    for (int cs : cin) {
-        const int cp = (cs + 3) / 4 * 4;
-        for (int kf = 0; kf < ks; ++kf)
-            for (int kt = 0; kt < ks; ++kt) {
-                for (int ci = 0; ci < cs; ++ci)
-                    for (int co = 0; co < cout; ++co) blob[c.w + (row + ci) * c.cout_pad + co] = (float)(w(co, cb + ci, kf, kt) * sc[co]);
-                row += cp;
-            }
-        cb += cs;
-    }
-    c.shift = blob.size();
-    blob.resize(blob.size() + c.cout_pad, 0.f);
-    for (int co = 0; co < cout; ++co) blob[c.shift + co] = (float)sh[co];
-    return c;
-}
-
-// Conv2DBNActiv under `p` over the concat `cin`
-HsConvW hs_pack_cba(const dsd_handle* h, std::vector<float>& blob, const std::string& p, int cout, std::vector<int> cin, int ks,
-                    int stride, int dil_f, int dil_t, int act) {
-    std::vector<double> sc, sh;
-    hs_bn(h, p + ".conv.1", cout, sc, sh);
-    int ct = 0;
-    for (int v : cin) ct += v;
-    const std::vector<float>& W = h->raw.at(p + ".conv.0.weight").data;
-    HsConvW c = hs_pack(blob, [&](int co, int ci, int kf, int kt) { return (double)W[(((size_t)co * ct + ci) * ks + kf) * ks + kt]; },
-                        cout, cin, ks, sc, sh);
-    c.stride = stride;
-    c.dil_f = dil_f;
-    c.dil_t = dil_t;
-    c.act = act;
-    return c;
-}
-
-void hs_pack_net(const dsd_handle* h, std::vector<float>& blob, HsNetW& N, const std::string& p, const HsNetDims& d,
-                 const std::vector<int>& in_split) {
-    const int n = d.nout;
-    N.nin = d.nin;
-    N.nout = n;
-    N.nin_lstm = d.nin_lstm;
-    N.H = d.nout_lstm / 2;
-    N.enc1 = hs_pack_cba(h, blob, p + ".enc1", n, in_split, 3, 1, 1, 1, 1);
-    const int ch[5] = {1, 2, 4, 6, 8};
-    for (int l = 1; l < 5; ++l) {
-        const std::string q = p + ".enc" + std::to_string(l + 1);
-        N.enc[l - 1][0] = hs_pack_cba(h, blob, q + ".conv1", n * ch[l], {n * ch[l - 1]}, 3, 2, 1, 1, 2);
-        N.enc[l - 1][1] = hs_pack_cba(h, blob, q + ".conv2", n * ch[l], {n * ch[l]}, 3, 1, 1, 1, 2);
-    }
-    N.aspp[0] = hs_pack_cba(h, blob, p + ".aspp.conv1.1", 8 * n, {8 * n}, 1, 1, 1, 1, 1);
-    N.aspp[1] = hs_pack_cba(h, blob, p + ".aspp.conv2", 8 * n, {8 * n}, 1, 1, 1, 1, 1);
-    const int dl[3][2] = {{4, 2}, {8, 4}, {12, 6}};      // BaseNet's dilations: (bins, frames)
-    for (int k = 0; k < 3; ++k)
-        N.aspp[2 + k] = hs_pack_cba(h, blob, p + ".aspp.conv" + std::to_string(k + 3), 8 * n, {8 * n}, 3, 1, dl[k][0], dl[k][1], 1);
-    N.bott = hs_pack_cba(h, blob, p + ".aspp.bottleneck", 8 * n, {8 * n, 32 * n}, 1, 1, 1, 1, 1);
-    N.dec4 = hs_pack_cba(h, blob, p + ".dec4.conv1", 6 * n, {8 * n, 6 * n}, 3, 1, 1, 1, 1);
-    N.dec3 = hs_pack_cba(h, blob, p + ".dec3.conv1", 4 * n, {6 * n, 4 * n}, 3, 1, 1, 1, 1);
-    N.dec2 = hs_pack_cba(h, blob, p + ".dec2.conv1", 2 * n, {4 * n, 2 * n}, 3, 1, 1, 1, 1);
-    N.lconv = hs_pack_cba(h, blob, p + ".lstm_dec2.conv", 1, {2 * n}, 1, 1, 1, 1, 1);
-    N.dec1 = hs_pack_cba(h, blob, p + ".dec1.conv1", n, {2 * n + 1, n}, 3, 1, 1, 1, 1);
-    // the LSTM's input projection of both directions as one 1x1 conv over the bins: cout = 2 x 4H (forward | reverse),
-    // shift = b_ih + b_hh
-    const int H = N.H, G = 4 * H, K = d.nin_lstm;
-    const std::string l = p + ".lstm_dec2.lstm.";
-    const std::vector<float>& wf = h->raw.at(l + "weight_ih_l0").data;
-    const std::vector<float>& wr = h->raw.at(l + "weight_ih_l0_reverse").data;
-    std::vector<double> one(2 * G, 1.0), bias(2 * G);
-    for (int d2 = 0; d2 < 2; ++d2) {
-        const char* sfx = d2 ? "_reverse" : "";
-        const auto &bi = h->raw.at(l + "bias_ih_l0" + sfx).data, &bh = h->raw.at(l + "bias_hh_l0" + sfx).data;
-        for (int g = 0; g < G; ++g) bias[d2 * G + g] = (double)bi[g] + (double)bh[g];
-    }
-    N.lproj = hs_pack(blob, [&](int co, int ci, int, int) { return (double)(co < G ? wf[(size_t)co * K + ci] : wr[(size_t)(co - G) * K + ci]); },
-                      2 * G, {K}, 1, one, bias);
-    N.whh = blob.size();
-    for (const char* sfx : {"", "_reverse"}) {
-        const std::vector<float>& w = h->raw.at(l + "weight_hh_l0" + sfx).data;
-        blob.insert(blob.end(), w.begin(), w.end());
-    }
-    // dense: Linear(2H, nin_lstm) + BatchNorm1d + ReLU folded: W s, (b - m) s + beta
-    std::vector<double> sc, sh;
-    hs_bn(h, p + ".lstm_dec2.dense.1", K, sc, sh);
-    const std::vector<float>& dw = h->raw.at(p + ".lstm_dec2.dense.0.weight").data;
-    const std::vector<float>& db = h->raw.at(p + ".lstm_dec2.dense.0.bias").data;
-    for (int k = 0; k < K; ++k) sh[k] += (double)db[k] * sc[k];
-    N.ldense = hs_pack(blob, [&](int co, int ci, int, int) { return (double)dw[(size_t)co * 2 * H + ci]; }, K, {2 * H}, 1, sc, sh);
-    N.ldense.act = 1;
-}
-
-int hnsep_finalize(dsd_handle* h) {
-    HnsepState& r = *h->hs;
-    std::string missing;
-    for (auto& e : r.expected)
-        if (!h->raw.count(e.first)) missing += (missing.empty() ? "" : ", ") + e.first;
-    if (!missing.empty()) return fail(h, DSD_ESTATE, "missing keys in state_dict: %s", missing.c_str());
-    const dsd_hnsep_config& c = r.cfg;
-    const int C = c.is_mono ? 1 : 2, n = c.nout;
-    HsNetDims d[5];
-    hs_net_dims(c, d);
-    std::vector<float> blob;
-    // network input sources: re channels, im channels, then the stage outputs
-    hs_pack_net(h, blob, r.net[0], HS_NET[0], d[0], {C, C});
-    hs_pack_net(h, blob, r.net[1], HS_NET[1], d[1], {C, C});
-    hs_pack_net(h, blob, r.net[2], HS_NET[2], d[2], {C, C, n / 4});
-    hs_pack_net(h, blob, r.net[3], HS_NET[3], d[3], {C, C, n / 4});
-    hs_pack_net(h, blob, r.net[4], HS_NET[4], d[4], {C, C, n / 4, n / 2});
-    r.tail1 = hs_pack_cba(h, blob, "stg1_low_band_net.1", n / 4, {n / 2}, 1, 1, 1, 1, 1);
-    r.tail2 = hs_pack_cba(h, blob, "stg2_low_band_net.1", n / 2, {n}, 1, 1, 1, 1, 1);
-    const std::vector<float>& ow = h->raw.at("out.weight").data;
-    std::vector<double> one(2 * C, 1.0), zero(2 * C, 0.0);
-    r.out = hs_pack(blob, [&](int co, int ci, int, int) { return (double)ow[(size_t)co * n + ci]; }, 2 * C, {n}, 1, one, zero);
-    if (r.blob) (void)hipFree(r.blob);
-    r.blob = nullptr;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    if (hipMalloc(&r.blob, blob.size() * sizeof(float)) != hipSuccess)
-        return fail(h, DSD_ENOMEM, "hipMalloc(%zu bytes of packed separator weights) failed", blob.size() * 4);
-    HIP_OK(h, hipMemcpy(r.blob, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
-    r.finalized = true;
-    return DSD_OK;
-}
-
-// the window (float32, as torch builds it) and the forward / inverse DFT bases of one (N, kind), built on first use and
-// complete before it returns (the cache serves every stream)
-const HsBasis* hs_basis(dsd_handle* h, int N, int kind, hipStream_t st) {
-    HnsepState& r = *h->hs;
-    for (auto& b : r.bases)
-        if (b.N == N && b.kind == kind) return &b;
-    std::vector<float> w(N);
-    for (int j = 0; j < N; ++j) {
-        if (kind == 0) {       // torch.hann_window(N) (periodic)
-            w[j] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * j / N));
-        } else {               // decomposed_waveform.py:168-174, in float32
-            const float ph = (float)j / (float)N * 2.f * (float)M_PI;
-            w[j] = 0.355768f - 0.487396f * cosf(ph) + 0.144232f * cosf(2.f * ph) - 0.012604f * cosf(3.f * ph);
-        }
-    }
-    HsBasis b;
-    b.N = N;
-    b.kind = kind;
-    const int nb = N / 2 + 1;
-    b.fRpad = (2 * nb + HS_ROWS - 1) / HS_ROWS * HS_ROWS;
-    b.fKpad = N;
-    b.iRpad = (N + HS_ROWS - 1) / HS_ROWS * HS_ROWS;
-    b.iKpad = (2 * nb + 31) / 32 * 32;
-    if (hipMalloc(&b.win, N * sizeof(float)) != hipSuccess || hipMalloc(&b.fwd, (size_t)b.fRpad * b.fKpad * sizeof(float)) != hipSuccess ||
-        hipMalloc(&b.inv, (size_t)b.iRpad * b.iKpad * sizeof(float)) != hipSuccess) {
-        for (void* p : {(void*)b.win, (void*)b.fwd, (void*)b.inv})
-            if (p) (void)hipFree(p);
-        return nullptr;
-    }
-    if (hipMemcpy(b.win, w.data(), N * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        launch_hs_basis(b.fwd, b.win, b.fRpad, b.fKpad, nb, N, 0, st) != hipSuccess ||
-        launch_hs_basis(b.inv, b.win, b.iRpad, b.iKpad, nb, N, 1, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {      // once per (N, window): later calls may come on other streams
-        for (void* p : {(void*)b.win, (void*)b.fwd, (void*)b.inv}) (void)hipFree(p);
-        return nullptr;
-    }
-    r.bases.push_back(b);
-    return &r.bases.back();
-}
-
-int hs_check(dsd_handle* h, const char* who, bool weights) {
-    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
-    if (!is_hs(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a harmonic-noise separator (dsd_hnsep_create)", who);
-    if (weights && !h->hs->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
-    return DSD_OK;
-}
-
-// per-call host block of ints and longs uploaded once: `add()` appends an array at an 8-byte aligned offset and returns
-// that offset, which the launches add to the block's device copy
-struct HsUpload {
-    std::vector<char>& buf;
-    size_t add(const void* p, size_t n) {
-        const size_t at = (buf.size() + 7) / 8 * 8;
-        buf.resize(at + n);
-        memcpy(buf.data() + at, p, n);
-        return at;
-    }
-};
-
-// CascadedNet.forward on B items of T_b frames (multiples of 16), input re / im sources at level 0 (bins [0, 2 bw)),
-// mask written through `mv` (re at c cs, im at im_off + c cs) for all nb = n_fft / 2 + 1 bins
-struct HsRun {
-    dsd_handle* h;
-    hipStream_t st;
-    int B, Tal;
-    const int* dT;                  // device: frames per item at level 0 .. 4 ([5][B])
-    std::vector<int> Tl[5];         // host copy
-    char* iw;                       // device work-list block
-    std::vector<char>* iw_host;
-    std::map<std::tuple<int, int, int>, std::pair<size_t, int>> conv_wl;   // (F, level out, level in) -> (offset, entries)
-    bool dry = true;                // sizing pass: count the workspace, launch nothing
-    float* ws = nullptr;            // bump allocator over the workspace
-    size_t ws_used = 0, ws_peak = 0;
-    float* alloc(size_t n) {
-        float* p = dry ? nullptr : ws + ws_used;
-        ws_used += (n + 63) / 64 * 64;
-        ws_peak = std::max(ws_peak, ws_used);
-        return p;
-    }
-};
-
-HsSrc hs_src(const float* p, long bs, long fs, long ts, long cs, int C, int mode = 0) {
-    HsSrc s;
-    s.p = p;
-    s.bs = bs;
-    s.fs = fs;
-    s.ts = ts;
-    s.cs = cs;
-    s.C = C;
-    s.Cp = (C + 3) / 4 * 4;
-    s.mode = mode;
-    return s;
-}
-HsView hs_view(float* p, long bs, long fs, long ts, long cs) {
-    HsView v;
-    v.p = p;
-    v.bs = bs;
-    v.fs = fs;
-    v.ts = ts;
-    v.cs = cs;
-    return v;
-}
-// a [B][F][Tal >> l][C] tensor
-struct HsT {
-    float* p = nullptr;
-    int F = 0, T = 0, C = 0;
-    long bs() const { return (long)F * T * C; }
-    HsSrc src(int c0 = 0, int nc = -1, int mode = 0) const { return hs_src(p + c0, bs(), (long)T * C, C, 1, nc < 0 ? C - c0 : nc, mode); }
-    HsView view(int f0 = 0, int c0 = 0) const { return hs_view(p + (long)f0 * T * C + c0, bs(), (long)T * C, C, 1); }
-};
-
-#define HS_LAUNCH(expr, what)                                                                            \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess) return fail(h, DSD_EHIP, "%s launch failed: %s", what, hipGetErrorString(e_)); \
-    } while (0)
-
-}  // namespace
-}  // extern "C++"
-
-extern "C++" {
-namespace {
-
-// conv work lists (b, q0, T_l out, T_l in) over 64 positions for every (F >> l, level) a forward at bands Fb meets
-void hs_conv_lists(HsRun& R, HsUpload& up, std::initializer_list<int> Fb) {
-    auto add = [&](int F, int lo, int li) {
-        const auto key = std::make_tuple(F, lo, li);
-        if (R.conv_wl.count(key)) return;
-        std::vector<int> e;
-        for (int b = 0; b < R.B; ++b) {
-            const int To = R.Tl[lo][b], Ti = R.Tl[li][b], np_ = F * To;
-            for (int q0 = 0; q0 < np_; q0 += 64) e.insert(e.end(), {b, q0, To, Ti});
-        }
-        R.conv_wl[key] = {up.add(e.data(), e.size() * sizeof(int)), (int)(e.size() / 4)};
-    };
-    for (int l = 0; l < 5; ++l) {
-        add(1, l, l);
-        for (int F : Fb) {
-            add(F >> l, l, l);
-            if (l) add(F >> l, l, l - 1);
-        }
-    }
-}
-
-int hs_conv(HsRun& R, const HsConvW& cw, const std::vector<HsSrc>& srcs, HsView y, int F, int Fin, int lo, int li) {
-    dsd_handle* h = R.h;
-    if (R.dry) return DSD_OK;
-    HsConvP p;
-    memset(&p, 0, sizeof(p));
-    p.nsrc = 0;
-    for (const HsSrc& s : srcs) p.src[p.nsrc++] = s;
-    if (p.nsrc != (int)cw.cin.size()) return fail(h, DSD_EINVAL, "internal: conv source count mismatch");
-    for (int i = 0; i < p.nsrc; ++i)
-        if (p.src[i].C != cw.cin[i]) return fail(h, DSD_EINVAL, "internal: conv source %d has %d channels, weights %d", i, p.src[i].C, cw.cin[i]);
-    p.w = h->hs->blob + cw.w;
-    p.shift = h->hs->blob + cw.shift;
-    p.y = y;
-    p.cout = cw.cout;
-    p.cout_pad = cw.cout_pad;
-    p.F = F;
-    p.Fin = Fin;
-    p.ks = cw.ks;
-    p.stride = cw.stride;
-    p.dil_f = cw.dil_f;
-    p.dil_t = cw.dil_t;
-    p.act = cw.act;
-    const auto& wl = R.conv_wl.at(std::make_tuple(F, lo, li));
-    p.work = (const int*)(R.iw + wl.first);
-    HS_LAUNCH(launch_hs_conv(p, wl.second, R.st), "hnsep conv");
-    return DSD_OK;
-}
-
-#define HS_RC(expr)             \
-    do {                        \
-        int rc_ = (expr);       \
-        if (rc_) return rc_;    \
-    } while (0)
-
-// One BaseNet (nets.py:30-42) on the sources `in` (level 0, F bins) -> `out` (nout channels), in two phases around the
-// LSTM recurrence, so that the sub-nets of one stage share its launch (hs_stage)
-struct HsNetRun {
-    const HsNetW* N;
-    std::vector<HsSrc> in;
-    int F;
-    HsView out;
-    HsT e0, d2;                     // kept for phase B: enc1's output (dec1's skip), dec2's output + the LSTM channel
-    float *gi = nullptr, *ly = nullptr;
-};
-
-// phase A: encoders, ASPP, decoders down to dec2, the LSTM module's 1x1 conv and the input projection
-int hs_net_a(HsRun& R, HsNetRun& r) {
-    const HsNetW& N = *r.N;
-    const int n = N.nout, B = R.B, F = r.F, ch[5] = {1, 2, 4, 6, 8};
-    dsd_handle* h = R.h;
-    auto T = [&](int l, int Fl, int C) {
-        HsT t;
-        t.F = Fl;
-        t.T = R.Tal >> l;
-        t.C = C;
-        t.p = R.alloc((size_t)B * t.bs());
-        return t;
-    };
-    HsT e[5];
-    e[0] = T(0, F, n);
-    HS_RC(hs_conv(R, N.enc1, r.in, e[0].view(), F, F, 0, 0));
-    for (int l = 1; l < 5; ++l) {
-        HsT a = T(l, F >> l, n * ch[l]);
-        e[l] = T(l, F >> l, n * ch[l]);
-        HS_RC(hs_conv(R, N.enc[l - 1][0], {e[l - 1].src()}, a.view(), F >> l, F >> (l - 1), l, l - 1));
-        HS_RC(hs_conv(R, N.enc[l - 1][1], {a.src()}, e[l].view(), F >> l, F >> l, l, l));
-    }
-    // ASPP at level 4: the bin mean's 1x1 conv is broadcast over bins inside the bottleneck's staging
-    const int F4 = F >> 4;
-    HsT m = T(4, 1, 8 * n), f1 = T(4, 1, 8 * n), cat = T(4, F4, 32 * n), h4 = T(4, F4, 8 * n);
-    if (!R.dry) {
-        HsBinMeanP bp;
-        bp.x = e[4].view();
-        bp.y = m.view();
-        bp.F = F4;
-        bp.C = 8 * n;
-        bp.T = R.dT + 4 * B;
-        HS_LAUNCH(launch_hs_binmean(bp, B, R.Tal >> 4, R.st), "hnsep bin mean");
-    }
-    HS_RC(hs_conv(R, N.aspp[0], {m.src()}, f1.view(), 1, 1, 4, 4));
-    for (int k = 1; k < 5; ++k) HS_RC(hs_conv(R, N.aspp[k], {e[4].src()}, cat.view(0, (k - 1) * 8 * n), F4, F4, 4, 4));
-    HS_RC(hs_conv(R, N.bott, {f1.src(0, -1, 2), cat.src()}, h4.view(), F4, F4, 4, 4));
-    // decoders: the x2 bilinear upsample of the coarser tensor is computed while the conv stages it
-    HsT d4 = T(3, F >> 3, 6 * n), d3 = T(2, F >> 2, 4 * n);
-    r.d2 = T(1, F >> 1, 2 * n + 1);
-    HS_RC(hs_conv(R, N.dec4, {h4.src(0, -1, 1), e[3].src()}, d4.view(), F >> 3, F >> 3, 3, 3));
-    HS_RC(hs_conv(R, N.dec3, {d4.src(0, -1, 1), e[2].src()}, d3.view(), F >> 2, F >> 2, 2, 2));
-    HS_RC(hs_conv(R, N.dec2, {d3.src(0, -1, 1), e[1].src()}, r.d2.view(), F >> 1, F >> 1, 1, 1));
-    // LSTMModule at level 1: 1x1 conv to one channel written as [t][bin], then the input projection of both directions
-    const int F1 = F >> 1, T1 = R.Tal >> 1, H = N.H;
-    float* li = R.alloc((size_t)B * T1 * F1);
-    r.gi = R.alloc((size_t)B * T1 * 8 * H);
-    r.ly = R.alloc((size_t)B * T1 * 2 * H);
-    r.e0 = e[0];
-    HS_RC(hs_conv(R, N.lconv, {r.d2.src(0, 2 * n)}, hs_view(li, (long)T1 * F1, 1, F1, 0), F1, F1, 1, 1));
-    HS_RC(hs_conv(R, N.lproj, {hs_src(li, (long)T1 * F1, 0, F1, 1, F1)}, hs_view(r.gi, (long)T1 * 8 * H, 0, 8 * H, 1), 1, 1,
-                  1, 1));
-    return DSD_OK;
-}
-
-// phase B: the dense layer (BatchNorm1d folded) written as the extra channel 2n of d2, then dec1 -> out
-int hs_net_b(HsRun& R, HsNetRun& r) {
-    const HsNetW& N = *r.N;
-    const int n = N.nout, T1 = R.Tal >> 1, H = N.H;
-    HS_RC(hs_conv(R, N.ldense, {hs_src(r.ly, (long)T1 * 2 * H, 0, 2 * H, 1, 2 * H)},
-                  hs_view(r.d2.p + 2 * n, r.d2.bs(), 0, r.d2.C, (long)r.d2.T * r.d2.C), 1, 1, 1, 1));
-    HS_RC(hs_conv(R, N.dec1, {r.d2.src(0, -1, 1), r.e0.src()}, r.out, r.F, r.F, 0, 0));
-    return DSD_OK;
-}
-
-// one stage of CascadedNet: phase A of each sub-net (1 or 2), ONE launch of the BiLSTM recurrence for all of them
-// (a workgroup per item, sub-net and direction), phase B of each; the stage's scratch is released at the end
-int hs_stage(HsRun& R, std::initializer_list<HsNetRun*> nets) {
-    dsd_handle* h = R.h;
-    const size_t mark = R.ws_used;
-    for (HsNetRun* r : nets) HS_RC(hs_net_a(R, *r));
-    if (!R.dry) {
-        HsLstmP lp;
-        memset(&lp, 0, sizeof(lp));
-        int k = 0;
-        for (HsNetRun* r : nets) {
-            const int T1 = R.Tal >> 1, H = r->N->H;
-            lp.net[k].gi = r->gi;
-            lp.net[k].gi_bs = (long)T1 * 8 * H;
-            lp.net[k].whh = h->hs->blob + r->N->whh;
-            lp.net[k].y = r->ly;
-            lp.net[k].y_bs = (long)T1 * 2 * H;
-            lp.net[k].H = H;
-            ++k;
-        }
-        lp.T = R.dT + R.B;
-        HS_LAUNCH(launch_hs_lstm(lp, R.B, k, R.st), "hnsep lstm");
-    }
-    for (HsNetRun* r : nets) HS_RC(hs_net_b(R, *r));
-    R.ws_used = mark;
-    return DSD_OK;
-}
-
-// CascadedNet.forward (nets.py:99-133): re / im sources (C channels each, bins from 0) -> the bounded mask through `mv`
-// (re at c cs, im at m_im + c cs) over n_fft / 2 + 1 bins
-int hs_forward(HsRun& R, const HsSrc& xre, const HsSrc& xim, HsView mv, long m_im) {
-    dsd_handle* h = R.h;
-    HnsepState& S = *h->hs;
-    const int C = S.cfg.is_mono ? 1 : 2, n = S.cfg.nout, mb = S.cfg.n_fft / 2, bw = mb / 2, B = R.B;
-    auto T = [&](int Fl, int Ch) {
-        HsT t;
-        t.F = Fl;
-        t.T = R.Tal;
-        t.C = Ch;
-        t.p = R.alloc((size_t)B * t.bs());
-        return t;
-    };
-    HsT aux1 = T(mb, n / 4), aux2 = T(mb, n / 2), tl = T(bw, n), f3 = T(mb, n), o = T(mb, 2 * C);
-    auto hi = [&](HsSrc s) {
-        s.p += (long)bw * s.fs;
-        return s;
-    };
-    auto part = [&](const HsT& t, int f0) {         // the bins from f0 of a full-band stage output
-        HsSrc s = t.src();
-        s.p += (long)f0 * s.fs;
-        return s;
-    };
-    // stage 1: low and high band side by side (the low band's output through its 1x1 tail into aux1's low bins)
-    HsT l1 = T(bw, n / 2);
-    HsNetRun s1l{&S.net[0], {xre, xim}, bw, l1.view()}, s1h{&S.net[1], {hi(xre), hi(xim)}, bw, aux1.view(bw)};
-    HS_RC(hs_stage(R, {&s1l, &s1h}));
-    HS_RC(hs_conv(R, S.tail1, {l1.src()}, aux1.view(0), bw, bw, 0, 0));
-    // stage 2: each band with its stage-1 output concatenated
-    HsNetRun s2l{&S.net[2], {xre, xim, part(aux1, 0)}, bw, tl.view()}, s2h{&S.net[3], {hi(xre), hi(xim), part(aux1, bw)}, bw,
-                                                                          aux2.view(bw)};
-    HS_RC(hs_stage(R, {&s2l, &s2h}));
-    HS_RC(hs_conv(R, S.tail2, {tl.src()}, aux2.view(0), bw, bw, 0, 0));
-    // stage 3: the full band with both stages' outputs
-    HsNetRun s3{&S.net[4], {xre, xim, aux1.src(), aux2.src()}, mb, f3.view()};
-    HS_RC(hs_stage(R, {&s3}));
-    HS_RC(hs_conv(R, S.out, {f3.src()}, o.view(), mb, mb, 0, 0));
-    if (!R.dry) {
-        HsMaskP mp;
-        mp.x = o.view();
-        mp.y = mv;
-        mp.y_im = m_im;
-        mp.F = mb + 1;
-        mp.Fx = mb;
-        mp.C = C;
-        mp.T = R.dT;
-        HS_LAUNCH(launch_hs_mask(mp, B, R.Tal, R.st), "hnsep mask");
-    }
-    return DSD_OK;
-}
-
-// set up R for B items of Tp[b] frames (multiples of 16): per-level frame counts, conv work lists
-void hs_setup(HsRun& R, dsd_handle* h, HsUpload& up, const std::vector<int>& Tp, hipStream_t st, size_t& dT_off) {
-    R.h = h;
-    R.st = st;
-    R.B = (int)Tp.size();
-    R.Tal = 0;
-    for (int v : Tp) R.Tal = std::max(R.Tal, v);
-    std::vector<int> all;
-    for (int l = 0; l < 5; ++l) {
-        R.Tl[l].resize(R.B);
-        for (int b = 0; b < R.B; ++b) all.push_back(R.Tl[l][b] = Tp[b] >> l);
-    }
-    dT_off = up.add(all.data(), all.size() * sizeof(int));
-    const int mb = h->hs->cfg.n_fft / 2;
-    hs_conv_lists(R, up, {mb / 2, mb});
-}
-
-// upload the host block, size the workspace by a dry run of `body`, then run it
-template <typename Body>
-int hs_execute(HsRun& R, std::vector<char>& up, size_t dT_off, const char* who, Body&& body) {
-    dsd_handle* h = R.h;
-    HnsepState& S = *h->hs;
-    R.dry = true;
-    R.ws_used = R.ws_peak = 0;
-    HS_RC(body());
-    const size_t need = R.ws_peak;
-    if (need * 4 >= ((size_t)1 << 40)) return fail(h, DSD_EINVAL, "%s: batch too large for one call", who);
-    HS_RC(rmvpe_reserve(h, S.ws, S.ws_cap, need, who));
-    char* iws = (char*)S.iws;
-    HS_RC(rmvpe_reserve(h, iws, S.iws_cap, std::max<size_t>(up.size(), 8), who));
-    S.iws = iws;
-    HIP_OK(h, hipMemcpyAsync(S.iws, up.data(), up.size(), hipMemcpyHostToDevice, R.st));
-    R.iw = (char*)S.iws;
-    R.dT = (const int*)(R.iw + dT_off);
-    R.dry = false;
-    R.ws = S.ws;
-    R.ws_used = 0;
-    return body();
-}
-
-}  // namespace
-}  // extern "C++"
-
-extern "C" {
-
-int dsd_hnsep_create(const dsd_hnsep_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_hnsep_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_hnsep_config));
-    if (cfg->n_fft < 128 || cfg->n_fft > 4096 || cfg->n_fft % 64 != 0 || cfg->hop_length < 1 || cfg->hop_length > cfg->n_fft / 2 ||
-        cfg->nout < 4 || cfg->nout > 64 || cfg->nout % 4 != 0 || cfg->nout_lstm < 8 || cfg->nout_lstm > 128 ||
-        cfg->nout_lstm % 8 != 0 || (cfg->is_mono != 0 && cfg->is_mono != 1))
-        return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: need n_fft a multiple of 64 in [128, 4096], 1 <= hop_length <= "
-                    "n_fft / 2, nout a multiple of 4 in [4, 64], nout_lstm a multiple of 8 in [8, 128], is_mono 0 or 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(nullptr, DSD_EHIP, "dsd_hnsep_create: no HIP device is visible (this library has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: device %d out of range [0, %d)", cfg->device, ndev);
-    if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_hnsep_create: hipSetDevice failed");
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_HNSEP_VR;
-    h->cfg.in_dims = cfg->n_fft / 2 + 1;
-    h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
-    h->hs = new HnsepState();
-    h->hs->cfg = *cfg;
-    h->hs->expected = hnsep_expected(*cfg);
-    *out = h;
-    return DSD_OK;
-}
-
-int64_t dsd_hnsep_num_frames(int64_t n_samples, int32_t hop_length) {
-    if (n_samples < 1 || hop_length < 1) return fail(nullptr, DSD_EINVAL, "dsd_hnsep_num_frames: need n_samples, hop_length >= 1");
-    const int64_t n = n_samples / hop_length + 1;
-    return 32 * (n / 32 + 1);
-}
-
-int dsd_hnsep_mask(dsd_handle* h, const float* spec, int32_t B, int32_t T, int64_t s_stride_b, int64_t s_stride_c,
-                   int64_t s_stride_f, int64_t s_stride_t, const int64_t* lengths, float* mask_out, int64_t m_stride_b,
-                   int64_t m_stride_c, int64_t m_stride_f, int64_t m_stride_t, void* stream) {
-    const char* who = "dsd_hnsep_mask";
-    HS_RC(hs_check(h, who, true));
-    if (!spec || !mask_out || B < 1 || T < 16) return fail(h, DSD_EINVAL, "%s: bad argument", who);
-    std::vector<int> Tp(B);
-    for (int b = 0; b < B; ++b) {
-        const int64_t v = lengths ? lengths[b] : T;
-        if (v < 16 || v > T || v % 16 != 0)
-            return fail(h, DSD_EINVAL, "%s: frame count %lld of item %d is not a multiple of 16 in [16, T]", who, (long long)v, b);
-        Tp[b] = (int)v;
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    HnsepState& S = *h->hs;
-    const int C = S.cfg.is_mono ? 1 : 2;
-    hipStream_t st = (hipStream_t)stream;
-    S.iw_host.clear();
-    HsUpload up{S.iw_host};
-    HsRun R;
-    size_t dT_off = 0;
-    hs_setup(R, h, up, Tp, st, dT_off);
-    const HsSrc xre = hs_src(spec, (long)s_stride_b, (long)s_stride_f, (long)s_stride_t, (long)s_stride_c, C);
-    const HsSrc xim = hs_src(spec + 1, (long)s_stride_b, (long)s_stride_f, (long)s_stride_t, (long)s_stride_c, C);
-    const HsView mv = hs_view(mask_out, (long)m_stride_b, (long)m_stride_f, (long)m_stride_t, (long)m_stride_c);
-    return hs_execute(R, S.iw_host, dT_off, who, [&]() { return hs_forward(R, xre, xim, mv, 1); });
-}
-
-int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
-                       int64_t wav_stride_c, const int64_t* lengths, float* harmonic_out, int64_t out_stride_b,
-                       int64_t out_stride_c, void* stream) {
-    const char* who = "dsd_hnsep_separate";
-    HS_RC(hs_check(h, who, true));
-    if (!wav || !harmonic_out || B < 1 || n_samples < 1 || wav_stride_c < 0 || out_stride_c < 0)
-        return fail(h, DSD_EINVAL, "%s: bad argument", who);
-    HnsepState& S = *h->hs;
-    const int N = S.cfg.n_fft, hop = S.cfg.hop_length, C = S.cfg.is_mono ? 1 : 2, nb = N / 2 + 1;
-    const bool repeat = C == 1 || wav_stride_c == 0;     // one clip on every channel: one STFT, copied to the channels
-    std::vector<int> Tp(B);
-    std::vector<int64_t> L(B), off0(B);
-    int64_t Lmax = 0;
-    for (int b = 0; b < B; ++b) {
-        L[b] = lengths ? lengths[b] : n_samples;
-        if (L[b] < 1 || L[b] > n_samples) return fail(h, DSD_EINVAL, "%s: length %lld of item %d out of [1, n_samples]", who, (long long)L[b], b);
-        if (L[b] >= ((int64_t)1 << 30)) return fail(h, DSD_EINVAL, "%s: clip too long", who);
-        const int64_t nf = L[b] / hop + 1, Tpad = (32 * (nf / 32 + 1) - 1) * hop - L[b], Tl_pad = Tpad / 2 / hop * hop;
-        Tp[b] = (int)(32 * (nf / 32 + 1));
-        off0[b] = N / 2 + Tl_pad;       // padded position of sample 0 in the iSTFT's frame space
-        Lmax = std::max(Lmax, L[b]);
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    const HsBasis* bs = hs_basis(h, N, 0, st);
-    if (!bs) return fail(h, DSD_ENOMEM, "%s: the DFT bases could not be placed on the device", who);
-    S.iw_host.clear();
-    HsUpload up{S.iw_host};
-    HsRun R;
-    size_t dT_off = 0;
-    hs_setup(R, h, up, Tp, st, dT_off);
-    std::vector<int> fw, iw;
-    for (int b = 0; b < B; ++b)
-        for (int t0 = 0; t0 < Tp[b]; t0 += HS_ROWS) {
-            for (int c = 0; c < (repeat ? 1 : C); ++c) fw.insert(fw.end(), {b, t0, (int)L[b], Tp[b], c, (int)off0[b]});
-            for (int c = 0; c < C; ++c) iw.insert(iw.end(), {b, t0, (int)L[b], Tp[b], c, 0});
-        }
-    const size_t fw_off = up.add(fw.data(), fw.size() * 4), iw_off = up.add(iw.data(), iw.size() * 4);
-    const size_t L_off = up.add(L.data(), B * 8), o_off = up.add(off0.data(), B * 8);
-    const int Tal = R.Tal;
-    return hs_execute(R, S.iw_host, dT_off, who, [&]() -> int {
-        HsT spec, mask;
-        spec.F = mask.F = nb;
-        spec.T = mask.T = Tal;
-        spec.C = mask.C = 2 * C;
-        spec.p = R.alloc((size_t)B * spec.bs());
-        mask.p = R.alloc((size_t)B * mask.bs());
-        float* frames = R.alloc((size_t)B * C * Tal * N);
-        if (!R.dry) {
-            HsDftP p;
-            memset(&p, 0, sizeof(p));
-            p.basis = bs->fwd;
-            p.Kpad = bs->fKpad;
-            p.K = N;
-            p.N = N;
-            p.nb = nb;
-            p.inv = 0;
-            p.wav = wav;
-            p.wav_sb = (long)wav_stride_b;
-            p.wav_sc = repeat ? 0 : (long)wav_stride_c;
-            p.H = hop;
-            p.reflect = 0;
-            p.out = spec.p;
-            p.o_sb = spec.bs();
-            p.o_sf = (long)Tal * 2 * C;
-            p.o_st = 2 * C;
-            p.o_cre = 0;
-            p.o_cim = C;
-            p.nrep = repeat ? C : 1;
-            p.work = (const int*)(R.iw + fw_off);
-            HS_LAUNCH(launch_hs_dft(p, (int)(fw.size() / 6), bs->fRpad / HS_ROWS, st), "hnsep stft");
-        }
-        HS_RC(hs_forward(R, spec.src(0, C), spec.src(C, C), mask.view(), C));
-        if (R.dry) return DSD_OK;
-        HsDftP p;
-        memset(&p, 0, sizeof(p));
-        p.basis = bs->inv;
-        p.Kpad = bs->iKpad;
-        p.K = 2 * nb;
-        p.N = N;
-        p.nb = nb;
-        p.inv = 1;
-        p.spec = spec.p;
-        p.s_sb = spec.bs();
-        p.s_sf = (long)Tal * 2 * C;
-        p.s_st = 2 * C;
-        p.s_cre = 0;
-        p.s_cim = C;
-        p.mask = mask.p;
-        p.m_sb = mask.bs();
-        p.m_sf = (long)Tal * 2 * C;
-        p.m_st = 2 * C;
-        p.m_cim = C;
-        p.mask_F = nb;
-        p.out = frames;
-        p.o_sb = (long)Tal * N;
-        p.nch = C;
-        p.work = (const int*)(R.iw + iw_off);
-        HS_LAUNCH(launch_hs_dft(p, (int)(iw.size() / 6), bs->iRpad / HS_ROWS, st), "hnsep istft");
-        HsOlaP op;
-        op.frames = frames;
-        op.f_sb = (long)Tal * N;
-        op.win = bs->win;
-        op.N = N;
-        op.H = hop;
-        op.nch = C;
-        op.T = R.dT;
-        op.len = (const long*)(R.iw + L_off);
-        op.off0 = (const long*)(R.iw + o_off);
-        op.out = harmonic_out;
-        op.o_sb = (long)out_stride_b;
-        op.o_sc = C == 1 ? 0 : (long)out_stride_c;
-        HS_LAUNCH(launch_hs_ola(op, B, (long)Lmax, st), "hnsep overlap-add");
-        return DSD_OK;
-    });
-}
-
-int dsd_base_harmonic(dsd_handle* h, const float* harmonic, int32_t B, int64_t n_samples, int64_t stride_b,
-                      const int64_t* lengths, const float* f0, int64_t f0_stride_b, const int64_t* f0_lengths,
-                      int32_t sample_rate, int32_t hop_size, int32_t win_size, float* out, int64_t out_stride_b,
-                      void* stream) {
-    const char* who = "dsd_base_harmonic";
-    HS_RC(hs_check(h, who, false));
-    if (!harmonic || !f0 || !f0_lengths || !out || B < 1 || n_samples < 1 || sample_rate < 1 || win_size < 64 ||
-        win_size > 4096 || win_size % 32 != 0 || hop_size < 1 || hop_size > win_size / 2)
-        return fail(h, DSD_EINVAL, "%s: bad argument (win_size must be a multiple of 32 in [64, 4096], 1 <= hop_size <= "
-                    "win_size / 2: past that the Nuttall window's square sum reaches 0, where torch.istft raises)", who);
-    HnsepState& S = *h->hs;
-    const int N = win_size, nb = N / 2 + 1;
-    std::vector<int> Tp(B), f0n(B);
-    std::vector<int64_t> L(B), off0(B, N / 2);
-    int64_t Lmax = 0;
-    int Tal = 0;
-    for (int b = 0; b < B; ++b) {
-        L[b] = lengths ? lengths[b] : n_samples;
-        if (L[b] <= N / 2 || L[b] > n_samples || L[b] >= ((int64_t)1 << 30))
-            return fail(h, DSD_EINVAL, "%s: length %lld of item %d must exceed win_size / 2 (torch's reflect pad)", who, (long long)L[b], b);
-        Tp[b] = (int)(L[b] / hop_size + 1);
-        if (f0_lengths[b] < 0) return fail(h, DSD_EINVAL, "%s: negative f0 length", who);
-        f0n[b] = (int)std::min<int64_t>(f0_lengths[b], Tp[b]);
-        Lmax = std::max(Lmax, L[b]);
-        Tal = std::max(Tal, Tp[b]);
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    const HsBasis* bs = hs_basis(h, N, 1, st);
-    if (!bs) return fail(h, DSD_ENOMEM, "%s: the DFT bases could not be placed on the device", who);
-    S.iw_host.clear();
-    HsUpload up{S.iw_host};
-    std::vector<int> fw, iw;
-    for (int b = 0; b < B; ++b)
-        for (int t0 = 0; t0 < Tp[b]; t0 += HS_ROWS) {
-            fw.insert(fw.end(), {b, t0, (int)L[b], Tp[b], 0, N / 2});
-            iw.insert(iw.end(), {b, t0, (int)L[b], Tp[b], 0, 0});
-        }
-    const size_t T_off = up.add(Tp.data(), B * 4), f0n_off = up.add(f0n.data(), B * 4);
-    const size_t fw_off = up.add(fw.data(), fw.size() * 4), iw_off = up.add(iw.data(), iw.size() * 4);
-    const size_t L_off = up.add(L.data(), B * 8), o_off = up.add(off0.data(), B * 8);
-    const size_t need = (size_t)B * nb * Tal * 2 + (size_t)B * Tal * N;
-    HS_RC(rmvpe_reserve(h, S.ws, S.ws_cap, need, who));
-    char* iws = (char*)S.iws;
-    HS_RC(rmvpe_reserve(h, iws, S.iws_cap, up.buf.size(), who));
-    S.iws = iws;
-    HIP_OK(h, hipMemcpyAsync(S.iws, S.iw_host.data(), S.iw_host.size(), hipMemcpyHostToDevice, st));
-    float *spec = S.ws, *frames = S.ws + (size_t)B * nb * Tal * 2;
-    HsDftP p;
-    memset(&p, 0, sizeof(p));
-    p.basis = bs->fwd;
-    p.Kpad = bs->fKpad;
-    p.K = N;
-    p.N = N;
-    p.nb = nb;
-    p.wav = harmonic;
-    p.wav_sb = (long)stride_b;
-    p.H = hop_size;
-    p.reflect = 1;
-    p.out = spec;
-    p.o_sb = (long)nb * Tal * 2;
-    p.o_sf = (long)Tal * 2;
-    p.o_st = 2;
-    p.o_cre = 0;
-    p.o_cim = 1;
-    p.nrep = 1;
-    p.work = (const int*)(iws + fw_off);
-    HS_LAUNCH(launch_hs_dft(p, (int)(fw.size() / 6), bs->fRpad / HS_ROWS, st), "base harmonic stft");
-    HsDftP q;
-    memset(&q, 0, sizeof(q));
-    q.basis = bs->inv;
-    q.Kpad = bs->iKpad;
-    q.K = 2 * nb;
-    q.N = N;
-    q.nb = nb;
-    q.inv = 1;
-    q.spec = spec;
-    q.s_sb = (long)nb * Tal * 2;
-    q.s_sf = (long)Tal * 2;
-    q.s_st = 2;
-    q.s_cre = 0;
-    q.s_cim = 1;
-    q.f0 = f0;
-    q.f0_sb = (long)f0_stride_b;
-    q.f0_len = (const int*)(iws + f0n_off);
-    q.sr = (float)sample_rate;
-    q.half_width = 3.5f;
-    q.out = frames;
-    q.o_sb = (long)Tal * N;
-    q.nch = 1;
-    q.work = (const int*)(iws + iw_off);
-    HS_LAUNCH(launch_hs_dft(q, (int)(iw.size() / 6), bs->iRpad / HS_ROWS, st), "base harmonic istft");
-    HsOlaP op;
-    op.frames = frames;
-    op.f_sb = (long)Tal * N;
-    op.win = bs->win;
-    op.N = N;
-    op.H = hop_size;
-    op.nch = 1;
-    op.T = (const int*)(iws + T_off);
-    op.len = (const long*)(iws + L_off);
-    op.off0 = (const long*)(iws + o_off);
-    op.out = out;
-    op.o_sb = (long)out_stride_b;
-    op.o_sc = 0;
-    HS_LAUNCH(launch_hs_ola(op, B, (long)Lmax, st), "base harmonic overlap-add");
-    return DSD_OK;
-}
-
-int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, const float* base, int32_t B,
-                        int64_t stride_b, const int64_t* lengths, int32_t hop_size, int32_t win_size, const int64_t* frames,
-                        int32_t tension_domain, int32_t energy_db, float* energy, float* breathiness, float* voicing,
-                        float* tension, int64_t out_stride_b, void* stream) {
-    const char* who = "dsd_variance_curves";
-    HS_RC(hs_check(h, who, false));
-    if (B < 1 || !lengths || !frames || hop_size < 1 || win_size < 1 || tension_domain < 0 || tension_domain > 2)
-        return fail(h, DSD_EINVAL, "%s: bad argument", who);
-    if ((energy && !wav) || (breathiness && (!wav || !harmonic)) || (voicing && !harmonic) || (tension && (!harmonic || !base)))
-        return fail(h, DSD_EINVAL, "%s: a requested curve is missing its input signal", who);
-    HnsepState& S = *h->hs;
-    std::vector<int> nfr(B), len(B);
-    std::vector<int64_t> L(B);
-    int Tmax = 1;
-    for (int b = 0; b < B; ++b) {
-        L[b] = lengths[b];
-        if (L[b] < 1 || L[b] >= ((int64_t)1 << 30) || frames[b] < 0 || frames[b] >= ((int64_t)1 << 24))
-            return fail(h, DSD_EINVAL, "%s: bad length of item %d", who, b);
-        const int64_t Lp = L[b] + 2 * (win_size / 2);
-        nfr[b] = Lp < win_size ? 0 : (int)(1 + (Lp - win_size) / hop_size);     // librosa.util.frame
-        len[b] = (int)frames[b];
-        Tmax = std::max(Tmax, nfr[b]);
-    }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    S.iw_host.clear();
-    HsUpload up{S.iw_host};
-    const size_t n_off = up.add(nfr.data(), B * 4), l_off = up.add(len.data(), B * 4), L_off = up.add(L.data(), B * 8);
-    HS_RC(rmvpe_reserve(h, S.ws, S.ws_cap, (size_t)4 * B * Tmax, who));
-    char* iws = (char*)S.iws;
-    HS_RC(rmvpe_reserve(h, iws, S.iws_cap, up.buf.size(), who));
-    S.iws = iws;
-    HIP_OK(h, hipMemcpyAsync(S.iws, S.iw_host.data(), S.iw_host.size(), hipMemcpyHostToDevice, st));
-    HsRmsP rp;
-    rp.wav = (energy || breathiness) ? wav : nullptr;
-    rp.harm = (breathiness || voicing || tension) ? harmonic : nullptr;
-    rp.base = tension ? base : nullptr;
-    rp.sb = (long)stride_b;
-    rp.len = (const long*)(iws + L_off);
-    rp.nfr = (const int*)(iws + n_off);
-    rp.hop = hop_size;
-    rp.win = win_size;
-    rp.B = B;
-    rp.Tmax = Tmax;
-    rp.rms = S.ws;
-    HS_LAUNCH(launch_hs_rms(rp, st), "variance rms");
-    HsCurvesP cp;
-    cp.rms = S.ws;
-    cp.nfr = rp.nfr;
-    cp.length = (const int*)(iws + l_off);
-    cp.B = B;
-    cp.Tmax = Tmax;
-    cp.domain = tension_domain;
-    cp.db = energy_db ? 1 : 0;
-    cp.out[0] = energy;
-    cp.out[1] = breathiness;
-    cp.out[2] = voicing;
-    cp.out[3] = tension;
-    cp.o_sb = (long)out_stride_b;
-    HS_LAUNCH(launch_hs_curves(cp, st), "variance curves");
     return DSD_OK;
 }
 

@@ -1,0 +1,305 @@
+// Private host-side header of libdsdenoise: what api.hip and the analysis families' host sources (mel_api.hip,
+// rmvpe_api.hip, hnsep_api.hip) share - the handle, error reporting, device-memory ownership, weight loading.  No kernels.
+#pragma once
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <functional>
+#include <map>
+#include <numeric>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/dsdenoise.h"
+#include "dsd_internal.h"
+
+using namespace dsd;
+
+struct dsd_handle;
+
+namespace dsd {
+
+// records the message on the handle (h == nullptr: for dsd_last_error(NULL), as the create functions do) and returns `code`
+int fail(dsd_handle* h, int code, const char* fmt, ...);
+
+#define HIP_OK(h, expr)                                                                          \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) return fail(h, DSD_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+
+// Device memory that its holder owns and only ever grows: reserve(n) keeps the allocation while n elements fit, otherwise
+// frees it and allocates anew (the contents are not carried over, and the address changes: whoever gave the old one to a
+// captured graph destroys that graph).  Move-only, so a std::vector of holders keeps the device addresses when it grows.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;         // elements
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    int reserve(dsd_handle* h, size_t n, const char* who) {
+        if (n <= cap) return DSD_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return fail(h, DSD_ENOMEM, "%s: hipMalloc of %zu bytes failed", who, n * sizeof(T));
+        cap = n;
+        return DSD_OK;
+    }
+};
+
+struct HostTensor {
+    std::vector<int64_t> shape;
+    std::vector<float> data;
+};
+
+// one packed GEMM operand set on the device
+struct PackedGemm {
+    size_t a_off = 0;     // float offset into the weight blob
+    size_t bias_off = 0;  // float offset, or SIZE_MAX
+    int M = 0;            // real rows
+    int K = 0;            // padded input channels
+    int Kreal = 0;
+    int taps = 1;
+    int pairC = 0;        // > 0: paired packing with this many pairs
+};
+
+// weights of a few-channel convolution in tconv.hip's B-fragment order
+struct PackedTConv {
+    size_t w_off = SIZE_MAX, b_off = 0;
+    int ci = 0, co = 0, co_real = 0, taps = 0;
+    bool valid() const { return w_off != SIZE_MAX; }
+};
+
+struct GraphEntry {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
+
+// dsd_vocode_ragged: one rate of the generator (stage i = after i upsamplings), all pointers into dsd_handle::vr_dev
+struct VocRagStage {
+    int T = 0;                          // padded length of the batch at this rate
+    const int* lens = nullptr;          // [B] item lengths at this rate
+    long valid = 0;                     // their sum
+    const int* cg[3] = {};              // GEMM column groups (item, frame tile) with valid frames, 16 / 32 / 64-frame tiles
+    int ncg[3] = {};
+    const int* tc = nullptr;            // tconv.hip's 256-frame tiles with valid frames
+    int ntc = 0;
+};
+
+// dsd_mel_analyze: per handle, the filterbank on the device and the DFT bases of the (N', W') sizes met so far
+struct MelBasis {
+    int N = 0, W = 0;
+    DevBuf<float> dev;
+};
+struct MelState {
+    dsd_mel_config cfg;
+    int k_lo = 0, k_hi = -1;            // the bins any filter reads (k_hi < k_lo: none)
+    std::vector<int> range_host;        // [M][2] bins [lo, hi) relative to k_lo
+    DevBuf<int> range, woff;
+    DevBuf<float> fw;                   // packed non-zero runs
+    std::vector<MelBasis> bases;        // most recent last
+    std::vector<int> work_host;
+    DevBuf<int> work;
+    DevBuf<float> mags;
+};
+
+
+// The STFT geometry of one (keyshift, speed) (nvSTFT.py:52-66): np.round is round-half-even, as nearbyint
+struct MelGeom {
+    int N, W, H, off, padL, padR;
+    bool rescale;
+};
+
+}  // namespace dsd
+
+struct RmvpeState;
+struct HnsepState;
+
+struct dsd_handle {
+    dsd_config cfg;
+    std::string err;
+    std::map<std::string, HostTensor> raw;
+    // WaveNet with a channel count that is not a multiple of 32: cfg.num_channels is the count the kernels run with
+    // (rounded up), c_user the caller's; `padded` holds the zero-extended tensors build_packed reads (pad_wavenet_weights)
+    std::map<std::string, HostTensor> padded;
+    int c_user = 0;
+    // wn_edge.hip: the state buffer whose input projection the previous evaluation's edge kernel already wrote into xh
+    const float* edge_xh_src = nullptr;
+    bool finalized = false;
+    PathOpts opts;                  // path switches: the snapshot of the last entry point that launches kernels (read_path_opts)
+
+    // packed weights
+    std::vector<float> blob_host;
+    DevBuf<float> blob;
+    PackedGemm g_inproj, g_emb0, g_emb1, g_dproj, g_cp, g_tail1, g_out;
+    std::vector<PackedGemm> g_conv, g_outp;          // WaveNet per layer
+    // split-bf16 precision mode (wn_layer_x3.hip): 0 = fp32 (default), 1 = bf16x3 where a kernel exists; the layers' weight
+    // streams (float offsets into the blob; empty: not built)
+    int precision = 0;
+    std::vector<size_t> x3_conv, x3_out;
+    int cus = 256;                  // compute units of the device (hipDeviceProp_t::multiProcessorCount): one fused round = `cus` tiles
+    std::vector<PackedGemm> g_pw1, g_pw2;            // LYNXNet per layer
+    std::vector<size_t> dw_w, dw_b, dw_prelu;        // LYNXNet / ConvNeXt depthwise params (float offsets)
+    PackedGemm g_ain, g_aout;                        // ConvNeXt aux decoder: dense k-tap in/out convs
+    // NSF-HiFiGAN generator
+    dsd_vocoder_config vcfg;
+    PackedGemm v_pre, v_post;
+    std::vector<PackedGemm> v_ups;                   // transposed convs as phase-row GEMMs
+    std::vector<std::vector<PackedGemm>> v_res;      // [stage * n_kernels + j][2 * n_dil (ResBlock1) or n_dil]
+    std::vector<std::vector<PackedTConv>> v_rest;    // same indexing: the 16- / 32-channel stages (tconv.hip)
+    PackedTConv v_postt;
+    std::vector<size_t> v_nw, v_nb;                  // noise conv weights / biases
+    std::vector<int> v_uptaps;
+    size_t v_linw = 0, v_linb = 0;
+    int vB = 0, vT = 0;
+    DevBuf<float> v_arena;
+    std::vector<float*> v_buf;                       // per stage: x, t1, r, acc
+    float *v_mel = nullptr, *v_pre_out = nullptr, *v_har = nullptr, *v_phase = nullptr, *v_wav = nullptr;
+    // ragged vocoder batches: per-rate lengths and valid-tile lists (one device block, rebuilt when B, T or the lengths change)
+    std::vector<int> vr_key, vr_host;
+    DevBuf<int> vr_dev;
+    std::vector<VocRagStage> vr_st;
+    // mel analysis (dsd_mel_create): the config, the filterbank's packed non-zero runs and the device blocks of dsd_mel_analyze
+    MelState* mel = nullptr;
+    // RMVPE pitch extraction (dsd_rmvpe_create): config, packed weights, its own mel front end, workspace
+    RmvpeState* pe = nullptr;
+    // VR harmonic-noise separation (dsd_hnsep_create): config, packed weights, DFT bases, workspace
+    HnsepState* hs = nullptr;
+    // FastSpeech2 acoustic encoder
+    dsd_encoder_config ecfg;
+    std::vector<PackedGemm> g_qkv, g_oproj, g_ffn1, g_ffn2;
+    std::vector<size_t> e_ln1g, e_ln1b, e_ln2g, e_ln2b;
+    size_t e_lng = 0, e_lnb = 0, e_txt = 0, e_lang = SIZE_MAX, e_durw = 0, e_durb = 0, e_freqs = 0, e_spk = SIZE_MAX;
+    size_t e_linw[7], e_linb[7];                     // pitch, energy, breathiness, voicing, tension, key shift, speed
+    int eL = 0, eLs = 0, eB = 0, e_pos = 0;
+    int e_ffn_act = DSD_FFN_GELU;                    // TransformerFFNLayer's activation (DSD_FFN_*)
+    float *e_x = nullptr, *e_y = nullptr, *e_qkv = nullptr, *e_mid = nullptr, *e_nonpad = nullptr;
+    int* e_dur = nullptr;
+    DevBuf<float> e_arena;
+    // token encoder (variance model): FastSpeech2Encoder + out_proj / DurationPredictor
+    dsd_token_encoder_config tcfg;
+    PackedGemm g_tout;
+    std::vector<PackedGemm> g_dconv;
+    std::vector<size_t> d_lng, d_lnb;
+    size_t d_linw = 0, d_linb = 0;
+    float *d_a = nullptr, *d_b = nullptr, *d_in = nullptr;
+    int dC = 0;
+    size_t freqs_off = 0;
+    int emb_act = ACT_MISH;
+
+    // workspace for (B, T)
+    int B = 0, T = 0, Ts = 0;
+    DevBuf<float> arena;
+    size_t arena_floats = 0;
+    float *cond_i = nullptr, *cp = nullptr, *xh = nullptr, *z = nullptr, *skip = nullptr, *hbuf = nullptr;
+    float *xin = nullptr, *ubuf = nullptr, *vbuf = nullptr, *stats = nullptr, *lnpart = nullptr;
+    float *io_in = nullptr, *io_out = nullptr;
+    bool cond_ready = false;
+    // ragged batches (dsd_set_lengths): per-item valid lengths on the device, nullptr = dense
+    DevBuf<int> lens_dev;
+    std::vector<int> lens_host;
+    // ... and, per tile width (16 / 32 / 64 frames), the list of column groups (item, frame tile) with valid frames
+    DevBuf<int> cg_dev[3];
+    int cg_n[3] = {0, 0, 0};
+    std::vector<int> cg_host[3];
+    int cg_T = -1;                  // the T the lists were built for (-1: stale)
+    bool use_cg = false;            // set around the launch sequences that may skip padded tiles
+    // sampler state buffers
+    DevBuf<float> state;
+    int state_nbufs = 0;
+    size_t state_buf_floats = 0;
+    // step-embedding tables (columns = steps or batch items)
+    DevBuf<float> emb_arena;
+    int emb_cols = 0, Ns = 0;
+    float *t_dev = nullptr, *E = nullptr, *Hd = nullptr, *E2 = nullptr, *D = nullptr;
+    float* Dt = nullptr;            // D transposed: [step column][L * C rows] - what the layer kernels read their FiLM vectors from
+    std::vector<float> t_host;
+
+    std::map<std::string, GraphEntry> graphs;
+    std::set<std::string> graph_seen;      // programs run once eagerly: a graph is captured when one comes back
+
+    // timing of the layer kernels (dsd_kernel_timing): per kernel CLASS - a launch site of run_backbone and the variant of
+    // it that ran (tile width, halo, segment of a mixed plan) - every timing_stride-th launch carries an event pair
+    struct TimedClass {
+        int key = 0;
+        std::string name;           // the instantiation, as rocprofv3 prints it (filled in by the launcher that took the slot)
+        double flops = 0, bytes = 0;    // algorithmic work of one launch (valid frames)
+        long launches = 0;          // all launches of the class since timing was switched on
+        std::vector<size_t> evs;    // indices into ev_pool
+    };
+    bool timing = false;
+    std::vector<TimedClass> tclasses;
+    long timing_evals = 0;         // backbone evaluations since timing was switched on
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
+    size_t ev_used = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> cal_pool;   // back-to-back pairs: the cost of the bracket itself
+    size_t cal_used = 0;
+    int timing_stride = 7;         // coprime with the layer count: every layer is sampled over a pass
+};
+
+namespace dsd {
+
+inline bool is_wavenet(const dsd_handle* h) { return h->cfg.backbone == DSD_BACKBONE_WAVENET; }
+inline bool is_aux(const dsd_handle* h) { return h->cfg.backbone == DSD_AUX_CONVNEXT; }
+inline bool is_enc(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_ACOUSTIC; }
+inline bool is_tok(const dsd_handle* h) { return h->cfg.backbone == DSD_ENC_FS2_TOKENS; }
+inline bool is_voc(const dsd_handle* h) { return h->cfg.backbone == DSD_VOC_NSF_HIFIGAN; }
+inline bool is_mel(const dsd_handle* h) { return h->cfg.backbone == DSD_MEL_ANALYSIS; }
+inline bool is_pe(const dsd_handle* h) { return h->cfg.backbone == DSD_PE_RMVPE; }
+inline bool is_hs(const dsd_handle* h) { return h->cfg.backbone == DSD_HNSEP_VR; }
+
+// a state dict layout: the names a handle accepts, with their shapes
+using ParamList = std::vector<std::pair<std::string, std::vector<int64_t>>>;
+
+// every create function and dsd_cond_assemble: the device must exist before anything is placed on it
+int select_device(const char* who, int device, bool say_range = true);
+// dsd_load_weight behind the caller's own name rules: looks `name` up in `expected` (nullptr: the caller has checked the
+// shape itself), compares the shape and copies the host or device data into h->raw
+int store_weight(dsd_handle* h, const ParamList* expected, const char* name, const float* data, const int64_t* shape,
+                 int32_t ndim, int32_t on_device);
+// dsd_finalize_weights: DSD_ESTATE naming every expected key that was not loaded
+int check_missing(dsd_handle* h, const ParamList& expected);
+// ... and its upload of the packed weights: a fresh allocation of host.size() + tail floats, the tail zeroed
+int upload_blob(dsd_handle* h, DevBuf<float>& dev, const std::vector<float>& host, size_t tail);
+// eval-mode BatchNorm (eps 1e-5) at state-dict prefix p as scale / shift, in double
+void bn_scale_shift(const dsd_handle* h, const std::string& p, int C, std::vector<double>& sc, std::vector<double>& sh);
+inline bool ends_with(const std::string& s, const char* suffix) {
+    const size_t n = strlen(suffix);
+    return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// mel analysis (mel_api.hip); RMVPE's front end runs it with a filterbank and geometry of its own
+void mel_filterbank_host(const dsd_mel_config& c, std::vector<float>& w, bool htk = false);
+bool mel_geometry(const dsd_mel_config& c, double keyshift, double speed, MelGeom& g);
+int64_t mel_frames(const MelGeom& g, int64_t L);
+int mel_state_build(MelState& mst, const dsd_mel_config* cfg, const std::vector<float>& w, const char* who);
+int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
+            const int64_t* lengths, float* mel_out, int64_t stride_b, int64_t stride_m, int64_t stride_t, void* stream,
+            const char* who);
+void mel_state_free(MelState* m);
+// what dsd_load_weight, dsd_finalize_weights and dsd_destroy hand on to the family of the handle (rmvpe_api.hip, hnsep_api.hip)
+int rmvpe_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim, int32_t on_device);
+int rmvpe_finalize(dsd_handle* h);
+void rmvpe_free(RmvpeState* r);
+int hnsep_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim, int32_t on_device);
+int hnsep_finalize(dsd_handle* h);
+void hnsep_free(HnsepState* s);
+
+}  // namespace dsd

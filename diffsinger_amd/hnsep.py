@@ -226,12 +226,7 @@ class HnSep:
         if rc != 0:
             raise _lib.NativeLibraryError(f"dsd_hnsep_create failed ({rc}): {_lib.lib().dsd_last_error(None).decode()}")
         self._h = hp
-        for name, v in sd.items():
-            a = np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v), dtype=np.float32)
-            shape = (C.c_int64 * max(1, a.ndim))(*(a.shape or (1,)))
-            _lib.check(hp, _lib.lib().dsd_load_weight(hp, name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), shape,
-                                                      a.ndim, 0), f"dsd_load_weight({name})")
-        _lib.check(hp, _lib.lib().dsd_finalize_weights(hp), "dsd_finalize_weights")
+        _lib.load_state_dict(hp, sd)
         self.is_mono = bool(c["is_mono"])
 
     def __del__(self):
