@@ -23,7 +23,7 @@ AUX_CONVNEXT = 2
 ACT_IDS = {"PReLU": 0, "SiLU": 1, "ReLU": 2}
 
 EXPORTS = [
-    "dsd_api_version", "dsd_create", "dsd_destroy", "dsd_last_error", "dsd_load_weight",
+    "dsd_api_version", "dsd_create", "dsd_create_any_width", "dsd_destroy", "dsd_last_error", "dsd_load_weight",
     "dsd_finalize_weights", "dsd_prepare_cond", "dsd_denoise", "dsd_sample", "dsd_get_stats",
     "dsd_kernel_timing", "dsd_kernel_timing_read", "dsd_kernel_timing_classes", "dsd_set_precision", "dsd_aux_decode", "dsd_encoder_create", "dsd_encode", "dsd_vocoder_create", "dsd_vocode", "dsd_vocode_ragged",
     "dsd_token_encoder_create", "dsd_token_encode", "dsd_predict_dur", "dsd_cond_assemble", "dsd_set_lengths",
@@ -154,6 +154,7 @@ def _load():
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     lib.dsd_api_version.restype = C.c_int
     lib.dsd_create.argtypes = [C.POINTER(DsdConfig), C.POINTER(vp)]
+    lib.dsd_create_any_width.argtypes = [C.POINTER(DsdConfig), C.POINTER(vp)]
     lib.dsd_destroy.argtypes = [vp]
     lib.dsd_destroy.restype = None
     lib.dsd_last_error.argtypes = [vp]

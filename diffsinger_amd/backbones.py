@@ -88,10 +88,11 @@ class _NativeBackbone(nn.Module):
             hp = C.c_void_p()
             create = (lib.dsd_encoder_create if isinstance(cfg, _lib.DsdEncoderConfig) else
                       lib.dsd_token_encoder_create if isinstance(cfg, _lib.DsdTokenEncoderConfig) else
-                      lib.dsd_vocoder_create if isinstance(cfg, _lib.DsdVocoderConfig) else lib.dsd_create)
+                      lib.dsd_vocoder_create if isinstance(cfg, _lib.DsdVocoderConfig) else
+                      lib.dsd_create_any_width)     # every width the reference builds (the network runs at the next multiple of 32)
             rc = create(C.byref(cfg), C.byref(hp))
             if rc != 0:
-                raise _lib.NativeLibraryError(f"dsd_create failed ({rc}): {lib.dsd_last_error(None).decode()}")
+                raise _lib.NativeLibraryError(f"creating the native handle failed ({rc}): {lib.dsd_last_error(None).decode()}")
             self._handle, self._handle_device = hp, idx
             self._weights_dirty = True
         if self._weights_dirty:

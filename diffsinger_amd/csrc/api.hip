@@ -186,6 +186,8 @@ inline int check_lens(dsd_handle* h, const char* who, int B, int T, hipStream_t 
 }
 
 inline int C_of(const dsd_handle* h) { return h->cfg.num_channels; }
+// the caller's channel count, where the kernels run on more (pad_weights): what a LayerNorm over the channels counts
+inline int true_channels(const dsd_handle* h) { return h->c_user ? h->c_user : h->cfg.num_channels; }
 inline int FM_of(const dsd_handle* h) { return h->cfg.in_dims * h->cfg.n_feats; }
 inline int L_of(const dsd_handle* h) { return h->cfg.num_layers; }
 inline int inner_of(const dsd_handle* h) { return h->cfg.num_channels * h->cfg.expansion_factor; }
@@ -480,20 +482,36 @@ bool has_W(const dsd_handle* h, const std::string& n) { return h->padded.count(n
 // the real channels see only zero contributions from them.  Rows of the [2C] tensors are two halves (gate | filter,
 // residual | skip): each half is extended on its own.  SinusoidalPosEmb keeps the frequencies of the REAL C
 // (common_layers.py:275-276) in the first C/2 of Cp/2 slots; mlp.0's columns follow its [sin | cos] halves.
-void pad_wavenet_weights(dsd_handle* h) {
-    h->padded.clear();
-    const int C = h->c_user, Cp = h->cfg.num_channels, L = h->cfg.num_layers;
-    if (!is_wavenet(h) || C == 0 || C == Cp) return;
-    enum Map { SAME, PLAIN, HALVES, QUAD, SINCOS };
-    auto size_of = [&](Map m, int n) { return m == SAME ? n : m == PLAIN ? Cp : m == HALVES ? 2 * Cp : m == QUAD ? 4 * Cp : Cp; };
-    auto map_of = [&](Map m, int i) {
+//
+// LYNXNet and the ConvNeXt aux decoder (dsd_create_any_width) the same way, with inner = C * expansion_factor running as
+// Cp * expansion_factor: gelu(0) = 0 after the input projection, the SwiGLU product 0 * silu(0) = 0 (pw1's [2 inner] rows are the
+// halves out | gate), a zero depthwise row with zero bias gives act(0) = 0 for PReLU / SiLU / ReLU / GELU, pw2's extra rows and
+// the residual 0 + 0 stay 0, and every consumer of a LayerNorm output has zero columns there.  What zero padding does NOT keep
+// is the LayerNorm itself: its mean and variance run over the C real rows (true_channels), which every kernel that forms
+// or merges the statistics is told (GemmP::ln_rows, LxLayerP::ln_rows, launch_ln_merge, launch_lynx_pre).
+struct ChannelPad {
+    enum Map { SAME, PLAIN, HALVES, QUAD, SINCOS, INNER, INNER2 };
+    dsd_handle* h;
+    int C, Cp, I, Ip;       // channels and LYNXNet's inner channels: the caller's, the kernels'
+    int size_of(Map m, int n) const {
+        switch (m) {
+            case SAME: return n;
+            case HALVES: return 2 * Cp;
+            case QUAD: return 4 * Cp;
+            case INNER: return Ip;
+            case INNER2: return 2 * Ip;
+            default: return Cp;
+        }
+    }
+    int map_of(Map m, int i) const {
         switch (m) {
             case HALVES: return i < C ? i : Cp + (i - C);
             case SINCOS: return i < C / 2 ? i : Cp / 2 + (i - C / 2);
+            case INNER2: return i < I ? i : Ip + (i - I);
             default: return i;
         }
-    };
-    auto pad = [&](const std::string& name, Map rm, Map cm) {
+    }
+    void pad(const std::string& name, Map rm, Map cm) const {
         const HostTensor& t = h->raw.at(name);
         const int rows = (int)t.shape[0], cols = t.shape.size() > 1 ? (int)t.shape[1] : 1;
         const int taps = t.shape.size() > 2 ? (int)t.shape[2] : 1;
@@ -508,39 +526,110 @@ void pad_wavenet_weights(dsd_handle* h) {
                 for (int k = 0; k < taps; ++k)
                     o.data[((size_t)map_of(rm, r) * cp + map_of(cm, c)) * taps + k] = t.data[((size_t)r * cols + c) * taps + k];
         h->padded[name] = std::move(o);
-    };
-    pad("input_projection.weight", PLAIN, SAME);
-    pad("input_projection.bias", PLAIN, SAME);
-    pad("mlp.0.weight", QUAD, SINCOS);
-    pad("mlp.0.bias", QUAD, SAME);
-    pad("mlp.2.weight", PLAIN, QUAD);
-    pad("mlp.2.bias", PLAIN, SAME);
+    }
+    // SinusoidalPosEmb's table as [Cp / 2]: the real C's, then zeros (sin 0 = 0 and cos 0 = 1 meet zero columns)
+    void pad_freqs() const {
+        HostTensor f;
+        f.shape = {Cp / 2};
+        f.data.assign((size_t)Cp / 2, 0.f);
+        const int half = C / 2;
+        if (h->raw.count("diffusion_embedding.freqs")) {
+            const auto& src = h->raw.at("diffusion_embedding.freqs").data;
+            for (int i = 0; i < half; ++i) f.data[i] = src[i];
+        } else {
+            const float step = -(float)(log(10000.0) / (half - 1));
+            for (int i = 0; i < half; ++i) f.data[i] = expf((float)i * step);
+        }
+        h->padded["diffusion_embedding.freqs"] = std::move(f);
+    }
+};
+
+void pad_wavenet_weights(const ChannelPad& cp, int L) {
+    using P = ChannelPad;
+    cp.pad("input_projection.weight", P::PLAIN, P::SAME);
+    cp.pad("input_projection.bias", P::PLAIN, P::SAME);
+    cp.pad("mlp.0.weight", P::QUAD, P::SINCOS);
+    cp.pad("mlp.0.bias", P::QUAD, P::SAME);
+    cp.pad("mlp.2.weight", P::PLAIN, P::QUAD);
+    cp.pad("mlp.2.bias", P::PLAIN, P::SAME);
     for (int l = 0; l < L; ++l) {
         const std::string p = "residual_layers." + std::to_string(l) + ".";
-        pad(p + "dilated_conv.weight", HALVES, PLAIN);
-        pad(p + "dilated_conv.bias", HALVES, SAME);
-        pad(p + "diffusion_projection.weight", PLAIN, PLAIN);
-        pad(p + "diffusion_projection.bias", PLAIN, SAME);
-        pad(p + "conditioner_projection.weight", HALVES, SAME);
-        pad(p + "conditioner_projection.bias", HALVES, SAME);
-        pad(p + "output_projection.weight", HALVES, PLAIN);
-        pad(p + "output_projection.bias", HALVES, SAME);
+        cp.pad(p + "dilated_conv.weight", P::HALVES, P::PLAIN);
+        cp.pad(p + "dilated_conv.bias", P::HALVES, P::SAME);
+        cp.pad(p + "diffusion_projection.weight", P::PLAIN, P::PLAIN);
+        cp.pad(p + "diffusion_projection.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "conditioner_projection.weight", P::HALVES, P::SAME);
+        cp.pad(p + "conditioner_projection.bias", P::HALVES, P::SAME);
+        cp.pad(p + "output_projection.weight", P::HALVES, P::PLAIN);
+        cp.pad(p + "output_projection.bias", P::HALVES, P::SAME);
     }
-    pad("skip_projection.weight", PLAIN, PLAIN);
-    pad("skip_projection.bias", PLAIN, SAME);
-    pad("output_projection.weight", SAME, PLAIN);
-    HostTensor f;                               // [Cp / 2]: the real C's table, then zeros (sin 0 = 0 and cos 0 = 1 meet zero columns)
-    f.shape = {Cp / 2};
-    f.data.assign((size_t)Cp / 2, 0.f);
-    const int half = C / 2;
-    if (h->raw.count("diffusion_embedding.freqs")) {
-        const auto& src = h->raw.at("diffusion_embedding.freqs").data;
-        for (int i = 0; i < half; ++i) f.data[i] = src[i];
-    } else {
-        const float step = -(float)(log(10000.0) / (half - 1));
-        for (int i = 0; i < half; ++i) f.data[i] = expf((float)i * step);
+    cp.pad("skip_projection.weight", P::PLAIN, P::PLAIN);
+    cp.pad("skip_projection.bias", P::PLAIN, P::SAME);
+    cp.pad("output_projection.weight", P::SAME, P::PLAIN);
+    cp.pad_freqs();
+}
+
+// lynxnet.py:90-126; convmodule.net = [0] LayerNorm, [2] pw1 C -> 2 inner, [4] depthwise, [5] PReLU slopes, [6] pw2 inner -> C
+void pad_lynxnet_weights(const ChannelPad& cp, int L, bool prelu) {
+    using P = ChannelPad;
+    cp.pad("input_projection.weight", P::PLAIN, P::SAME);
+    cp.pad("input_projection.bias", P::PLAIN, P::SAME);
+    cp.pad("diffusion_embedding.1.weight", P::QUAD, P::SINCOS);
+    cp.pad("diffusion_embedding.1.bias", P::QUAD, P::SAME);
+    cp.pad("diffusion_embedding.3.weight", P::PLAIN, P::QUAD);
+    cp.pad("diffusion_embedding.3.bias", P::PLAIN, P::SAME);
+    for (int l = 0; l < L; ++l) {
+        const std::string p = "residual_layers." + std::to_string(l) + ".";
+        cp.pad(p + "diffusion_projection.weight", P::PLAIN, P::PLAIN);
+        cp.pad(p + "diffusion_projection.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "conditioner_projection.weight", P::PLAIN, P::SAME);
+        cp.pad(p + "conditioner_projection.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "convmodule.net.0.weight", P::PLAIN, P::SAME);
+        cp.pad(p + "convmodule.net.0.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "convmodule.net.2.weight", P::INNER2, P::PLAIN);
+        cp.pad(p + "convmodule.net.2.bias", P::INNER2, P::SAME);
+        cp.pad(p + "convmodule.net.4.weight", P::INNER, P::SAME);
+        cp.pad(p + "convmodule.net.4.bias", P::INNER, P::SAME);
+        if (prelu) cp.pad(p + "convmodule.net.5.weight", P::INNER, P::SAME);
+        cp.pad(p + "convmodule.net.6.weight", P::PLAIN, P::INNER);
+        cp.pad(p + "convmodule.net.6.bias", P::PLAIN, P::SAME);
     }
-    h->padded["diffusion_embedding.freqs"] = std::move(f);
+    cp.pad("norm.weight", P::PLAIN, P::SAME);
+    cp.pad("norm.bias", P::PLAIN, P::SAME);
+    cp.pad("output_projection.weight", P::SAME, P::PLAIN);
+    cp.pad_freqs();
+}
+
+// convnext.py:17-85
+void pad_convnext_weights(const ChannelPad& cp, int L) {
+    using P = ChannelPad;
+    cp.pad("inconv.weight", P::PLAIN, P::SAME);
+    cp.pad("inconv.bias", P::PLAIN, P::SAME);
+    for (int l = 0; l < L; ++l) {
+        const std::string p = "conv." + std::to_string(l) + ".";
+        cp.pad(p + "gamma", P::PLAIN, P::SAME);
+        cp.pad(p + "dwconv.weight", P::PLAIN, P::SAME);
+        cp.pad(p + "dwconv.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "norm.weight", P::PLAIN, P::SAME);
+        cp.pad(p + "norm.bias", P::PLAIN, P::SAME);
+        cp.pad(p + "pwconv1.weight", P::QUAD, P::PLAIN);
+        cp.pad(p + "pwconv1.bias", P::QUAD, P::SAME);
+        cp.pad(p + "pwconv2.weight", P::PLAIN, P::QUAD);
+        cp.pad(p + "pwconv2.bias", P::PLAIN, P::SAME);
+    }
+    cp.pad("outconv.weight", P::SAME, P::PLAIN);
+}
+
+// h->padded for a handle whose caller's channel count is not the kernels' (empty otherwise)
+void pad_weights(dsd_handle* h) {
+    h->padded.clear();
+    const int C = h->c_user, Cp = h->cfg.num_channels, L = h->cfg.num_layers;
+    if (C == 0 || C == Cp) return;
+    const int ef = is_wavenet(h) || is_aux(h) ? 1 : h->cfg.expansion_factor;
+    const ChannelPad cp{h, C, Cp, C * ef, Cp * ef};
+    if (is_wavenet(h)) pad_wavenet_weights(cp, L);
+    else if (is_aux(h)) pad_convnext_weights(cp, L);
+    else if (h->cfg.backbone == DSD_BACKBONE_LYNXNET) pad_lynxnet_weights(cp, L, h->cfg.activation == DSD_ACT_PRELU);
 }
 
 // ConvNeXt aux decoder (convnext.py:17-85).  LayerNorm affine folded into pwconv1, the layer scale gamma folded
@@ -861,6 +950,7 @@ size_t pack_x3(dsd_handle* h, int nrt, int nsteps, const std::function<int(int, 
 }
 
 int build_packed(dsd_handle* h) {
+    pad_weights(h);
     if (is_aux(h)) return build_packed_aux(h);
     if (is_enc(h)) return build_packed_enc(h);
     if (is_tok(h)) return build_packed_tok(h);
@@ -868,7 +958,6 @@ int build_packed(dsd_handle* h) {
     const dsd_config& c = h->cfg;
     const int C = c.num_channels, M = FM_of(h), H = c.hidden_size, L = c.num_layers;
     h->blob_host.clear();
-    pad_wavenet_weights(h);
     // frequency table of SinusoidalPosEmb (common_layers.py:275-276)
     h->freqs_off = blob_reserve(h, (size_t)C / 2);
     if (has_W(h, "diffusion_embedding.freqs")) {
@@ -1605,7 +1694,7 @@ void lynx_next(const dsd_handle* h, GemmP& p, int next, int film_col0, int film_
     const int C = C_of(h), L = L_of(h), Ts = h->Ts;
     p.out = h->xh; p.o_bstride = (long)C * Ts; p.o_rstride = Ts;
     p.out2 = next < L ? h->xin : nullptr;
-    p.lnpart = h->lnpart; p.lnpart_ts = Ts;
+    p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_rows = true_channels(h);
     p.strong = h->cfg.strong_cond;
     if (next < L) {
         p.cpn = h->cp + (long)next * C * Ts; p.cpn_bstride = (long)L * C * Ts; p.cpn_rstride = Ts;
@@ -1780,7 +1869,8 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     int rc;
     // LayerNorm statistics of the next GEMM's input: merged from the producer's per-tile partials by a small kernel
     // (merging inside the consuming GEMM's prologue was measured slower: every one of its ~1 k workgroups repeats it)
-    auto ln_merge = [&] { return launch_rc(h, launch_ln_merge(h->lnpart, ln_tiles, C, B, T, Ts, 1e-5f, h->stats, st), "LayerNorm merge"); };
+    // (over the caller's channels: the last tile's partials may count fewer rows than it holds, pad_weights)
+    auto ln_merge = [&] { return launch_rc(h, launch_ln_merge(h->lnpart, ln_tiles, true_channels(h), B, T, Ts, 1e-5f, h->stats, st), "LayerNorm merge"); };
     // algorithmic work per valid frame of the two pointwise GEMMs: pw1 C -> 2 inner (reads x_in, writes the
     // SwiGLU product), pw2 inner -> C (reads the depthwise conv's output, the residual stream and the next layer's hoisted
     // conditioner projection, writes x and x_in)
@@ -1809,7 +1899,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         if (ragged) { p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
         p.inv_nft = 1.0f / (float)std::max(1, ragged ? p.ncg : p.nft);
         p.strong = h->cfg.strong_cond;
-        p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles;
+        p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles; p.ln_rows = true_channels(h);
         p.lnpart_in = h->lnpart;        // (read by pw1 before pw2 of this layer replaces it with the next layer's partials)
         const int next = l + 1;
         p.xin_out = next < L ? h->xin : nullptr;
@@ -1918,39 +2008,51 @@ int dsd_api_version(void) { return DSD_API_VERSION; }
 
 const char* dsd_last_error(const dsd_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int dsd_create(const dsd_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_create: null argument");
+}  // extern "C"
+
+namespace {
+
+// dsd_create (any_width = false) and dsd_create_any_width: the same handle, two width rules for LYNXNet and the aux decoder
+int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const char* who) {
+    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "%s: null argument", who);
     if (cfg->struct_size != (int32_t)sizeof(dsd_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_config));
+        return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, cfg->struct_size, sizeof(dsd_config));
     if (cfg->backbone != DSD_BACKBONE_WAVENET && cfg->backbone != DSD_BACKBONE_LYNXNET && cfg->backbone != DSD_AUX_CONVNEXT)
-        return fail(nullptr, DSD_EINVAL, "dsd_create: unknown backbone %d", cfg->backbone);
+        return fail(nullptr, DSD_EINVAL, "%s: unknown backbone %d", who, cfg->backbone);
     if (cfg->in_dims < 1 || cfg->n_feats < 1 || cfg->num_layers < 1 || cfg->hidden_size < 1)
-        return fail(nullptr, DSD_EINVAL, "dsd_create: non-positive dimension");
+        return fail(nullptr, DSD_EINVAL, "%s: non-positive dimension", who);
     if (cfg->backbone == DSD_BACKBONE_WAVENET) {
         // any even count the reference itself can run (SinusoidalPosEmb: two halves of C / 2, exponent / (C / 2 - 1),
-        // common_layers.py:275-279); not a multiple of 32: run as the next multiple with zero channels (pad_wavenet_weights)
+        // common_layers.py:275-279); not a multiple of 32: run as the next multiple with zero channels (pad_weights)
         if (cfg->num_channels < 4 || cfg->num_channels % 2 != 0)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: WaveNet num_channels must be even and >= 4 (got %d)", cfg->num_channels);
+            return fail(nullptr, DSD_EINVAL, "%s: WaveNet num_channels must be even and >= 4 (got %d)", who, cfg->num_channels);
+    } else if (any_width) {
+        // LYNXNet: SinusoidalPosEmb's rule again (lynxnet.py:109-114); the aux decoder has no rule of its own (convnext.py:58-76)
+        if (cfg->backbone == DSD_BACKBONE_LYNXNET && (cfg->num_channels < 4 || cfg->num_channels % 2 != 0))
+            return fail(nullptr, DSD_EINVAL, "%s: LYNXNet num_channels must be even and >= 4 (got %d): the reference cannot build "
+                        "this width either (SinusoidalPosEmb emits 2 * (C // 2) values into Linear(C, 4C) and divides by C / 2 - 1)",
+                        who, cfg->num_channels);
+        if (cfg->num_channels < 1) return fail(nullptr, DSD_EINVAL, "%s: num_channels must be positive (got %d)", who, cfg->num_channels);
     } else if (cfg->num_channels < 32 || cfg->num_channels % 32 != 0) {
-        return fail(nullptr, DSD_EINVAL, "dsd_create: num_channels must be a positive multiple of 32 (got %d)",
-                    cfg->num_channels);
+        return fail(nullptr, DSD_EINVAL, "%s: num_channels must be a positive multiple of 32 (got %d); dsd_create_any_width "
+                    "takes every width the reference builds", who, cfg->num_channels);
     }
     if (cfg->backbone == DSD_AUX_CONVNEXT) {
-        if (cfg->n_feats != 1) return fail(nullptr, DSD_EINVAL, "dsd_create: the aux decoder has n_feats == 1 (toplevel.py:50)");
+        if (cfg->n_feats != 1) return fail(nullptr, DSD_EINVAL, "%s: the aux decoder has n_feats == 1 (toplevel.py:50)", who);
         if (cfg->kernel_size < 1 || cfg->kernel_size % 2 == 0 || cfg->kernel_size > 15)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: ConvNeXt aux decoder needs an odd kernel_size <= 15");
+            return fail(nullptr, DSD_EINVAL, "%s: ConvNeXt aux decoder needs an odd kernel_size <= 15", who);
     } else if (cfg->backbone == DSD_BACKBONE_WAVENET) {
         if (cfg->dilation_cycle_length < 1 || cfg->dilation_cycle_length > 8)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: dilation_cycle_length must be in [1, 8]");
+            return fail(nullptr, DSD_EINVAL, "%s: dilation_cycle_length must be in [1, 8]", who);
     } else {
         if (cfg->expansion_factor < 1 || cfg->kernel_size < 1 || cfg->kernel_size % 2 == 0 || cfg->kernel_size > 63)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: LYNXNet needs expansion_factor >= 1 and odd kernel_size <= 63");
-        if ((cfg->num_channels * cfg->expansion_factor) % 32 != 0)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: num_channels * expansion_factor must be a multiple of 32");
+            return fail(nullptr, DSD_EINVAL, "%s: LYNXNet needs expansion_factor >= 1 and odd kernel_size <= 63", who);
+        if (!any_width && (cfg->num_channels * cfg->expansion_factor) % 32 != 0)
+            return fail(nullptr, DSD_EINVAL, "%s: num_channels * expansion_factor must be a multiple of 32", who);
         if (cfg->activation < DSD_ACT_PRELU || cfg->activation > DSD_ACT_RELU)
-            return fail(nullptr, DSD_EINVAL, "dsd_create: %d is not a valid activation", cfg->activation);
+            return fail(nullptr, DSD_EINVAL, "%s: %d is not a valid activation", who, cfg->activation);
     }
-    if (int rc = select_device("dsd_create", cfg->device)) return rc;
+    if (int rc = select_device(who, cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_layer_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_rowsplit_init_all();
@@ -1959,7 +2061,7 @@ int dsd_create(const dsd_config* cfg, dsd_handle** out) {
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_LYNXNET) ie = lx_x3_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_edge_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_LYNXNET) ie = lx_layer_init_all();
-    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
+    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: kernel attribute setup failed: %s", who, hipGetErrorString(ie));
     dsd_handle* h = new dsd_handle();
     h->cfg = *cfg;
     h->opts = read_path_opts();
@@ -1968,13 +2070,22 @@ int dsd_create(const dsd_config* cfg, dsd_handle** out) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) h->cus = prop.multiProcessorCount;
     }
-    if (cfg->backbone == DSD_BACKBONE_WAVENET) {      // the kernels run on a multiple of 32 channels (pad_wavenet_weights)
+    // the kernels run on a multiple of 32 channels (pad_weights): every WaveNet, and what dsd_create_any_width alone lets through
+    if (cfg->backbone == DSD_BACKBONE_WAVENET || cfg->num_channels % 32 != 0) {
         h->c_user = cfg->num_channels;
         h->cfg.num_channels = (cfg->num_channels + 31) / 32 * 32;
     }
     *out = h;
     return DSD_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int dsd_create(const dsd_config* cfg, dsd_handle** out) { return create_impl(cfg, out, false, "dsd_create"); }
+
+int dsd_create_any_width(const dsd_config* cfg, dsd_handle** out) { return create_impl(cfg, out, true, "dsd_create_any_width"); }
 
 void dsd_destroy(dsd_handle* h) {
     if (!h) return;
@@ -2731,7 +2842,8 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
         e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev.p,
                           h->blob.p + h->dw_w[l], h->blob.p + h->dw_b[l], 7, 3, nullptr, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
-        e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, C, B, T, 0, h->stats, Ts, 1e-6f, st);
+        // (statistics only, over the caller's channels: rows beyond them are zero padding, pad_weights)
+        e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, true_channels(h), B, T, 0, h->stats, Ts, 1e-6f, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm stats launch failed: %s", hipGetErrorString(e));
         GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_BIAS_ACT, 0);
         g.p.ln_stats = h->stats; g.p.ln_ts = Ts;

@@ -136,8 +136,9 @@ struct dsd_handle {
     dsd_config cfg;
     std::string err;
     std::map<std::string, HostTensor> raw;
-    // WaveNet with a channel count that is not a multiple of 32: cfg.num_channels is the count the kernels run with
-    // (rounded up), c_user the caller's; `padded` holds the zero-extended tensors build_packed reads (pad_wavenet_weights)
+    // A channel count that is not a multiple of 32 (any WaveNet; LYNXNet and the aux decoder through dsd_create_any_width):
+    // cfg.num_channels is the count the kernels run with (rounded up), c_user the caller's (0: the same); `padded` holds the
+    // zero-extended tensors build_packed reads (pad_weights)
     std::map<std::string, HostTensor> padded;
     int c_user = 0;
     // wn_edge.hip: the state buffer whose input projection the previous evaluation's edge kernel already wrote into xh

@@ -170,6 +170,9 @@ struct GemmP {
     int strong;
     float* lnpart;
     int lnpart_ts;
+    // ... over the first ln_rows of the M rows only: a network run with zero-padded channels (api.hip, pad_weights) takes its
+    // LayerNorm over the real ones, so tile i holds n_i = clamp(ln_rows - 64 i, 0, 64) rows for the statistics (M: all of them)
+    int ln_rows;
     int nout;               // EP_LINCOMB
     LinOut lo[kMaxOut];
 };
@@ -288,6 +291,8 @@ struct LxLayerP {
     int film_cstride, film_col0, film_colb;
     float* lnpart;          // [B][C / 64][2][lnpart_ts]: per 64-row tile mean and sum of squared deviations of xin_out
     int lnpart_ts, ln_tiles;
+    int ln_rows;            // the rows of xin a LayerNorm counts: C, or fewer (above C - 32) when the last channels are zero padding
+                            // (api.hip, pad_weights) - partials in and out carry n_i = min(64, ln_rows - 64 i) rows per tile
     long x_bstride, u_bstride;
     int inner, Ts, T, tiles_per_b, nft, strong;
     float inv_tiles_per_b, inv_nft;     // inv_nft = 1 / (ragged ? ncg : nft)
@@ -402,6 +407,7 @@ hipError_t launch_enc_attention(const float* qkv, const float* nonpad, float* ou
                                 hipStream_t st);
 hipError_t launch_enc_expand(const float* enc, const long long* mel2ph, const EncExpandArgs& a, int H, int B, int L, int Ls,
                              int T, float* cond, hipStream_t st);
+// (C = the rows the LayerNorm counts: tile i holds min(64, C - 64 i) of them, which may leave mtiles * 64 above C)
 hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T, int ts, float eps, float* stats,
                            hipStream_t stream);
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,

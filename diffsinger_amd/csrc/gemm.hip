@@ -687,7 +687,9 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
         // (two-pass inside the tile: mean first, then squared deviations; tiles are merged by ln_merge_kernel with
         // the parallel-variance formula, so no E[x^2] - mean^2 cancellation anywhere).
         float xi[2][NB][4];
-        const int nrows = min(64, p.M - mtile * 64);                 // valid rows of this tile
+        // (p.ln_rows <= p.M: rows beyond it are zero padding of the channels and count for nothing, above all not as
+        // (0 - mean)^2 in the second pass; every tile keeps at least one counted row, as ln_rows > M - 32)
+        const int nrows = min(64, p.ln_rows - mtile * 64);           // counted rows of this tile
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
             const int t = t0 + wn * (16 * NB) + n * 16 + lcol;
@@ -728,7 +730,7 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
                     for (int r = 0; r < 4; ++r) {
                         const int row = mtile * 64 + (wm * 2 + mb) * 16 + rq + r;
                         const float dlt = xi[mb][n][r] - (pass ? mean[n] : 0.f);
-                        s += (row < p.M) ? (pass ? dlt * dlt : dlt) : 0.f;
+                        s += (row < p.ln_rows) ? (pass ? dlt * dlt : dlt) : 0.f;
                     }
                 s += __shfl_xor(s, 16, 64);
                 s += __shfl_xor(s, 32, 64);

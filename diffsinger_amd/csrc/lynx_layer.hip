@@ -103,6 +103,8 @@ __device__ __forceinline__ void k_phase(f32x4 (&acc)[MBW][2], f32x4 (&W)[3][MBW]
 // LayerNorm statistics of a tile's 32 frames from the producer's per-64-row partials (mean_i, M2_i): ln_merge_kernel's arithmetic
 // in ln_merge_kernel's order (tiles ascending; parallel-variance formula), every thread for its own four frames c4 * 4 .. + 3,
 // all 2 * KT / 64 partial vectors in flight at once (a run-time loop here serialised 48 load round trips: + 1.4 % on config 3)
+// p.ln_rows rows count (LxLayerP): all tiles but the last hold 64 of them, the last one n_last = ln_rows - (KT - 64), and the
+// divisor is ln_rows - at ln_rows == KT the very operations of the constants 64.f and KT
 template <int KT>
 __device__ __forceinline__ void lx_merge_stats(const LxLayerP& p, int bu, int t0u, int c4, f32x4& mean, f32x4& rstd) {
     constexpr int NT = KT / 64;                                  // 64-row tiles of xin (= p.ln_tiles)
@@ -113,19 +115,20 @@ __device__ __forceinline__ void lx_merge_stats(const LxLayerP& p, int bu, int t0
         pm[i] = ld4(r_p, c4 * 16, i * 2 * p.lnpart_ts * 4);
         pq[i] = ld4(r_p, c4 * 16, (i * 2 + 1) * p.lnpart_ts * 4);
     }
+    const float n_last = (float)(p.ln_rows - (KT - 64)), n_all = (float)p.ln_rows;
     f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < NT; ++i) s += 64.f * pm[i];
+    for (int i = 0; i < NT; ++i) s += (i + 1 < NT ? 64.f : n_last) * pm[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) mean[e] = s[e] / (float)KT;
+    for (int e = 0; e < 4; ++e) mean[e] = s[e] / n_all;
     f32x4 m2 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         const f32x4 d = pm[i] - mean;
-        m2 += pq[i] + 64.f * d * d;
+        m2 += pq[i] + (i + 1 < NT ? 64.f : n_last) * d * d;
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(m2[e] / (float)KT + 1e-5f);
+    for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(m2[e] / n_all + 1e-5f);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -534,9 +537,12 @@ __global__ __launch_bounds__(256, 1) void lx_pw2_kernel(const LxLayerP p) {
     }
     // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers.
     // A frame's 64 rows sit in 8 slots m of the 8 lanes with equal (lane & 7): sum over m, then over lanes 8, 16, 32 apart.
+    // Of a tile's rows the first n = min(64, ln_rows - 64 tile) count (the rest is zero padding of the channels: nothing in the
+    // sum, masked out of the squared deviations); n >= 1, and at n = 64 the reciprocal is the constant 1 / 64 it replaces.
     if (p.lnpart) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
+            const int cnt = min(64, p.ln_rows - (row0 + 64 * h));        // counted rows of this tile (uniform)
             f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) s += xi[8 * h + m];
@@ -546,12 +552,12 @@ __global__ __launch_bounds__(256, 1) void lx_pw2_kernel(const LxLayerP p) {
                 s[e] += __shfl_xor(s[e], 16, 64);
                 s[e] += __shfl_xor(s[e], 32, 64);
             }
-            const f32x4 mu4 = s * (1.f / 64.f);
+            const f32x4 mu4 = s * (1.f / (float)cnt);
             f32x4 q = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const f32x4 d = xi[8 * h + m] - mu4;
-                q += d * d;
+                if ((lane >> 3) + 8 * m < cnt) q += d * d;
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -730,9 +736,12 @@ __global__ __launch_bounds__(256, 1) void lx_pw2d_kernel(const LxLayerP p) {
     }
     // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers.
     // A frame's 64 rows sit in 8 slots m of the 8 lanes with equal (lane & 7): sum over m, then over lanes 8, 16, 32 apart.
+    // Of a tile's rows the first n = min(64, ln_rows - 64 tile) count (the rest is zero padding of the channels: nothing in the
+    // sum, masked out of the squared deviations); n >= 1, and at n = 64 the reciprocal is the constant 1 / 64 it replaces.
     if (p.lnpart) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
+            const int cnt = min(64, p.ln_rows - (row0 + 64 * h));        // counted rows of this tile (uniform)
             f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) s += xi[8 * h + m];
@@ -742,12 +751,12 @@ __global__ __launch_bounds__(256, 1) void lx_pw2d_kernel(const LxLayerP p) {
                 s[e] += __shfl_xor(s[e], 16, 64);
                 s[e] += __shfl_xor(s[e], 32, 64);
             }
-            const f32x4 mu4 = s * (1.f / 64.f);
+            const f32x4 mu4 = s * (1.f / (float)cnt);
             f32x4 q = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
                 const f32x4 d = xi[8 * h + m] - mu4;
-                q += d * d;
+                if ((lane >> 3) + 8 * m < cnt) q += d * d;
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -961,6 +970,7 @@ __global__ __launch_bounds__(512, 1) void lx_pw2q_kernel(const LxLayerP p) {
     }
     // LayerNorm partials of xin per 64-row tile (item k of every thread = tile k of this workgroup): two passes.  A frame quad's 64
     // rows sit in the 8 lanes with equal (lane & 7) of each of the 8 waves: lanes 8, 16, 32 apart, then the waves through LDS.
+    // Of a tile's rows the first min(64, ln_rows - 64 tile) >= 1 count, as in lx_pw2_kernel.
     if (p.lnpart) {
         auto wave_sum = [&](f32x4 v) {
 #pragma unroll
@@ -985,11 +995,11 @@ __global__ __launch_bounds__(512, 1) void lx_pw2q_kernel(const LxLayerP p) {
         }
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < 2; ++k) mu4[k] = all_sum(k) * (1.f / 64.f);
+        for (int k = 0; k < 2; ++k) mu4[k] = all_sum(k) * (1.f / (float)min(64, p.ln_rows - (row0 + 64 * k)));
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const f32x4 d = xi[k] - mu4[k];
+        for (int k = 0; k < 2; ++k) {                            // (rows beyond p.ln_rows: zero padding, not counted)
+            const f32x4 d = row0 + 64 * k + (tid >> 3) < p.ln_rows ? xi[k] - mu4[k] : f32x4{0.f, 0.f, 0.f, 0.f};
             const f32x4 qv = wave_sum(d * d);
             if (lane < 8) *reinterpret_cast<f32x4*>(&red[(k * 8 + wave) * 32 + lane * 4]) = qv;
         }

@@ -101,19 +101,21 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
             pm[i] = ld4(r_p, fq * 16, i * 2 * p.lnpart_ts * 4);
             pq[i] = ld4(r_p, fq * 16, (i * 2 + 1) * p.lnpart_ts * 4);
         }
+        // (p.ln_rows rows count: 64 per tile but n_last in the last one, as lx_merge_stats of lynx_layer.hip)
+        const float n_last = (float)(p.ln_rows - (KT - 64)), n_all = (float)p.ln_rows;
         f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int i = 0; i < NT; ++i) s += 64.f * pm[i];
+        for (int i = 0; i < NT; ++i) s += (i + 1 < NT ? 64.f : n_last) * pm[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) mean[e] = s[e] / (float)KT;
+        for (int e = 0; e < 4; ++e) mean[e] = s[e] / n_all;
         f32x4 m2 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
             const f32x4 d = pm[i] - mean;
-            m2 += pq[i] + 64.f * d * d;
+            m2 += pq[i] + (i + 1 < NT ? 64.f : n_last) * d * d;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(m2[e] / (float)KT + 1e-5f);
+        for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(m2[e] / n_all + 1e-5f);
     }
     const __amdgpu_buffer_rsrc_t r_in = MODE == 0 ? rsrc(p.xin + (long)bu * p.x_bstride + t0u) : rsrc(p.v + (long)bu * p.u_bstride + t0u);
     auto stage = [&](int ph) {
@@ -280,10 +282,12 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
                 st4_l2(xo, w_xo, ev0, m * 8 * Ts * 4);
                 if (p.xin_out) st4_l2(xi[m], w_xi, ev0, m * 8 * Ts * 4);
             }
-            // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers
+            // LayerNorm partials of xin per 64-row tile (tiles 2w, 2w + 1 of this workgroup's 8): two passes over the registers;
+            // of a tile's rows the first cnt = min(64, ln_rows - 64 tile) >= 1 count, as in lx_pw2_kernel
             if (p.lnpart) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
+                    const int cnt = min(64, p.ln_rows - (row0 + 64 * h));
                     f32x4 sm = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int m = 0; m < 8; ++m) sm += xi[8 * h + m];
@@ -293,12 +297,12 @@ __global__ __launch_bounds__(256, 1) void lx_x3_kernel(const LxLayerP p) {
                         sm[e] += __shfl_xor(sm[e], 16, 64);
                         sm[e] += __shfl_xor(sm[e], 32, 64);
                     }
-                    const f32x4 mu4 = sm * (1.f / 64.f);
+                    const f32x4 mu4 = sm * (1.f / (float)cnt);
                     f32x4 q = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int m = 0; m < 8; ++m) {
                         const f32x4 d = xi[8 * h + m] - mu4;
-                        q += d * d;
+                        if ((lane >> 3) + 8 * m < cnt) q += d * d;
                     }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {

@@ -87,8 +87,26 @@ typedef struct dsd_config {
 
 /* Replaces: BACKBONES[backbone_type](out_dims, num_feats, **kwargs)  (backbones/__init__.py:16-18). */
 int dsd_create(const dsd_config* cfg, dsd_handle** out);
+/*
+ * dsd_create for every width the reference builds.  dsd_create itself returns DSD_EINVAL for a LYNXNet or a ConvNeXt aux
+ * decoder whose num_channels is not a multiple of 32, and for a LYNXNet whose num_channels * expansion_factor is not; the
+ * reference has neither rule.  Same struct, same handle, same calls afterwards; `num_channels` is the model's true width and
+ * dsd_load_weight takes the reference's state_dict names and shapes at that width.
+ *   LYNXNet (modules/backbones/lynxnet.py:90-126): every even num_channels >= 4 and every expansion_factor >= 1.  Odd widths
+ *     and widths below 4 are DSD_EINVAL because the reference cannot build them either: SinusoidalPosEmb
+ *     (modules/commons/common_layers.py:268-281) emits 2 * (C // 2) values into a Linear(C, 4C) and divides by C / 2 - 1 - the
+ *     rule dsd_create applies to a WaveNet.  kernel_size stays odd and <= 63 (with an even one the reference's own residual
+ *     add fails: padding = kernel_size // 2 gives T + 1 frames).
+ *   ConvNeXt aux decoder (modules/aux_decoder/convnext.py:58-85): every num_channels >= 1.
+ *   WaveNet, and every width dsd_create accepts: exactly what dsd_create does.
+ * Cost: the network RUNS at the next multiple of 32, Cp = (num_channels + 31) / 32 * 32 (LYNXNet's inner width at
+ * Cp * expansion_factor), with the extra channels exactly zero throughout and every LayerNorm taken over the true
+ * num_channels.  Weight memory, workspace (dsd_get_stats) and time are those of a model of width Cp: a LYNXNet of 500 channels
+ * costs what one of 512 does and takes the same kernels.
+ */
+int dsd_create_any_width(const dsd_config* cfg, dsd_handle** out);
 void dsd_destroy(dsd_handle* h);
-/* Message for the last failed call on `h` (h == NULL: last failed dsd_create).  Never NULL. */
+/* Message for the last failed call on `h` (h == NULL: last failed dsd_create / dsd_create_any_width).  Never NULL. */
 const char* dsd_last_error(const dsd_handle* h);
 int dsd_api_version(void);
 

@@ -48,7 +48,7 @@ int main(int argc, char** argv) {
     hipMemcpy(w, hw.data(), nw * 2, hipMemcpyHostToDevice);
     if (lx_x3_init_all() != hipSuccess) { printf("init failed\n"); return 1; }
     LxLayerP p{};
-    p.A1 = reinterpret_cast<const float*>(w); p.bias1 = bias; p.xin = x; p.lnpart_in = part; p.lnpart_ts = lts; p.u = u;
+    p.A1 = reinterpret_cast<const float*>(w); p.bias1 = bias; p.xin = x; p.lnpart_in = part; p.lnpart_ts = lts; p.ln_rows = C; p.u = u;
     p.x_bstride = (long)xs; p.u_bstride = (long)us; p.inner = inner; p.Ts = Ts; p.T = T;
     std::vector<std::vector<float>> res;
     for (int ncb : {2, 4, 4, 4, 2}) {

@@ -4,7 +4,12 @@ counts 32 ... 512, dilation cycles up to 6, n_feats > 1, hidden sizes other than
 evaluation timed with HIP events over a replayed hipGraph -> gpurun_out/<tag>_shapes.json (GPU box only; copy to profiles/).
 `frac` = algorithmic flops of one evaluation (in-projection, L x (dilated conv + 1x1 out), skip and output projections; the
 hoisted conditioner projection is not in the loop) / time / the fp32-MFMA peak (157.3 TF, MI355X_MICROARCH.md).
-Usage: python tools/sweep_shapes.py [tag, default r03] [batch, default 8] [frames, default 1000]"""
+Usage: python tools/sweep_shapes.py [tag, default r03] [batch, default 8] [frames, default 1000]
+
+`python tools/sweep_shapes.py widths [tag]`: LYNXNet at a width that is not a multiple of 32 beside its padded twin (500 / 512,
+1000 / 1024; 6 layers, expansion 2, k = 31) at B = 1 and B = 8, T = 1000, eager evaluations in one process: per grid the four nets
+are built once, warmed up, then timed in 5 interleaved rounds of 20 evaluations each (median of the rounds; the spread is
+reported) -> <tag>_widths_shapes.json beside the shape sweep's file."""
 import json
 import os
 import sys
@@ -35,13 +40,64 @@ def flops_per_eval(in_dims, n_feats, c, nl, bsz, t_len):
     return per_frame * bsz * t_len
 
 
+def widths_rows():
+    dev = torch.device("cuda", 0)
+    set_hp(hidden_size=256)
+    rows = []
+    for bsz in (1, 8):
+        t_len = 1000
+        x = torch.from_numpy(synth.synth_normal((bsz, 1, 128, t_len), 31)).to(dev)
+        cond = torch.from_numpy(synth.synth_normal((bsz, 256, t_len), 32)).to(dev)
+        t = torch.from_numpy((np.arange(bsz) * 97.5 + 3.0).astype(np.float32)).to(dev)
+        nets = {}
+        for c in (500, 512, 1000, 1024):
+            args = dict(num_layers=6, num_channels=c, expansion_factor=2, kernel_size=31, activation="PReLU", strong_cond=c >= 1000)
+            shapes = synth.backbone_param_shapes("lynxnet", 128, 1, hidden_size=256, **args)
+            net = build_backbone(128, 1, "lynxnet", args)
+            net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(shapes, seed=100 + c).items()}, strict=True)
+            nets[c] = net.to(dev).eval()
+        times = {c: [] for c in nets}
+        with torch.no_grad():
+            for c, net in nets.items():
+                for _ in range(5):
+                    net(x, t, cond)
+            torch.cuda.synchronize()
+            for _ in range(5):
+                for c, net in nets.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        net(x, t, cond)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    times[c].append(e0.elapsed_time(e1) / 20)
+            for c, net in nets.items():
+                net.kernel_timing(True)
+                net(x, t, cond)
+                torch.cuda.synchronize()
+                ks = net.kernel_classes()
+                net.kernel_timing(False)
+                row = dict(C=c, batch=bsz, frames=t_len, ms_per_eval=round(float(np.median(times[c])), 4),
+                           ms_min=round(min(times[c]), 4), ms_max=round(max(times[c]), 4),
+                           kernels=sorted(k["name"] for k in ks), launches=sum(k["launches"] for k in ks))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                net.release_native()
+        for odd, twin in ((500, 512), (1000, 1024)):
+            print(json.dumps(dict(batch=bsz, pair=[odd, twin], ratio=round(float(np.median(times[odd]) / np.median(times[twin])), 4))), flush=True)
+    return rows
+
+
 def main():
+    widths = len(sys.argv) > 1 and sys.argv[1] == "widths"
+    if widths:          # the rows of the width pairs, written below like the shape sweep's: <tag>_widths_shapes.json
+        sys.argv[1:] = [(sys.argv[2] if len(sys.argv) > 2 else "r04") + "_widths"]
     tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
     bsz = int(sys.argv[2]) if len(sys.argv) > 2 else 8
     t_len = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
     dev = torch.device("cuda", 0)
-    rows = []
-    for i, (in_dims, n_feats, c, nl, cyc, hidden) in enumerate(SHAPES):
+    rows = widths_rows() if widths else []
+    for i, (in_dims, n_feats, c, nl, cyc, hidden) in enumerate([] if widths else SHAPES):
         set_hp(hidden_size=hidden)
         args = dict(num_layers=nl, num_channels=c, dilation_cycle_length=cyc)
         shapes = synth.backbone_param_shapes("wavenet", in_dims, n_feats, hidden_size=hidden, **args)
