@@ -2174,6 +2174,12 @@ int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int
     return DSD_OK;
 }
 
+// A k-tap convolution (k > 1) of the encoders runs on the generic GEMM path, which keeps all K = round_up(channels, 16) input
+// rows of a tile resident in LDS.  make_gemm narrows the tile to 32 frames where 64 do not fit, and 48 floats is that tile's
+// row stride for every odd k <= 15 at dilation 1 (32 + 2 * HL <= 48), so K * 48 * 4 <= 160 KiB decides it for every (B, L):
+// K <= 848.  The creates refuse what run_gemm would refuse at the first encode call.
+constexpr int kEncConvMaxK = kMaxDynLds / (48 * 4) / 16 * 16;
+
 int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
     if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: null argument");
     if (cfg->struct_size != (int32_t)sizeof(dsd_encoder_config))
@@ -2186,6 +2192,10 @@ int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
         return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: head dimension must be a multiple of 8, at most 256");
     if (cfg->ffn_kernel_size < 1 || cfg->ffn_kernel_size % 2 == 0 || cfg->ffn_kernel_size > 15)
         return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: enc_ffn_kernel_size must be odd and <= 15");
+    if (cfg->ffn_kernel_size > 1 && cfg->hidden_size > kEncConvMaxK)
+        return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: hidden_size %d: the FFN conv keeps %d bytes of LDS resident per tile "
+                    "(> 160 KiB); hidden_size is at most %d with enc_ffn_kernel_size > 1", cfg->hidden_size,
+                    cfg->hidden_size * 48 * 4, kEncConvMaxK / 32 * 32);
     if (cfg->num_spk < 0 || cfg->num_lang < 0) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: negative table size");
     if (cfg->pos_mode < DSD_POS_ROPE || cfg->pos_mode > DSD_POS_SIN) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: pos_mode must be one of DSD_POS_*");
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: ffn_act must be one of DSD_FFN_*");
@@ -2356,12 +2366,23 @@ int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** o
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: head dimension must be a multiple of 8, at most 256");
     if (cfg->ffn_kernel_size < 1 || cfg->ffn_kernel_size % 2 == 0 || cfg->ffn_kernel_size > 15)
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: enc_ffn_kernel_size must be odd and <= 15");
+    if (cfg->ffn_kernel_size > 1 && cfg->hidden_size > kEncConvMaxK)
+        return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: hidden_size %d: the FFN conv keeps %d bytes of LDS resident per "
+                    "tile (> 160 KiB); hidden_size is at most %d with enc_ffn_kernel_size > 1", cfg->hidden_size,
+                    cfg->hidden_size * 48 * 4, kEncConvMaxK / 32 * 32);
     if (cfg->out_dims < 0 || cfg->dur_layers < 0) return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: negative size");
     if (cfg->out_dims > 4 * cfg->hidden_size) return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: out_dims above 4 * hidden_size is not supported");
     if (cfg->pos_mode < DSD_POS_ROPE || cfg->pos_mode > DSD_POS_SIN) return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: pos_mode must be one of DSD_POS_*");
     if (cfg->dur_layers > 0 && (cfg->dur_chans < 1 || cfg->dur_kernel_size < 1 || cfg->dur_kernel_size % 2 == 0 ||
                                 cfg->dur_kernel_size > 15))
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: duration predictor needs channels >= 1 and an odd kernel size <= 15");
+    if (cfg->dur_layers > 0 && cfg->dur_kernel_size > 1) {      // layer 0 reads hidden_size channels, every later layer dur_chans
+        const int cin = std::max(cfg->hidden_size, cfg->dur_layers > 1 ? cfg->dur_chans : 0);
+        if (round_up(cin, 16) > kEncConvMaxK)
+            return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: a duration predictor conv with kernel size > 1 takes at most "
+                        "%d input channels (%d bytes of LDS resident per tile, 160 KiB); got %d", kEncConvMaxK,
+                        kEncConvMaxK * 48 * 4, cin);
+    }
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU)
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: ffn_act must be one of DSD_FFN_*");
     if (int rc = select_device("dsd_token_encoder_create", cfg->device)) return rc;
