@@ -1,6 +1,6 @@
 // Device primitives shared by the hand-written kernel files of libdsdenoise (gfx950, device code only; included after
 // dsd_internal.h): vector types, buffer-descriptor loads and the 16-byte store with its two cache policies, index helpers,
-// the activations named for their arithmetic, the split-bf16 products and the diagnostic stamps.
+// the compensated DFT tile walk, the activations named for their arithmetic, the split-bf16 products and the diagnostic stamps.
 #pragma once
 #include <type_traits>
 
@@ -117,6 +117,64 @@ __device__ __forceinline__ void wn_pin_args(const WnLayerP& p) {
 
 __device__ __forceinline__ f32x4 mfma_16x16x4(float wfrag, float xfrag, f32x4 acc) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(wfrag, xfrag, acc, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The compensated DFT tile walk of mel_dft_kernel and hs_dft_kernel: [kDftRows basis rows] x [kDftFrames frames] per
+// workgroup of 256, wave w owns basis rows 16w..16w+15 and all 64 frames (four 16x16 accumulators).  Operand maps of
+// v_mfma_f32_16x16x4_f32: A[i = lane & 15][k = lane >> 4] (basis rows), B[k = lane >> 4][j = lane & 15] (frames);
+// D[row = 4 (lane >> 4) + reg][col = lane & 15].
+// Accuracy: one fp32 accumulator over all K taps carries the rounding of large partial sums that
+// cancel by the end, so each kDftKS taps go into a fresh accumulator (2 MFMAs) and the partial sums are added with TwoSum
+// into a (hi, lo) pair; the caller's epilogue reads hi + lo.
+// bas = the row tile of a basis [.][Kpad] (K <= Kpad, a multiple of kDftTaps); stage(f, j) = the B operand of frame f < nf,
+// tap j < K of the tile (zero elsewhere); sA / sB = LDS of kDftRows / kDftFrames rows of kDftLS floats.
+// ---------------------------------------------------------------------------------------------
+constexpr int kDftKS = 8;               // taps per fresh MFMA accumulator
+constexpr int kDftLS = kDftTaps + 4;    // LDS row stride: the 16 rows x 4 taps of an MFMA operand read hit 64 distinct banks
+template <typename Stage>
+__device__ __forceinline__ void dft_tile_walk(const float* __restrict__ bas, int Kpad, int K, int nf, float* sA, float* sB,
+                                              Stage&& stage, f32x4 (&hi)[4], f32x4 (&lo)[4]) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+    for (int f = 0; f < 4; ++f) hi[f] = lo[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += kDftTaps) {
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < (kDftRows * kDftTaps) / 256; ++s) {
+            const int idx = tid + 256 * s, row = idx / kDftTaps, kk = idx % kDftTaps;
+            sA[row * kDftLS + kk] = bas[(long)row * Kpad + k0 + kk];
+        }
+#pragma unroll
+        for (int s = 0; s < (kDftFrames * kDftTaps) / 256; ++s) {
+            const int idx = tid + 256 * s, f = idx / kDftTaps, kk = idx % kDftTaps, j = k0 + kk;
+            sB[f * kDftLS + kk] = (f < nf && j < K) ? stage(f, j) : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int half = 0; half < kDftTaps / kDftKS; ++half) {
+            f32x4 part[4];
+#pragma unroll
+            for (int f = 0; f < 4; ++f) part[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = half * kDftKS / 4; ks < (half + 1) * kDftKS / 4; ++ks) {
+                const float a = sA[(16 * w + (lane & 15)) * kDftLS + 4 * ks + (lane >> 4)];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    const float bv = sB[(16 * f + (lane & 15)) * kDftLS + 4 * ks + (lane >> 4)];
+                    part[f] = mfma_16x16x4(a, bv, part[f]);
+                }
+            }
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {       // TwoSum: hi + lo carries the running sum to about 2 x 24 bits
+                    const float x = part[f][r], s = hi[f][r] + x, bp = s - hi[f][r];
+                    lo[f][r] += (hi[f][r] - (s - bp)) + (x - bp);
+                    hi[f][r] = s;
+                }
+        }
+    }
 }
 
 // one row block x all NCB 16-frame column blocks of a k32 step in split-bf16 arithmetic: lo.hi, hi.lo, hi.hi (smallest terms

@@ -413,13 +413,19 @@ hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T,
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
                          const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream);
 
+// The DFT tile of mel_dft_kernel and hs_dft_kernel (dsd_device.h, dft_tile_walk), as far as the host sizes bases and work
+// lists by it
+constexpr int kDftFrames = 64;      // frames per tile (one work-list entry)
+constexpr int kDftRows = 64;        // basis rows per tile: a basis holds a multiple of them
+constexpr int kDftTaps = 32;        // taps staged per chunk: a basis row holds a multiple of them
+
 // mel_kernels.hip: waveform -> log-mel (dsd_mel_analyze).  work: 5 ints per (item, 64-frame tile) entry = item b, first
 // frame t0, item length L in samples, item frame count T_b, index of the entry's first frame in the magnitude buffer
 struct MelDftP {
     const float* wav;
     long wav_bstride;
     const int* work;
-    const float* basis;     // [row tiles * 64][Kpad] (mel_basis_kernel)
+    const float* basis;     // [row tiles * kDftRows][Kpad] (mel_basis_kernel)
     int Kpad, W, H, off, padL;
     int nb;                 // bins computed: k_lo .. k_lo + nb - 1
     int rescale;            // keyshift != 0: |X| * win_size / W'
@@ -561,29 +567,36 @@ struct HsMaskP {
     int F, Fx, C;                   // mask bins, conv bins (the last one replicated)
     const int* T;
 };
-struct HsDftP {
-    const float* basis;
-    int Kpad, K, N, nb, inv;
-    // forward
+// hs_dft_kernel<0 / 1>.  The spectrum of both directions: element (b, bin, t) at + b s_sb + bin s_sf + t s_st, re at channel
+// ch, im at channel s_cim + ch.  work: 6 ints per (item, 64-frame tile, channel) entry = b, t0, L, T_b, ch, padL (forward).
+struct HsStftP {
+    const float* basis;             // [row tiles * 64][N] (hs_basis_kernel, forward)
+    int N, nb;
     const float* wav;               // channel ch of item b at wav + b wav_sb + ch wav_sc
     long wav_sb, wav_sc;
-    int H, reflect;                 // (padL per work entry)
-    // inverse: spectrum (b, bin, t) at spec + b s_sb + bin s_sf + t s_st, re / im at channel s_cre / s_cim + ch
+    int H, reflect;                 // hop; outside the item: 0 zeros (pad_mode 'constant'), 1 torch's 'reflect'
+    float* spec;
+    long s_sb, s_sf, s_st;
+    int s_cim, nrep;                // nrep > 1: one clip written to channels ch .. ch + nrep - 1 (wav_sc = 0)
+    const int* work;
+};
+struct HsIstftP {
+    const float* basis;             // [row tiles * 64][Kpad] (hs_basis_kernel, inverse)
+    int Kpad, N, nb;
     const float* spec;
     long s_sb, s_sf, s_st;
-    int s_cre, s_cim;
-    const float* mask;              // the network's mask (NULL: the f0 bin mask)
-    long m_sb, m_sf, m_st;
+    int s_cim;
+    const float* mask;              // the network's mask (NULL: the f0 bin mask): (b, bin, t) at + b m_sb + bin m_sf + t m_st,
+    long m_sb, m_sf, m_st;          // re / im at channel ch / m_cim + ch, mask_F bins (the last one replicated)
     int m_cim, mask_F;
     const float* f0;                // [b f0_sb + t], f0_len[b] frames
     long f0_sb;
     const int* f0_len;
     float sr, half_width;
-    // output: forward spectrum view, inverse frames [(b nch + ch) o_sb + t N + j]
-    float* out;
-    long o_sb, o_sf, o_st;
-    int o_cre, o_cim, nrep, nch;
-    const int* work;                // (b, t0, L, T_b, ch, padL)
+    float* frames;                  // [(b nch + ch) f_sb + t N + j]
+    long f_sb;
+    int nch;
+    const int* work;
 };
 struct HsOlaP {
     const float* frames;            // [(b nch + c) f_sb + t N + j]
@@ -612,7 +625,8 @@ struct HsCurvesP {
     long o_sb;
 };
 hipError_t launch_hs_basis(float* basis, const float* win, int Rpad, int Kpad, int nb, int N, int inv, hipStream_t st);
-hipError_t launch_hs_dft(const HsDftP& p, int n_entries, int row_tiles, hipStream_t st);
+hipError_t launch_hs_stft(const HsStftP& p, int n_entries, int row_tiles, hipStream_t st);
+hipError_t launch_hs_istft(const HsIstftP& p, int n_entries, int row_tiles, hipStream_t st);
 hipError_t launch_hs_ola(const HsOlaP& p, int B, long max_len, hipStream_t st);
 hipError_t launch_hs_conv(const HsConvP& p, int n_entries, hipStream_t st);
 hipError_t launch_hs_binmean(const HsBinMeanP& p, int B, int Tmax, hipStream_t st);

@@ -16,7 +16,6 @@ struct HsNetW {                             // one BaseNet
     HsConvW enc1, enc[4][2], aspp[5], bott, dec4, dec3, dec2, dec1, lconv, lproj, ldense;
     size_t whh = 0;
 };
-constexpr int HS_ROWS = 64;                 // hs_dft_kernel's basis rows per tile
 struct HsBasis {
     int N = 0, kind = 0;                    // kind 0: periodic Hann (VR), 1: Nuttall (_kth_harmonic)
     DevBuf<float> win, fwd, inv;
@@ -270,10 +269,10 @@ const HsBasis* hs_basis(dsd_handle* h, int N, int kind, hipStream_t st) {
     b.N = N;
     b.kind = kind;
     const int nb = N / 2 + 1;
-    b.fRpad = (2 * nb + HS_ROWS - 1) / HS_ROWS * HS_ROWS;
+    b.fRpad = (2 * nb + kDftRows - 1) / kDftRows * kDftRows;
     b.fKpad = N;
-    b.iRpad = (N + HS_ROWS - 1) / HS_ROWS * HS_ROWS;
-    b.iKpad = (2 * nb + 31) / 32 * 32;
+    b.iRpad = (N + kDftRows - 1) / kDftRows * kDftRows;
+    b.iKpad = (2 * nb + kDftTaps - 1) / kDftTaps * kDftTaps;
     const char* who = "hs_basis";
     if (b.win.reserve(h, N, who) || b.fwd.reserve(h, (size_t)b.fRpad * b.fKpad, who) || b.inv.reserve(h, (size_t)b.iRpad * b.iKpad, who))
         return nullptr;
@@ -612,6 +611,111 @@ int hs_execute(HsRun& R, std::vector<char>& up, size_t dT_off, const char* who, 
     return body();
 }
 
+// The STFT -> (mask) -> iSTFT -> overlap-add chain of dsd_hnsep_separate and dsd_base_harmonic.  The spectrum (and the
+// network's mask) is an HsT [b][bin][t][re of the C channels | im of the C channels]; the frames are [(b C + c)][t < T][N].
+struct HsDft {
+    dsd_handle* h;
+    hipStream_t st;
+    const HsBasis* bs;
+    std::string fam;                // "hnsep" / "base harmonic": the family in the launch error texts
+    int hop, B;
+    long Lmax;
+    size_t fw = 0, iw = 0, len = 0, off0 = 0;      // offsets in the uploaded block: work lists, samples and offset per item
+    int nfw = 0, niw = 0;
+};
+
+// the work lists (b, t0, L, T_b, channel, padL) per (item, 64-frame tile, channel): forward over fch channels with padL =
+// off0[b] (the padded position of sample 0), inverse over C channels; and the overlap-add's per-item L and off0
+void hs_dft_lists(HsDft& d, HsUpload& up, const std::vector<int>& Tp, const std::vector<int64_t>& L, const std::vector<int64_t>& off0,
+                  int fch, int C) {
+    std::vector<int> fw, iw;
+    for (int b = 0; b < d.B; ++b)
+        for (int t0 = 0; t0 < Tp[b]; t0 += kDftFrames) {
+            for (int c = 0; c < fch; ++c) fw.insert(fw.end(), {b, t0, (int)L[b], Tp[b], c, (int)off0[b]});
+            for (int c = 0; c < C; ++c) iw.insert(iw.end(), {b, t0, (int)L[b], Tp[b], c, 0});
+        }
+    d.nfw = (int)(fw.size() / 6);
+    d.niw = (int)(iw.size() / 6);
+    d.fw = up.add(fw.data(), fw.size() * 4);
+    d.iw = up.add(iw.data(), iw.size() * 4);
+    d.len = up.add(L.data(), d.B * 8);
+    d.off0 = up.add(off0.data(), d.B * 8);
+}
+
+// blk: the device copy of the uploaded block
+int hs_stft(const HsDft& d, const char* blk, const float* wav, long wav_sb, long wav_sc, bool reflect, const HsT& spec, int nrep) {
+    dsd_handle* h = d.h;
+    HsStftP p;
+    p.basis = d.bs->fwd.p;
+    p.N = d.bs->N;
+    p.nb = spec.F;
+    p.wav = wav;
+    p.wav_sb = wav_sb;
+    p.wav_sc = wav_sc;
+    p.H = d.hop;
+    p.reflect = reflect ? 1 : 0;
+    p.spec = spec.p;
+    p.s_sb = spec.bs();
+    p.s_sf = (long)spec.T * spec.C;
+    p.s_st = spec.C;
+    p.s_cim = spec.C / 2;
+    p.nrep = nrep;
+    p.work = (const int*)(blk + d.fw);
+    HS_LAUNCH(launch_hs_stft(p, d.nfw, d.bs->fRpad / kDftRows, d.st), (d.fam + " stft").c_str());
+    return DSD_OK;
+}
+
+// spectrum x mask -> frames -> out.  mask: the network's, or NULL for the f0 bin mask of f0[b f0_sb + t], f0_len[b] frames,
+// at sample rate sr.  T: frames per item (device); o_sc 0: the channels' mean
+int hs_istft_ola(const HsDft& d, const char* blk, const HsT& spec, const HsT* mask, const float* f0, long f0_sb, const int* f0_len,
+                 float sr, float* frames, const int* T, float* out, long o_sb, long o_sc) {
+    dsd_handle* h = d.h;
+    const int N = d.bs->N, C = spec.C / 2;
+    HsIstftP p = {};                // (the mask's strides stay 0 under the f0 bin mask)
+    p.basis = d.bs->inv.p;
+    p.Kpad = d.bs->iKpad;
+    p.N = N;
+    p.nb = spec.F;
+    p.spec = spec.p;
+    p.s_sb = spec.bs();
+    p.s_sf = (long)spec.T * spec.C;
+    p.s_st = spec.C;
+    p.s_cim = C;
+    p.mask = mask ? mask->p : nullptr;
+    if (mask) {
+        p.m_sb = mask->bs();
+        p.m_sf = (long)mask->T * mask->C;
+        p.m_st = mask->C;
+        p.m_cim = mask->C / 2;
+        p.mask_F = mask->F;
+    }
+    p.f0 = f0;
+    p.f0_sb = f0_sb;
+    p.f0_len = f0_len;
+    p.sr = sr;
+    p.half_width = 3.5f;
+    p.frames = frames;
+    p.f_sb = (long)spec.T * N;
+    p.nch = C;
+    p.work = (const int*)(blk + d.iw);
+    HS_LAUNCH(launch_hs_istft(p, d.niw, d.bs->iRpad / kDftRows, d.st), (d.fam + " istft").c_str());
+    HsOlaP op;
+    op.frames = frames;
+    op.f_sb = p.f_sb;
+    op.win = d.bs->win.p;
+    op.N = N;
+    op.H = d.hop;
+    op.nch = C;
+    op.T = T;
+    op.len = (const long*)(blk + d.len);
+    op.off0 = (const long*)(blk + d.off0);
+    op.out = out;
+    op.o_sb = o_sb;
+    op.o_sc = o_sc;
+    HS_LAUNCH(launch_hs_ola(op, d.B, d.Lmax, d.st), (d.fam + " overlap-add").c_str());
+    return DSD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -705,14 +809,8 @@ int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_sam
     HsRun R;
     size_t dT_off = 0;
     hs_setup(R, h, up, Tp, st, dT_off);
-    std::vector<int> fw, iw;
-    for (int b = 0; b < B; ++b)
-        for (int t0 = 0; t0 < Tp[b]; t0 += HS_ROWS) {
-            for (int c = 0; c < (repeat ? 1 : C); ++c) fw.insert(fw.end(), {b, t0, (int)L[b], Tp[b], c, (int)off0[b]});
-            for (int c = 0; c < C; ++c) iw.insert(iw.end(), {b, t0, (int)L[b], Tp[b], c, 0});
-        }
-    const size_t fw_off = up.add(fw.data(), fw.size() * 4), iw_off = up.add(iw.data(), iw.size() * 4);
-    const size_t L_off = up.add(L.data(), B * 8), o_off = up.add(off0.data(), B * 8);
+    HsDft d{h, st, bs, "hnsep", hop, B, (long)Lmax};
+    hs_dft_lists(d, up, Tp, L, off0, repeat ? 1 : C, C);
     const int Tal = R.Tal;
     return hs_execute(R, S.iw_host, dT_off, who, [&]() -> int {
         HsT spec, mask;
@@ -722,72 +820,11 @@ int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_sam
         spec.p = R.alloc((size_t)B * spec.bs());
         mask.p = R.alloc((size_t)B * mask.bs());
         float* frames = R.alloc((size_t)B * C * Tal * N);
-        if (!R.dry) {
-            HsDftP p;
-            memset(&p, 0, sizeof(p));
-            p.basis = bs->fwd.p;
-            p.Kpad = bs->fKpad;
-            p.K = N;
-            p.N = N;
-            p.nb = nb;
-            p.inv = 0;
-            p.wav = wav;
-            p.wav_sb = (long)wav_stride_b;
-            p.wav_sc = repeat ? 0 : (long)wav_stride_c;
-            p.H = hop;
-            p.reflect = 0;
-            p.out = spec.p;
-            p.o_sb = spec.bs();
-            p.o_sf = (long)Tal * 2 * C;
-            p.o_st = 2 * C;
-            p.o_cre = 0;
-            p.o_cim = C;
-            p.nrep = repeat ? C : 1;
-            p.work = (const int*)(R.iw + fw_off);
-            HS_LAUNCH(launch_hs_dft(p, (int)(fw.size() / 6), bs->fRpad / HS_ROWS, st), "hnsep stft");
-        }
+        if (!R.dry) HS_RC(hs_stft(d, R.iw, wav, (long)wav_stride_b, repeat ? 0 : (long)wav_stride_c, false, spec, repeat ? C : 1));
         HS_RC(hs_forward(R, spec.src(0, C), spec.src(C, C), mask.view(), C));
         if (R.dry) return DSD_OK;
-        HsDftP p;
-        memset(&p, 0, sizeof(p));
-        p.basis = bs->inv.p;
-        p.Kpad = bs->iKpad;
-        p.K = 2 * nb;
-        p.N = N;
-        p.nb = nb;
-        p.inv = 1;
-        p.spec = spec.p;
-        p.s_sb = spec.bs();
-        p.s_sf = (long)Tal * 2 * C;
-        p.s_st = 2 * C;
-        p.s_cre = 0;
-        p.s_cim = C;
-        p.mask = mask.p;
-        p.m_sb = mask.bs();
-        p.m_sf = (long)Tal * 2 * C;
-        p.m_st = 2 * C;
-        p.m_cim = C;
-        p.mask_F = nb;
-        p.out = frames;
-        p.o_sb = (long)Tal * N;
-        p.nch = C;
-        p.work = (const int*)(R.iw + iw_off);
-        HS_LAUNCH(launch_hs_dft(p, (int)(iw.size() / 6), bs->iRpad / HS_ROWS, st), "hnsep istft");
-        HsOlaP op;
-        op.frames = frames;
-        op.f_sb = (long)Tal * N;
-        op.win = bs->win.p;
-        op.N = N;
-        op.H = hop;
-        op.nch = C;
-        op.T = R.dT;
-        op.len = (const long*)(R.iw + L_off);
-        op.off0 = (const long*)(R.iw + o_off);
-        op.out = harmonic_out;
-        op.o_sb = (long)out_stride_b;
-        op.o_sc = C == 1 ? 0 : (long)out_stride_c;
-        HS_LAUNCH(launch_hs_ola(op, B, (long)Lmax, st), "hnsep overlap-add");
-        return DSD_OK;
+        return hs_istft_ola(d, R.iw, spec, &mask, nullptr, 0, nullptr, 0.f, frames, R.dT, harmonic_out, (long)out_stride_b,
+                            C == 1 ? 0 : (long)out_stride_c);
     });
 }
 
@@ -823,80 +860,21 @@ int dsd_base_harmonic(dsd_handle* h, const float* harmonic, int32_t B, int64_t n
     if (!bs) return fail(h, DSD_ENOMEM, "%s: the DFT bases could not be placed on the device", who);
     S.iw_host.clear();
     HsUpload up{S.iw_host};
-    std::vector<int> fw, iw;
-    for (int b = 0; b < B; ++b)
-        for (int t0 = 0; t0 < Tp[b]; t0 += HS_ROWS) {
-            fw.insert(fw.end(), {b, t0, (int)L[b], Tp[b], 0, N / 2});
-            iw.insert(iw.end(), {b, t0, (int)L[b], Tp[b], 0, 0});
-        }
     const size_t T_off = up.add(Tp.data(), B * 4), f0n_off = up.add(f0n.data(), B * 4);
-    const size_t fw_off = up.add(fw.data(), fw.size() * 4), iw_off = up.add(iw.data(), iw.size() * 4);
-    const size_t L_off = up.add(L.data(), B * 8), o_off = up.add(off0.data(), B * 8);
-    const size_t need = (size_t)B * nb * Tal * 2 + (size_t)B * Tal * N;
-    HS_RC(S.ws.reserve(h, need, who));
+    HsDft d{h, st, bs, "base harmonic", hop_size, B, (long)Lmax};
+    hs_dft_lists(d, up, Tp, L, off0, 1, 1);
+    HsT spec;
+    spec.F = nb;
+    spec.T = Tal;
+    spec.C = 2;
+    HS_RC(S.ws.reserve(h, (size_t)B * spec.bs() + (size_t)B * Tal * N, who));
     HS_RC(S.iws.reserve(h, up.buf.size(), who));
     const char* iws = S.iws.p;
     HIP_OK(h, hipMemcpyAsync(S.iws.p, S.iw_host.data(), S.iw_host.size(), hipMemcpyHostToDevice, st));
-    float *spec = S.ws.p, *frames = S.ws.p + (size_t)B * nb * Tal * 2;
-    HsDftP p;
-    memset(&p, 0, sizeof(p));
-    p.basis = bs->fwd.p;
-    p.Kpad = bs->fKpad;
-    p.K = N;
-    p.N = N;
-    p.nb = nb;
-    p.wav = harmonic;
-    p.wav_sb = (long)stride_b;
-    p.H = hop_size;
-    p.reflect = 1;
-    p.out = spec;
-    p.o_sb = (long)nb * Tal * 2;
-    p.o_sf = (long)Tal * 2;
-    p.o_st = 2;
-    p.o_cre = 0;
-    p.o_cim = 1;
-    p.nrep = 1;
-    p.work = (const int*)(iws + fw_off);
-    HS_LAUNCH(launch_hs_dft(p, (int)(fw.size() / 6), bs->fRpad / HS_ROWS, st), "base harmonic stft");
-    HsDftP q;
-    memset(&q, 0, sizeof(q));
-    q.basis = bs->inv.p;
-    q.Kpad = bs->iKpad;
-    q.K = 2 * nb;
-    q.N = N;
-    q.nb = nb;
-    q.inv = 1;
-    q.spec = spec;
-    q.s_sb = (long)nb * Tal * 2;
-    q.s_sf = (long)Tal * 2;
-    q.s_st = 2;
-    q.s_cre = 0;
-    q.s_cim = 1;
-    q.f0 = f0;
-    q.f0_sb = (long)f0_stride_b;
-    q.f0_len = (const int*)(iws + f0n_off);
-    q.sr = (float)sample_rate;
-    q.half_width = 3.5f;
-    q.out = frames;
-    q.o_sb = (long)Tal * N;
-    q.nch = 1;
-    q.work = (const int*)(iws + iw_off);
-    HS_LAUNCH(launch_hs_dft(q, (int)(iw.size() / 6), bs->iRpad / HS_ROWS, st), "base harmonic istft");
-    HsOlaP op;
-    op.frames = frames;
-    op.f_sb = (long)Tal * N;
-    op.win = bs->win.p;
-    op.N = N;
-    op.H = hop_size;
-    op.nch = 1;
-    op.T = (const int*)(iws + T_off);
-    op.len = (const long*)(iws + L_off);
-    op.off0 = (const long*)(iws + o_off);
-    op.out = out;
-    op.o_sb = (long)out_stride_b;
-    op.o_sc = 0;
-    HS_LAUNCH(launch_hs_ola(op, B, (long)Lmax, st), "base harmonic overlap-add");
-    return DSD_OK;
+    spec.p = S.ws.p;
+    HS_RC(hs_stft(d, iws, harmonic, (long)stride_b, 0, true, spec, 1));
+    return hs_istft_ola(d, iws, spec, nullptr, f0, (long)f0_stride_b, (const int*)(iws + f0n_off), (float)sample_rate,
+                        S.ws.p + (size_t)B * spec.bs(), (const int*)(iws + T_off), out, (long)out_stride_b, 0);
 }
 
 int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, const float* base, int32_t B,

@@ -25,17 +25,12 @@
 
 namespace dsd {
 
-constexpr int HS_FT = 64;           // DFT: frames per tile
-constexpr int HS_RT = 64;           // DFT: basis rows per tile
-constexpr int HS_KC = 32;           // DFT: taps per staged chunk
-constexpr int HS_KS = 8;            // DFT: taps per fresh MFMA accumulator (TwoSum of the partial sums, as mel_dft_kernel)
-constexpr int HS_LS = HS_KC + 4;    // LDS row stride
-
 // ---------------------------------------------------------------------------------------------
 // Forward (inv = 0): basis[r][j], r < Rpad, j < Kpad: row 2i = w[j] cos(2 pi i j / N), row 2i + 1 = -w[j] sin(...), i < nb.
 // Inverse (inv = 1): basis[j][r], j < Rpad (samples), r < Kpad: column 2i = a_i w[j] cos(2 pi i j / N) / N, column 2i + 1 =
 // -a_i w[j] sin(...) / N, a_0 = a_{N/2} = 1, else 2 (irfft: the imaginary parts of DC and Nyquist drop out as sin = 0).
-// The phase is reduced as the integer i j mod N before sincospif.
+// The phase is reduced as the integer i j mod N before sincospif.  (Kept apart from mel_basis_kernel, which computes its
+// Hann window on the device in fp32 with cospif: one kernel for both would change bits.)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hs_basis_kernel(float* __restrict__ basis, const float* __restrict__ win, int Rpad,
                                                        int Kpad, int nb, int N, int inv) {
@@ -60,110 +55,76 @@ __global__ __launch_bounds__(256) void hs_basis_kernel(float* __restrict__ basis
 }
 
 // ---------------------------------------------------------------------------------------------
-// One workgroup = one (item, 64-frame tile) x one 64-row tile of the basis; wave w owns rows 16w..16w+15, all 64 frames.
-// A[i = lane & 15][k = lane >> 4] = basis rows, B[k = lane >> 4][j = lane & 15] = frames; D[4 (lane >> 4) + reg][lane & 15].
-// Forward: frame t reads sample t H + j - padL of channel ch of the item (L samples), zero (pad_mode 'constant') or
-// reflected (torch's 'reflect') outside; registers 0 / 1 (2 / 3) are re / im of one bin, written to channels
-// [c_re + ch + r] / [c_im + ch + r], r < nrep (nrep > 1: one clip repeated to every channel, wav_sc = 0).
-// Inverse: frame t's K vector is (re, im) of the spectrum times the mask: the network's complex mask [bin min(i, mask_F - 1)]
-// (replicate pad), or the f0 bin mask of _kth_harmonic (frames t >= f0 frames: 0); rows are samples j -> frames buffer.
-// work: (b, t0, L, T_b, channel of the spectrum / mask (inverse), padL (forward)).
+// One workgroup = one (item, 64-frame tile, channel) entry x one 64-row tile of the basis, through dft_tile_walk
+// (dsd_device.h).  work: (b, t0, L, T_b, ch, padL).
+// Forward (INV = 0): frame t reads sample t H + j - padL of channel ch of the item (L samples), zero (pad_mode 'constant')
+// or reflected (torch's 'reflect') outside; accumulator registers 0 / 1 (2 / 3) are re / im of one bin, written to channels
+// [c] / [s_cim + c], ch <= c < ch + nrep (nrep > 1: one clip repeated to every channel, wav_sc = 0).
+// Inverse (INV = 1): frame t's K = 2 nb vector is (re, im) of the spectrum times the mask: the network's complex mask [bin min(i, mask_F - 1)]
+// (replicate pad), or the
+// f0 bin mask of _kth_harmonic (frames t >= f0 frames: 0); rows are samples j -> frames buffer.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void hs_dft_kernel(const HsDftP p) {
-    __shared__ float sA[HS_RT * HS_LS];
-    __shared__ float sB[HS_FT * HS_LS];
+template <int INV>
+__global__ __launch_bounds__(256) void hs_dft_kernel(const std::conditional_t<INV, HsIstftP, HsStftP> p) {
+    __shared__ float sA[kDftRows * kDftLS];
+    __shared__ float sB[kDftFrames * kDftLS];
     const int* e = p.work + 6 * blockIdx.x;
-    const int b = e[0], t0 = e[1], L = e[2], Tb = e[3], ch = e[4], padL = e[5];
-    const int rt = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float* __restrict__ bas = p.basis + (long)rt * HS_RT * p.Kpad;
+    const int b = e[0], t0 = e[1], Tb = e[3], ch = e[4];
+    const int rt = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     f32x4 hi[4], lo[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) hi[f] = lo[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < p.K; k0 += HS_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < (HS_RT * HS_KC) / 256; ++s) {
-            const int idx = tid + 256 * s, row = idx / HS_KC, kk = idx % HS_KC;
-            sA[row * HS_LS + kk] = bas[(long)row * p.Kpad + k0 + kk];
-        }
-#pragma unroll
-        for (int s = 0; s < (HS_FT * HS_KC) / 256; ++s) {
-            const int idx = tid + 256 * s, f = idx / HS_KC, kk = idx % HS_KC, j = k0 + kk, t = t0 + f;
-            float v = 0.f;
-            if (t < Tb && j < p.K) {
-                if (!p.inv) {
-                    long i = (long)t * p.H + j - padL;
-                    if (p.reflect) {
-                        if (i < 0) i = -i;
-                        if (i >= L) i = 2 * (long)(L - 1) - i;
-                    }
-                    if (i >= 0 && i < L) v = p.wav[(long)b * p.wav_sb + (long)ch * p.wav_sc + i];
-                } else {
-                    const int bin = j >> 1;
-                    const float* sp = p.spec + (long)b * p.s_sb + (long)bin * p.s_sf + (long)t * p.s_st;
-                    const float sr = sp[p.s_cre + ch], si = sp[p.s_cim + ch];
-                    float mr, mi;
-                    if (p.mask) {
-                        const float* mp = p.mask + (long)b * p.m_sb + (long)min(bin, p.mask_F - 1) * p.m_sf + (long)t * p.m_st;
-                        mr = mp[ch];
-                        mi = mp[p.m_cim + ch];
-                    } else {        // _kth_harmonic: center = f0 win / sr, [max(center - hw, 0), min(center + hw, n_specs))
-                        const float f0 = t < p.f0_len[b] ? p.f0[(long)b * p.f0_sb + t] : 0.f;
-                        const float center = f0 * (float)p.N / p.sr;
-                        const float st = fmaxf(center - p.half_width, 0.f), en = fminf(center + p.half_width, (float)p.nb);
-                        const float fb = (float)bin;
-                        mr = (t < p.f0_len[b] && center >= 1.f && fb >= st && fb < en) ? 1.f : 0.f;
-                        mi = 0.f;
-                    }
-                    v = (j & 1) ? sr * mi + si * mr : sr * mr - si * mi;
-                }
+    if constexpr (!INV) {
+        const int L = e[2], padL = e[5];
+        dft_tile_walk(p.basis + (long)rt * kDftRows * p.N, p.N, p.N, Tb - t0, sA, sB, [&](int f, int j) {
+            long i = (long)(t0 + f) * p.H + j - padL;
+            if (p.reflect) {
+                if (i < 0) i = -i;
+                if (i >= L) i = 2 * (long)(L - 1) - i;
             }
-            sB[f * HS_LS + kk] = v;
-        }
-        __syncthreads();
+            return i >= 0 && i < L ? p.wav[(long)b * p.wav_sb + (long)ch * p.wav_sc + i] : 0.f;
+        }, hi, lo);
+        const int bin0 = rt * (kDftRows / 2) + 8 * w + 2 * (lane >> 4);
 #pragma unroll
-        for (int half = 0; half < HS_KC / HS_KS; ++half) {
-            f32x4 part[4];
-#pragma unroll
-            for (int f = 0; f < 4; ++f) part[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = half * HS_KS / 4; ks < (half + 1) * HS_KS / 4; ++ks) {
-                const float a = sA[(16 * w + (lane & 15)) * HS_LS + 4 * ks + (lane >> 4)];
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const float bv = sB[(16 * f + (lane & 15)) * HS_LS + 4 * ks + (lane >> 4)];
-                    part[f] = mfma_16x16x4(a, bv, part[f]);
-                }
-            }
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = part[f][r], s = hi[f][r] + x, bp = s - hi[f][r];
-                    lo[f][r] += (hi[f][r] - (s - bp)) + (x - bp);
-                    hi[f][r] = s;
-                }
-        }
-    }
-    const int row0 = rt * HS_RT + 16 * w + 4 * (lane >> 4);
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int t = t0 + 16 * f + (lane & 15);
-        if (t >= Tb) continue;
-        if (!p.inv) {
+        for (int f = 0; f < 4; ++f) {
+            const int t = t0 + 16 * f + (lane & 15);
+            if (t >= Tb) continue;
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int bin = (row0 >> 1) + h;
+                const int bin = bin0 + h;
                 if (bin >= p.nb) continue;
-                float* o = p.out + (long)b * p.o_sb + (long)bin * p.o_sf + (long)t * p.o_st;
+                float* o = p.spec + (long)b * p.s_sb + (long)bin * p.s_sf + (long)t * p.s_st;
                 const float re = hi[f][2 * h] + lo[f][2 * h], im = hi[f][2 * h + 1] + lo[f][2 * h + 1];
                 for (int c = ch; c < ch + p.nrep; ++c) {
-                    o[p.o_cre + c] = re;
-                    o[p.o_cim + c] = im;
+                    o[c] = re;
+                    o[p.s_cim + c] = im;
                 }
             }
-        } else {
-            float* o = p.out + ((long)(b * p.nch + ch) * p.o_sb) + (long)t * p.N;
+        }
+    } else {
+        dft_tile_walk(p.basis + (long)rt * kDftRows * p.Kpad, p.Kpad, 2 * p.nb, Tb - t0, sA, sB, [&](int f, int j) {
+            const int t = t0 + f, bin = j >> 1;
+            const float* sp = p.spec + (long)b * p.s_sb + (long)bin * p.s_sf + (long)t * p.s_st;
+            const float sr = sp[ch], si = sp[p.s_cim + ch];
+            float mr, mi;
+            if (p.mask) {
+                const float* mp = p.mask + (long)b * p.m_sb + (long)min(bin, p.mask_F - 1) * p.m_sf + (long)t * p.m_st;
+                mr = mp[ch];
+                mi = mp[p.m_cim + ch];
+            } else {        // _kth_harmonic: center = f0 win / sr, [max(center - hw, 0), min(center + hw, n_specs))
+                const float f0 = t < p.f0_len[b] ? p.f0[(long)b * p.f0_sb + t] : 0.f;
+                const float center = f0 * (float)p.N / p.sr;
+                const float st = fmaxf(center - p.half_width, 0.f), en = fminf(center + p.half_width, (float)p.nb);
+                const float fb = (float)bin;
+                mr = (t < p.f0_len[b] && center >= 1.f && fb >= st && fb < en) ? 1.f : 0.f;
+                mi = 0.f;
+            }
+            return (j & 1) ? sr * mi + si * mr : sr * mr - si * mi;
+        }, hi, lo);
+        const int row0 = rt * kDftRows + 16 * w + 4 * (lane >> 4);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+            const int t = t0 + 16 * f + (lane & 15);
+            if (t >= Tb) continue;
+            float* o = p.frames + ((long)(b * p.nch + ch) * p.f_sb) + (long)t * p.N;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (row0 + r < p.N) o[row0 + r] = hi[f][r] + lo[f][r];
@@ -454,8 +415,12 @@ hipError_t launch_hs_basis(float* basis, const float* win, int Rpad, int Kpad, i
     hipLaunchKernelGGL(hs_basis_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, basis, win, Rpad, Kpad, nb, N, inv);
     return hipGetLastError();
 }
-hipError_t launch_hs_dft(const HsDftP& p, int n_entries, int row_tiles, hipStream_t st) {
-    hipLaunchKernelGGL(hs_dft_kernel, dim3((unsigned)n_entries, (unsigned)row_tiles), dim3(256), 0, st, p);
+hipError_t launch_hs_stft(const HsStftP& p, int n_entries, int row_tiles, hipStream_t st) {
+    hipLaunchKernelGGL(hs_dft_kernel<0>, dim3((unsigned)n_entries, (unsigned)row_tiles), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_hs_istft(const HsIstftP& p, int n_entries, int row_tiles, hipStream_t st) {
+    hipLaunchKernelGGL(hs_dft_kernel<1>, dim3((unsigned)n_entries, (unsigned)row_tiles), dim3(256), 0, st, p);
     return hipGetLastError();
 }
 hipError_t launch_hs_ola(const HsOlaP& p, int B, long max_len, hipStream_t st) {

@@ -204,7 +204,7 @@ int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int
         if (T < 1)
             return fail(h, DSD_EINVAL, "%s: item %d (%lld samples) is too short for N' = %d, W' = %d, H' = %d "
                         "(torch.stft / reflect pad raise)", who, b, (long long)L, g.N, g.W, g.H);
-        for (int64_t t0 = 0; t0 < T; t0 += 64) {
+        for (int64_t t0 = 0; t0 < T; t0 += kDftFrames) {
             const int e[5] = {b, (int)t0, (int)L, (int)T, (int)(G + t0)};
             work.insert(work.end(), e, e + 5);
         }
@@ -214,7 +214,7 @@ int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int
     const int n_entries = (int)(work.size() / 5);
     // bins the filterbank reads that this N' has: nvSTFT.py:76-80 zero-pads the bins past N'/2
     const int k_hi = std::min(ms.k_hi, g.N / 2), nb = std::max(0, k_hi - ms.k_lo + 1);
-    const int row_tiles = (2 * nb + 63) / 64, Kpad = (g.W + 31) / 32 * 32;
+    const int row_tiles = (2 * nb + kDftRows - 1) / kDftRows, Kpad = (g.W + kDftTaps - 1) / kDftTaps * kDftTaps;
     hipStream_t st = (hipStream_t)stream;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     float* basis = nullptr;
@@ -230,10 +230,10 @@ int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int
             MelBasis mb;
             mb.N = g.N;
             mb.W = g.W;
-            if (int rc = mb.dev.reserve(h, (size_t)row_tiles * 64 * Kpad, who)) return rc;
+            if (int rc = mb.dev.reserve(h, (size_t)row_tiles * kDftRows * Kpad, who)) return rc;
             basis = mb.dev.p;
             ms.bases.push_back(std::move(mb));
-            hipError_t e = launch_mel_basis(basis, row_tiles * 64, Kpad, ms.k_lo, nb, g.N, g.W, g.off, st);
+            hipError_t e = launch_mel_basis(basis, row_tiles * kDftRows, Kpad, ms.k_lo, nb, g.N, g.W, g.off, st);
             if (e != hipSuccess) return fail(h, DSD_EHIP, "mel basis launch failed: %s", hipGetErrorString(e));
         }
     }

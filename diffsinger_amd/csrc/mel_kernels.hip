@@ -10,12 +10,6 @@
 
 namespace dsd {
 
-constexpr int MEL_FT = 64;          // frames per tile
-constexpr int MEL_RT = 64;          // basis rows per tile (32 bins: re / im rows interleaved)
-constexpr int MEL_KC = 32;          // window taps per staged chunk
-constexpr int MEL_KS = 8;           // taps per fresh MFMA accumulator (see mel_dft_kernel)
-constexpr int MEL_LS = MEL_KC + 4;  // LDS row stride: the 16 rows x 4 taps of an MFMA operand read hit 64 distinct banks
-
 // ---------------------------------------------------------------------------------------------
 // basis[r][j], r < Rpad, j < Kpad: row 2i = w[j] cos(2 pi k (off + j) / N), row 2i + 1 = -w[j] sin(...), k = k_lo + i, for
 // the taps j < W of the periodic Hann window w[j] = 0.5 - 0.5 cos(2 pi j / W) (torch.hann_window), which torch.stft places
@@ -39,74 +33,27 @@ __global__ __launch_bounds__(256) void mel_basis_kernel(float* __restrict__ basi
 }
 
 // ---------------------------------------------------------------------------------------------
-// One workgroup = one (item, 64-frame tile) entry x one 64-row tile of the basis; wave w owns basis rows 16w..16w+15 and
-// all 64 frames (four 16x16 accumulators).  Operand maps of v_mfma_f32_16x16x4_f32: A[i = lane & 15][k = lane >> 4] (basis
-// rows), B[k = lane >> 4][j = lane & 15] (frames); D[row = 4 (lane >> 4) + reg][col = lane & 15], so registers 0 / 1 hold
-// the re / im rows of one bin and 2 / 3 those of the next: the magnitude needs no lane movement.
-// Accuracy: a bin the signal barely reaches still sees large partial sums along the window (leakage of the strong bins that
-// cancels by the end), and one fp32 accumulator over all W' taps carries their rounding into the result: 2.4e-4 in log-mel
-// at W' = 4096, 3x the reference's own fp32 FFT.  So each 8 taps go into a fresh accumulator (2 MFMAs) and the partial sums
-// are added with TwoSum into a (hi, lo) pair, which brings the error to the reference's level.
-// Frame t of item b reads padded sample t H + off + j, i.e. sample i = t H + off + j - padL of the item, reflected at
-// both ends of its own length L (torch's reflect pad: -i, 2 (L - 1) - i); a ragged item never reads past its end.
+// One workgroup = one (item, 64-frame tile) entry x one 64-row tile of the basis, through dft_tile_walk (dsd_device.h):
+// accumulator registers 0 / 1 hold the re / im rows of one bin and 2 / 3 those of the next, so the magnitude needs no lane
+// movement.  Frame t of item b reads padded sample t H + off + j, i.e. sample i = t H + off + j - padL of the item,
+// reflected at both ends of its own length L (torch's reflect pad: -i, 2 (L - 1) - i); a ragged item never reads past its end.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mel_dft_kernel(const MelDftP p) {
-    __shared__ float sA[MEL_RT * MEL_LS];
-    __shared__ float sB[MEL_FT * MEL_LS];
+    __shared__ float sA[kDftRows * kDftLS];
+    __shared__ float sB[kDftFrames * kDftLS];
     const int* e = p.work + 5 * blockIdx.x;
     const int b = e[0], t0 = e[1], L = e[2], Tb = e[3], g0 = e[4];
-    const int rt = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int rt = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float* __restrict__ x = p.wav + (long)b * p.wav_bstride;
-    const float* __restrict__ bas = p.basis + (long)rt * MEL_RT * p.Kpad;
     f32x4 hi[4], lo[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) hi[f] = lo[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < p.W; k0 += MEL_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < (MEL_RT * MEL_KC) / 256; ++s) {
-            const int idx = tid + 256 * s, row = idx / MEL_KC, kk = idx % MEL_KC;
-            sA[row * MEL_LS + kk] = bas[(long)row * p.Kpad + k0 + kk];
-        }
-#pragma unroll
-        for (int s = 0; s < (MEL_FT * MEL_KC) / 256; ++s) {
-            const int idx = tid + 256 * s, f = idx / MEL_KC, kk = idx % MEL_KC, j = k0 + kk, t = t0 + f;
-            float v = 0.f;
-            if (t < Tb && j < p.W) {
-                long i = (long)t * p.H + p.off + j - p.padL;
-                if (i < 0) i = -i;
-                if (i >= L) i = 2 * (long)(L - 1) - i;
-                v = x[i];
-            }
-            sB[f * MEL_LS + kk] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int half = 0; half < MEL_KC / MEL_KS; ++half) {
-            f32x4 part[4];
-#pragma unroll
-            for (int f = 0; f < 4; ++f) part[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = half * MEL_KS / 4; ks < (half + 1) * MEL_KS / 4; ++ks) {
-                const float a = sA[(16 * w + (lane & 15)) * MEL_LS + 4 * ks + (lane >> 4)];
-#pragma unroll
-                for (int f = 0; f < 4; ++f) {
-                    const float bv = sB[(16 * f + (lane & 15)) * MEL_LS + 4 * ks + (lane >> 4)];
-                    part[f] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bv, part[f], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {       // TwoSum: hi + lo carries the running sum to about 2 x 24 bits
-                    const float x = part[f][r], s = hi[f][r] + x, bp = s - hi[f][r];
-                    lo[f][r] += (hi[f][r] - (s - bp)) + (x - bp);
-                    hi[f][r] = s;
-                }
-        }
-    }
+    dft_tile_walk(p.basis + (long)rt * kDftRows * p.Kpad, p.Kpad, p.W, Tb - t0, sA, sB, [&](int f, int j) {
+        long i = (long)(t0 + f) * p.H + p.off + j - p.padL;
+        if (i < 0) i = -i;
+        if (i >= L) i = 2 * (long)(L - 1) - i;
+        return x[i];
+    }, hi, lo);
     // epilogue: |X| (nvSTFT.py:69-74 .abs()), then with a key shift * win_size / W' in torch's order (nvSTFT.py:80)
-    const int bin0 = rt * (MEL_RT / 2) + 8 * w + 2 * (lane >> 4);
+    const int bin0 = rt * (kDftRows / 2) + 8 * w + 2 * (lane >> 4);
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
         const int fr = 16 * f + (lane & 15);
@@ -130,8 +77,8 @@ __global__ __launch_bounds__(256) void mel_dft_kernel(const MelDftP p) {
 __global__ __launch_bounds__(256) void mel_project_kernel(const MelProjP p) {
     const int* e = p.work + 5 * blockIdx.x;
     const int b = e[0], t0 = e[1], Tb = e[3], g0 = e[4];
-    for (int idx = threadIdx.x; idx < MEL_FT * p.M; idx += 256) {
-        const int f = idx % MEL_FT, m = idx / MEL_FT, t = t0 + f;
+    for (int idx = threadIdx.x; idx < kDftFrames * p.M; idx += 256) {
+        const int f = idx % kDftFrames, m = idx / kDftFrames, t = t0 + f;
         if (t >= Tb) continue;
         const int lo = p.range[2 * m], hi = min(p.range[2 * m + 1], p.nb), woff = p.woff[m];
         float s = 0.f;

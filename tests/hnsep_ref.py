@@ -29,20 +29,26 @@ def nuttall(n):
     return 0.355768 - 0.487396 * np.cos(ph) + 0.144232 * np.cos(2 * ph) - 0.012604 * np.cos(3 * ph)
 
 
-def stft(x, n_fft, hop, win, mode):
-    """torch.stft(center=True): pad n_fft / 2 (mode 'constant' or 'reflect'), frames of hop -> [bins, frames] complex."""
-    xp = np.pad(np.asarray(x, np.float64), n_fft // 2, mode=mode)
+def stft(x, n_fft, hop, win, mode, dtype=np.float64):
+    """torch.stft(center=True): pad n_fft / 2 (mode 'constant' or 'reflect'), frames of hop -> [bins, frames] complex.
+    dtype float32: the same steps in single precision (numpy's pocketfft keeps float32 input in float32)."""
+    xp = np.pad(np.asarray(x, dtype), n_fft // 2, mode=mode)
+    win = np.asarray(win, dtype)
     n = 1 + (len(xp) - n_fft) // hop
     fr = np.stack([xp[t * hop:t * hop + n_fft] * win for t in range(n)])
-    return np.fft.rfft(fr, axis=1).T
+    spec = np.fft.rfft(fr, axis=1).T
+    assert spec.dtype == np.result_type(dtype, np.complex64), spec.dtype
+    return spec
 
 
-def istft(spec, n_fft, hop, win, length=None):
+def istft(spec, n_fft, hop, win, length=None, dtype=np.float64):
     """torch.istft(center=True): irfft, window, overlap-add / sum of window^2, trim n_fft / 2 (and to `length`)."""
+    win = np.asarray(win, dtype)
     fr = np.fft.irfft(spec.T, n=n_fft, axis=1) * win
+    assert fr.dtype == dtype, fr.dtype
     n = spec.shape[1]
     total = n_fft + hop * (n - 1)
-    y, env = np.zeros(total), np.zeros(total)
+    y, env = np.zeros(total, dtype), np.zeros(total, dtype)
     for t in range(n):
         y[t * hop:t * hop + n_fft] += fr[t]
         env[t * hop:t * hop + n_fft] += win ** 2
@@ -85,12 +91,13 @@ def base_f0(f0, n_samples, hop):
     return interp_f0(f0)[0]
 
 
-def base_harmonic(h, f0, sr, hop, win_size, f0_interp=None):
-    """_kth_harmonic(0) on the harmonic part h (float64)."""
+def base_harmonic(h, f0, sr, hop, win_size, f0_interp=None, dtype=np.float64):
+    """_kth_harmonic(0) on the harmonic part h (float64; dtype float32: STFT and iSTFT in single precision with the same
+    bin mask, the floor a float32 implementation is measured against)."""
     n = len(h)
     f0 = base_f0(f0, n, hop) if f0_interp is None else np.asarray(f0_interp, np.float64)
     w = nuttall(win_size)
-    spec = stft(h, win_size, hop, w, "reflect")
+    spec = stft(h, win_size, hop, w, "reflect", dtype)
     nb, nt = spec.shape
     idx = np.arange(nb)[None]
     center = (f0 * win_size / sr)[:, None]
@@ -98,7 +105,7 @@ def base_harmonic(h, f0, sr, hop, win_size, f0_interp=None):
     mk = np.zeros((nt, nb), bool)
     k = min(nt, len(f0))
     mk[:k] = m[:k]
-    return istft(spec * mk.T, win_size, hop, w, length=n)
+    return istft(spec * mk.T, win_size, hop, w, length=n, dtype=dtype)
 
 
 def rms(y, hop, win):

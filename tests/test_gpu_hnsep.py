@@ -141,6 +141,30 @@ def test_base_harmonic(g19):
     assert np.abs(got).max() > 0.01
 
 
+def test_base_harmonic_win96_ragged():
+    """win_size 96, hop 24: the window is no multiple of the 64-row tile, so the inverse DFT's second row tile is partly
+    past the frame (rows 96..127 are not written), and 2 (win / 2 + 1) = 98 leaves the forward one partly empty too.  Two
+    clips of 0.2 s and 0.35 s (368 and 644 frames: 6 and 11 frame tiles, the last ones partial) in one ragged call are
+    bit-identical to their lone calls and within twice the float32 restatement's own error of the float64 oracle."""
+    sp, _, _ = sep_of("small", 1900)
+    hop, win = 24, 96
+    lens = [int(0.2 * SR), int(0.35 * SR)]
+    hs = [mel_ref.waveform(1985 + i, n, SR).astype(np.float32) for i, n in enumerate(lens)]
+    # center = f0 win / sr from 2.8 to 4.1 bins (the band's edges cross bins), an unvoiced gap, f0 shorter than the frames
+    f0s = [1600.0 + 300.0 * np.sin(np.arange(n // hop + 1 - 5) / 9.0 + i) for i, n in enumerate(lens)]
+    for f0 in f0s:
+        f0[40:60] = 0.0
+    rag = sp.base_harmonic_ragged(hs, f0s, SR, hop, win)
+    for h, f0, r in zip(hs, f0s, rag):
+        assert torch.equal(r, sp.base_harmonic_ragged([h], [f0], SR, hop, win)[0])
+        want = hnsep_ref.base_harmonic(h, f0, SR, hop, win)
+        floor = float(np.abs(hnsep_ref.base_harmonic(h, f0, SR, hop, win, dtype=np.float32) - want).max())
+        err = float(np.abs(r.cpu().numpy() - want).max())
+        print(f"base harmonic win 96, {len(h)} samples: error {err:.3g}, float32 restatement {floor:.3g}, peak {np.abs(want).max():.3g}")
+        assert np.abs(want).max() > 0.01 and floor > 0
+        assert err <= 2 * floor, (err, floor)
+
+
 def test_curves():
     """energy, breathiness, voicing (dB) and tension in every domain against the float64 restatement, with `length`
     both past the RMS frames (zero pad, then the top-db clamp) and short of them (crop)."""
