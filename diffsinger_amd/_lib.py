@@ -32,6 +32,7 @@ EXPORTS = [
     "dsd_rmvpe_infer",
     "dsd_hnsep_create", "dsd_hnsep_num_frames", "dsd_hnsep_mask", "dsd_hnsep_separate", "dsd_base_harmonic",
     "dsd_variance_curves",
+    "dsd_length_regulate", "dsd_frame_curve",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -195,6 +196,8 @@ def _load():
     lib.dsd_base_harmonic.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), i32, i32, i32, vp, i64, vp]
     lib.dsd_variance_curves.argtypes = [vp, vp, vp, vp, i32, i64, C.POINTER(i64), i32, i32, C.POINTER(i64), i32, i32, vp, vp, vp,
                                         vp, i64, vp]
+    lib.dsd_length_regulate.argtypes = [i32, vp, i32, i32, i32, vp, vp]
+    lib.dsd_frame_curve.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_float), i32, vp, vp, vp, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

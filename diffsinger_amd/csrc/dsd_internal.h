@@ -413,6 +413,25 @@ hipError_t launch_ln_merge(const float* lnpart, int mtiles, int C, int B, int T,
 hipError_t launch_dwconv(const float* src, float* dst, long bstride, int rstride, int C, int B, int T, const int* lens,
                          const float* w, const float* bias, int ksz, int act, const float* prelu, hipStream_t stream);
 
+// frames_kernels.hip: durations -> frames (dsd_length_regulate) and the smoothed frame-level MIDI curve with its retake
+// blend (dsd_frame_curve).  A FrameCurveP launch covers up to kCurveItems batch items starting at item b0; the smoothing
+// taps and the items' lengths travel in the kernel arguments, so neither entry owns device memory.
+constexpr int kRegulateMaxTokens = 2048;    // the encoders' own token limit
+constexpr int kCurveMaxTaps = 255;
+constexpr int kCurveItems = 64;
+struct FrameCurveP {
+    const float* note_midi;         // [B][N]
+    const long long* mel2note;      // [B][T]
+    const float* pitch;             // [B][T]
+    const unsigned char* retake;    // [B][T]
+    float *base, *blend, *delta;    // [B][T] each
+    int N, T, K, b0;
+    int len[kCurveItems];
+    float w[kCurveMaxTaps];
+};
+hipError_t launch_length_regulate(const long long* dur, int B, int L, int T, long long* mel2x, hipStream_t st);
+hipError_t launch_frame_curve(const FrameCurveP& p, int items, hipStream_t st);
+
 // The DFT tile of mel_dft_kernel and hs_dft_kernel (dsd_device.h, dft_tile_walk), as far as the host sizes bases and work
 // lists by it
 constexpr int kDftFrames = 64;      // frames per tile (one work-list entry)

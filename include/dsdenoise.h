@@ -309,6 +309,46 @@ typedef struct dsd_assemble_args {
 
 int dsd_cond_assemble(const dsd_assemble_args* args, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Duration-to-frame stages of the deployment twins (deployment/modules/): what an editor's staged calls do between the
+ * token-level encoders and a frame-level condition.  Both entries are handle-free like dsd_cond_assemble: `device` is
+ * the HIP device index, nothing has weights, and neither keeps device memory.
+ * ------------------------------------------------------------------------------------------ */
+/*
+ * Replaces: LengthRegulator.forward(dur) (deployment/modules/fastspeech2.py:31-40).
+ *   dur      [B, L] int64 on the device, 1 <= L <= 2048 (the encoders' token limit)
+ *   mel2x    [B, T] int64 on the device: frame p of item b holds i + 1 for the token i with
+ *            cumsum(dur)[i - 1] <= p < cumsum(dur)[i], and 0 at or past the item's total (the reference's masked sum adds
+ *            nothing there).  A zero duration owns no frame and is skipped, as in the reference.
+ * T is the caller's: the reference sizes its output by the largest total of the batch, which is a device read-back; pass
+ * that total to get its shape, or the frame count of the curves the result will be used with.  Durations past T are cut.
+ * B < 1, L outside [1, 2048] or T < 1 is DSD_EINVAL.  The durations themselves are not read back: non-negative values are
+ * the caller's contract (a negative one counts as 0 here, where the reference would shift every later token).
+ */
+int dsd_length_regulate(int32_t device, const int64_t* dur, int32_t B, int32_t L, int32_t T, int64_t* mel2x, void* stream);
+/*
+ * Replaces: the curve part of DiffSingerVarianceONNX.forward_pitch_preprocess (deployment/modules/toplevel.py:251-258)
+ * with the smoothing operator of build_smooth_op (:179-194):
+ *   frame_midi[t] = pad(note_midi, [1, 0])[mel2note[t]]            forward_mel2x_gather with x_dim=None (:214-222)
+ *   base[t]       = sum_k weights[k] * frame_midi[clamp(t - (K - 1) / 2 + k, 0, len - 1)]
+ *                   Conv1d(1, 1, K, bias=False, padding='same', padding_mode='replicate'): (K - 1) / 2 frames of padding
+ *                   in front and the rest behind, so an even K looks one frame further ahead than back
+ *   blend[t]      = base[t] * retake[t] + pitch[t] * !retake[t]     the base pitch without a melody encoder (:257)
+ *   delta[t]      = (pitch[t] - base[t]) * !retake[t]               the delta pitch with one (:254); its base pitch is base
+ * All three outputs are always written; the caller picks the form its model uses.
+ *   note_midi [B, N] fp32, mel2note [B, T] int64 (an index outside [1, N] reads 0), pitch [B, T] fp32, retake [B, T] bytes
+ *   (non-zero = retake); base_out, blend_out, delta_out [B, T] fp32; all on the device
+ *   lengths   HOST array of B frame counts in [0, T], or NULL (every item has T frames): item b replicates at its own
+ *             last frame, nothing at or past lengths[b] is read, and its outputs there are 0
+ *   weights   HOST array of the K taps, 1 <= K <= 255.  The reference's are sin(pi * linspace(0, 1, K)) in fp32 divided
+ *             by their fp32 sum, K = round(midi_smooth_width * audio_sample_rate / hop_size); they travel in the launch's
+ *             arguments, so any K costs the same and nothing is cached.  (K = 1 makes that 0 / 0: the reference's
+ *             operator is NaN there, and so is this one when given the same tap.)
+ */
+int dsd_frame_curve(int32_t device, const float* note_midi, const int64_t* mel2note, const float* pitch,
+                    const uint8_t* retake, int32_t B, int32_t N, int32_t T, const int32_t* lengths, const float* weights,
+                    int32_t K, float* base_out, float* blend_out, float* delta_out, void* stream);
+
 /*
  * NSF-HiFiGAN generator (the step after the loop: mel -> waveform).  The constructor arguments are the fields of the
  * checkpoint's config.json that Generator.__init__ reads (modules/nsf_hifigan/models.py:207-260), `mini_nsf: false`.
