@@ -1024,11 +1024,22 @@ int build_packed(dsd_handle* h) {
     if (wn) {
         h->g_conv.resize(L);
         h->g_outp.resize(L);
+        h->g_wino.clear();
+        if (C == 256) h->g_wino.resize(L);      // the only width wn_rowsplit.hip runs (narrower networks arrive here padded to it)
         for (int l = 0; l < L; ++l) {
             const std::string p = "residual_layers." + std::to_string(l) + ".";
             const HostTensor* t = &W(h, p + "dilated_conv.weight");    // [2C, C, 3]
             WGet w = [t, C](int r, int k, int tap) { return (double)t->data[((size_t)r * C + k) * 3 + tap]; };
             h->g_conv[l] = pack_gemm(h, 2 * C, C, 3, C, w, nullptr);
+            if (!h->g_wino.empty()) {
+                // Winograd F(2,3) along time: G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2, formed in double
+                // and rounded once; packed as a 4-"tap" matrix in the same block order (wn_conv_wq_kernel)
+                WGet wG = [w](int r, int k, int i) {
+                    const double g0 = w(r, k, 0), g1 = w(r, k, 1), g2 = w(r, k, 2);
+                    return i == 0 ? g0 : i == 1 ? 0.5 * (g0 + g1 + g2) : i == 2 ? 0.5 * (g0 - g1 + g2) : g2;
+                };
+                h->g_wino[l] = pack_gemm(h, 2 * C, C, 4, C, wG, nullptr);
+            }
             auto b = bias_of(p + "output_projection.bias");
             h->g_outp[l] = pack_gemm(h, 2 * C, C, 1, 0, conv1(p + "output_projection.weight"), &b);
         }
@@ -1741,14 +1752,19 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         p.first_layer = (l == 0);
     };
     // the row-split pair (rows per workgroup: 64 = wn_rowsplit.hip, else wn_rows.hip) on the tiles of `p`; class keys 200 + v / 300 + v
-    auto rowsplit = [&](const WnLayerP& p, int bn, int rows, int v, double fr) {
-        const int q = h->opts.rs_conv_q;
-        int r = timed_launch(h, 200 + v, fl_conv * fr, 16.0 * C * fr, "row-split WaveNet layer", [&] {
-            return rows > 64 ? launch_wn_rows(p, 0, C, B, rows, st) : launch_wn_rowsplit(p, 0, C, B, bn, q, st);
+    // The conv's layout is chosen per layer (wn_rowsplit_conv_layout): its Winograd form has a class of its own (250 + v) and
+    // reads the layer's Winograd matrix.  Its FLOPs stay the direct convolution's 3 taps - the work the layer asks for - so the
+    // class's rate against the MFMA peak is an EFFECTIVE rate (the kernel issues 4 products per output pair, 2/3 of the MFMAs).
+    auto rowsplit = [&](const WnLayerP& p, int l, int bn, int rows, int v, double fr) {
+        const int lay = rows > 64 ? 0 : wn_rowsplit_conv_layout(p, B, bn, h->opts.rs_conv_q);
+        WnLayerP pc = p;
+        if (lay == 2) pc.Aconv = h->blob.p + h->g_wino[l].a_off;
+        int r = timed_launch(h, (lay == 2 ? 250 : 200) + v, fl_conv * fr, 16.0 * C * fr, "row-split WaveNet layer", [&] {
+            return rows > 64 ? launch_wn_rows(pc, 0, C, B, rows, st) : launch_wn_rowsplit(pc, 0, C, B, bn, lay, st);
         });
         if (r) return r;
         return timed_launch(h, 300 + v, fl_out * fr, 20.0 * C * fr, "row-split WaveNet layer", [&] {
-            return rows > 64 ? launch_wn_rows(p, 1, C, B, rows, st) : launch_wn_rowsplit(p, 1, C, B, bn, q, st);
+            return rows > 64 ? launch_wn_rows(p, 1, C, B, rows, st) : launch_wn_rowsplit(p, 1, C, B, bn, lay, st);
         });
     };
     if (!pl.segs.empty()) {
@@ -1777,7 +1793,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                     rc = timed_launch(h, 100 + vkey, (fl_conv + fl_out) * fr, 24.0 * C * fr, "fused WaveNet layer",
                                       [&] { return launch_wn_layer(p, C, B, st, sg.bn); });
                 } else {
-                    rc = rowsplit(p, sg.bn, sg.rows, vkey, fr);
+                    rc = rowsplit(p, l, sg.bn, sg.rows, vkey, fr);
                 }
                 if (rc) return rc;
             }
@@ -1794,7 +1810,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 layer_params(p, l, form.rs_bn);
                 p.xin = h->xh; p.xout = h->xh; p.z = h->z;
                 if (ragged) { p.lens = h->lens_dev.p; p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
-                if ((rc = rowsplit(p, form.rs_bn, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
+                if ((rc = rowsplit(p, l, form.rs_bn, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
                 continue;
             }
             GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, ST_FILM, EP_GATE, dil, false, form.rs_pair);

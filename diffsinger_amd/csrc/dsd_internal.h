@@ -36,7 +36,7 @@ struct PathOpts {
     int wn_plan = -1;       // DSD_WN_PLAN         0: one launch shape per layer (no mixed plans, no wide row tiles; whole-layer 16-frame
                             //                     fused tiles stay allowed), 1/unset: mixed plans (plan_denoise)
     int rowsplit = -1;      // DSD_ROWSPLIT        0: never wn_rowsplit.hip
-    int rs_conv_q = -1;     // DSD_RS_CONV_Q       0 / 1: K-half / K-quarter layout of the row-split conv (launch_wn_rowsplit)
+    int rs_conv_q = -1;     // DSD_RS_CONV_Q       0 / 1: K-half / K-quarter layout of the row-split conv, 2: its Winograd form (wn_rowsplit_conv_layout)
     int rs_rows = -1;       // DSD_RS_ROWS         64 / 128 / 256: rows per workgroup of the row-split pair
     int edge = -1;          // DSD_EDGE            0: never wn_edge.hip, 1: on every grid
     int lynx_resident = -1; // DSD_LYNX_RESIDENT   0: never lynx_layer.hip, 1: on every supported grid
@@ -216,8 +216,10 @@ bool wn_layer_supported(int C, int dil);
 hipError_t wn_layer_init_all();
 // wn_rowsplit.hip: the same layer as two launches with the 2C rows split over 2C / 64 workgroups per 32-frame tile, for
 // grids too small for full-row tiles.  which = 0: conv + FiLM + gate (xin -> z); 1: out-proj + residual / skip (in place
-// when xout == xin)
-hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, int conv_q, hipStream_t st);   // conv_q: DSD_RS_CONV_Q
+// when xout == xin).  layout = wn_rowsplit_conv_layout(p, batch, bn, DSD_RS_CONV_Q): 0 / 1 the direct K-half / K-quarter conv, 2 the
+// K-quarter conv on Winograd F(2,3) operands - p.Aconv is then the layer's Winograd matrix (4 products, api.hip g_wino)
+int wn_rowsplit_conv_layout(const WnLayerP& p, int batch, int bn, int conv_q);
+hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, int layout, hipStream_t st);
 hipError_t wn_rowsplit_init_all();
 bool wn_rowsplit_supported(int C, int dil, long Ts);
 

@@ -469,6 +469,224 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
     RS_STAMP(0, 5);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Conv, K-quarter layout on WINOGRAD F(2,3) operands (DSD_RS_CONV_Q = 2): the outputs y[t], y[t + d] (d = the dilation) share
+// the inputs x[t - d], x[t], x[t + d], x[t + 2d] and take 4 products instead of 6.  With g0, g1, g2 the tap matrices [2C x C]:
+//   G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2                 (host: p.Aconv, packed with 4 "taps")
+//   D0 = x[t-d] - x[t+d], D1 = x[t] + x[t+d], D2 = x[t+d] - x[t], D3 = x[t] - x[t+2d]  (x = FiLM-added, zero-padded: staging)
+//   m_i = G_i D_i;   y[t] = m0 + m1 + m2,  y[t+d] = m1 - m2 - m3                        (tail)
+// A 32-frame tile is 16 pairs for d = 1, 2, 4, 8 (2d divides 32): pair p = k d + j (j < d) is frame f(p) = 2 d k + j = p + d (p / d) of
+// the tile with its partner at f(p) + d.  The three taps x two 16-frame column blocks of wn_conv_rq_kernel become four products
+// x ONE 16-pair column block: a wave walks 16 steps of 8 MFMAs (128) instead of 12 of 16 (192), with one B-fragment LDS read per
+// two MFMAs as there.  Step order inside a quarter: [32-channel half][product][k16 of the half]; within a step the two row
+// blocks' accumulators alternate.
+// LDS holds the TRANSFORMED tile [C][4 products x 16 pairs] (row stride 80 = 16 mod 64).  The transform runs in the staging
+// threads from registers: a thread owns (row, 4 consecutive pair columns) and loads the four float4 of x that hold their 16
+// inputs - for d <= 4 the 16 consecutive frames from tile frame 2 p0 - 4 on, for d = 8 the float4 at f(p0) - 8, f(p0), + 8, + 16 -
+// 4096 float4 loads per workgroup against the direct form's 3072 (the overlaps come from L2).  Early / late rows as in the
+// direct kernel: channels [0, 32) of every chunk before the walk, the others fetched behind the first two steps, written
+// after step LW, barrier after LB (step 7 fetches step 8's operands, the first of the second half).
+// Tail: the output transform is linear, so every wave applies it to its own quarter's partial products in registers and writes
+// the two outputs of a pair into its quarter's tile at their frames; reduction, gate and store are then the direct kernel's.
+// (First version: the four m tiles [64][64] in LDS, transform in the gate threads - twice the transpose writes and three times
+// the reads: tail 3.5 k cycles against the direct kernel's 2.6 k.)
+// Measured: 9.2 -> 8.4 us per launch at the headline.  The walk takes ~790 cycles per step, not the 512 of its
+// MFMAs: the four products stream 262 KB of weights per workgroup (direct: 196 KB) and a step's 16 wave-level weight loads per
+// CU at ~50 cycles each are now what bounds it.
+// ---------------------------------------------------------------------------------------------------------------
+template <int DIL, int RAG>
+__global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
+    constexpr int BN = 32, HL = 8, SX = 80, ES = 36;            // (shadow the constants of the K-half kernels)
+    static_assert(DIL == 1 || DIL == 2 || DIL == 4 || DIL == 8, "2 d divides the 32-frame tile, halo 8");
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    RS_STAMP(0, 6);
+    wn_pin_args(p);
+    RS_STAMP(0, 7);
+    constexpr int NS = NCH * 16;                    // weight blocks per packed row block: [chunk][product][k16 in chunk]
+    constexpr int NQ = 16;                          // steps per wave (one chunk)
+    constexpr int LW = 5, LB = 6;                   // late rows: written after step LW, barrier after step LB, read from step 8 on
+    constexpr int CPS = 10;                         // the conditioner projection's two loads: steps CPS and CPS + 1
+    static_assert(LW >= 2 && LW <= LB && LB <= 6 && CPS >= 2 && CPS <= 14, "step 7 fetches step 8's operands");
+    float* xs = lds;                                 // [C][SX]: column 16 i + pair = D_i
+    float* et = lds + C * SX;                        // [4 quarters][64][ES]: FiLM vector first, the quarters' accumulators last
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = wave >> 1, wr = wave & 1;
+    const int lrow = lane >> 4, lcol = lane & 15, rq = lrow * 4;
+    const int work = xcd_work();
+    const int rest0 = work / MT, mtile = work - rest0 * MT;
+    const int rest = RAG ? p.cgmap[rest0] : rest0 + p.tile0;
+    const int b = fdiv_floor(rest, p.inv_tiles_per_b);
+    const int t0 = (rest - b * p.tiles_per_b) * BN;
+    const int Tb = (RAG && p.lens) ? p.lens[b] : p.T;
+    const int Ts = p.Ts;
+    const int bu = __builtin_amdgcn_readfirstlane(b), t0u = __builtin_amdgcn_readfirstlane(t0);
+    RS_STAMP(0, 0);
+
+    // ---------------- prologue: the first 32 channels of every chunk, FiLM vector, step 0's weights ----------------
+    const __amdgpu_buffer_rsrc_t r_x = rsrc(p.xin + (long)bu * p.x_bstride + (t0u - HL));
+    const __amdgpu_buffer_rsrc_t r_f = rsrc(p.film + p.film_col0 + bu * p.film_colb);
+    float fmine = 0.f;                                           // 256 values: the first four waves fetch them (wave-uniform branch)
+    if (wave < 4) fmine = ld1(r_f, tid * p.film_cstride * 4, 0);
+    // staging task of a thread: pair columns [4 pg, 4 pg + 4) of one row of a 128-row set; late = 0: channels [0, 32) of each
+    // chunk, 1: [32, 64).  Its float4 u = 0 .. 3 of the 48-frame window (frame t0 - 8 + 4 c4 + e)
+    const int pg = tid & 3;
+    auto x_row = [&](int late) {
+        const int re = tid >> 2;
+        return (re >> 5) * 64 + (re & 31) + 32 * late;
+    };
+    auto x_c4 = [&](int u) { return DIL == 8 ? 4 * (pg >> 1) + (pg & 1) + 2 * u : 2 * pg + 1 + u; };
+    f32x4 sv[4], svl[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) sv[u] = ld4(r_x, row_ts(x_row(0), Ts) + x_c4(u) * 16, 0);
+    RS_PIN();
+    // this wave's two row blocks: packed blocks 4 mtile + 2 wr (gate rows) and + 1 (filter rows) of the same 16 channels;
+    // local step t of quarter kq = block 16 kq + product * 4 + k16 of either
+    const __amdgpu_buffer_rsrc_t r_w = rsrc(p.Aconv + ((long)(4 * mtile + 2 * wr) * NS + 16 * kq) * 256);
+    const int wl = lane * 16;
+    auto blk = [](int t) { return ((t % 8) / 2) * 4 + (t / 8) * 2 + (t % 2); };
+    f32x4 W[3][2];
+    auto w_load = [&](int t, int rb) {
+        const int g = blk(t);
+        W[t % 3][rb] = ld4(r_w, wl + (g & 3) * 1024, (g >> 2) * 4096 + rb * NS * 1024);
+    };
+    w_load(0, 0);
+    w_load(0, 1);
+    RS_PIN();
+    // the hoisted conditioner projection (+ biases) of this tile's 32 channels, row-major float4 for the gate below:
+    // thread (of the first 256; the others hold a copy) -> channel gcw, frames 4 gc4
+    const int gcw = (tid & 255) >> 3, gc4 = tid & 7;
+    const int gch = 32 * mtile + gcw;
+    const __amdgpu_buffer_rsrc_t r_c = rsrc(p.cp + (long)bu * p.cp_bstride + t0u);
+    f32x4 cpg = f32x4{0.f, 0.f, 0.f, 0.f}, cpf = cpg;
+    RS_STAMP(0, 1);
+    if (wave < 4) et[tid] = fmine;
+    __syncthreads();
+    const float fa0 = et[x_row(0)], fa1 = et[x_row(1)];
+    const bool inner = t0u >= HL && t0u + BN + HL <= __builtin_amdgcn_readfirstlane(Tb);      // no frame of the window is padding (uniform)
+    // FiLM add, then the zero padding (wavenet.py:36-38), then the input transform, then LDS
+    auto stage_write = [&](const f32x4 (&v)[4], int late) {
+        const float fa = late ? fa1 : fa0;
+        float xv[16];
+        if (inner) {                                             // (most tiles: no compare / select per element)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[4 * u + e] = v[u][e] + fa;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int t = t0 - HL + x_c4(u) * 4 + e;
+                    xv[4 * u + e] = (t >= 0 && t < Tb) ? v[u][e] + fa : 0.f;
+                }
+        }
+        f32x4 D[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                            // pair 4 pg + q: x[t - d], x[t], x[t + d], x[t + 2d] = xv[a - d .. a + 2d]
+            const int a = DIL == 8 ? 4 + q : 4 + q + DIL * (q / DIL);
+            const int sd = DIL == 8 ? 4 : DIL;
+            const float xm = xv[a - sd], x0 = xv[a], x1 = xv[a + sd], x2 = xv[a + 2 * sd];
+            D[0][q] = xm - x1;
+            D[1][q] = x0 + x1;
+            D[2][q] = x1 - x0;
+            D[3][q] = x0 - x2;
+        }
+        float* dst = xs + x_row(late) * SX + 4 * pg;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<f32x4*>(dst + 16 * i) = D[i];
+    };
+    // (the FiLM values are in registers: the barrier below also orders these reads before the tail's writes to `et`)
+    stage_write(sv, 0);
+    __syncthreads();
+    RS_STAMP(0, 2);
+
+    // ---------------- K walk ----------------
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[rb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* bt = xs + (kq * 64 + lrow) * SX + lcol;
+    float bq[2][4];
+    auto read_b1 = [&](float (&bv)[4], int t, int j) {           // the pair column block of k4 step j of local step t
+        const int i = (t % 8) / 2, k16 = (t / 8) * 2 + (t % 2);
+        bv[j] = bt[(k16 * 16 + j * 4) * SX + 16 * i];
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j) read_b1(bq[0], 0, j);
+    RS_PIN();
+    static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
+        constexpr int t = decltype(tc)::value;
+        constexpr int i = (t % 8) / 2;
+        const f32x4 wv0 = W[t % 3][0], wv1 = W[t % 3][1];
+        float (&bc)[4] = bq[t & 1];
+        float (&bn)[4] = bq[(t + 1) & 1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            acc[0][i] = mfma_16x16x4(wv0[j], bc[j], acc[0][i]);
+            if (t == 0) w_load(1 + j / 2, j & 1);                // step 0 issues steps 1 and 2 ...
+            else if (j < 2 && t + 2 < NQ) w_load(t + 2, j);      // ... step t >= 1 issues step t + 2
+            if (j == 0 && t + 1 < NQ) {                          // the next step's LDS reads in one burst
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj) read_b1(bn, t + 1, jj);
+            }
+            RS_PIN();
+            acc[1][i] = mfma_16x16x4(wv1[j], bc[j], acc[1][i]);
+            if (j < 2 && t < 2) svl[(2 * t + j) & 3] = ld4(r_x, row_ts(x_row(1), Ts) + x_c4((2 * t + j) & 3) * 16, 0);
+            if (j == 0 && t == CPS) cpg = ld4(r_c, row_ts(gch, Ts) + gc4 * 16, 0);
+            if (j == 0 && t == CPS + 1) cpf = ld4(r_c, row_ts(gch + C, Ts) + gc4 * 16, 0);
+            RS_PIN();
+        }
+        if (t == LW) {
+            stage_write(svl, 1);
+            RS_PIN();
+        }
+        if (t == LB) {
+            __syncthreads();
+            RS_PIN();
+        }
+        RS_STAMP(0, 10 + t);
+    });
+    RS_STAMP(0, 3);
+
+    // ---------------- the four quarters' sums: every wave applies the output transform to its own partial products (it is
+    // linear) and transposes the two outputs of pair lcol into its quarter's tile at their FRAMES (rows [0, 32): gate,
+    // [32, 64): filter), ONE barrier, the gate's threads add the four tiles - from here on as the direct kernel ----------------
+    {
+        float* tk = et + kq * (64 * ES);
+        const int fc = lcol + DIL * (lcol / DIL);                // frame of pair lcol's first output
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float* o = &tk[(rb * 32 + wr * 16 + rq + r) * ES + fc];
+                o[0] = acc[rb][1][r] + (acc[rb][2][r] + acc[rb][0][r]);
+                o[DIL] = acc[rb][1][r] - (acc[rb][2][r] + acc[rb][3][r]);
+            }
+    }
+    __syncthreads();
+    if (tid < 256) {
+        f32x4 g = *reinterpret_cast<const f32x4*>(&et[gcw * ES + gc4 * 4]);
+        f32x4 f = *reinterpret_cast<const f32x4*>(&et[(32 + gcw) * ES + gc4 * 4]);
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+            g += *reinterpret_cast<const f32x4*>(&et[q * (64 * ES) + gcw * ES + gc4 * 4]);
+            f += *reinterpret_cast<const f32x4*>(&et[q * (64 * ES) + (32 + gcw) * ES + gc4 * 4]);
+        }
+        f32x4 z;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[e] = sigmoid_fast(g[e] + cpg[e]) * tanh_fast(f[e] + cpf[e]);      // wavenet.py:41-42
+        const dsd_i32x4 w_z = dsd_rsrc_words(p.z + (long)bu * p.x_bstride + t0u);
+        st4_l2(z, w_z, row_ts(gch, Ts) + gc4 * 16, 0);
+    }
+    RS_STAMP(0, 4);
+    RS_STAMP(0, 5);
+}
+
 template <int NCB, int RAG>
 __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
     constexpr int BN = 16 * NCB, ES = BN + 4, B4 = BN / 4;      // (shadow the 32-frame constants)
@@ -617,6 +835,7 @@ __global__ __launch_bounds__(512, 2) void wn_out_rs_kernel(const WnLayerP p) {
 
 // x tile + the K parts' transpose tiles
 int wn_rs_conv_lds_bytes(int sw, int bn, bool quarters) { return (256 * sw + (quarters ? 4 : 2) * 64 * (bn + 4)) * 4; }
+int wn_rs_wq_lds_bytes() { return (256 * 80 + 4 * 64 * 36) * 4; }      // transformed tile + the four quarters' output tiles
 int wn_rs_out_lds_bytes(int bn) { return (256 * 48 + 2 * 64 * (bn + 4)) * 4; }
 
 // 48-frame tiles (NCB = 3) exist in the K-quarter layout only, on dense batches: they are chosen where they make the launch ONE
@@ -624,13 +843,19 @@ int wn_rs_out_lds_bytes(int bn) { return (256 * 48 + 2 * 64 * (bn + 4)) * 4; }
 bool wn_rowsplit_supported(int C, int dil, long Ts) { return C == 256 && dil >= 1 && dil <= 16 && Ts < (1L << 22); }
 
 template <int SW, int RAG>
-static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int conv_q, hipStream_t st) {
+static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int layout, hipStream_t st) {
     constexpr int HL = SW == 48 ? 8 : 16;
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = allow_max_lds(wn_conv_rq_kernel<2, SW, HL, RAG>);
         if (e == hipSuccess) e = allow_max_lds(wn_conv_rs_kernel<SW, RAG>);
         if (e == hipSuccess && !RAG) e = allow_max_lds(wn_conv_rq_kernel<3, 80, HL, 0>);
+        if constexpr (SW == 48) {
+            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<1, RAG>);
+            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<2, RAG>);
+            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<4, RAG>);
+            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<8, RAG>);
+        }
         if (e != hipSuccess) return e;
         attr_done = true;
     }
@@ -640,9 +865,23 @@ static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int conv_q,
         return launch_timed(wn_conv_rq_kernel<3, 80, HL, 0>, dim3(nwg), dim3(512), wn_rs_conv_lds_bytes(80, 48, true), st, p,
                             "wn_conv_rq_kernel<3, 80, %d, 0>", HL);
     }
-    // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two.  conv_q
-    // (DSD_RS_CONV_Q) = 0 / 1 forces the choice (A/B, tests).
-    const bool quarters = conv_q >= 0 ? conv_q != 0 : nwg <= 256;
+    // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two; the Winograd form
+    // of the K-quarter layout 116 KiB.  `layout` = wn_rowsplit_conv_layout's answer (2: p.Aconv is the Winograd matrix).
+    if (layout == 2) {
+        if constexpr (SW == 48) {
+            const int ldsw = wn_rs_wq_lds_bytes();
+#define WQ_LAUNCH(D) launch_timed(wn_conv_wq_kernel<D, RAG>, dim3(nwg), dim3(512), ldsw, st, p, "wn_conv_wq_kernel<%d, %d>", D, RAG)
+            switch (p.dil) {
+                case 1: return WQ_LAUNCH(1);
+                case 2: return WQ_LAUNCH(2);
+                case 4: return WQ_LAUNCH(4);
+                case 8: return WQ_LAUNCH(8);
+            }
+#undef WQ_LAUNCH
+        }
+        return hipErrorInvalidValue;
+    }
+    const bool quarters = layout != 0;
     const int ldsb = wn_rs_conv_lds_bytes(SW, 32, quarters);
     if (quarters)
         return launch_timed(wn_conv_rq_kernel<2, SW, HL, RAG>, dim3(nwg), dim3(512), ldsb, st, p, "wn_conv_rq_kernel<2, %d, %d, %d>",
@@ -667,19 +906,34 @@ static hipError_t rs_launch_out(const WnLayerP& p, int nwg, int bn, hipStream_t 
     return launch_timed(wn_out_rs_kernel<2, RAG>, dim3(nwg), dim3(512), wn_rs_out_lds_bytes(32), st, p, "wn_out_rs_kernel<2, %d>", RAG);
 }
 
+static int rs_tiles(const WnLayerP& p, int batch) { return p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b); }
+
+// The conv of a 32-frame-tile launch: 0 = K halves, 1 = K quarters, 2 = K quarters on Winograd operands (the caller then passes
+// the Winograd matrix as p.Aconv).  conv_q = DSD_RS_CONV_Q: 0 / 1 force a direct layout, 2 forces Winograd on every layer that
+// has it (dilation <= 8; a dilation-16 layer keeps the rule's direct kernel), -1: by grid - up to one workgroup per CU the
+// K-quarter layout, kWinogradAuto deciding between its two forms.
+constexpr bool kWinogradAuto = true;
+int wn_rowsplit_conv_layout(const WnLayerP& p, int batch, int bn, int conv_q) {
+    if (bn != 32) return 1;
+    const bool wq_ok = p.dil <= 8;
+    if (conv_q == 2 && wq_ok) return 2;
+    if (conv_q == 0 || conv_q == 1) return conv_q;
+    if (rs_tiles(p, batch) * 8 > 256) return 0;
+    return wq_ok && kWinogradAuto ? 2 : 1;
+}
+
 // which = 0: conv + FiLM + gate (p.xin -> p.z);  which = 1: out-proj + residual / skip (p.z, p.xin -> p.xout, p.skip);
-// bn = frames per tile (32, or 48 on dense batches): p.tiles_per_b counts tiles of that width;  conv_q: DSD_RS_CONV_Q (-1: by grid)
-hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, int bn, int conv_q, hipStream_t st) {
+// bn = frames per tile (32, or 48 on dense batches): p.tiles_per_b counts tiles of that width;  layout: wn_rowsplit_conv_layout
+hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, int bn, int layout, hipStream_t st) {
     if (C_ != 256 || (bn != 32 && bn != 48)) return hipErrorInvalidValue;
     // every store of a tile stays inside its row: the last tile of an item reaches column tiles_per_b * bn (48-frame tiles: up to
     // 47 past T), and rows are Ts = padded_ts(T) floats apart - holds for every T with the present padded_ts, checked here so that
     // a change of the padding rule cannot make x / skip / z spill into the next row
     if ((long)p.tiles_per_b * bn > p.Ts) return hipErrorInvalidValue;
-    const int nt = p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b);
-    const int nwg = nt * 8;
+    const int nwg = rs_tiles(p, batch) * 8;
     if (which == 1) return p.cgmap ? rs_launch_out<1>(p, nwg, bn, st) : rs_launch_out<0>(p, nwg, bn, st);
-    if (p.dil <= 8) return p.cgmap ? rs_launch_conv<48, 1>(p, nwg, bn, conv_q, st) : rs_launch_conv<48, 0>(p, nwg, bn, conv_q, st);
-    return p.cgmap ? rs_launch_conv<80, 1>(p, nwg, bn, conv_q, st) : rs_launch_conv<80, 0>(p, nwg, bn, conv_q, st);
+    if (p.dil <= 8) return p.cgmap ? rs_launch_conv<48, 1>(p, nwg, bn, layout, st) : rs_launch_conv<48, 0>(p, nwg, bn, layout, st);
+    return p.cgmap ? rs_launch_conv<80, 1>(p, nwg, bn, layout, st) : rs_launch_conv<80, 0>(p, nwg, bn, layout, st);
 }
 
 hipError_t wn_rowsplit_init_all() {
@@ -691,8 +945,8 @@ hipError_t wn_rowsplit_init_all() {
             p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;      // (no launch: the grid is empty)
             p.ncg = 0;
             p.tiles_per_b = 0;
-            if ((e = launch_wn_rowsplit(p, 0, 256, 0, 32, -1, nullptr)) != hipSuccess) return e;
-            if ((e = launch_wn_rowsplit(p, 1, 256, 0, 32, -1, nullptr)) != hipSuccess) return e;
+            if ((e = launch_wn_rowsplit(p, 0, 256, 0, 32, 1, nullptr)) != hipSuccess) return e;
+            if ((e = launch_wn_rowsplit(p, 1, 256, 0, 32, 1, nullptr)) != hipSuccess) return e;
         }
     return hipSuccess;
 }
