@@ -111,8 +111,11 @@ class _NativeBackbone(nn.Module):
 
     def set_precision(self, mode, device=None):
         """Arithmetic of the residual layers' GEMMs (dsd_set_precision): "f32" (default, the reference's) or "bf16x3" - every
-        operand split into two bf16 values, three bf16 MFMAs per fp32 one, fp32 accumulation (opt-in; WaveNet, C = 256,
-        batched grids; measured 9.9e-6 off fp32 on one evaluation)."""
+        operand split into two bf16 values, three bf16 MFMAs per fp32 one, fp32 accumulation.  Opt-in, and only where a
+        split-bf16 kernel exists: WaveNet at C = 256 on batched grids (measured 9.9e-6 off fp32 on one evaluation), LYNXNet's
+        pointwise GEMMs, and the vocoder's residual-block convolutions of the stages with 64 to 256 channels (a multiple of
+        32; 7e-6 to 2.4e-5 off the fp32 oracle on the waveform) - everything else of those models, and every other model,
+        stays fp32.  The fp32 tolerances hold in either mode; `stats()["precision"]` says which path the last call ran."""
         modes = {"f32": 0, "fp32": 0, "bf16x3": 1}
         if mode not in modes:
             raise ValueError(f"unknown precision {mode!r}: one of {sorted(modes)}")

@@ -787,6 +787,8 @@ void pack_fs2_layers(dsd_handle* h, int H, int L, int ks, int pos_mode) {
 //   y[o][u q + r] = sum_i sum_n W[i][o][k0 + u n] x[i][q + e - n],   k0 = (r + pad) mod u,  e = (r + pad) div u
 // so tap a (input offset d = a - D) of phase row (r, o) holds W[i][o][k0 + u (e - d)] when that index is a valid
 // kernel position and zero otherwise; the GEMM's scatter epilogue writes column q of row (r, o) to out[o][u q + r].
+size_t pack_voc_x3(dsd_handle* h, int C, int taps, const WGet& w);
+
 int build_packed_voc(dsd_handle* h) {
     const dsd_vocoder_config& v = h->vcfg;
     h->blob_host.clear();
@@ -836,6 +838,14 @@ int build_packed_voc(dsd_handle* h) {
     h->v_nb.resize(v.n_ups);
     h->v_res.assign((size_t)v.n_ups * v.n_kernels, {});
     h->v_rest.assign((size_t)v.n_ups * v.n_kernels, {});
+    h->v_resx3.assign((size_t)v.n_ups * v.n_kernels, {});
+    // split-bf16 mode: a residual-block convolution's weights once more as voc_x3.hip's hi | lo stream, next to the fp32 packing
+    // (which is built the same in either mode: switching back reproduces the fp32 results bit for bit)
+    auto x3_stream = [&](const std::string& name, int ch, int ks, int dil) {
+        if (h->precision != 1 || voc_x3_max_ncb(ch, ks, dil) == 0) return (size_t)SIZE_MAX;
+        const HostTensor* t = &W(h, name + ".weight");
+        return pack_voc_x3(h, ch, ks, [t, ch, ks](int r, int k, int tap) { return (double)t->data[((size_t)r * ch + k) * ks + tap]; });
+    };
     for (int i = 0; i < v.n_ups; ++i) {
         const int ch = voc_stage_channels(v, i), u = v.upsample_rates[i], K = v.upsample_kernel_sizes[i], pad = (K - u) / 2;
         int D = 0;
@@ -872,6 +882,7 @@ int build_packed_voc(dsd_handle* h) {
             const std::string p = "resblocks." + std::to_string(i * v.n_kernels + j) + ".";
             auto& list = h->v_res[(size_t)i * v.n_kernels + j];
             auto& tlist = h->v_rest[(size_t)i * v.n_kernels + j];
+            auto& xlist = h->v_resx3[(size_t)i * v.n_kernels + j];
             for (int d = 0; d < v.n_dilations[j]; ++d) {
                 if (few(ch)) {
                     const int ks = v.resblock_kernel_sizes[j];
@@ -883,11 +894,15 @@ int build_packed_voc(dsd_handle* h) {
                     }
                     continue;
                 }
+                const int ks = v.resblock_kernel_sizes[j], dil = v.resblock_dilation_sizes[j][d];
                 if (v.resblock == 1) {
-                    list.push_back(dense(p + "convs1." + std::to_string(d), ch, ch, v.resblock_kernel_sizes[j]));
-                    list.push_back(dense(p + "convs2." + std::to_string(d), ch, ch, v.resblock_kernel_sizes[j]));
+                    list.push_back(dense(p + "convs1." + std::to_string(d), ch, ch, ks));
+                    list.push_back(dense(p + "convs2." + std::to_string(d), ch, ch, ks));
+                    xlist.push_back(x3_stream(p + "convs1." + std::to_string(d), ch, ks, dil));
+                    xlist.push_back(x3_stream(p + "convs2." + std::to_string(d), ch, ks, 1));
                 } else {
-                    list.push_back(dense(p + "convs." + std::to_string(d), ch, ch, v.resblock_kernel_sizes[j]));
+                    list.push_back(dense(p + "convs." + std::to_string(d), ch, ch, ks));
+                    xlist.push_back(x3_stream(p + "convs." + std::to_string(d), ch, ks, dil));
                 }
             }
         }
@@ -946,6 +961,29 @@ size_t pack_x3(dsd_handle* h, int nrt, int nsteps, const std::function<int(int, 
                             blk[512 + lane * 8 + j] = bf16_bits(v - bf16_value(hi));
                         }
                 }
+    return off;
+}
+
+// Weight stream of voc_x3.hip for one Conv1d(C -> C, taps): [wave 4][k32 step = tap * C/32 + chunk][row block MBW][hi | lo]
+// [lane 64][8 bf16]; packed row (wave * MBW + k) * 16 + (lane & 15) is the output channel (zero at or above C), k index
+// 8 (lane >> 4) + j of a step the input channel 32 chunk + that.
+size_t pack_voc_x3(dsd_handle* h, int C, int taps, const WGet& w) {
+    const int mbw = voc_x3_mbw(C), nch = C / 32, nsteps = taps * nch;
+    const size_t off = blob_reserve(h, (size_t)4 * nsteps * mbw * 2 * 512 / 2);
+    uint16_t* dst = reinterpret_cast<uint16_t*>(h->blob_host.data() + off);
+    for (int wave = 0; wave < 4; ++wave)
+        for (int s = 0; s < nsteps; ++s)
+            for (int k = 0; k < mbw; ++k) {
+                uint16_t* blk = dst + (((size_t)wave * nsteps + s) * mbw + k) * 2 * 512;
+                for (int lane = 0; lane < 64; ++lane)
+                    for (int j = 0; j < 8; ++j) {
+                        const int row = (wave * mbw + k) * 16 + (lane & 15);
+                        const float v = row < C ? (float)w(row, (s % nch) * 32 + 8 * (lane >> 4) + j, s / nch) : 0.f;
+                        const uint16_t hi = bf16_bits(v);
+                        blk[lane * 8 + j] = hi;
+                        blk[512 + lane * 8 + j] = bf16_bits(v - bf16_value(hi));
+                    }
+            }
     return off;
 }
 
@@ -2581,6 +2619,7 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
     if (int rc = select_device("dsd_vocoder_create", cfg->device)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess) ie = tconv_init_all();
+    if (ie == hipSuccess) ie = voc_x3_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
     dsd_handle* h = new dsd_handle();
     memset(&h->cfg, 0, sizeof(h->cfg));
@@ -2599,8 +2638,49 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
 
 namespace {
 
+// One residual-block convolution on voc_x3.hip (split-bf16 mode; stream = its weights, build_packed_voc).  Tile width: 64 frames
+// when the images fit in LDS and that still gives every CU a workgroup, else 32 - the result does not depend on it.  Returns
+// DSD_OK with *ran = false where the launch is outside the kernel's 32-bit addressing: the caller runs the fp32 GEMM.
+int run_voc_x3(dsd_handle* h, size_t stream, const PackedGemm& g, const float* x, const float* res, float* out, int B, int C,
+               int T, int Ts, int dil, float slope_in, float slope_out, const VocRagStage* vr, hipStream_t st, bool* ran) {
+    *ran = false;
+    int ncb = voc_x3_max_ncb(C, g.taps, dil);
+    if (stream == SIZE_MAX || ncb == 0 || (long)C * Ts * 4 >= (1L << 31) - (1L << 20)) return DSD_OK;
+    const long t64 = vr ? (long)vr->ncg[2] : (long)B * ((T + 63) / 64);
+    const int xw = h->opts.x3_wide;                      // DSD_X3_WIDE: 0 never 64-frame tiles, 1 wherever they fit
+    if (ncb == 4 && (xw == 0 || (xw != 1 && t64 < h->cus))) ncb = 2;
+    const int BN = 16 * ncb;
+    VocX3P p;
+    memset(&p, 0, sizeof(p));
+    p.tiles_per_b = (T + BN - 1) / BN;
+    const long ntiles = vr ? (long)vr->ncg[ncb / 2] : (long)B * p.tiles_per_b;
+    if ((long)B * p.tiles_per_b >= (1L << 22)) return DSD_OK;
+    p.W = h->blob.p + stream;
+    p.bias = h->blob.p + g.bias_off;
+    p.x = x; p.res = res; p.out = out;
+    p.bstride = (long)C * Ts;
+    p.Ts = Ts; p.T = T; p.C = C; p.taps = g.taps; p.dil = dil;
+    p.HL = round_up((g.taps / 2) * dil, 4);
+    p.nsteps = g.taps * (C / 32);
+    p.nfq = (BN + 2 * p.HL) / 4;
+    p.inv_nfq = 1.0f / (float)p.nfq;
+    p.slope_in = slope_in; p.slope_out = slope_out;
+    p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+    if (vr) {
+        p.lens = vr->lens; p.cgmap = vr->cg[ncb / 2]; p.ncg = vr->ncg[ncb / 2];
+    }
+    const double frames = vr ? (double)vr->valid : (double)B * T;
+    const int rc = timed_launch(h, 900 + 4 * voc_x3_mbw(C) + ncb + (vr ? 1 : 0), 2.0 * C * C * g.taps * frames,
+                                4.0 * C * frames * (res ? 3 : 2), "vocoder split-bf16 conv",
+                                [&] { return launch_voc_x3(p, ncb, (int)ntiles, st); });
+    if (rc) return rc;
+    *ran = true;
+    h->v_x3_ran = true;
+    return DSD_OK;
+}
+
 // dsd_vocode_ragged's bookkeeping: item lengths at every rate and the lists of tiles that hold valid frames - for the GEMMs
-// at 32 / 64 frames (the vocoder's convolutions run on the generic path, never on 16-frame tiles) and for tconv.hip at 256 -
+// at 32 / 64 frames (the vocoder's convolutions run on the generic path or on voc_x3.hip, never on 16-frame tiles) and for tconv.hip at 256 -
 // in one device block, copied on the caller's stream; kept while B, T and the lengths stay the same
 int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipStream_t st) {
     const dsd_vocoder_config& v = h->vcfg;
@@ -2711,6 +2791,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         for (size_t o : ob) h->v_buf.push_back(a + o);
     }
     int rc;
+    h->v_x3_ran = false;
     if (lengths && (rc = prepare_voc_ragged(h, B, T, lengths, st))) return rc;
     // per rate: nullptr (dense) or the ragged batch's lengths and tiles
     auto rag = [&](int i) -> const VocRagStage* { return lengths ? &h->vr_st[i] : nullptr; };
@@ -2771,6 +2852,15 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         for (int j = 0; j < v.n_kernels; ++j) {     // residual blocks  (models.py:280-286; ResBlock1 :62-69, ResBlock2 :92-97)
             const auto& cv = h->v_res[(size_t)i * v.n_kernels + j];
             const auto& tv = h->v_rest[(size_t)i * v.n_kernels + j];
+            const auto& xv = h->v_resx3[(size_t)i * v.n_kernels + j];
+            // split-bf16 mode: convolution n of this block on voc_x3.hip where it has a stream (else false: the fp32 GEMM below)
+            auto x3 = [&](size_t n, const PackedGemm& g, const float* in, const float* res, float* out, int dil_, float s_in,
+                          float s_out, bool* ran) {
+                *ran = false;
+                if (h->precision != 1 || n >= xv.size()) return (int)DSD_OK;
+                return run_voc_x3(h, xv[n], g, in, res, out, B, ch, Tq, Tsq, dil_, s_in, s_out, rag(i + 1), st, ran);
+            };
+            bool ran;
             for (int d = 0; d < v.n_dilations[j]; ++d) {
                 const float* src = d == 0 ? x : r;
                 const int dil = v.resblock_dilation_sizes[j][d];
@@ -2788,11 +2878,16 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                     continue;
                 }
                 if (v.resblock == 1) {
-                    GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, dil, true, false,
-                                            rag(i + 1));
-                    c1.p.in_scale = 0.1f; c1.p.act = ACT_LRELU;
-                    c1.p.out = t1; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
-                    if ((rc = run_gemm(h, c1, st))) return rc;
+                    if ((rc = x3(2 * d, cv[2 * d], src, nullptr, t1, dil, 0.1f, 0.1f, &ran))) return rc;
+                    if (!ran) {
+                        GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, dil, true, false,
+                                                rag(i + 1));
+                        c1.p.in_scale = 0.1f; c1.p.act = ACT_LRELU;
+                        c1.p.out = t1; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
+                        if ((rc = run_gemm(h, c1, st))) return rc;
+                    }
+                    if ((rc = x3(2 * d + 1, cv[2 * d + 1], t1, src, r, 1, 1.f, 1.f, &ran))) return rc;
+                    if (ran) continue;
                     GemmCall c2 = make_gemm(h, cv[2 * d + 1], t1, xs, Tsq, B, Tq, ST_PLAIN, EP_BIAS_RES, 1, true, false,
                                             rag(i + 1));
                     c2.p.aux = src; c2.p.aux_bstride = xs; c2.p.aux_rstride = Tsq;
@@ -2802,12 +2897,15 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                     // xt + x with x read both as the (leaky-ReLU'd) conv input and as the residual: the output goes to
                     // the other buffer, the conv's halo reads must not see this launch's own stores
                     float* dst = (src == x || src == t1) ? r : t1;
-                    GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_RES, dil, true, false,
-                                            rag(i + 1));
-                    c1.p.in_scale = 0.1f;
-                    c1.p.aux = src; c1.p.aux_bstride = xs; c1.p.aux_rstride = Tsq;
-                    c1.p.out = dst; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
-                    if ((rc = run_gemm(h, c1, st))) return rc;
+                    if ((rc = x3(d, cv[d], src, src, dst, dil, 0.1f, 1.f, &ran))) return rc;
+                    if (!ran) {
+                        GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_RES, dil, true, false,
+                                                rag(i + 1));
+                        c1.p.in_scale = 0.1f;
+                        c1.p.aux = src; c1.p.aux_bstride = xs; c1.p.aux_rstride = Tsq;
+                        c1.p.out = dst; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
+                        if ((rc = run_gemm(h, c1, st))) return rc;
+                    }
                     if (dst == t1) {        // keep the running state in r for the next iteration / the accumulation
                         float* tmp = r; r = t1; t1 = tmp;
                     }
@@ -3074,8 +3172,8 @@ int dsd_set_precision(dsd_handle* h, int32_t mode) {
     if (!h) return DSD_EINVAL;
     if (mode != DSD_PRECISION_F32 && mode != DSD_PRECISION_BF16X3)
         return fail(h, DSD_EINVAL, "dsd_set_precision: unknown mode %d", mode);
-    if (!is_wavenet(h) && h->cfg.backbone != DSD_BACKBONE_LYNXNET)
-        return fail(h, DSD_ESTATE, "dsd_set_precision: only denoiser handles have a split-bf16 path");
+    if (!is_wavenet(h) && h->cfg.backbone != DSD_BACKBONE_LYNXNET && !is_voc(h))
+        return fail(h, DSD_ESTATE, "dsd_set_precision: only denoiser and vocoder handles have a split-bf16 path");
     if (mode == h->precision) return DSD_OK;
     h->precision = mode;
     if (h->finalized) {                   // the bf16x3 weight streams are built with the packed weights
@@ -3147,7 +3245,11 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         out->flops_per_frame_nfe = 2 * (M * C + L * (C * 2 * inner + ks * inner + inner * C) + C * M);
         out->bytes_per_frame_nfe = L * 12 * C + 8 * M;
         out->kernels_per_nfe = 1 + 4 * (int)L + 2;
-        if (h->arena.p && plan_denoise(h).bf16x3()) out->precision = DSD_PRECISION_BF16X3;
+        if (is_voc(h)) {                  // from the launches of the last vocode call
+            if (h->v_x3_ran) out->precision = DSD_PRECISION_BF16X3;
+        } else if (h->arena.p && plan_denoise(h).bf16x3()) {
+            out->precision = DSD_PRECISION_BF16X3;
+        }
     }
     out->graphs_cached = (int)h->graphs.size();
     return DSD_OK;

@@ -167,6 +167,10 @@ struct dsd_handle {
     std::vector<PackedGemm> v_ups;                   // transposed convs as phase-row GEMMs
     std::vector<std::vector<PackedGemm>> v_res;      // [stage * n_kernels + j][2 * n_dil (ResBlock1) or n_dil]
     std::vector<std::vector<PackedTConv>> v_rest;    // same indexing: the 16- / 32-channel stages (tconv.hip)
+    // split-bf16 mode (precision == 1): same indexing as v_res, the convolution's weight stream of voc_x3.hip as a float offset
+    // into the blob, SIZE_MAX where the convolution stays on the fp32 kernel; v_x3_ran: the last vocode call launched voc_x3.hip
+    std::vector<std::vector<size_t>> v_resx3;
+    bool v_x3_ran = false;
     PackedTConv v_postt;
     std::vector<size_t> v_nw, v_nb;                  // noise conv weights / biases
     std::vector<int> v_uptaps;

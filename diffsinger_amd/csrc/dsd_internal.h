@@ -43,7 +43,7 @@ struct PathOpts {
     int lynx_pw1p = -1;     // DSD_LYNX_PW1P       0: pw1 with one workgroup per (frame tile, row tile), g >= 1: g per frame tile
     int lynx_pw2q = -1;     // DSD_LYNX_PW2Q       0: never the 128-row pw2 of one-utterance grids (gemm.hip instead), 1: on every grid
     int precision = -1;     // DSD_PRECISION       1: split-bf16 (bf16x3) layer kernels where they exist (opt-in, own tolerance)
-    int x3_wide = -1;       // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet kernels, 1: wherever they exist
+    int x3_wide = -1;       // DSD_X3_WIDE         0: never 64-frame tiles in the split-bf16 LYNXNet and vocoder kernels, 1: wherever they exist
 };
 static_assert(std::has_unique_object_representations<PathOpts>::value, "PathOpts has padding bytes (it is hashed as raw bytes)");
 
@@ -355,6 +355,31 @@ struct TConvP {
 int tconv_lds_bytes(int ci, int co, int taps, int SP);
 hipError_t tconv_init_all();
 hipError_t launch_tconv(const TConvP& p, int ci, int co, int batch, hipStream_t st);
+// voc_x3.hip: a residual-block convolution Conv1d(C -> C, k taps, dilated) of the vocoder in split-bf16 arithmetic (opt-in
+// precision mode):  out = lrelu(bias + W * lrelu(x, slope_in), slope_out) (+ res), a slope of 1 = no activation
+struct VocX3P {
+    const void* W;          // bf16x3 weight stream [wave 4][k32 step = tap * C/32 + chunk][row block][hi | lo][lane][8 bf16]
+    const float* bias;      // [C]
+    const float* x;         // input, internal layout [B][C][Ts]
+    const float* res;       // residual added last, same layout (may be x), or nullptr
+    float* out;             // same layout; never x or res (neighbouring tiles read their halo)
+    long bstride;           // floats between batch items: C * Ts
+    int Ts, T, C, taps, dil;
+    int HL;                 // staged halo frames on each side: (taps / 2) * dil rounded up to 4
+    int nsteps;             // taps * C / 32
+    int nfq;                // staged frame quads: (tile width + 2 HL) / 4
+    float inv_nfq;
+    float slope_in, slope_out;
+    int tiles_per_b;
+    float inv_tiles_per_b;
+    const int* lens;        // ragged batch: per-item valid frames (nullptr: T)
+    const int* cgmap;       // ragged batch: the (item, tile) entries b * tiles_per_b + tile with valid frames, of this tile width
+    int ncg;
+};
+int voc_x3_mbw(int C);                              // 16-row blocks per wave: the stream holds 4 * voc_x3_mbw(C) * 16 rows, zero above C
+int voc_x3_max_ncb(int C, int taps, int dil);       // widest tile in 16-frame blocks (4 or 2) whose LDS images fit; 0: not supported
+hipError_t launch_voc_x3(const VocX3P& p, int ncb, int ntiles, hipStream_t st);
+hipError_t voc_x3_init_all();
 // vocoder_kernels.hip (NSF-HiFiGAN source, noise convs, residual-block average)
 hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w,
                              const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp, float noise_std,

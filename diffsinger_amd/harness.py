@@ -132,16 +132,20 @@ def load_ckpt(model, ckpt_base_dir, ckpt_steps: Optional[int] = None, prefix_in_
     return path
 
 
-def load_vocoder(model_path, device='cuda'):
+def load_vocoder(model_path, device='cuda', precision='f32'):
     """`modules/nsf_hifigan/models.py:18-33` + `modules/vocoders/nsf_hifigan.py:18-37`: `config.json` next to the generator
-    checkpoint, weights under 'generator' (weight norm folded on load) -> vocoder.NsfHifiGAN."""
+    checkpoint, weights under 'generator' (weight norm folded on load) -> vocoder.NsfHifiGAN.  `precision`: "f32" (default) or
+    "bf16x3", the generator's `set_precision`."""
     from .vocoder import Generator, NsfHifiGAN
     model_path = pathlib.Path(model_path)
     with open(model_path.with_name('config.json')) as f:
         h = json.load(f)
     gen = Generator(h)
     gen.load_state_dict(torch.load(model_path, map_location='cpu', weights_only=True)['generator'], strict=True)
-    return NsfHifiGAN(gen.to(device).eval(), mel_base=hparams.get('mel_base', '10'))
+    gen = gen.to(device).eval()
+    if precision not in ('f32', 'fp32'):
+        gen.set_precision(precision)
+    return NsfHifiGAN(gen, mel_base=hparams.get('mel_base', '10'))
 
 
 class SimplePhonemeTable:

@@ -3,7 +3,7 @@
 library only (no DiffSinger checkout needed at run time).
 
     python examples/ds_to_wav.py checkpoints/my_exp song.ds nsf_hifigan/model.ckpt -o song.wav [--steps 20] [--depth 0.6]
-                                 [--batch-size 8] [--seed 42]
+                                 [--batch-size 8] [--seed 42] [--precision bf16x3]
 
 checkpoints/my_exp holds what a training run leaves there: config.yaml, model_ckpt_steps_<N>.ckpt, dictionary-<lang>.txt
 (or dictionary.txt), and - for multi-speaker / multilingual models - spk_map.json / lang_map.json.
@@ -30,6 +30,8 @@ def main():
     ap.add_argument("--seed", type=int, default=-1)
     ap.add_argument("--key", type=int, default=0, help="transpose by this many semitones (scripts/infer.py --key)")
     ap.add_argument("--spk", default=None, help='speaker or mix, e.g. "alice" or "alice:0.3|bob" (scripts/infer.py --spk)')
+    ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32",
+                    help="arithmetic of the denoiser's and the vocoder's residual layers (set_precision); default: fp32")
     args = ap.parse_args()
 
     load_config(args.exp / "config.yaml", overrides=dict(infer=True, work_dir=str(args.exp)))
@@ -42,7 +44,9 @@ def main():
     model = DiffSingerAcoustic(len(dictionary), hparams["audio_num_mel_bins"]).cuda().eval()
     ckpt = harness.load_ckpt(model, args.exp, ckpt_steps=args.ckpt, prefix_in_ckpt="model", strict=True)
     print(f"| acoustic model: {ckpt}")
-    vocoder = harness.load_vocoder(args.vocoder)
+    if args.precision != "f32":
+        model.diffusion._backbone().set_precision(args.precision)
+    vocoder = harness.load_vocoder(args.vocoder, precision=args.precision)
     h = harness.AcousticHarness(model, vocoder, dictionary, spk_map=maps["spk_map"], lang_map=maps["lang_map"], device="cuda")
     out = args.out or args.proj.with_suffix(".wav")
     params = harness.load_ds(args.proj)

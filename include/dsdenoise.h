@@ -609,9 +609,15 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
  * arithmetic stay fp32.  Measured against the fp32 oracle: 9.9e-6 on one evaluation, 1.9e-6 on the 50-NFE DPM-Solver++
  * sample (tools/bf16x3_tolerance.py; asserted on the GPU in tests/test_gpu_bf16x3.py at the fp32 tolerances).  Exists for the
  * fused WaveNet layer kernel at C = 256 (batched grids) and for LYNXNet's two pointwise GEMMs at C = 1024 / 512 with
- * expansion 2; other shapes and kernels run fp32 whatever the mode.  Also set for
- * every handle of the process by the environment variable DSD_PRECISION=1 at dsd_create.  May be called at any time; after
- * dsd_finalize_weights it re-packs the weights.
+ * expansion 2, and - on a vocoder handle (dsd_vocoder_create) - for the residual-block convolutions of every stage with 64 to 256
+ * channels, a multiple of 32 (voc_x3.hip: 7e-6 .. 2.4e-5 off the fp32 oracle on the waveform, tools/bf16x3_vocoder_tolerance.py;
+ * asserted at the fp32 tolerance in tests/test_gpu_vocoder_x3.py); conv_pre, the transposed convolutions, the 32- / 16-channel
+ * stages, conv_post and the source stay fp32, as do other shapes and kernels whatever the mode.  Denoiser, LYNXNet and vocoder
+ * handles take the call; every other kind of handle answers DSD_ESTATE, an unknown mode DSD_EINVAL.  Also set for every DENOISER
+ * handle of the process by the environment variable DSD_PRECISION=1 at dsd_create (a vocoder handle takes the explicit call
+ * only).  May be called at any time; after dsd_finalize_weights it re-packs the weights - the fp32 packing is the same in either
+ * mode, so switching back reproduces the fp32 results bit for bit.  dsd_get_stats().precision reports the mode from the path that
+ * ran: for a vocoder, BF16X3 after a dsd_vocode / dsd_vocode_ragged call that launched a split-bf16 kernel.
  */
 #define DSD_PRECISION_F32 0
 #define DSD_PRECISION_BF16X3 1
@@ -632,7 +638,7 @@ typedef struct dsd_stats {
     int32_t layer_launches;
     int32_t fused_tiles;
     int32_t split_tiles;
-    int32_t precision;           /* DSD_PRECISION_BF16X3: the plan has a split-bf16 launch (dsd_set_precision), else F32 */
+    int32_t precision;           /* DSD_PRECISION_BF16X3: the plan (vocoder: the last call) has a split-bf16 launch, else F32 */
 } dsd_stats;
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out);
 
