@@ -250,7 +250,7 @@ int dsd::hnsep_finalize(dsd_handle* h) {
 
 namespace {
 
-// the window (float32, as torch builds it) and the forward / inverse DFT bases of one (N, kind), built on first use and
+// the window (computed in double, stored as float32) and the forward / inverse DFT bases of one (N, kind), built on first use and
 // complete before it returns (the cache serves every stream)
 const HsBasis* hs_basis(dsd_handle* h, int N, int kind, hipStream_t st) {
     HnsepState& r = *h->hs;
@@ -260,9 +260,11 @@ const HsBasis* hs_basis(dsd_handle* h, int N, int kind, hipStream_t st) {
     for (int j = 0; j < N; ++j) {
         if (kind == 0) {       // torch.hann_window(N) (periodic)
             w[j] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * j / N));
-        } else {               // decomposed_waveform.py:168-174, in float32
-            const float ph = (float)j / (float)N * 2.f * (float)M_PI;
-            w[j] = 0.355768f - 0.487396f * cosf(ph) + 0.144232f * cosf(2.f * ph) - 0.012604f * cosf(3.f * ph);
+        } else {               // decomposed_waveform.py:168-174, in double and rounded once: the four terms cancel to 0 at the
+                               // window's ends, where torch's float32 sum is 2.4e-7 off, and at hop == win / 2 the iSTFT
+                               // divides by this window alone (3.2e-7 in the base harmonic at win 64, hop 32)
+            const double ph = (double)j / (double)N * 2.0 * M_PI;
+            w[j] = (float)(0.355768 - 0.487396 * cos(ph) + 0.144232 * cos(2.0 * ph) - 0.012604 * cos(3.0 * ph));
         }
     }
     HsBasis b;

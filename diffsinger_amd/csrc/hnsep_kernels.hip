@@ -217,6 +217,12 @@ __global__ __launch_bounds__(256) void hs_conv_kernel(const HsConvP p) {
                         o11 = o10 + wp * S.ts;
                     }
                 }
+                // one tap's channels sum into a fresh accumulator, the taps' partial sums into acc: at nout 64 a conv's K
+                // reaches 8064, and 2016 MFMA steps into one fp32 accumulator left the harmonic part 2.1e-6 from the float64
+                // oracle where the blocked sums of the reference's CPU path are 5e-7 from it
+                f32x4 part[NB];
+#pragma unroll
+                for (int n = 0; n < NB; ++n) part[n] = f32x4{0.f, 0.f, 0.f, 0.f};
                 for (int c0 = 0; c0 < S.Cp; c0 += 4) {
                     const int c = c0 + kq;
                     float a = 0.f;
@@ -229,8 +235,10 @@ __global__ __launch_bounds__(256) void hs_conv_kernel(const HsConvP p) {
                     }
                     const float* __restrict__ wk = wrow + (long)(kb + c) * p.cout_pad;
 #pragma unroll
-                    for (int n = 0; n < NB; ++n) acc[n] = mfma_16x16x4(a, wk[16 * n], acc[n]);
+                    for (int n = 0; n < NB; ++n) part[n] = mfma_16x16x4(a, wk[16 * n], part[n]);
                 }
+#pragma unroll
+                for (int n = 0; n < NB; ++n) acc[n] += part[n];
                 kb += S.Cp;
             }
     }

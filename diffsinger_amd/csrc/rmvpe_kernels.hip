@@ -30,12 +30,27 @@ __global__ __launch_bounds__(256) void rm_resample_kernel(const RmResampleP p) {
     const float* __restrict__ x = p.x + (long)b * p.x_sb;
     const float* __restrict__ kr = p.kern + (long)ph * p.K;
     const long j0 = blk * p.orig - p.width;
-    float s = 0.f;
-    for (int k = 0; k < p.K; ++k) {
-        const long j = j0 + k;
-        if (j >= 0 && j < L) s = fmaf(kr[k], x[j], s);
+    float out;
+    if (p.nw > p.orig) {
+        // upsampling (nw > orig: every rate below 16 kHz; measured at 8 kHz): the bands above the input's Nyquist hold the
+        // filter's stop band alone, next to the log-mel's clamp, and there the 5e-7 of a sequential fp32 sum is what the
+        // network sees (2.4e-6 in the hidden): summed in double and rounded once.  Downsampling fills the whole band and
+        // keeps the fp32 sum
+        double s = 0.0;
+        for (int k = 0; k < p.K; ++k) {
+            const long j = j0 + k;
+            if (j >= 0 && j < L) s = fma((double)kr[k], (double)x[j], s);
+        }
+        out = (float)s;
+    } else {
+        float s = 0.f;
+        for (int k = 0; k < p.K; ++k) {
+            const long j = j0 + k;
+            if (j >= 0 && j < L) s = fmaf(kr[k], x[j], s);
+        }
+        out = s;
     }
-    p.y[(long)b * p.y_sb + i] = s;
+    p.y[(long)b * p.y_sb + i] = out;
 }
 
 // x0[b][t][f] = scale * mel[b][f][t] + shift for t < T_b, the BatchNorm of the zero padding (shift) for T_b <= t < Tp_b

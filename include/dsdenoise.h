@@ -490,7 +490,7 @@ typedef struct dsd_rmvpe_config {
     int32_t n_gru;              /* 1: BiGRU(384, 256) + Linear(512, 360); 0: Linear(384, 360)      */
     int32_t en_de_layers;       /* 1 .. 5                                                          */
     int32_t inter_layers;       /* >= 1                                                            */
-    int32_t en_out_channels;    /* a positive multiple of 8                                        */
+    int32_t en_out_channels;    /* a multiple of 8, 8 .. 64                                        */
     int32_t device;
 } dsd_rmvpe_config;
 
