@@ -29,7 +29,7 @@ EXPORTS = [
     "dsd_token_encoder_create", "dsd_token_encode", "dsd_predict_dur", "dsd_cond_assemble", "dsd_set_lengths",
     "dsd_mel_create", "dsd_mel_filterbank", "dsd_mel_num_frames", "dsd_mel_analyze",
     "dsd_rmvpe_create", "dsd_rmvpe_num_frames", "dsd_rmvpe_filterbank", "dsd_rmvpe_mel_to_hidden", "dsd_rmvpe_decode",
-    "dsd_rmvpe_infer",
+    "dsd_rmvpe_decode_at", "dsd_rmvpe_decode_viterbi", "dsd_rmvpe_infer",
     "dsd_hnsep_create", "dsd_hnsep_num_frames", "dsd_hnsep_mask", "dsd_hnsep_separate", "dsd_base_harmonic",
     "dsd_variance_curves",
     "dsd_length_regulate", "dsd_frame_curve",
@@ -187,6 +187,8 @@ def _load():
     lib.dsd_rmvpe_filterbank.argtypes = [C.POINTER(C.c_float)]
     lib.dsd_rmvpe_mel_to_hidden.argtypes = [vp, vp, i32, i32, i64, i64, i64, C.POINTER(i64), vp, i64, i64, vp]
     lib.dsd_rmvpe_decode.argtypes = [vp, vp, i32, i32, i64, i64, C.c_float, vp, i64, vp]
+    lib.dsd_rmvpe_decode_at.argtypes = [vp, vp, vp, i32, i32, i64, i64, i64, C.c_float, vp, i64, vp]
+    lib.dsd_rmvpe_decode_viterbi.argtypes = [vp, vp, i32, i32, i64, i64, C.POINTER(i64), C.c_float, vp, i64, vp, i64, vp]
     lib.dsd_rmvpe_infer.argtypes = [vp, vp, i32, i64, i64, C.POINTER(i64), i32, C.c_float, vp, i64, vp, i64, i64, vp]
     lib.dsd_hnsep_create.argtypes = [C.POINTER(DsdHnsepConfig), C.POINTER(vp)]
     lib.dsd_hnsep_num_frames.argtypes = [i64, i32]

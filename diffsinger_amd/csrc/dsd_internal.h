@@ -556,6 +556,23 @@ struct RmDecodeP {
     long f_sb;
     float* out_hidden;              // optional copy, [b o_sb + t o_st + class]
     long o_sb, o_st;
+    const int* center;              // optional: the window's centre of frame (b, t) at center[b c_sb + t]; null = the argmax
+    long c_sb;
+};
+// Viterbi decode: the band of the transition matrix is 59 wide (|k - j| <= 29)
+constexpr int RM_VT_BAND = 29, RM_VT_W = 2 * RM_VT_BAND + 1;
+struct RmViterbiP {
+    const float* hidden;            // as RmDecodeP
+    long h_sb, h_st;
+    const int* T;
+    int B, Tmax;
+    const double* tab;              // [59][360]: tab[d + 29][j] = log_trans[j + d][j] (0 where j + d is no state)
+    double eps, log_eps, log_p_init;
+    double* lp;                     // workspace [b][Tmax][360]: log_prob
+    unsigned short* ptr;            // workspace [b][Tmax][360]: back-pointers (row 0 unused)
+    int* center;                    // [b][Tmax]: the path
+    int* path_out;                  // optional copy: path_out[b p_sb + t]
+    long p_sb;
 };
 hipError_t launch_rm_resample(const RmResampleP& p, int B, long max_blocks, int nw, hipStream_t st);
 hipError_t launch_rm_prep(const RmPrepP& p, int B, int Tal, hipStream_t st);
@@ -564,6 +581,7 @@ hipError_t launch_rm_tconv(const RmConvP& p, int n_entries, hipStream_t st);
 hipError_t launch_rm_linear(const RmLinearP& p, int n_entries, hipStream_t st);
 hipError_t launch_rm_gru(const RmGruP& p, int B, hipStream_t st);
 hipError_t launch_rm_decode(const RmDecodeP& p, hipStream_t st);
+hipError_t launch_rm_viterbi(const RmViterbiP& p, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // hnsep_kernels.hip: VR harmonic-noise separation and the variance curves

@@ -1,5 +1,6 @@
 // libdsdenoise, host side of RMVPE pitch extraction: dsd_rmvpe_* (kernels: rmvpe_kernels.hip; front end: mel_api.hip)
 #include "api_host.h"
+#include <float.h>
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // RMVPE pitch extraction (dsd_rmvpe_*): modules/pe/rmvpe/ (inference.py, model.py, deepunet.py, seq.py, spec.py, utils.py)
@@ -34,6 +35,11 @@ struct RmvpeState {
     std::vector<int> iw_host, lens_host;
     DevBuf<float> fe;                                        // front end: log-mel, resampled audio
     DevBuf<int> lens;                                        // resampler: samples in / out per item
+    // Viterbi decode: the transition table (built at the first call), log_prob, the back-pointers, frame counts + the path
+    DevBuf<double> vt_tab, vt_lp;
+    DevBuf<unsigned short> vt_ptr;
+    DevBuf<int> vt_iw;
+    std::vector<int> vt_iw_host;
 };
 
 namespace {
@@ -517,6 +523,8 @@ int rmvpe_run(dsd_handle* h, const float* mel, int64_t sb, int64_t sm, int64_t s
     dp.out_hidden = hidden_out;
     dp.o_sb = (long)o_sb;
     dp.o_st = (long)o_st;
+    dp.center = nullptr;
+    dp.c_sb = 0;
     RM_LAUNCH(launch_rm_decode(dp, st), "rmvpe decode");
     return DSD_OK;
 }
@@ -554,6 +562,62 @@ const RmvpeState::Resampler* rmvpe_resampler(dsd_handle* h, int sr) {
         return nullptr;
     r.rs.push_back(std::move(x));
     return &r.rs.back();
+}
+
+// to_local_average_f0 around the argmax (centers NULL) or around centers[b * c_stride_b + t]
+int rmvpe_decode_frames(dsd_handle* h, const char* who, const float* hidden, const int* centers, int B, int T, int64_t h_stride_b,
+                        int64_t h_stride_t, int64_t c_stride_b, float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
+    RmvpeState& r = *h->pe;
+    HIP_OK(h, hipSetDevice(h->cfg.device));
+    std::vector<int>& iw = r.iw_host;
+    iw.assign(B, T);
+    int rc = r.iws.reserve(h, iw.size(), who);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_OK(h, hipMemcpyAsync(r.iws.p, iw.data(), iw.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    RmDecodeP dp;
+    dp.hidden = hidden;
+    dp.h_sb = (long)h_stride_b;
+    dp.h_st = (long)h_stride_t;
+    dp.T = r.iws.p;
+    dp.B = B;
+    dp.Tmax = T;
+    dp.thred = thred;
+    dp.f0 = f0_out;
+    dp.f_sb = (long)f0_stride_b;
+    dp.out_hidden = nullptr;
+    dp.o_sb = dp.o_st = 0;
+    dp.center = centers;
+    dp.c_sb = (long)c_stride_b;
+    RM_LAUNCH(launch_rm_decode(dp, st), "rmvpe decode");
+    return DSD_OK;
+}
+
+// The Viterbi decode keeps 360 doubles of log_prob and 360 two-byte back-pointers per frame: 3,600 bytes
+constexpr int RM_VT_MAX_T = 131072;
+constexpr int64_t RM_VT_MAX_FRAMES = 1 << 20;
+// librosa.util.tiny of the float32 probabilities (utils.py:35 hands librosa a float32 array)
+constexpr double RM_VT_EPS = (double)FLT_MIN;
+
+// log(transition + eps) of utils.py:29-31 in float64, the band of column j as tab[d + 29][j] = log_trans[j + d][j]: row k is
+// divided by its own sum, which is smaller for the 29 rows at either end, so the matrix is not Toeplitz
+int rmvpe_viterbi_table(dsd_handle* h, const char* who) {
+    RmvpeState& r = *h->pe;
+    if (r.vt_tab.p) return DSD_OK;
+    std::vector<double> tab((size_t)RM_VT_W * RM_CLASSES, 0.0);
+    for (int k = 0; k < RM_CLASSES; ++k) {
+        long sum = 0;
+        for (int j = 0; j < RM_CLASSES; ++j) sum += std::max(30 - std::abs(k - j), 0);
+        for (int j = std::max(k - RM_VT_BAND, 0); j <= std::min(k + RM_VT_BAND, RM_CLASSES - 1); ++j)
+            tab[(size_t)(k - j + RM_VT_BAND) * RM_CLASSES + j] = log((double)(30 - std::abs(k - j)) / (double)sum + RM_VT_EPS);
+    }
+    int rc = r.vt_tab.reserve(h, tab.size(), who);
+    if (rc) return rc;
+    if (hipMemcpy(r.vt_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+        r.vt_tab = DevBuf<double>();
+        return fail(h, DSD_EHIP, "%s: the transition table could not be placed on the device", who);
+    }
+    return DSD_OK;
 }
 
 }  // namespace
@@ -633,19 +697,66 @@ int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, i
     if (!h || !hidden || !f0_out) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: null argument");
     if (!is_pe(h)) return fail(h, DSD_ESTATE, "dsd_rmvpe_decode: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)");
     if (B < 1 || T < 1 || T > (1 << 24)) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: need B >= 1 and 1 <= T <= 2^24");
+    return rmvpe_decode_frames(h, "dsd_rmvpe_decode", hidden, nullptr, B, T, h_stride_b, h_stride_t, 0, thred, f0_out, f0_stride_b,
+                               stream);
+}
+
+int dsd_rmvpe_decode_at(dsd_handle* h, const float* hidden, const int32_t* centers, int32_t B, int32_t T, int64_t h_stride_b,
+                        int64_t h_stride_t, int64_t c_stride_b, float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
+    const char* who = "dsd_rmvpe_decode_at";
+    if (!h || !hidden || !centers || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
+    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
+    if (B < 1 || T < 1 || T > RM_VT_MAX_T) return fail(h, DSD_EINVAL, "%s: need B >= 1 and 1 <= T <= %d frames", who, RM_VT_MAX_T);
+    return rmvpe_decode_frames(h, who, hidden, centers, B, T, h_stride_b, h_stride_t, c_stride_b, thred, f0_out, f0_stride_b, stream);
+}
+
+int dsd_rmvpe_decode_viterbi(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
+                             const int64_t* lengths, float thred, float* f0_out, int64_t f0_stride_b, int32_t* path_out,
+                             int64_t path_stride_b, void* stream) {
+    const char* who = "dsd_rmvpe_decode_viterbi";
+    if (!h || !hidden || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
+    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
+    if (B < 1 || T < 1 || T > RM_VT_MAX_T || (int64_t)B * T > RM_VT_MAX_FRAMES)
+        return fail(h, DSD_EINVAL, "%s: need B >= 1, 1 <= T <= %d frames and B * T <= %lld frames (the back-pointer and log_prob "
+                    "workspaces take 3600 bytes per frame)", who, RM_VT_MAX_T, (long long)RM_VT_MAX_FRAMES);
     RmvpeState& r = *h->pe;
+    std::vector<int>& iw = r.vt_iw_host;
+    iw.resize(B);
+    for (int b = 0; b < B; ++b) {
+        const int64_t v = lengths ? lengths[b] : T;
+        if (v < 1 || v > T) return fail(h, DSD_EINVAL, "%s: lengths[%d] = %lld outside [1, %d]", who, b, (long long)v, T);
+        iw[b] = (int)v;
+    }
     HIP_OK(h, hipSetDevice(h->cfg.device));
-    std::vector<int>& iw = r.iw_host;
-    iw.assign(B, T);
-    int rc = r.iws.reserve(h, iw.size(), "dsd_rmvpe_decode");
-    if (rc) return rc;
+    const size_t frames = (size_t)B * T;
+    int rc;
+    if ((rc = rmvpe_viterbi_table(h, who)) || (rc = r.vt_lp.reserve(h, frames * RM_CLASSES, who)) ||
+        (rc = r.vt_ptr.reserve(h, frames * RM_CLASSES, who)) || (rc = r.vt_iw.reserve(h, B + frames, who)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipMemcpyAsync(r.iws.p, iw.data(), iw.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(r.vt_iw.p, iw.data(), iw.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    RmViterbiP vp;
+    vp.hidden = hidden;
+    vp.h_sb = (long)h_stride_b;
+    vp.h_st = (long)h_stride_t;
+    vp.T = r.vt_iw.p;
+    vp.B = B;
+    vp.Tmax = T;
+    vp.tab = r.vt_tab.p;
+    vp.eps = RM_VT_EPS;
+    vp.log_eps = log(RM_VT_EPS);
+    vp.log_p_init = log(1.0 / RM_CLASSES + RM_VT_EPS);
+    vp.lp = r.vt_lp.p;
+    vp.ptr = r.vt_ptr.p;
+    vp.center = r.vt_iw.p + B;
+    vp.path_out = path_out;
+    vp.p_sb = (long)path_stride_b;
+    RM_LAUNCH(launch_rm_viterbi(vp, st), "rmvpe viterbi");
     RmDecodeP dp;
     dp.hidden = hidden;
     dp.h_sb = (long)h_stride_b;
     dp.h_st = (long)h_stride_t;
-    dp.T = r.iws.p;
+    dp.T = r.vt_iw.p;
     dp.B = B;
     dp.Tmax = T;
     dp.thred = thred;
@@ -653,6 +764,8 @@ int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, i
     dp.f_sb = (long)f0_stride_b;
     dp.out_hidden = nullptr;
     dp.o_sb = dp.o_st = 0;
+    dp.center = vp.center;
+    dp.c_sb = T;
     RM_LAUNCH(launch_rm_decode(dp, st), "rmvpe decode");
     return DSD_OK;
 }

@@ -1,4 +1,5 @@
-// RMVPE pitch extraction (modules/pe/rmvpe/, E2E0 + MelSpectrogram + to_local_average_f0), fp32 throughout:
+// RMVPE pitch extraction (modules/pe/rmvpe/, E2E0 + MelSpectrogram + to_local_average_f0 / to_viterbi_f0), fp32 throughout
+// but for the Viterbi recursion, which is double:
 //   rm_resample_kernel  torchaudio's sinc_interp_hann Resample(sr, 16000, lowpass_filter_width=128) as a polyphase FIR
 //   rm_prep_kernel      log-mel [b][m][t] (caller strides) -> unet.encoder.bn(pad(mel)) in the [b][t][f] layout
 //   rm_conv3_kernel     3x3 conv (BN folded into the weights) + ReLU, then the ConvBlockRes residual (identity or the 1x1
@@ -6,7 +7,8 @@
 //   rm_tconv_kernel     ConvTranspose2d(3x3, stride 2, padding 1, output_padding 1) + folded BN + ReLU
 //   rm_linear_kernel    frames x weights (+ bias, optional sigmoid): the GRU input projections and the Linear heads
 //   rm_gru_kernel       one GRU direction of one item per workgroup; W_hh split over registers, LDS and L2
-//   rm_decode_kernel    argmax, the local weighted average of the cents, f0, the threshold
+//   rm_decode_kernel    argmax (or a given centre), the local weighted average of the cents, f0, the threshold
+//   rm_logprob_kernel, rm_viterbi_kernel   to_viterbi_f0's path (librosa.sequence.viterbi) in double: the centres of the decode
 // Activations are [item][frame][bin][channel] (channels innermost): the K walk of a conv is contiguous in the channels,
 // and the head's [frame][bin][3] output is the GRU's input row as it stands.
 // Work is listed per (item, tile) with the item's own frame count, so a ragged item computes exactly as its lone call.
@@ -361,7 +363,8 @@ __global__ __launch_bounds__(768) void rm_gru_kernel(const RmGruP p) {
 // ---------------------------------------------------------------------------------------------
 // to_local_average_f0 (utils.py:8-23): one wave per frame (b, t < T_b).  argmax over the 360 classes (first index on ties),
 // the weighted mean of 20 i + CONST over [c - 4, c + 5) clipped to [0, 360), f0 = 10 * 2^(cents / 1200), 0 where max < thred.
-// Optionally copies the frame's 360 values to hidden_out.
+// Optionally copies the frame's 360 values to hidden_out.  With p.center the window sits around that class instead of the
+// argmax (to_local_average_f0(hidden, center=...), utils.py:11-14); the threshold still reads the frame's maximum.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rm_decode_kernel(const RmDecodeP p) {
     const int lane = threadIdx.x & 63;
@@ -388,6 +391,7 @@ __global__ __launch_bounds__(256) void rm_decode_kernel(const RmDecodeP p) {
         }
     }
     if (lane != 0 || !p.f0) return;
+    if (p.center) bi = min(max(p.center[(long)b * p.c_sb + t], 0), 359);     // the threshold still reads the frame's maximum
     const int lo = max(bi - 4, 0), hi = min(bi + 5, 360);
     float ps = 0.f, ws = 0.f;
     for (int i = lo; i < hi; ++i) {
@@ -397,6 +401,158 @@ __global__ __launch_bounds__(256) void rm_decode_kernel(const RmDecodeP p) {
     const float cents = ps / (ws + (ws == 0.f ? 1.f : 0.f));
     const float f0 = 10.f * exp2f(cents / 1200.f);
     p.f0[(long)b * p.f_sb + t] = best < p.thred ? 0.f : f0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// to_viterbi_f0 (utils.py:26-43) = librosa.sequence.viterbi (0.9.2) over 360 states, in double from the fp32 hidden:
+//   log_prob[t][j] = log(hidden[t][j] / sum_i hidden[t][i] + eps), eps = the float32 tiny (what a zero probability and a
+//   jump of 30 classes or more cost: log(eps) = -87.34)
+//   value[0] = log_prob[0] + log(1 / 360 + eps);   value[t][j] = log_prob[t][j] + max_k (value[t - 1][k] + log_trans[k][j]),
+//   ptr[t][j] = the first k at that maximum;   state[T - 1] = argmax value[T - 1], state[t] = ptr[t + 1][state[t + 1]]
+// rm_logprob_kernel: one wave per frame (b, t < T_b) writes the frame's log_prob row.
+// ---------------------------------------------------------------------------------------------
+constexpr int VT_S = 360, VT_THREADS = 384, VT_WAVES = VT_THREADS / 64, VT_PAD = VT_THREADS + RM_VT_W - 1;
+constexpr int VT_ROWS = 32, VT_ROW_DW = VT_S / 2, VT_PRE = VT_ROWS * VT_ROW_DW / VT_THREADS;
+static_assert(VT_PRE * VT_THREADS == VT_ROWS * VT_ROW_DW, "a chunk of back-pointer rows is a whole number of dwords per thread");
+
+__global__ __launch_bounds__(256) void rm_logprob_kernel(const RmViterbiP p) {
+    const int lane = threadIdx.x & 63;
+    const long fr = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int b = (int)(fr / p.Tmax), t = (int)(fr % p.Tmax);
+    if (b >= p.B || t >= p.T[b]) return;
+    const float* __restrict__ hv = p.hidden + (long)b * p.h_sb + (long)t * p.h_st;
+    double s = 0.0;
+    for (int i = lane; i < VT_S; i += 64) s += (double)hv[i];
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    double* __restrict__ lp = p.lp + ((long)b * p.Tmax + t) * VT_S;
+    for (int i = lane; i < VT_S; i += 64) lp[i] = log((double)hv[i] / s + p.eps);
+}
+
+// value[t] of thread j's state into the step's LDS buffer, and the wave's first-index argmax of it; ends in the step's barrier
+__device__ __forceinline__ void vt_publish(double v, int j, double* sv, double* wv, int* wk) {
+    if (j < VT_S) sv[j + RM_VT_BAND] = v;
+    double m = v;
+    int k = j;
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(m, off);
+        const int ok = __shfl_xor(k, off);
+        if (ov > m || (ov == m && ok < k)) {
+            m = ov;
+            k = ok;
+        }
+    }
+    if ((j & 63) == 0) {
+        wv[j >> 6] = m;
+        wk[j >> 6] = k;
+    }
+    __syncthreads();
+}
+// the workgroup's first-index argmax from the waves' (ascending classes: a strict > keeps the first index)
+__device__ __forceinline__ void vt_argmax(const double* wv, const int* wk, double& gv, int& gk) {
+    gv = wv[0];
+    gk = wk[0];
+#pragma unroll
+    for (int q = 1; q < VT_WAVES; ++q)
+        if (wv[q] > gv) {
+            gv = wv[q];
+            gk = wk[q];
+        }
+    gk = min(gk, VT_S - 1);         // NaN input (a frame that sums to zero) compares false everywhere: keep every index a state
+}
+
+// ---------------------------------------------------------------------------------------------
+// rm_viterbi_kernel: one workgroup per item, thread j owns state j, the item's own T_b steps.  value[t - 1] sits in LDS
+// (double-buffered, -inf on 29 classes either side), the 59 transition terms of column j in registers.  Outside the band
+// every candidate is value[t - 1][k] + log(eps), so the only one that can win is the workgroup's first-index argmax k* of
+// value[t - 1], and only where |k* - j| >= 30; first index on ties throughout.  One barrier per step.
+// The backtrack follows in the same workgroup: the back-pointer rows to visit are known (T_b - 1 .. 1), only the column is
+// not, so a chunk of 32 rows is fetched by all threads into registers while thread 0 walks the previous chunk in LDS.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(VT_THREADS) void rm_viterbi_kernel(const RmViterbiP p) {
+    __shared__ double sv[2][VT_PAD];
+    __shared__ double wv[2][VT_WAVES];
+    __shared__ int wk[2][VT_WAVES];
+    __shared__ unsigned int srow[VT_ROWS * VT_ROW_DW];
+    __shared__ int spath[VT_ROWS];
+    const int b = blockIdx.x, j = threadIdx.x, T = p.T[b];
+    const bool live = j < VT_S;
+    double w[RM_VT_W];
+#pragma unroll
+    for (int d = 0; d < RM_VT_W; ++d) w[d] = live ? p.tab[d * VT_S + j] : 0.0;
+    for (int i = j; i < 2 * VT_PAD; i += VT_THREADS) (&sv[0][0])[i] = -INFINITY;
+    __syncthreads();
+    const double* __restrict__ lp = p.lp + (long)b * p.Tmax * VT_S;
+    unsigned short* ptr = p.ptr + (long)b * p.Tmax * VT_S;
+    int cur = 0;
+    vt_publish(live ? lp[j] + p.log_p_init : -INFINITY, j, sv[0], wv[0], wk[0]);
+    for (int t = 1; t < T; ++t) {
+        const double lpt = live ? lp[(long)t * VT_S + j] : 0.0;
+        const double* pv = sv[cur] + j;         // pv[d] = value[t - 1][j + d - 29]
+        double best = -INFINITY;
+        int bd = RM_VT_BAND;
+#pragma unroll
+        for (int d = 0; d < RM_VT_W; ++d) {
+            const double c = pv[d] + w[d];
+            if (c > best) {
+                best = c;
+                bd = d;
+            }
+        }
+        int bk = j + bd - RM_VT_BAND;
+        double gv;
+        int gk;
+        vt_argmax(wv[cur], wk[cur], gv, gk);
+        if (abs(gk - j) > RM_VT_BAND) {
+            const double c = gv + p.log_eps;
+            if (c > best || (c == best && gk < bk)) {
+                best = c;
+                bk = gk;
+            }
+        }
+        if (live) ptr[(long)t * VT_S + j] = (unsigned short)bk;
+        cur ^= 1;
+        vt_publish(live ? lpt + best : -INFINITY, j, sv[cur], wv[cur], wk[cur]);
+    }
+    double gv;
+    int state;
+    vt_argmax(wv[cur], wk[cur], gv, state);
+    int* __restrict__ center = p.center + (long)b * p.Tmax;
+    int* __restrict__ path = p.path_out ? p.path_out + (long)b * p.p_sb : nullptr;
+    if (j == 0) {
+        center[T - 1] = state;
+        if (path) path[T - 1] = state;
+    }
+    // rows hi .. lo (descending) give state[hi - 1] .. state[lo - 1]; the stores above are this workgroup's own, behind a barrier
+    unsigned int pre[VT_PRE];
+    auto fetch = [&](int hi) {
+        const int lo = max(hi - VT_ROWS + 1, 1), n = (hi - lo + 1) * VT_ROW_DW;
+        const unsigned int* src = reinterpret_cast<const unsigned int*>(ptr + (long)lo * VT_S);
+#pragma unroll
+        for (int q = 0; q < VT_PRE; ++q) {
+            const int i = j + q * VT_THREADS;
+            pre[q] = i < n ? src[i] : 0u;
+        }
+    };
+    if (T > 1) fetch(T - 1);
+    for (int hi = T - 1; hi >= 1; hi -= VT_ROWS) {
+        const int lo = max(hi - VT_ROWS + 1, 1), n = hi - lo + 1;
+#pragma unroll
+        for (int q = 0; q < VT_PRE; ++q) srow[j + q * VT_THREADS] = pre[q];
+        __syncthreads();
+        if (hi - VT_ROWS >= 1) fetch(hi - VT_ROWS);
+        if (j == 0) {
+            const unsigned short* rows = reinterpret_cast<const unsigned short*>(srow);
+            for (int r = n - 1; r >= 0; --r) {
+                state = min((int)rows[r * VT_S + state], VT_S - 1);
+                spath[r] = state;
+            }
+        }
+        __syncthreads();
+        if (j < n) {
+            center[lo - 1 + j] = spath[j];
+            if (path) path[lo - 1 + j] = spath[j];
+        }
+    }
 }
 
 hipError_t launch_rm_resample(const RmResampleP& p, int B, long max_blocks, int nw, hipStream_t st) {
@@ -429,6 +585,12 @@ hipError_t launch_rm_gru(const RmGruP& p, int B, hipStream_t st) {
 hipError_t launch_rm_decode(const RmDecodeP& p, hipStream_t st) {
     const long frames = (long)p.B * p.Tmax;
     hipLaunchKernelGGL(rm_decode_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_rm_viterbi(const RmViterbiP& p, hipStream_t st) {
+    const long frames = (long)p.B * p.Tmax;
+    hipLaunchKernelGGL(rm_logprob_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(rm_viterbi_kernel, dim3((unsigned)p.B), dim3(VT_THREADS), 0, st, p);
     return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 
 `RMVPE(model_path_or_state_dict)` runs waveform -> f0 on the GPU: the resampler to 16 kHz, the HTK log-mel, E2E0 and
 to_local_average_f0 are HIP kernels (rmvpe_kernels.hip, mel_kernels.hip); get_pitch's post-processing is numpy on the
-host, as in the reference.  `infer_from_audio_ragged` extracts the f0 of clips of different lengths in one call, each
+host, as in the reference.  `decode_viterbi` / `use_viterbi=True` is to_viterbi_f0: librosa.sequence.viterbi restated as
+a HIP kernel in double.  `infer_from_audio_ragged` extracts the f0 of clips of different lengths in one call, each
 exactly as a lone call would.  `E2E0` is the reference's torch module (same module and state_dict names): the weight
 container of synthetic checkpoints and the torch restatement tools/time_pitch.py times against.  No CPU path.
 """
@@ -239,27 +240,71 @@ class RMVPE:
                    "dsd_rmvpe_mel_to_hidden")
         return out
 
-    @torch.no_grad()
-    def decode(self, hidden, thred=0.03, use_viterbi=False):
-        """to_local_average_f0 on hidden [B, T, 360] (or [T, 360]) -> f0 numpy [B, T] ([T] for B = 1, as the reference's
-        .squeeze(0))."""
-        if use_viterbi:
-            raise NotImplementedError("use_viterbi=True (librosa.sequence.viterbi) is not implemented on the GPU")
+    def _hidden(self, hidden):
         h = torch.as_tensor(hidden, dtype=torch.float32, device=self.device)
         if h.dim() == 2:
             h = h[None]
-        h = h.contiguous()
+        return h.contiguous()
+
+    @torch.no_grad()
+    def decode(self, hidden, thred=0.03, use_viterbi=False, center=None):
+        """to_local_average_f0 on hidden [B, T, 360] (or [T, 360]) -> f0 numpy [B, T] ([T] for B = 1, as the reference's
+        .squeeze(0)).  `center` [B, T] (or [T]) integers: the window sits around them instead of the argmax
+        (to_local_average_f0(hidden, center=...)).  The Viterbi decode is `decode_viterbi`."""
+        if use_viterbi:
+            raise NotImplementedError("decode(use_viterbi=True) is spelled decode_viterbi(hidden, thred) here "
+                                      "(librosa.sequence.viterbi restated on the GPU)")
+        h = self._hidden(hidden)
         b, t, _ = h.shape
         f0 = torch.empty(b, t, device=self.device)
-        _lib.check(self._h, _lib.lib().dsd_rmvpe_decode(self._h, C.c_void_p(h.data_ptr()), b, t, t * N_CLASS, N_CLASS,
-                                                        float(thred), C.c_void_p(f0.data_ptr()), t, self._stream()),
-                   "dsd_rmvpe_decode")
+        if center is None:
+            _lib.check(self._h, _lib.lib().dsd_rmvpe_decode(self._h, C.c_void_p(h.data_ptr()), b, t, t * N_CLASS, N_CLASS,
+                                                            float(thred), C.c_void_p(f0.data_ptr()), t, self._stream()),
+                       "dsd_rmvpe_decode")
+        else:
+            c = torch.as_tensor(center, device=self.device).to(torch.int32).reshape(b, t).contiguous()
+            _lib.check(self._h, _lib.lib().dsd_rmvpe_decode_at(self._h, C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), b, t,
+                                                               t * N_CLASS, N_CLASS, t, float(thred),
+                                                               C.c_void_p(f0.data_ptr()), t, self._stream()),
+                       "dsd_rmvpe_decode_at")
         f0 = f0.cpu().numpy()
         return f0[0] if b == 1 else f0
 
+    def _viterbi(self, h, lengths, thred, f0, path=None):
+        """dsd_rmvpe_decode_viterbi on device tensors: hidden h [B, T, 360] (contiguous) -> f0 [B, T] (and the int32 path
+        [B, T]); frames at or past lengths[b] are left as they are."""
+        b, t, _ = h.shape
+        lens = None if lengths is None else (C.c_int64 * b)(*[int(v) for v in lengths])
+        _lib.check(self._h, _lib.lib().dsd_rmvpe_decode_viterbi(
+            self._h, C.c_void_p(h.data_ptr()), b, t, t * N_CLASS, N_CLASS, lens, float(thred), C.c_void_p(f0.data_ptr()),
+            f0.stride(0), C.c_void_p(None if path is None else path.data_ptr()), 0 if path is None else path.stride(0),
+            self._stream()), "dsd_rmvpe_decode_viterbi")
+
     @torch.no_grad()
-    def _infer(self, wav, lengths, sample_rate, thred, want_hidden=False):
+    def decode_viterbi(self, hidden, thred=0.03, lengths=None, return_path=False):
+        """to_viterbi_f0 (utils.py:26-43) on hidden [B, T, 360] (or [T, 360]): the librosa.sequence.viterbi path over the 360
+        classes, then to_local_average_f0 around it -> f0 numpy [B, T] ([T] for B = 1).  With `lengths` (B frame counts)
+        item b is decoded as a lone call on its first lengths[b] frames and a list of B arrays comes back.  With
+        return_path: (f0, path), the path as int64 like librosa's."""
+        h = self._hidden(hidden)
+        b, t, _ = h.shape
+        f0 = torch.zeros(b, t, device=self.device)
+        path = torch.zeros(b, t, dtype=torch.int32, device=self.device) if return_path else None
+        self._viterbi(h, lengths, thred, f0, path)
+        f0 = f0.cpu().numpy()
+        if return_path:
+            path = path.cpu().numpy().astype(np.int64)
+        if lengths is not None:
+            f0 = [f0[i, : int(n)] for i, n in enumerate(lengths)]
+            path = [path[i, : int(n)] for i, n in enumerate(lengths)] if return_path else None
+        elif b == 1:
+            f0, path = f0[0], (path[0] if return_path else None)
+        return (f0, path) if return_path else f0
+
+    @torch.no_grad()
+    def _infer(self, wav, lengths, sample_rate, thred, want_hidden=False, use_viterbi=False):
         b, n = wav.shape
+        want_hidden = want_hidden or use_viterbi     # the Viterbi decode reads the hidden where dsd_rmvpe_infer left it
         frames = [num_frames(v, sample_rate) for v in lengths]
         t = max(frames)
         f0 = torch.zeros(b, t, device=self.device)
@@ -269,17 +314,17 @@ class RMVPE:
             self._h, C.c_void_p(wav.data_ptr()), b, n, wav.stride(0), lens, int(sample_rate), float(thred),
             C.c_void_p(f0.data_ptr()), t, C.c_void_p(hid.data_ptr() if want_hidden else None), t * N_CLASS, N_CLASS,
             self._stream()), "dsd_rmvpe_infer")
+        if use_viterbi:
+            self._viterbi(hid, frames, thred, f0)
         return f0, hid, frames
 
     def infer_from_audio(self, audio, sample_rate=16000, thred=0.03, use_viterbi=False):
         """inference.py:38-51: a 1-D numpy waveform -> f0 numpy [T] float32."""
-        if use_viterbi:
-            raise NotImplementedError("use_viterbi=True (librosa.sequence.viterbi) is not implemented on the GPU")
         wav = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device)[None]
-        f0, _, _ = self._infer(wav, [wav.shape[1]], sample_rate, thred)
+        f0, _, _ = self._infer(wav, [wav.shape[1]], sample_rate, thred, use_viterbi=use_viterbi)
         return f0[0].cpu().numpy()
 
-    def infer_from_audio_ragged(self, waveforms, sample_rate=16000, thred=0.03, want_hidden=False):
+    def infer_from_audio_ragged(self, waveforms, sample_rate=16000, thred=0.03, want_hidden=False, *, use_viterbi=False):
         """One call over clips of different lengths: a list of 1-D waveforms (numpy or tensors) -> a list of f0 numpy
         arrays, each equal to infer_from_audio on that clip alone (with want_hidden: a list of (f0, hidden) pairs)."""
         if not len(waveforms):
@@ -289,16 +334,18 @@ class RMVPE:
         wav = torch.zeros(len(ws), max(lengths), device=self.device)
         for i, w in enumerate(ws):
             wav[i, : lengths[i]] = w.to(self.device)
-        f0, hid, frames = self._infer(wav, lengths, sample_rate, thred, want_hidden)
+        f0, hid, frames = self._infer(wav, lengths, sample_rate, thred, want_hidden, use_viterbi)
         f0 = f0.cpu().numpy()
         if not want_hidden:
             return [f0[i, : frames[i]] for i in range(len(ws))]
         hid = hid.cpu().numpy()
         return [(f0[i, : frames[i]], hid[i, : frames[i]]) for i in range(len(ws))]
 
-    def get_pitch(self, waveform, samplerate, length, *, hop_size, f0_min=65, f0_max=1100, speed=1, interp_uv=False):
-        """inference.py:53-70 -> (f0 [length] float32, uv [length] bool)."""
-        f0 = self.infer_from_audio(waveform, sample_rate=samplerate)
+    def get_pitch(self, waveform, samplerate, length, *, hop_size, f0_min=65, f0_max=1100, speed=1, interp_uv=False,
+                  use_viterbi=False):
+        """inference.py:53-70 -> (f0 [length] float32, uv [length] bool).  `use_viterbi` is an extension of the reference's
+        signature (its get_pitch always decodes by the local average): the binarizers' way to the Viterbi decode."""
+        f0 = self.infer_from_audio(waveform, sample_rate=samplerate, use_viterbi=use_viterbi)
         f0, uv = interp_f0(f0)
         hop_size = int(np.round(hop_size * speed))
         time_step = hop_size / samplerate

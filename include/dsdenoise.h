@@ -526,6 +526,30 @@ int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t 
 int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
                      float thred, float* f0_out, int64_t f0_stride_b, void* stream);
 /*
+ * Replaces: to_local_average_f0(hidden, center=centers, thred)  (utils.py:8-23 with the argument of :11-14): the window
+ * [clip(c - 4, 0), clip(c + 5, 360)) sits around centers[b * c_stride_b + t] (device int32, clamped to [0, 359]) instead of
+ * the argmax; the threshold still reads the frame's maximum, so a window of zeros on a voiced frame gives 10 Hz.
+ * 1 <= T <= 131072 frames, as dsd_rmvpe_decode_viterbi: above it DSD_EINVAL before any launch.
+ */
+int dsd_rmvpe_decode_at(dsd_handle* h, const float* hidden, const int32_t* centers, int32_t B, int32_t T, int64_t h_stride_b,
+                        int64_t h_stride_t, int64_t c_stride_b, float thred, float* f0_out, int64_t f0_stride_b, void* stream);
+/*
+ * Replaces: RMVPE.decode(hidden, thred, use_viterbi=True) = to_viterbi_f0  (utils.py:26-43) and the
+ * librosa.sequence.viterbi (0.9.2; the reference pins librosa < 0.10) it calls, restated: 360 states, the row-normalised
+ * triangular transition matrix of utils.py:29-31, a uniform initial distribution, eps = the float32 tiny.  log_prob is
+ * formed in double from the fp32 hidden (the reference: in float32); value, the transition terms and every comparison are
+ * double, first index on ties.  Then to_local_average_f0 around the path.
+ *   lengths     HOST array of B frame counts (1 <= lengths[b] <= T) or NULL; item b is decoded exactly as a lone call on
+ *               its own lengths[b] frames, and frames at or past T_b are not written (f0_out and path_out)
+ *   path_out    NULL, or the path: state of frame t at path_out[b * path_stride_b + t] (device int32, 0 .. 359)
+ * A frame whose 360 values sum to zero makes the reference's probabilities NaN; here the call returns and every state it
+ * writes is in [0, 359], nothing more.  The log_prob and back-pointer workspaces take 3600 bytes per frame: 1 <= T <= 131072
+ * frames and B * T <= 1048576 frames per call, above which DSD_EINVAL (naming the cap) before any launch.
+ */
+int dsd_rmvpe_decode_viterbi(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
+                             const int64_t* lengths, float thred, float* f0_out, int64_t f0_stride_b, int32_t* path_out,
+                             int64_t path_stride_b, void* stream);
+/*
  * Replaces: RMVPE.infer_from_audio(audio, sample_rate, thred, use_viterbi=False)  (inference.py:38-51): resample to 16 kHz
  * unless sample_rate == 16000 (torchaudio Resample(sr, 16000, lowpass_filter_width=128): Hann-windowed sinc, rolloff
  * 0.99), MelSpectrogram(center=True), mel2hidden, decode.
