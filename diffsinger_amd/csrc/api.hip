@@ -23,9 +23,9 @@
 #include "api_host.h"
 
 // ------------------------------------------------------------------------------------------
-// path switches: every C-ABI entry point that launches kernels takes a snapshot into its handle (dsd_internal.h, PathOpts)
+// path switches: every C-ABI entry point that launches kernels takes a snapshot into its handle (enter() in api_host.h)
 // ------------------------------------------------------------------------------------------
-namespace {
+namespace dsd {
 PathOpts read_path_opts() {
     auto geti = [](const char* name) {
         const char* v = getenv(name);
@@ -46,9 +46,7 @@ PathOpts read_path_opts() {
     o.x3_wide = geti("DSD_X3_WIDE");
     return o;
 }
-}  // namespace
 
-namespace dsd {
 TimingSlot& timing_slot() {
     static thread_local TimingSlot slot;
     return slot;
@@ -191,14 +189,6 @@ inline int true_channels(const dsd_handle* h) { return h->c_user ? h->c_user : h
 inline int FM_of(const dsd_handle* h) { return h->cfg.in_dims * h->cfg.n_feats; }
 inline int L_of(const dsd_handle* h) { return h->cfg.num_layers; }
 inline int inner_of(const dsd_handle* h) { return h->cfg.num_channels * h->cfg.expansion_factor; }
-// the entry points of the model families refuse an analysis handle, which has entry points of its own
-int reject_analysis_handle(const dsd_handle* h, const char* who) {
-    const char* is = is_mel(h)  ? "a mel analysis handle (use dsd_mel_analyze)"
-                     : is_pe(h) ? "an RMVPE pitch extractor (use dsd_rmvpe_*)"
-                     : is_hs(h) ? "a harmonic-noise separator (use dsd_hnsep_*)"
-                                : nullptr;
-    return is ? fail(const_cast<dsd_handle*>(h), DSD_ESTATE, "%s: this handle is %s", who, is) : DSD_OK;
-}
 
 inline int voc_stage_channels(const dsd_vocoder_config& v, int i) { return v.upsample_initial_channel >> (i + 1); }
 inline long voc_upp(const dsd_vocoder_config& v, int from) {     // product of upsample_rates[from:]
@@ -2067,10 +2057,7 @@ const char* dsd_last_error(const dsd_handle* h) { return h ? h->err.c_str() : g_
 namespace {
 
 // dsd_create (any_width = false) and dsd_create_any_width: the same handle, two width rules for LYNXNet and the aux decoder
-int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const char* who) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "%s: null argument", who);
-    if (cfg->struct_size != (int32_t)sizeof(dsd_config))
-        return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, cfg->struct_size, sizeof(dsd_config));
+int check_config(const dsd_config* cfg, bool any_width, const char* who) {
     if (cfg->backbone != DSD_BACKBONE_WAVENET && cfg->backbone != DSD_BACKBONE_LYNXNET && cfg->backbone != DSD_AUX_CONVNEXT)
         return fail(nullptr, DSD_EINVAL, "%s: unknown backbone %d", who, cfg->backbone);
     if (cfg->in_dims < 1 || cfg->n_feats < 1 || cfg->num_layers < 1 || cfg->hidden_size < 1)
@@ -2106,7 +2093,11 @@ int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const c
         if (cfg->activation < DSD_ACT_PRELU || cfg->activation > DSD_ACT_RELU)
             return fail(nullptr, DSD_EINVAL, "%s: %d is not a valid activation", who, cfg->activation);
     }
-    if (int rc = select_device(who, cfg->device)) return rc;
+    return DSD_OK;
+}
+
+int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const char* who) {
+    if (int rc = create_check(cfg, out, who, [&](const dsd_config* c) { return check_config(c, any_width, who); })) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_layer_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_rowsplit_init_all();
@@ -2116,8 +2107,8 @@ int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const c
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_edge_init_all();
     if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_LYNXNET) ie = lx_layer_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: kernel attribute setup failed: %s", who, hipGetErrorString(ie));
-    dsd_handle* h = new dsd_handle();
-    h->cfg = *cfg;
+    dsd_handle* h = new_handle(cfg->backbone, cfg->device);
+    h->cfg = *cfg;              // every other field is the caller's too
     h->opts = read_path_opts();
     h->precision = h->opts.precision == 1 ? 1 : 0;       // DSD_PRECISION=1: split-bf16 layer kernels (dsd_set_precision)
     {
@@ -2161,10 +2152,11 @@ void dsd_destroy(dsd_handle* h) {
 
 int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const int64_t* shape, int32_t ndim,
                     int32_t on_device) {
-    if (h && is_pe(h)) return rmvpe_load_weight(h, name, data, shape, ndim, on_device);
-    if (h && is_hs(h)) return hnsep_load_weight(h, name, data, shape, ndim, on_device);
-    if (!h || !name || !data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
-    if (int rc = reject_analysis_handle(h, "dsd_load_weight")) return rc;
+    if (!h) return fail(nullptr, DSD_EINVAL, "dsd_load_weight: bad argument");
+    if (int rc = enter(h, "dsd_load_weight", K_WEIGHTS)) return rc;
+    if (is_pe(h)) return rmvpe_load_weight(h, name, data, shape, ndim, on_device);
+    if (is_hs(h)) return hnsep_load_weight(h, name, data, shape, ndim, on_device);
+    if (!name || !data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
     const std::string n(name);
     if ((is_enc(h) || is_tok(h)) && n == "encoder.embed_positions._float_tensor")
         return DSD_OK;       // SinusoidalPositionalEmbedding's device/dtype marker buffer (common_layers.py:59): carries no value
@@ -2184,11 +2176,11 @@ int dsd_load_weight(dsd_handle* h, const char* name, const float* data, const in
 
 int dsd_finalize_weights(dsd_handle* h) {
     if (!h) return DSD_EINVAL;
+    int rc = enter(h, "dsd_finalize_weights", K_WEIGHTS);
+    if (rc) return rc;
     if (is_pe(h)) return rmvpe_finalize(h);
     if (is_hs(h)) return hnsep_finalize(h);
-    if (int rc = reject_analysis_handle(h, "dsd_finalize_weights")) return rc;
-    int rc = check_missing(h, expected_for(h));
-    if (rc) return rc;
+    if ((rc = check_missing(h, expected_for(h)))) return rc;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if ((rc = build_packed(h))) return rc;
     destroy_graphs(h);
@@ -2203,19 +2195,13 @@ int dsd_finalize_weights(dsd_handle* h) {
 int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,
                      int64_t stride_t, void* stream) {
     if (!h || !cond) return fail(h, DSD_EINVAL, "dsd_prepare_cond: null argument");
-    h->opts = read_path_opts();
-    if (is_aux(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an aux decoder (use dsd_aux_decode)");
-    if (is_enc(h) || is_tok(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is an encoder (use dsd_encode / dsd_token_encode)");
-    if (is_voc(h)) return fail(h, DSD_ESTATE, "dsd_prepare_cond: this handle is a vocoder (use dsd_vocode)");
-    if (int rc = reject_analysis_handle(h, "dsd_prepare_cond")) return rc;
-    if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_prepare_cond: weights are not finalized");
+    int rc = enter(h, "dsd_prepare_cond", K_DENOISER, ENTER_WEIGHTS | ENTER_LAUNCH);
+    if (rc) return rc;
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_prepare_cond: B and T must be positive (B=%d, T=%d)", B, T);
     if (stride_t != 1 && stride_h != 1)
         return fail(h, DSD_EINVAL, "dsd_prepare_cond: cond must be contiguous along T ([B,H,T]) or along H ([B,T,H])");
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    int rc = ensure_workspace(h, B, T, st);
-    if (rc) return rc;
+    if ((rc = ensure_workspace(h, B, T, st))) return rc;
     const int H = h->cfg.hidden_size, Ts = h->Ts, L = L_of(h), R = cp_rows(h);
     hipError_t e = launch_pack(cond, stride_b, stride_h, stride_t, h->cond_i, B, H, T, Ts, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "pack(cond) launch failed: %s", hipGetErrorString(e));
@@ -2234,10 +2220,7 @@ int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int
 // K <= 848.  The creates refuse what run_gemm would refuse at the first encode call.
 constexpr int kEncConvMaxK = kMaxDynLds / (48 * 4) / 16 * 16;
 
-int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_encoder_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_encoder_config));
+static int check_encoder_config(const dsd_encoder_config* cfg) {
     if (cfg->vocab_size < 2 || cfg->enc_layers < 1 || cfg->num_heads < 1)
         return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: non-positive dimension");
     if (cfg->hidden_size < 32 || cfg->hidden_size % 32 != 0 || cfg->hidden_size % (2 * cfg->num_heads) != 0)
@@ -2253,20 +2236,20 @@ int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
     if (cfg->num_spk < 0 || cfg->num_lang < 0) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: negative table size");
     if (cfg->pos_mode < DSD_POS_ROPE || cfg->pos_mode > DSD_POS_SIN) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: pos_mode must be one of DSD_POS_*");
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU) return fail(nullptr, DSD_EINVAL, "dsd_encoder_create: ffn_act must be one of DSD_FFN_*");
-    if (int rc = select_device("dsd_encoder_create", cfg->device)) return rc;
+    return DSD_OK;
+}
+
+int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
+    if (int rc = create_check(cfg, out, "dsd_encoder_create", check_encoder_config)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_ENC_FS2_ACOUSTIC;
+    dsd_handle* h = new_handle(DSD_ENC_FS2_ACOUSTIC, cfg->device);
     h->cfg.in_dims = cfg->vocab_size;
     h->cfg.n_feats = 1;
     h->cfg.num_layers = cfg->enc_layers;
     h->cfg.num_channels = cfg->hidden_size;
     h->cfg.hidden_size = cfg->hidden_size;
     h->cfg.kernel_size = cfg->ffn_kernel_size;
-    h->cfg.device = cfg->device;
     h->ecfg = *cfg;
     h->e_ffn_act = cfg->ffn_act;
     *out = h;
@@ -2350,9 +2333,8 @@ static int run_fs2_layers(dsd_handle* h, int H, int NL, int heads, int ffn_ks, i
 int dsd_encode(dsd_handle* h, const int64_t* txt_tokens, const int64_t* mel2ph, const float* f0, int32_t B, int32_t L,
                int32_t T, const dsd_encode_extras* ex, float* cond_out, void* stream) {
     if (!h || !txt_tokens || !mel2ph || !f0 || !cond_out) return fail(h, DSD_EINVAL, "dsd_encode: null argument");
-    h->opts = read_path_opts();
-    if (!is_enc(h)) return fail(h, DSD_ESTATE, "dsd_encode: this handle is not an encoder");
-    if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_encode: weights are not finalized");
+    int rc = enter(h, "dsd_encode", K_ENC, ENTER_WEIGHTS | ENTER_LAUNCH);
+    if (rc) return rc;
     if (B < 1 || L < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_encode: B, T_txt and T must be positive (%d, %d, %d)", B, L, T);
     if (L > 2048) return fail(h, DSD_EINVAL, "dsd_encode: T_txt = %d tokens exceeds the supported 2048", L);
     const dsd_encoder_config& e = h->ecfg;
@@ -2366,10 +2348,8 @@ int dsd_encode(dsd_handle* h, const int64_t* txt_tokens, const int64_t* mel2ph, 
     for (int k = 1; k < 7; ++k)
         if (lin_present(e, k) && !feats[k]) return fail(h, DSD_EINVAL, "dsd_encode: input for %s is missing", kLinNames[k]);
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(e.device));
     const int H = e.hidden_size, Ls = padded_ts(L);
-    int rc = enc_workspace(h, B, L, H, 0, st);
-    if (rc) return rc;
+    if ((rc = enc_workspace(h, B, L, H, 0, st))) return rc;
     const float* blob = h->blob.p;
     hipError_t er;
 #define ENC_OK(expr, what)                                                                        \
@@ -2408,11 +2388,7 @@ int dsd_encode(dsd_handle* h, const int64_t* txt_tokens, const int64_t* mel2ph, 
     return DSD_OK;
 }
 
-int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_token_encoder_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: struct_size %d != %zu", cfg->struct_size,
-                    sizeof(dsd_token_encoder_config));
+static int check_token_encoder_config(const dsd_token_encoder_config* cfg) {
     if (cfg->enc_layers < 1 || cfg->num_heads < 1) return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: non-positive dimension");
     if (cfg->hidden_size < 32 || cfg->hidden_size % 32 != 0 || cfg->hidden_size % (2 * cfg->num_heads) != 0)
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: hidden_size must be a multiple of 32 and of 2 * num_heads");
@@ -2439,20 +2415,20 @@ int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** o
     }
     if (cfg->ffn_act < DSD_FFN_GELU || cfg->ffn_act > DSD_FFN_SWIGLU)
         return fail(nullptr, DSD_EINVAL, "dsd_token_encoder_create: ffn_act must be one of DSD_FFN_*");
-    if (int rc = select_device("dsd_token_encoder_create", cfg->device)) return rc;
+    return DSD_OK;
+}
+
+int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** out) {
+    if (int rc = create_check(cfg, out, "dsd_token_encoder_create", check_token_encoder_config)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_token_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_ENC_FS2_TOKENS;
+    dsd_handle* h = new_handle(DSD_ENC_FS2_TOKENS, cfg->device);
     h->cfg.in_dims = cfg->hidden_size;
     h->cfg.n_feats = 1;
     h->cfg.num_layers = cfg->enc_layers;
     h->cfg.num_channels = cfg->hidden_size;
     h->cfg.hidden_size = cfg->hidden_size;
     h->cfg.kernel_size = cfg->ffn_kernel_size;
-    h->cfg.device = cfg->device;
     h->tcfg = *cfg;
     h->e_ffn_act = cfg->ffn_act;
     *out = h;
@@ -2461,8 +2437,7 @@ int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** o
 
 static int tok_common(dsd_handle* h, const char* who, const void* a, const void* b, const void* c, int B, int L) {
     if (!h || !a || !b || !c) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    if (!is_tok(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a token encoder", who);
-    if (!h->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
+    if (int rc = enter(h, who, K_TOK, ENTER_WEIGHTS | ENTER_LAUNCH)) return rc;
     if (B < 1 || L < 1) return fail(h, DSD_EINVAL, "%s: B and L must be positive (%d, %d)", who, B, L);
     if (L > 2048) return fail(h, DSD_EINVAL, "%s: L = %d tokens exceeds the supported 2048", who, L);
     return DSD_OK;
@@ -2472,10 +2447,8 @@ int dsd_token_encode(dsd_handle* h, const float* embed, const uint8_t* padding_m
                      void* stream) {
     int rc = tok_common(h, "dsd_token_encode", embed, padding_mask, enc_out, B, L);
     if (rc) return rc;
-    h->opts = read_path_opts();
     const dsd_token_encoder_config& t = h->tcfg;
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(t.device));
     const int H = t.hidden_size;
     if ((rc = enc_workspace(h, B, L, H, t.dur_layers > 0 ? t.dur_chans : 0, st))) return rc;
     const int Ls = h->eLs;
@@ -2507,11 +2480,9 @@ int dsd_predict_dur(dsd_handle* h, const float* dur_cond, const uint8_t* padding
                     void* stream) {
     int rc = tok_common(h, "dsd_predict_dur", dur_cond, padding_mask, dur_out, B, L);
     if (rc) return rc;
-    h->opts = read_path_opts();
     const dsd_token_encoder_config& t = h->tcfg;
     if (t.dur_layers < 1) return fail(h, DSD_ESTATE, "dsd_predict_dur: this encoder was created without a duration predictor");
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(t.device));
     const int H = t.hidden_size, Cd = t.dur_chans;
     if ((rc = enc_workspace(h, B, L, H, Cd, st))) return rc;
     const int Ls = h->eLs;
@@ -2591,10 +2562,7 @@ static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float
     return DSD_OK;
 }
 
-int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_vocoder_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_vocoder_config));
+static int check_vocoder_config(const dsd_vocoder_config* cfg) {
     if (cfg->num_mels < 1 || cfg->sampling_rate < 1 || cfg->n_ups < 1 || cfg->n_ups > DSD_VOC_MAX_UPS || cfg->n_kernels < 1 ||
         cfg->n_kernels > DSD_VOC_MAX_KERNELS || (cfg->resblock != 1 && cfg->resblock != 2))
         return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: bad layer counts");
@@ -2616,21 +2584,21 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
             if (cfg->resblock_dilation_sizes[j][d] < 1 || cfg->resblock_dilation_sizes[j][d] * (cfg->resblock_kernel_sizes[j] / 2) > 48)
                 return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: residual block %d dilation %d reaches beyond 48 frames", j, d);
     }
-    if (int rc = select_device("dsd_vocoder_create", cfg->device)) return rc;
+    return DSD_OK;
+}
+
+int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
+    if (int rc = create_check(cfg, out, "dsd_vocoder_create", check_vocoder_config)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess) ie = tconv_init_all();
     if (ie == hipSuccess) ie = voc_x3_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_VOC_NSF_HIFIGAN;
+    dsd_handle* h = new_handle(DSD_VOC_NSF_HIFIGAN, cfg->device);
     h->cfg.in_dims = cfg->num_mels;
     h->cfg.n_feats = 1;
     h->cfg.num_layers = cfg->n_ups;
     h->cfg.num_channels = cfg->upsample_initial_channel;
     h->cfg.hidden_size = cfg->num_mels;
-    h->cfg.device = cfg->device;
     h->vcfg = *cfg;
     *out = h;
     return DSD_OK;
@@ -2740,13 +2708,11 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                 int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
                 const float* pre_noise, float* wav_out, void* stream) {
     if (!h || !mel || !f0 || !wav_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    h->opts = read_path_opts();
-    if (!is_voc(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a vocoder", who);
+    if (int rc = enter(h, who, K_VOC, ENTER_WEIGHTS | ENTER_LAUNCH)) return rc;
     if (!h->vcfg.mini_nsf && (!rand_ini || !noise))
         return fail(h, DSD_EINVAL, "%s: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)", who);
     if (h->vcfg.noise_sigma > 0.f && !pre_noise)
         return fail(h, DSD_EINVAL, "%s: pre_noise is required when noise_sigma > 0 (models.py:272-273)", who);
-    if (!h->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "%s: B and T must be positive (B=%d, T=%d)", who, B, T);
     if (stride_t != 1 && stride_m != 1)
         return fail(h, DSD_EINVAL, "%s: mel must be contiguous along T ([B,M,T]) or along M ([B,T,M])", who);
@@ -2758,7 +2724,6 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     const long upp = voc_upp(v, 0);
     if ((long)T * upp > (1L << 28)) return fail(h, DSD_EINVAL, "%s: %ld output samples per utterance is too long", who, (long)T * upp);
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(v.device));
     const int NU = v.n_ups, C0 = v.upsample_initial_channel, Ts0 = padded_ts(T);
     // stage lengths
     std::vector<long> len(NU + 1);
@@ -2952,16 +2917,13 @@ int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int
 int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,
                    int64_t stride_t, float* out, const float* out_scale, const float* out_shift, void* stream) {
     if (!h || !cond || !out) return fail(h, DSD_EINVAL, "dsd_aux_decode: null argument");
-    h->opts = read_path_opts();
-    if (!is_aux(h)) return fail(h, DSD_ESTATE, "dsd_aux_decode: this handle is a denoiser backbone");
-    if (!h->finalized) return fail(h, DSD_ESTATE, "dsd_aux_decode: weights are not finalized");
+    int rc = enter(h, "dsd_aux_decode", K_AUX, ENTER_WEIGHTS | ENTER_LAUNCH);
+    if (rc) return rc;
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "dsd_aux_decode: B and T must be positive (B=%d, T=%d)", B, T);
     if (stride_t != 1 && stride_h != 1)
         return fail(h, DSD_EINVAL, "dsd_aux_decode: cond must be contiguous along T ([B,H,T]) or along H ([B,T,H])");
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    int rc = ensure_workspace(h, B, T, st);
-    if (rc) return rc;
+    if ((rc = ensure_workspace(h, B, T, st))) return rc;
     if ((rc = check_lens(h, "dsd_aux_decode", B, T, st))) return rc;
     RaggedScope ragged_scope(h);
     const int H = h->cfg.hidden_size, Ts = h->Ts, L = L_of(h), C = C_of(h), M = FM_of(h);
@@ -3002,15 +2964,14 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
 
 int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, float* out, void* stream) {
     if (!h || !x || !t || !out) return fail(h, DSD_EINVAL, "dsd_denoise: null argument");
-    h->opts = read_path_opts();
+    int rc = enter(h, "dsd_denoise", K_DENOISER, ENTER_LAUNCH);      // weights: dsd_prepare_cond's, which cond_ready vouches for
+    if (rc) return rc;
     if (!h->cond_ready) return fail(h, DSD_ESTATE, "dsd_denoise: call dsd_prepare_cond first");
     if (x == out) return fail(h, DSD_EINVAL, "dsd_denoise: out must not alias x");
     if (t_len != 1 && t_len != h->B) return fail(h, DSD_EINVAL, "dsd_denoise: t_len must be 1 or B=%d (got %d)", h->B, t_len);
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, T = h->T, Ts = h->Ts, FM = FM_of(h);
-    int rc = check_path_opts(h);
-    if (rc || (rc = check_lens(h, "dsd_denoise", B, T, st))) return rc;
+    if ((rc = check_path_opts(h)) || (rc = check_lens(h, "dsd_denoise", B, T, st))) return rc;
     const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_emb(h, t_len))) return rc;
     HIP_OK(h, hipMemcpyAsync(h->t_dev, t, sizeof(float) * t_len, hipMemcpyDeviceToDevice, st));
@@ -3033,14 +2994,14 @@ int dsd_denoise(dsd_handle* h, const float* x, const float* t, int32_t t_len, fl
 int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, const float* noise, float* out,
                const float* out_scale, const float* out_shift, uint32_t flags, void* stream) {
     if (!h || !prog || !x_init || !out) return fail(h, DSD_EINVAL, "dsd_sample: null argument");
-    h->opts = read_path_opts();
+    int rc = enter(h, "dsd_sample", K_DENOISER, ENTER_LAUNCH);       // weights: as dsd_denoise
+    if (rc) return rc;
     if (!h->cond_ready) return fail(h, DSD_ESTATE, "dsd_sample: call dsd_prepare_cond first");
     if (prog->n_bufs < 1 || prog->n_bufs > 64 || prog->n_evals < 0 || (prog->n_evals > 0 && !prog->evals))
         return fail(h, DSD_EINVAL, "dsd_sample: malformed program");
     if (prog->result_buf < 0 || prog->result_buf >= prog->n_bufs) return fail(h, DSD_EINVAL, "dsd_sample: bad result_buf");
     if (prog->n_noise > 0 && !noise) return fail(h, DSD_EINVAL, "dsd_sample: program references noise but noise == NULL");
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     const int B = h->B, T = h->T, Ts = h->Ts, FM = FM_of(h);
     // validate the program before anything is launched
     for (int i = 0; i < prog->n_evals; ++i) {
@@ -3059,8 +3020,7 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
             }
         }
     }
-    int rc = check_path_opts(h);
-    if (rc || (rc = check_lens(h, "dsd_sample", B, T, st))) return rc;
+    if ((rc = check_path_opts(h)) || (rc = check_lens(h, "dsd_sample", B, T, st))) return rc;
     const DenoisePlan pl = plan_denoise(h);
     if ((rc = ensure_state(h, prog->n_bufs, st))) return rc;
     if (prog->n_evals > 0 && (rc = ensure_emb(h, prog->n_evals))) return rc;
@@ -3172,8 +3132,7 @@ int dsd_set_precision(dsd_handle* h, int32_t mode) {
     if (!h) return DSD_EINVAL;
     if (mode != DSD_PRECISION_F32 && mode != DSD_PRECISION_BF16X3)
         return fail(h, DSD_EINVAL, "dsd_set_precision: unknown mode %d", mode);
-    if (!is_wavenet(h) && h->cfg.backbone != DSD_BACKBONE_LYNXNET && !is_voc(h))
-        return fail(h, DSD_ESTATE, "dsd_set_precision: only denoiser and vocoder handles have a split-bf16 path");
+    if (int rc = enter(h, "dsd_set_precision", K_DENOISER | K_VOC)) return rc;      // the kinds with a split-bf16 path
     if (mode == h->precision) return DSD_OK;
     h->precision = mode;
     if (h->finalized) {                   // the bf16x3 weight streams are built with the packed weights
@@ -3186,8 +3145,7 @@ int dsd_set_precision(dsd_handle* h, int32_t mode) {
 
 int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stream) {
     if (!h) return DSD_EINVAL;
-    if (is_enc(h) || is_tok(h) || is_voc(h) || is_mel(h) || is_pe(h) || is_hs(h))
-        return fail(h, DSD_ESTATE, "dsd_set_lengths: only denoiser and aux-decoder handles take ragged batches");
+    if (int rc = enter(h, "dsd_set_lengths", K_DENOISER | K_AUX)) return rc;        // the kinds that take ragged batches
     if (!lengths) {             // back to dense batches
         h->lens_host.clear();
         return DSD_OK;
@@ -3209,7 +3167,7 @@ int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stre
 
 int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
     if (!h || !out) return DSD_EINVAL;
-    if (int rc = reject_analysis_handle(h, "dsd_get_stats")) return rc;
+    if (int rc = enter(const_cast<dsd_handle*>(h), "dsd_get_stats", K_MODEL)) return rc;
     memset(out, 0, sizeof(*out));
     const int64_t C = h->c_user ? h->c_user : C_of(h), M = FM_of(h), L = L_of(h);
     out->weight_bytes = (int64_t)h->blob.cap * 4;
@@ -3257,7 +3215,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
 
 int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
     if (!h) return DSD_EINVAL;
-    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing")) return rc;
+    if (int rc = enter(h, "dsd_kernel_timing", K_MODEL)) return rc;
     h->timing = enable != 0;
     h->tclasses.clear();
     h->timing_evals = 0;
@@ -3270,7 +3228,7 @@ int dsd_kernel_timing(dsd_handle* h, int32_t enable) {
 int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_classes, int32_t* n_classes,
                               double* empty_pair_ms) {
     if (!h || !out || !n_classes || max_classes < 1) return DSD_EINVAL;
-    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing_classes")) return rc;
+    if (int rc = enter(h, "dsd_kernel_timing_classes", K_MODEL)) return rc;
     HIP_OK(h, hipSetDevice(h->cfg.device));
     int n = 0;
     // largest share of the evaluation first
@@ -3319,7 +3277,7 @@ int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_c
 
 int dsd_kernel_timing_read(dsd_handle* h, double* mean_ms, double* empty_pair_ms, int64_t* launches) {
     if (!h || !mean_ms || !empty_pair_ms || !launches) return DSD_EINVAL;
-    if (int rc = reject_analysis_handle(h, "dsd_kernel_timing_read")) return rc;
+    if (int rc = enter(h, "dsd_kernel_timing_read", K_MODEL)) return rc;
     dsd_kernel_time top;
     int32_t n = 0;
     int rc = dsd_kernel_timing_classes(h, &top, 1, &n, empty_pair_ms);      // the class with the largest share of the pass

@@ -1,5 +1,6 @@
 // Private host-side header of libdsdenoise: what api.hip and the analysis families' host sources (mel_api.hip,
-// rmvpe_api.hip, hnsep_api.hip) share - the handle, error reporting, device-memory ownership, weight loading.  No kernels.
+// rmvpe_api.hip, hnsep_api.hip) share - the handle, error reporting, the entry check of every call that takes a handle
+// (enter) and the prologue of every create, device-memory ownership, weight loading.  No kernels.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -143,7 +144,7 @@ struct dsd_handle {
     int c_user = 0;
     // wn_edge.hip: the state buffer whose input projection the previous evaluation's edge kernel already wrote into xh
     const float* edge_xh_src = nullptr;
-    bool finalized = false;
+    bool finalized = false;         // the packed weights are on the device, for every kind that has some (enter() reads it)
     PathOpts opts;                  // path switches: the snapshot of the last entry point that launches kernels (read_path_opts)
 
     // packed weights
@@ -272,11 +273,82 @@ inline bool is_mel(const dsd_handle* h) { return h->cfg.backbone == DSD_MEL_ANAL
 inline bool is_pe(const dsd_handle* h) { return h->cfg.backbone == DSD_PE_RMVPE; }
 inline bool is_hs(const dsd_handle* h) { return h->cfg.backbone == DSD_HNSEP_VR; }
 
+// ------------------------------------------------------------------------------------------
+// Which handle may call what.  Every exported call that takes a handle checks its own arguments for NULL and then calls
+// enter() with the kinds it takes; nothing else decides whether a handle is of the right kind for a call (the is_*
+// predicates above are for code that branches on the kind after entry).  INTEGRATION.md states the same sets as a table.
+// ------------------------------------------------------------------------------------------
+constexpr unsigned kind_bit(int backbone) { return 1u << backbone; }
+constexpr unsigned K_WAVENET = kind_bit(DSD_BACKBONE_WAVENET), K_LYNXNET = kind_bit(DSD_BACKBONE_LYNXNET),
+                   K_AUX = kind_bit(DSD_AUX_CONVNEXT), K_ENC = kind_bit(DSD_ENC_FS2_ACOUSTIC), K_VOC = kind_bit(DSD_VOC_NSF_HIFIGAN),
+                   K_TOK = kind_bit(DSD_ENC_FS2_TOKENS), K_MEL = kind_bit(DSD_MEL_ANALYSIS), K_PE = kind_bit(DSD_PE_RMVPE),
+                   K_HS = kind_bit(DSD_HNSEP_VR);
+constexpr unsigned K_DENOISER = K_WAVENET | K_LYNXNET;
+constexpr unsigned K_MODEL = K_DENOISER | K_AUX | K_ENC | K_VOC | K_TOK;         // all but the analysis kinds (mel, RMVPE, separator)
+constexpr unsigned K_WEIGHTS = K_MODEL | K_PE | K_HS;                            // has a weight blob: a mel handle has none
+
+// what a handle of each kind is, and the calls to use on it instead: the text of a wrong-kind refusal
+struct KindName {
+    const char *what, *use;
+};
+constexpr KindName kKindNames[] = {
+    {"a WaveNet denoiser", "dsd_prepare_cond / dsd_denoise / dsd_sample"},
+    {"a LYNXNet denoiser", "dsd_prepare_cond / dsd_denoise / dsd_sample"},
+    {"an aux decoder", "dsd_aux_decode"},
+    {"an acoustic encoder", "dsd_encode"},
+    {"a vocoder", "dsd_vocode / dsd_vocode_ragged"},
+    {"a token encoder", "dsd_token_encode / dsd_predict_dur"},
+    {"a mel analysis handle", "dsd_mel_analyze"},
+    {"an RMVPE pitch extractor", "dsd_rmvpe_infer / dsd_rmvpe_mel_to_hidden / dsd_rmvpe_decode*"},
+    {"a harmonic-noise separator", "dsd_hnsep_separate / dsd_hnsep_mask / dsd_base_harmonic / dsd_variance_curves"},
+};
+static_assert(sizeof(kKindNames) / sizeof(kKindNames[0]) == DSD_HNSEP_VR + 1, "one name per DSD_* kind");
+
+// path switches: every C-ABI entry point that launches kernels takes a snapshot into its handle (dsd_internal.h, PathOpts)
+PathOpts read_path_opts();
+
+enum : unsigned {
+    ENTER_WEIGHTS = 1,      // the call reads the packed weights: dsd_finalize_weights must have succeeded
+    ENTER_LAUNCH = 2,       // the call launches kernels: snapshot the path switches, make the handle's device current
+};
+// The one entry check (h != nullptr): DSD_ESTATE for a handle whose kind is not in `takes`, then for missing weights.
+inline int enter(dsd_handle* h, const char* who, unsigned takes, unsigned flags = 0) {
+    if (!(takes & kind_bit(h->cfg.backbone))) {
+        const KindName& k = kKindNames[h->cfg.backbone];
+        return fail(h, DSD_ESTATE, "%s: this handle is %s (use %s)", who, k.what, k.use);
+    }
+    if ((flags & ENTER_WEIGHTS) && !h->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
+    if (flags & ENTER_LAUNCH) {
+        h->opts = read_path_opts();
+        HIP_OK(h, hipSetDevice(h->cfg.device));
+    }
+    return DSD_OK;
+}
+
 // a state dict layout: the names a handle accepts, with their shapes
 using ParamList = std::vector<std::pair<std::string, std::vector<int64_t>>>;
 
 // every create function and dsd_cond_assemble: the device must exist before anything is placed on it
 int select_device(const char* who, int device, bool say_range = true);
+// What the seven create functions share, in this order: the arguments, struct_size, the family's own rules (`validate(cfg)`
+// returns DSD_OK or the code of its fail()), the device ...
+template <typename Cfg, typename Validate>
+int create_check(const Cfg* cfg, dsd_handle** out, const char* who, Validate&& validate) {
+    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "%s: null argument", who);
+    if (cfg->struct_size != (int32_t)sizeof(Cfg))
+        return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, cfg->struct_size, sizeof(Cfg));
+    if (int rc = validate(cfg)) return rc;
+    return select_device(who, cfg->device);
+}
+// ... and the handle, its cfg zero but for the fields every kind has
+inline dsd_handle* new_handle(int backbone, int device) {
+    dsd_handle* h = new dsd_handle();
+    memset(&h->cfg, 0, sizeof(h->cfg));
+    h->cfg.struct_size = sizeof(dsd_config);
+    h->cfg.backbone = backbone;
+    h->cfg.device = device;
+    return h;
+}
 // dsd_load_weight behind the caller's own name rules: looks `name` up in `expected` (nullptr: the caller has checked the
 // shape itself), compares the shape and copies the host or device data into h->raw
 int store_weight(dsd_handle* h, const ParamList* expected, const char* name, const float* data, const int64_t* shape,

@@ -24,7 +24,6 @@ struct HsBasis {
 struct HnsepState {
     dsd_hnsep_config cfg;
     std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
-    bool finalized = false;
     DevBuf<float> blob;
     HsNetW net[5];                          // stg1 low, stg1 high, stg2 low, stg2 high, stg3 full
     HsConvW tail1, tail2, out;              // stg1_low_band_net.1, stg2_low_band_net.1, out
@@ -111,7 +110,7 @@ int dsd::hnsep_load_weight(dsd_handle* h, const char* name, const float* data, c
     if (!data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
     HnsepState& r = *h->hs;
     const int rc = store_weight(h, &r.expected, name, data, shape, ndim, on_device);
-    if (rc == DSD_OK) r.finalized = false;
+    if (rc == DSD_OK) h->finalized = false;
     return rc;
 }
 
@@ -244,7 +243,7 @@ int dsd::hnsep_finalize(dsd_handle* h) {
     r.out = hs_pack(blob, [&](int co, int ci, int, int) { return (double)ow[(size_t)co * n + ci]; }, 2 * C, {n}, 1, one, zero);
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if ((rc = upload_blob(h, r.blob, blob, 0))) return rc;
-    r.finalized = true;
+    h->finalized = true;
     return DSD_OK;
 }
 
@@ -285,13 +284,6 @@ const HsBasis* hs_basis(dsd_handle* h, int N, int kind, hipStream_t st) {
         return nullptr;
     r.bases.push_back(std::move(b));
     return &r.bases.back();
-}
-
-int hs_check(dsd_handle* h, const char* who, bool weights) {
-    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
-    if (!is_hs(h)) return fail(h, DSD_ESTATE, "%s: this handle is not a harmonic-noise separator (dsd_hnsep_create)", who);
-    if (weights && !h->hs->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
-    return DSD_OK;
 }
 
 // per-call host block of ints and longs uploaded once: `add()` appends an array at an 8-byte aligned offset and returns
@@ -723,22 +715,18 @@ int hs_istft_ola(const HsDft& d, const char* blk, const HsT& spec, const HsT* ma
 extern "C" {
 
 int dsd_hnsep_create(const dsd_hnsep_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_hnsep_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_hnsep_config));
-    if (cfg->n_fft < 128 || cfg->n_fft > 4096 || cfg->n_fft % 64 != 0 || cfg->hop_length < 1 || cfg->hop_length > cfg->n_fft / 2 ||
-        cfg->nout < 4 || cfg->nout > 64 || cfg->nout % 4 != 0 || cfg->nout_lstm < 8 || cfg->nout_lstm > 128 ||
-        cfg->nout_lstm % 8 != 0 || (cfg->is_mono != 0 && cfg->is_mono != 1))
-        return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: need n_fft a multiple of 64 in [128, 4096], 1 <= hop_length <= "
-                    "n_fft / 2, nout a multiple of 4 in [4, 64], nout_lstm a multiple of 8 in [8, 128], is_mono 0 or 1");
-    if (int rc = select_device("dsd_hnsep_create", cfg->device)) return rc;
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_HNSEP_VR;
+    const int rc = create_check(cfg, out, "dsd_hnsep_create", [](const dsd_hnsep_config* c) {
+        if (c->n_fft < 128 || c->n_fft > 4096 || c->n_fft % 64 != 0 || c->hop_length < 1 || c->hop_length > c->n_fft / 2 ||
+            c->nout < 4 || c->nout > 64 || c->nout % 4 != 0 || c->nout_lstm < 8 || c->nout_lstm > 128 || c->nout_lstm % 8 != 0 ||
+            (c->is_mono != 0 && c->is_mono != 1))
+            return fail(nullptr, DSD_EINVAL, "dsd_hnsep_create: need n_fft a multiple of 64 in [128, 4096], 1 <= hop_length <= "
+                        "n_fft / 2, nout a multiple of 4 in [4, 64], nout_lstm a multiple of 8 in [8, 128], is_mono 0 or 1");
+        return DSD_OK;
+    });
+    if (rc) return rc;
+    dsd_handle* h = new_handle(DSD_HNSEP_VR, cfg->device);
     h->cfg.in_dims = cfg->n_fft / 2 + 1;
     h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
     h->hs = new HnsepState();
     h->hs->cfg = *cfg;
     h->hs->expected = hnsep_expected(*cfg);
@@ -756,7 +744,8 @@ int dsd_hnsep_mask(dsd_handle* h, const float* spec, int32_t B, int32_t T, int64
                    int64_t s_stride_f, int64_t s_stride_t, const int64_t* lengths, float* mask_out, int64_t m_stride_b,
                    int64_t m_stride_c, int64_t m_stride_f, int64_t m_stride_t, void* stream) {
     const char* who = "dsd_hnsep_mask";
-    HS_RC(hs_check(h, who, true));
+    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
+    HS_RC(enter(h, who, K_HS, ENTER_WEIGHTS | ENTER_LAUNCH));
     if (!spec || !mask_out || B < 1 || T < 16) return fail(h, DSD_EINVAL, "%s: bad argument", who);
     std::vector<int> Tp(B);
     for (int b = 0; b < B; ++b) {
@@ -765,7 +754,6 @@ int dsd_hnsep_mask(dsd_handle* h, const float* spec, int32_t B, int32_t T, int64
             return fail(h, DSD_EINVAL, "%s: frame count %lld of item %d is not a multiple of 16 in [16, T]", who, (long long)v, b);
         Tp[b] = (int)v;
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     HnsepState& S = *h->hs;
     const int C = S.cfg.is_mono ? 1 : 2;
     hipStream_t st = (hipStream_t)stream;
@@ -784,7 +772,8 @@ int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_sam
                        int64_t wav_stride_c, const int64_t* lengths, float* harmonic_out, int64_t out_stride_b,
                        int64_t out_stride_c, void* stream) {
     const char* who = "dsd_hnsep_separate";
-    HS_RC(hs_check(h, who, true));
+    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
+    HS_RC(enter(h, who, K_HS, ENTER_WEIGHTS | ENTER_LAUNCH));
     if (!wav || !harmonic_out || B < 1 || n_samples < 1 || wav_stride_c < 0 || out_stride_c < 0)
         return fail(h, DSD_EINVAL, "%s: bad argument", who);
     HnsepState& S = *h->hs;
@@ -802,7 +791,6 @@ int dsd_hnsep_separate(dsd_handle* h, const float* wav, int32_t B, int64_t n_sam
         off0[b] = N / 2 + Tl_pad;       // padded position of sample 0 in the iSTFT's frame space
         Lmax = std::max(Lmax, L[b]);
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const HsBasis* bs = hs_basis(h, N, 0, st);
     if (!bs) return fail(h, DSD_ENOMEM, "%s: the DFT bases could not be placed on the device", who);
@@ -835,7 +823,8 @@ int dsd_base_harmonic(dsd_handle* h, const float* harmonic, int32_t B, int64_t n
                       int32_t sample_rate, int32_t hop_size, int32_t win_size, float* out, int64_t out_stride_b,
                       void* stream) {
     const char* who = "dsd_base_harmonic";
-    HS_RC(hs_check(h, who, false));
+    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
+    HS_RC(enter(h, who, K_HS, ENTER_LAUNCH));       // no weights are used
     if (!harmonic || !f0 || !f0_lengths || !out || B < 1 || n_samples < 1 || sample_rate < 1 || win_size < 64 ||
         win_size > 4096 || win_size % 32 != 0 || hop_size < 1 || hop_size > win_size / 2)
         return fail(h, DSD_EINVAL, "%s: bad argument (win_size must be a multiple of 32 in [64, 4096], 1 <= hop_size <= "
@@ -856,7 +845,6 @@ int dsd_base_harmonic(dsd_handle* h, const float* harmonic, int32_t B, int64_t n
         Lmax = std::max(Lmax, L[b]);
         Tal = std::max(Tal, Tp[b]);
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     const HsBasis* bs = hs_basis(h, N, 1, st);
     if (!bs) return fail(h, DSD_ENOMEM, "%s: the DFT bases could not be placed on the device", who);
@@ -884,7 +872,8 @@ int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, 
                         int32_t tension_domain, int32_t energy_db, float* energy, float* breathiness, float* voicing,
                         float* tension, int64_t out_stride_b, void* stream) {
     const char* who = "dsd_variance_curves";
-    HS_RC(hs_check(h, who, false));
+    if (!h) return fail(nullptr, DSD_EINVAL, "%s: null handle", who);
+    HS_RC(enter(h, who, K_HS, ENTER_LAUNCH));       // no weights are used
     if (B < 1 || !lengths || !frames || hop_size < 1 || win_size < 1 || tension_domain < 0 || tension_domain > 2)
         return fail(h, DSD_EINVAL, "%s: bad argument", who);
     if ((energy && !wav) || (breathiness && (!wav || !harmonic)) || (voicing && !harmonic) || (tension && (!harmonic || !base)))
@@ -902,7 +891,6 @@ int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, 
         len[b] = (int)frames[b];
         Tmax = std::max(Tmax, nfr[b]);
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
     S.iw_host.clear();
     HsUpload up{S.iw_host};

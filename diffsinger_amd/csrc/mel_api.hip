@@ -160,17 +160,11 @@ int64_t dsd_mel_num_frames(const dsd_mel_config* cfg, int64_t n_samples, double 
 }
 
 int dsd_mel_create(const dsd_mel_config* cfg, dsd_handle** out) {
-    if (!out) return fail(nullptr, DSD_EINVAL, "dsd_mel_create: null argument");
-    int rc = mel_check_config(cfg, "dsd_mel_create");
+    int rc = create_check(cfg, out, "dsd_mel_create", [](const dsd_mel_config* c) { return mel_check_config(c, "dsd_mel_create"); });
     if (rc) return rc;
-    if (int rc = select_device("dsd_mel_create", cfg->device)) return rc;
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_MEL_ANALYSIS;
+    dsd_handle* h = new_handle(DSD_MEL_ANALYSIS, cfg->device);
     h->cfg.in_dims = cfg->num_mels;
     h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
     std::vector<float> w;
     mel_filterbank_host(*cfg, w);
     h->mel = new MelState();
@@ -187,7 +181,7 @@ int dsd_mel_create(const dsd_mel_config* cfg, dsd_handle** out) {
 
 namespace dsd {
 
-// the analysis of dsd_mel_analyze after its argument checks, for one STFT geometry (RMVPE's front end calls it too)
+// the analysis of dsd_mel_analyze after its entry and argument checks, for one STFT geometry (RMVPE's front end calls it too)
 int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int32_t B, int64_t n_samples, int64_t wav_stride_b,
             const int64_t* lengths, float* mel_out, int64_t stride_b, int64_t stride_m, int64_t stride_t, void* stream,
             const char* who) {
@@ -216,7 +210,6 @@ int mel_run(dsd_handle* h, MelState& ms, const MelGeom& g, const float* wav, int
     const int k_hi = std::min(ms.k_hi, g.N / 2), nb = std::max(0, k_hi - ms.k_lo + 1);
     const int row_tiles = (2 * nb + kDftRows - 1) / kDftRows, Kpad = (g.W + kDftTaps - 1) / kDftTaps * kDftTaps;
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     float* basis = nullptr;
     if (nb > 0) {
         for (size_t i = 0; i < ms.bases.size(); ++i)
@@ -286,7 +279,7 @@ extern "C" int dsd_mel_analyze(dsd_handle* h, const float* wav, int32_t B, int64
                     const int64_t* lengths, double keyshift, double speed, float* mel_out, int64_t stride_b,
                     int64_t stride_m, int64_t stride_t, void* stream) {
     if (!h || !wav || !mel_out) return fail(h, DSD_EINVAL, "dsd_mel_analyze: null argument");
-    if (!is_mel(h)) return fail(h, DSD_ESTATE, "dsd_mel_analyze: this handle is not a mel analysis handle (dsd_mel_create)");
+    if (int rc = enter(h, "dsd_mel_analyze", K_MEL, ENTER_LAUNCH)) return rc;
     MelState& ms = *h->mel;
     const dsd_mel_config& c = ms.cfg;
     if (B < 1 || n_samples < 1) return fail(h, DSD_EINVAL, "dsd_mel_analyze: B and n_samples must be positive (%d, %lld)", B,

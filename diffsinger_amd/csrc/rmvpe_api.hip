@@ -17,7 +17,6 @@ struct RmBlockW {
 struct RmvpeState {
     dsd_rmvpe_config cfg;
     std::vector<std::pair<std::string, std::vector<int64_t>>> expected;
-    bool finalized = false;
     DevBuf<float> blob;
     float bn0_scale = 1.f, bn0_shift = 0.f;                  // unet.encoder.bn (1 channel)
     std::vector<std::vector<RmBlockW>> enc, inter, dec;     // [layer][block]
@@ -143,7 +142,7 @@ int dsd::rmvpe_load_weight(dsd_handle* h, const char* name, const float* data, c
     if (!data || !shape || ndim < 1 || ndim > 4) return fail(h, DSD_EINVAL, "dsd_load_weight: bad argument");
     RmvpeState& r = *h->pe;
     const int rc = store_weight(h, &r.expected, name, data, shape, ndim, on_device);
-    if (rc == DSD_OK) r.finalized = false;
+    if (rc == DSD_OK) h->finalized = false;
     return rc;
 }
 
@@ -280,7 +279,7 @@ int dsd::rmvpe_finalize(dsd_handle* h) {
     }
     HIP_OK(h, hipSetDevice(h->cfg.device));
     if ((rc = upload_blob(h, r.blob, blob, 0))) return rc;
-    r.finalized = true;
+    h->finalized = true;
     return DSD_OK;
 }
 
@@ -290,12 +289,6 @@ void dsd::rmvpe_free(RmvpeState* r) {
 }
 
 namespace {
-
-int rmvpe_check(dsd_handle* h, const char* who) {
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
-    if (!h->pe->finalized) return fail(h, DSD_ESTATE, "%s: weights are not finalized", who);
-    return DSD_OK;
-}
 
 #define RM_LAUNCH(expr, what)                                                                            \
     do {                                                                                                 \
@@ -568,7 +561,6 @@ const RmvpeState::Resampler* rmvpe_resampler(dsd_handle* h, int sr) {
 int rmvpe_decode_frames(dsd_handle* h, const char* who, const float* hidden, const int* centers, int B, int T, int64_t h_stride_b,
                         int64_t h_stride_t, int64_t c_stride_b, float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
     RmvpeState& r = *h->pe;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     std::vector<int>& iw = r.iw_host;
     iw.assign(B, T);
     int rc = r.iws.reserve(h, iw.size(), who);
@@ -625,21 +617,17 @@ int rmvpe_viterbi_table(dsd_handle* h, const char* who) {
 extern "C" {
 
 int dsd_rmvpe_create(const dsd_rmvpe_config* cfg, dsd_handle** out) {
-    if (!cfg || !out) return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: null argument");
-    if (cfg->struct_size != (int32_t)sizeof(dsd_rmvpe_config))
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: struct_size %d != %zu", cfg->struct_size, sizeof(dsd_rmvpe_config));
-    if (cfg->n_blocks < 1 || (cfg->n_gru != 0 && cfg->n_gru != 1) || cfg->en_de_layers < 1 || cfg->en_de_layers > 5 ||
-        cfg->inter_layers < 1 || cfg->en_out_channels < 8 || cfg->en_out_channels % 8 != 0 || cfg->en_out_channels > 64)
-        return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: need n_blocks >= 1, n_gru in {0, 1}, 1 <= en_de_layers <= 5, "
-                    "inter_layers >= 1 and en_out_channels a multiple of 8 in [8, 64]");
-    if (int rc = select_device("dsd_rmvpe_create", cfg->device)) return rc;
-    dsd_handle* h = new dsd_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    h->cfg.struct_size = sizeof(dsd_config);
-    h->cfg.backbone = DSD_PE_RMVPE;
+    int rc = create_check(cfg, out, "dsd_rmvpe_create", [](const dsd_rmvpe_config* c) {
+        if (c->n_blocks < 1 || (c->n_gru != 0 && c->n_gru != 1) || c->en_de_layers < 1 || c->en_de_layers > 5 ||
+            c->inter_layers < 1 || c->en_out_channels < 8 || c->en_out_channels % 8 != 0 || c->en_out_channels > 64)
+            return fail(nullptr, DSD_EINVAL, "dsd_rmvpe_create: need n_blocks >= 1, n_gru in {0, 1}, 1 <= en_de_layers <= 5, "
+                        "inter_layers >= 1 and en_out_channels a multiple of 8 in [8, 64]");
+        return DSD_OK;
+    });
+    if (rc) return rc;
+    dsd_handle* h = new_handle(DSD_PE_RMVPE, cfg->device);
     h->cfg.in_dims = RM_MELS;
     h->cfg.n_feats = 1;
-    h->cfg.device = cfg->device;
     h->pe = new RmvpeState();
     h->pe->cfg = *cfg;
     h->pe->expected = rmvpe_expected(*cfg);
@@ -647,7 +635,7 @@ int dsd_rmvpe_create(const dsd_rmvpe_config* cfg, dsd_handle** out) {
     std::vector<float> w;
     mel_filterbank_host(mc, w, true);
     h->pe->mel = new MelState();
-    int rc = mel_state_build(*h->pe->mel, &mc, w, "dsd_rmvpe_create");
+    rc = mel_state_build(*h->pe->mel, &mc, w, "dsd_rmvpe_create");
     if (rc) {
         dsd_destroy(h);
         return rc;
@@ -678,7 +666,7 @@ int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t 
                          int64_t stride_t, const int64_t* lengths, float* hidden_out, int64_t h_stride_b,
                          int64_t h_stride_t, void* stream) {
     if (!h || !mel || !hidden_out) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: null argument");
-    int rc = rmvpe_check(h, "dsd_rmvpe_mel_to_hidden");
+    int rc = enter(h, "dsd_rmvpe_mel_to_hidden", K_PE, ENTER_WEIGHTS | ENTER_LAUNCH);
     if (rc) return rc;
     if (B < 1 || T < 1 || T > (1 << 24)) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: need B >= 1 and 1 <= T <= 2^24");
     std::vector<int> Tb(B);
@@ -687,7 +675,6 @@ int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t 
         if (v < 1 || v > T) return fail(h, DSD_EINVAL, "dsd_rmvpe_mel_to_hidden: lengths[%d] = %lld outside [1, %d]", b, (long long)v, T);
         Tb[b] = (int)v;
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     return rmvpe_run(h, mel, stride_b, stride_m, stride_t, B, Tb, 0.f, nullptr, 0, hidden_out, h_stride_b, h_stride_t,
                      (hipStream_t)stream, "dsd_rmvpe_mel_to_hidden");
 }
@@ -695,7 +682,7 @@ int dsd_rmvpe_mel_to_hidden(dsd_handle* h, const float* mel, int32_t B, int32_t 
 int dsd_rmvpe_decode(dsd_handle* h, const float* hidden, int32_t B, int32_t T, int64_t h_stride_b, int64_t h_stride_t,
                      float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
     if (!h || !hidden || !f0_out) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: null argument");
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "dsd_rmvpe_decode: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)");
+    if (int rc = enter(h, "dsd_rmvpe_decode", K_PE, ENTER_LAUNCH)) return rc;       // no weights: the hidden is the caller's
     if (B < 1 || T < 1 || T > (1 << 24)) return fail(h, DSD_EINVAL, "dsd_rmvpe_decode: need B >= 1 and 1 <= T <= 2^24");
     return rmvpe_decode_frames(h, "dsd_rmvpe_decode", hidden, nullptr, B, T, h_stride_b, h_stride_t, 0, thred, f0_out, f0_stride_b,
                                stream);
@@ -705,7 +692,7 @@ int dsd_rmvpe_decode_at(dsd_handle* h, const float* hidden, const int32_t* cente
                         int64_t h_stride_t, int64_t c_stride_b, float thred, float* f0_out, int64_t f0_stride_b, void* stream) {
     const char* who = "dsd_rmvpe_decode_at";
     if (!h || !hidden || !centers || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
+    if (int rc = enter(h, who, K_PE, ENTER_LAUNCH)) return rc;
     if (B < 1 || T < 1 || T > RM_VT_MAX_T) return fail(h, DSD_EINVAL, "%s: need B >= 1 and 1 <= T <= %d frames", who, RM_VT_MAX_T);
     return rmvpe_decode_frames(h, who, hidden, centers, B, T, h_stride_b, h_stride_t, c_stride_b, thred, f0_out, f0_stride_b, stream);
 }
@@ -715,7 +702,8 @@ int dsd_rmvpe_decode_viterbi(dsd_handle* h, const float* hidden, int32_t B, int3
                              int64_t path_stride_b, void* stream) {
     const char* who = "dsd_rmvpe_decode_viterbi";
     if (!h || !hidden || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    if (!is_pe(h)) return fail(h, DSD_ESTATE, "%s: this handle is not an RMVPE pitch extractor (dsd_rmvpe_create)", who);
+    int rc = enter(h, who, K_PE, ENTER_LAUNCH);
+    if (rc) return rc;
     if (B < 1 || T < 1 || T > RM_VT_MAX_T || (int64_t)B * T > RM_VT_MAX_FRAMES)
         return fail(h, DSD_EINVAL, "%s: need B >= 1, 1 <= T <= %d frames and B * T <= %lld frames (the back-pointer and log_prob "
                     "workspaces take 3600 bytes per frame)", who, RM_VT_MAX_T, (long long)RM_VT_MAX_FRAMES);
@@ -727,9 +715,7 @@ int dsd_rmvpe_decode_viterbi(dsd_handle* h, const float* hidden, int32_t B, int3
         if (v < 1 || v > T) return fail(h, DSD_EINVAL, "%s: lengths[%d] = %lld outside [1, %d]", who, b, (long long)v, T);
         iw[b] = (int)v;
     }
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     const size_t frames = (size_t)B * T;
-    int rc;
     if ((rc = rmvpe_viterbi_table(h, who)) || (rc = r.vt_lp.reserve(h, frames * RM_CLASSES, who)) ||
         (rc = r.vt_ptr.reserve(h, frames * RM_CLASSES, who)) || (rc = r.vt_iw.reserve(h, B + frames, who)))
         return rc;
@@ -775,7 +761,7 @@ int dsd_rmvpe_infer(dsd_handle* h, const float* wav, int32_t B, int64_t n_sample
                     float* hidden_out, int64_t h_stride_b, int64_t h_stride_t, void* stream) {
     const char* who = "dsd_rmvpe_infer";
     if (!h || !wav || !f0_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
-    int rc = rmvpe_check(h, who);
+    int rc = enter(h, who, K_PE, ENTER_WEIGHTS | ENTER_LAUNCH);
     if (rc) return rc;
     RmvpeState& r = *h->pe;
     if (B < 1 || n_samples < 1 || sample_rate < 1) return fail(h, DSD_EINVAL, "%s: B, n_samples and sample_rate must be positive", who);
@@ -799,7 +785,6 @@ int dsd_rmvpe_infer(dsd_handle* h, const float* wav, int32_t B, int64_t n_sample
         Tmax = std::max(Tmax, T[b]);
     }
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK(h, hipSetDevice(h->cfg.device));
     // the front end's log-mel and resampled audio live in a block of their own: rmvpe_run reuses the workspace
     const float* w16 = wav;
     int64_t w16_sb = wav_stride_b;

@@ -10,6 +10,9 @@
  *
  * Return value: 0 on success, a negative DSD_E* code on failure; nothing is thrown across the
  * ABI.  `dsd_last_error` returns a human-readable message for the last failure on a handle.
+ * One `dsd_handle` type stands behind nine kinds of model (the DSD_* enum below); a call on a
+ * kind it does not take returns DSD_ESTATE with "<call>: this handle is <what> (use <calls>)",
+ * a NULL handle DSD_EINVAL.  INTEGRATION.md has the table of calls and kinds.
  *
  * Threading: like the reference modules (module-level `noise_list`/`bar`,
  * modules/core/ddpm.py:78,276,324) a handle is NOT re-entrant: calls on one handle are
@@ -420,7 +423,9 @@ int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int
  * convolution of LYNXNet and the ConvNeXt aux decoder - so item b of a padded batch comes out as if it had been run alone
  * at T = lengths[b] (outputs at its padded frames are unspecified), and several segments of a project can share one
  * launch.  lengths: HOST array of B values (copied, stream-ordered); applies to the following dsd_prepare_cond / dsd_denoise
- * / dsd_sample / dsd_aux_decode calls at batch size B until changed; NULL restores dense batches.
+ * / dsd_sample / dsd_aux_decode calls at batch size B until changed; NULL restores dense batches.  WaveNet, LYNXNet and
+ * aux-decoder handles take the call; every other kind answers DSD_ESTATE (a vocoder takes dsd_vocode_ragged, the analysis
+ * calls take their lengths as an argument).
  */
 int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stream);
 
@@ -636,7 +641,7 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
  * expansion 2, and - on a vocoder handle (dsd_vocoder_create) - for the residual-block convolutions of every stage with 64 to 256
  * channels, a multiple of 32 (voc_x3.hip: 7e-6 .. 2.4e-5 off the fp32 oracle on the waveform, tools/bf16x3_vocoder_tolerance.py;
  * asserted at the fp32 tolerance in tests/test_gpu_vocoder_x3.py); conv_pre, the transposed convolutions, the 32- / 16-channel
- * stages, conv_post and the source stay fp32, as do other shapes and kernels whatever the mode.  Denoiser, LYNXNet and vocoder
+ * stages, conv_post and the source stay fp32, as do other shapes and kernels whatever the mode.  WaveNet, LYNXNet and vocoder
  * handles take the call; every other kind of handle answers DSD_ESTATE, an unknown mode DSD_EINVAL.  Also set for every DENOISER
  * handle of the process by the environment variable DSD_PRECISION=1 at dsd_create (a vocoder handle takes the explicit call
  * only).  May be called at any time; after dsd_finalize_weights it re-packs the weights - the fp32 packing is the same in either
@@ -647,7 +652,8 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
 #define DSD_PRECISION_BF16X3 1
 int dsd_set_precision(dsd_handle* h, int32_t mode);
 
-/* Introspection used by tests, bench.py and the roofline report. */
+/* Introspection used by tests, bench.py and the roofline report.  dsd_get_stats and the dsd_kernel_timing* calls below take
+   every kind of handle but the analysis ones (mel, RMVPE, separator: DSD_ESTATE). */
 typedef struct dsd_stats {
     int64_t weight_bytes;        /* packed weights on the device                        */
     int64_t workspace_bytes;     /* current arena size                                  */

@@ -60,6 +60,23 @@ def test_bad_config_rejected():
     assert b"multiple of 32" in _lib.lib().dsd_last_error(None)
 
 
+def test_null_handle_is_einval():
+    """Every export that takes a handle answers DSD_EINVAL to a NULL one, every other argument being in order (the rows
+    and their argument tuples are those of test_gpu_handle_kinds, on host memory: nothing is dereferenced)."""
+    from types import SimpleNamespace
+    from diffsinger_amd import _lib
+    from test_gpu_handle_kinds import calls
+    lib = _lib.lib()
+    host = (C.c_float * 64)()
+    ptr = C.cast(host, C.c_void_p)
+    table = calls(SimpleNamespace(f=ptr, g=ptr, i64=ptr, i32=ptr, u8=ptr, host_f=ptr))
+    assert len(table) == 27
+    for name, (args, _, _) in table.items():
+        assert getattr(lib, name)(None, *args) == -1, name
+    lib.dsd_destroy(None)
+    assert lib.dsd_last_error(None) is not None
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "diffsinger_amd")
     for fn in os.listdir(pkg):

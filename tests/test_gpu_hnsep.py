@@ -247,14 +247,14 @@ def test_error_paths():
         assert b"missing keys" in lib.dsd_last_error(hp)
         # wrong handle kind: a separator handle on another family's entry point, and the reverse
         assert lib.dsd_set_lengths(hp, None, 1, None) != 0
-        assert b"only denoiser and aux-decoder handles" in lib.dsd_last_error(hp)
+        assert b"dsd_set_lengths: this handle is a harmonic-noise separator" in lib.dsd_last_error(hp)
         mc = _lib.DsdMelConfig(C.sizeof(_lib.DsdMelConfig), 44100, 2048, 2048, 512, 128, 40.0, 16000.0, 1e-5, 0)
         mh = C.c_void_p()
         assert lib.dsd_mel_create(C.byref(mc), C.byref(mh)) == 0
         try:
             rc = lib.dsd_variance_curves(mh, C.c_void_p(x.data_ptr()), None, None, 1, 1000, (C.c_int64 * 1)(1000), 128, 512,
                                          (C.c_int64 * 1)(8), 2, 1, C.c_void_p(x.data_ptr()), None, None, None, 8, None)
-            assert rc != 0 and b"not a harmonic-noise separator" in lib.dsd_last_error(mh)
+            assert rc != 0 and b"dsd_variance_curves: this handle is a mel analysis handle" in lib.dsd_last_error(mh)
         finally:
             lib.dsd_destroy(mh)
         # a requested curve without its input signal
