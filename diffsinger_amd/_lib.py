@@ -20,6 +20,7 @@ DSD_SAMPLE_TRANSPOSE = 2
 DSD_SAMPLE_GRAPH_LAZY = 4
 BACKBONE_IDS = {"wavenet": 0, "lynxnet": 1}
 AUX_CONVNEXT = 2
+DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
 ACT_IDS = {"PReLU": 0, "SiLU": 1, "ReLU": 2}
 
 EXPORTS = [
@@ -33,6 +34,7 @@ EXPORTS = [
     "dsd_hnsep_create", "dsd_hnsep_num_frames", "dsd_hnsep_mask", "dsd_hnsep_separate", "dsd_base_harmonic",
     "dsd_variance_curves",
     "dsd_length_regulate", "dsd_frame_curve",
+    "dsd_noise_fill",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -103,6 +105,12 @@ class DsdEncodeExtras(C.Structure):
                 ("spk_mix_bstride", C.c_int64), ("spk_mix_tstride", C.c_int64), ("key_shift", C.c_void_p),
                 ("speed", C.c_void_p), ("energy", C.c_void_p), ("breathiness", C.c_void_p), ("voicing", C.c_void_p),
                 ("tension", C.c_void_p)]
+
+
+class DsdNoiseSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("domain", C.c_uint32), ("first_stream", C.c_int32),
+                ("n", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("seeds", C.POINTER(C.c_uint64)), ("scale", C.c_float), ("src", C.c_void_p), ("src_scale", C.c_float)]
 
 
 class DsdTerm(C.Structure):
@@ -200,6 +208,7 @@ def _load():
                                         vp, i64, vp]
     lib.dsd_length_regulate.argtypes = [i32, vp, i32, i32, i32, vp, vp]
     lib.dsd_frame_curve.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_float), i32, vp, vp, vp, vp]
+    lib.dsd_noise_fill.argtypes = [i32, C.POINTER(DsdNoiseSpec), vp, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

@@ -1,6 +1,6 @@
 // Device primitives shared by the hand-written kernel files of libdsdenoise (gfx950, device code only; included after
 // dsd_internal.h): vector types, buffer-descriptor loads and the 16-byte store with its two cache policies, index helpers,
-// the compensated DFT tile walk, the activations named for their arithmetic, the split-bf16 products and the diagnostic stamps.
+// the compensated DFT tile walk, the activations named for their arithmetic, the split-bf16 products, the counter-based random draws and the diagnostic stamps.
 #pragma once
 #include <type_traits>
 
@@ -200,6 +200,32 @@ __device__ __forceinline__ float tanh_fast(float v) { return 1.f - 2.f * __built
 // LYNXNet's SwiGLU in lynx_layer.hip / lynx_x3.hip: expf as the library computes it; the reciprocal as v_rcp_f32 (<= 1 ulp)
 // instead of an IEEE division sequence (~10 VALU instructions per element, 64 elements per lane and row tile in the epilogue)
 __device__ __forceinline__ float sigmoid_rcp(float v) { return __builtin_amdgcn_rcpf(1.f + expf(-v)); }
+
+// ---------------------------------------------------------------------------------------------
+// Counter-based random draws (noise_kernels.hip; the specification is in include/dsdenoise.h above dsd_noise_fill).
+// Philox4x32-10 (Salmon et al., Random123): ten rounds of two 32 x 32 -> 64-bit products, the key bumped between rounds.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ dsd_u32x4 philox4x32_10(dsd_u32x4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+        c = dsd_u32x4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+// ((w >> 9) + 0.5) * 2^-23: every step exact in fp32 (k + 0.5 with k < 2^23 needs 24 bits), strictly inside (0, 1)
+__device__ __forceinline__ float philox_uniform(unsigned w) { return ((float)(w >> 9) + 0.5f) * 0x1p-23f; }
+// Box-Muller on one word pair with the precise logf / sqrtf / sincosf: |z| <= sqrt(-2 ln 2^-24) = 5.7681
+__device__ __forceinline__ void philox_normal2(unsigned w0, unsigned w1, float& z0, float& z1) {
+    const float r = sqrtf(-2.f * logf(philox_uniform(w0)));
+    float s, c;
+    sincosf(6.283185307179586f * philox_uniform(w1), &s, &c);
+    z0 = r * c;
+    z1 = r * s;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Diagnostic builds only (-DDSD_STAMPS; tools/stamp_*.py): thread 0 of workgroups < 4096 writes a clock into `elem` of its

@@ -459,6 +459,19 @@ struct FrameCurveP {
 hipError_t launch_length_regulate(const long long* dur, int B, int L, int T, long long* mel2x, hipStream_t st);
 hipError_t launch_frame_curve(const FrameCurveP& p, int items, hipStream_t st);
 
+// noise_kernels.hip: seeded draws (dsd_noise_fill).  A NoiseP launch covers up to kNoiseItems batch items starting at item
+// b0; their seeds travel in the kernel arguments, so the entry owns no device memory and never synchronises.
+constexpr int kNoiseItems = 64;
+struct NoiseP {
+    float* out;                     // [n][B][rows][cols]
+    const float* src;               // the same layout, or nullptr
+    float scale, src_scale;         // out = src_scale * src + scale * eps
+    unsigned domain, first_stream;
+    int n, B, rows, cols, b0, kind; // kind: 0 normal, 1 uniform
+    unsigned long long seed[kNoiseItems];
+};
+hipError_t launch_noise_fill(const NoiseP& p, int items, hipStream_t st);
+
 // The DFT tile of mel_dft_kernel and hs_dft_kernel (dsd_device.h, dft_tile_walk), as far as the host sizes bases and work
 // lists by it
 constexpr int kDftFrames = 64;      // frames per tile (one work-list entry)

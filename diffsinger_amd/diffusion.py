@@ -9,7 +9,9 @@ every NFE plus the fused solver update, by default replayed from a cached hipGra
 
 Inference only: `infer=False` (p_losses, ddpm.py:360-367) raises - training stays on the reference.
 Randomness: x_T (and the per-step noise of ancestral DDPM) is drawn with `torch.randn` exactly where the
-reference draws it, or injected through the keyword-only `noise=` / `step_noise=` arguments (tests).
+reference draws it, or injected through the keyword-only `noise=` / `step_noise=` arguments (tests), or - with the
+keyword-only `seed=` (an int, or one int per batch item) - drawn on the device by the library's counter-based generator
+(noise.py): item b then gets the same draws whatever batch it is part of.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib, schedule
+from . import noise as seeded
 from .backbones import build_backbone
 from .hparams import hparams
 
@@ -89,6 +92,20 @@ class _SamplerMixin:
             None if scale is None else C.c_void_p(scale.data_ptr()),
             None if shift is None else C.c_void_p(shift.data_ptr()), flags, C.c_void_p(stream)), "dsd_sample")
         return out
+
+    def _seeds(self, seed, b, *explicit):
+        """`seed=` of forward / inference -> None (draw with torch, as ever) or the batch's b seeds."""
+        if seed is None:
+            return None
+        if any(e is not None for e in explicit):
+            raise ValueError("seed= draws the noise on the device: pass either seed or noise / step_noise, not both")
+        return seeded.as_seeds(seed, b)
+
+    def _seeded_state(self, seeds, domain, b, t, device, src=None, src_scale=1., scale=1.):
+        """[b, F, M, t]: src_scale * src + scale * eps with eps the seeded x_T of each item, one launch."""
+        x = seeded.fill((1, b, self.num_feats * self.out_dims, t), seeds, domain, src=src, scale=scale, src_scale=src_scale,
+                        device=device)
+        return x.view(b, self.num_feats, self.out_dims, t)
 
 
 class GaussianDiffusion(nn.Module, _SamplerMixin):
@@ -163,7 +180,28 @@ class GaussianDiffusion(nn.Module, _SamplerMixin):
             return self.q_sample(x_start, torch.full((b,), t_max - 1, device=device, dtype=torch.long), noise)
         return x_start
 
-    def _run_loop(self, cond, x, t_max, speedup, algorithm, b, device, step_noise, scale, shift):
+    def _seeded_start(self, t_max, x_start, seeds, domain, b, t, device):
+        """`_start_state` with the noise drawn under the items' seeds, the shallow mix in the same launch."""
+        if t_max >= self.timesteps:
+            return self._seeded_state(seeds, domain, b, t, device)
+        assert x_start is not None, 'Missing shallow diffusion source.'
+        if t_max > 0:
+            return self._seeded_state(seeds, domain, b, t, device, src=x_start,
+                                      src_scale=float(self.sqrt_alphas_cumprod[t_max - 1]),
+                                      scale=float(self.sqrt_one_minus_alphas_cumprod[t_max - 1]))
+        return x_start
+
+    def _step_buffer(self, x):
+        """Seeded ancestral sampling: the chunk's noise lives in ONE buffer per (module, state shape), kept between runs -
+        dsd_sample's graph key holds the noise pointer, so a fresh tensor per chunk would never find its graph again."""
+        n = self._ANCESTRAL_CHUNK * x.numel()
+        buf = getattr(self, '_step_buf', None)
+        if buf is None or buf.device != x.device or buf.numel() < n:
+            buf = torch.empty(n, device=x.device, dtype=torch.float32)
+            object.__setattr__(self, '_step_buf', buf)
+        return buf
+
+    def _run_loop(self, cond, x, t_max, speedup, algorithm, b, device, step_noise, scale, shift, seeds=None):
         """The sampler dispatch of ddpm.py:245-351 on (t_max, speedup) that the caller has already decided."""
         tb = self._tables
         if speedup > 1 and t_max > 0:
@@ -194,6 +232,9 @@ class GaussianDiffusion(nn.Module, _SamplerMixin):
             n = hi - lo
             if step_noise is not None:
                 chunk = step_noise[k:k + n]
+            elif seeds is not None:         # one launch per chunk: streams k .. k + n - 1 of the STEP domain
+                chunk = seeded.fill((n, b, x.shape[1] * x.shape[2], x.shape[3]), seeds, seeded.STEP, first_stream=k,
+                                    out=self._step_buffer(x)[:n * x.numel()]).view((n,) + tuple(x.shape))
             else:
                 chunk = torch.stack([torch.randn(x.shape, device=device) for _ in range(n)])
             k += n
@@ -205,24 +246,32 @@ class GaussianDiffusion(nn.Module, _SamplerMixin):
         return x
 
     @torch.no_grad()
-    def inference(self, cond, b=1, x_start=None, device=None, *, noise=None, step_noise=None, _denorm=False):
+    def inference(self, cond, b=1, x_start=None, device=None, *, noise=None, step_noise=None, seed=None,
+                  noise_domain=seeded.X_T, _denorm=False):
+        seeds = self._seeds(seed, b, noise, step_noise)
         depth = hparams.get('K_step_infer', self.k_step)
         speedup = hparams['diff_speedup']
         if speedup > 0:
             assert depth % speedup == 0, f'Acceleration ratio must be a factor of diffusion depth {depth}.'
-        if noise is None:
+        if noise is None and seeds is None:
             noise = torch.randn(b, self.num_feats, self.out_dims, cond.shape[2], device=device)
         t_max = min(depth, self.k_step) if self.use_shallow_diffusion else self.k_step
-        x = self._start_state(t_max, x_start, noise, b, device)
+        if seeds is None:
+            x = self._start_state(t_max, x_start, noise, b, device)
+        else:
+            x = self._seeded_start(t_max, x_start, seeds, noise_domain, b, cond.shape[2], cond.device)
         scale, shift = self._affine_out() if _denorm else (None, None)
         return self._run_loop(cond, x, t_max, speedup, hparams['diff_accelerator'] if speedup > 1 else None,
-                              b, device, step_noise, scale, shift)
+                              b, device, step_noise, scale, shift, seeds)
 
-    def forward(self, condition, gt_spec=None, src_spec=None, infer=True, *, noise=None, step_noise=None, lengths=None):
+    def forward(self, condition, gt_spec=None, src_spec=None, infer=True, *, noise=None, step_noise=None, lengths=None,
+                seed=None, noise_domain=seeded.X_T):
         """
             conditioning diffusion, use fastspeech2 encoder output as the condition
             `lengths` [B]: ragged batch - item b is run as if alone at T = lengths[b] (dsd_set_lengths); frames beyond
             an item's length are unspecified in the result.
+            `seed` (an int, or B ints): x_T - under `noise_domain` - and ancestral sampling's step noise are drawn on the
+            device from the items' seeds (noise.py) instead of torch's generator; not together with `noise` / `step_noise`.
         """
         if not infer:
             raise NotImplementedError(
@@ -231,7 +280,8 @@ class GaussianDiffusion(nn.Module, _SamplerMixin):
         b, device = condition.shape[0], condition.device
         spec = None if src_spec is None else _to_bfmt(self.norm_spec(src_spec), self.num_feats)
         with _ragged(self.denoise_fn, lengths, device):
-            x = self.inference(cond, b=b, x_start=spec, device=device, noise=noise, step_noise=step_noise, _denorm=True)
+            x = self.inference(cond, b=b, x_start=spec, device=device, noise=noise, step_noise=step_noise, seed=seed,
+                               noise_domain=noise_domain, _denorm=True)
         return self._finish_denorm(x)
 
     @torch.no_grad()
@@ -335,8 +385,10 @@ class RectifiedFlow(nn.Module, _SamplerMixin):
     _affine_out = GaussianDiffusion._affine_out
 
     @torch.no_grad()
-    def inference(self, cond, b=1, x_end=None, device=None, *, noise=None, _denorm=False):
-        if noise is None:
+    def inference(self, cond, b=1, x_end=None, device=None, *, noise=None, seed=None, noise_domain=seeded.X_T,
+                  _denorm=False):
+        seeds = self._seeds(seed, b, noise)
+        if noise is None and seeds is None:
             noise = torch.randn(b, self.num_feats, self.out_dims, cond.shape[2], device=device)
         t_start = hparams.get('T_start_infer', self.t_start)
         if self.use_shallow_diffusion and t_start > 0:
@@ -344,11 +396,14 @@ class RectifiedFlow(nn.Module, _SamplerMixin):
             if t_start >= 1.:
                 t_start = 1.
                 x = x_end
+            elif seeds is not None:         # the start mix and the draw in one launch
+                x = self._seeded_state(seeds, noise_domain, b, cond.shape[2], cond.device, src=x_end, src_scale=t_start,
+                                       scale=1 - t_start)
             else:
                 x = t_start * x_end + (1 - t_start) * noise
         else:
             t_start = 0.
-            x = noise
+            x = noise if seeds is None else self._seeded_state(seeds, noise_domain, b, cond.shape[2], cond.device)
 
         algorithm = hparams['sampling_algorithm']
         infer_step = hparams['sampling_steps']
@@ -361,8 +416,11 @@ class RectifiedFlow(nn.Module, _SamplerMixin):
             entry = self._cached_program(('noop',), lambda: schedule.Program(1, 0, []))
         return self._run_program(entry, cond, x, scale=scale, shift=shift)
 
-    def forward(self, condition, gt_spec=None, src_spec=None, infer=True, *, noise=None, lengths=None):
-        """`lengths` [B]: ragged batch - item b is run as if alone at T = lengths[b] (dsd_set_lengths)."""
+    def forward(self, condition, gt_spec=None, src_spec=None, infer=True, *, noise=None, lengths=None, seed=None,
+                noise_domain=seeded.X_T):
+        """`lengths` [B]: ragged batch - item b is run as if alone at T = lengths[b] (dsd_set_lengths).
+        `seed` (an int, or B ints): x_T is drawn on the device from the items' seeds under `noise_domain` (noise.py)
+        instead of torch's generator; not together with `noise`."""
         if not infer:
             raise NotImplementedError(
                 "diffsinger_amd.RectifiedFlow is inference-only (infer=True); train with the reference module")
@@ -370,7 +428,8 @@ class RectifiedFlow(nn.Module, _SamplerMixin):
         b, device = condition.shape[0], condition.device
         spec = None if src_spec is None else _to_bfmt(self.norm_spec(src_spec), self.num_feats)
         with _ragged(self.velocity_fn, lengths, device):
-            x = self.inference(cond, b=b, x_end=spec, device=device, noise=noise, _denorm=True)
+            x = self.inference(cond, b=b, x_end=spec, device=device, noise=noise, seed=seed, noise_domain=noise_domain,
+                               _denorm=True)
         return self._finish_denorm(x)
 
     @torch.no_grad()

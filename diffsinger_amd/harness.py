@@ -311,8 +311,10 @@ class AcousticHarness:
 
     # -- model, vocoder ---------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward_model(self, sample):
+    def forward_model(self, sample, seed=None):
         kwargs = {v: sample.get(v) for v in self.variances_to_embed}
+        if seed is not None:            # device_noise: the sampler's draws come from this seed (noise.py)
+            kwargs['seed'] = seed
         if hparams['use_spk_id']:
             table = self.model.fs2.spk_embed(sample['spk_mix_id'])                       # [1, 1, N, H]
             kwargs['spk_mix_embed'] = torch.sum(table * sample['spk_mix_value'].unsqueeze(3), dim=2, keepdim=False)
@@ -332,6 +334,16 @@ class AcousticHarness:
         torch.manual_seed(value & 0xffff_ffff)
         torch.cuda.manual_seed_all(value & 0xffff_ffff)
 
+    @staticmethod
+    def _device_seed(param, seed):
+        """`device_noise=True`: the segment's own 64-bit seed - its 'seed' entry, else the run's `seed`, else a fresh 63-bit
+        draw from torch's CPU generator.  Nothing is reseeded: the draws are a function of this number alone (noise.py)."""
+        if 'seed' in param:
+            return int(param['seed']) & 0xffff_ffff_ffff_ffff
+        if seed >= 0:
+            return int(seed) & 0xffff_ffff_ffff_ffff
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
     # -- several segments in one launch (ragged batch) --------------------------------------------------------------
     def _draw_noise(self, param, seed, t_len):
         """x_T of one segment, drawn exactly as the model would draw it when run alone (same seeding, same call)."""
@@ -343,9 +355,10 @@ class AcousticHarness:
         return torch.randn(1, d.num_feats, d.out_dims, t_len, device=self.device)
 
     @torch.no_grad()
-    def forward_model_batch(self, samples, noises):
+    def forward_model_batch(self, samples, noises, seeds=None):
         """`forward_model` for several segments at once: inputs zero-padded to the longest, per-segment lengths handed to
-        the library (dsd_set_lengths), so every mel equals the one the segment gives alone.  -> list of [1, T_i, M]."""
+        the library (dsd_set_lengths), so every mel equals the one the segment gives alone.  `noises`: each segment's x_T,
+        or None with `seeds` (one per segment: drawn on the device).  -> list of [1, T_i, M]."""
         lens = [int(s['mel2ph'].size(1)) for s in samples]
         t_max, n = max(lens), len(samples)
 
@@ -368,16 +381,19 @@ class AcousticHarness:
         for key in ('key_shift', 'speed'):
             kwargs[key] = torch.cat([pad_t(s[key], t) for s, t in zip(samples, lens)]) if samples[0].get(key) is not None else None
         languages = cat('languages', l_max) if samples[0].get('languages') is not None else None
-        noise = torch.cat([torch.nn.functional.pad(z, [0, t_max - z.size(-1)]) for z in noises])
+        if seeds is not None:
+            kwargs['seed'] = list(seeds)
+        else:
+            kwargs['noise'] = torch.cat([torch.nn.functional.pad(z, [0, t_max - z.size(-1)]) for z in noises])
         out = self.model(cat('tokens', l_max), languages=languages, mel2ph=cat('mel2ph', t_max), f0=cat('f0', t_max),
-                         infer=True, noise=noise, lengths=lens, **kwargs).diff_out
+                         infer=True, lengths=lens, **kwargs).diff_out
         return [out[i:i + 1, :lens[i]] for i in range(n)]
 
     @torch.no_grad()
-    def run_vocoder_batch(self, mels, f0s, draws):
+    def run_vocoder_batch(self, mels, f0s, draws, seeds=None):
         """The vocoder over several segments in one ragged call (dsd_vocode_ragged): mels [1, T_i, M], f0s [1, T_i] and each
-        segment's (rand_ini, noise, pre_noise) as `Generator.draw` makes them -> list of [T_i * upp] waveforms, each the one
-        the segment gives alone with those draws."""
+        segment's (rand_ini, noise, pre_noise) as `Generator.draw` makes them - or None with `seeds`, one per segment, for
+        draws made on the device - -> list of [T_i * upp] waveforms, each the one the segment gives alone with those draws."""
         gen = self.vocoder.model
         lens = [int(m.size(1)) for m in mels]
         t_max, upp = max(lens), gen.upp
@@ -385,10 +401,12 @@ class AcousticHarness:
         mel = torch.cat([torch.nn.functional.pad(m, [0, 0, 0, t_max - m.size(1)]) for m in mels])
         f0 = torch.cat([pad(f.to(mel.device), t_max) for f in f0s])
         kwargs = {}
-        if draws[0][0] is not None:
+        if seeds is not None:
+            kwargs['seed'] = list(seeds)
+        elif draws[0][0] is not None:
             kwargs['rand_ini'] = torch.stack([d[0] for d in draws])
             kwargs['noise'] = torch.cat([torch.nn.functional.pad(d[1], [0, 0, 0, t_max * upp - d[1].size(1)]) for d in draws])
-        if draws[0][2] is not None:
+        if seeds is None and draws[0][2] is not None:
             kwargs['pre_noise'] = torch.cat([pad(d[2], t_max) for d in draws])
         wav = self.vocoder.spec2wav_torch(mel, f0=f0, lengths=lens, **kwargs).view(len(mels), -1)
         return [wav[i, :n * upp] for i, n in enumerate(lens)]
@@ -403,7 +421,7 @@ class AcousticHarness:
         return hparams.get('diff_accelerator') in ('ddim', 'pndm', 'dpm-solver', 'unipc') and hparams.get('diff_speedup', 1) > 1
 
     def run_inference(self, params: List[dict], out_path=None, seed: int = -1, save_mel: bool = False, batch_size: int = 1,
-                      out_dir=None, title: Optional[str] = None, num_runs: int = 1):
+                      out_dir=None, title: Optional[str] = None, num_runs: int = 1, device_noise: bool = False):
         """One pass over the segments of a project: returns the assembled waveform (or the list of mels) and, when
         `out_path` is given, writes it.  Each segment is placed at its `offset`; where it overlaps what is already
         there the two are cross-faded.  `batch_size` > 1 runs that many segments per launch of the acoustic model as
@@ -412,7 +430,10 @@ class AcousticHarness:
         segment's random draws made in the generator state a one-by-one run makes them in (same track up to the
         vocoder's fp32 rounding).
         With `out_dir` and `title` the reference's own calling convention applies: `num_runs` passes, written to
-        `out_dir/title[-NNN].wav` (or `.mel.pt` with `save_mel`); the last pass is returned."""
+        `out_dir/title[-NNN].wav` (or `.mel.pt` with `save_mel`); the last pass is returned.
+        `device_noise=True`: every random draw of a segment - the sampler's and the vocoder's - is made on the device from the
+        segment's own seed (its 'seed' entry, else `seed`, else a fresh draw), so torch's generators are not reseeded and a
+        segment sounds the same at any `batch_size`."""
         if out_dir is not None:
             assert title is not None, 'run_inference(out_dir=...) needs a title'
             suffix = '.mel.pt' if save_mel else '.wav'
@@ -420,18 +441,28 @@ class AcousticHarness:
             for run in range(num_runs):
                 name = f'{title}-{str(run).zfill(3)}{suffix}' if num_runs > 1 else title + suffix
                 result = self.run_inference(params, out_path=pathlib.Path(out_dir) / name, seed=seed, save_mel=save_mel,
-                                            batch_size=batch_size)
+                                            batch_size=batch_size, device_noise=device_noise)
             return result
         batches = [self.preprocess_input(param, idx=i) for i, param in enumerate(params)]
         ready, wavs = {}, {}
+        seeds = [self._device_seed(p, seed) for p in params] if device_noise else None
         if batch_size > 1 and self._batchable():
-            noises = [self._draw_noise(p, seed, int(b['mel2ph'].size(1))) for p, b in zip(params, batches)]
+            if seeds is None:
+                noises = [self._draw_noise(p, seed, int(b['mel2ph'].size(1))) for p, b in zip(params, batches)]
             order = sorted(range(len(params)), key=lambda i: -int(batches[i]['mel2ph'].size(1)))     # similar lengths together
             groups = [order[k:k + batch_size] for k in range(0, len(order), batch_size)]
             for group in groups:
-                mels_g = self.forward_model_batch([batches[i] for i in group], [noises[i] for i in group])
+                if seeds is None:
+                    mels_g = self.forward_model_batch([batches[i] for i in group], [noises[i] for i in group])
+                else:
+                    mels_g = self.forward_model_batch([batches[i] for i in group], None, seeds=[seeds[i] for i in group])
                 ready.update(zip(group, mels_g))
-            if not save_mel:
+            if not save_mel and seeds is not None:
+                for group in groups:
+                    wav_g = self.run_vocoder_batch([ready[i] for i in group], [batches[i]['f0'] for i in group], None,
+                                                   seeds=[seeds[i] for i in group])
+                    wavs.update(zip(group, wav_g))
+            elif not save_mel:
                 # the vocoder's draws of every segment in the generator state a lone run of it makes them in: after its
                 # seed and its x_T draw; then each group in one ragged call
                 draws = []
@@ -447,6 +478,8 @@ class AcousticHarness:
         for i, (param, batch) in enumerate(zip(params, batches)):
             if i in ready:
                 mel = ready[i]
+            elif seeds is not None:
+                mel = self.forward_model(batch, seed=seeds[i])
             else:
                 if 'seed' in param:
                     self._seed(param['seed'])
@@ -456,7 +489,8 @@ class AcousticHarness:
             if save_mel:
                 mels.append({'offset': param.get('offset', 0.), 'mel': mel.cpu(), 'f0': batch['f0'].cpu()})
                 continue
-            wav = (wavs[i] if i in wavs else self.run_vocoder(mel, f0=batch['f0'])[0]).cpu().numpy()
+            voc_seed = {} if seeds is None else {'seed': seeds[i]}
+            wav = (wavs[i] if i in wavs else self.run_vocoder(mel, f0=batch['f0'], **voc_seed)[0]).cpu().numpy()
             gap = round(param.get('offset', 0) * hparams['audio_sample_rate']) - cursor
             if gap >= 0:
                 track = np.concatenate((track, np.zeros(gap), wav))

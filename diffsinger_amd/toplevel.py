@@ -106,7 +106,8 @@ class DiffSingerAcoustic(AcousticDecoder):
         self._init_decoder(out_dims)
 
     def forward(self, txt_tokens, mel2ph, f0, key_shift=None, speed=None, spk_embed_id=None, languages=None,
-                gt_mel=None, infer=True, noise=None, step_noise=None, lengths=None, **kwargs) -> ShallowDiffusionOutput:
+                gt_mel=None, infer=True, noise=None, step_noise=None, lengths=None, seed=None,
+                **kwargs) -> ShallowDiffusionOutput:
         condition = self.fs2(txt_tokens, mel2ph, f0, key_shift=key_shift, speed=speed, spk_embed_id=spk_embed_id,
                              languages=languages, **kwargs)
         extra = {}
@@ -114,4 +115,6 @@ class DiffSingerAcoustic(AcousticDecoder):
             extra["noise"] = noise
         if step_noise is not None:
             extra["step_noise"] = step_noise
+        if seed is not None:            # an int or B ints: the sampler's draws are made on the device (noise.py)
+            extra["seed"] = seed
         return AcousticDecoder.forward(self, condition, mel2ph, gt_mel=gt_mel, infer=infer, lengths=lengths, **extra)

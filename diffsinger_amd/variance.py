@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import noise as seeded
 from .backbones import _NativeBackbone
 from .diffusion import (MultiVarianceDiffusion, MultiVarianceRectifiedFlow, PitchDiffusion, PitchRectifiedFlow)
 from .encoder import PAD_INDEX, _Encoder, ffn_act_of, pos_mode_of, positional_extra_weights
@@ -369,7 +370,8 @@ class DiffSingerVariance(ParameterAdaptorModule):
                 **kwargs):
         """-> dur_pred [B, T_ph] | None, pitch_pred [B, T] | None, {name: [B, T]}.  Extra keywords: the current variance
         curves by name (`energy=...`), `ph_spk_mix_embed` / `spk_mix_embed`, and - for reproducible runs - the x_T of the
-        two denoisers, `pitch_noise` [B, 1, R, T] and `variance_noise` [B, F, R, T]; `lengths` [B] runs a zero-padded batch
+        two denoisers, `pitch_noise` [B, 1, R, T] and `variance_noise` [B, F, R, T], or `seed` (an int, or B ints: both x_T
+        are drawn on the device, under noise.PITCH_X_T and noise.VARIANCE_X_T); `lengths` [B] runs a zero-padded batch
         of segments as a ragged batch (each comes out as if alone at its own frame count, dsd_set_lengths)."""
         _check_infer(self)
         if not infer:
@@ -419,7 +421,8 @@ class DiffSingerVariance(ParameterAdaptorModule):
                     base_pitch = base_pitch * pitch_retake + pitch * ~pitch_retake
                 terms += lin1(self.base_pitch_embed, base_pitch)
             pitch_cond = assemble(bsz, t_len, h, gathers, terms, dev)
-            pitch_pred_out = self.pitch_predictor(pitch_cond, infer=True, noise=kwargs.get('pitch_noise'), lengths=lengths)
+            pitch_pred_out = self.pitch_predictor(pitch_cond, infer=True, noise=kwargs.get('pitch_noise'), lengths=lengths,
+                                                  seed=kwargs.get('seed'), noise_domain=seeded.PITCH_X_T)
         if not self.predict_variances:
             return dur_pred_out, pitch_pred_out, {}
 
@@ -433,5 +436,6 @@ class DiffSingerVariance(ParameterAdaptorModule):
                 layer = self.variance_embeds[name]
                 terms += [(v_in * keep, layer.weight.reshape(-1)), (keep, layer.bias)]
         var_cond = assemble(bsz, t_len, h, cond_g, terms, dev)
-        outs = self.variance_predictor(var_cond, infer=True, noise=kwargs.get('variance_noise'), lengths=lengths)
+        outs = self.variance_predictor(var_cond, infer=True, noise=kwargs.get('variance_noise'), lengths=lengths,
+                                       seed=kwargs.get('seed'), noise_domain=seeded.VARIANCE_X_T)
         return dur_pred_out, pitch_pred_out, self.collect_variance_outputs(outs)

@@ -199,9 +199,11 @@ class VarianceHarness(AcousticHarness):
 
     # -- model ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward_model(self, sample):
+    def forward_model(self, sample, seed=None):
         """-> (durations aligned to the words [1, T_ph] | None, pitch in MIDI [1, T] | None, {name: [1, T]})"""
         kwargs = dict(ph_spk_mix_embed=None, spk_mix_embed=None)
+        if seed is not None:            # device_noise: both loops' x_T come from this seed (noise.py)
+            kwargs['seed'] = seed
         if hparams['use_spk_id']:
             for key in ('ph_spk_mix', 'spk_mix'):
                 table = self.model.spk_embed(sample[key + '_id'])                       # [1, 1, N, H]
@@ -238,9 +240,10 @@ class VarianceHarness(AcousticHarness):
         return flag, tuple(sorted(k for k, v in batch.items() if v is not None))
 
     @torch.no_grad()
-    def forward_model_batch(self, samples, noises):
+    def forward_model_batch(self, samples, noises, seeds=None):
         """`forward_model` for several segments with one signature: inputs padded to the longest (notes with the padding
-        marker -1), frame counts handed on as `lengths` (dsd_set_lengths) -> per segment what `forward_model` returns."""
+        marker -1), frame counts handed on as `lengths` (dsd_set_lengths); `noises` None with `seeds` (one per segment):
+        the x_T are drawn on the device -> per segment what `forward_model` returns."""
         pad = torch.nn.functional.pad
         lens = [int(s['base_pitch'].size(1)) for s in samples]
         t_max = max(lens)
@@ -267,7 +270,10 @@ class VarianceHarness(AcousticHarness):
                     rows.append(e.expand(-1, n_of(s), -1) if e.size(1) == 1 else e)
                 width = max(int(r.size(1)) for r in rows)
                 kwargs[key + '_embed'] = torch.cat([pad(r, [0, 0, 0, width - r.size(1)]) for r in rows])
-        noise = {k: torch.cat([pad(z[k], [0, t_max - z[k].size(-1)]) for z in noises]) for k in noises[0]}
+        if seeds is not None:
+            noise = {'seed': list(seeds)}
+        else:
+            noise = {k: torch.cat([pad(z[k], [0, t_max - z[k].size(-1)]) for z in noises]) for k in noises[0]}
         dur, pitch, variances = self.model(
             cat('tokens'), languages=cat('languages'), midi=cat('midi'), ph2word=cat('ph2word'), ph_dur=cat('ph_dur'),
             mel2ph=cat('mel2ph'), word_dur=cat('word_dur'), note_midi=cat('note_midi', value=-1.), note_rest=cat('note_rest'),
@@ -310,8 +316,11 @@ class VarianceHarness(AcousticHarness):
             m.fs2.predict_dur, m.predict_pitch, m.predict_variances = saved
 
     def run_inference(self, params: List[dict], out_dir=None, title: str = None, num_runs: int = 1, seed: int = -1,
-                      batch_size: int = 1):
+                      batch_size: int = 1, device_noise: bool = False):
         """-> the completed projects (one list of segments per run); written to `out_dir/title[-NNN].ds` when given.
+        `device_noise=True`: the x_T of both loops are drawn on the device from the segment's own seed (its 'seed' entry,
+        else `seed`, else a fresh draw; noise.PITCH_X_T / noise.VARIANCE_X_T), torch's generators are not reseeded, and a
+        segment's curves are the same at any `batch_size`.
         `batch_size` > 1: segments on which the same predictors run on the same kinds of inputs share a launch as a ragged
         batch (same predictions as one by one, which is the reference's order and the default)."""
         flags = [self._flags(p) for p in params]
@@ -320,6 +329,7 @@ class VarianceHarness(AcousticHarness):
         runs = []
         for run in range(num_runs):
             ready = {}
+            seeds = [self._device_seed(p, seed) for p in params] if device_noise else None
             if batch_size > 1 and hasattr(self.model, 'fs2') and hasattr(self.model.fs2, 'native_handle'):
                 groups = {}
                 for i, (f, b) in enumerate(zip(flags, batches)):
@@ -330,14 +340,20 @@ class VarianceHarness(AcousticHarness):
                         part = members[k:k + batch_size]
                         if len(part) < 2:
                             continue
-                        noises = [self._draw_noises(params[i], seed, flag, int(batches[i]['base_pitch'].size(1))) for i in part]
-                        got = self._with_flags(flag, lambda: self.forward_model_batch([batches[i] for i in part], noises))
+                        if seeds is None:
+                            noises = [self._draw_noises(params[i], seed, flag, int(batches[i]['base_pitch'].size(1))) for i in part]
+                            got = self._with_flags(flag, lambda: self.forward_model_batch([batches[i] for i in part], noises))
+                        else:
+                            got = self._with_flags(flag, lambda: self.forward_model_batch(
+                                [batches[i] for i in part], None, seeds=[seeds[i] for i in part]))
                         ready.update(zip(part, got))
             results = []
             for i, (param, flag, batch) in enumerate(zip(params, flags, batches)):
                 done = copy.deepcopy(param)
                 if i in ready:
                     dur, pitch, variances = ready[i]
+                elif seeds is not None:
+                    dur, pitch, variances = self._with_flags(flag, lambda: self.forward_model(batch, seed=seeds[i]))
                 else:
                     if 'seed' in param:
                         self._seed(param['seed'])

@@ -5,8 +5,9 @@
 parameters under the reference's names in their inference form (after `remove_weight_norm()`); a checkpoint that
 still carries `weight_g` / `weight_v` pairs is folded on load (`w = g * v / ||v||`, the norm over all dims but 0,
 torch.nn.utils.weight_norm's default).  `forward(x, f0)` = models.py:262-290 with SineGen's two random draws
-(`torch.rand` initial phases, `torch.randn_like` noise) made on the caller's device, or passed in for
-reproducibility; `mini_nsf: true` generators (fastsinegen source, `source_conv`) have no random draws.
+(`torch.rand` initial phases, `torch.randn_like` noise) made on the caller's device, passed in for
+reproducibility, or - `forward(x, f0, seed=...)` - drawn by the library's counter-based generator (noise.py);
+`mini_nsf: true` generators (fastsinegen source, `source_conv`) have no random draws.
 `forward(x, f0, lengths=[...])` vocodes a zero-padded batch of segments in one ragged call (dsd_vocode_ragged): item b
 comes out as the segment alone at T = lengths[b] would, draws included.
 Inference only; no CPU path.
@@ -20,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import noise as seeded
 from .backbones import _NativeBackbone
 
 
@@ -121,20 +123,42 @@ class Generator(_NativeBackbone):
     def prepare_cond(self, cond, layout="BHT"):
         raise RuntimeError("the vocoder has no conditioner; call forward(mel, f0)")
 
-    def forward(self, x, f0, *, lengths=None, rand_ini=None, noise=None, pre_noise=None):
+    def _seeded_draws(self, seed, b, t, dev, per_item):
+        """The draws of `forward(seed=)`: -> (rand_ini [dim] - per_item: [b, dim] -, noise [b, t * upp, dim], pre_noise
+        [b, C0, t]), those a lone `forward` would not draw None.  Item i's values depend on its seed alone, not on b or t."""
+        seeds = seeded.as_seeds(seed, b)
+        dim = self.harmonic_num + 1
+        rand_ini = noise = pre = None
+        if not self.mini_nsf:
+            ini_seeds = seeds if per_item else seeds[:1]
+            rand_ini = seeded.fill((1, len(ini_seeds), 1, dim), ini_seeds, seeded.VOC_PHASE, kind="uniform", device=dev)
+            rand_ini = rand_ini.view(b, dim) if per_item else rand_ini.view(dim)
+            noise = seeded.fill((1, b, t * self.upp, dim), seeds, seeded.VOC_SOURCE, device=dev)[0]
+        if self.noise_sigma is not None and self.noise_sigma > 0:
+            pre = seeded.fill((1, b, self.upsample_initial_channel, t), seeds, seeded.VOC_PRE, device=dev)[0]
+        return rand_ini, noise, pre
+
+    def forward(self, x, f0, *, lengths=None, rand_ini=None, noise=None, pre_noise=None, seed=None):
         """x: [B, num_mels, T] natural-log mel, f0: [B, T] -> [B, 1, T * prod(upsample_rates)].
 
         `lengths` (B ints in [1, T]): a ragged batch - item b holds `lengths[b]` valid frames and comes out as it would
         alone at that length; the output past `lengths[b] * prod(upsample_rates)` is zero.  The draws are then per item:
         `rand_ini` [B, harmonic_num + 1], `noise` [B, T * upp, harmonic_num + 1] (item b's first lengths[b] * upp rows),
         `pre_noise` [B, C0, T] (item b's first lengths[b] frames); those not passed are drawn item by item in the order
-        and shapes B lone calls would draw them, so the generator state afterwards is the one those calls leave."""
+        and shapes B lone calls would draw them, so the generator state afterwards is the one those calls leave.
+
+        `seed`: every draw is made on the device from it instead (noise.py; domains VOC_PHASE, VOC_SOURCE, VOC_PRE), torch's
+        generator is not touched, and no draw may be passed as well.  A dense call takes one int (its one `rand_ini` comes
+        from it, as the reference draws one; B ints give each item's noise its own seed and the phases the first), a ragged
+        call one int per item: item b then comes out as it does alone with `seed=seeds[b]`."""
+        if seed is not None and not (rand_ini is None and noise is None and pre_noise is None):
+            raise ValueError("seed= draws on the device: pass either seed or rand_ini / noise / pre_noise, not both")
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise RuntimeError("diffsinger_amd.vocoder.Generator is inference-only: call it under torch.no_grad()")
         if x.dim() != 3 or x.shape[1] != self.num_mels or tuple(f0.shape) != (x.shape[0], x.shape[2]):
             raise ValueError(f"x [B, {self.num_mels}, T] and f0 [B, T] expected; got {tuple(x.shape)}, {tuple(f0.shape)}")
         if lengths is not None:
-            return self._forward_ragged(x, f0, lengths, rand_ini, noise, pre_noise)
+            return self._forward_ragged(x, f0, lengths, rand_ini, noise, pre_noise, seed)
         dev = x.device
         handle = self.native_handle(dev)
         b, _, t = x.shape
@@ -149,6 +173,8 @@ class Generator(_NativeBackbone):
         f0 = f0.detach().to(device=dev, dtype=torch.float32).contiguous()
         dim = self.harmonic_num + 1
         want_pre = self.noise_sigma is not None and self.noise_sigma > 0      # models.py:272-273
+        if seed is not None:
+            rand_ini, noise, pre_noise = self._seeded_draws(seed, b, t, dev, per_item=False)
         # the reference's order of random draws (same generator state in, same state out): SineGen's initial phases
         # (models.py:145), its additive noise (:165), and only then - after conv_pre - the noise_sigma normals (:272-273)
         if not self.mini_nsf:
@@ -194,7 +220,7 @@ class Generator(_NativeBackbone):
             pre = torch.randn((1, self.upsample_initial_channel, t_len), device=device)
         return rand_ini, noise, pre
 
-    def _forward_ragged(self, x, f0, lengths, rand_ini, noise, pre_noise):
+    def _forward_ragged(self, x, f0, lengths, rand_ini, noise, pre_noise, seed=None):
         lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
         b, _, t = x.shape
         if len(lens) != b or any(v < 1 or v > t for v in lens):
@@ -209,6 +235,8 @@ class Generator(_NativeBackbone):
         f0 = f0.detach().to(device=dev, dtype=torch.float32).contiguous()
         dim, upp, c0 = self.harmonic_num + 1, self.upp, self.upsample_initial_channel
         want_pre = self.noise_sigma is not None and self.noise_sigma > 0
+        if seed is not None:        # whole-batch draws: item i's first lengths[i] frames are what it draws alone
+            rand_ini, noise, pre_noise = self._seeded_draws(seed, b, t, dev, per_item=True)
         draw_ini = not self.mini_nsf and rand_ini is None
         draw_noise = not self.mini_nsf and noise is None
         draw_pre = want_pre and pre_noise is None
@@ -266,5 +294,5 @@ class NsfHifiGAN:
             f0 = kwargs.get('f0')
             if f0 is None:
                 raise ValueError("the NSF generator needs f0 (models.py:262)")
-            extra = {k: kwargs[k] for k in ("lengths", "rand_ini", "noise", "pre_noise") if kwargs.get(k) is not None}
+            extra = {k: kwargs[k] for k in ("lengths", "rand_ini", "noise", "pre_noise", "seed") if kwargs.get(k) is not None}
             return self.model(c, f0, **extra).view(-1)

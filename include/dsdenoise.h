@@ -352,6 +352,52 @@ int dsd_frame_curve(int32_t device, const float* note_midi, const int64_t* mel2n
                     const uint8_t* retake, int32_t B, int32_t N, int32_t T, const int32_t* lengths, const float* weights,
                     int32_t K, float* base_out, float* blend_out, float* delta_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Seeded draws on the device: the x_T and step noise of the samplers, the vocoder's phases and noise.  Handle-free:
+ * `device` is the HIP device index.  Element (row, col) of a draw is a pure function of (seed, domain, stream, row, col):
+ * it does not depend on B, on padding, on the launch shape or on what the process drew before, so a ragged batch draws
+ * for item b exactly what a lone call with seeds[b] draws, and a C caller draws what the Python side draws.
+ *
+ * The generator:
+ *   block     Philox4x32-10 (Salmon et al., Random123): multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 /
+ *             0xBB67AE85.  Known answers (counter; key -> output):
+ *               0 0 0 0; 0 0                                          -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *               ffffffff x 4; ffffffff x 2                            -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *               243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   address   key = (seed & 0xffffffff, seed >> 32) of the item's 64-bit seed; counter = (col >> 2, row, stream, domain);
+ *             the four output words w[0..3] serve the columns 4 * (col >> 2) + 0..3
+ *   uniform   u(w) = ((w >> 9) + 0.5) * 2^-23: exact in fp32, strictly inside (0, 1).  DSD_NOISE_UNIFORM: column c is
+ *             u(w[c & 3]).
+ *   normal    Box-Muller on word pairs in fp32 with the precise logf / sqrtf / sincosf: r = sqrt(-2 log u(w0)),
+ *             theta = 2 pi u(w1), z0 = r cos(theta), z1 = r sin(theta); (w2, w3) gives z2, z3.  |z| <= 5.7681.
+ *   domain    a caller-chosen 32-bit tag that keeps the tensors drawn under one seed apart (the Python side uses 1 = x_T,
+ *             2 = sampler step noise, 3 = vocoder source noise, 4 = vocoder pre-noise, 5 = vocoder initial phases,
+ *             6 = pitch x_T, 7 = variance x_T)
+ *   stream    numbers the tensors of a sequence: the k-th step noise of a sampler run
+ *
+ *   out = src_scale * src + scale * eps   (src == NULL: out = scale * eps), each product and the sum rounded to fp32 on
+ *   its own.  With src this is the start mix of shallow diffusion / reflow in the same launch; out may be src.
+ *
+ * The seeds travel in the launch arguments: the call does not synchronise, allocates nothing and can be captured into a
+ * hipGraph (the seeds are then part of the captured launch).  A 16-byte store per four columns when cols % 4 == 0 and
+ * out (and src) are 16-byte aligned, scalar stores otherwise.  DSD_EINVAL before any device work for a NULL spec, out or
+ * seeds, a wrong struct_size, an unknown kind, n, B, rows or cols below 1, or more than 2^31 - 1 elements.
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_NOISE_NORMAL 0
+#define DSD_NOISE_UNIFORM 1
+typedef struct dsd_noise_spec {
+    int32_t struct_size;
+    int32_t kind;            /* DSD_NOISE_NORMAL or DSD_NOISE_UNIFORM                          */
+    uint32_t domain;
+    int32_t first_stream;    /* out[k] is stream first_stream + k                              */
+    int32_t n, B, rows, cols;/* out is dense [n][B][rows][cols]                                */
+    const uint64_t* seeds;   /* HOST, B values: one seed per item                              */
+    float scale;
+    const float* src;        /* device, [n][B][rows][cols] dense, or NULL                      */
+    float src_scale;
+} dsd_noise_spec;
+int dsd_noise_fill(int32_t device, const dsd_noise_spec* spec, float* out, void* stream);
+
 /*
  * NSF-HiFiGAN generator (the step after the loop: mel -> waveform).  The constructor arguments are the fields of the
  * checkpoint's config.json that Generator.__init__ reads (modules/nsf_hifigan/models.py:207-260), `mini_nsf: false`.
