@@ -22,6 +22,11 @@ BACKBONE_IDS = {"wavenet": 0, "lynxnet": 1}
 AUX_CONVNEXT = 2
 DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
 ACT_IDS = {"PReLU": 0, "SiLU": 1, "ReLU": 2}
+SCHEDULE_IDS = {"linear": 0, "cosine": 1}                  # DSD_SCHEDULE_*
+DSD_DDPM_TABLES = 12
+# DSD_SAMPLER_*: the DDPM family under the names of hparams['diff_accelerator'], rectified flow under `rf_` + algorithm
+SAMPLER_IDS = {"ddpm": 0, "ddim": 1, "pndm": 2, "dpm-solver": 3, "unipc": 4, "rf_euler": 5, "rf_rk2": 6, "rf_rk4": 7,
+               "rf_rk5": 8, "rf_euler_onnx": 9}
 
 EXPORTS = [
     "dsd_api_version", "dsd_create", "dsd_create_any_width", "dsd_destroy", "dsd_last_error", "dsd_load_weight",
@@ -35,6 +40,7 @@ EXPORTS = [
     "dsd_variance_curves",
     "dsd_length_regulate", "dsd_frame_curve",
     "dsd_noise_fill",
+    "dsd_ddpm_tables_fill", "dsd_program_build", "dsd_program_free", "dsd_onnx_ddpm_plan",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -130,6 +136,12 @@ class DsdProgram(C.Structure):
                 ("n_noise", C.c_int32), ("evals", C.POINTER(DsdEval))]
 
 
+class DsdSamplerSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("sampler", C.c_int32), ("timesteps", C.c_int32), ("t_max", C.c_int32),
+                ("speedup", C.c_int32), ("t_lo", C.c_int32), ("noise_index0", C.c_int32), ("steps", C.c_int32),
+                ("tables", C.POINTER(C.c_float)), ("t_start", C.c_double), ("time_scale_factor", C.c_double)]
+
+
 class DsdStats(C.Structure):
     _fields_ = [("weight_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
                 ("flops_per_frame_nfe", C.c_int64), ("bytes_per_frame_nfe", C.c_int64),
@@ -209,6 +221,11 @@ def _load():
     lib.dsd_length_regulate.argtypes = [i32, vp, i32, i32, i32, vp, vp]
     lib.dsd_frame_curve.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_float), i32, vp, vp, vp, vp]
     lib.dsd_noise_fill.argtypes = [i32, C.POINTER(DsdNoiseSpec), vp, vp]
+    lib.dsd_ddpm_tables_fill.argtypes = [i32, i32, C.c_double, C.POINTER(C.c_float)]
+    lib.dsd_program_build.argtypes = [C.POINTER(DsdSamplerSpec), C.POINTER(C.POINTER(DsdProgram))]
+    lib.dsd_program_free.argtypes = [C.POINTER(DsdProgram)]
+    lib.dsd_program_free.restype = None
+    lib.dsd_onnx_ddpm_plan.argtypes = [i32, i32, C.POINTER(i64), i32, i32, C.c_double, C.POINTER(i32), C.POINTER(i32)]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

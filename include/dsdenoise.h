@@ -622,8 +622,10 @@ int dsd_rmvpe_infer(dsd_handle* h, const float* wav, int32_t B, int64_t n_sample
  * before the loop starts.  A program states exactly that: per evaluation, the state buffer fed
  * to the backbone, the model time, and up to DSD_MAX_OUT linear combinations
  *      dst = sum_k coef_k * src_k,     src_k in { model output, state buffers, injected noise }
- * which the library fuses into the epilogue of the backbone's last GEMM.  The host-side
- * scheduler (diffsinger_amd/schedule.py) computes the coefficients; the device does NFE + axpy.
+ * which the library fuses into the epilogue of the backbone's last GEMM.  The coefficients are
+ * computed on the host, once per (sampler, schedule, steps) - by dsd_program_build below for a
+ * caller of this header, by diffsinger_amd/schedule.py (the same arithmetic, and the yardstick the
+ * library's builder is tested against) for the Python side; the device does NFE + axpy.
  * ------------------------------------------------------------------------------------------ */
 #define DSD_MAX_TERMS 8
 #define DSD_MAX_OUT 3
@@ -675,6 +677,81 @@ typedef struct dsd_program {
  */
 int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, const float* noise,
                float* out, const float* out_scale, const float* out_shift, uint32_t flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Building the programs.  Host only and handle-free: no device is touched, and a failure leaves its message in
+ * dsd_last_error(NULL).  One build per (sampler, schedule, steps); the result can be run any number of times.
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_SCHEDULE_LINEAR 0   /* linear_beta_schedule(timesteps, max_beta)  (ddpm.py:64-68): linspace(1e-4, max_beta) */
+#define DSD_SCHEDULE_COSINE 1   /* cosine_beta_schedule(timesteps, s=0.008)   (ddpm.py:71-82); max_beta is not read     */
+#define DSD_DDPM_TABLES 12
+/*
+ * Replaces: the register_buffer block of GaussianDiffusion.__init__ (ddpm.py:93-115).  out: HOST, [12][timesteps] fp32 -
+ * betas, alphas_cumprod, alphas_cumprod_prev, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod,
+ * log_one_minus_alphas_cumprod, sqrt_recip_alphas_cumprod, sqrt_recipm1_alphas_cumprod, posterior_variance,
+ * posterior_log_variance_clipped, posterior_mean_coef1, posterior_mean_coef2, in this order.  Double arithmetic in the
+ * reference's (numpy's) operation order, each value rounded to fp32 once.  DSD_EINVAL for a NULL out, an unknown
+ * schedule_type or timesteps < 1.
+ */
+int dsd_ddpm_tables_fill(int32_t schedule_type, int32_t timesteps, double max_beta, float* out);
+
+enum { DSD_SAMPLER_DDPM = 0,            /* p_sample, ancestral (ddpm.py:123-156,347-349): t_max - t_lo steps, one injected
+                                           noise tensor per step                                                         */
+       DSD_SAMPLER_DDIM = 1,            /* p_sample_ddim (ddpm.py:158-167,334-343)                                       */
+       DSD_SAMPLER_PLMS = 2,            /* p_sample_plms, 'pndm' (ddpm.py:169-204,323-333)                               */
+       DSD_SAMPLER_DPM_SOLVER_PP = 3,   /* DPM-Solver++ 2M, time_uniform, multistep (dpm_solver_pytorch.py:1171-1213)    */
+       DSD_SAMPLER_UNIPC = 4,           /* UniPC bh2, order 2, time_uniform, multistep (uni_pc.py:590-672)               */
+       DSD_SAMPLER_RF_EULER = 5,        /* RectifiedFlow.inference (reflow.py:66-138)                                    */
+       DSD_SAMPLER_RF_RK2 = 6,
+       DSD_SAMPLER_RF_RK4 = 7,
+       DSD_SAMPLER_RF_RK5 = 8,
+       DSD_SAMPLER_RF_EULER_ONNX = 9 }; /* RectifiedFlowONNX's euler loop (deployment/modules/rectified_flow.py:58-62):
+                                           t_start is rounded to fp32 first and dt, the step times are fp32 arithmetic   */
+
+typedef struct dsd_sampler_spec {
+    int32_t struct_size;       /* sizeof(dsd_sampler_spec)                                                              */
+    int32_t sampler;           /* DSD_SAMPLER_*                                                                          */
+    /* the DDPM family (DSD_SAMPLER_DDPM .. DSD_SAMPLER_UNIPC); not read for rectified flow */
+    int32_t timesteps;         /* length of each table                                                                  */
+    int32_t t_max;             /* the loop starts at step t_max - 1 (K_step_infer, or timesteps); 0 = the empty program  */
+    int32_t speedup;           /* >= 1: DDIM / PLMS step by it, DPM-Solver++ / UniPC run t_max / speedup steps over
+                                  betas[:t_max]; the ancestral sampler does not read it                                  */
+    int32_t t_lo;              /* ancestral only: this program covers steps t_max - 1 .. t_lo (a chunk of the loop)      */
+    int32_t noise_index0;      /* ancestral only: the step at t_max - 1 takes noise tensor noise_index0, the next one
+                                  noise_index0 + 1, ...; n_noise = noise_index0 + t_max - t_lo                           */
+    /* rectified flow (DSD_SAMPLER_RF_*); not read for the DDPM family */
+    int32_t steps;             /* sampling_steps                                                                        */
+    const float* tables;       /* HOST, [12][timesteps]: from dsd_ddpm_tables_fill, or a checkpoint's own buffers in that
+                                  order (the reference reads the buffers as they stand, ddpm.py:117-167)                 */
+    double t_start;            /* T_start_infer (0 without a shallow source)                                            */
+    double time_scale_factor;  /* hparams['time_scale_factor']                                                          */
+} dsd_sampler_spec;
+
+/*
+ * Replaces: the sampler dispatch of GaussianDiffusion.inference (ddpm.py:244-349) and RectifiedFlow.inference
+ * (reflow.py:117-136) up to the point where the loop runs - everything they compute that does not depend on x.
+ * *out is ONE allocation that owns its `evals`; release it with dsd_program_free (NULL is fine).  The scalar arithmetic is
+ * the reference's own: fp32 where it works on fp32 tensors (the discrete VP schedule of DPM-Solver++ / UniPC with
+ * interpolate_fn's neighbour choice, torch.linspace's two-sided rule, the lambda = -5.1 clip of DPM-Solver++), double for
+ * the products of such scalars that multiply one tensor, rounded to fp32 once.  expf / logf / expm1f are the C library's.
+ * DSD_EINVAL, with *out untouched and nothing allocated: a NULL argument, a wrong struct_size, an unknown sampler; for the
+ * DDPM family NULL tables, timesteps < 1, t_max outside [0, timesteps], speedup < 1, t_lo outside [0, t_max], a negative noise_index0,
+ * t_max / speedup < 2 for DPM-Solver++ / UniPC (the reference asserts steps >= order); steps < 0 for rectified flow; a
+ * program that would exceed DSD_MAX_TERMS or DSD_MAX_OUT (none of today's samplers does).
+ */
+int dsd_program_build(const dsd_sampler_spec* spec, dsd_program** out);
+void dsd_program_free(dsd_program* prog);
+
+/*
+ * Replaces: how GaussianDiffusionONNX.forward derives its loop from the runtime inputs `steps` and `depth`
+ * (deployment/modules/diffusion.py:105-131).  depth < 0 (no shallow source): *speedup = timesteps / steps snapped DOWN to
+ * one of `factors` (HOST, ascending: the factors of timesteps), *t_max = k_step.  Otherwise depth * timesteps is rounded in
+ * fp32, half to even, and capped at k_step; *speedup = that / steps (at least 1, NOT snapped) and *t_max = the depth
+ * rounded down to a multiple of it.  DSD_EINVAL for NULL outputs, timesteps or steps < 1, k_step < 0, a NaN depth, or
+ * (depth < 0) no factor <= the wanted speed-up.
+ */
+int dsd_onnx_ddpm_plan(int32_t timesteps, int32_t k_step, const int64_t* factors, int32_t n_factors, int32_t steps,
+                       double depth, int32_t* t_max, int32_t* speedup);
 
 /*
  * Arithmetic of the residual layers' two GEMMs (API v10).  DSD_PRECISION_F32 (default): fp32 operands on
