@@ -21,6 +21,7 @@ DSD_SAMPLE_GRAPH_LAZY = 4
 BACKBONE_IDS = {"wavenet": 0, "lynxnet": 1}
 AUX_CONVNEXT = 2
 DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
+DSD_TRACK_F64, DSD_TRACK_F32, DSD_TRACK_PCM = 0, 1, 2
 ACT_IDS = {"PReLU": 0, "SiLU": 1, "ReLU": 2}
 SCHEDULE_IDS = {"linear": 0, "cosine": 1}                  # DSD_SCHEDULE_*
 DSD_DDPM_TABLES = 12
@@ -41,6 +42,7 @@ EXPORTS = [
     "dsd_length_regulate", "dsd_frame_curve",
     "dsd_noise_fill",
     "dsd_ddpm_tables_fill", "dsd_program_build", "dsd_program_free", "dsd_onnx_ddpm_plan",
+    "dsd_track_plan", "dsd_track_place", "dsd_track_peak", "dsd_track_export",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -226,6 +228,10 @@ def _load():
     lib.dsd_program_free.argtypes = [C.POINTER(DsdProgram)]
     lib.dsd_program_free.restype = None
     lib.dsd_onnx_ddpm_plan.argtypes = [i32, i32, C.POINTER(i64), i32, i32, C.c_double, C.POINTER(i32), C.POINTER(i32)]
+    lib.dsd_track_plan.argtypes = [i32, C.POINTER(C.c_double), C.POINTER(i64), i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    lib.dsd_track_place.argtypes = [i32, vp, i64, i64, i64, vp, i64, vp]
+    lib.dsd_track_peak.argtypes = [i32, vp, i64, vp, vp]
+    lib.dsd_track_export.argtypes = [i32, vp, i64, i32, vp, vp, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

@@ -472,6 +472,15 @@ struct NoiseP {
 };
 hipError_t launch_noise_fill(const NoiseP& p, int items, hipStream_t st);
 
+// track_kernels.hip: a project's track (dsd_track_place / _peak / _export).  One workgroup covers kTrackSpan consecutive
+// samples of the track: 256 threads, each one 16-byte aligned pair of doubles (diffsinger_amd/track.py: SPAN).  The
+// launchers take the stream as void* and answer nullptr or hipGetErrorString's text, so that track_api.hip - the plan and
+// every argument check - stays free of HIP headers and compiles with a plain host compiler (tools/harness/track_harness.cpp).
+constexpr int kTrackSpan = 512;
+const char* launch_track_place(double* track, long long start, long long prev_end, const float* src, long long n, void* stream);
+const char* launch_track_peak(const double* track, long long total, double* peak_out, void* stream);
+const char* launch_track_export(const double* track, long long total, int kind, const double* peak, void* out, void* stream);
+
 // The DFT tile of mel_dft_kernel and hs_dft_kernel (dsd_device.h, dft_tile_walk), as far as the host sizes bases and work
 // lists by it
 constexpr int kDftFrames = 64;      // frames per tile (one work-list entry)

@@ -421,7 +421,8 @@ class AcousticHarness:
         return hparams.get('diff_accelerator') in ('ddim', 'pndm', 'dpm-solver', 'unipc') and hparams.get('diff_speedup', 1) > 1
 
     def run_inference(self, params: List[dict], out_path=None, seed: int = -1, save_mel: bool = False, batch_size: int = 1,
-                      out_dir=None, title: Optional[str] = None, num_runs: int = 1, device_noise: bool = False):
+                      out_dir=None, title: Optional[str] = None, num_runs: int = 1, device_noise: bool = False,
+                      device_mix: bool = False):
         """One pass over the segments of a project: returns the assembled waveform (or the list of mels) and, when
         `out_path` is given, writes it.  Each segment is placed at its `offset`; where it overlaps what is already
         there the two are cross-faded.  `batch_size` > 1 runs that many segments per launch of the acoustic model as
@@ -433,7 +434,12 @@ class AcousticHarness:
         `out_dir/title[-NNN].wav` (or `.mel.pt` with `save_mel`); the last pass is returned.
         `device_noise=True`: every random draw of a segment - the sampler's and the vocoder's - is made on the device from the
         segment's own seed (its 'seed' entry, else `seed`, else a fresh draw), so torch's generators are not reseeded and a
-        segment sounds the same at any `batch_size`."""
+        segment sounds the same at any `batch_size`.
+        `device_mix=True`: the track is assembled on the device (track.py): planned and allocated before the first segment
+        runs, each segment placed by one launch on the vocoder's stream, in segment order, and copied to the host once at
+        the end - the same float64 array, and with `out_path` the same file bytes, as the default path.  A layout numpy
+        raises on (a segment that starts before the track, an overlap longer than the new segment) raises ValueError
+        with the library's message before anything runs.  `save_mel` ignores the flag."""
         if out_dir is not None:
             assert title is not None, 'run_inference(out_dir=...) needs a title'
             suffix = '.mel.pt' if save_mel else '.wav'
@@ -441,10 +447,17 @@ class AcousticHarness:
             for run in range(num_runs):
                 name = f'{title}-{str(run).zfill(3)}{suffix}' if num_runs > 1 else title + suffix
                 result = self.run_inference(params, out_path=pathlib.Path(out_dir) / name, seed=seed, save_mel=save_mel,
-                                            batch_size=batch_size, device_noise=device_noise)
+                                            batch_size=batch_size, device_noise=device_noise, device_mix=device_mix)
             return result
         batches = [self.preprocess_input(param, idx=i) for i, param in enumerate(params)]
         ready, wavs = {}, {}
+        mix = None
+        if device_mix and not save_mel:
+            from . import track as _track
+            sr = hparams['audio_sample_rate']
+            layout = _track.plan([p.get('offset', 0) for p in params],
+                                 [int(b['mel2ph'].size(1)) * hparams['hop_size'] for b in batches], sr)
+            mix = _track.Track(layout.total, self.device, layout)
         seeds = [self._device_seed(p, seed) for p in params] if device_noise else None
         if batch_size > 1 and self._batchable():
             if seeds is None:
@@ -490,13 +503,19 @@ class AcousticHarness:
                 mels.append({'offset': param.get('offset', 0.), 'mel': mel.cpu(), 'f0': batch['f0'].cpu()})
                 continue
             voc_seed = {} if seeds is None else {'seed': seeds[i]}
-            wav = (wavs[i] if i in wavs else self.run_vocoder(mel, f0=batch['f0'], **voc_seed)[0]).cpu().numpy()
+            wav = wavs[i] if i in wavs else self.run_vocoder(mel, f0=batch['f0'], **voc_seed)[0]
+            if mix is not None:
+                mix.place(i, wav)
+                continue
+            wav = wav.cpu().numpy()
             gap = round(param.get('offset', 0) * hparams['audio_sample_rate']) - cursor
             if gap >= 0:
                 track = np.concatenate((track, np.zeros(gap), wav))
             else:
                 track = cross_fade(track, wav, cursor + gap)
             cursor += gap + wav.shape[0]
+        if mix is not None:
+            return self._finish_device_mix(mix, out_path)
         result = mels if save_mel else track
         if out_path is not None:
             out_path = pathlib.Path(out_path)
@@ -506,6 +525,23 @@ class AcousticHarness:
             else:
                 save_wav(result, out_path, hparams['audio_sample_rate'])
         return result
+
+    @staticmethod
+    def _finish_device_mix(mix, out_path):
+        """The track to the host in ONE copy: alone, or with `out_path` packed in front of its int16 export, from which
+        the file is written (the bytes `save_wav` writes)."""
+        if out_path is None:
+            return mix.numpy()
+        from scipy.io import wavfile
+        n = mix.total
+        packed = torch.empty(10 * n, dtype=torch.uint8, device=mix.device)
+        mix.export('f64', out=packed[:8 * n].view(torch.float64))
+        mix.export('pcm', out=packed[8 * n:].view(torch.int16))
+        host = packed.cpu().numpy()
+        out_path = pathlib.Path(out_path)
+        out_path.parent.mkdir(parents=True, exist_ok=True)
+        wavfile.write(out_path, hparams['audio_sample_rate'], host[8 * n:].view(np.int16))
+        return host[:8 * n].view(np.float64)
 
 
 class PhonemeDictionary:

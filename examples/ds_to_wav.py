@@ -3,7 +3,7 @@
 library only (no DiffSinger checkout needed at run time).
 
     python examples/ds_to_wav.py checkpoints/my_exp song.ds nsf_hifigan/model.ckpt -o song.wav [--steps 20] [--depth 0.6]
-                                 [--batch-size 8] [--seed 42] [--precision bf16x3]
+                                 [--batch-size 8] [--seed 42] [--precision bf16x3] [--device-mix]
 
 checkpoints/my_exp holds what a training run leaves there: config.yaml, model_ckpt_steps_<N>.ckpt, dictionary-<lang>.txt
 (or dictionary.txt), and - for multi-speaker / multilingual models - spk_map.json / lang_map.json.
@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--spk", default=None, help='speaker or mix, e.g. "alice" or "alice:0.3|bob" (scripts/infer.py --spk)')
     ap.add_argument("--precision", choices=("f32", "bf16x3"), default="f32",
                     help="arithmetic of the denoiser's and the vocoder's residual layers (set_precision); default: fp32")
+    ap.add_argument("--device-mix", action="store_true",
+                    help="assemble the track on the GPU (place, cross-fade, int16): one copy to the host at the end")
     args = ap.parse_args()
 
     load_config(args.exp / "config.yaml", overrides=dict(infer=True, work_dir=str(args.exp)))
@@ -56,7 +58,8 @@ def main():
         mix = harness.parse_commandline_spk_mix(args.spk)
         for seg in params:
             seg["spk_mix"] = mix
-    track = h.run_inference(params, out_path=out, seed=args.seed, batch_size=args.batch_size)
+    track = h.run_inference(params, out_path=out, seed=args.seed, batch_size=args.batch_size,
+                            device_mix=args.device_mix)
     print(f"| wrote {out}: {track.shape[0] / hparams['audio_sample_rate']:.2f} s")
 
 

@@ -914,6 +914,73 @@ int dsd_variance_curves(dsd_handle* h, const float* wav, const float* harmonic, 
                         int32_t tension_domain, int32_t energy_db, float* energy, float* breathiness, float* voicing,
                         float* tension, int64_t out_stride_b, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A project's track on the device: place each vocoded segment at its offset, cross-fade where it overlaps what is there,
+ * export the samples.  Handle-free like dsd_noise_fill: `device` is the HIP device index; no call allocates or
+ * synchronises, and every device call can be captured into a hipGraph (one chain of launches).
+ *
+ * Replaces: the fold of inference/ds_acoustic.py:231-259 over the segments (result = [], cursor = 0; per segment
+ * gap = round(offset * sr) - cursor; gap >= 0: append gap zeros and the waveform; else cross_fade(result, wav, cursor + gap))
+ * with cross_fade of utils/infer_utils.py:89-96, and save_wav of utils/infer_utils.py:99-104.  Everything float64.
+ *
+ * The track always ends where the last placed segment ends, so the fold equals placing segment k in place into a float64
+ * track of the final length.  With s = round(offset_k * sr), n = len(wav_k), p = the end of segment k - 1 (0 for the
+ * first) and F = p - s:
+ *   gap      F <= 0:  track[p:s] = 0, track[s:s+n] = wav
+ *   overlap  F > 0:   for j in [0, F): r_j = j * (1.0 / (F - 1)), r_{F-1} = 1.0 exactly, r_0 = 0 when F == 1 (np.linspace);
+ *                     track[s+j] = (1 - r_j) * track[s+j] + r_j * wav[j], each operation rounded on its own in float64;
+ *                     then track[p:s+n] = wav[F:]
+ * The results are bit for bit numpy's.
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Replaces: round(param['offset'] * sr) and the cursor bookkeeping of ds_acoustic.py:253-259.  Host only: never touches a
+ * device.  starts_out[k] = nearbyint(offsets_seconds[k] * sample_rate) in double - half to even, as Python's round;
+ * prev_ends_out[k] = the p above; *total_out = the end of the last segment = the length of the track.
+ * DSD_EINVAL (message under dsd_last_error(NULL)), with nothing promised about the outputs, for: a NULL argument, n_seg < 1 or
+ * sample_rate < 1; a length below 1 (stricter than the reference, which would append an empty array: the vocoder never
+ * returns one); a start below 0, or an overlap longer than the new segment (F > n) - the two layouts where the reference
+ * raises ValueError; a track of more than 2^31 - 1 samples.
+ */
+int dsd_track_plan(int32_t n_seg, const double* offsets_seconds, const int64_t* lengths, int32_t sample_rate,
+                   int64_t* starts_out, int64_t* prev_ends_out, int64_t* total_out);
+
+/*
+ * Replaces: one turn of the loop of ds_acoustic.py:252-259 with cross_fade (infer_utils.py:89-96).  One launch: the gap's
+ * zeros, the blend and the copy of segment `src` (device fp32, n samples) into `track` (device float64, `total` samples,
+ * 8-byte aligned), as above.  Calls are placed in segment order on one stream; after the last one every sample of
+ * [0, total) has been written, so the track needs no memset.
+ * The call checks the geometry of its own arguments - 0 <= start, n >= 1, start + n <= total <= 2^31 - 1,
+ * 0 <= prev_end <= total, prev_end - start <= n - and returns DSD_EINVAL before device selection and before any launch
+ * where they fail (also for a NULL or misaligned pointer): a caller without a plan cannot write outside the track.
+ */
+int dsd_track_place(int32_t device, double* track, int64_t total, int64_t start, int64_t prev_end, const float* src,
+                    int64_t n, void* stream);
+
+/*
+ * Replaces: np.abs(wav).max() of save_wav(norm=True) (infer_utils.py:100-101).  *peak_out (device, 8-byte aligned) =
+ * max |track[i]| over [0, total): exact, a maximum does not depend on the order.  A NaN sample gives a NaN, as in numpy.
+ * The call zeroes peak_out itself (a memset node in front of the one launch).
+ */
+int dsd_track_peak(int32_t device, const double* track, int64_t total, double* peak_out, void* stream);
+
+/*
+ * Replaces: save_wav's arithmetic (infer_utils.py:100-104), and the track's way out in the other two formats.
+ *   DSD_TRACK_F64   out is double[total]: a copy
+ *   DSD_TRACK_F32   out is float[total]: each sample rounded once to fp32
+ *   DSD_TRACK_PCM   out is int16_t[total]: v * 32767 in double, truncated toward zero (numpy's astype(np.int16))
+ * peak (device double, from dsd_track_peak), or NULL: with a peak the value is (v / *peak) * 32767, in that order
+ * (norm=True); DSD_TRACK_PCM only, DSD_EINVAL with the other kinds.
+ * Two deviations, both where numpy's own result is undefined: a product outside int16 saturates to -32768 / 32767 (numpy
+ * wraps, platform-dependent; NaN gives 0), and a zero peak gives zeros (numpy divides 0 / 0).
+ * DSD_EINVAL before any launch for a NULL track or out, an unknown kind, total outside [1, 2^31 - 1] or a misaligned pointer.
+ */
+#define DSD_TRACK_F64 0
+#define DSD_TRACK_F32 1
+#define DSD_TRACK_PCM 2
+int dsd_track_export(int32_t device, const double* track, int64_t total, int32_t kind, const double* peak, void* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
