@@ -22,6 +22,10 @@ BACKBONE_IDS = {"wavenet": 0, "lynxnet": 1}
 AUX_CONVNEXT = 2
 DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
 DSD_TRACK_F64, DSD_TRACK_F32, DSD_TRACK_PCM = 0, 1, 2
+DSD_SCORE_WORKSPACE_BYTES = 65536
+DSD_DIFFUSE_DDPM, DSD_DIFFUSE_REFLOW = 0, 1
+LOSS_IDS = {"l1": 0, "l2": 1}                               # DSD_LOSS_*
+DUR_LOSS_IDS = {"mse": 0, "huber": 1}                       # DSD_DUR_*
 ACT_IDS = {"PReLU": 0, "SiLU": 1, "ReLU": 2}
 SCHEDULE_IDS = {"linear": 0, "cosine": 1}                  # DSD_SCHEDULE_*
 DSD_DDPM_TABLES = 12
@@ -43,6 +47,7 @@ EXPORTS = [
     "dsd_noise_fill",
     "dsd_ddpm_tables_fill", "dsd_program_build", "dsd_program_free", "dsd_onnx_ddpm_plan",
     "dsd_track_plan", "dsd_track_place", "dsd_track_peak", "dsd_track_export",
+    "dsd_diffuse", "dsd_masked_loss", "dsd_curve_stats", "dsd_dur_score",
 ]
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
@@ -119,6 +124,33 @@ class DsdNoiseSpec(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("domain", C.c_uint32), ("first_stream", C.c_int32),
                 ("n", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("seeds", C.POINTER(C.c_uint64)), ("scale", C.c_float), ("src", C.c_void_p), ("src_scale", C.c_float)]
+
+
+class DsdDiffuseSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("domain", C.c_uint32), ("x0", C.c_void_p), ("eps", C.c_void_p), ("a", C.c_void_p), ("c", C.c_void_p),
+                ("seeds", C.POINTER(C.c_uint64))]
+
+
+class DsdLossSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("pred", C.c_void_p), ("target", C.c_void_p), ("non_padding", C.c_void_p), ("t", C.c_void_p)]
+
+
+class DsdCurveResult(C.Structure):
+    _fields_ = [("close", C.c_int64), ("total", C.c_int64), ("sum_target", C.c_double), ("sum_target_sq", C.c_double),
+                ("sum_residual_sq", C.c_double)]
+
+
+class DsdDurSpec(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("n_words", C.c_int32),
+                ("offset", C.c_float), ("rhythm_tolerance", C.c_float), ("pdur_tolerance", C.c_float),
+                ("dur_pred", C.c_void_p), ("dur_gt", C.c_void_p), ("ph2word", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class DsdDurResult(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("pdur_sum", "wdur_sum", "sdur_sum", "pdur_mean", "wdur_mean", "sdur_mean")] + \
+               [(n, C.c_int64) for n in ("rhythm_correct", "rhythm_total", "pdur_accurate", "pdur_total")]
 
 
 class DsdTerm(C.Structure):
@@ -232,6 +264,10 @@ def _load():
     lib.dsd_track_place.argtypes = [i32, vp, i64, i64, i64, vp, i64, vp]
     lib.dsd_track_peak.argtypes = [i32, vp, i64, vp, vp]
     lib.dsd_track_export.argtypes = [i32, vp, i64, i32, vp, vp, vp]
+    lib.dsd_diffuse.argtypes = [i32, C.POINTER(DsdDiffuseSpec), vp, vp, vp]
+    lib.dsd_masked_loss.argtypes = [i32, C.POINTER(DsdLossSpec), vp, vp, vp]
+    lib.dsd_curve_stats.argtypes = [i32, vp, vp, vp, i64, C.c_float, vp, vp, vp]
+    lib.dsd_dur_score.argtypes = [i32, C.POINTER(DsdDurSpec), vp, vp, vp, vp, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

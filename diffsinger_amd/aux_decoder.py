@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .losses import L1Loss
 from .backbones import _NativeBackbone, filter_kwargs
 
 
@@ -93,7 +94,7 @@ AUX_DECODERS = {
     'convnext': ConvNeXtDecoder
 }
 AUX_LOSSES = {
-    'convnext': nn.L1Loss
+    'convnext': L1Loss          # nn.L1Loss() as a device reduction (losses.py: dsd_masked_loss without a mask)
 }
 
 
@@ -105,6 +106,7 @@ def build_aux_decoder(in_dims: int, out_dims: int, aux_decoder_arch: str, aux_de
 
 
 def build_aux_loss(aux_decoder_arch):
+    """modules/aux_decoder/__init__.py:24-25."""
     return AUX_LOSSES[aux_decoder_arch]()
 
 

@@ -472,6 +472,52 @@ struct NoiseP {
 };
 hipError_t launch_noise_fill(const NoiseP& p, int items, hipStream_t st);
 
+// score_kernels.hip: validation scoring (dsd_diffuse, dsd_masked_loss, dsd_curve_stats, dsd_dur_score).  The reductions
+// sum doubles in an order fixed by the element count alone (include/dsdenoise.h, "the rounding rule"): workgroup g of
+// score_blocks(n) takes the spans g, g + G, ... of kScoreSpan elements; its sums go to slot-major partials in the caller's
+// workspace, [kScoreSlots][kScoreMaxBlocks] 8-byte values, and a one-workgroup launch adds those.
+constexpr int kScoreThreads = 256;
+constexpr int kScoreSpan = 2048;
+constexpr int kScoreMaxBlocks = 1024;
+constexpr int kScoreSlots = 8;
+inline int score_blocks(long long n) {
+    const long long spans = (n + kScoreSpan - 1) / kScoreSpan;
+    return (int)(spans < kScoreMaxBlocks ? spans : kScoreMaxBlocks);
+}
+struct DiffuseP {                   // a launch covers up to kNoiseItems items from b0, as NoiseP
+    float* x_t;
+    float* target;                  // or nullptr
+    const float* x0;
+    const float* eps;               // or nullptr: drawn from seed[]
+    const float* a;
+    const float* c;
+    unsigned domain;
+    int rows, cols, b0, kind;       // kind: 0 ddpm, 1 reflow
+    unsigned long long seed[kNoiseItems];
+};
+hipError_t launch_diffuse(const DiffuseP& p, int items, hipStream_t st);
+struct LossP {
+    const float* pred;
+    const float* target;
+    const float* non_padding;       // or nullptr
+    const float* t;                 // or nullptr
+    int B, rows, cols, kind;        // kind: 0 l1, 1 l2
+};
+hipError_t launch_masked_loss(const LossP& p, void* ws, double* out, hipStream_t st);
+hipError_t launch_curve_stats(const float* pred, const float* target, const unsigned char* mask, long long n, float tol, void* ws,
+                              void* out, hipStream_t st);
+struct DurP {
+    const float* dur_pred;
+    const float* dur_gt;
+    const long long* ph2word;
+    const unsigned char* mask;      // or nullptr
+    float* wdur_pred;               // [B][n_words - 1]
+    float* wdur_gt;
+    int B, L, n_words, kind;        // kind: 0 mse, 1 huber
+    float offset, tol_rhythm, tol_pdur;
+};
+hipError_t launch_dur_score(const DurP& p, void* ws, void* out, hipStream_t st);
+
 // track_kernels.hip: a project's track (dsd_track_place / _peak / _export).  One workgroup covers kTrackSpan consecutive
 // samples of the track: 256 threads, each one 16-byte aligned pair of doubles (diffsinger_amd/track.py: SPAN).  The
 // launchers take the stream as void* and answer nullptr or hipGetErrorString's text, so that track_api.hip - the plan and

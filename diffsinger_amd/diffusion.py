@@ -7,7 +7,9 @@ src_spec=None, infer=True)` has the reference signature; the sampling loop itsel
 library (dsd_sample): the host computes the solver's scalar coefficients (schedule.py), the device runs
 every NFE plus the fused solver update, by default replayed from a cached hipGraph.
 
-Inference only: `infer=False` (p_losses, ddpm.py:360-367) raises - training stays on the reference.
+Inference only: `infer=False` (p_losses, ddpm.py:360-367) raises - training stays on the reference.  What validation
+needs of that branch - one noising step and ONE denoiser evaluation, no gradients - is `forward_score`, which returns
+what the reference's `forward(infer=False)` returns.
 Randomness: x_T (and the per-step noise of ancestral DDPM) is drawn with `torch.randn` exactly where the
 reference draws it, or injected through the keyword-only `noise=` / `step_noise=` arguments (tests), or - with the
 keyword-only `seed=` (an int, or one int per batch item) - drawn on the device by the library's counter-based generator
@@ -21,7 +23,7 @@ from typing import List, Tuple
 import torch
 from torch import nn
 
-from . import _lib, schedule
+from . import _lib, schedule, score
 from . import noise as seeded
 from .backbones import build_backbone
 from .hparams import hparams
@@ -101,11 +103,31 @@ class _SamplerMixin:
             raise ValueError("seed= draws the noise on the device: pass either seed or noise / step_noise, not both")
         return seeded.as_seeds(seed, b)
 
+    def _score_draws(self, seed, b, t, noise, device, t_domain):
+        """forward_score's `seed=`: None, or (the b seeds, u [b] - each item's uniform draw under `t_domain`)."""
+        seeds = self._seeds(seed, b, t, noise)
+        if seeds is None:
+            return None, None
+        return seeds, seeded.fill((1, b, 1, 1), seeds, t_domain, kind="uniform", device=device).reshape(b)
+
     def _seeded_state(self, seeds, domain, b, t, device, src=None, src_scale=1., scale=1.):
         """[b, F, M, t]: src_scale * src + scale * eps with eps the seeded x_T of each item, one launch."""
         x = seeded.fill((1, b, self.num_feats * self.out_dims, t), seeds, domain, src=src, scale=scale, src_scale=src_scale,
                         device=device)
         return x.view(b, self.num_feats, self.out_dims, t)
+
+
+def seeded_t_ddpm(u, k_step):
+    """forward_score(seed=) of the DDPM wrapper: the uniform draw u in (0, 1) -> the integer step
+    min(k_step - 1, floor(float64(u) * k_step)).  (u <= 1 - 2^-24 and the product is formed in float64, where it stays
+    below k_step for every k_step < 2^28; the min only states the range.)"""
+    return (u.to(torch.float64) * k_step).floor().clamp(max=k_step - 1).long()
+
+
+def seeded_t_reflow(u, t_start):
+    """forward_score(seed=) of the rectified-flow wrapper: t = t_start + (1 - t_start) * u in fp32, the expression of
+    reflow.py:52 on the seeded u."""
+    return t_start + (1.0 - t_start) * u.to(torch.float32)
 
 
 class GaussianDiffusion(nn.Module, _SamplerMixin):
@@ -285,6 +307,31 @@ class GaussianDiffusion(nn.Module, _SamplerMixin):
         return self._finish_denorm(x)
 
     @torch.no_grad()
+    def forward_score(self, condition, gt_spec, *, t=None, noise=None, seed=None,
+                      domains=(seeded.SCORE_T, seeded.SCORE_NOISE)):
+        """What `forward(condition, gt_spec, infer=False)` of the reference returns (ddpm.py:360-367, 212-219):
+        (x_recon, noise), both [B, F, M, T] - one q_sample (dsd_diffuse) and ONE denoiser evaluation, no gradients.
+        `t` [B] int64 and `noise` [B, F, M, T] default to torch's draws, made where the reference makes them and in its
+        order (t, then the noise).  `seed` (an int, or B ints) draws both on the device from the items' seeds instead
+        (noise.py: `domains` = the t draw's and the noise's, SCORE_T and SCORE_NOISE; `seeded_t_ddpm`): item b then scores
+        the same whatever batch it is in.  Not together with `t` / `noise`."""
+        cond = condition.transpose(1, 2)
+        b, device = condition.shape[0], condition.device
+        seeds, u = self._score_draws(seed, b, t, noise, device, domains[0])
+        spec = _to_bfmt(self.norm_spec(gt_spec), self.num_feats)
+        if seeds is not None:
+            t = seeded_t_ddpm(u, self.k_step)
+        else:
+            if t is None:
+                t = torch.randint(0, self.k_step, (b,), device=device).long()
+            if noise is None:
+                noise = torch.randn_like(spec)
+        t = t.to(device)
+        x_noisy, drawn = score.diffuse("ddpm", spec, self.sqrt_alphas_cumprod[t], self.sqrt_one_minus_alphas_cumprod[t],
+                                       eps=noise, seeds=seeds, domain=domains[1], want_target=False)     # a given noise IS the target
+        return self.denoise_fn(x_noisy, t, cond), noise if seeds is None else drawn
+
+    @torch.no_grad()
     def forward_onnx(self, condition, x_start=None, depth=None, steps: int = 10, *, noise=None, step_noise=None):
         """The runtime inputs of the ONNX deployment twin, `GaussianDiffusionONNX.forward(condition, x_start, depth, steps)`
         (deployment/modules/diffusion.py:105-161): `steps` and `depth` arrive per call, any `steps` is legal - the
@@ -431,6 +478,28 @@ class RectifiedFlow(nn.Module, _SamplerMixin):
             x = self.inference(cond, b=b, x_end=spec, device=device, noise=noise, seed=seed, noise_domain=noise_domain,
                                _denorm=True)
         return self._finish_denorm(x)
+
+    @torch.no_grad()
+    def forward_score(self, condition, gt_spec, *, t=None, noise=None, seed=None,
+                      domains=(seeded.SCORE_T, seeded.SCORE_NOISE)):
+        """What `forward(condition, gt_spec, infer=False)` of the reference returns (reflow.py:47-54, 36-41):
+        (v_pred, v_gt, t) - x_t = x_start + t * (x_end - x_start) and v_gt = x_end - x_start in one launch (dsd_diffuse),
+        then ONE evaluation of the velocity network at t * time_scale_factor.  `t` [B] fp32 and `noise` (the reference's
+        x_start) default to torch's draws in the reference's order; `seed` draws both on the device (`seeded_t_reflow`)."""
+        cond = condition.transpose(1, 2)
+        b, device = condition.shape[0], condition.device
+        seeds, u = self._score_draws(seed, b, t, noise, device, domains[0])
+        spec = _to_bfmt(self.norm_spec(gt_spec), self.num_feats)
+        if seeds is not None:
+            t = seeded_t_reflow(u, self.t_start)
+        else:
+            if t is None:
+                t = self.t_start + (1.0 - self.t_start) * torch.rand((b,), device=device)
+            if noise is None:
+                noise = torch.randn_like(spec)
+        t = t.to(device=device, dtype=torch.float32)
+        x_t, v_gt = score.diffuse("reflow", spec, t, eps=noise, seeds=seeds, domain=domains[1])
+        return self.velocity_fn(x_t, t * self.time_scale_factor, cond), v_gt, t
 
     @torch.no_grad()
     def forward_onnx(self, condition, x_end=None, depth=None, steps: int = 10, *, noise=None):

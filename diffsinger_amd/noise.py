@@ -24,6 +24,10 @@ VOC_PRE = 4         # its noise_sigma normals after conv_pre [C0, T]
 VOC_PHASE = 5       # SineGen's initial phases (uniform) [1, harmonic_num + 1]
 PITCH_X_T = 6       # the variance pair: the pitch predictor's start state ...
 VARIANCE_X_T = 7    # ... and the variance predictor's
+SCORE_T = 8         # forward_score: the items' diffusion time (uniform) [1, 1] ...
+SCORE_NOISE = 9     # ... and the noise of its noising step
+SCORE_VAR_T = 10    # the variance model scores two predictors under one seed: the pitch predictor draws under the two
+SCORE_VAR_NOISE = 11    # above, the variance predictor under these
 
 KINDS = {"normal": _lib.DSD_NOISE_NORMAL, "uniform": _lib.DSD_NOISE_UNIFORM}
 

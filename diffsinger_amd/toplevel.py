@@ -3,7 +3,8 @@
 `AcousticDecoder` is everything after the FastSpeech2 encoder has produced `condition` (aux decoder, padding
 masks, denoise loop); `DiffSingerAcoustic` adds the encoder (`fs2`) in front.  Same attribute names as the
 reference (`fs2`, `aux_decoder`, `diffusion`), so an acoustic checkpoint loads with strict=True; same hparams read
-at construction (toplevel.py:44-83) and the same infer-branch behaviour (:84-105).  Inference only.
+at construction (toplevel.py:44-83) and the same infer-branch behaviour (:84-105).  Inference only; what validation
+needs of the other branch (:106-122) - no gradients - is `forward_score`.
 """
 from __future__ import annotations
 
@@ -40,6 +41,13 @@ def get_backbone_args(hp, backbone_type):
         return {'num_layers': hp.get('residual_layers'), 'num_channels': hp.get('residual_channels'),
                 'dilation_cycle_length': hp.get('dilation_cycle_length')}
     return None
+
+
+def need_eval(module):
+    """forward_score scores a checkpoint as the reference's validation does: with the module in eval()."""
+    if module.training:
+        raise RuntimeError(f"diffsinger_amd.{type(module).__name__}.forward_score scores in eval() mode, as the reference's "
+                           "validation runs: call .eval() first")
 
 
 class AcousticDecoder(nn.Module):
@@ -97,6 +105,21 @@ class AcousticDecoder(nn.Module):
         return ShallowDiffusionOutput(aux_out=aux_mel_pred, diff_out=mel_pred)
 
 
+    @torch.no_grad()
+    def forward_score(self, condition, gt_mel, *, t=None, noise=None, seed=None) -> ShallowDiffusionOutput:
+        """The `else` branch of toplevel.py:106-122 with `condition = self.fs2(...)` already evaluated, as validation runs
+        it (the module in eval(), no gradients): `aux_out` is the aux decoder's raw (normalised) output - the
+        `aux_decoder_grad` mix of the condition is the identity without gradients - and `diff_out` what the wrapper's
+        `forward_score` returns, (x_recon, noise) or (v_pred, v_gt, t).  `t`, `noise`, `seed`: the wrapper's."""
+        need_eval(self)
+        aux_out = diff_out = None
+        if self.use_shallow_diffusion and self.shallow_args['train_aux_decoder']:
+            aux_out = self.aux_decoder(condition, infer=False)
+        if not self.use_shallow_diffusion or self.shallow_args['train_diffusion']:
+            diff_out = self.diffusion.forward_score(condition, gt_mel, t=t, noise=noise, seed=seed)
+        return ShallowDiffusionOutput(aux_out=aux_out, diff_out=diff_out)
+
+
 class DiffSingerAcoustic(AcousticDecoder):
     """toplevel.py:32-120: `fs2` encoder -> (aux decoder ->) denoise loop, tokens in, mel out."""
 
@@ -118,3 +141,12 @@ class DiffSingerAcoustic(AcousticDecoder):
         if seed is not None:            # an int or B ints: the sampler's draws are made on the device (noise.py)
             extra["seed"] = seed
         return AcousticDecoder.forward(self, condition, mel2ph, gt_mel=gt_mel, infer=infer, lengths=lengths, **extra)
+
+    @torch.no_grad()
+    def forward_score(self, txt_tokens, mel2ph, f0, key_shift=None, speed=None, spk_embed_id=None, languages=None,
+                      gt_mel=None, *, t=None, noise=None, seed=None, **kwargs) -> ShallowDiffusionOutput:
+        """`forward(..., gt_mel=gt_mel, infer=False)` of the reference (toplevel.py:84-92,106-122) without gradients."""
+        need_eval(self)
+        condition = self.fs2(txt_tokens, mel2ph, f0, key_shift=key_shift, speed=speed, spk_embed_id=spk_embed_id,
+                             languages=languages, **kwargs)
+        return AcousticDecoder.forward_score(self, condition, gt_mel, t=t, noise=noise, seed=seed)

@@ -8,7 +8,9 @@ library: the FastSpeech2Encoder stacks and the DurationPredictor (`dsd_token_enc
 embedding sum (`dsd_cond_assemble`), and the pitch / multi-variance denoisers (diffusion.py).  What stays in torch is
 integer bookkeeping on [B, T_ph]-sized tensors: word onsets, the rhythm and length regulators.
 Encoders: the rotary configuration (`use_rope: true`, configs/variance.yaml:38) and the pre-rotary ones (`use_rope:
-false` with `rel_pos: true` or `false`, or `use_pos_embed: false`); inference only; no CPU path.
+false` with `rel_pos: true` or `false`, or `use_pos_embed: false`); inference only; no CPU path.  `forward_score` is the
+`infer=False` path of toplevel.py:217-309 as validation runs it: raw durations and one noising step plus ONE denoiser
+evaluation per predictor, no gradients.
 """
 from __future__ import annotations
 
@@ -27,7 +29,7 @@ from .diffusion import (MultiVarianceDiffusion, MultiVarianceRectifiedFlow, Pitc
 from .encoder import PAD_INDEX, _Encoder, ffn_act_of, pos_mode_of, positional_extra_weights
 from .harness import length_regulator
 from .hparams import hparams
-from .toplevel import get_backbone_args
+from .toplevel import get_backbone_args, need_eval
 
 VARIANCE_CHECKLIST = ['energy', 'breathiness', 'voicing', 'tension']      # param_adaptor.py:10
 
@@ -145,6 +147,30 @@ class DurationPredictor(nn.Module):
         self.linear = nn.Linear(n_chans, 1)
 
 
+class _RawDurationTwin(_NativeBackbone):
+    """DurationPredictor.forward(infer=False) (tts_modules.py:112-134) is exp(x) - offset WITHOUT inference's clamp at 0,
+    and dsd_predict_dur clamps.  A handle created with dur_offset = 0 computes max(exp(x) - 0, 0) = exp(x) - the clamp never
+    binds - and the caller subtracts the offset: the one fp32 subtraction the kernel makes, and exp(0) - offset at padding.
+    The twin is such a handle with the owner's weights: a second copy of fs2 on the device, made at the first scoring call.
+    (A dsd_predict_dur_raw entry point would save the copy; every call that takes a handle has a row in the handle-kind table
+    of tests/test_gpu_handle_kinds.py, which is pinned.)"""
+
+    def __init__(self, owner):
+        super().__init__()
+        object.__setattr__(self, '_owner', owner)       # not a submodule: the owner's state_dict stays the reference's
+
+    def _config(self, device_index):
+        cfg = self._owner._config(device_index)
+        cfg.dur_offset = 0.0
+        return cfg
+
+    def _native_state(self):
+        return self._owner._native_state()
+
+    def _extra_weights(self):
+        return self._owner._extra_weights()
+
+
 class FastSpeech2Variance(_TokenEncoderBase):
     """modules/fastspeech/variance_encoder.py:14-99."""
     _native_prefixes = ("encoder.", "dur_predictor.")
@@ -181,8 +207,22 @@ class FastSpeech2Variance(_TokenEncoderBase):
                                           d.kernel_size if d else 0, float(d.offset) if d else 0.0, self.pos_mode, device_index,
                                           self.ffn_act)
 
-    def forward(self, txt_tokens, midi, ph2word, ph_dur=None, word_dur=None, spk_embed=None, languages=None, infer=True):
-        """-> encoder_out [B, T_ph, H], ph_dur_pred [B, T_ph] or None (variance_encoder.py:52-99)."""
+    def _mark_dirty(self):
+        super()._mark_dirty()
+        twin = self.__dict__.get('_raw_twin')
+        if twin is not None:
+            twin._mark_dirty()
+
+    def _raw_dur_twin(self):
+        if self.__dict__.get('_raw_twin') is None:
+            object.__setattr__(self, '_raw_twin', _RawDurationTwin(self))
+        return self._raw_twin
+
+    def forward(self, txt_tokens, midi, ph2word, ph_dur=None, word_dur=None, spk_embed=None, languages=None, infer=True, *,
+                raw_dur=False):
+        """-> encoder_out [B, T_ph, H], ph_dur_pred [B, T_ph] or None (variance_encoder.py:52-99).  `raw_dur=True`: the
+        durations as `DurationPredictor.forward(infer=False)` returns them - exp(x) - offset, not clamped at 0 - for
+        DurationLoss (scoring; no gradients)."""
         _check_infer(self)
         if not infer:
             raise NotImplementedError("training (infer=False) stays on the reference module")
@@ -212,12 +252,14 @@ class FastSpeech2Variance(_TokenEncoderBase):
                 torch.zeros((bsz, n_ph), dtype=torch.int64, device=dev)
             gathers.append((spk_embed.expand(bsz, -1, -1), idx, 0, 1.0))
         dur_cond = assemble(bsz, n_ph, h, gathers, [], dev)
-        handle = self.native_handle(dev)
+        handle = (self._raw_dur_twin() if raw_dur else self).native_handle(dev)
         mask = pad.to(torch.uint8).contiguous()
         dur = torch.empty((bsz, n_ph), device=dev, dtype=torch.float32)
         stream = torch.cuda.current_stream(dev).cuda_stream
         _lib.check(handle, _lib.lib().dsd_predict_dur(handle, C.c_void_p(dur_cond.data_ptr()), C.c_void_p(mask.data_ptr()), bsz,
                                                       n_ph, C.c_void_p(dur.data_ptr()), C.c_void_p(stream)), "dsd_predict_dur")
+        if raw_dur:         # the twin's exp(x), minus the offset in fp32 as the kernel subtracts it
+            dur = dur - float(self.dur_predictor.offset)
         return enc, dur
 
 
@@ -376,6 +418,31 @@ class DiffSingerVariance(ParameterAdaptorModule):
         _check_infer(self)
         if not infer:
             raise NotImplementedError("training (infer=False) stays on the reference DiffSingerVariance")
+        return self._run(None, txt_tokens, midi, ph2word, ph_dur, word_dur, mel2ph, note_midi, note_rest, note_dur, note_glide,
+                         mel2note, base_pitch, pitch, pitch_expr, pitch_retake, variance_retake, spk_id, languages, lengths,
+                         kwargs)
+
+    @torch.no_grad()
+    def forward_score(self, txt_tokens, midi, ph2word, ph_dur=None, word_dur=None, mel2ph=None,
+                      note_midi=None, note_rest=None, note_dur=None, note_glide=None, mel2note=None,
+                      base_pitch=None, pitch=None, pitch_expr=None, pitch_retake=None,
+                      variance_retake: Dict[str, torch.Tensor] = None, spk_id=None, languages=None, *, seed=None, **kwargs):
+        """What `forward(..., infer=False)` of the reference returns (toplevel.py:217-309), without gradients and with the
+        module in eval() as validation runs it: the RAW duration prediction [B, T_ph] | None, the pitch predictor's
+        `forward_score` output on `pitch - base_pitch` | None, the variance predictor's on the curves given by name | None.
+        Extra keywords: the curves, `ph_spk_mix_embed` / `spk_mix_embed`, and the draws of the two scoring steps -
+        `pitch_t` / `pitch_noise`, `variance_t` / `variance_noise` (torch's by default, in the reference's order) or `seed`
+        (an int, or B ints: drawn on the device; the variance predictor under noise.SCORE_VAR_T / SCORE_VAR_NOISE, so that the
+        two predictors do not share their draws)."""
+        need_eval(self)
+        draws = {k: kwargs.pop(k, None) for k in ('pitch_t', 'pitch_noise', 'variance_t', 'variance_noise')}
+        draws['seed'] = seed
+        return self._run(draws, txt_tokens, midi, ph2word, ph_dur, word_dur, mel2ph, note_midi, note_rest, note_dur, note_glide,
+                         mel2note, base_pitch, pitch, pitch_expr, pitch_retake, variance_retake, spk_id, languages, None, kwargs)
+
+    def _run(self, score, txt_tokens, midi, ph2word, ph_dur, word_dur, mel2ph, note_midi, note_rest, note_dur, note_glide,
+             mel2note, base_pitch, pitch, pitch_expr, pitch_retake, variance_retake, spk_id, languages, lengths, kwargs):
+        """toplevel.py:198-309.  `score` None: the infer=True branch; else forward_score's draws and the infer=False branch."""
         dev = txt_tokens.device
         h = hparams['hidden_size']
         if self.use_spk_id:
@@ -387,9 +454,10 @@ class DiffSingerVariance(ParameterAdaptorModule):
         else:
             ph_spk_embed = spk_embed = None
         encoder_out, dur_pred_out = self.fs2(txt_tokens, midi=midi, ph2word=ph2word, ph_dur=ph_dur, word_dur=word_dur,
-                                             spk_embed=ph_spk_embed, languages=languages, infer=True)
+                                             spk_embed=ph_spk_embed, languages=languages, infer=True,
+                                             raw_dur=score is not None)
         if not self.predict_pitch and not self.predict_variances:
-            return dur_pred_out, None, {}
+            return dur_pred_out, None, ({} if score is None else None)
         if mel2ph is None and word_dur is not None:                 # inference from file
             mel2ph = self.lr(self.rr(dur_pred_out, ph2word, word_dur))
             mel2ph = F.pad(mel2ph, [0, base_pitch.shape[1] - mel2ph.shape[1]])
@@ -421,10 +489,14 @@ class DiffSingerVariance(ParameterAdaptorModule):
                     base_pitch = base_pitch * pitch_retake + pitch * ~pitch_retake
                 terms += lin1(self.base_pitch_embed, base_pitch)
             pitch_cond = assemble(bsz, t_len, h, gathers, terms, dev)
-            pitch_pred_out = self.pitch_predictor(pitch_cond, infer=True, noise=kwargs.get('pitch_noise'), lengths=lengths,
-                                                  seed=kwargs.get('seed'), noise_domain=seeded.PITCH_X_T)
+            if score is None:
+                pitch_pred_out = self.pitch_predictor(pitch_cond, infer=True, noise=kwargs.get('pitch_noise'), lengths=lengths,
+                                                      seed=kwargs.get('seed'), noise_domain=seeded.PITCH_X_T)
+            else:
+                pitch_pred_out = self.pitch_predictor.forward_score(pitch_cond, pitch - base_pitch, t=score['pitch_t'],
+                                                                    noise=score['pitch_noise'], seed=score['seed'])
         if not self.predict_variances:
-            return dur_pred_out, pitch_pred_out, {}
+            return dur_pred_out, pitch_pred_out, ({} if score is None else None)
 
         if pitch is None:
             pitch = base_pitch + pitch_pred_out
@@ -436,6 +508,11 @@ class DiffSingerVariance(ParameterAdaptorModule):
                 layer = self.variance_embeds[name]
                 terms += [(v_in * keep, layer.weight.reshape(-1)), (keep, layer.bias)]
         var_cond = assemble(bsz, t_len, h, cond_g, terms, dev)
+        if score is not None:
+            outs = self.variance_predictor.forward_score(var_cond, variance_inputs, t=score['variance_t'],
+                                                         noise=score['variance_noise'], seed=score['seed'],
+                                                         domains=(seeded.SCORE_VAR_T, seeded.SCORE_VAR_NOISE))
+            return dur_pred_out, pitch_pred_out, outs
         outs = self.variance_predictor(var_cond, infer=True, noise=kwargs.get('variance_noise'), lengths=lengths,
                                        seed=kwargs.get('seed'), noise_domain=seeded.VARIANCE_X_T)
         return dur_pred_out, pitch_pred_out, self.collect_variance_outputs(outs)

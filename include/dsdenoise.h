@@ -372,7 +372,8 @@ int dsd_frame_curve(int32_t device, const float* note_midi, const int64_t* mel2n
  *             theta = 2 pi u(w1), z0 = r cos(theta), z1 = r sin(theta); (w2, w3) gives z2, z3.  |z| <= 5.7681.
  *   domain    a caller-chosen 32-bit tag that keeps the tensors drawn under one seed apart (the Python side uses 1 = x_T,
  *             2 = sampler step noise, 3 = vocoder source noise, 4 = vocoder pre-noise, 5 = vocoder initial phases,
- *             6 = pitch x_T, 7 = variance x_T)
+ *             6 = pitch x_T, 7 = variance x_T, 8 = the scoring step's t, 9 = the scoring step's noise,
+ *             10 / 11 = the same two for the variance predictor)
  *   stream    numbers the tensors of a sequence: the k-th step noise of a sampler run
  *
  *   out = src_scale * src + scale * eps   (src == NULL: out = scale * eps), each product and the sum rounded to fp32 on
@@ -980,6 +981,117 @@ int dsd_track_peak(int32_t device, const double* track, int64_t total, double* p
 #define DSD_TRACK_PCM 2
 int dsd_track_export(int32_t device, const double* track, int64_t total, int32_t kind, const double* peak, void* out,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Validation scoring: what the reference's `_validation_step` computes around ONE denoiser evaluation
+ * (training/acoustic_task.py:119-197, training/variance_task.py:162-305) - the noising step of p_losses, the masked
+ * losses, the curve metrics and the duration loss with its metrics.  No backward pass; training stays out of scope.
+ * Handle-free like dsd_noise_fill: `device` is the HIP device index.  No call synchronises or allocates, and every call
+ * can be captured into a hipGraph.  DSD_EINVAL before any device work for a NULL pointer that is not marked optional, a
+ * wrong struct_size, an unknown kind, a size below 1, more than 2^31 - 1 elements, or a misaligned pointer.
+ *
+ * The rounding rule of every reduction below:
+ *   - a term is formed as the reference forms it wherever only IEEE fp32 add / sub / mul / div is involved, each
+ *     operation rounded on its own (no contraction into FMAs);
+ *   - whatever goes through the math library (log, exp) is evaluated in double from the fp32 input;
+ *   - the terms are summed in DOUBLE in an order fixed by the problem size alone: workgroup g of G = min(1024,
+ *     ceil(n / 2048)) takes the spans g, g + G, ... of 2048 consecutive elements, thread i of 256 takes the elements
+ *     i, i + 256, ... of a span in turn, the 256 thread sums are added pairwise (i with i + 128, then + 64, ... + 1), the
+ *     G workgroup sums go to `workspace`, and one last workgroup adds them the same way (thread i: partials i, i + 256,
+ *     ...).  No floating-point atomics: a result is bit-identical from run to run.
+ * workspace: device, DSD_SCORE_WORKSPACE_BYTES, 8-byte aligned, the caller's; two calls on different streams need two.
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_SCORE_WORKSPACE_BYTES 65536
+
+/* The noising step of p_losses on a dense [B][rows][cols] tensor (rows = F * M, cols = T).
+ *   DSD_DIFFUSE_DDPM    ddpm.py:206-219   x_t = fl(fl(a[b] * x0) + fl(c[b] * eps)),  target = eps
+ *                       (a = sqrt_alphas_cumprod[t], c = sqrt_one_minus_alphas_cumprod[t], gathered by the caller)
+ *   DSD_DIFFUSE_REFLOW  reflow.py:36-41   target = fl(x0 - eps),  x_t = fl(eps + fl(a[b] * target))  with a = t; the
+ *                       reference's own association, not (1 - t) * eps + t * x0.  c is not read.
+ * eps == NULL: eps is drawn inside the launch from `seeds` under `domain`, stream 0, DSD_NOISE_NORMAL - element for
+ * element what dsd_noise_fill draws at the same (seed, domain, row, col) - and `target` is required.  With a given eps
+ * and DSD_DIFFUSE_DDPM target may be NULL.  16-byte loads and stores when cols % 4 == 0 and every pointer is 16-byte
+ * aligned, the scalar path otherwise.  An output equal to an input (or to the other output) is DSD_EINVAL. */
+#define DSD_DIFFUSE_DDPM 0
+#define DSD_DIFFUSE_REFLOW 1
+typedef struct dsd_diffuse_spec {
+    int32_t struct_size;
+    int32_t kind;            /* DSD_DIFFUSE_*                                                   */
+    int32_t B, rows, cols;
+    uint32_t domain;         /* of the in-launch draw (the Python side uses 9 = scoring noise; 8 = scoring t) */
+    const float* x0;         /* device [B][rows][cols]: the normalised ground truth             */
+    const float* eps;        /* device, the same shape, or NULL: drawn from seeds               */
+    const float* a;          /* device [B]                                                      */
+    const float* c;          /* device [B]; DSD_DIFFUSE_DDPM only                               */
+    const uint64_t* seeds;   /* HOST, B values; read when eps == NULL                           */
+} dsd_diffuse_spec;
+int dsd_diffuse(int32_t device, const dsd_diffuse_spec* spec, float* x_t, float* target, void* stream);
+
+/* DiffusionLoss / RectifiedFlowLoss / nn.L1Loss as a reduction (diff_loss.py:16-34, reflow_loss.py:18-50,
+ * aux_decoder/__init__.py:10-12) over pred, target [B][rows][cols].
+ *   term   = |d| (DSD_LOSS_L1) or fl(d * d) (DSD_LOSS_L2) with d = fl(fl(pred * m) - fl(target * m)) in fp32,
+ *            m = non_padding[b][col] (NULL: d = fl(pred - target))
+ *   weight   t != NULL: the term times, in double, the log-norm weight of item b (reflow_loss.py:26-34)
+ *            0.398942 / t' / (1 - t') * exp(-0.5 * log(t' / (1 - t'))^2) + 1e-7,  t' = clip((double)t[b], 1e-7, 1 - 1e-7),
+ *            evaluated in double once per item
+ *   out[0] = the sum, out[1] = sum / (B * rows * cols): the reference's .mean() over all elements, padded ones included */
+#define DSD_LOSS_L1 0
+#define DSD_LOSS_L2 1
+typedef struct dsd_loss_spec {
+    int32_t struct_size;
+    int32_t kind;                /* DSD_LOSS_*                        */
+    int32_t B, rows, cols;
+    const float* pred;           /* device [B][rows][cols]            */
+    const float* target;         /* device [B][rows][cols]            */
+    const float* non_padding;    /* device [B][cols], or NULL         */
+    const float* t;              /* device [B], or NULL               */
+} dsd_loss_spec;
+int dsd_masked_loss(int32_t device, const dsd_loss_spec* spec, void* workspace, double* out, void* stream);
+
+/* RawCurveAccuracy and RawCurveR2Score in one pass (metrics/curve.py) over n elements, valid where mask != 0 (NULL: all):
+ *   close = count of |fl(pred - target)| <= tolerance (fp32 compare), total = count of valid elements,
+ *   sum_target = sum target, sum_target_sq = sum fl(target * target), sum_residual_sq = sum fl(r * r), r = fl(target - pred) */
+typedef struct dsd_curve_result {
+    int64_t close, total;
+    double sum_target, sum_target_sq, sum_residual_sq;
+} dsd_curve_result;
+int dsd_curve_stats(int32_t device, const float* pred, const float* target, const uint8_t* mask, int64_t n, float tolerance,
+                    void* workspace, dsd_curve_result* out, void* stream);
+
+/* DurationLoss, RhythmCorrectness and PhonemeDurationAccuracy (dur_loss.py:30-56, metrics/duration.py,
+ * tts_modules.py:250-275) on dur_pred, dur_gt [B][L] fp32, ph2word [B][L] int64 (0 = padding; values outside
+ * [0, n_words) belong to no word), n_words = ph2word.max() + 1 >= 2, optional mask [B][L] uint8.
+ *   word sums   p = dur_pred clamped at 0 (NaN kept); wdur_pred[b][w - 1], wdur_gt[b][w - 1], w = 1 .. n_words - 1, are
+ *               the sums of p / dur_gt over the phonemes of word w, added in phoneme order in fp32 - bit for bit torch's
+ *               CPU scatter_add, and the same on every run.  The item sums (sdur) are added the same way over all L.
+ *   losses      per element e(x, y) = g(log((double)fl(x + offset)) - log((double)fl(y + offset))), g(d) = d * d
+ *               (DSD_DUR_MSE) or the Huber function with delta 1 (DSD_DUR_HUBER); pdur over B * L on the UNCLAMPED
+ *               prediction, wdur over B * (n_words - 1) word sums, sdur over B item sums; sums and means as doubles.
+ *               The lambda-weighted total is the caller's.
+ *   rhythm      a word is valid when mask is NULL or any of its phonemes has mask != 0;
+ *               correct = valid and |fl(wdur_pred - wdur_gt)| <= fl(wdur_gt * rhythm_tolerance)
+ *   phonemes    pd = p * (ph2word > 0); align = rint(fl(pd * fl(wdur_gt[w] / max(wdur_pred[w], 1e-5)))) (0 at w = 0);
+ *               accurate = |fl(align - dur_gt)| <= fl(dur_gt * pdur_tolerance) and mask; total = B * L or the mask's count */
+#define DSD_DUR_MSE 0
+#define DSD_DUR_HUBER 1
+typedef struct dsd_dur_spec {
+    int32_t struct_size;
+    int32_t kind;                /* DSD_DUR_*                         */
+    int32_t B, L, n_words;
+    float offset;                /* DurationLoss.offset (log_offset)  */
+    float rhythm_tolerance, pdur_tolerance;
+    const float* dur_pred;       /* device [B][L], raw                */
+    const float* dur_gt;         /* device [B][L]                     */
+    const int64_t* ph2word;      /* device [B][L]                     */
+    const uint8_t* mask;         /* device [B][L], or NULL            */
+} dsd_dur_spec;
+typedef struct dsd_dur_result {
+    double pdur_sum, wdur_sum, sdur_sum;
+    double pdur_mean, wdur_mean, sdur_mean;
+    int64_t rhythm_correct, rhythm_total, pdur_accurate, pdur_total;
+} dsd_dur_result;
+int dsd_dur_score(int32_t device, const dsd_dur_spec* spec, float* wdur_pred, float* wdur_gt, void* workspace,
+                  dsd_dur_result* out, void* stream);
 
 #ifdef __cplusplus
 }
