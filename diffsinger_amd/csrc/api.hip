@@ -1052,22 +1052,11 @@ int build_packed(dsd_handle* h) {
     if (wn) {
         h->g_conv.resize(L);
         h->g_outp.resize(L);
-        h->g_wino.clear();
-        if (C == 256) h->g_wino.resize(L);      // the only width wn_rowsplit.hip runs (narrower networks arrive here padded to it)
         for (int l = 0; l < L; ++l) {
             const std::string p = "residual_layers." + std::to_string(l) + ".";
             const HostTensor* t = &W(h, p + "dilated_conv.weight");    // [2C, C, 3]
             WGet w = [t, C](int r, int k, int tap) { return (double)t->data[((size_t)r * C + k) * 3 + tap]; };
-            h->g_conv[l] = pack_gemm(h, 2 * C, C, 3, C, w, nullptr);
-            if (!h->g_wino.empty()) {
-                // Winograd F(2,3) along time: G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2, formed in double
-                // and rounded once; packed as a 4-"tap" matrix in the same block order (wn_conv_wq_kernel)
-                WGet wG = [w](int r, int k, int i) {
-                    const double g0 = w(r, k, 0), g1 = w(r, k, 1), g2 = w(r, k, 2);
-                    return i == 0 ? g0 : i == 1 ? 0.5 * (g0 + g1 + g2) : i == 2 ? 0.5 * (g0 - g1 + g2) : g2;
-                };
-                h->g_wino[l] = pack_gemm(h, 2 * C, C, 4, C, wG, nullptr);
-            }
+            h->g_conv[l] = pack_gemm(h, 2 * C, C, 3, C, w, nullptr);      // (wn_conv_wq_kernel forms its Winograd operands from it)
             auto b = bias_of(p + "output_projection.bias");
             h->g_outp[l] = pack_gemm(h, 2 * C, C, 1, 0, conv1(p + "output_projection.weight"), &b);
         }
@@ -1781,14 +1770,12 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     };
     // the row-split pair (rows per workgroup: 64 = wn_rowsplit.hip, else wn_rows.hip) on the tiles of `p`; class keys 200 + v / 300 + v
     // The conv's layout is chosen per layer (wn_rowsplit_conv_layout): its Winograd form has a class of its own (250 + v) and
-    // reads the layer's Winograd matrix.  Its FLOPs stay the direct convolution's 3 taps - the work the layer asks for - so the
+    // reads the same packed matrix.  Its FLOPs stay the direct convolution's 3 taps - the work the layer asks for - so the
     // class's rate against the MFMA peak is an EFFECTIVE rate (the kernel issues 4 products per output pair, 2/3 of the MFMAs).
     auto rowsplit = [&](const WnLayerP& p, int l, int bn, int rows, int v, double fr) {
         const int lay = rows > 64 ? 0 : wn_rowsplit_conv_layout(p, B, bn, h->opts.rs_conv_q);
-        WnLayerP pc = p;
-        if (lay == 2) pc.Aconv = h->blob.p + h->g_wino[l].a_off;
         int r = timed_launch(h, (lay == 2 ? 250 : 200) + v, fl_conv * fr, 16.0 * C * fr, "row-split WaveNet layer", [&] {
-            return rows > 64 ? launch_wn_rows(pc, 0, C, B, rows, st) : launch_wn_rowsplit(pc, 0, C, B, bn, lay, st);
+            return rows > 64 ? launch_wn_rows(p, 0, C, B, rows, st) : launch_wn_rowsplit(p, 0, C, B, bn, lay, st);
         });
         if (r) return r;
         return timed_launch(h, 300 + v, fl_out * fr, 20.0 * C * fr, "row-split WaveNet layer", [&] {

@@ -152,8 +152,6 @@ struct dsd_handle {
     DevBuf<float> blob;
     PackedGemm g_inproj, g_emb0, g_emb1, g_dproj, g_cp, g_tail1, g_out;
     std::vector<PackedGemm> g_conv, g_outp;          // WaveNet per layer
-    // ... and the conv once more as the four Winograd F(2,3) matrices G0 .. G3 of wn_conv_wq_kernel (C = 256 only; else empty)
-    std::vector<PackedGemm> g_wino;
     // split-bf16 precision mode (wn_layer_x3.hip): 0 = fp32 (default), 1 = bf16x3 where a kernel exists; the layers' weight
     // streams (float offsets into the blob; empty: not built)
     int precision = 0;

@@ -217,7 +217,7 @@ hipError_t wn_layer_init_all();
 // wn_rowsplit.hip: the same layer as two launches with the 2C rows split over 2C / 64 workgroups per 32-frame tile, for
 // grids too small for full-row tiles.  which = 0: conv + FiLM + gate (xin -> z); 1: out-proj + residual / skip (in place
 // when xout == xin).  layout = wn_rowsplit_conv_layout(p, batch, bn, DSD_RS_CONV_Q): 0 / 1 the direct K-half / K-quarter conv, 2 the
-// K-quarter conv on Winograd F(2,3) operands - p.Aconv is then the layer's Winograd matrix (4 products, api.hip g_wino)
+// K-quarter conv on Winograd F(2,3) operands - p.Aconv stays the layer's direct packed matrix, the kernel forms G1, G2 from its taps
 int wn_rowsplit_conv_layout(const WnLayerP& p, int batch, int bn, int conv_q);
 hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, int layout, hipStream_t st);
 hipError_t wn_rowsplit_init_all();

@@ -472,14 +472,21 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
 // ---------------------------------------------------------------------------------------------------------------
 // Conv, K-quarter layout on WINOGRAD F(2,3) operands (DSD_RS_CONV_Q = 2): the outputs y[t], y[t + d] (d = the dilation) share
 // the inputs x[t - d], x[t], x[t + d], x[t + 2d] and take 4 products instead of 6.  With g0, g1, g2 the tap matrices [2C x C]:
-//   G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2                 (host: p.Aconv, packed with 4 "taps")
+//   G0 = g0, G1 = (g0 + g1 + g2) / 2, G2 = (g0 - g1 + g2) / 2, G3 = g2                 (G1, G2: formed in the walk, below)
 //   D0 = x[t-d] - x[t+d], D1 = x[t] + x[t+d], D2 = x[t+d] - x[t], D3 = x[t] - x[t+2d]  (x = FiLM-added, zero-padded: staging)
 //   m_i = G_i D_i;   y[t] = m0 + m1 + m2,  y[t+d] = m1 - m2 - m3                        (tail)
 // A 32-frame tile is 16 pairs for d = 1, 2, 4, 8 (2d divides 32): pair p = k d + j (j < d) is frame f(p) = 2 d k + j = p + d (p / d) of
 // the tile with its partner at f(p) + d.  The three taps x two 16-frame column blocks of wn_conv_rq_kernel become four products
 // x ONE 16-pair column block: a wave walks 16 steps of 8 MFMAs (128) instead of 12 of 16 (192), with one B-fragment LDS read per
-// two MFMAs as there.  Step order inside a quarter: [32-channel half][product][k16 of the half]; within a step the two row
+// two MFMAs as there.  Step order inside a quarter: [32-channel half][k16 of the half][product]; within a step the two row
 // blocks' accumulators alternate.
+// Weights: the kernel streams the DIRECT packed matrix of wn_conv_rq_kernel ([chunk][tap][k16], 196 KB per workgroup) and walks it
+// by GROUPS of four steps = the four products of one k16 block: a group's operand is its three tap blocks x two row blocks, six
+// 1-KB loads per wave where a four-matrix operand took eight, and 2 G1 = s + g1, 2 G2 = s - g1, s = g0 + g2 are formed in
+// registers in fp32 (12 packed VALU per lane per group, behind the MFMAs of the group's second step; the tail halves m1, m2).
+// Inside a group the products run
+// in the order of what they need: G0 = g0, G3 = g2, then G1, G2; the loads are issued in that order too, one group ahead (a ring
+// of two groups, 48 VGPRs, 2048 MFMA cycles of cover with two waves per SIMD).
 // LDS holds the TRANSFORMED tile [C][4 products x 16 pairs] (row stride 80 = 16 mod 64).  The transform runs in the staging
 // threads from registers: a thread owns (row, 4 consecutive pair columns) and loads the four float4 of x that hold their 16
 // inputs - for d <= 4 the 16 consecutive frames from tile frame 2 p0 - 4 on, for d = 8 the float4 at f(p0) - 8, f(p0), + 8, + 16 -
@@ -490,9 +497,9 @@ __global__ __launch_bounds__(512, 2) void wn_conv_rq_kernel(const WnLayerP p) {
 // the two outputs of a pair into its quarter's tile at their frames; reduction, gate and store are then the direct kernel's.
 // (First version: the four m tiles [64][64] in LDS, transform in the gate threads - twice the transpose writes and three times
 // the reads: tail 3.5 k cycles against the direct kernel's 2.6 k.)
-// Measured: 9.2 -> 8.4 us per launch at the headline.  The walk takes ~790 cycles per step, not the 512 of its
-// MFMAs: the four products stream 262 KB of weights per workgroup (direct: 196 KB) and a step's 16 wave-level weight loads per
-// CU at ~50 cycles each are now what bounds it.
+// Measured: 9.2 -> 8.4 us per launch at the headline on a four-matrix operand (262 KB per workgroup), whose
+// walk took ~790 cycles per step, not the 512 of its MFMAs; every wave-level weight load costs the issuing wave ~130 cycles that
+// no deeper ring hides, so the gain of this walk is its 8 loads fewer per wave minus the forming.
 // ---------------------------------------------------------------------------------------------------------------
 template <int DIL, int RAG>
 __global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
@@ -502,11 +509,14 @@ __global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
     RS_STAMP(0, 6);
     wn_pin_args(p);
     RS_STAMP(0, 7);
-    constexpr int NS = NCH * 16;                    // weight blocks per packed row block: [chunk][product][k16 in chunk]
-    constexpr int NQ = 16;                          // steps per wave (one chunk)
-    constexpr int LW = 5, LB = 6;                   // late rows: written after step LW, barrier after step LB, read from step 8 on
+    constexpr int NS = NCH * 12;                    // weight blocks per packed row block: [chunk][tap][k16 in chunk] (the direct matrix)
+    constexpr int NQ = 16;                          // steps per wave (one chunk): group g = steps 4 g .. 4 g + 3 = k16 block g
+    constexpr int NG = NQ / 4;
+    // late rows: fetched during steps 0 and 1, written after step LW, barrier after step LB.  Groups 0 and 1 (k16 blocks 0, 1) read
+    // channels [0, 32) of the quarter, so step 8 = 4 * (NG / 2) is still the first to read [32, 64) and step 7 fetches its operands
+    constexpr int LW = 5, LB = 6;
     constexpr int CPS = 10;                         // the conditioner projection's two loads: steps CPS and CPS + 1
-    static_assert(LW >= 2 && LW <= LB && LB <= 6 && CPS >= 2 && CPS <= 14, "step 7 fetches step 8's operands");
+    static_assert(LW >= 2 && LW <= LB && LB <= 4 * (NG / 2) - 2 && CPS >= 2 && CPS <= NQ - 2, "step 7 fetches step 8's operands");
     float* xs = lds;                                 // [C][SX]: column 16 i + pair = D_i
     float* et = lds + C * SX;                        // [4 quarters][64][ES]: FiLM vector first, the quarters' accumulators last
 
@@ -543,17 +553,14 @@ __global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
     for (int u = 0; u < 4; ++u) sv[u] = ld4(r_x, row_ts(x_row(0), Ts) + x_c4(u) * 16, 0);
     RS_PIN();
     // this wave's two row blocks: packed blocks 4 mtile + 2 wr (gate rows) and + 1 (filter rows) of the same 16 channels;
-    // local step t of quarter kq = block 16 kq + product * 4 + k16 of either
-    const __amdgpu_buffer_rsrc_t r_w = rsrc(p.Aconv + ((long)(4 * mtile + 2 * wr) * NS + 16 * kq) * 256);
+    // group g of quarter kq = blocks 12 kq + tap * 4 + g of either, the three taps of k16 block g.  The ring holds two whole
+    // groups: group g + 1's six blocks are issued during group g in the order of need g0, g2, g1 (one group of lookahead)
+    const __amdgpu_buffer_rsrc_t r_w = rsrc(p.Aconv + ((long)(4 * mtile + 2 * wr) * NS + 12 * kq) * 256);
     const int wl = lane * 16;
-    auto blk = [](int t) { return ((t % 8) / 2) * 4 + (t / 8) * 2 + (t % 2); };
-    f32x4 W[3][2];
-    auto w_load = [&](int t, int rb) {
-        const int g = blk(t);
-        W[t % 3][rb] = ld4(r_w, wl + (g & 3) * 1024, (g >> 2) * 4096 + rb * NS * 1024);
-    };
-    w_load(0, 0);
-    w_load(0, 1);
+    f32x4 W[2][3][2];                                            // [group parity][tap][row block]
+    auto w_load = [&](int g, int tap, int rb) { W[g % 2][tap][rb] = ld4(r_w, wl + g * 1024, tap * 4096 + rb * NS * 1024); };
+    w_load(0, 0, 0);                                            // only group 0's g0 pair is in the burst before the walk
+    w_load(0, 0, 1);
     RS_PIN();
     // the hoisted conditioner projection (+ biases) of this tile's 32 channels, row-major float4 for the gate below:
     // thread (of the first 256; the others hold a copy) -> channel gcw, frames 4 gc4
@@ -612,30 +619,57 @@ __global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
         for (int i = 0; i < 4; ++i) acc[rb][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* bt = xs + (kq * 64 + lrow) * SX + lcol;
     float bq[2][4];
+    // step t = 4 g + slot: the four products of k16 block g in the order of what they need - G0 = g0, G3 = g2, then G1 and G2,
+    // which the product-3 step forms from the three taps behind its MFMAs, in fp32 as the taps are.  Formed and multiplied
+    // are 2 G1 = s + g1 and 2 G2 = s - g1: a factor 2 is exact in every product and sum, and the output transform halves
+    // m1, m2 once per output (folded into its adds) instead of two packed multiplies per forming: 3 packed VALU per MFMA
+    // pair.  The walk pays for every instruction it issues (timing builds: forming with 16 packed VALU per group 0.30 ms per
+    // 50-NFE loop, with 12 0.20 ms), whatever hides behind the MFMAs in theory.
+    auto prod_of = [](int t) { return (0x2130 >> (4 * (t % 4))) & 3; };
     auto read_b1 = [&](float (&bv)[4], int t, int j) {           // the pair column block of k4 step j of local step t
-        const int i = (t % 8) / 2, k16 = (t / 8) * 2 + (t % 2);
-        bv[j] = bt[(k16 * 16 + j * 4) * SX + 16 * i];
+        bv[j] = bt[((t / 4) * 16 + j * 4) * SX + 16 * prod_of(t)];
     };
 #pragma unroll
     for (int j = 0; j < 4; ++j) read_b1(bq[0], 0, j);
     RS_PIN();
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    f32x4 GF[2][2];                                              // [G1, G2][row block] of the current group
     static_for<0, NQ>([&](auto tc) __attribute__((always_inline)) {
         constexpr int t = decltype(tc)::value;
-        constexpr int i = (t % 8) / 2;
-        const f32x4 wv0 = W[t % 3][0], wv1 = W[t % 3][1];
+        constexpr int g = t / 4, slot = t % 4;
+        constexpr int i = (0x2130 >> (4 * slot)) & 3;
+        constexpr int gp = g % 2;
+        const f32x4(&wv)[2] = *(slot == 0 ? &W[gp][0] : slot == 1 ? &W[gp][2] : &GF[slot & 1]);
+        const f32x4 wv0 = wv[0], wv1 = wv[1];
         float (&bc)[4] = bq[t & 1];
         float (&bn)[4] = bq[(t + 1) & 1];
+        auto form = [&](int rb, int h) {                          // elements 2 h, 2 h + 1 of a row block: packed fp32 VALU
+            const f32x2 s = (h ? W[gp][0][rb].zw : W[gp][0][rb].xy) + (h ? W[gp][2][rb].zw : W[gp][2][rb].xy);
+            const f32x2 g1 = h ? W[gp][1][rb].zw : W[gp][1][rb].xy;
+            const f32x2 a = s + g1, b = s - g1;                   // 2 G1, 2 G2: the halving waits for the output transform
+            if (h) {
+                GF[0][rb].zw = a;
+                GF[1][rb].zw = b;
+            } else {
+                GF[0][rb].xy = a;
+                GF[1][rb].xy = b;
+            }
+        };
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             acc[0][i] = mfma_16x16x4(wv0[j], bc[j], acc[0][i]);
-            if (t == 0) w_load(1 + j / 2, j & 1);                // step 0 issues steps 1 and 2 ...
-            else if (j < 2 && t + 2 < NQ) w_load(t + 2, j);      // ... step t >= 1 issues step t + 2
+            // weight loads, a pair behind the first two MFMAs of a step: step 0 issues its own group's g2 and g1 pairs, steps
+            // 1 .. 3 group 1 (g0, g2, g1), steps 4 g .. 4 g + 2 of group g >= 1 group g + 1
+            if (t == 0) w_load(0, 2 - j / 2, j & 1);
+            else if (g == 0 && j < 2) w_load(1, (0x120 >> (4 * (slot - 1))) & 3, j);
+            else if (g >= 1 && g + 1 < NG && slot < 3 && j < 2) w_load(g + 1, (0x120 >> (4 * slot)) & 3, j);
             if (j == 0 && t + 1 < NQ) {                          // the next step's LDS reads in one burst
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) read_b1(bn, t + 1, jj);
             }
             RS_PIN();
             acc[1][i] = mfma_16x16x4(wv1[j], bc[j], acc[1][i]);
+            if (slot == 1) form(j & 1, j >> 1);
             if (j < 2 && t < 2) svl[(2 * t + j) & 3] = ld4(r_x, row_ts(x_row(1), Ts) + x_c4((2 * t + j) & 3) * 16, 0);
             if (j == 0 && t == CPS) cpg = ld4(r_c, row_ts(gch, Ts) + gc4 * 16, 0);
             if (j == 0 && t == CPS + 1) cpf = ld4(r_c, row_ts(gch + C, Ts) + gc4 * 16, 0);
@@ -664,8 +698,9 @@ __global__ __launch_bounds__(512, 2) void wn_conv_wq_kernel(const WnLayerP p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 float* o = &tk[(rb * 32 + wr * 16 + rq + r) * ES + fc];
-                o[0] = acc[rb][1][r] + (acc[rb][2][r] + acc[rb][0][r]);
-                o[DIL] = acc[rb][1][r] - (acc[rb][2][r] + acc[rb][3][r]);
+                const float m1 = 0.5f * acc[rb][1][r], m2 = 0.5f * acc[rb][2][r];      // the walk multiplied 2 G1, 2 G2
+                o[0] = m1 + (m2 + acc[rb][0][r]);
+                o[DIL] = m1 - (m2 + acc[rb][3][r]);
             }
     }
     __syncthreads();
@@ -866,7 +901,7 @@ static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int layout,
                             "wn_conv_rq_kernel<3, 80, %d, 0>", HL);
     }
     // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two; the Winograd form
-    // of the K-quarter layout 116 KiB.  `layout` = wn_rowsplit_conv_layout's answer (2: p.Aconv is the Winograd matrix).
+    // of the K-quarter layout 116 KiB.  `layout` = wn_rowsplit_conv_layout's answer (every layout reads the same p.Aconv).
     if (layout == 2) {
         if constexpr (SW == 48) {
             const int ldsw = wn_rs_wq_lds_bytes();
@@ -908,8 +943,8 @@ static hipError_t rs_launch_out(const WnLayerP& p, int nwg, int bn, hipStream_t 
 
 static int rs_tiles(const WnLayerP& p, int batch) { return p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b); }
 
-// The conv of a 32-frame-tile launch: 0 = K halves, 1 = K quarters, 2 = K quarters on Winograd operands (the caller then passes
-// the Winograd matrix as p.Aconv).  conv_q = DSD_RS_CONV_Q: 0 / 1 force a direct layout, 2 forces Winograd on every layer that
+// The conv of a 32-frame-tile launch: 0 = K halves, 1 = K quarters, 2 = K quarters on Winograd operands (formed in the
+// kernel from the same p.Aconv).  conv_q = DSD_RS_CONV_Q: 0 / 1 force a direct layout, 2 forces Winograd on every layer that
 // has it (dilation <= 8; a dilation-16 layer keeps the rule's direct kernel), -1: by grid - up to one workgroup per CU the
 // K-quarter layout, kWinogradAuto deciding between its two forms.
 constexpr bool kWinogradAuto = true;
