@@ -12,7 +12,7 @@ namespace dsd {
 
 // ---------------------------------------------------------------------------------------------
 // basis[r][j], r < Rpad, j < Kpad: row 2i = w[j] cos(2 pi k (off + j) / N), row 2i + 1 = -w[j] sin(...), k = k_lo + i, for
-// the taps j < W of the periodic Hann window w[j] = 0.5 - 0.5 cos(2 pi j / W) (torch.hann_window), which torch.stft places
+// the taps j < W of the periodic Hann window w[j] = 0.5 - 0.5 cos(2 pi j / W) (torch.hann_window; [1] at W = 1), which torch.stft places
 // at off = (N - W) / 2 of the N-sample frame; zero elsewhere.  The phase is reduced exactly as the integer k (off + j) mod N
 // before sincospif, so no fp32 angle ever exceeds 2 pi.
 // ---------------------------------------------------------------------------------------------
@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void mel_basis_kernel(float* __restrict__ basi
         const long q = ((long)(k_lo + i) * (long)(off + j)) % N;
         float s, c;
         sincospif(2.f * (float)q / (float)N, &s, &c);
-        const float w = 0.5f - 0.5f * cospif(2.f * (float)j / (float)W);
+        const float w = W > 1 ? 0.5f - 0.5f * cospif(2.f * (float)j / (float)W) : 1.f;      // torch.hann_window(1) = [1.]
         v = (r & 1) ? -(w * s) : w * c;
     }
     basis[idx] = v;
@@ -83,7 +83,9 @@ __global__ __launch_bounds__(256) void mel_project_kernel(const MelProjP p) {
         const int lo = p.range[2 * m], hi = min(p.range[2 * m + 1], p.nb), woff = p.woff[m];
         float s = 0.f;
         for (int k = lo; k < hi; ++k) s = fmaf(p.fw[woff + k - lo], p.mags[(long)k * p.G + g0 + f], s);
-        p.out[(long)b * p.o_sb + (long)m * p.o_sm + (long)t * p.o_st] = logf(fmaxf(s, p.clip));
+        // the logarithm in double, rounded once: the device's logf is up to 2 ulp off (1.9e-6 at log(1e-5), which every
+        // clamped entry holds; 8e-7 of the peak mel, linear, where the peak is ~1e-4), the reference's CPU log within 1
+        p.out[(long)b * p.o_sb + (long)m * p.o_sm + (long)t * p.o_st] = (float)log((double)fmaxf(s, p.clip));
     }
 }
 

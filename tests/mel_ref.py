@@ -49,8 +49,8 @@ def num_frames(n_samples, n_fft, win_size, hop, keyshift=0, speed=1):
     return 1 + (n_samples + pl + pr - n) // h
 
 
-def get_mel(y, cfg, keyshift=0, speed=1, fb=None, linear=False):
-    """y [L] -> [n_mels, T] float64 (natural-log mel; linear=True: before the clamp and log)."""
+def get_mel(y, cfg, keyshift=0, speed=1, fb=None, linear=False, clip=1e-5):
+    """y [L] -> [n_mels, T] float64 (natural-log mel clamped at `clip`; linear=True: before the clamp and log)."""
     n, w, h, pl, pr = geometry(cfg["n_fft"], cfg["win_size"], cfg["hop"], keyshift, speed)
     y = np.asarray(y, dtype=np.float64)
     y = np.pad(y, (max(pl, 0), max(pr, 0)), mode="reflect")
@@ -58,7 +58,8 @@ def get_mel(y, cfg, keyshift=0, speed=1, fb=None, linear=False):
     t = 1 + (len(y) - n) // h
     win = np.zeros(n)
     off = (n - w) // 2
-    win[off: off + w] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(w) / w)
+    # torch.hann_window(w): periodic, and [1.] at w == 1 (where the formula would give 0)
+    win[off: off + w] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(w) / w) if w > 1 else 1.0
     spec = np.empty((n // 2 + 1, t))                              # [bins, T], in pieces of 1024 frames
     for t0 in range(0, t, 1024):
         nt = min(1024, t - t0)
@@ -72,7 +73,7 @@ def get_mel(y, cfg, keyshift=0, speed=1, fb=None, linear=False):
     if fb is None:
         fb = filterbank(cfg["sr"], cfg["n_fft"], cfg["n_mels"], cfg["fmin"], cfg["fmax"])
     mel = fb.astype(np.float64) @ spec
-    return mel if linear else np.log(np.maximum(mel, 1e-5))
+    return mel if linear else np.log(np.maximum(mel, clip))
 
 
 def waveform(seed, n_samples, sr):
