@@ -23,6 +23,8 @@ AUX_CONVNEXT = 2
 DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
 DSD_TRACK_F64, DSD_TRACK_F32, DSD_TRACK_PCM = 0, 1, 2
 DSD_SCORE_WORKSPACE_BYTES = 65536
+DSD_CURVE_MAX, DSD_CURVE_CHUNK = 32, 256
+DSD_CURVE_PLAIN, DSD_CURVE_CLIP, DSD_CURVE_GENDER, DSD_CURVE_PITCH = 0, 1, 2, 3
 DSD_DIFFUSE_DDPM, DSD_DIFFUSE_REFLOW = 0, 1
 LOSS_IDS = {"l1": 0, "l2": 1}                               # DSD_LOSS_*
 DUR_LOSS_IDS = {"mse": 0, "huber": 1}                       # DSD_DUR_*
@@ -43,7 +45,7 @@ EXPORTS = [
     "dsd_rmvpe_decode_at", "dsd_rmvpe_decode_viterbi", "dsd_rmvpe_infer",
     "dsd_hnsep_create", "dsd_hnsep_num_frames", "dsd_hnsep_mask", "dsd_hnsep_separate", "dsd_base_harmonic",
     "dsd_variance_curves",
-    "dsd_length_regulate", "dsd_frame_curve",
+    "dsd_length_regulate", "dsd_frame_curve", "dsd_seconds_to_frames", "dsd_curve_resample",
     "dsd_noise_fill",
     "dsd_ddpm_tables_fill", "dsd_program_build", "dsd_program_free", "dsd_onnx_ddpm_plan",
     "dsd_track_plan", "dsd_track_place", "dsd_track_peak", "dsd_track_export",
@@ -153,6 +155,12 @@ class DsdDurResult(C.Structure):
                [(n, C.c_int64) for n in ("rhythm_correct", "rhythm_total", "pdur_accurate", "pdur_total")]
 
 
+class DsdCurve(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("out", C.c_void_p), ("uv_out", C.c_void_p), ("src_step", C.c_double),
+                ("dst_step", C.c_double), ("n_points", C.c_int32), ("length", C.c_int32), ("pad_to", C.c_int32),
+                ("op", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
 class DsdTerm(C.Structure):
     _fields_ = [("src", C.c_int32), ("coef", C.c_float)]
 
@@ -254,6 +262,8 @@ def _load():
                                         vp, i64, vp]
     lib.dsd_length_regulate.argtypes = [i32, vp, i32, i32, i32, vp, vp]
     lib.dsd_frame_curve.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, C.POINTER(i32), C.POINTER(C.c_float), i32, vp, vp, vp, vp]
+    lib.dsd_seconds_to_frames.argtypes = [C.POINTER(C.c_float), i32, C.c_double, C.POINTER(i64), C.POINTER(i64)]
+    lib.dsd_curve_resample.argtypes = [i32, C.POINTER(DsdCurve), i32, vp]
     lib.dsd_noise_fill.argtypes = [i32, C.POINTER(DsdNoiseSpec), vp, vp]
     lib.dsd_ddpm_tables_fill.argtypes = [i32, i32, C.c_double, C.POINTER(C.c_float)]
     lib.dsd_program_build.argtypes = [C.POINTER(DsdSamplerSpec), C.POINTER(C.POINTER(DsdProgram))]

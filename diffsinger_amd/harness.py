@@ -166,11 +166,17 @@ class SimplePhonemeTable:
 
 
 # ------------------------------------------------------------------------------------------------- speaker mix
-def _mix_track(values, name, param, timestep, length, mode, device):
-    """One speaker's proportion over the `length` tokens / frames: a constant, or a curve given as a string."""
+def _mix_track(values, name, param, timestep, length, mode, device, resampled=None):
+    """One speaker's proportion over the `length` tokens / frames: a constant, or a curve given as a string (`resampled`:
+    that curve already at the frame rate, [1, length] on the device - the library's front end, front.py)."""
     if not isinstance(values, str):
         assert values >= 0., f'Speaker mix checks failed.\nProportion of speaker \'{name}\' is negative.'
         return torch.full((1, length), fill_value=values, dtype=torch.float32, device=device)
+    if resampled is not None:
+        track = resampled
+        assert torch.all(track >= 0.), (f'Speaker mix checks failed.\nProportions of speaker \'{name}\' on some {mode}s '
+                                        f'are negative.')
+        return track
     if mode == 'token':
         items = values.split()
         assert len(items) == length, ('Speaker mix checks failed. In dynamic token-level mix, '
@@ -186,8 +192,10 @@ def _mix_track(values, name, param, timestep, length, mode, device):
 
 
 def load_speaker_mix(param_src: dict, summary_dst: dict, spk_map: Dict[str, int], timestep: float, device,
-                     mix_mode: str = 'frame', mix_length: int = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """-> spk_mix_id [1, 1, N], spk_mix_value [1, T or 1, N] (normalised to sum 1 over the N speakers)."""
+                     mix_mode: str = 'frame', mix_length: int = None,
+                     tracks: Optional[Dict[str, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> spk_mix_id [1, 1, N], spk_mix_value [1, T or 1, N] (normalised to sum 1 over the N speakers).  `tracks`: the
+    frame-level curves of a dynamic mix already resampled by the library ({speaker: [1, T]}, front.py)."""
     assert mix_mode in ('token', 'frame')
     key = 'spk_mix' if mix_mode == 'frame' else 'ph_spk_mix'
     mix = param_src.get(key)
@@ -205,8 +213,8 @@ def load_speaker_mix(param_src: dict, summary_dst: dict, spk_map: Dict[str, int]
         summary_dst[key] = 'static(' + '|'.join(f'{n}:{mix[n]:.3f}' for n in mix) + ')'
     ids = torch.LongTensor([spk_map[n] for n in mix]).to(device)[None, None]
     if dynamic:
-        weights = torch.stack([_mix_track(v, n, param_src, timestep, mix_length, mix_mode, device) for n, v in mix.items()],
-                              dim=2)
+        weights = torch.stack([_mix_track(v, n, param_src, timestep, mix_length, mix_mode, device,
+                                          None if tracks is None else tracks.get(n)) for n, v in mix.items()], dim=2)
         total = weights.sum(dim=2, keepdim=True)
         assert torch.all(total > 0.), 'Speaker mix checks failed.\nProportions of speaker mix on some frames sum to zero.'
     else:
@@ -259,7 +267,9 @@ class AcousticHarness:
                     return 0
                 return self.lang_map[p.split('/', maxsplit=1)[0] if '/' in p else lang]
             batch['languages'] = torch.LongTensor([lang_id(p) for p in phones]).to(self.device)
-        batch['tokens'] = torch.LongTensor([self.phoneme_dictionary.encode(param['ph_seq'], lang=lang)]).to(self.device)
+        ids = self.phoneme_dictionary.encode(param['ph_seq'], lang=lang)
+        batch['tokens'] = torch.LongTensor([ids]).to(self.device)
+        return ids
 
     def _frames(self, param, batch):
         """Phoneme durations in seconds -> integer frame counts by rounding the cumulative boundaries, -> mel2ph."""
@@ -269,26 +279,36 @@ class AcousticHarness:
         batch['mel2ph'] = length_regulator(frames, batch['tokens'] == 0)
         return batch['mel2ph'].size(1)
 
-    def _key_shift(self, param, length):
+    def _key_shift(self, param, length, resampled=None):
         lo, hi = hparams['augmentation_args']['random_pitch_shifting']['range']
         gender = param.get('gender', None)
         gender = 0. if gender is None else gender
         if isinstance(gender, (int, float, bool)):
             value = gender * hi if gender >= 0 else gender * abs(lo)
             return torch.FloatTensor([value]).to(self.device)[:, None], f'static({gender:.3f})'
+        if resampled is not None:       # device_front: the library's DSD_CURVE_GENDER row
+            return resampled, 'dynamic'
         curve = self._curve(param, 'gender', 'gender_timestep', length)
         up = curve >= 0
         shift = curve * (up * hi + (1 - up) * abs(lo))
         return torch.clip(torch.from_numpy(shift.astype(np.float32)).to(self.device)[None], min=lo, max=hi), 'dynamic'
 
-    def _speed(self, param, length):
+    def _speed(self, param, length, resampled=None):
         if param.get('velocity') is None:
             return torch.FloatTensor([1.]).to(self.device)[:, None], 'default'
+        if resampled is not None:       # device_front: the library's DSD_CURVE_CLIP row
+            return resampled, 'manual'
         lo, hi = hparams['augmentation_args']['random_time_stretching']['range']
         curve = self._curve(param, 'velocity', 'velocity_timestep', length)
         return torch.clip(torch.from_numpy(curve.astype(np.float32)).to(self.device)[None], min=lo, max=hi), 'manual'
 
-    def preprocess_input(self, param: dict, idx: int = 0, verbose: bool = False) -> Dict[str, torch.Tensor]:
+    def preprocess_input(self, param: dict, idx: int = 0, verbose: bool = False,
+                         device_front: bool = False) -> Dict[str, torch.Tensor]:
+        """`device_front=True`: the same tensors on the library's front end (front.py) - frame counts from
+        dsd_seconds_to_frames (the reference's CPU result, known on the host: no read-back), mel2ph from dsd_length_regulate,
+        every curve from one dsd_curve_resample launch after ONE upload."""
+        if device_front:
+            return self.preprocess_group([param], idx=idx, verbose=verbose)[0][0]
         batch, summary = {}, {}
         self._tokens(param, batch)
         length = self._frames(param, batch)
@@ -308,6 +328,67 @@ class AcousticHarness:
         if verbose:
             print(f'[{idx}]\t' + ', '.join(f'{k}: {v}' for k, v in summary.items()))
         return batch
+
+    # -- the same on the library's front end (front.py) -------------------------------------------------------------
+    def _front_curves(self, param):
+        """{name: front.CurveSpec} of every curve `preprocess_input` resamples for this segment."""
+        from . import front
+        specs = {'f0': front.CurveSpec(param['f0_seq'], float(param['f0_timestep']))}
+        for name in VARIANCE_NAMES:
+            if name in self.variances_to_embed:
+                specs[name] = front.CurveSpec(param[name], float(param[f'{name}_timestep']))
+        gender = param.get('gender', None)
+        if hparams['use_key_shift_embed'] and gender is not None and not isinstance(gender, (int, float, bool)):
+            lo, hi = hparams['augmentation_args']['random_pitch_shifting']['range']
+            specs['key_shift'] = front.CurveSpec(gender, float(param['gender_timestep']), front.GENDER, lo, hi)
+        if hparams['use_speed_embed'] and param.get('velocity') is not None:
+            lo, hi = hparams['augmentation_args']['random_time_stretching']['range']
+            specs['speed'] = front.CurveSpec(param['velocity'], float(param['velocity_timestep']), front.CLIP, lo, hi)
+        mix = param.get('spk_mix') if hparams['use_spk_id'] else None
+        if mix is not None and len(mix) > 1 and any(isinstance(v, str) for v in mix.values()):
+            for name, values in mix.items():
+                if isinstance(values, str):
+                    specs['spk_mix:' + name] = front.CurveSpec(values, float(param['spk_mix_timestep']))
+        return specs
+
+    def preprocess_group(self, params: List[dict], idx: int = 0, verbose: bool = False):
+        """`preprocess_input(device_front=True)` for one segment or a ragged group: ONE upload, one dsd_length_regulate and
+        one dsd_curve_resample (two past 32 curves) for all of them (front.segment_inputs).  -> (the segments' batches,
+        {key: [B, T_max]} the zero-padded rows those batches' mel2ph / f0 / variance tensors are views of)."""
+        from . import front
+        heads, frames = [], []
+        for param in params:
+            batch = {}
+            ids = self._tokens(param, batch)
+            heads.append(batch)
+            per_token, _ = front.seconds_to_frames(front.parse_curve(param['ph_dur']), self.timestep)
+            frames.append({'ph': per_token * (np.asarray(ids) != 0)})        # a padding token owns no frame
+        lengths = [int(f['ph'].sum()) for f in frames]
+        specs = [self._front_curves(param) for param in params]
+        got = front.segment_inputs(frames, lengths, specs, self.timestep, self.device)
+        rows = {'mel2ph': got['mel2x']['ph'], 'f0': got['curves']['f0'],
+                **{name: got['curves'][name] for name in VARIANCE_NAMES if name in self.variances_to_embed}}
+        for i, (param, batch, spec) in enumerate(zip(params, heads, specs)):
+            length, summary = lengths[i], {}
+            row = lambda name: got['curves'][name][i:i + 1, :length] if name in spec else None     # noqa: E731
+            batch['mel2ph'] = rows['mel2ph'][i:i + 1, :length]
+            summary.update(tokens=batch['tokens'].size(1), frames=length, seconds='%.2f' % (length * self.timestep))
+            if hparams['use_spk_id']:
+                tracks = {name[len('spk_mix:'):]: row(name) for name in spec if name.startswith('spk_mix:')}
+                batch['spk_mix_id'], batch['spk_mix_value'] = load_speaker_mix(
+                    param, summary, self.spk_map, self.timestep, self.device, mix_mode='frame', mix_length=length, tracks=tracks)
+            batch['f0'] = row('f0')
+            for name in VARIANCE_NAMES:
+                if name in self.variances_to_embed:
+                    batch[name] = row(name)
+                    summary[name] = 'manual'
+            if hparams['use_key_shift_embed']:
+                batch['key_shift'], summary['gender'] = self._key_shift(param, length, row('key_shift'))
+            if hparams['use_speed_embed']:
+                batch['speed'], summary['velocity'] = self._speed(param, length, row('speed'))
+            if verbose:
+                print(f'[{idx + i}]\t' + ', '.join(f'{k}: {v}' for k, v in summary.items()))
+        return heads, rows
 
     # -- model, vocoder ---------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -354,13 +435,13 @@ class AcousticHarness:
         d = self.model.diffusion
         return torch.randn(1, d.num_feats, d.out_dims, t_len, device=self.device)
 
-    @torch.no_grad()
-    def forward_model_batch(self, samples, noises, seeds=None):
-        """`forward_model` for several segments at once: inputs zero-padded to the longest, per-segment lengths handed to
-        the library (dsd_set_lengths), so every mel equals the one the segment gives alone.  `noises`: each segment's x_T,
-        or None with `seeds` (one per segment: drawn on the device).  -> list of [1, T_i, M]."""
+    def collate(self, samples, rows=None):
+        """The ragged collate: several segments' batches -> (the model's keyword arguments, inputs zero-padded to the longest;
+        the segments' frame counts).  `rows`: padded [B, T_max] tensors that already exist - `preprocess_group`'s, which the
+        library's front end wrote row by row - taken as they are instead of padding the segments' views of them again."""
+        rows = rows or {}
         lens = [int(s['mel2ph'].size(1)) for s in samples]
-        t_max, n = max(lens), len(samples)
+        t_max = max(lens)
 
         def pad_t(v, t_len):                         # [1, T_i or 1, ...] -> [1, t_max, ...]
             if v.size(1) == 1 and t_len > 1:
@@ -369,7 +450,8 @@ class AcousticHarness:
 
         l_max = max(int(s['tokens'].size(1)) for s in samples)
         cat = lambda key, width: torch.cat([torch.nn.functional.pad(s[key], [0, width - s[key].size(1)]) for s in samples])  # noqa: E731
-        kwargs = {v: torch.cat([pad_t(s[v], t) for s, t in zip(samples, lens)]) for v in self.variances_to_embed}
+        kwargs = {v: rows[v] if v in rows else torch.cat([pad_t(s[v], t) for s, t in zip(samples, lens)])
+                  for v in self.variances_to_embed}
         if hparams['use_spk_id']:
             mixes = []
             for s, t in zip(samples, lens):
@@ -380,13 +462,24 @@ class AcousticHarness:
             kwargs['spk_mix_embed'] = None
         for key in ('key_shift', 'speed'):
             kwargs[key] = torch.cat([pad_t(s[key], t) for s, t in zip(samples, lens)]) if samples[0].get(key) is not None else None
-        languages = cat('languages', l_max) if samples[0].get('languages') is not None else None
+        kwargs['languages'] = cat('languages', l_max) if samples[0].get('languages') is not None else None
+        kwargs['tokens'] = cat('tokens', l_max)
+        kwargs['mel2ph'] = rows['mel2ph'] if 'mel2ph' in rows else cat('mel2ph', t_max)
+        kwargs['f0'] = rows['f0'] if 'f0' in rows else cat('f0', t_max)
+        return kwargs, lens
+
+    @torch.no_grad()
+    def forward_model_batch(self, samples, noises, seeds=None, rows=None):
+        """`forward_model` for several segments at once: inputs zero-padded to the longest (`collate`), per-segment lengths
+        handed to the library (dsd_set_lengths), so every mel equals the one the segment gives alone.  `noises`: each
+        segment's x_T, or None with `seeds` (one per segment: drawn on the device).  -> list of [1, T_i, M]."""
+        kwargs, lens = self.collate(samples, rows)
+        t_max, n = max(lens), len(samples)
         if seeds is not None:
             kwargs['seed'] = list(seeds)
         else:
             kwargs['noise'] = torch.cat([torch.nn.functional.pad(z, [0, t_max - z.size(-1)]) for z in noises])
-        out = self.model(cat('tokens', l_max), languages=languages, mel2ph=cat('mel2ph', t_max), f0=cat('f0', t_max),
-                         infer=True, lengths=lens, **kwargs).diff_out
+        out = self.model(kwargs.pop('tokens'), infer=True, lengths=lens, **kwargs).diff_out
         return [out[i:i + 1, :lens[i]] for i in range(n)]
 
     @torch.no_grad()
@@ -422,7 +515,7 @@ class AcousticHarness:
 
     def run_inference(self, params: List[dict], out_path=None, seed: int = -1, save_mel: bool = False, batch_size: int = 1,
                       out_dir=None, title: Optional[str] = None, num_runs: int = 1, device_noise: bool = False,
-                      device_mix: bool = False):
+                      device_mix: bool = False, device_front: bool = False):
         """One pass over the segments of a project: returns the assembled waveform (or the list of mels) and, when
         `out_path` is given, writes it.  Each segment is placed at its `offset`; where it overlaps what is already
         there the two are cross-faded.  `batch_size` > 1 runs that many segments per launch of the acoustic model as
@@ -439,7 +532,10 @@ class AcousticHarness:
         runs, each segment placed by one launch on the vocoder's stream, in segment order, and copied to the host once at
         the end - the same float64 array, and with `out_path` the same file bytes, as the default path.  A layout numpy
         raises on (a segment that starts before the track, an overlap longer than the new segment) raises ValueError
-        with the library's message before anything runs.  `save_mel` ignores the flag."""
+        with the library's message before anything runs.  `save_mel` ignores the flag.
+        `device_front=True`: the segments' inputs come from the library's front end (`preprocess_input(device_front=True)`;
+        with `batch_size` > 1 a whole group at a time, `preprocess_group`, whose padded rows the ragged batch then takes as
+        they are).  The frame counts are the reference's CPU result whatever device the harness sits on."""
         if out_dir is not None:
             assert title is not None, 'run_inference(out_dir=...) needs a title'
             suffix = '.mel.pt' if save_mel else '.wav'
@@ -447,9 +543,24 @@ class AcousticHarness:
             for run in range(num_runs):
                 name = f'{title}-{str(run).zfill(3)}{suffix}' if num_runs > 1 else title + suffix
                 result = self.run_inference(params, out_path=pathlib.Path(out_dir) / name, seed=seed, save_mel=save_mel,
-                                            batch_size=batch_size, device_noise=device_noise, device_mix=device_mix)
+                                            batch_size=batch_size, device_noise=device_noise, device_mix=device_mix,
+                                            device_front=device_front)
             return result
-        batches = [self.preprocess_input(param, idx=i) for i, param in enumerate(params)]
+        group_rows = {}
+        if device_front and batch_size > 1 and self._batchable():
+            # the frame counts are host arithmetic, so the groups are known before anything is on the device
+            from . import front
+            host_len = [front.seconds_to_frames(front.parse_curve(p['ph_dur']), self.timestep)[1] for p in params]
+            order = sorted(range(len(params)), key=lambda i: -host_len[i])
+            batches = [None] * len(params)
+            for k in range(0, len(order), batch_size):
+                group = order[k:k + batch_size]
+                got, rows = self.preprocess_group([params[i] for i in group], idx=k)
+                group_rows[tuple(group)] = rows
+                for i, b in zip(group, got):
+                    batches[i] = b
+        else:
+            batches = [self.preprocess_input(param, idx=i, device_front=device_front) for i, param in enumerate(params)]
         ready, wavs = {}, {}
         mix = None
         if device_mix and not save_mel:
@@ -465,10 +576,12 @@ class AcousticHarness:
             order = sorted(range(len(params)), key=lambda i: -int(batches[i]['mel2ph'].size(1)))     # similar lengths together
             groups = [order[k:k + batch_size] for k in range(0, len(order), batch_size)]
             for group in groups:
+                rows = group_rows.get(tuple(group))         # device_front: the group as the front end padded it
                 if seeds is None:
-                    mels_g = self.forward_model_batch([batches[i] for i in group], [noises[i] for i in group])
+                    mels_g = self.forward_model_batch([batches[i] for i in group], [noises[i] for i in group], rows=rows)
                 else:
-                    mels_g = self.forward_model_batch([batches[i] for i in group], None, seeds=[seeds[i] for i in group])
+                    mels_g = self.forward_model_batch([batches[i] for i in group], None, seeds=[seeds[i] for i in group],
+                                                      rows=rows)
                 ready.update(zip(group, mels_g))
             if not save_mel and seeds is not None:
                 for group in groups:

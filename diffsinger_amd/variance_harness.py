@@ -98,7 +98,7 @@ class VarianceHarness(AcousticHarness):
         return F.conv1d(padded, self.smooth_kernel[None, None])[:, 0]
 
     # -- one segment -> model inputs --------------------------------------------------------------------------
-    def _notes(self, param, batch):
+    def _notes(self, param, batch, pre=None):
         midi = np.array([note_to_midi(n) if n != 'rest' else -1 for n in param['note_seq'].split()], dtype=np.float32)
         rest = midi < 0
         if rest.all():
@@ -109,9 +109,12 @@ class VarianceHarness(AcousticHarness):
             midi[rest] = nearest(np.where(rest)[0])
         batch['note_midi'] = torch.from_numpy(midi).to(self.device)[None]
         batch['note_rest'] = torch.from_numpy(rest).to(self.device)[None]
-        seconds = torch.from_numpy(np.array([param['note_dur'].split()], np.float32)).to(self.device)
-        batch['note_dur'] = _seconds_to_frames(seconds, self.timestep)
-        batch['mel2note'] = length_regulator(batch['note_dur'])
+        if pre is not None:             # device_front: the library's frame counts and dsd_length_regulate
+            batch['note_dur'], batch['mel2note'] = pre['note_dur'], pre['mel2note']
+        else:
+            seconds = torch.from_numpy(np.array([param['note_dur'].split()], np.float32)).to(self.device)
+            batch['note_dur'] = _seconds_to_frames(seconds, self.timestep)
+            batch['mel2note'] = length_regulator(batch['note_dur'])
         n_notes = midi.shape[0]
         if hparams.get('use_glide_embed', False) and param.get('note_glide') is not None:
             batch['note_glide'] = torch.LongTensor([[self.glide_map.get(x, 0) for x in param['note_glide'].split()]]).to(self.device)
@@ -125,30 +128,76 @@ class VarianceHarness(AcousticHarness):
         size = torch.gather(F.pad(group_frames, [1, 0], value=1), 1, frame2group)
         return curve.new_zeros(1, n_groups + 1).scatter_add(1, frame2group, curve / size)[:, 1:]
 
+    def _wants_expr_curve(self, param, load_pitch):
+        return (self.model.predict_pitch and not load_pitch and (self.auto_completion_mode or self.global_predict_pitch)
+                and not isinstance(param.get('expr', 1.), (int, float, bool)))
+
+    def _front(self, param, ids, load_dur, load_pitch):
+        """device_front: the durations and curves of one segment on the library's front end (front.py).  The frame counts
+        are host arithmetic (dsd_seconds_to_frames), so the frame count and the alignment of the phones to the notes are
+        known before anything is on the device; then ONE upload, a dsd_length_regulate per duration and one
+        dsd_curve_resample (two launches with the `load_pitch` curve) for everything."""
+        from . import front
+        note_frames, n_frames = front.seconds_to_frames(front.parse_curve(param['note_dur']), self.timestep)
+        frames = {'note': note_frames}
+        if load_dur:
+            ph_frames, _ = front.seconds_to_frames(front.parse_curve(param['ph_dur']), self.timestep)
+            ph_frames = ph_frames * (np.asarray(ids) != 0)
+            total = int(ph_frames.sum())
+            if total < n_frames:        # the last phone with frames takes the rest (mel2ph padded with its last value)
+                ph_frames[np.flatnonzero(ph_frames)[-1]] += n_frames - total
+            elif total > n_frames:      # ... or the phones are cut where the notes end
+                ph_frames = np.diff(np.minimum(np.cumsum(ph_frames), n_frames), prepend=0)
+            frames['ph'] = ph_frames
+        specs = {}
+        if load_pitch:
+            specs['pitch'] = front.CurveSpec(param['f0_seq'], float(param['f0_timestep']), front.PITCH)
+        if self._wants_expr_curve(param, load_pitch):
+            specs['expr'] = front.CurveSpec(param['expr'], float(param['expr_timestep']))
+        mix = param.get('spk_mix') if hparams['use_spk_id'] else None
+        if mix is not None and len(mix) > 1 and any(isinstance(v, str) for v in mix.values()):
+            for name, values in mix.items():
+                if isinstance(values, str):
+                    specs['spk_mix:' + name] = front.CurveSpec(values, float(param['spk_mix_timestep']))
+        got = front.segment_inputs([frames], [n_frames], [specs], self.timestep, self.device)
+        pre = dict(note_dur=got['dur']['note'], mel2note=got['mel2x']['note'], curves=got['curves'])
+        if load_dur:
+            pre.update(ph_dur=got['dur']['ph'], mel2ph=got['mel2x']['ph'])
+        return pre
+
     def preprocess_input(self, param: dict, idx: int = 0, load_dur: bool = False, load_pitch: bool = False,
-                         verbose: bool = False) -> Dict[str, torch.Tensor]:
+                         verbose: bool = False, device_front: bool = False) -> Dict[str, torch.Tensor]:
+        """`device_front=True`: note and phone durations, the frame count, `mel2note` / `mel2ph` and every resampled curve
+        (the `load_pitch` f0 with its unvoiced frames filled, `expr`, a dynamic frame-level speaker mix) come from the
+        library's front end (`_front`); the token / word / note index algebra stays in torch.  `pitch` is then within a few
+        fp32 roundings of the default's, everything else equal to it."""
         batch, summary = {}, {}
-        self._tokens(param, batch)
+        ids = self._tokens(param, batch)
+        pre = self._front(param, ids, load_dur, load_pitch) if device_front else None
         tokens = batch['tokens']
         n_ph = tokens.shape[1]
         ph_num = torch.from_numpy(np.array([param['ph_num'].split()], np.int64)).to(self.device)
         ph2word = batch['ph2word'] = length_regulator(ph_num)
         n_word = int(ph2word.max())
-        n_notes, n_frames = self._notes(param, batch)
+        n_notes, n_frames = self._notes(param, batch, pre)
         note_dur = batch['note_dur']
         summary.update(words=n_word, notes=n_notes, tokens=n_ph, frames=n_frames, seconds='%.2f' % (n_frames * self.timestep))
         if hparams['use_spk_id']:
             batch['ph_spk_mix_id'], batch['ph_spk_mix_value'] = load_speaker_mix(
                 param, summary, self.spk_map, self.timestep, self.device, mix_mode='token', mix_length=n_ph)
+            tracks = None if pre is None else {k[len('spk_mix:'):]: v for k, v in pre['curves'].items() if k.startswith('spk_mix:')}
             batch['spk_mix_id'], batch['spk_mix_value'] = load_speaker_mix(
-                param, summary, self.spk_map, self.timestep, self.device, mix_mode='frame', mix_length=n_frames)
+                param, summary, self.spk_map, self.timestep, self.device, mix_mode='frame', mix_length=n_frames, tracks=tracks)
         if load_dur:                                # phoneme durations come with the segment
-            seconds = torch.from_numpy(np.array([param['ph_dur'].split()], np.float32)).to(self.device)
-            ph_dur = _seconds_to_frames(seconds, self.timestep)
-            mel2ph = length_regulator(ph_dur, tokens == 0)
-            if mel2ph.shape[1] != n_frames:         # align the phones with the notes: the last phone takes the rest
-                mel2ph = F.pad(mel2ph, [0, n_frames - mel2ph.shape[1]], value=mel2ph[0, -1])
-                ph_dur = mel2ph_to_dur(mel2ph, n_ph)
+            if pre is not None:                     # device_front: aligned with the notes on the host (_front)
+                ph_dur, mel2ph = pre['ph_dur'], pre['mel2ph']
+            else:
+                seconds = torch.from_numpy(np.array([param['ph_dur'].split()], np.float32)).to(self.device)
+                ph_dur = _seconds_to_frames(seconds, self.timestep)
+                mel2ph = length_regulator(ph_dur, tokens == 0)
+                if mel2ph.shape[1] != n_frames:     # align the phones with the notes: the last phone takes the rest
+                    mel2ph = F.pad(mel2ph, [0, n_frames - mel2ph.shape[1]], value=mel2ph[0, -1])
+                    ph_dur = mel2ph_to_dur(mel2ph, n_ph)
             word_dur = note_dur.new_zeros(1, n_word + 1).scatter_add(1, ph2word, ph_dur)[:, 1:]
         else:                                       # word durations from the notes: a slur continues the word
             ph_dur = mel2ph = None
@@ -169,7 +218,9 @@ class VarianceHarness(AcousticHarness):
         else:
             ph_midi = torch.gather(F.pad(self._per_group_mean(frame_midi, mel2word, word_dur, n_word), [1, 0]), 1, ph2word)
         batch['midi'] = ph_midi.round().long()
-        if load_pitch:
+        if load_pitch and pre is not None:
+            batch['pitch'] = pre['curves']['pitch']
+        elif load_pitch:
             f0 = self._curve(param, 'f0_seq', 'f0_timestep', n_frames)
             batch['pitch'] = torch.from_numpy(hz_to_midi(interp_f0(f0)[0]).astype(np.float32)).to(self.device)[None]
         if self.model.predict_dur:
@@ -185,8 +236,11 @@ class VarianceHarness(AcousticHarness):
                     batch['expr'] = torch.FloatTensor([expr]).to(self.device)[:, None]
                 else:
                     summary['expr'] = 'dynamic'
-                    curve = self._curve(param, 'expr', 'expr_timestep', n_frames)
-                    batch['expr'] = torch.from_numpy(curve.astype(np.float32)).to(self.device)[None]
+                    if pre is not None:
+                        batch['expr'] = pre['curves']['expr']
+                    else:
+                        curve = self._curve(param, 'expr', 'expr_timestep', n_frames)
+                        batch['expr'] = torch.from_numpy(curve.astype(np.float32)).to(self.device)[None]
             else:
                 summary['pitch'] = 'ignored'
         if self.model.predict_variances:
@@ -316,15 +370,17 @@ class VarianceHarness(AcousticHarness):
             m.fs2.predict_dur, m.predict_pitch, m.predict_variances = saved
 
     def run_inference(self, params: List[dict], out_dir=None, title: str = None, num_runs: int = 1, seed: int = -1,
-                      batch_size: int = 1, device_noise: bool = False):
+                      batch_size: int = 1, device_noise: bool = False, device_front: bool = False):
         """-> the completed projects (one list of segments per run); written to `out_dir/title[-NNN].ds` when given.
         `device_noise=True`: the x_T of both loops are drawn on the device from the segment's own seed (its 'seed' entry,
         else `seed`, else a fresh draw; noise.PITCH_X_T / noise.VARIANCE_X_T), torch's generators are not reseeded, and a
         segment's curves are the same at any `batch_size`.
         `batch_size` > 1: segments on which the same predictors run on the same kinds of inputs share a launch as a ragged
-        batch (same predictions as one by one, which is the reference's order and the default)."""
+        batch (same predictions as one by one, which is the reference's order and the default).
+        `device_front=True`: the segments' durations and curves go through the library's front end (`preprocess_input`)."""
         flags = [self._flags(p) for p in params]
-        batches = [self.preprocess_input(p, idx=i, load_dur=not f[0] and (f[1] or f[2]), load_pitch=not f[1] and f[2])
+        batches = [self.preprocess_input(p, idx=i, load_dur=not f[0] and (f[1] or f[2]), load_pitch=not f[1] and f[2],
+                                         device_front=device_front)
                    for i, (p, f) in enumerate(zip(params, flags))]
         runs = []
         for run in range(num_runs):

@@ -4,6 +4,7 @@ library only (no DiffSinger checkout needed at run time).
 
     python examples/ds_to_wav.py checkpoints/my_exp song.ds nsf_hifigan/model.ckpt -o song.wav [--steps 20] [--depth 0.6]
                                  [--batch-size 8] [--seed 42] [--precision bf16x3] [--device-mix]
+                                 [--device-front]
 
 checkpoints/my_exp holds what a training run leaves there: config.yaml, model_ckpt_steps_<N>.ckpt, dictionary-<lang>.txt
 (or dictionary.txt), and - for multi-speaker / multilingual models - spk_map.json / lang_map.json.
@@ -34,6 +35,8 @@ def main():
                     help="arithmetic of the denoiser's and the vocoder's residual layers (set_precision); default: fp32")
     ap.add_argument("--device-mix", action="store_true",
                     help="assemble the track on the GPU (place, cross-fade, int16): one copy to the host at the end")
+    ap.add_argument("--device-front", action="store_true",
+                    help="durations to frames and every control curve through the library (one upload, one launch per group)")
     args = ap.parse_args()
 
     load_config(args.exp / "config.yaml", overrides=dict(infer=True, work_dir=str(args.exp)))
@@ -59,7 +62,7 @@ def main():
         for seg in params:
             seg["spk_mix"] = mix
     track = h.run_inference(params, out_path=out, seed=args.seed, batch_size=args.batch_size,
-                            device_mix=args.device_mix)
+                            device_mix=args.device_mix, device_front=args.device_front)
     print(f"| wrote {out}: {track.shape[0] / hparams['audio_sample_rate']:.2f} s")
 
 

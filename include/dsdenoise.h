@@ -353,6 +353,71 @@ int dsd_frame_curve(int32_t device, const float* note_midi, const int64_t* mel2n
                     int32_t K, float* base_out, float* blend_out, float* delta_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The segment front end: what stands between a `.ds` segment's text fields and the calls above.  Handle-free.
+ * ------------------------------------------------------------------------------------------ */
+/*
+ * Replaces: ph_acc = round(cumsum(ph_dur) / timestep + 0.5); durations = diff(ph_acc, prepend 0)
+ * (inference/ds_acoustic.py:102-104, inference/ds_variance.py:151,179), as torch evaluates it ON THE CPU, on any host:
+ *   acc      a double running sum of the fp32 inputs (torch's CPU cumsum accumulates fp32 in double)
+ *   c_i      = (float)acc
+ *   b_i      = rintf(c_i / (float)timestep + 0.5f)      an fp32 divide, half to even
+ *   frames_i = b_i - b_{i-1}, b_{-1} = 0;  *total_out = b_{n-1}
+ * Host arithmetic only: no device is touched, so the caller knows the frame count T of a segment without a read-back.
+ *   seconds     HOST array of n durations, each finite and >= 0
+ *   frames_out  HOST array of n frame counts (a zero duration may give 0)
+ * DSD_EINVAL for a NULL pointer, n < 1, a timestep that is not finite or not positive, an input that is not finite or is
+ * negative, or a boundary that does not fit int32 frames.
+ */
+int dsd_seconds_to_frames(const float* seconds, int32_t n, double timestep, int64_t* frames_out, int64_t* total_out);
+/*
+ * Replaces: resample_align_curve (utils/infer_utils.py:41-53) and what the inference front ends do to its result, for up
+ * to DSD_CURVE_MAX curves in one launch (two when a DSD_CURVE_PITCH curve is among them).  The descriptors are a HOST
+ * array that travels in the launch arguments: no device memory is allocated, nothing is synchronised, and the call can
+ * be captured into a hipGraph.
+ *
+ * Resampling, bit for bit numpy's (np.interp over original_timestep * arange(n) at arange(0, (n - 1) * original_timestep,
+ * target_timestep)), all in IEEE double without contraction:
+ *   count = ceil(((n_points - 1) * src_step) / dst_step)
+ *   frame k < min(count, length):  x = k * dst_step;  j = the largest index with src_step * j <= x
+ *       j >= n_points - 1     -> p[n_points - 1]
+ *       src_step * j == x     -> p[j]
+ *       otherwise             -> ((p[j + 1] - p[j]) / (src_step * (j + 1) - src_step * j)) * (x - src_step * j) + p[j]
+ *     rounded to fp32;  frames count .. length hold the last computed value;  out[length .. pad_to) = 0
+ * then, on the fp32 value v:
+ *   DSD_CURVE_PLAIN    nothing
+ *   DSD_CURVE_CLIP     min(max(v, lo), hi)                                      velocity (ds_acoustic.py:169-176)
+ *   DSD_CURVE_GENDER   v * (v >= 0 ? hi : |lo|) in double, rounded to fp32, then clipped to [lo, hi]: the key shift of a
+ *                      gender curve (ds_acoustic.py:154-159), lo <= 0 <= hi the model's key-shift range
+ *   DSD_CURVE_PITCH    an f0 curve in Hz to MIDI pitch with the unvoiced frames filled (ds_variance.py:244-249 through
+ *                      interp_f0, utils/pitch_utils.py:13-20, and librosa's hz_to_midi): uv = (v == 0); an unvoiced frame
+ *                      takes the linear interpolation of log2 f0 between the nearest voiced frames on either side, the
+ *                      nearest voiced value at the ends, -inf when no frame is voiced; out = 12 * (log2 f - log2 440) + 69.
+ *                      Evaluated in double, rounded to fp32 where the host path stores fp32 (log2 f0 and the filled f0) and
+ *                      at the output: within a few fp32 roundings of the host path, not bit-equal to it.  uv_out (bytes,
+ *                      1 = unvoiced) is written when given; out[length .. pad_to) = 0 and uv_out there = 0.
+ * The points are finite by the caller's contract; they are not read back.  DSD_EINVAL before the device is touched, the
+ * message naming the curve and the field: a NULL curves, n_curves outside [1, DSD_CURVE_MAX], a NULL points or out,
+ * n_points < 2 (the reference itself fails on one point), length < 1, pad_to < length, a step that is not finite or not
+ * positive, an unknown op, CLIP bounds with lo > hi or a NaN, a GENDER range without lo <= 0 <= hi, a uv_out on a curve
+ * that is not DSD_CURVE_PITCH.
+ */
+#define DSD_CURVE_MAX 32
+#define DSD_CURVE_CHUNK 256     /* frames a workgroup takes at a time (a PITCH curve's fill carries across them) */
+enum { DSD_CURVE_PLAIN = 0, DSD_CURVE_CLIP = 1, DSD_CURVE_GENDER = 2, DSD_CURVE_PITCH = 3 };
+typedef struct dsd_curve {
+    const float* points;        /* device, n_points fp32, finite */
+    float* out;                 /* device, pad_to floats */
+    uint8_t* uv_out;            /* DSD_CURVE_PITCH: device, pad_to bytes, or NULL */
+    double src_step, dst_step;  /* seconds, > 0 */
+    int32_t n_points;           /* >= 2 */
+    int32_t length;             /* align_length, >= 1 */
+    int32_t pad_to;             /* >= length: the row of a zero-padded batch */
+    int32_t op;                 /* DSD_CURVE_* */
+    float lo, hi;               /* CLIP: bounds; GENDER: the key-shift range */
+} dsd_curve;
+int dsd_curve_resample(int32_t device, const dsd_curve* curves, int32_t n_curves, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Seeded draws on the device: the x_T and step noise of the samplers, the vocoder's phases and noise.  Handle-free:
  * `device` is the HIP device index.  Element (row, col) of a draw is a pure function of (seed, domain, stream, row, col):
  * it does not depend on B, on padding, on the launch shape or on what the process drew before, so a ragged batch draws
