@@ -1060,6 +1060,43 @@ int build_packed(dsd_handle* h) {
             auto b = bias_of(p + "output_projection.bias");
             h->g_outp[l] = pack_gemm(h, 2 * C, C, 1, 0, conv1(p + "output_projection.weight"), &b);
         }
+        // fp32 mode: the out-proj of every layer once more, with the skip projection folded into its skip rows.  wavenet.py:96-98
+        // computes  h = relu(W1 (sum_l (Ws_l z_l + bs_l)) / sqrt(L) + b1)  with weights only around the sum, so
+        //   h = relu(sum_l (V_l z_l + c_l)),   V_l = W1 Ws_l / sqrt(L),   c_l = W1 bs_l / sqrt(L)  (+ b1 on layer 0, once)
+        // and a layer that accumulates V_l z_l + c_l into the running skip rows leaves relu's argument there: the C x C
+        // skip-projection GEMM of every evaluation is gone (run_wavenet).  Products and the 1 / sqrt(L) in double, rounded to fp32
+        // once.  Formed from the zero-extended tensors where C is not a multiple of 32: the extra terms are exact zeros, so this
+        // IS the caller's true-width product, zero-extended.  The unfolded pack above stays: the edge kernel (wn_edge.hip)
+        // applies W1 itself, and the split-bf16 streams are built from the caller's matrices.
+        h->g_outf.clear();
+        if (h->precision == 0) {
+            h->g_outf.resize(L);
+            const HostTensor* w1 = &W(h, "skip_projection.weight");     // [C, C, 1]
+            const HostTensor* b1 = &W(h, "skip_projection.bias");
+            const double inv = 1.0 / sqrt((double)L);
+            std::vector<double> v((size_t)C * C), cb(C);
+            for (int l = 0; l < L; ++l) {
+                const std::string p = "residual_layers." + std::to_string(l) + ".";
+                const HostTensor* wo = &W(h, p + "output_projection.weight");    // [2C, C, 1]: residual | skip rows
+                const HostTensor* bo = &W(h, p + "output_projection.bias");
+                std::fill(v.begin(), v.end(), 0.0);
+                for (int r = 0; r < C; ++r) {
+                    double* vr = v.data() + (size_t)r * C;
+                    double s = 0.0;
+                    for (int j = 0; j < C; ++j) {
+                        const double a = (double)w1->data[(size_t)r * C + j];
+                        const float* ws = wo->data.data() + (size_t)(C + j) * C;
+                        for (int k = 0; k < C; ++k) vr[k] += a * (double)ws[k];
+                        s += a * (double)bo->data[C + j];
+                    }
+                    for (int k = 0; k < C; ++k) vr[k] *= inv;
+                    cb[r] = s * inv + (l == 0 ? (double)b1->data[r] : 0.0);
+                }
+                WGet wf = [wo, &v, C](int r, int k, int) { return r < C ? (double)wo->data[(size_t)r * C + k] : v[(size_t)(r - C) * C + k]; };
+                std::function<double(int)> bf = [bo, &cb, C](int i) { return i < C ? (double)bo->data[i] : cb[i - C]; };
+                h->g_outf[l] = pack_gemm(h, 2 * C, C, 1, 0, wf, &bf);
+            }
+        }
         // split-bf16 mode: the same two matrices of every layer once more, split hi / lo, as wn_layer_x3.hip's streams
         h->x3_conv.clear();
         h->x3_out.clear();
@@ -1737,6 +1774,45 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     const long xs = (long)C * Ts, cps = (long)L * 2 * C * Ts;
     const bool ragged = !h->lens_host.empty();
     int rc;
+    // What follows the layers is decided before they run: the edge kernel (wn_edge.hip, one workgroup per 32-frame tile) where the
+    // plan has it and the sampler's terms fit it, else the GEMMs of gemm.hip - and only an evaluation that ends in those runs its
+    // layers on the folded out-proj pack (build_packed), since the edge kernel applies the skip projection itself
+    WnEdgeP ep;
+    bool edge = false;
+    int edge_nwg = 0;
+    if (pl.edge && nout >= 1 && nout <= kMaxOut) {
+        const int bnw = 32;
+        WnEdgeP& p = ep;
+        memset(&p, 0, sizeof(p));
+        p.A1 = h->blob.p + h->g_tail1.a_off; p.b1 = h->blob.p + h->g_tail1.bias_off;
+        p.A2 = h->blob.p + h->g_out.a_off; p.b2 = h->blob.p + h->g_out.bias_off;
+        p.A3 = h->blob.p + h->g_inproj.a_off; p.b3 = h->blob.p + h->g_inproj.bias_off;
+        p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
+        p.in_scale = sqrtf((float)L);
+        p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        p.nout = nout;
+        edge = true;
+        for (int i = 0; i < nout; ++i) {
+            p.dst[i] = lo[i].dst;
+            for (int k = 0; k < lo[i].nterms; ++k) {
+                const LinTerm& tm = lo[i].t[k];
+                if (tm.ptr == nullptr) { p.cm[i] += tm.coef; continue; }
+                // (more state terms than the kernel holds at once, caller-noise terms: the GEMM path)
+                if (p.nq == kEdgeMaxTerms || tm.ext) { edge = false; break; }
+                EdgeTerm& q = p.q[p.nq++];
+                q.ptr = tm.ptr; q.bstride = tm.bstride; q.rstride = tm.rstride; q.ext = tm.ext; q.coef = tm.coef; q.out = i;
+            }
+        }
+        p.o_bstride = (long)FM * Ts; p.o_rstride = Ts;
+        p.next_src = -1;
+        if (next_xin)
+            for (int i = 0; i < nout; ++i)
+                if (lo[i].dst == next_xin) p.next_src = i;
+        edge_nwg = B * p.tiles_per_b;
+        if (ragged) { p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; edge_nwg = p.ncg; }
+    }
+    const bool folded = !edge && !h->g_outf.empty();
+    const std::vector<PackedGemm>& outp = folded ? h->g_outf : h->g_outp;
     // algorithmic work of the layer kernels per VALID frame: conv 3*C*2C MACs, out-proj C*2C;
     // bytes: the conv launch reads x and the hoisted conditioner projection and writes z (16 C), the out-proj launch
     // reads z, updates x and the skip sum (20 C); fused: x r/w, conditioner projection, skip r/w (24 C)
@@ -1758,8 +1834,8 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     auto layer_params = [&](WnLayerP& p, int l, int bn) {
         memset(&p, 0, sizeof(p));
         p.Aconv = h->blob.p + h->g_conv[l].a_off;
-        p.Aout = h->blob.p + h->g_outp[l].a_off;
-        p.bias_out = h->blob.p + h->g_outp[l].bias_off;
+        p.Aout = h->blob.p + outp[l].a_off;
+        p.bias_out = h->blob.p + outp[l].bias_off;
         p.skip = h->skip;
         p.x_bstride = xs; p.Ts = Ts;
         p.cp = h->cp + (long)l * 2 * C * Ts; p.cp_bstride = cps;
@@ -1834,57 +1910,30 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             g.p.out = h->z; g.p.o_bstride = xs; g.p.o_rstride = Ts;
             if ((rc = timed_launch(h, 400 + (dil > 8 ? 2 : 0), fl_conv * fr_all, 16.0 * C * fr_all, "WaveNet conv GEMM", [&] { return run_gemm(h, g, st); })))
                 return rc;
-            GemmCall o = make_gemm(h, h->g_outp[l], h->z, xs, Ts, B, T, ST_PLAIN, EP_RESSKIP, 0);
+            GemmCall o = make_gemm(h, outp[l], h->z, xs, Ts, B, T, ST_PLAIN, EP_RESSKIP, 0);
             o.p.C = C; o.p.x = h->xh; o.p.skip = h->skip; o.p.first_layer = (l == 0);
             o.p.o_bstride = xs; o.p.o_rstride = Ts;
             if ((rc = timed_launch(h, 500, fl_out * fr_all, 20.0 * C * fr_all, "WaveNet out-proj GEMM", [&] { return run_gemm(h, o, st); }))) return rc;
         }
     }
-    if (pl.edge && nout >= 1 && nout <= kMaxOut) {      // the edge kernel (wn_edge.hip), one workgroup per 32-frame tile
-        const int ncb = 2;
-        const int bnw = 16 * ncb;
-        WnEdgeP p;
-        memset(&p, 0, sizeof(p));
-        p.A1 = h->blob.p + h->g_tail1.a_off; p.b1 = h->blob.p + h->g_tail1.bias_off;
-        p.A2 = h->blob.p + h->g_out.a_off; p.b2 = h->blob.p + h->g_out.bias_off;
-        p.A3 = h->blob.p + h->g_inproj.a_off; p.b3 = h->blob.p + h->g_inproj.bias_off;
-        p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
-        p.in_scale = sqrtf((float)L);
-        p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-        p.nout = nout;
-        bool fits = true;
-        for (int i = 0; i < nout; ++i) {
-            p.dst[i] = lo[i].dst;
-            for (int k = 0; k < lo[i].nterms; ++k) {
-                const LinTerm& tm = lo[i].t[k];
-                if (tm.ptr == nullptr) { p.cm[i] += tm.coef; continue; }
-                if (p.nq == kEdgeMaxTerms || tm.ext) { fits = false; break; }      // (caller-noise terms: the GEMM path)
-                EdgeTerm& q = p.q[p.nq++];
-                q.ptr = tm.ptr; q.bstride = tm.bstride; q.rstride = tm.rstride; q.ext = tm.ext; q.coef = tm.coef; q.out = i;
-            }
-        }
-        p.o_bstride = (long)FM * Ts; p.o_rstride = Ts;
-        p.next_src = -1;
-        if (next_xin)
-            for (int i = 0; i < nout; ++i)
-                if (lo[i].dst == next_xin) p.next_src = i;
-        int nwg = B * p.tiles_per_b;
-        if (ragged) { p.cgmap = h->cg_dev[ncb == 2 ? 1 : 0].p; p.ncg = h->cg_n[ncb == 2 ? 1 : 0]; nwg = p.ncg; }
-        if (fits) {      // (more state terms than the kernel holds at once: the three GEMMs below)
-            double fr_all = (double)B * T;
-            if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
-            if ((rc = timed_launch(h, 700, 2.0 * (C * C + 2.0 * C * FM) * fr_all, 4.0 * (2 * C + 3 * FM) * fr_all, "WaveNet edge-kernel",
-                                   [&] { return launch_wn_edge(p, C, ncb, nwg, st); })))
-                return rc;
-            if (p.next_src >= 0) h->edge_xh_src = next_xin;
-            return DSD_OK;
-        }
+    if (edge) {
+        double fr_all = (double)B * T;
+        if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
+        if ((rc = timed_launch(h, 700, 2.0 * (C * C + 2.0 * C * FM) * fr_all, 4.0 * (2 * C + 3 * FM) * fr_all, "WaveNet edge-kernel",
+                               [&] { return launch_wn_edge(ep, C, 2, edge_nwg, st); })))
+            return rc;
+        if (ep.next_src >= 0) h->edge_xh_src = next_xin;
+        return DSD_OK;
     }
-    GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, ST_SCALE, EP_BIAS_ACT, 0);
-    t1.p.in_scale = sqrtf((float)L);      // staged value is DIVIDED by in_scale (wavenet.py:96)
-    t1.p.act = ACT_RELU; t1.p.out = h->hbuf; t1.p.o_bstride = xs; t1.p.o_rstride = Ts;
-    if ((rc = run_gemm(h, t1, st))) return rc;
-    GemmCall t2 = make_gemm(h, h->g_out, h->hbuf, xs, Ts, B, T, ST_PLAIN, EP_LINCOMB, 0);
+    // the GEMMs of gemm.hip.  Folded layers left relu's argument in the skip rows: the output projection stages max(skip, 0)
+    // itself (ST_RELU) and hbuf is not written
+    if (!folded) {
+        GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, ST_SCALE, EP_BIAS_ACT, 0);
+        t1.p.in_scale = sqrtf((float)L);      // staged value is DIVIDED by in_scale (wavenet.py:96)
+        t1.p.act = ACT_RELU; t1.p.out = h->hbuf; t1.p.o_bstride = xs; t1.p.o_rstride = Ts;
+        if ((rc = run_gemm(h, t1, st))) return rc;
+    }
+    GemmCall t2 = make_gemm(h, h->g_out, folded ? h->skip : h->hbuf, xs, Ts, B, T, folded ? ST_RELU : ST_PLAIN, EP_LINCOMB, 0);
     t2.p.nout = nout;
     for (int i = 0; i < nout; ++i) t2.p.lo[i] = lo[i];
     t2.p.o_bstride = (long)FM * Ts; t2.p.o_rstride = Ts;
@@ -3175,7 +3224,9 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         out->bytes_per_frame_nfe = L * 24 * C + 8 * M;
         // the plan of the handle's last call (plan_denoise): segments, or the row-split pair / the two GEMMs per layer; around the
         // layers the edge kernel (skip projection, output projection + solver update, the next evaluation's input projection;
-        // wn_edge.hip) or the three GEMMs of gemm.hip
+        // wn_edge.hip) or the three GEMMs of gemm.hip.  kernels_per_nfe counts launch SITES: an fp32 evaluation on the GEMM path
+        // launches nothing at the skip projection's (folded into the layers' out-proj pack, run_wavenet) - the suite tells the
+        // layer forms apart by "+ 3" / "+ 1", so the count keeps that meaning
         const DenoisePlan pl = h->arena.p ? plan_denoise(h) : DenoisePlan();
         out->layer_launches = pl.segs.empty() ? 2 : 0;
         if (pl.segs.empty()) out->split_tiles = (int32_t)tiles_at(h, 32);

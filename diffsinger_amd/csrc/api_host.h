@@ -152,6 +152,9 @@ struct dsd_handle {
     DevBuf<float> blob;
     PackedGemm g_inproj, g_emb0, g_emb1, g_dproj, g_cp, g_tail1, g_out;
     std::vector<PackedGemm> g_conv, g_outp;          // WaveNet per layer
+    // fp32 mode: every layer's out-proj once more with the skip projection folded into its skip rows (build_packed); the
+    // evaluations that do not end in the edge kernel read it and run no skip-projection GEMM.  Empty: not built (bf16x3 mode)
+    std::vector<PackedGemm> g_outf;
     // split-bf16 precision mode (wn_layer_x3.hip): 0 = fp32 (default), 1 = bf16x3 where a kernel exists; the layers' weight
     // streams (float offsets into the blob; empty: not built)
     int precision = 0;

@@ -19,7 +19,7 @@ namespace dsd {
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline int padded_ts(int T) { return round_up(T, 64) + 32; }
 
-enum Stage { ST_PLAIN = 0, ST_FILM = 1, ST_LN = 2, ST_SCALE = 3, ST_LRELU = 4 };
+enum Stage { ST_PLAIN = 0, ST_FILM = 1, ST_LN = 2, ST_SCALE = 3, ST_LRELU = 4, ST_RELU = 5 };
 enum Epi { EP_BIAS_ACT = 0, EP_GATE = 1, EP_RESSKIP = 2, EP_LINCOMB = 3, EP_SWIGLU = 4, EP_BIAS_RES = 5, EP_SCATTER = 6, EP_LYNX_NEXT = 7 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_MISH = 2, ACT_GELU = 3, ACT_LRELU = 4, ACT_TANH = 5, ACT_SILU = 6 };
 
@@ -134,6 +134,7 @@ struct GemmP {
     int HL;                 // halo columns staged on each side (multiple of 4, >= (taps / 2) * dil)
     int S;                  // LDS row stride in floats, S % 32 == 16
     float in_scale;         // ST_SCALE: staged value DIVIDED by this;  ST_LRELU: negative slope of the leaky ReLU
+    // ST_RELU: y = max(x, 0) (the folded skip rows of the WaveNet, build_packed; unlike ST_LRELU it has the resident variants)
     // ST_FILM: y = x + film[c * film_cstride + film_col0 + b * film_colb]
     const float* film;
     int film_cstride, film_col0, film_colb;

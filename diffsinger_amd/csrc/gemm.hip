@@ -307,6 +307,7 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
                     if (STAGE == ST_FILM) y = y + add;
                     else if (STAGE == ST_LN) y = (y - mean[e]) * rstd[e];
                     else if (STAGE == ST_SCALE) y = y / p.in_scale;        // skip sum DIVIDED by sqrt(L) (wavenet.py:96)
+                    else if (STAGE == ST_RELU) y = fmaxf(y, 0.f);          // relu of the folded skip rows (wavenet.py:97)
                     o[e] = ((s_mask[u] >> e) & 1u) ? y : 0.f;              // zero padding AFTER the FiLM add (wavenet.py:36-38)
                 }
                 if (s_valid[u]) *reinterpret_cast<f32x4*>(&buf[s_loff[u]]) = o;
@@ -547,6 +548,7 @@ __global__ __launch_bounds__(256, (SW > 0 && NB * WN == 4) ? 3 : 1) void gemm_ke
                             if (STAGE == ST_FILM) y = y + add[u];
                             else if (STAGE == ST_LN) y = (y - mean[e]) * rstd[e];
                             else if (STAGE == ST_SCALE) y = y / p.in_scale;   // skip sum DIVIDED by sqrt(L) (wavenet.py:96)
+                            else if (STAGE == ST_RELU) y = fmaxf(y, 0.f);     // relu of the folded skip rows (wavenet.py:97)
                             else if (STAGE == ST_LRELU) y = y >= 0.f ? y : y * p.in_scale;   // F.leaky_relu on the input
                             const bool ok = (t >= 0) && (t < Tb) && row_ok;
                             o[e] = ok ? y : 0.f;       // zero padding applies AFTER the FiLM add (wavenet.py:36-38)
@@ -940,6 +942,7 @@ hipError_t gemm_init_all() {
     if ((e = attr_all<ST_FILM, 3, EP_GATE>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_RESSKIP>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_LINCOMB>()) != hipSuccess) return e;
+    if ((e = attr_all<ST_RELU, 1, EP_LINCOMB>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_SWIGLU>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_LINCOMB>()) != hipSuccess) return e;
@@ -956,6 +959,7 @@ hipError_t gemm_init_all() {
     if ((e = attr_all<ST_FILM, 3, EP_GATE, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_RESSKIP, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
+    if ((e = attr_all<ST_RELU, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_SWIGLU, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES, 1>()) != hipSuccess) return e;
     if ((e = attr_all<ST_LN, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
@@ -999,6 +1003,7 @@ hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int
         DSD_CASE_R(ST_FILM, 3, EP_GATE)
         DSD_CASE_R(ST_PLAIN, 1, EP_RESSKIP)
         DSD_CASE_R(ST_PLAIN, 1, EP_LINCOMB)
+        DSD_CASE_R(ST_RELU, 1, EP_LINCOMB)
         DSD_CASE_R(ST_LN, 1, EP_SWIGLU)
         DSD_CASE_R(ST_PLAIN, 1, EP_BIAS_RES)
         DSD_CASE_R(ST_LN, 1, EP_LINCOMB)
@@ -1027,6 +1032,7 @@ hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int
     DSD_CASE(ST_FILM, 3, EP_GATE)
     DSD_CASE(ST_PLAIN, 1, EP_RESSKIP)
     DSD_CASE(ST_PLAIN, 1, EP_LINCOMB)
+    DSD_CASE(ST_RELU, 1, EP_LINCOMB)
     DSD_CASE(ST_LN, 1, EP_SWIGLU)
     DSD_CASE(ST_PLAIN, 1, EP_BIAS_RES)
     DSD_CASE(ST_LN, 1, EP_LINCOMB)

@@ -848,7 +848,9 @@ typedef struct dsd_stats {
     int64_t workspace_bytes;     /* current arena size                                  */
     int64_t flops_per_frame_nfe; /* algorithmic FLOPs per mel frame per NFE (hoisted)   */
     int64_t bytes_per_frame_nfe; /* algorithmic HBM bytes per mel frame per NFE         */
-    int32_t kernels_per_nfe;     /* kernel launches per backbone evaluation             */
+    int32_t kernels_per_nfe;     /* launch sites of a backbone evaluation: the layers' launches and 3 around them (1: the
+                                    edge kernel).  A WaveNet in fp32 without the edge kernel launches one kernel fewer than
+                                    this: its skip-projection site is folded into the layers' out-proj weights */
     int32_t graphs_cached;
     /* The launch plan of the handle's last call, under the path switches of that call.  WaveNet, how a residual layer runs
        on the current batch shape (API v10): launches per layer (1 = the fused layer kernel over every tile, 2 = the row-split
