@@ -196,6 +196,17 @@ inline long voc_upp(const dsd_vocoder_config& v, int from) {     // product of u
     for (int i = from; i < v.n_ups; ++i) p *= v.upsample_rates[i];
     return p;
 }
+// taps of the phase-row GEMM that stands for ConvTranspose1d(kernel K, stride u, padding (K - u) / 2): 2 D + 1 with D the
+// farthest input offset any output phase reads (build_packed_voc)
+inline int voc_up_taps(int u, int K) {
+    const int pad = (K - u) / 2;
+    int D = 0;
+    for (int r = 0; r < u; ++r) {
+        const int k0 = (r + pad) % u, e = (r + pad) / u, nmax = (K - 1 - k0) / u;
+        D = std::max(D, std::max(e, nmax - e));
+    }
+    return 2 * D + 1;
+}
 
 // Generator state_dict after remove_weight_norm()  (nsf_hifigan/models.py:207-260)
 std::vector<std::pair<std::string, std::vector<int64_t>>> expected_params_voc(const dsd_vocoder_config& v) {
@@ -838,12 +849,7 @@ int build_packed_voc(dsd_handle* h) {
     };
     for (int i = 0; i < v.n_ups; ++i) {
         const int ch = voc_stage_channels(v, i), u = v.upsample_rates[i], K = v.upsample_kernel_sizes[i], pad = (K - u) / 2;
-        int D = 0;
-        for (int r = 0; r < u; ++r) {
-            const int k0 = (r + pad) % u, e = (r + pad) / u, nmax = (K - 1 - k0) / u;
-            D = std::max(D, std::max(e, nmax - e));
-        }
-        const int taps = 2 * D + 1;
+        const int taps = voc_up_taps(u, K), D = taps / 2;
         h->v_uptaps[i] = taps;
         const HostTensor* t = &W(h, "ups." + std::to_string(i) + ".weight");      // [2ch, ch, K]
         const HostTensor* b = &W(h, "ups." + std::to_string(i) + ".bias");
@@ -1286,6 +1292,19 @@ struct GemmCall {
     int stage, taps, epi, nb, batch, fast;
 };
 
+// Tile geometry of a k-tap GEMM, shared by make_gemm and by the create-time checks that refuse what run_gemm would refuse:
+// the halo per side (the reach rounded up to 4 frames) and the LDS row stride of a BN-frame tile (16 mod 32 floats)
+inline int gemm_halo(int taps, int dil) { return taps > 1 ? round_up((taps / 2) * dil, 4) : 0; }
+inline int gemm_row_stride(int BN, int HL) {
+    int S = BN + 2 * HL;
+    while (S % 32 != 16) S += 4;
+    return S;
+}
+// LDS of one BN-frame tile on the generic path: a k-tap conv keeps all K input rows resident, a 1x1 walks chunks of 256
+inline int gemm_generic_lds_bytes(int K, int taps, int dil, int BN) {
+    return gemm_lds_bytes(taps > 1 ? K : std::min(K, 256), gemm_row_stride(BN, gemm_halo(taps, dil)));
+}
+
 // vr: a ragged vocoder batch at this GEMM's rate (dsd_vocode_ragged): its lengths and valid tiles instead of dsd_set_lengths'
 GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b_bstride, int b_rstride, int batch,
                    int T, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false,
@@ -1306,7 +1325,7 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     p.T = T;
     p.dil = dil;
     p.taps = g.taps;
-    p.HL = g.taps > 1 ? round_up((g.taps / 2) * dil, 4) : 0;
+    p.HL = gemm_halo(g.taps, dil);
     p.in_scale = 1.f;
     // ragged batches: only a convolution along time can carry an item's padded frames into its valid ones, so only the
     // k-tap GEMMs over the utterances' (B, T) frames mask their input (not the 1x1s, not the step-embedding MLPs)
@@ -1322,14 +1341,16 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     const long wg64 = (vr ? (long)vr->ncg[2] : (long)batch * ((T + 63) / 64)) * mtiles;
     c.nb = wg64 >= 512 ? 2 : 1;
     // a conv on the generic path keeps all input channels resident: 64-frame tiles only while that fits in LDS
+    // (the second test: the row stride's rounding can add 24 frames, not 16 - K = 368 at a halo of 12 passes the first and
+    // needs 164 864 bytes; what fits on 32-frame tiles must run at every (B, T))
     if ((g.taps > 3 || (generic_only && g.taps > 1)) &&
-        (size_t)g.K * (64 + 2 * round_up((g.taps / 2) * dil, 4) + 16) * 4 > 150 * 1024) c.nb = 1;
+        ((size_t)g.K * (64 + 2 * p.HL + 16) * 4 > 150 * 1024 || gemm_lds_bytes(g.K, gemm_row_stride(64, p.HL)) > kMaxDynLds))
+        c.nb = 1;
     // narrow tiles (64 rows x 16 frames, c.nb == 0): when 32-frame tiles would put at most ~1.5 workgroups on a CU,
     // twice as many half-size workgroups share each SIMD between two waves and halve the latency of a lone one
     if (c.nb == 1) {
         const long wg32 = (long)batch * ((T + 31) / 32) * mtiles;
-        int s16 = 16 + 2 * p.HL;
-        while (s16 % 32 != 16) s16 += 4;
+        const int s16 = gemm_row_stride(16, p.HL);
         const bool ok = (g.taps == 1 || g.taps == 3) && g.K % 64 == 0 && g.Kreal == g.K && stage != ST_LN &&
                         epi != EP_SWIGLU && epi != EP_LYNX_NEXT && gemm_has_fast(g.taps, 0, s16);
         // ... and above that while they still lower the frames the busiest CU has to cover (a launch this small is one
@@ -1349,8 +1370,7 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
         p.cgmap = vr ? vr->cg[c.nb] : h->cg_dev[c.nb].p;
         p.ncg = vr ? vr->ncg[c.nb] : h->cg_n[c.nb];
     }
-    int S = BN + 2 * p.HL;
-    while (S % 32 != 16) S += 4;
+    const int S = gemm_row_stride(BN, p.HL);
     p.S = S;
     p.mtiles = mtiles;
     const int w4 = (BN + 2 * p.HL) / 4;
@@ -2620,6 +2640,46 @@ static int check_vocoder_config(const dsd_vocoder_config* cfg) {
             if (cfg->resblock_dilation_sizes[j][d] < 1 || cfg->resblock_dilation_sizes[j][d] * (cfg->resblock_kernel_sizes[j] / 2) > 48)
                 return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: residual block %d dilation %d reaches beyond 48 frames", j, d);
     }
+    // models.py:239-245: noise_convs[i] of a stage before the last is Conv1d(1, C, 2 sf, stride sf, padding sf // 2) with
+    // sf = prod(rates[i+1:]); for an odd sf it yields one frame fewer than the stage has and `x + x_source` raises in the
+    // reference.  sf is odd only when every later rate is, and the stage before the last has sf = the last rate.
+    if (!cfg->mini_nsf && cfg->n_ups >= 2 && cfg->upsample_rates[cfg->n_ups - 1] % 2 != 0)
+        return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: the last upsample rate (%d) must be even unless mini_nsf: "
+                    "noise_convs.%d (kernel 2 sf, stride sf, padding sf // 2 at sf = %d, models.py:239-245) gives one frame too few "
+                    "and the reference cannot run this configuration", cfg->upsample_rates[cfg->n_ups - 1], cfg->n_ups - 2,
+                    cfg->upsample_rates[cfg->n_ups - 1]);
+    // What run_gemm would refuse at the first dsd_vocode call is refused here.  Every convolution of the generator runs on the
+    // generic GEMM path, which keeps all round_up(cin, 16) input rows of a tile resident; make_gemm falls back to 32-frame
+    // tiles whenever 64-frame tiles do not fit, so the 32-frame tile decides, for every (B, T).
+    auto conv_fits = [](const char* layer, int idx, int cin, int taps, int dil) {
+        const int bytes = gemm_generic_lds_bytes(round_up(cin, 16), taps, dil, 32);
+        if (bytes <= kMaxDynLds) return (int)DSD_OK;
+        char name[32];
+        if (idx >= 0) snprintf(name, sizeof(name), "%s.%d", layer, idx);
+        else snprintf(name, sizeof(name), "%s", layer);
+        return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: %s (%d input channels, k = %d taps, dilation %d) needs %d bytes of "
+                    "LDS resident per 32-frame tile, above the %d available", name, cin, taps, dil, bytes, kMaxDynLds);
+    };
+    if (int rc = conv_fits("conv_pre", -1, cfg->num_mels, 7, 1)) return rc;
+    dsd_vocoder_config v = *cfg;
+    for (int i = 0; i < cfg->n_ups; ++i) {
+        const int ch = voc_stage_channels(v, i);
+        if (int rc = conv_fits("ups", i, 2 * ch, voc_up_taps(cfg->upsample_rates[i], cfg->upsample_kernel_sizes[i]), 1)) return rc;
+        if (!cfg->mini_nsf && i + 1 < cfg->n_ups) {      // the noise conv's source window: one group of frames at least
+            const long sf = voc_upp(v, i + 1);
+            if (sf > (1L << 28) || voc_noise_groups(ch, (int)sf, 2 * (int)sf) == 0)
+                return fail(nullptr, DSD_EINVAL, "dsd_vocoder_create: noise_convs.%d (stride %ld, kernel %ld) needs a source window "
+                            "of %ld bytes of LDS for one group of frames, above the %d available", i, sf, 2 * sf,
+                            (long)((VOC_NOISE_NQ - 1) * sf + 2 * sf) * 4, kMaxDynLds);
+        }
+        if (ch == 16 || ch == 32) continue;              // residual blocks on tconv.hip: at most 108 544 bytes (k 15, reach 48)
+        for (int j = 0; j < cfg->n_kernels; ++j)
+            for (int d = 0; d < cfg->n_dilations[j]; ++d)
+                if (int rc = conv_fits("resblocks", i * cfg->n_kernels + j, ch, cfg->resblock_kernel_sizes[j],
+                                       cfg->resblock_dilation_sizes[j][d]))
+                    return rc;
+    }
+    if (int rc = conv_fits("conv_post", -1, voc_stage_channels(v, cfg->n_ups - 1), 7, 1)) return rc;
     return DSD_OK;
 }
 
@@ -2627,6 +2687,7 @@ int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
     if (int rc = create_check(cfg, out, "dsd_vocoder_create", check_vocoder_config)) return rc;
     hipError_t ie = gemm_init_all();
     if (ie == hipSuccess) ie = tconv_init_all();
+    if (ie == hipSuccess) ie = voc_noise_init_all();
     if (ie == hipSuccess) ie = voc_x3_init_all();
     if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
     dsd_handle* h = new_handle(DSD_VOC_NSF_HIFIGAN, cfg->device);

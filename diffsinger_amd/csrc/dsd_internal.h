@@ -389,6 +389,9 @@ hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int 
                                 const int* lens = nullptr);
 hipError_t launch_voc_fast_source(const float* f0, int B, int T, int upp, float source_sr, float* acc_tmp, int Tsu, float* har,
                                   hipStream_t st, const int* lens = nullptr);
+constexpr int VOC_NOISE_NQ = 16;                    // frames per thread of the noise conv
+int voc_noise_groups(int C, int sf, int ksz);       // frame groups per workgroup whose source window fits in LDS; 0: none does
+hipError_t voc_noise_init_all();
 // lens_q / lens_up (ragged: per-item output frames / source samples) both or neither
 hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, const float* bias, int B, int C, int Tq,
                                  int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st, const int* lens_q = nullptr,

@@ -85,17 +85,21 @@ __global__ void voc_source_kernel(const float* __restrict__ f0, const float* __r
 // NQ consecutive frames of its channel, and the source window of the workgroup's frames sits in LDS, read as a
 // broadcast.  One workgroup = min(C, 256) channels x (256 / C) groups of NQ frames.
 // ---------------------------------------------------------------------------------------------
+// The window is (groups * NQ - 1) * sf + ksz floats: thin stages far from the output rate (C = 16 at sf = 64: 65 792 bytes)
+// outgrow the LDS, so the launch caps `groups` (voc_noise_groups) to what the raised limit holds and the threads of the
+// groups cut away idle; a frame's sum does not depend on the group that forms it.
 // RAG = 1: item b has lens_q[b] output frames and lens_up[b] source samples; a workgroup past its item's end returns.
-constexpr int VOC_NQ = 16;
+constexpr int VOC_NQ = VOC_NOISE_NQ;
 template <int RAG>
 __global__ __launch_bounds__(256) void voc_noise_conv_kernel(float* __restrict__ x, const float* __restrict__ har,
                                                              const float* __restrict__ wt, const float* __restrict__ bias,
                                                              int C, int Tq, int Tsq, int sf, int ksz, long Tup, int Tsu,
-                                                             const int* __restrict__ lens_q, const int* __restrict__ lens_up) {
+                                                             int groups, const int* __restrict__ lens_q,
+                                                             const int* __restrict__ lens_up) {
     extern __shared__ float win[];                  // (frames per workgroup - 1) * sf + ksz source samples
     const int b = blockIdx.z;
     const int cpb = C < 256 ? C : 256;              // channels per workgroup
-    const int groups = 256 / cpb;                   // frame groups per workgroup
+    // groups: frame groups per workgroup, 256 / cpb or fewer (the launch's choice: voc_noise_groups)
     const int fpb = groups * VOC_NQ;                // frames per workgroup
     const int q0 = blockIdx.x * fpb;
     if (RAG) {
@@ -230,16 +234,35 @@ hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float
 hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, const float* bias, int B, int C, int Tq,
                                  int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st, const int* lens_q,
                                  const int* lens_up) {
-    const int cpb = C < 256 ? C : 256, fpb = (256 / cpb) * VOC_NQ;
+    const int groups = voc_noise_groups(C, sf, ksz);
+    if (groups < 1) return hipErrorInvalidValue;    // not even one group's window fits (dsd_vocoder_create refuses these)
+    const int cpb = C < 256 ? C : 256, fpb = groups * VOC_NQ;
     const int nwin = (fpb - 1) * sf + ksz;
     const dim3 grid((Tq + fpb - 1) / fpb, (C + cpb - 1) / cpb, B);
     if (lens_q)
         hipLaunchKernelGGL(voc_noise_conv_kernel<1>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
-                           ksz, Tup, Tsu, lens_q, lens_up);
+                           ksz, Tup, Tsu, groups, lens_q, lens_up);
     else
         hipLaunchKernelGGL(voc_noise_conv_kernel<0>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
-                           ksz, Tup, Tsu, nullptr, nullptr);
+                           ksz, Tup, Tsu, groups, nullptr, nullptr);
     return hipGetLastError();
+}
+
+// frame groups per workgroup of voc_noise_conv_kernel: one per min(C, 256) threads, fewer where the source window of that many
+// would not fit the LDS the kernel may use; 0: not even one fits
+int voc_noise_groups(int C, int sf, int ksz) {
+    const int cpb = C < 256 ? C : 256;
+    const long room = kMaxDynLds / (long)sizeof(float) - ksz;      // floats left for (groups * NQ - 1) * sf
+    if (room < (long)(VOC_NQ - 1) * sf) return 0;
+    const long fit = (room / sf + 1) / VOC_NQ;
+    return (int)std::min<long>(256 / cpb, fit);
+}
+
+// the noise conv's window is dynamic LDS beyond the default 64 KiB: raise the limit once, outside any stream capture
+hipError_t voc_noise_init_all() {
+    hipError_t e = allow_max_lds(voc_noise_conv_kernel<0>);
+    if (e == hipSuccess) e = allow_max_lds(voc_noise_conv_kernel<1>);
+    return e;
 }
 
 // x[row][t] += sigma * noise[row][t]  (models.py:272-273; x rows are padded to Ts, the caller's noise is dense)

@@ -167,7 +167,7 @@ def nsf_hifigan_param_shapes(h):
     shapes = OrderedDict()
     mini = bool(h.get("mini_nsf", False))
     if not mini:
-        shapes["m_source.l_linear.weight"] = (1, 9)
+        shapes["m_source.l_linear.weight"] = (1, int(h.get("harmonic_num", 8)) + 1)      # optional key, the reference's 8
         shapes["m_source.l_linear.bias"] = (1,)
     ch = h["upsample_initial_channel"]
     rates = list(h["upsample_rates"])

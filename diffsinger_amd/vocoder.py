@@ -61,7 +61,7 @@ class Generator(_NativeBackbone):
         self.resblock_kernel_sizes = [int(v) for v in _get(h, "resblock_kernel_sizes")]
         self.resblock_dilation_sizes = [[int(d) for d in ds] for ds in _get(h, "resblock_dilation_sizes")]
         self.noise_sigma = _get(h, "noise_sigma", None)          # models.py:213: > 0 adds sigma * randn after conv_pre
-        self.harmonic_num = 8
+        self.harmonic_num = int(_get(h, "harmonic_num", 8))      # optional key; the reference hard-codes 8 (models.py:223)
         self.upp = int(np.prod(self.upsample_rates))
         self._hidden = self.num_mels
         if not self.mini_nsf:

@@ -471,6 +471,13 @@ int dsd_noise_fill(int32_t device, const dsd_noise_spec* spec, float* out, void*
  * `m_source.l_linear.*`, `noise_convs.N.*`, `conv_pre.*`, `ups.N.*` ([C_in, C_out, K] as ConvTranspose1d stores it),
  * `resblocks.N.convs1.M.* / convs2.M.*` (ResBlock1) or `resblocks.N.convs.M.*` (ResBlock2), `conv_post.*`;
  * with mini_nsf: `source_conv.*` instead of `m_source.*` / `noise_convs.*`.
+ * Accepted (DSD_EINVAL otherwise, with the layer named; what is accepted runs for every (B, T) - DESIGN.md 4d, "Vocoder
+ * configurations"): 1..8 upsampling stages of any rate u >= 1 with a kernel in [u, 8u], kernel - u even; 1..8 residual
+ * kernels, odd and <= 15, with 1..4 dilations each and dilation * (kernel / 2) <= 48; harmonic_num 0..15;
+ * upsample_initial_channel divisible by 2^n_ups; every convolution's resident input rows within 160 KiB of LDS per 32-frame
+ * tile (num_mels <= 848, upsample_initial_channel >> i <= 848 at stage i, a residual stage of at most 272 channels at a reach
+ * of 48 frames, 352 at k 11 / dilation 5); without mini_nsf and with two or more stages an even last rate (the reference's
+ * noise_convs give one frame too few for an odd one, models.py:239-245) and prod(upsample_rates[i+1:]) <= 2409.
  */
 #define DSD_VOC_MAX_UPS 8
 #define DSD_VOC_MAX_KERNELS 8

@@ -1,4 +1,4 @@
-"""numpy fp32 restatement of the NSF-HiFiGAN generator (TEST ORACLE - SURVEY.md section 8(f) rank 3, the step after
+"""numpy restatement of the NSF-HiFiGAN generator (TEST ORACLE - SURVEY.md section 8(f) rank 3, the step after
 the denoise loop: mel + f0 -> waveform).
 
 Follows modules/nsf_hifigan/models.py (weights in their inference form, i.e. after `remove_weight_norm()`):
@@ -7,6 +7,12 @@ Follows modules/nsf_hifigan/models.py (weights in their inference form, i.e. aft
   * ResBlock1.forward / ResBlock2.forward :62-69, :92-97
   * Generator.forward (mini_nsf = False)  :262-290
 and the wrapper's mel scaling, modules/vocoders/nsf_hifigan.py:59-64 (log10 -> ln).
+
+fp32 throughout by default, as the reference computes.  `generator_forward(..., dtype=np.float64)` evaluates everything after
+the source - convolutions, transposed convolutions, residual blocks, tanh - in float64 on the same fp32 weights and inputs: the
+yardstick that says how far fp32 arithmetic alone moves a waveform.  The source stays fp32 in either mode (the reference
+defines it as an fp32 running sum); its output is cast.  `harmonic_num` is read from the config (default 8, the value the
+reference hard-codes at models.py:223).
 """
 from __future__ import annotations
 
@@ -17,33 +23,33 @@ from .backbones import F32
 LRELU_SLOPE = 0.1
 
 
-def lrelu(x, slope):
-    return np.where(x >= 0, x, x * F32(slope)).astype(F32)
+def lrelu(x, slope, dt=F32):
+    return np.where(x >= 0, x, x * dt(slope)).astype(dt)
 
 
-def conv1d(x, w, b, dilation=1, padding=0, stride=1):
+def conv1d(x, w, b, dilation=1, padding=0, stride=1, dt=F32):
     """x [B,Ci,T], w [Co,Ci,K] -> [B,Co,To]."""
     bsz, ci, t = x.shape
     co, _, k = w.shape
-    xp = np.zeros((bsz, ci, t + 2 * padding), dtype=F32)
+    xp = np.zeros((bsz, ci, t + 2 * padding), dtype=dt)
     xp[:, :, padding:padding + t] = x
     to = (t + 2 * padding - dilation * (k - 1) - 1) // stride + 1
-    y = np.zeros((bsz, co, to), dtype=F32)
+    y = np.zeros((bsz, co, to), dtype=dt)
     for j in range(k):
         seg = xp[:, :, j * dilation: j * dilation + (to - 1) * stride + 1: stride]
         y += np.matmul(np.ascontiguousarray(w[:, :, j]), seg)
-    return (y + b[None, :, None]).astype(F32)
+    return (y + b[None, :, None]).astype(dt)
 
 
-def conv_transpose1d(x, w, b, stride, padding):
+def conv_transpose1d(x, w, b, stride, padding, dt=F32):
     """x [B,Ci,T], w [Ci,Co,K] -> [B,Co,(T-1)*stride - 2*padding + K]."""
     bsz, ci, t = x.shape
     _, co, k = w.shape
-    full = np.zeros((bsz, co, (t - 1) * stride + k), dtype=F32)
+    full = np.zeros((bsz, co, (t - 1) * stride + k), dtype=dt)
     for j in range(k):
         full[:, :, j: j + (t - 1) * stride + 1: stride] += np.matmul(np.ascontiguousarray(w[:, :, j]).T, x)
     out = full[:, :, padding: full.shape[2] - padding]
-    return (out + b[None, :, None]).astype(F32)
+    return (out + b[None, :, None]).astype(dt)
 
 
 def sine_source(p, f0, upp, sampling_rate, rand_ini, noise, harmonic_num=8, sine_amp=0.1, noise_std=0.003):
@@ -98,27 +104,41 @@ def fast_sine_source(f0, upp, source_sr):
     return np.sin(F32(2 * np.pi) * rad).astype(F32)
 
 
-def resblock1(p, pre, x, kernel_size, dilations):
+def resblock1(p, pre, x, kernel_size, dilations, dt=F32):
     for j, d in enumerate(dilations):
-        xt = lrelu(x, LRELU_SLOPE)
+        xt = lrelu(x, LRELU_SLOPE, dt)
         xt = conv1d(xt, p[f"{pre}convs1.{j}.weight"], p[f"{pre}convs1.{j}.bias"], dilation=d,
-                    padding=(kernel_size * d - d) // 2)
-        xt = lrelu(xt, LRELU_SLOPE)
-        xt = conv1d(xt, p[f"{pre}convs2.{j}.weight"], p[f"{pre}convs2.{j}.bias"], dilation=1, padding=(kernel_size - 1) // 2)
-        x = (xt + x).astype(F32)
+                    padding=(kernel_size * d - d) // 2, dt=dt)
+        xt = lrelu(xt, LRELU_SLOPE, dt)
+        xt = conv1d(xt, p[f"{pre}convs2.{j}.weight"], p[f"{pre}convs2.{j}.bias"], dilation=1, padding=(kernel_size - 1) // 2,
+                    dt=dt)
+        x = (xt + x).astype(dt)
     return x
 
 
-def resblock2(p, pre, x, kernel_size, dilations):
+def resblock2(p, pre, x, kernel_size, dilations, dt=F32):
     for j, d in enumerate(dilations):
-        xt = lrelu(x, LRELU_SLOPE)
-        xt = conv1d(xt, p[f"{pre}convs.{j}.weight"], p[f"{pre}convs.{j}.bias"], dilation=d, padding=(kernel_size * d - d) // 2)
-        x = (xt + x).astype(F32)
+        xt = lrelu(x, LRELU_SLOPE, dt)
+        xt = conv1d(xt, p[f"{pre}convs.{j}.weight"], p[f"{pre}convs.{j}.bias"], dilation=d, padding=(kernel_size * d - d) // 2,
+                    dt=dt)
+        x = (xt + x).astype(dt)
     return x
 
 
-def generator_forward(p, h, mel, f0, rand_ini=None, noise=None, pre_noise=None):
-    """Generator.forward: mel [B, num_mels, T] (natural-log mel), f0 [B, T] -> wav [B, 1, T*prod(upsample_rates)]."""
+def harmonic_num_of(h):
+    """the optional `harmonic_num` config key: 8 where absent (models.py:223 hard-codes it)"""
+    v = h.get("harmonic_num", None)
+    return 8 if v is None else int(v)
+
+
+def generator_forward(p, h, mel, f0, rand_ini=None, noise=None, pre_noise=None, dtype=F32):
+    """Generator.forward: mel [B, num_mels, T] (natural-log mel), f0 [B, T] -> wav [B, 1, T*prod(upsample_rates)].
+    dtype: np.float32 (the reference's arithmetic) or np.float64 (everything after the fp32 source in float64)."""
+    dt = np.dtype(dtype).type
+    if dt is not F32:       # the fp32 weights, exactly, in the wider type (the source keeps the fp32 ones)
+        p32, p = p, {k: np.asarray(v, dtype=dt) for k, v in p.items()}
+    else:
+        p32 = p
     rates, ksz = list(h["upsample_rates"]), list(h["upsample_kernel_sizes"])
     rk, rd = list(h["resblock_kernel_sizes"]), [list(d) for d in h["resblock_dilation_sizes"]]
     mini = bool(h.get("mini_nsf", False))
@@ -127,33 +147,37 @@ def generator_forward(p, h, mel, f0, rand_ini=None, noise=None, pre_noise=None):
         har = fast_sine_source(f0, upp, h["sampling_rate"] / int(np.prod(rates[2:])))
     else:
         upp = int(np.prod(rates))
-        har = sine_source(p, f0, upp, h["sampling_rate"], rand_ini, noise)
-    x = conv1d(np.asarray(mel, dtype=F32), p["conv_pre.weight"], p["conv_pre.bias"], padding=3)
+        har = sine_source(p32, f0, upp, h["sampling_rate"], rand_ini, noise, harmonic_num=harmonic_num_of(h))
+    har = har.astype(dt)
+    x = conv1d(np.asarray(mel, dtype=F32).astype(dt), p["conv_pre.weight"], p["conv_pre.bias"], padding=3, dt=dt)
     sigma = h.get("noise_sigma", None)
     if sigma is not None and sigma > 0:                  # models.py:272-273
-        x = (x + F32(sigma) * np.asarray(pre_noise, dtype=F32)).astype(F32)
+        x = (x + dt(F32(sigma)) * np.asarray(pre_noise, dtype=F32).astype(dt)).astype(dt)
     rb = resblock1 if str(h.get("resblock", "1")) == "1" else resblock2
     for i, (u, k) in enumerate(zip(rates, ksz)):
-        x = lrelu(x, LRELU_SLOPE)
-        x = conv_transpose1d(x, p[f"ups.{i}.weight"], p[f"ups.{i}.bias"], stride=u, padding=(k - u) // 2)
+        x = lrelu(x, LRELU_SLOPE, dt)
+        x = conv_transpose1d(x, p[f"ups.{i}.weight"], p[f"ups.{i}.bias"], stride=u, padding=(k - u) // 2, dt=dt)
         if mini:
             if i == 1:
-                x = (x + conv1d(har, p["source_conv.weight"], p["source_conv.bias"])).astype(F32)
+                x = (x + conv1d(har, p["source_conv.weight"], p["source_conv.bias"], dt=dt)).astype(dt)
         else:
             if i + 1 < len(rates):
                 sf = int(np.prod(rates[i + 1:]))
-                xs = conv1d(har, p[f"noise_convs.{i}.weight"], p[f"noise_convs.{i}.bias"], stride=sf, padding=sf // 2)
+                xs = conv1d(har, p[f"noise_convs.{i}.weight"], p[f"noise_convs.{i}.bias"], stride=sf, padding=sf // 2, dt=dt)
             else:
-                xs = conv1d(har, p[f"noise_convs.{i}.weight"], p[f"noise_convs.{i}.bias"])
-            x = (x + xs).astype(F32)
+                xs = conv1d(har, p[f"noise_convs.{i}.weight"], p[f"noise_convs.{i}.bias"], dt=dt)
+            if xs.shape != x.shape:                      # an odd sf: the reference's `x + x_source` raises here too
+                raise ValueError(f"noise_convs.{i} gives {xs.shape[2]} frames for the stage's {x.shape[2]} (stride {sf}, "
+                                 f"padding {sf // 2}, models.py:239-245): the reference cannot run this configuration")
+            x = (x + xs).astype(dt)
         acc = None
         for j in range(len(rk)):
-            y = rb(p, f"resblocks.{i * len(rk) + j}.", x, rk[j], rd[j])
-            acc = y if acc is None else (acc + y).astype(F32)
-        x = (acc / F32(len(rk))).astype(F32)
-    x = lrelu(x, 0.01)                                   # F.leaky_relu default slope (models.py:287)
-    x = conv1d(x, p["conv_post.weight"], p["conv_post.bias"], padding=3)
-    return np.tanh(x).astype(F32)
+            y = rb(p, f"resblocks.{i * len(rk) + j}.", x, rk[j], rd[j], dt)
+            acc = y if acc is None else (acc + y).astype(dt)
+        x = (acc / dt(len(rk))).astype(dt)
+    x = lrelu(x, 0.01, dt)                               # F.leaky_relu default slope (models.py:287)
+    x = conv1d(x, p["conv_post.weight"], p["conv_post.bias"], padding=3, dt=dt)
+    return np.tanh(x).astype(dt)
 
 
 def spec2wav(p, h, mel_btm, f0, rand_ini=None, noise=None, mel_base="10", pre_noise=None):

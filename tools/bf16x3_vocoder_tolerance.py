@@ -4,7 +4,7 @@
 Inside the residual blocks every Conv1d(C -> C) that voc_x3.hip takes (C a multiple of 32, 64 <= C <= 256) is evaluated tap by
 tap with `matmul3` of tools/bf16x3_tolerance.py - operands split hi = bf16(x), lo = bf16(x - hi), product hi.hi + hi.lo + lo.hi
 in fp32 - and everything else (conv_pre, the transposed convolutions, the 16- / 32-channel stages, conv_post, the source) is the
-plain fp32 oracle.  Prints, for every case of tests/vocoder_x3_cases.py, max |diff| / max |want| against the fp32 oracle, and the
+plain fp32 oracle.  Prints, for every case of tests/vocoder_x3_cases.py and every split-bf16 layout of tests/vocoder_config_cases.py, max |diff| / max |want| against the fp32 oracle, and the
 same with plain bf16 operands for scale.  DESIGN.md section 4d quotes the table; tests/test_vocoder_x3_host.py asserts it."""
 import os
 import sys
@@ -23,15 +23,19 @@ def eligible(c_out, c_in):
     return c_out == c_in and c_in % 32 == 0 and 64 <= c_in <= 256
 
 
-def emulate(layout, inp, product=matmul3):
-    """generator_forward of oracle/vocoder.py with the eligible residual-block convolutions' products replaced by `product`"""
-    import vocoder_x3_cases as cases
+def emulate(layout, inp, product=matmul3, cases=None):
+    """generator_forward of oracle/vocoder.py with the eligible residual-block convolutions' products replaced by `product`;
+    `cases`: the module whose oracle(layout, inp) is evaluated (default tests/vocoder_x3_cases.py)"""
+    if cases is None:
+        import vocoder_x3_cases as cases
     plain = (ov.conv1d, ov.resblock1, ov.resblock2)
     in_block = [False]
 
-    def conv1d(x, w, b, dilation=1, padding=0, stride=1):
+    def conv1d(x, w, b, dilation=1, padding=0, stride=1, **kw):
+        # kw: the oracle's optional `dt`, handed on as given, so that an oracle whose conv1d has no such argument still works
         if not in_block[0] or stride != 1 or not eligible(w.shape[0], w.shape[1]):
-            return plain[0](x, w, b, dilation=dilation, padding=padding, stride=stride)
+            return plain[0](x, w, b, dilation=dilation, padding=padding, stride=stride, **kw)
+        assert kw.get("dt", F32) is F32        # the emulation is of the fp32 mode's arithmetic
         bsz, ci, t = x.shape
         k = w.shape[2]
         xp = np.zeros((bsz, ci, t + 2 * padding), dtype=F32)
@@ -72,11 +76,20 @@ def all_cases():
         yield f"{cases.RAGGED_LAYOUT} ragged item {b} (1, {n})", cases.RAGGED_LAYOUT, inp, cases.ragged_reference(b)
 
 
+def config_cases():
+    """the same of the split-bf16 layouts of tests/vocoder_config_cases.py (taps 1 / 13 / 15, C = 192 / 160)"""
+    import vocoder_config_cases as cc
+    for tag, c in cc.X3.items():
+        for bsz, t_len in c["shapes"]:
+            yield f"{tag} ({bsz}, {t_len})", tag, cc.inputs(tag, bsz, t_len), cc.reference(tag, bsz, t_len, np.float32)
+
+
 def main():
     print(f"{'case':28s} {'split-bf16 vs fp32':>20s} {'plain bf16 operands':>20s}")
-    for label, layout, inp, want in all_cases():
-        x3 = rel(emulate(layout, inp), want)
-        b1 = rel(emulate(layout, inp, lambda a, b: np.matmul(bf16(a), bf16(b)).astype(F32)), want)
+    import vocoder_config_cases as cc
+    for label, layout, inp, want, cases in [c + (None,) for c in all_cases()] + [c + (cc,) for c in config_cases()]:
+        x3 = rel(emulate(layout, inp, cases=cases), want)
+        b1 = rel(emulate(layout, inp, lambda a, b: np.matmul(bf16(a), bf16(b)).astype(F32), cases=cases), want)
         print(f"{label:28s} {x3:20.2e} {b1:20.2e}", flush=True)
 
 
