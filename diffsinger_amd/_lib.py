@@ -50,7 +50,13 @@ EXPORTS = [
     "dsd_ddpm_tables_fill", "dsd_program_build", "dsd_program_free", "dsd_onnx_ddpm_plan",
     "dsd_track_plan", "dsd_track_place", "dsd_track_peak", "dsd_track_export",
     "dsd_diffuse", "dsd_masked_loss", "dsd_curve_stats", "dsd_dur_score",
+    "dsd_model_open", "dsd_model_close", "dsd_model_count", "dsd_model_find", "dsd_model_section", "dsd_model_config",
+    "dsd_model_tensor", "dsd_model_meta_at", "dsd_model_meta", "dsd_model_create",
 ]
+DSD_API_VERSION = 10
+DSD_EINVAL, DSD_ESTATE, DSD_EHIP, DSD_ENOMEM, DSD_ENOTFOUND, DSD_EIO = -1, -2, -3, -4, -5, -6
+DSD_MODEL_FORMAT_VERSION, DSD_MODEL_MAX_SECTIONS, DSD_MODEL_MAX_TENSORS, DSD_MODEL_MAX_META = 1, 64, 65536, 65536
+DSD_MODEL_MAX_NAME, DSD_MODEL_ALIGN = 255, 64
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
 EMBED_FLAGS = {"energy": 1, "breathiness": 2, "voicing": 4, "tension": 8, "key_shift": 16, "speed": 32}
@@ -159,6 +165,23 @@ class DsdCurve(C.Structure):
     _fields_ = [("points", C.c_void_p), ("out", C.c_void_p), ("uv_out", C.c_void_p), ("src_step", C.c_double),
                 ("dst_step", C.c_double), ("n_points", C.c_int32), ("length", C.c_int32), ("pad_to", C.c_int32),
                 ("op", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class DsdModelSectionInfo(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("kind", C.c_int32), ("config_size", C.c_int32), ("n_tensors", C.c_int32),
+                ("total_floats", C.c_int64)]
+
+
+class DsdModelTensorInfo(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("ndim", C.c_int32), ("shape", C.c_int64 * 4), ("count", C.c_int64),
+                ("data", C.POINTER(C.c_float))]
+
+
+# the config struct of each handle kind (the DSD_* enum), and the create call dsd_model_create makes for it
+KIND_CONFIGS = {0: DsdConfig, 1: DsdConfig, 2: DsdConfig, 3: DsdEncoderConfig, 4: DsdVocoderConfig, 5: DsdTokenEncoderConfig,
+                6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig}
+KIND_NAMES = {0: "wavenet", 1: "lynxnet", 2: "aux_convnext", 3: "fs2_acoustic", 4: "nsf_hifigan", 5: "fs2_tokens", 6: "mel",
+              7: "rmvpe", 8: "hnsep_vr"}
 
 
 class DsdTerm(C.Structure):
@@ -278,6 +301,18 @@ def _load():
     lib.dsd_masked_loss.argtypes = [i32, C.POINTER(DsdLossSpec), vp, vp, vp]
     lib.dsd_curve_stats.argtypes = [i32, vp, vp, vp, i64, C.c_float, vp, vp, vp]
     lib.dsd_dur_score.argtypes = [i32, C.POINTER(DsdDurSpec), vp, vp, vp, vp, vp]
+    lib.dsd_model_open.argtypes = [C.c_char_p, C.POINTER(vp)]
+    lib.dsd_model_close.argtypes = [vp]
+    lib.dsd_model_close.restype = None
+    lib.dsd_model_count.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    lib.dsd_model_find.argtypes = [vp, C.c_char_p]
+    lib.dsd_model_section.argtypes = [vp, i32, C.POINTER(DsdModelSectionInfo)]
+    lib.dsd_model_config.argtypes = [vp, i32, vp, i32]
+    lib.dsd_model_tensor.argtypes = [vp, i32, i32, C.POINTER(DsdModelTensorInfo)]
+    lib.dsd_model_meta_at.argtypes = [vp, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]
+    lib.dsd_model_meta.argtypes = [vp, C.c_char_p]
+    lib.dsd_model_meta.restype = C.c_char_p
+    lib.dsd_model_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

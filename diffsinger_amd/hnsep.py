@@ -218,16 +218,30 @@ class HnSep:
             raise RuntimeError("diffsinger_amd.hnsep.HnSep runs only on an MI355X (HIP) device; there is no CPU path")
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
-        c = self.config
-        cfg = _lib.DsdHnsepConfig(C.sizeof(_lib.DsdHnsepConfig), int(c["n_fft"]), int(c["hop_length"]), int(c["nout"]),
-                                  int(c["nout_lstm"]), int(bool(c["is_mono"])), idx)
+        cfg = self._native_config(idx)
         hp = C.c_void_p()
         rc = _lib.lib().dsd_hnsep_create(C.byref(cfg), C.byref(hp))
         if rc != 0:
             raise _lib.NativeLibraryError(f"dsd_hnsep_create failed ({rc}): {_lib.lib().dsd_last_error(None).decode()}")
         self._h = hp
+        self._sd = sd
         _lib.load_state_dict(hp, sd)
-        self.is_mono = bool(c["is_mono"])
+        self.is_mono = bool(self.config["is_mono"])
+
+    # -- model files (diffsinger_amd/modelfile.py: section_of / attach) --------------------------------------------------
+    def _native_config(self, device_index):
+        c = self.config
+        return _lib.DsdHnsepConfig(C.sizeof(_lib.DsdHnsepConfig), int(c["n_fft"]), int(c["hop_length"]), int(c["nout"]),
+                                   int(c["nout_lstm"]), int(bool(c["is_mono"])), device_index)
+
+    def _native_tensors(self):
+        """name -> tensor of what the handle loaded"""
+        return dict(self._sd)
+
+    def _install_native(self, handle, sd, device):
+        """run on `handle` (finalized, of this configuration, on `device`) from now on; `sd` is what it holds"""
+        _lib.lib().dsd_destroy(self._h)
+        self._h, self._sd, self.device = handle, sd, device
 
     def __del__(self):
         try:

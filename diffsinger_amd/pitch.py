@@ -208,14 +208,29 @@ class RMVPE:
         self.config = _config_of(sd)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", idx)
-        cfg = _lib.DsdRmvpeConfig(C.sizeof(_lib.DsdRmvpeConfig), self.config["n_blocks"], self.config["n_gru"],
-                                  self.config["en_de_layers"], self.config["inter_layers"], self.config["en_out_channels"], idx)
+        cfg = self._native_config(idx)
         hp = C.c_void_p()
         rc = _lib.lib().dsd_rmvpe_create(C.byref(cfg), C.byref(hp))
         if rc != 0:
             raise _lib.NativeLibraryError(f"dsd_rmvpe_create failed ({rc}): {_lib.lib().dsd_last_error(None).decode()}")
         self._h = hp
+        self._sd = sd
         _lib.load_state_dict(hp, sd)
+
+    # -- model files (diffsinger_amd/modelfile.py: section_of / attach) --------------------------------------------------
+    def _native_config(self, device_index):
+        return _lib.DsdRmvpeConfig(C.sizeof(_lib.DsdRmvpeConfig), self.config["n_blocks"], self.config["n_gru"],
+                                   self.config["en_de_layers"], self.config["inter_layers"], self.config["en_out_channels"],
+                                   device_index)
+
+    def _native_tensors(self):
+        """name -> tensor of what the handle loaded"""
+        return dict(self._sd)
+
+    def _install_native(self, handle, sd, device):
+        """run on `handle` (finalized, of this configuration, on `device`) from now on; `sd` is what it holds"""
+        _lib.lib().dsd_destroy(self._h)
+        self._h, self._sd, self.device = handle, sd, device
 
     def __del__(self):
         try:

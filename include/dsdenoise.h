@@ -36,6 +36,7 @@ extern "C" {
 #define DSD_EHIP (-3)     /* a HIP runtime call failed                          */
 #define DSD_ENOMEM (-4)   /* device allocation failed                           */
 #define DSD_ENOTFOUND (-5) /* unknown weight name                                */
+#define DSD_EIO (-6)      /* a path that cannot be opened or read (dsd_model_open) */
 
 typedef struct dsd_handle dsd_handle;
 
@@ -1166,6 +1167,85 @@ typedef struct dsd_dur_result {
 } dsd_dur_result;
 int dsd_dur_score(int32_t device, const dsd_dur_spec* spec, float* wdur_pred, float* wdur_gt, void* workspace,
                   dsd_dur_result* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Model files: every model a render needs in ONE file, opened without Python.  A file holds up to DSD_MODEL_MAX_SECTIONS
+ * named sections - each one handle: its kind (the DSD_* enum), the bytes of that kind's config struct and its tensors
+ * under the names, shapes and fp32 data dsd_load_weight takes - and a table of UTF-8 key / value strings for what a
+ * caller needs besides weights (timesteps, K_step, spec_min / spec_max, hop size, sample rate, the phoneme list; the
+ * value syntax is the caller's, the library stores and returns it).  The byte layout (format version 1, little-endian)
+ * is DESIGN.md section 4n; diffsinger_amd/modelfile.py writes it.
+ *
+ * Replaces: torch.load of a checkpoint + load_state_dict (utils/__init__.py:166-222 load_ckpt), the config.json beside a
+ * vocoder checkpoint (modules/nsf_hifigan/env.py, vocoders/nsf_hifigan.py:22-30) and the hparams a model's constructor
+ * reads - for a process that has none of them.
+ *
+ * dsd_model_open reads the whole file into host memory and validates ALL of it before it returns - magic, version, the
+ * recorded size against the file's, the CRC-32, every count, offset, length, name, shape and config size - so no accessor
+ * ever looks at an unchecked byte, and every pointer an accessor hands out (names, keys, values, tensor data: 64-byte
+ * aligned) points into that one buffer and stays valid until dsd_model_close.  The reader is host code only: no device is
+ * touched before dsd_model_create.  A failure of any call below leaves its message under dsd_last_error(NULL).
+ *   DSD_EIO     the path cannot be opened, is not a regular file, or cannot be read to its end
+ *   DSD_ENOMEM  no host memory for the file
+ *   DSD_EINVAL  a NULL argument, an index out of range, or a file that is refused (the message names the section, the
+ *               tensor and the field): bad magic; unknown format version; recorded size != file size; CRC mismatch; a count
+ *               over its limit; an offset, length or table past the end of the file; tensor data not 64-byte aligned; a
+ *               shape whose product is not the stored count, or overflows 64 bits; a negative dim; ndim > 4; a name or key
+ *               that is empty, longer than 255 bytes, holds a NUL or is not followed by one; two sections, two tensors of
+ *               a section or two keys with one name; an unknown kind; a config size that is not sizeof that kind's struct;
+ *               a stored struct_size that is not the config size (for kinds 0..2: a `backbone` that is not the kind); a
+ *               tensor on a DSD_MEL_ANALYSIS section
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_MODEL_FORMAT_VERSION 1
+#define DSD_MODEL_MAX_SECTIONS 64
+#define DSD_MODEL_MAX_TENSORS 65536     /* per section */
+#define DSD_MODEL_MAX_META 65536
+#define DSD_MODEL_MAX_NAME 255          /* bytes of a section name, tensor name or metadata key */
+#define DSD_MODEL_ALIGN 64              /* of tensor data, in the file and in memory */
+
+typedef struct dsd_model_file dsd_model_file;
+
+typedef struct dsd_model_section_info {
+    const char* name;
+    int32_t kind;            /* DSD_BACKBONE_WAVENET .. DSD_HNSEP_VR                                     */
+    int32_t config_size;     /* sizeof the kind's config struct: what dsd_model_config copies            */
+    int32_t n_tensors;
+    int64_t total_floats;    /* the sum of the tensors' counts                                           */
+} dsd_model_section_info;
+
+typedef struct dsd_model_tensor_info {
+    const char* name;        /* the reference state_dict key, as dsd_load_weight takes it                */
+    int32_t ndim;            /* 0 .. 4                                                                   */
+    int64_t shape[4];        /* shape[ndim ..] = 0                                                       */
+    int64_t count;           /* the product of shape[0 .. ndim) (1 for ndim == 0)                        */
+    const float* data;       /* host, count floats, DSD_MODEL_ALIGN-aligned                              */
+} dsd_model_tensor_info;
+
+int dsd_model_open(const char* path, dsd_model_file** out);      /* *out = NULL on failure */
+void dsd_model_close(dsd_model_file* f);                         /* NULL is fine */
+int dsd_model_count(const dsd_model_file* f, int32_t* n_sections, int32_t* n_meta);    /* either output may be NULL */
+/* index of the section called section_name, DSD_ENOTFOUND when there is none, DSD_EINVAL for a NULL argument */
+int dsd_model_find(const dsd_model_file* f, const char* section_name);
+int dsd_model_section(const dsd_model_file* f, int32_t i, dsd_model_section_info* out);
+/* Copies section i's config struct as stored; cfg_size must be its config_size.  The stored `device` field means nothing:
+   dsd_model_create overwrites it, and so does every other reader of the copy. */
+int dsd_model_config(const dsd_model_file* f, int32_t i, void* cfg_out, int32_t cfg_size);
+int dsd_model_tensor(const dsd_model_file* f, int32_t i, int32_t j, dsd_model_tensor_info* out);
+int dsd_model_meta_at(const dsd_model_file* f, int32_t k, const char** key, const char** value);
+/* the value stored under key, NULL if there is none (or an argument is NULL) */
+const char* dsd_model_meta(const dsd_model_file* f, const char* key);
+
+/*
+ * One section -> one finalized handle on `device`: the create call of the section's kind (dsd_create_any_width for
+ * DSD_BACKBONE_WAVENET / _LYNXNET / DSD_AUX_CONVNEXT, dsd_encoder_create, dsd_vocoder_create, dsd_token_encoder_create,
+ * dsd_mel_create, dsd_rmvpe_create, dsd_hnsep_create) on the stored config with `device` put into it, dsd_load_weight
+ * (on_device = 0) of every tensor in file order, dsd_finalize_weights; a DSD_MEL_ANALYSIS section stops after the create.
+ * The handle is what those calls would have given: release it with dsd_destroy; it does not refer to the file afterwards.
+ * On failure the half-built handle is destroyed, *out = NULL, the code is the failing call's (DSD_ESTATE for a section that
+ * lacks a tensor its model needs, DSD_ENOTFOUND for one it does not know) and the message under dsd_last_error(NULL) names
+ * the section, the tensor where one was being loaded, and that call's own message.
+ */
+int dsd_model_create(const dsd_model_file* f, int32_t section, int32_t device, dsd_handle** out);
 
 #ifdef __cplusplus
 }
