@@ -20,6 +20,8 @@
 //   RMVPE pitch extraction ........... rmvpe_api.hip  dsd_rmvpe_*  (its front end is mel_api.hip's mel_run)
 //   VR harmonic-noise separation ..... hnsep_api.hip  dsd_hnsep_*, dsd_base_harmonic, dsd_variance_curves
 // dsd_load_weight, dsd_finalize_weights and dsd_destroy hand an RMVPE or separator handle on to them.
+#include <mutex>
+
 #include "api_host.h"
 
 // ------------------------------------------------------------------------------------------
@@ -81,6 +83,49 @@ int select_device(const char* who, int device, bool say_range) {
         return say_range ? fail(nullptr, DSD_EINVAL, "%s: device %d out of range [0, %d)", who, device, ndev)
                          : fail(nullptr, DSD_EINVAL, "%s: device %d out of range", who, device);
     if (hipSetDevice(device) != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: hipSetDevice failed", who);
+    return DSD_OK;
+}
+
+// The kernel registry (dsd_internal.h, KernelReg): filled while the library is loaded, by the initialisers of the launch
+// helpers' instantiations - a function-local static, so their order across translation units does not matter.
+namespace {
+struct KernelEntry {
+    const void* host_stub;
+    int group;
+    std::vector<bool> ready;    // by device: the limit is raised there
+};
+std::vector<KernelEntry>& kernel_registry() {
+    static std::vector<KernelEntry> reg;
+    return reg;
+}
+std::mutex g_prepare_mutex;
+}  // namespace
+
+bool register_kernel(const void* host_stub, int group) {
+    kernel_registry().push_back({host_stub, group, {}});
+    return true;
+}
+
+int kernel_registry_get(int i, const void** host_stub, int* group) {
+    const auto& reg = kernel_registry();
+    if (i < 0 || i >= (int)reg.size()) return 0;
+    *host_stub = reg[i].host_stub;
+    *group = reg[i].group;
+    return 1;
+}
+
+// Every create function, after select_device(device) and outside any stream capture: raise the dynamic-LDS limit of each kernel
+// of `groups` (KernelGroup bits) that does not have it on this device yet (the attribute is kept per device).
+int prepare_kernels(const char* who, int device, int groups) {
+    std::lock_guard<std::mutex> lock(g_prepare_mutex);
+    for (KernelEntry& k : kernel_registry()) {
+        if (!(k.group & groups)) continue;
+        if ((int)k.ready.size() <= device) k.ready.resize(device + 1, false);
+        if (k.ready[device]) continue;
+        const hipError_t e = hipFuncSetAttribute(k.host_stub, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+        if (e != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: kernel attribute setup failed: %s", who, hipGetErrorString(e));
+        k.ready[device] = true;
+    }
     return DSD_OK;
 }
 
@@ -2154,15 +2199,8 @@ int check_config(const dsd_config* cfg, bool any_width, const char* who) {
 
 int create_impl(const dsd_config* cfg, dsd_handle** out, bool any_width, const char* who) {
     if (int rc = create_check(cfg, out, who, [&](const dsd_config* c) { return check_config(c, any_width, who); })) return rc;
-    hipError_t ie = gemm_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_layer_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_rowsplit_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_rows_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_layer_x3_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_LYNXNET) ie = lx_x3_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_WAVENET) ie = wn_edge_init_all();
-    if (ie == hipSuccess && cfg->backbone == DSD_BACKBONE_LYNXNET) ie = lx_layer_init_all();
-    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: kernel attribute setup failed: %s", who, hipGetErrorString(ie));
+    const int family = cfg->backbone == DSD_BACKBONE_WAVENET ? KG_WAVENET : cfg->backbone == DSD_BACKBONE_LYNXNET ? KG_LYNXNET : 0;
+    if (int rc = prepare_kernels(who, cfg->device, KG_GEMM | family)) return rc;
     dsd_handle* h = new_handle(cfg->backbone, cfg->device);
     h->cfg = *cfg;              // every other field is the caller's too
     h->opts = read_path_opts();
@@ -2297,8 +2335,7 @@ static int check_encoder_config(const dsd_encoder_config* cfg) {
 
 int dsd_encoder_create(const dsd_encoder_config* cfg, dsd_handle** out) {
     if (int rc = create_check(cfg, out, "dsd_encoder_create", check_encoder_config)) return rc;
-    hipError_t ie = gemm_init_all();
-    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
+    if (int rc = prepare_kernels("dsd_encoder_create", cfg->device, KG_GEMM)) return rc;
     dsd_handle* h = new_handle(DSD_ENC_FS2_ACOUSTIC, cfg->device);
     h->cfg.in_dims = cfg->vocab_size;
     h->cfg.n_feats = 1;
@@ -2476,8 +2513,7 @@ static int check_token_encoder_config(const dsd_token_encoder_config* cfg) {
 
 int dsd_token_encoder_create(const dsd_token_encoder_config* cfg, dsd_handle** out) {
     if (int rc = create_check(cfg, out, "dsd_token_encoder_create", check_token_encoder_config)) return rc;
-    hipError_t ie = gemm_init_all();
-    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_token_encoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
+    if (int rc = prepare_kernels("dsd_token_encoder_create", cfg->device, KG_GEMM)) return rc;
     dsd_handle* h = new_handle(DSD_ENC_FS2_TOKENS, cfg->device);
     h->cfg.in_dims = cfg->hidden_size;
     h->cfg.n_feats = 1;
@@ -2685,11 +2721,7 @@ static int check_vocoder_config(const dsd_vocoder_config* cfg) {
 
 int dsd_vocoder_create(const dsd_vocoder_config* cfg, dsd_handle** out) {
     if (int rc = create_check(cfg, out, "dsd_vocoder_create", check_vocoder_config)) return rc;
-    hipError_t ie = gemm_init_all();
-    if (ie == hipSuccess) ie = tconv_init_all();
-    if (ie == hipSuccess) ie = voc_noise_init_all();
-    if (ie == hipSuccess) ie = voc_x3_init_all();
-    if (ie != hipSuccess) return fail(nullptr, DSD_EHIP, "dsd_vocoder_create: kernel attribute setup failed: %s", hipGetErrorString(ie));
+    if (int rc = prepare_kernels("dsd_vocoder_create", cfg->device, KG_GEMM | KG_VOCODER)) return rc;
     dsd_handle* h = new_handle(DSD_VOC_NSF_HIFIGAN, cfg->device);
     h->cfg.in_dims = cfg->num_mels;
     h->cfg.n_feats = 1;

@@ -59,8 +59,30 @@ struct TimingSlot {
 };
 TimingSlot& timing_slot();      // thread-local (api.hip)
 
-template <typename K, typename P, typename... NameArgs>
-inline hipError_t launch_timed(K kern, dim3 grid, dim3 block, int lds, hipStream_t st, const P& p, const char* name_fmt,
+// The dynamic-LDS limit of every kernel instantiation is raised to all of gfx950's 160 KiB per CU, once per instantiation and
+// device and outside any stream capture.  A kernel form is declared where it is launched and nowhere else: launch_plain and
+// launch_timed take the kernel as a template argument, and instantiating either one puts that kernel into a registry when
+// the library is loaded - so whatever a code path can launch is in it, and nothing else is.  The create functions raise the
+// limits of their groups' entries (prepare_kernels, api.hip); each kernel file names its group once, at its top.
+constexpr int kMaxDynLds = 160 * 1024;
+enum KernelGroup { KG_GEMM = 1, KG_WAVENET = 2, KG_LYNXNET = 4, KG_VOCODER = 8 };
+bool register_kernel(const void* host_stub, int group);                    // api.hip; always true
+int kernel_registry_get(int i, const void** host_stub, int* group);        // entry i, or 0 past the last (tests/test_kernel_registry.py)
+int prepare_kernels(const char* who, int device, int groups);              // DSD_OK or DSD_EHIP through fail()
+template <auto kern, int GROUP>
+struct KernelReg {
+    static inline const bool registered = register_kernel(reinterpret_cast<const void*>(kern), GROUP);
+};
+
+template <auto kern, int GROUP, typename... Args>
+inline hipError_t launch_plain(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
+    (void)&KernelReg<kern, GROUP>::registered;       // (odr-use: the registration runs at load time, not here)
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+
+template <auto kern, int GROUP, typename P, typename... NameArgs>
+inline hipError_t launch_timed(dim3 grid, dim3 block, int lds, hipStream_t st, const P& p, const char* name_fmt,
                                NameArgs... name_args) {
     TimingSlot& ts = timing_slot();
     if (ts.e0 && ts.e1 && !ts.taken) {
@@ -70,18 +92,9 @@ inline hipError_t launch_timed(K kern, dim3 grid, dim3 block, int lds, hipStream
         snprintf(ts.name, sizeof(ts.name), name_fmt, name_args...);      // (every caller passes a literal)
 #pragma clang diagnostic pop
         ts.taken = true;
-    } else {
-        hipLaunchKernelGGL(kern, grid, block, lds, st, p);
+        return hipGetLastError();
     }
-    return hipGetLastError();
-}
-
-// The dynamic-LDS limit of every kernel instantiation is raised to all of gfx950's 160 KiB per CU, once per instantiation
-// and outside any stream capture (the *_init_all() functions; the launchers' attr_done flags).
-constexpr int kMaxDynLds = 160 * 1024;
-template <typename K>
-inline hipError_t allow_max_lds(K kern) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    return launch_plain<kern, GROUP>(grid, block, lds, st, p);
 }
 
 constexpr int kMaxTerms = 8;
@@ -184,7 +197,6 @@ bool gemm_has_fast(int taps, int nb, int S);
 int gemm_lds_bytes(int KC, int S);
 int gemm_lds_bytes_fast(int S, int stage, int taps, int K, int nb, int resident);
 int gemm_fast_chunk_rows(int taps, int nb);
-hipError_t gemm_init_all();
 
 // wn_layer.hip: one WaveNet residual layer (conv + FiLM + gate + out-proj + residual / skip) per launch, for grids of
 // at least one 32-frame tile per CU
@@ -214,26 +226,22 @@ struct WnLayerP {
 hipError_t launch_wn_layer(const WnLayerP& p, int C, int batch, hipStream_t st, int bn = 32);      // bn: 32, or 16 (wn_layer16_kernel)
 bool wn_layer16_supported(int C, int dil);
 bool wn_layer_supported(int C, int dil);
-hipError_t wn_layer_init_all();
 // wn_rowsplit.hip: the same layer as two launches with the 2C rows split over 2C / 64 workgroups per 32-frame tile, for
 // grids too small for full-row tiles.  which = 0: conv + FiLM + gate (xin -> z); 1: out-proj + residual / skip (in place
 // when xout == xin).  layout = wn_rowsplit_conv_layout(p, batch, bn, DSD_RS_CONV_Q): 0 / 1 the direct K-half / K-quarter conv, 2 the
 // K-quarter conv on Winograd F(2,3) operands - p.Aconv stays the layer's direct packed matrix, the kernel forms G1, G2 from its taps
 int wn_rowsplit_conv_layout(const WnLayerP& p, int batch, int bn, int conv_q);
 hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C, int batch, int bn, int layout, hipStream_t st);
-hipError_t wn_rowsplit_init_all();
 bool wn_rowsplit_supported(int C, int dil, long Ts);
 
 // wn_layer_x3.hip: the fused layer in split-bf16 arithmetic (opt-in precision mode); p.Aconv / p.Aout = the layer's bf16x3
 // weight streams [wave][k32 step][row block][hi | lo][lane][8 bf16]
 hipError_t launch_wn_layer_x3(const WnLayerP& p, int C, int batch, hipStream_t st);
-hipError_t wn_layer_x3_init_all();
 bool wn_layer_x3_supported(int C, int dil);
 
 // wn_rows.hip: the same two launches with 128 or 256 rows per workgroup (4 / 2 workgroups per 32-frame tile), for grids between
 // the one-utterance case and one tile per CU
 hipError_t launch_wn_rows(const WnLayerP& p, int which, int C, int batch, int rows, hipStream_t st);
-hipError_t wn_rows_init_all();
 bool wn_rows_supported(int C, int dil, long Ts);
 
 // wn_edge.hip: the WaveNet's small GEMMs around the residual layers (skip projection -> output projection + solver update ->
@@ -271,7 +279,6 @@ struct WnEdgeP {
     int ncg;
 };
 hipError_t launch_wn_edge(const WnEdgeP& p, int C, int ncb, int nwg, hipStream_t st);
-hipError_t wn_edge_init_all();
 bool wn_edge_supported(int C, int FM);
 
 // lynx_layer.hip: LYNXNet's two pointwise GEMMs with the whole K extent of a 32-frame tile resident in LDS (batched grids)
@@ -310,12 +317,10 @@ bool lx_layer_supported(int C, int inner);
 bool lx_pw1p_force_ok(int inner, int force);
 hipError_t launch_lx_pw2q(const LxLayerP& p, int C, hipStream_t st);      // pw2 with 128 rows per workgroup: one-utterance grids
 bool lx_pw2q_supported(int C, int inner);
-hipError_t lx_layer_init_all();
 
 // lynx_x3.hip: the two pointwise GEMMs in split-bf16 arithmetic (opt-in precision mode); p.A1 / p.A2 = the layer's bf16x3 weight
 // streams [row tile][wave][k32 step][row block][hi | lo][lane][8 bf16]
 hipError_t launch_lx_x3(const LxLayerP& p, int which, int C, int ncb, hipStream_t st);     // ncb: 2 = 32-frame tiles, 4 = 64-frame tiles
-hipError_t lx_x3_init_all();
 bool lx_x3_supported(int C, int inner);
 
 // aux_kernels.hip
@@ -354,7 +359,6 @@ struct TConvP {
     int ncg, tiles;
 };
 int tconv_lds_bytes(int ci, int co, int taps, int SP);
-hipError_t tconv_init_all();
 hipError_t launch_tconv(const TConvP& p, int ci, int co, int batch, hipStream_t st);
 // voc_x3.hip: a residual-block convolution Conv1d(C -> C, k taps, dilated) of the vocoder in split-bf16 arithmetic (opt-in
 // precision mode):  out = lrelu(bias + W * lrelu(x, slope_in), slope_out) (+ res), a slope of 1 = no activation
@@ -380,7 +384,6 @@ struct VocX3P {
 int voc_x3_mbw(int C);                              // 16-row blocks per wave: the stream holds 4 * voc_x3_mbw(C) * 16 rows, zero above C
 int voc_x3_max_ncb(int C, int taps, int dil);       // widest tile in 16-frame blocks (4 or 2) whose LDS images fit; 0: not supported
 hipError_t launch_voc_x3(const VocX3P& p, int ncb, int ntiles, hipStream_t st);
-hipError_t voc_x3_init_all();
 // vocoder_kernels.hip (NSF-HiFiGAN source, noise convs, residual-block average)
 hipError_t launch_voc_source(const float* f0, const float* rand_ini, const float* noise, const float* lin_w,
                              const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp, float noise_std,
@@ -391,7 +394,6 @@ hipError_t launch_voc_fast_source(const float* f0, int B, int T, int upp, float 
                                   hipStream_t st, const int* lens = nullptr);
 constexpr int VOC_NOISE_NQ = 16;                    // frames per thread of the noise conv
 int voc_noise_groups(int C, int sf, int ksz);       // frame groups per workgroup whose source window fits in LDS; 0: none does
-hipError_t voc_noise_init_all();
 // lens_q / lens_up (ragged: per-item output frames / source samples) both or neither
 hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, const float* bias, int B, int C, int Tq,
                                  int Tsq, int sf, int ksz, long Tup, int Tsu, hipStream_t st, const int* lens_q = nullptr,

@@ -31,6 +31,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_GEMM;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 __device__ __forceinline__ float act_apply(float v, int act) {
     switch (act) {
@@ -866,13 +867,13 @@ int gemm_lds_bytes_fast(int S, int stage, int taps, int K, int nb, int resident)
     return ((resident ? 4 : 2) * gemm_fast_chunk_rows(taps, nb) * S + (stage == ST_LN ? 2 * 32 * (nb ? nb : 1) : 0)) * 4;
 }
 
-template <int STAGE, int TAPS, int EPI, int NB, int SW, int RES = 0, int WN = 2, int RAG = 0>
+template <int STAGE, int TAPS, int EPI, int NB, int SW, int RES, int WN, int RAG>
 static hipError_t launch_one(const GemmP& p, int batch, hipStream_t st) {
     const int lds = p.lds_bytes;
     dim3 grid((RAG ? p.ncg : batch * p.tiles_per_b) * p.mtiles, 1, 1);
     if (grid.x == 0) return hipSuccess;          // a ragged batch of empty items
-    return launch_timed(gemm_kernel<STAGE, TAPS, EPI, NB, SW, RES, WN, RAG>, grid, dim3(256), lds, st, p,
-                        "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", STAGE, TAPS, EPI, NB, SW, RES, WN, RAG);
+    return launch_timed<gemm_kernel<STAGE, TAPS, EPI, NB, SW, RES, WN, RAG>, kGroup>(
+        grid, dim3(256), lds, st, p, "gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", STAGE, TAPS, EPI, NB, SW, RES, WN, RAG);
 }
 
 // fast instantiations exist for S = 48 / 80 (32-frame tiles) and 80 / 112 (64-frame tiles); 1x1 GEMMs have
@@ -883,7 +884,7 @@ bool gemm_has_fast(int taps, int nb, int S) {
     return S == 80 || (taps == 3 && S == 112);
 }
 
-template <int STAGE, int TAPS, int EPI, int RAG = 0>
+template <int STAGE, int TAPS, int EPI, int RAG>
 static hipError_t dispatch(const GemmP& p, int nb, int fast, int batch, hipStream_t st) {
     if constexpr (STAGE != ST_LN && EPI != EP_SWIGLU) {
         if (nb == 0) {      // narrow tiles: fast path only (the host never asks for them otherwise)
@@ -910,123 +911,11 @@ static hipError_t dispatch(const GemmP& p, int nb, int fast, int batch, hipStrea
     return launch_one<STAGE, TAPS, EPI, 2, 0, 0, 2, RAG>(p, batch, st);
 }
 
-template <int STAGE, int TAPS, int EPI, int RAG = 0>
-static hipError_t attr_all() {
-    hipError_t e;
-    if constexpr (STAGE != ST_LN && EPI != EP_SWIGLU) {
-        if constexpr (TAPS == 1) {
-            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 16, 1, 1, RAG>)) != hipSuccess) return e;
-            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 16, 0, 1, RAG>)) != hipSuccess) return e;
-        } else {
-            if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 0, 1, RAG>)) != hipSuccess) return e;
-        }
-    }
-    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 0, 0, 2, RAG>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 0, 0, 2, RAG>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 0, 2, RAG>)) != hipSuccess) return e;
-    if constexpr (TAPS == 1)
-        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 48, 1, 2, RAG>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 80, 0, 2, RAG>)) != hipSuccess) return e;
-    if constexpr (TAPS == 3) {
-        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 1, 80, 0, 2, RAG>)) != hipSuccess) return e;
-        if ((e = allow_max_lds(gemm_kernel<STAGE, TAPS, EPI, 2, 112, 0, 2, RAG>)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Raise the dynamic-LDS limit of every instantiation once, outside any stream capture.
-hipError_t gemm_init_all() {
-    hipError_t e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_ACT>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_SCALE, 1, EP_BIAS_ACT>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_FILM, 3, EP_GATE>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_RESSKIP>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_LINCOMB>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_RELU, 1, EP_LINCOMB>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_SWIGLU>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_LINCOMB>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_BIAS_ACT>()) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0>)) != hipSuccess) return e;
-    // ragged batches (RAG = 1): every GEMM of the denoisers and of the aux decoder
-    if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_SCALE, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_FILM, 3, EP_GATE, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_RESSKIP, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_RELU, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_SWIGLU, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_PLAIN, 1, EP_BIAS_RES, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_LINCOMB, 1>()) != hipSuccess) return e;
-    if ((e = attr_all<ST_LN, 1, EP_BIAS_ACT, 1>()) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    // NSF-HiFiGAN: leaky-ReLU staged k-tap convs, residual epilogue, transposed-conv scatter (generic path only)
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 2, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 2, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 2, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 1, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 2, 0>)) != hipSuccess) return e;
-    // ... and their ragged forms (dsd_vocode_ragged; conv_pre is the aux decoder's ST_PLAIN k-tap instantiation above)
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_ACT, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_PLAIN, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_BIAS_RES, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 1, 0, 0, 2, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(gemm_kernel<ST_LRELU, 0, EP_SCATTER, 2, 0, 0, 2, 1>)) != hipSuccess) return e;
-    return hipSuccess;
-}
-
+// Every (stage, taps, epilogue) combination the host asks for; RAG = 1: the same choices for a ragged batch
+template <int RAG>
+static hipError_t launch_gemm_as(const GemmP& p, int stage, int taps, int epi, int nb, int fast, int batch, hipStream_t st) {
 #define DSD_CASE(ST, TP, EP) \
-    if (stage == ST && taps == TP && epi == EP) return dispatch<ST, TP, EP>(p, nb, fast, batch, st);
-
-hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int fast, int batch, hipStream_t st) {
-    if (p.cgmap) {      // ragged batch: the same choices with the RAG = 1 instantiations
-#define DSD_CASE_R(ST, TP, EP) \
-        if (stage == ST && taps == TP && epi == EP) return dispatch<ST, TP, EP, 1>(p, nb, fast, batch, st);
-        DSD_CASE_R(ST_PLAIN, 1, EP_BIAS_ACT)
-        DSD_CASE_R(ST_SCALE, 1, EP_BIAS_ACT)
-        DSD_CASE_R(ST_FILM, 3, EP_GATE)
-        DSD_CASE_R(ST_PLAIN, 1, EP_RESSKIP)
-        DSD_CASE_R(ST_PLAIN, 1, EP_LINCOMB)
-        DSD_CASE_R(ST_RELU, 1, EP_LINCOMB)
-        DSD_CASE_R(ST_LN, 1, EP_SWIGLU)
-        DSD_CASE_R(ST_PLAIN, 1, EP_BIAS_RES)
-        DSD_CASE_R(ST_LN, 1, EP_LINCOMB)
-        DSD_CASE_R(ST_LN, 1, EP_BIAS_ACT)
-#undef DSD_CASE_R
-        if (stage == ST_PLAIN && taps == 1 && epi == EP_LYNX_NEXT && nb >= 1) {
-            if (nb == 1) return (fast && p.S == 48) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48, 0, 2, 1>(p, batch, st)
-                                                    : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0, 0, 2, 1>(p, batch, st);
-            return (fast && p.S == 80) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, 1>(p, batch, st)
-                                       : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, 1>(p, batch, st);
-        }
-        // k-tap convs with the kernel size taken from the argument block: the aux decoder's, NSF-HiFiGAN's
-#define DSD_DENSE_R(ST, EP)                                                                                       \
-        if (stage == ST && epi == EP && taps == p.taps && !fast && nb >= 1)                                         \
-            return nb == 1 ? launch_one<ST, 0, EP, 1, 0, 0, 2, 1>(p, batch, st) : launch_one<ST, 0, EP, 2, 0, 0, 2, 1>(p, batch, st);
-        DSD_DENSE_R(ST_PLAIN, EP_BIAS_ACT)
-        DSD_DENSE_R(ST_LRELU, EP_BIAS_ACT)
-        DSD_DENSE_R(ST_PLAIN, EP_BIAS_RES)
-        DSD_DENSE_R(ST_LRELU, EP_BIAS_RES)
-        DSD_DENSE_R(ST_LRELU, EP_SCATTER)
-#undef DSD_DENSE_R
-        return hipErrorInvalidValue;
-    }
+    if (stage == ST && taps == TP && epi == EP) return dispatch<ST, TP, EP, RAG>(p, nb, fast, batch, st);
     DSD_CASE(ST_PLAIN, 1, EP_BIAS_ACT)
     DSD_CASE(ST_SCALE, 1, EP_BIAS_ACT)
     DSD_CASE(ST_FILM, 3, EP_GATE)
@@ -1037,16 +926,18 @@ hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int
     DSD_CASE(ST_PLAIN, 1, EP_BIAS_RES)
     DSD_CASE(ST_LN, 1, EP_LINCOMB)
     DSD_CASE(ST_LN, 1, EP_BIAS_ACT)
+#undef DSD_CASE
     if (stage == ST_PLAIN && taps == 1 && epi == EP_LYNX_NEXT && nb >= 1) {       // 2 x 2 layout only, no resident variant
-        if (nb == 1) return (fast && p.S == 48) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48>(p, batch, st)
-                                                : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0>(p, batch, st);
-        return (fast && p.S == 80) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80>(p, batch, st)
-                                   : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0>(p, batch, st);
+        if (nb == 1) return (fast && p.S == 48) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 48, 0, 2, RAG>(p, batch, st)
+                                                : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 1, 0, 0, 2, RAG>(p, batch, st);
+        return (fast && p.S == 80) ? launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 80, 0, 2, RAG>(p, batch, st)
+                                   : launch_one<ST_PLAIN, 1, EP_LYNX_NEXT, 2, 0, 0, 2, RAG>(p, batch, st);
     }
-#define DSD_DENSE(ST, EP)                                                                   \
-    if (stage == ST && epi == EP && taps == p.taps && !fast && nb >= 1)                      \
-        return nb == 1 ? launch_one<ST, 0, EP, 1, 0>(p, batch, st) : launch_one<ST, 0, EP, 2, 0>(p, batch, st);
-    // dense k-tap convs with the kernel size taken from the argument block (generic path)
+    // k-tap convs with the kernel size taken from the argument block (generic path): the aux decoder's, and NSF-HiFiGAN's
+    // leaky-ReLU staged convs, residual epilogue and transposed-conv scatter
+#define DSD_DENSE(ST, EP)                                                                                           \
+    if (stage == ST && epi == EP && taps == p.taps && !fast && nb >= 1)                                              \
+        return nb == 1 ? launch_one<ST, 0, EP, 1, 0, 0, 2, RAG>(p, batch, st) : launch_one<ST, 0, EP, 2, 0, 0, 2, RAG>(p, batch, st);
     DSD_DENSE(ST_PLAIN, EP_BIAS_ACT)
     DSD_DENSE(ST_LRELU, EP_BIAS_ACT)
     DSD_DENSE(ST_PLAIN, EP_BIAS_RES)
@@ -1054,6 +945,11 @@ hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int
     DSD_DENSE(ST_LRELU, EP_SCATTER)
 #undef DSD_DENSE
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_gemm(const GemmP& p, int stage, int taps, int epi, int nb, int fast, int batch, hipStream_t st) {
+    return p.cgmap ? launch_gemm_as<1>(p, stage, taps, epi, nb, fast, batch, st)
+                   : launch_gemm_as<0>(p, stage, taps, epi, nb, fast, batch, st);
 }
 
 }  // namespace dsd

@@ -21,6 +21,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_LYNXNET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 #ifdef DSD_STAMPS
 // lx_pw1p_kernel, wave 0 of each workgroup: [0] start, [1] activation tile staged (after the barrier), [2] sum over the row
@@ -1020,14 +1021,8 @@ bool lx_pw2q_supported(int C, int inner) { return (C == 1024 && inner == 2048) |
 
 template <int KQ, int RAG>
 static hipError_t lx_launch_pw2q(const LxLayerP& p, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = allow_max_lds(lx_pw2q_kernel<KQ, RAG>);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    if (nwg == 0) return hipSuccess;
-    return launch_timed(lx_pw2q_kernel<KQ, RAG>, dim3(nwg), dim3(512), lx_pw2q_lds_bytes(), st, p, "lx_pw2q_kernel<%d, %d>", KQ, RAG);
+    if (nwg == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<lx_pw2q_kernel<KQ, RAG>, kGroup>(dim3(nwg), dim3(512), lx_pw2q_lds_bytes(), st, p, "lx_pw2q_kernel<%d, %d>", KQ, RAG);
 }
 
 // pw2 with 128 rows per workgroup (one-utterance grids); p as for launch_lx_layer
@@ -1050,15 +1045,8 @@ bool lx_layer_supported(int C, int inner) {
 
 template <int KT, int RAG>
 static hipError_t lx_launch_pw1p(const LxLayerP& p, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = allow_max_lds(lx_pw1p_kernel<KT, RAG>);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    if (nwg == 0) return hipSuccess;
     const int ldsb = lx_pw1p_lds_bytes(KT);
-    return launch_timed(lx_pw1p_kernel<KT, RAG>, dim3(nwg), dim3(256), ldsb, st, p, "lx_pw1p_kernel<%d, %d>", KT, RAG);
+    return launch_timed<lx_pw1p_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw1p_kernel<%d, %d>", KT, RAG);
 }
 
 // pw1 with the activation tile staged once per workgroup and a loop over row tiles: how many row-tile GROUPS (= workgroups per
@@ -1088,75 +1076,38 @@ bool lx_pw1p_force_ok(int inner, int force) {
 
 template <int KT, int RAG>
 static hipError_t lx_launch(const LxLayerP& p, int which, int nwg, hipStream_t st) {
-    static bool attr1 = false, attr2 = false;
-    if (which == 0 && !attr1) {
-        hipError_t e = allow_max_lds(lx_pw1_kernel<KT, RAG>);
-        if (e != hipSuccess) return e;
-        attr1 = true;
-    }
-    if (which == 1 && !attr2) {
-        hipError_t e = allow_max_lds(lx_pw2_kernel<KT, RAG>);
-        if (e != hipSuccess) return e;
-        attr2 = true;
-    }
-    if (nwg == 0) return hipSuccess;
     const int ldsb = lx_lds_bytes(KT);
-    if (which == 0) return launch_timed(lx_pw1_kernel<KT, RAG>, dim3(nwg), dim3(256), ldsb, st, p, "lx_pw1_kernel<%d, %d>", KT, RAG);
-    return launch_timed(lx_pw2_kernel<KT, RAG>, dim3(nwg), dim3(256), ldsb, st, p, "lx_pw2_kernel<%d, %d>", KT, RAG);
+    if (which == 0) return launch_timed<lx_pw1_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw1_kernel<%d, %d>", KT, RAG);
+    return launch_timed<lx_pw2_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw2_kernel<%d, %d>", KT, RAG);
 }
 
 template <int NP, int RAG>
 static hipError_t lx_launch_pw2d(const LxLayerP& p, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = allow_max_lds(lx_pw2d_kernel<NP, RAG>);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    if (nwg == 0) return hipSuccess;
-    return launch_timed(lx_pw2d_kernel<NP, RAG>, dim3(nwg), dim3(256), (2 * 512 * 32 + 1024) * 4, st, p, "lx_pw2d_kernel<%d, %d>", NP, RAG);
+    return launch_timed<lx_pw2d_kernel<NP, RAG>, kGroup>(dim3(nwg), dim3(256), (2 * 512 * 32 + 1024) * 4, st, p, "lx_pw2d_kernel<%d, %d>", NP, RAG);
 }
 
 // which = 0: pw1 (LayerNorm -> C -> 2 inner -> SwiGLU);  1: pw2 (inner -> C + residual + next-layer transition)
 hipError_t launch_lx_layer(const LxLayerP& p, int which, int C, int pw1p, int cus, hipStream_t st) {
+    if (C != 1024 && C != 512) return hipErrorInvalidValue;
     const int nft = p.cgmap ? p.ncg : p.nft;
+    if (nft == 0) return hipSuccess;          // a ragged batch of empty items
     const int mtiles = which == 0 ? (2 * p.inner) / 512 : C / 512;
     const int nwg = nft * mtiles;
-    const int groups = which == 0 && nft > 0 ? lx_pw1p_groups(nft, mtiles, pw1p, cus) : 0;
-    if (which == 0 && (nft == 0 || groups > 0)) {      // (nft == 0: attribute set-up of both forms at create)
+    const int groups = which == 0 ? lx_pw1p_groups(nft, mtiles, pw1p, cus) : 0;
+    if (groups > 0) {
         LxLayerP q = p;
-        q.rt_groups = nft == 0 ? 1 : groups;
-        const int nwg1 = nft * q.rt_groups;
-        hipError_t e = C == 1024 ? (q.cgmap ? lx_launch_pw1p<1024, 1>(q, nwg1, st) : lx_launch_pw1p<1024, 0>(q, nwg1, st))
-                     : C == 512 ? (q.cgmap ? lx_launch_pw1p<512, 1>(q, nwg1, st) : lx_launch_pw1p<512, 0>(q, nwg1, st))
-                                : hipErrorInvalidValue;
-        if (nft != 0 || e != hipSuccess) return e;
+        q.rt_groups = groups;
+        const int nwg1 = nft * groups;
+        if (C == 1024) return q.cgmap ? lx_launch_pw1p<1024, 1>(q, nwg1, st) : lx_launch_pw1p<1024, 0>(q, nwg1, st);
+        return q.cgmap ? lx_launch_pw1p<512, 1>(q, nwg1, st) : lx_launch_pw1p<512, 0>(q, nwg1, st);
     }
     // pw2 with double-buffered 512-channel half-phases (inner = 1024 or 2048); lx_pw2_kernel's two-phase form for inner = 512
-    if (which == 1 && (p.inner == 2048 || p.inner == 1024) && (C == 1024 || C == 512)) {
-        hipError_t e = p.inner == 2048 ? (p.cgmap ? lx_launch_pw2d<4, 1>(p, nwg, st) : lx_launch_pw2d<4, 0>(p, nwg, st))
-                                       : (p.cgmap ? lx_launch_pw2d<2, 1>(p, nwg, st) : lx_launch_pw2d<2, 0>(p, nwg, st));
-        if (nwg != 0 || e != hipSuccess) return e;
+    if (which == 1 && (p.inner == 2048 || p.inner == 1024)) {
+        if (p.inner == 2048) return p.cgmap ? lx_launch_pw2d<4, 1>(p, nwg, st) : lx_launch_pw2d<4, 0>(p, nwg, st);
+        return p.cgmap ? lx_launch_pw2d<2, 1>(p, nwg, st) : lx_launch_pw2d<2, 0>(p, nwg, st);
     }
     if (C == 1024) return p.cgmap ? lx_launch<1024, 1>(p, which, nwg, st) : lx_launch<1024, 0>(p, which, nwg, st);
-    if (C == 512) return p.cgmap ? lx_launch<512, 1>(p, which, nwg, st) : lx_launch<512, 0>(p, which, nwg, st);
-    return hipErrorInvalidValue;
-}
-
-hipError_t lx_layer_init_all() {
-    LxLayerP p{};
-    hipError_t e;
-    for (int C : {512, 1024})
-        for (int rag = 0; rag < 2; ++rag) {
-            p.inner = 2 * C;
-            p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
-            p.ncg = 0;
-            p.nft = 0;
-            if ((e = launch_lx_layer(p, 0, C, -1, 256, nullptr)) != hipSuccess) return e;
-            if ((e = launch_lx_layer(p, 1, C, -1, 256, nullptr)) != hipSuccess) return e;
-            if ((e = launch_lx_pw2q(p, C, nullptr)) != hipSuccess) return e;
-        }
-    return hipSuccess;
+    return p.cgmap ? lx_launch<512, 1>(p, which, nwg, st) : lx_launch<512, 0>(p, which, nwg, st);
 }
 
 }  // namespace dsd

@@ -19,6 +19,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_LYNXNET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 #ifdef DSD_STAMPS
 // [pw1 / pw2][workgroup][0..7]: s_memtime at the phase boundaries of wave 0 (tools/stamp_lynx_x3.py)
@@ -338,14 +339,9 @@ bool lx_x3_supported(int C, int inner) { return (C == 1024 && inner == 2048) || 
 
 template <int MODE, int KT, int RAG, int NCB>
 static hipError_t lx_x3_launch(const LxLayerP& p, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = allow_max_lds(lx_x3_kernel<MODE, KT, RAG, NCB>);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    if (nwg == 0) return hipSuccess;
-    return launch_timed(lx_x3_kernel<MODE, KT, RAG, NCB>, dim3(nwg), dim3(256), lx_x3_lds_bytes(KT, NCB), st, p, "lx_x3_kernel<%d, %d, %d, %d>", MODE, KT, RAG, NCB);
+    if (nwg == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<lx_x3_kernel<MODE, KT, RAG, NCB>, kGroup>(dim3(nwg), dim3(256), lx_x3_lds_bytes(KT, NCB), st, p,
+                                                                  "lx_x3_kernel<%d, %d, %d, %d>", MODE, KT, RAG, NCB);
 }
 
 // which = 0: pw1 (p.A1 = the bf16x3 stream), 1: pw2 (p.A2); ncb = 2: 32-frame tiles, 4: 64-frame tiles (p.tiles_per_b / nft / cgmap
@@ -366,22 +362,6 @@ hipError_t launch_lx_x3(const LxLayerP& p, int which, int C, int ncb, hipStream_
     if (p.inner == 2048) LX3_CASE(1, 2048)
     LX3_CASE(1, 1024)
 #undef LX3_CASE
-}
-
-hipError_t lx_x3_init_all() {
-    LxLayerP p{};
-    hipError_t e;
-    for (int C : {512, 1024})
-        for (int rag = 0; rag < 2; ++rag)
-            for (int ncb : {2, 4}) {
-                p.inner = 2 * C;
-                p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
-                p.ncg = 0;
-                p.nft = 0;
-                if ((e = launch_lx_x3(p, 0, C, ncb, nullptr)) != hipSuccess) return e;
-                if ((e = launch_lx_x3(p, 1, C, ncb, nullptr)) != hipSuccess) return e;
-            }
-    return hipSuccess;
 }
 
 }  // namespace dsd

@@ -15,6 +15,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_VOCODER;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 constexpr int TC_TT = 256;          // frames per workgroup (4 waves x 4 blocks of 16)
 
@@ -129,28 +130,9 @@ int tconv_lds_bytes(int ci, int co, int taps, int SP) {
 
 template <int CI, int CO, int RAG>
 static hipError_t tconv_go(const TConvP& p, int batch, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = allow_max_lds(tconv_kernel<CI, CO, RAG>);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    if (RAG) {
-        if (p.ncg == 0) return hipSuccess;
-        hipLaunchKernelGGL((tconv_kernel<CI, CO, RAG>), dim3(p.ncg), dim3(256), p.lds_bytes, st, p);
-    } else {
-        hipLaunchKernelGGL((tconv_kernel<CI, CO, RAG>), dim3((p.T + TC_TT - 1) / TC_TT, batch), dim3(256), p.lds_bytes, st, p);
-    }
-    return hipGetLastError();
-}
-
-hipError_t tconv_init_all() {      // raise the dynamic-LDS limits once, outside any stream capture
-    hipError_t e;
-    if ((e = allow_max_lds(tconv_kernel<16, 16, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(tconv_kernel<32, 32, 0>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(tconv_kernel<16, 16, 1>)) != hipSuccess) return e;
-    if ((e = allow_max_lds(tconv_kernel<32, 32, 1>)) != hipSuccess) return e;
-    return hipSuccess;
+    if (RAG && p.ncg == 0) return hipSuccess;          // a ragged batch of empty items
+    const dim3 grid = RAG ? dim3(p.ncg) : dim3((p.T + TC_TT - 1) / TC_TT, batch);
+    return launch_plain<tconv_kernel<CI, CO, RAG>, kGroup>(grid, dim3(256), p.lds_bytes, st, p);
 }
 
 hipError_t launch_tconv(const TConvP& p, int ci, int co, int batch, hipStream_t st) {

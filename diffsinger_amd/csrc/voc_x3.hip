@@ -30,6 +30,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_VOCODER;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 // MBW: 16-row blocks per wave; NCB: 16-frame column blocks per tile; RAG: ragged batch (the valid (item, tile) list)
 template <int MBW, int NCB, int RAG>
@@ -197,15 +198,9 @@ int voc_x3_max_ncb(int C, int taps, int dil) {
 
 template <int MBW, int NCB, int RAG>
 static hipError_t voc_x3_launch(const VocX3P& p, int ntiles, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(voc_conv_x3_kernel<MBW, NCB, RAG>);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (ntiles == 0) return hipSuccess;
-    return launch_timed(voc_conv_x3_kernel<MBW, NCB, RAG>, dim3(ntiles), dim3(256), voc_x3_lds_bytes(p.C, p.HL, NCB), st, p,
-                        "voc_conv_x3_kernel<%d, %d, %d>", MBW, NCB, RAG);
+    if (ntiles == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<voc_conv_x3_kernel<MBW, NCB, RAG>, kGroup>(dim3(ntiles), dim3(256), voc_x3_lds_bytes(p.C, p.HL, NCB), st, p,
+                                                                   "voc_conv_x3_kernel<%d, %d, %d>", MBW, NCB, RAG);
 }
 
 template <int MBW>
@@ -224,21 +219,6 @@ hipError_t launch_voc_x3(const VocX3P& p, int ncb, int ntiles, hipStream_t st) {
         case 4: return voc_x3_pick<4>(p, ncb, ntiles, st);
     }
     return hipErrorInvalidValue;
-}
-
-hipError_t voc_x3_init_all() {
-    VocX3P p{};
-    p.taps = 1;
-    p.dil = 1;
-    hipError_t e;
-    for (int C : {64, 128, 192, 256})
-        for (int ncb : {2, 4})
-            for (int rag = 0; rag < 2; ++rag) {
-                p.C = C;
-                p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
-                if ((e = launch_voc_x3(p, ncb, 0, nullptr)) != hipSuccess) return e;
-            }
-    return hipSuccess;
 }
 
 }  // namespace dsd

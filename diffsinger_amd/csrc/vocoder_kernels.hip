@@ -9,6 +9,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_VOCODER;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 // ---------------------------------------------------------------------------------------------
 // SineGen._f02sine, frame level (models.py:139-142): the phase each frame starts from is the running fp32 sum of
@@ -239,13 +240,12 @@ hipError_t launch_voc_noise_conv(float* x, const float* har, const float* w, con
     const int cpb = C < 256 ? C : 256, fpb = groups * VOC_NQ;
     const int nwin = (fpb - 1) * sf + ksz;
     const dim3 grid((Tq + fpb - 1) / fpb, (C + cpb - 1) / cpb, B);
+    // (the window is dynamic LDS beyond the default 64 KiB: the one kernel of this file that goes through the registry)
     if (lens_q)
-        hipLaunchKernelGGL(voc_noise_conv_kernel<1>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
-                           ksz, Tup, Tsu, groups, lens_q, lens_up);
-    else
-        hipLaunchKernelGGL(voc_noise_conv_kernel<0>, grid, dim3(256), nwin * sizeof(float), st, x, har, w, bias, C, Tq, Tsq, sf,
-                           ksz, Tup, Tsu, groups, nullptr, nullptr);
-    return hipGetLastError();
+        return launch_plain<voc_noise_conv_kernel<1>, kGroup>(grid, dim3(256), nwin * (int)sizeof(float), st, x, har, w, bias, C, Tq,
+                                                              Tsq, sf, ksz, Tup, Tsu, groups, lens_q, lens_up);
+    return launch_plain<voc_noise_conv_kernel<0>, kGroup>(grid, dim3(256), nwin * (int)sizeof(float), st, x, har, w, bias, C, Tq, Tsq,
+                                                          sf, ksz, Tup, Tsu, groups, (const int*)nullptr, (const int*)nullptr);
 }
 
 // frame groups per workgroup of voc_noise_conv_kernel: one per min(C, 256) threads, fewer where the source window of that many
@@ -256,13 +256,6 @@ int voc_noise_groups(int C, int sf, int ksz) {
     if (room < (long)(VOC_NQ - 1) * sf) return 0;
     const long fit = (room / sf + 1) / VOC_NQ;
     return (int)std::min<long>(256 / cpb, fit);
-}
-
-// the noise conv's window is dynamic LDS beyond the default 64 KiB: raise the limit once, outside any stream capture
-hipError_t voc_noise_init_all() {
-    hipError_t e = allow_max_lds(voc_noise_conv_kernel<0>);
-    if (e == hipSuccess) e = allow_max_lds(voc_noise_conv_kernel<1>);
-    return e;
 }
 
 // x[row][t] += sigma * noise[row][t]  (models.py:272-273; x rows are padded to Ts, the caller's noise is dense)

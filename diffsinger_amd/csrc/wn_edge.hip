@@ -18,6 +18,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_WAVENET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 #ifdef DSD_STAMPS
 // [launch with / without a fused input projection][workgroup][0..9]: s_memtime at the phase boundaries (wave 0)
@@ -386,15 +387,9 @@ bool wn_edge_supported(int C, int FM) { return (C == 256 || C == 192 || C == 128
 
 template <int NCH, int FMB, int NCB, int RAG>
 static hipError_t edge_launch(const WnEdgeP& p, int nwg, hipStream_t st) {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = allow_max_lds(wn_edge_kernel<NCH, FMB, NCB, RAG>);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    if (nwg == 0) return hipSuccess;
-    return launch_timed(wn_edge_kernel<NCH, FMB, NCB, RAG>, dim3(nwg), dim3(256), wn_edge_lds_bytes(64 * NCH, FMB, NCB), st, p,
-                        "wn_edge_kernel<%d, %d, %d, %d>", NCH, FMB, NCB, RAG);
+    if (nwg == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<wn_edge_kernel<NCH, FMB, NCB, RAG>, kGroup>(dim3(nwg), dim3(256), wn_edge_lds_bytes(64 * NCH, FMB, NCB), st, p,
+                                                                    "wn_edge_kernel<%d, %d, %d, %d>", NCH, FMB, NCB, RAG);
 }
 
 // (the kernel also instantiates with 16-frame tiles, NCB = 1; measured at B = 1, T = 1000 - 63 workgroups - it takes 18.6 us
@@ -421,20 +416,6 @@ hipError_t launch_wn_edge(const WnEdgeP& p, int C, int ncb, int nwg, hipStream_t
     if (C == 128 && p.FM == 64) return edge_dispatch<2, 4>(p, ncb, nwg, st);
     if (C == 128 && p.FM == 48) return edge_dispatch<2, 3>(p, ncb, nwg, st);
     return hipErrorInvalidValue;
-}
-
-hipError_t wn_edge_init_all() {
-    WnEdgeP p{};
-    hipError_t e;
-    for (int C : {256, 192, 128})
-        for (int fm : {128, 80, 64, 48})
-            for (int ncb = 2; ncb <= 2; ++ncb)
-                for (int rag = 0; rag < 2; ++rag) {
-                    p.FM = fm;
-                    p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
-                    if ((e = launch_wn_edge(p, C, ncb, 0, nullptr)) != hipSuccess) return e;
-                }
-    return hipSuccess;
 }
 
 }  // namespace dsd

@@ -29,6 +29,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_WAVENET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 namespace {
 
@@ -419,17 +420,11 @@ bool wn_layer_supported(int C, int dil) { return (C == 256 || C == 192 || C == 1
 template <int NCH, int SW, int RAG, int NCB>
 static hipError_t wn_launch(const WnLayerP& p, int ntiles, hipStream_t st) {
     const int ldsb = wn_layer_lds_bytes(NCH, SW, NCB);
-    static bool attr_done = false;       // per instantiation; set outside any capture by wn_layer_init_all
-    void (*kern)(const WnLayerP);
-    if constexpr (NCB == 2) kern = wn_layer_kernel<NCH, SW, RAG>;
-    else kern = wn_layer16_kernel<NCH, SW, RAG>;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(kern);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (ntiles == 0) return hipSuccess;
-    return launch_timed(kern, dim3(ntiles), dim3(256), ldsb, st, p, NCB == 2 ? "wn_layer_kernel<%d, %d, %d>" : "wn_layer16_kernel<%d, %d, %d>", NCH, SW, RAG);
+    if (ntiles == 0) return hipSuccess;          // a ragged batch of empty items
+    if constexpr (NCB == 2)
+        return launch_timed<wn_layer_kernel<NCH, SW, RAG>, kGroup>(dim3(ntiles), dim3(256), ldsb, st, p, "wn_layer_kernel<%d, %d, %d>", NCH, SW, RAG);
+    else
+        return launch_timed<wn_layer16_kernel<NCH, SW, RAG>, kGroup>(dim3(ntiles), dim3(256), ldsb, st, p, "wn_layer16_kernel<%d, %d, %d>", NCH, SW, RAG);
 }
 
 bool wn_layer16_supported(int C, int dil) { return (C == 256 || C == 192) && dil >= 1 && dil <= 16; }
@@ -458,27 +453,6 @@ hipError_t launch_wn_layer(const WnLayerP& p, int C, int batch, hipStream_t st, 
 #undef WN_CASE
 #undef WN_CASE16
     return hipErrorInvalidValue;
-}
-
-// raise the dynamic-LDS limit of every instantiation once, outside any stream capture
-hipError_t wn_layer_init_all() {
-    WnLayerP p{};
-    hipError_t e;
-#define WN_INIT(NCH_, SW_, NCB_)                                                                  \
-    if ((e = wn_launch<NCH_, SW_, 0, NCB_>(p, 0, nullptr)) != hipSuccess) return e;               \
-    if ((e = wn_launch<NCH_, SW_, 1, NCB_>(p, 0, nullptr)) != hipSuccess) return e;
-    WN_INIT(4, 48, 2)
-    WN_INIT(4, 80, 2)
-    WN_INIT(3, 48, 2)
-    WN_INIT(3, 80, 2)
-    WN_INIT(2, 48, 2)
-    WN_INIT(2, 80, 2)
-    WN_INIT(4, 48, 1)
-    WN_INIT(4, 80, 1)
-    WN_INIT(3, 48, 1)
-    WN_INIT(3, 80, 1)
-#undef WN_INIT
-    return hipSuccess;
 }
 
 }  // namespace dsd

@@ -25,6 +25,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_WAVENET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -278,15 +279,9 @@ bool wn_layer_x3_supported(int C_, int dil) { return C_ == 256 && dil >= 1 && di
 
 template <int HL, int RAG>
 static hipError_t x3_launch(const WnLayerP& p, int ntiles, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(wn_layer_x3_kernel<HL, RAG>);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (ntiles == 0) return hipSuccess;
-    return launch_timed(wn_layer_x3_kernel<HL, RAG>, dim3(ntiles), dim3(256), wn_layer_x3_lds_bytes(HL), st, p,
-                        "wn_layer_x3_kernel<%d, %d>", HL, RAG);
+    if (ntiles == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<wn_layer_x3_kernel<HL, RAG>, kGroup>(dim3(ntiles), dim3(256), wn_layer_x3_lds_bytes(HL), st, p,
+                                                             "wn_layer_x3_kernel<%d, %d>", HL, RAG);
 }
 
 // p.Aconv / p.Aout point at the layer's bf16x3 weight streams (api.hip: pack_x3)
@@ -295,20 +290,6 @@ hipError_t launch_wn_layer_x3(const WnLayerP& p, int C_, int batch, hipStream_t 
     const int ntiles = p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b);
     if (p.dil <= 8) return p.cgmap ? x3_launch<8, 1>(p, ntiles, st) : x3_launch<8, 0>(p, ntiles, st);
     return p.cgmap ? x3_launch<16, 1>(p, ntiles, st) : x3_launch<16, 0>(p, ntiles, st);
-}
-
-hipError_t wn_layer_x3_init_all() {
-    WnLayerP p{};
-    hipError_t e;
-    for (int dil : {1, 16})
-        for (int rag = 0; rag < 2; ++rag) {
-            p.dil = dil;
-            p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;
-            p.ncg = 0;
-            p.tiles_per_b = 0;
-            if ((e = launch_wn_layer_x3(p, 256, 0, nullptr)) != hipSuccess) return e;
-        }
-    return hipSuccess;
 }
 
 }  // namespace dsd

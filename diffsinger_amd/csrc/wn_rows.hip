@@ -21,6 +21,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_WAVENET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 namespace {
 
@@ -405,27 +406,15 @@ bool wn_rows_supported(int C_, int dil, long Ts) { return C_ == 256 && dil >= 1 
 template <int MP, int SW, int RAG>
 static hipError_t rw_launch_conv(const WnLayerP& p, int nwg, hipStream_t st) {
     constexpr int HL = SW == 48 ? 8 : 16;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(wn_conv_rw_kernel<MP, SW, HL, RAG>);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (nwg == 0) return hipSuccess;
-    return launch_timed(wn_conv_rw_kernel<MP, SW, HL, RAG>, dim3(nwg), dim3(512), wn_rw_conv_lds_bytes(MP, SW), st, p,
-                        "wn_conv_rw_kernel<%d, %d, %d, %d>", MP, SW, HL, RAG);
+    if (nwg == 0) return hipSuccess;          // a ragged batch of empty items
+    return launch_timed<wn_conv_rw_kernel<MP, SW, HL, RAG>, kGroup>(dim3(nwg), dim3(512), wn_rw_conv_lds_bytes(MP, SW), st, p,
+                                                                    "wn_conv_rw_kernel<%d, %d, %d, %d>", MP, SW, HL, RAG);
 }
 
 template <int MP, int RAG>
 static hipError_t rw_launch_out(const WnLayerP& p, int nwg, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(wn_out_rw_kernel<MP, RAG>);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
     if (nwg == 0) return hipSuccess;
-    return launch_timed(wn_out_rw_kernel<MP, RAG>, dim3(nwg), dim3(512), wn_rw_out_lds_bytes(MP), st, p, "wn_out_rw_kernel<%d, %d>", MP, RAG);
+    return launch_timed<wn_out_rw_kernel<MP, RAG>, kGroup>(dim3(nwg), dim3(512), wn_rw_out_lds_bytes(MP), st, p, "wn_out_rw_kernel<%d, %d>", MP, RAG);
 }
 
 // which = 0: conv + FiLM + gate (p.xin -> p.z);  1: out-proj + residual / skip (p.z, p.xin -> p.xout, p.skip);
@@ -445,23 +434,6 @@ hipError_t launch_wn_rows(const WnLayerP& p, int which, int C_, int batch, int r
     RW_CASE(4)
 #undef RW_CASE
     return hipErrorInvalidValue;
-}
-
-// raise the dynamic-LDS limit of every instantiation once, outside any stream capture
-hipError_t wn_rows_init_all() {
-    WnLayerP p{};
-    hipError_t e;
-    for (int rows : {128, 256})
-        for (int dil : {1, 16})
-            for (int rag = 0; rag < 2; ++rag) {
-                p.dil = dil;
-                p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;      // (no launch: the grid is empty)
-                p.ncg = 0;
-                p.tiles_per_b = 0;
-                if ((e = launch_wn_rows(p, 0, 256, 0, rows, nullptr)) != hipSuccess) return e;
-                if ((e = launch_wn_rows(p, 1, 256, 0, rows, nullptr)) != hipSuccess) return e;
-            }
-    return hipSuccess;
 }
 
 }  // namespace dsd

@@ -22,6 +22,7 @@
 #include "dsd_device.h"
 
 namespace dsd {
+constexpr int kGroup = KG_WAVENET;      // whose create functions prepare this file's kernels (dsd_internal.h: KernelReg)
 
 namespace {
 
@@ -880,32 +881,18 @@ bool wn_rowsplit_supported(int C, int dil, long Ts) { return C == 256 && dil >= 
 template <int SW, int RAG>
 static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int layout, hipStream_t st) {
     constexpr int HL = SW == 48 ? 8 : 16;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(wn_conv_rq_kernel<2, SW, HL, RAG>);
-        if (e == hipSuccess) e = allow_max_lds(wn_conv_rs_kernel<SW, RAG>);
-        if (e == hipSuccess && !RAG) e = allow_max_lds(wn_conv_rq_kernel<3, 80, HL, 0>);
-        if constexpr (SW == 48) {
-            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<1, RAG>);
-            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<2, RAG>);
-            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<4, RAG>);
-            if (e == hipSuccess) e = allow_max_lds(wn_conv_wq_kernel<8, RAG>);
-        }
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    if (nwg == 0) return hipSuccess;
+    if (nwg == 0) return hipSuccess;          // a ragged batch of empty items
     if (bn == 48) {
         if (RAG) return hipErrorInvalidValue;
-        return launch_timed(wn_conv_rq_kernel<3, 80, HL, 0>, dim3(nwg), dim3(512), wn_rs_conv_lds_bytes(80, 48, true), st, p,
-                            "wn_conv_rq_kernel<3, 80, %d, 0>", HL);
+        return launch_timed<wn_conv_rq_kernel<3, 80, HL, 0>, kGroup>(dim3(nwg), dim3(512), wn_rs_conv_lds_bytes(80, 48, true), st, p,
+                                                                     "wn_conv_rq_kernel<3, 80, %d, 0>", HL);
     }
     // The K-quarter layout needs 86 KiB of LDS (SW 48), one workgroup per CU; the K-half layout 67 KiB, two; the Winograd form
     // of the K-quarter layout 116 KiB.  `layout` = wn_rowsplit_conv_layout's answer (every layout reads the same p.Aconv).
     if (layout == 2) {
         if constexpr (SW == 48) {
             const int ldsw = wn_rs_wq_lds_bytes();
-#define WQ_LAUNCH(D) launch_timed(wn_conv_wq_kernel<D, RAG>, dim3(nwg), dim3(512), ldsw, st, p, "wn_conv_wq_kernel<%d, %d>", D, RAG)
+#define WQ_LAUNCH(D) launch_timed<wn_conv_wq_kernel<D, RAG>, kGroup>(dim3(nwg), dim3(512), ldsw, st, p, "wn_conv_wq_kernel<%d, %d>", D, RAG)
             switch (p.dil) {
                 case 1: return WQ_LAUNCH(1);
                 case 2: return WQ_LAUNCH(2);
@@ -919,26 +906,19 @@ static hipError_t rs_launch_conv(const WnLayerP& p, int nwg, int bn, int layout,
     const bool quarters = layout != 0;
     const int ldsb = wn_rs_conv_lds_bytes(SW, 32, quarters);
     if (quarters)
-        return launch_timed(wn_conv_rq_kernel<2, SW, HL, RAG>, dim3(nwg), dim3(512), ldsb, st, p, "wn_conv_rq_kernel<2, %d, %d, %d>",
-                            SW, HL, RAG);
-    return launch_timed(wn_conv_rs_kernel<SW, RAG>, dim3(nwg), dim3(512), ldsb, st, p, "wn_conv_rs_kernel<%d, %d>", SW, RAG);
+        return launch_timed<wn_conv_rq_kernel<2, SW, HL, RAG>, kGroup>(dim3(nwg), dim3(512), ldsb, st, p,
+                                                                       "wn_conv_rq_kernel<2, %d, %d, %d>", SW, HL, RAG);
+    return launch_timed<wn_conv_rs_kernel<SW, RAG>, kGroup>(dim3(nwg), dim3(512), ldsb, st, p, "wn_conv_rs_kernel<%d, %d>", SW, RAG);
 }
 
 template <int RAG>
 static hipError_t rs_launch_out(const WnLayerP& p, int nwg, int bn, hipStream_t st) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = allow_max_lds(wn_out_rs_kernel<2, RAG>);
-        if (e == hipSuccess && !RAG) e = allow_max_lds(wn_out_rs_kernel<3, 0>);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
     if (nwg == 0) return hipSuccess;
     if (bn == 48) {
         if (RAG) return hipErrorInvalidValue;
-        return launch_timed(wn_out_rs_kernel<3, 0>, dim3(nwg), dim3(512), wn_rs_out_lds_bytes(48), st, p, "wn_out_rs_kernel<3, 0>");
+        return launch_timed<wn_out_rs_kernel<3, 0>, kGroup>(dim3(nwg), dim3(512), wn_rs_out_lds_bytes(48), st, p, "wn_out_rs_kernel<3, 0>");
     }
-    return launch_timed(wn_out_rs_kernel<2, RAG>, dim3(nwg), dim3(512), wn_rs_out_lds_bytes(32), st, p, "wn_out_rs_kernel<2, %d>", RAG);
+    return launch_timed<wn_out_rs_kernel<2, RAG>, kGroup>(dim3(nwg), dim3(512), wn_rs_out_lds_bytes(32), st, p, "wn_out_rs_kernel<2, %d>", RAG);
 }
 
 static int rs_tiles(const WnLayerP& p, int batch) { return p.cgmap ? p.ncg : (p.ntiles > 0 ? p.ntiles : batch * p.tiles_per_b); }
@@ -969,21 +949,6 @@ hipError_t launch_wn_rowsplit(const WnLayerP& p, int which, int C_, int batch, i
     if (which == 1) return p.cgmap ? rs_launch_out<1>(p, nwg, bn, st) : rs_launch_out<0>(p, nwg, bn, st);
     if (p.dil <= 8) return p.cgmap ? rs_launch_conv<48, 1>(p, nwg, bn, layout, st) : rs_launch_conv<48, 0>(p, nwg, bn, layout, st);
     return p.cgmap ? rs_launch_conv<80, 1>(p, nwg, bn, layout, st) : rs_launch_conv<80, 0>(p, nwg, bn, layout, st);
-}
-
-hipError_t wn_rowsplit_init_all() {
-    WnLayerP p{};
-    hipError_t e;
-    for (int dil : {1, 16})
-        for (int rag = 0; rag < 2; ++rag) {
-            p.dil = dil;
-            p.cgmap = rag ? reinterpret_cast<const int*>(&p) : nullptr;      // (no launch: the grid is empty)
-            p.ncg = 0;
-            p.tiles_per_b = 0;
-            if ((e = launch_wn_rowsplit(p, 0, 256, 0, 32, 1, nullptr)) != hipSuccess) return e;
-            if ((e = launch_wn_rowsplit(p, 1, 256, 0, 32, 1, nullptr)) != hipSuccess) return e;
-        }
-    return hipSuccess;
 }
 
 }  // namespace dsd

@@ -12,6 +12,14 @@
 #include "dsd_internal.h"
 namespace dsd {
 TimingSlot& timing_slot() { static thread_local TimingSlot s; return s; }
+// the library's registry (api.hip), as far as one kernel file needs it: every kernel the file can launch
+static std::vector<const void*>& kernels() { static std::vector<const void*> k; return k; }
+bool register_kernel(const void* host_stub, int) { kernels().push_back(host_stub); return true; }
+static hipError_t prepare_all() {
+    for (const void* k : kernels())
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds)) return e;
+    return hipSuccess;
+}
 }
 using namespace dsd;
 static unsigned short bf16_bits(float v) { unsigned u; memcpy(&u, &v, 4); u += 0x7fffu + ((u >> 16) & 1u); return (unsigned short)(u >> 16); }
@@ -46,7 +54,7 @@ int main(int argc, char** argv) {
     hipMemcpy(part, hp.data(), hp.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(bias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(w, hw.data(), nw * 2, hipMemcpyHostToDevice);
-    if (lx_x3_init_all() != hipSuccess) { printf("init failed\n"); return 1; }
+    if (prepare_all() != hipSuccess) { printf("init failed\n"); return 1; }
     LxLayerP p{};
     p.A1 = reinterpret_cast<const float*>(w); p.bias1 = bias; p.xin = x; p.lnpart_in = part; p.lnpart_ts = lts; p.ln_rows = C; p.u = u;
     p.x_bstride = (long)xs; p.u_bstride = (long)us; p.inner = inner; p.Ts = Ts; p.T = T;
