@@ -38,7 +38,7 @@ SAMPLER_IDS = {"ddpm": 0, "ddim": 1, "pndm": 2, "dpm-solver": 3, "unipc": 4, "rf
 EXPORTS = [
     "dsd_api_version", "dsd_create", "dsd_create_any_width", "dsd_destroy", "dsd_last_error", "dsd_load_weight",
     "dsd_finalize_weights", "dsd_prepare_cond", "dsd_denoise", "dsd_sample", "dsd_get_stats",
-    "dsd_kernel_timing", "dsd_kernel_timing_read", "dsd_kernel_timing_classes", "dsd_set_precision", "dsd_aux_decode", "dsd_encoder_create", "dsd_encode", "dsd_vocoder_create", "dsd_vocode", "dsd_vocode_ragged",
+    "dsd_kernel_timing", "dsd_kernel_timing_read", "dsd_kernel_timing_classes", "dsd_kernel_ledger", "dsd_kernel_ledger_reset", "dsd_set_precision", "dsd_aux_decode", "dsd_encoder_create", "dsd_encode", "dsd_vocoder_create", "dsd_vocode", "dsd_vocode_ragged",
     "dsd_token_encoder_create", "dsd_token_encode", "dsd_predict_dur", "dsd_cond_assemble", "dsd_set_lengths",
     "dsd_mel_create", "dsd_mel_filterbank", "dsd_mel_num_frames", "dsd_mel_analyze",
     "dsd_rmvpe_create", "dsd_rmvpe_num_frames", "dsd_rmvpe_filterbank", "dsd_rmvpe_mel_to_hidden", "dsd_rmvpe_decode",
@@ -221,6 +221,10 @@ class DsdKernelTime(C.Structure):
                 ("bytes_per_launch", C.c_double)]
 
 
+class DsdKernelLaunches(C.Structure):
+    _fields_ = [("symbol", C.c_char_p), ("group", C.c_int32), ("reserved", C.c_int32), ("launches", C.c_int64)]
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -318,6 +322,8 @@ def _load():
     lib.dsd_set_precision.argtypes = [vp, i32]
     lib.dsd_kernel_timing_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64)]
     lib.dsd_kernel_timing_classes.argtypes = [vp, C.POINTER(DsdKernelTime), i32, C.POINTER(i32), C.POINTER(C.c_double)]
+    lib.dsd_kernel_ledger.argtypes = [C.POINTER(DsdKernelLaunches), i32, C.POINTER(i32)]
+    lib.dsd_kernel_ledger_reset.argtypes = []
     for name in EXPORTS:
         getattr(lib, name)
     if lib.dsd_api_version() != 10:
@@ -340,6 +346,20 @@ def check(handle, rc, what):
         return
     msg = lib().dsd_last_error(handle).decode("utf-8", "replace")
     raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
+
+
+def kernel_ledger():
+    """The launch ledger (dsd_kernel_ledger): [(mangled host-stub symbol or None, kernel group, launches)], one per kernel
+    instantiation the library can launch, in registry order."""
+    n = C.c_int32(0)
+    check(None, lib().dsd_kernel_ledger(None, 0, C.byref(n)), "dsd_kernel_ledger")
+    rows = (DsdKernelLaunches * max(1, n.value))()
+    check(None, lib().dsd_kernel_ledger(rows, n.value, C.byref(n)), "dsd_kernel_ledger")
+    return [(r.symbol.decode() if r.symbol else None, int(r.group), int(r.launches)) for r in rows[:n.value]]
+
+
+def kernel_ledger_reset():
+    check(None, lib().dsd_kernel_ledger_reset(), "dsd_kernel_ledger_reset")
 
 
 def load_state_dict(handle, sd):

@@ -51,7 +51,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if failed:
         raise RuntimeError("hipcc failed")
     if force or procs or _stale(LIB, objs):
-        cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", LIB] + objs
+        cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", LIB] + objs + ["-ldl"]       # dladdr (dsd_kernel_ledger)
         if verbose:
             print("[build]", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)

@@ -14,12 +14,15 @@
 //   variance-model encoders .......... dsd_token_encoder_create, dsd_token_encode, dsd_predict_dur, dsd_cond_assemble
 //   vocoder .......................... run_tconv, dsd_vocoder_create, dsd_vocode, dsd_vocode_ragged
 //   aux decoder ...................... dsd_aux_decode
-//   diagnostics ...................... dsd_get_stats, dsd_kernel_timing*
+//   diagnostics ...................... dsd_get_stats, dsd_kernel_timing*, dsd_kernel_ledger*
 // The analysis families use none of the above but the handle and have host files of their own:
 //   mel analysis ..................... mel_api.hip    dsd_mel_*
 //   RMVPE pitch extraction ........... rmvpe_api.hip  dsd_rmvpe_*  (its front end is mel_api.hip's mel_run)
 //   VR harmonic-noise separation ..... hnsep_api.hip  dsd_hnsep_*, dsd_base_harmonic, dsd_variance_curves
 // dsd_load_weight, dsd_finalize_weights and dsd_destroy hand an RMVPE or separator handle on to them.
+#include <dlfcn.h>
+
+#include <deque>
 #include <mutex>
 
 #include "api_host.h"
@@ -93,17 +96,18 @@ struct KernelEntry {
     const void* host_stub;
     int group;
     std::vector<bool> ready;    // by device: the limit is raised there
+    LaunchCount launches;       // the launch ledger (dsd_kernel_ledger); the launch helpers hold its address
 };
-std::vector<KernelEntry>& kernel_registry() {
-    static std::vector<KernelEntry> reg;
+std::deque<KernelEntry>& kernel_registry() {      // (a deque: an entry keeps its address while later ones register)
+    static std::deque<KernelEntry> reg;
     return reg;
 }
 std::mutex g_prepare_mutex;
 }  // namespace
 
-bool register_kernel(const void* host_stub, int group) {
-    kernel_registry().push_back({host_stub, group, {}});
-    return true;
+LaunchCount* register_kernel(const void* host_stub, int group) {
+    kernel_registry().push_back({host_stub, group, {}, 0});
+    return &kernel_registry().back().launches;
 }
 
 int kernel_registry_get(int i, const void** host_stub, int* group) {
@@ -3403,6 +3407,26 @@ int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_c
         }
         *empty_pair_ms = h->cal_used ? cal / (double)h->cal_used : 0.0;
     }
+    return DSD_OK;
+}
+
+int dsd_kernel_ledger(dsd_kernel_launches* out, int32_t max_entries, int32_t* n_entries) {
+    if (!n_entries || max_entries < 0 || (max_entries > 0 && !out)) return DSD_EINVAL;
+    const auto& reg = kernel_registry();
+    for (int i = 0; i < (int)reg.size() && i < max_entries; ++i) {
+        Dl_info info;
+        const bool named = dladdr(reg[i].host_stub, &info) && info.dli_sname && info.dli_saddr == reg[i].host_stub;
+        out[i].symbol = named ? info.dli_sname : nullptr;
+        out[i].group = reg[i].group;
+        out[i].reserved = 0;
+        out[i].launches = (int64_t)__atomic_load_n(&reg[i].launches, __ATOMIC_RELAXED);
+    }
+    *n_entries = (int32_t)reg.size();
+    return DSD_OK;
+}
+
+int dsd_kernel_ledger_reset(void) {
+    for (KernelEntry& k : kernel_registry()) __atomic_store_n(&k.launches, 0ull, __ATOMIC_RELAXED);
     return DSD_OK;
 }
 

@@ -66,17 +66,22 @@ TimingSlot& timing_slot();      // thread-local (api.hip)
 // limits of their groups' entries (prepare_kernels, api.hip); each kernel file names its group once, at its top.
 constexpr int kMaxDynLds = 160 * 1024;
 enum KernelGroup { KG_GEMM = 1, KG_WAVENET = 2, KG_LYNXNET = 4, KG_VOCODER = 8 };
-bool register_kernel(const void* host_stub, int group);                    // api.hip; always true
+// The launch ledger (dsd_kernel_ledger): every entry counts the launches of its instantiation through the two helpers, on the
+// host, whether the launch executes at once or is recorded into a stream capture (a graph replay counts nothing: no helper
+// runs).  One relaxed increment per launch; tests/test_gpu_kernel_ledger.py reads which instantiations a call ran.
+typedef unsigned long long LaunchCount;
+LaunchCount* register_kernel(const void* host_stub, int group);            // api.hip; the entry's launch counter (never null)
 int kernel_registry_get(int i, const void** host_stub, int* group);        // entry i, or 0 past the last (tests/test_kernel_registry.py)
 int prepare_kernels(const char* who, int device, int groups);              // DSD_OK or DSD_EHIP through fail()
 template <auto kern, int GROUP>
 struct KernelReg {
-    static inline const bool registered = register_kernel(reinterpret_cast<const void*>(kern), GROUP);
+    static inline LaunchCount* const launches = register_kernel(reinterpret_cast<const void*>(kern), GROUP);
+    static void count() { __atomic_fetch_add(launches, 1ull, __ATOMIC_RELAXED); }     // (odr-use: the registration runs at load time, not here)
 };
 
 template <auto kern, int GROUP, typename... Args>
 inline hipError_t launch_plain(dim3 grid, dim3 block, int lds, hipStream_t st, const Args&... args) {
-    (void)&KernelReg<kern, GROUP>::registered;       // (odr-use: the registration runs at load time, not here)
+    KernelReg<kern, GROUP>::count();
     hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
     return hipGetLastError();
 }
@@ -86,6 +91,7 @@ inline hipError_t launch_timed(dim3 grid, dim3 block, int lds, hipStream_t st, c
                                NameArgs... name_args) {
     TimingSlot& ts = timing_slot();
     if (ts.e0 && ts.e1 && !ts.taken) {
+        KernelReg<kern, GROUP>::count();
         hipExtLaunchKernelGGL(kern, grid, block, lds, st, ts.e0, ts.e1, 0, p);
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wformat-security"

@@ -10,7 +10,8 @@
 //   lx_pw2_kernel : v = W2 u' + b2 + x  (residual), then the NEXT layer's transition exactly as gemm.hip's EP_LYNX_NEXT:
 //                   strong: x = v + cpn, xin = x + d;  else: x = v, xin = v + cpn + d;  no next layer: x = xin = v;
 //                   plus the LayerNorm partials (mean, sum of squared deviations) of xin per 64-row tile and frame.
-//                   K = inner (2048) is walked as two resident phases of 1024 channels.
+//                   Launched for inner = 512 at C = 512 only (one resident phase); inner = 1024 / 2048 is lx_pw2d_kernel's
+//                   (double-buffered 512-channel half-phases), on one-utterance grids lx_pw2q_kernel's.
 //
 // LDS tile: [K][32] floats with NO padding (a 1024-channel tile is 128 KiB): the 4 k-rows x 16 columns of a B-fragment
 // read hit 64 distinct banks because odd rows are stored with their two 16-column halves swapped (physical column =
@@ -1078,7 +1079,9 @@ template <int KT, int RAG>
 static hipError_t lx_launch(const LxLayerP& p, int which, int nwg, hipStream_t st) {
     const int ldsb = lx_lds_bytes(KT);
     if (which == 0) return launch_timed<lx_pw1_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw1_kernel<%d, %d>", KT, RAG);
-    return launch_timed<lx_pw2_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw2_kernel<%d, %d>", KT, RAG);
+    // pw2 here is inner = 512, which only C = 512 has (lx_layer_supported: inner is C or 2 C; 1024 and 2048 are lx_pw2d_kernel's)
+    if constexpr (KT == 512) return launch_timed<lx_pw2_kernel<KT, RAG>, kGroup>(dim3(nwg), dim3(256), ldsb, st, p, "lx_pw2_kernel<%d, %d>", KT, RAG);
+    return hipErrorInvalidValue;
 }
 
 template <int NP, int RAG>

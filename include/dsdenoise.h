@@ -904,6 +904,27 @@ int dsd_kernel_timing_classes(dsd_handle* h, dsd_kernel_time* out, int32_t max_c
                               double* empty_pair_ms);
 
 /*
+ * The launch ledger: which kernel instantiations ran.  The library keeps one entry per kernel instantiation it can launch
+ * (the GEMM forms, the WaveNet and LYNXNet layer kernels, the vocoder's), and every launch adds one to its entry's count -
+ * on the host, when the launch is issued, whether it executes at once or is recorded into a stream capture (the replays of
+ * a captured graph add nothing).  The counts are per process, over all handles and devices.  Takes no handle.
+ *   dsd_kernel_ledger        fills out[0 .. min(max_entries, *n_entries)) and sets *n_entries to the number of entries the
+ *                            library has (constant from load on: call with max_entries = 0 to size the array)
+ *   dsd_kernel_ledger_reset  zeroes every count
+ *   symbol    the mangled name of the kernel's host-side launch stub, e.g. _ZN3dsd27__device_stub__gemm_kernelILi0E...;
+ *             c++filt gives the kernel and its template arguments.  Owned by the library; NULL if it did not resolve
+ *   group     1: GEMM forms, 2: WaveNet layer kernels, 4: LYNXNet layer kernels, 8: vocoder kernels
+ */
+typedef struct dsd_kernel_launches {
+    const char* symbol;
+    int32_t group;
+    int32_t reserved;
+    int64_t launches;
+} dsd_kernel_launches;
+int dsd_kernel_ledger(dsd_kernel_launches* out, int32_t max_entries, int32_t* n_entries);
+int dsd_kernel_ledger_reset(void);
+
+/*
  * VR harmonic-noise separation and the variance curves (utils/decomposed_waveform.py: DecomposedWaveformVocalRemover,
  * utils/binarizer_utils.py: get_energy_librosa, get_breathiness, get_voicing, get_tension_base_harmonic).  fp32 throughout.
  * Weights load through dsd_load_weight under CascadedNet's state_dict names (aux_out.weight and num_batches_tracked are

@@ -33,6 +33,7 @@ def test_struct_sizes_match_header():
     assert C.sizeof(_lib.DsdLincomb) == 8 + 8 * _lib.DSD_MAX_TERMS
     assert C.sizeof(_lib.DsdEval) == 12 + _lib.DSD_MAX_OUT * C.sizeof(_lib.DsdLincomb)
     assert C.sizeof(_lib.DsdProgram) == 24
+    assert C.sizeof(_lib.DsdKernelLaunches) == 24 and _lib.DsdKernelLaunches.launches.offset == 16      # dsd_kernel_launches
 
 
 def test_create_fails_loudly_without_gpu():

@@ -117,3 +117,41 @@ def test_the_limit_is_raised_in_one_place():
     body = api[api.index("int prepare_kernels("):]
     body = body[:body.index("\n}\n")]
     assert "hipFuncAttributeMaxDynamicSharedMemorySize" in body
+
+
+def test_launch_ledger_lists_the_registry(registry):
+    """dsd_kernel_ledger (the launch counts tests/test_gpu_kernel_ledger.py reads): one entry per registry entry, in the
+    registry's order and under its group, every name resolved inside the library (dladdr) to the instantiation the
+    stand-alone program names; nothing has been launched, so every count is zero, and stays zero over a reset."""
+    from diffsinger_amd import _lib
+    rows = _lib.kernel_ledger()
+    assert len(rows) == sum(len(v) for v in registry.values()) > 0
+    assert all(sym for sym, _, _ in rows), [r for r in rows if not r[0]][:8]
+    names = demangle([sym for sym, _, _ in rows])
+    assert len(set(names)) == len(names)
+    odd = [n for n in names if not re.fullmatch(r"(void )?dsd::\w+(<.*>)?\(.*\)", n)]       # a kernel, not some other symbol
+    assert not odd, odd[:8]
+    got = {}
+    for (_, group, _), n in zip(rows, names):
+        got.setdefault(group, []).append(n)
+    assert got == registry
+    assert [c for _, _, c in rows] == [0] * len(rows)
+    _lib.kernel_ledger_reset()
+    assert _lib.kernel_ledger() == rows
+
+
+def test_launch_ledger_argument_checks():
+    """max_entries = 0 sizes the array; a short array is filled as far as it goes and the count is still the whole
+    ledger's; the mistakes a caller can make are DSD_EINVAL."""
+    import ctypes as C
+    from diffsinger_amd import _lib
+    lib, n, m = _lib.lib(), C.c_int32(-1), C.c_int32(-1)
+    assert lib.dsd_kernel_ledger(None, 0, C.byref(n)) == 0 and n.value > 3
+    rows = (_lib.DsdKernelLaunches * 3)()
+    rows[2].group = -7
+    assert lib.dsd_kernel_ledger(rows, 2, C.byref(m)) == 0 and m.value == n.value
+    assert rows[0].symbol and rows[1].symbol and rows[2].group == -7
+    assert [(r[0].encode(), r[1]) for r in _lib.kernel_ledger()[:2]] == [(r.symbol, r.group) for r in rows[:2]]
+    assert lib.dsd_kernel_ledger(rows, 3, None) == _lib.DSD_EINVAL
+    assert lib.dsd_kernel_ledger(None, 3, C.byref(m)) == _lib.DSD_EINVAL
+    assert lib.dsd_kernel_ledger(rows, -1, C.byref(m)) == _lib.DSD_EINVAL
