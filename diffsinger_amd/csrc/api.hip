@@ -7,7 +7,8 @@
 //   state-dict layouts ............... expected_params*(): the names and shapes the library accepts
 //   weight re-layout ................. pack_gemm (MFMA fragment order), build_packed{,_aux,_enc,_tok,_voc}
 //   workspaces ....................... ensure_workspace / ensure_state / ensure_emb (kept across shape changes)
-//   GEMM launch decisions ............ make_gemm (tile width, fast / generic path, ragged lengths), run_gemm
+//   ragged batches ................... upload_ragged, check_lens (the builder, the grid and the filler: ragged_tiles.h)
+//   GEMM launch decisions ............ make_gemm (tile width, fast / generic path, the grid of a ragged batch), run_gemm
 //   denoiser ......................... run_step_tables, run_backbone (WaveNet 43 kernels, LYNXNet), dsd_create ...
 //                                      dsd_prepare_cond, dsd_denoise, dsd_sample (+ hipGraph cache), dsd_set_lengths
 //   acoustic encoder ................. dsd_encoder_create, enc_workspace, run_fs2_layers, dsd_encode
@@ -198,38 +199,36 @@ namespace {
 
 void destroy_graphs(dsd_handle* h);
 
-// the launch sequences that may skip padded tiles (denoiser evaluations, aux decoder) run inside one of these
-struct RaggedScope {
-    dsd_handle* h;
-    explicit RaggedScope(dsd_handle* hh) : h(hh) { h->use_cg = true; }
-    ~RaggedScope() { h->use_cg = false; }
-};
-
-// ragged batch bookkeeping: the lengths given by dsd_set_lengths must describe this call's batch; the lists of valid
-// column groups are (re)built here, on the caller's stream and outside any graph capture
-inline int check_lens(dsd_handle* h, const char* who, int B, int T, hipStream_t st) {
-    if (h->lens_host.empty()) return DSD_OK;
-    if ((int)h->lens_host.size() != B)
-        return fail(h, DSD_ESTATE, "%s: dsd_set_lengths gave %zu lengths but this call runs a batch of %d", who, h->lens_host.size(), B);
-    for (int v : h->lens_host)
-        if (v > T) return fail(h, DSD_EINVAL, "%s: a length (%d) exceeds T = %d", who, v, T);
-    if (h->cg_T == T) return DSD_OK;
-    for (int k = 0; k < 3; ++k) {
-        const int BN = k == 0 ? 16 : 32 * k, tiles = (T + BN - 1) / BN;
-        std::vector<int>& v = h->cg_host[k];
-        v.clear();
-        for (int b = 0; b < B; ++b)
-            for (int ft = 0; ft * BN < h->lens_host[b]; ++ft) v.push_back(b * tiles + ft);
-        h->cg_n[k] = (int)v.size();
-        if (v.size() > h->cg_dev[k].cap) {
-            if (int rc = h->cg_dev[k].reserve(h, (size_t)B * tiles, who)) return rc;
-            destroy_graphs(h);      // cached graphs captured the old pointer
-        }
-        if (!v.empty() && hipMemcpyAsync(h->cg_dev[k].p, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice, st) != hipSuccess)
-            return fail(h, DSD_EHIP, "%s: upload of the valid-tile list failed", who);
+// Puts a ragged batch's block on the device unless it is there: on the caller's stream, outside any graph capture and before
+// the launches that read it
+int upload_ragged(dsd_handle* h, RaggedOwner& r, const char* who, hipStream_t st) {
+    if (r.on_device) return DSD_OK;
+    if (r.dense > r.dev.cap) {
+        if (int rc = r.dev.reserve(h, r.dense, who)) return rc;
+        destroy_graphs(h);      // cached graphs captured the old pointers
     }
-    h->cg_T = T;
+    if (hipMemcpyAsync(r.dev.p, r.host.data(), sizeof(int) * r.host.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(h, DSD_EHIP, "%s: upload of the valid-tile lists failed", who);
+    for (RaggedGrid& g : r.grids) g.point(r.host.data(), r.dev.p);
+    r.on_device = true;
     return DSD_OK;
+}
+
+// The denoisers' and the aux decoder's lists: 16 / 32 / 64-frame tiles at the one rate they run at, with the denoiser policies
+// (RaggedGrid).  dsd_set_lengths builds at the handle's current T, so that dsd_get_stats sees the lengths at once ...
+inline void build_lengths(dsd_handle* h, const int* lengths, int B, int T) {
+    h->rag.build(lengths, B, T, RAG_W16 | RAG_W32 | RAG_W64, {1}, false, false);
+}
+// ... and every call that launches on them checks that they describe its batch, rebuilds for its T if that has changed and uploads
+inline int check_lens(dsd_handle* h, const char* who, int B, int T, hipStream_t st) {
+    RaggedOwner& r = h->rag;
+    if (!r.active) return DSD_OK;
+    if (r.key[0] != B)
+        return fail(h, DSD_ESTATE, "%s: dsd_set_lengths gave %d lengths but this call runs a batch of %d", who, r.key[0], B);
+    for (int b = 0; b < B; ++b)
+        if (r.lengths()[b] > T) return fail(h, DSD_EINVAL, "%s: a length (%d) exceeds T = %d", who, r.lengths()[b], T);
+    if (r.key[1] != T) build_lengths(h, r.lengths(), B, T);
+    return upload_ragged(h, r, who, st);
 }
 
 inline int C_of(const dsd_handle* h) { return h->cfg.num_channels; }
@@ -1354,10 +1353,10 @@ inline int gemm_generic_lds_bytes(int K, int taps, int dil, int BN) {
     return gemm_lds_bytes(taps > 1 ? K : std::min(K, 256), gemm_row_stride(BN, gemm_halo(taps, dil)));
 }
 
-// vr: a ragged vocoder batch at this GEMM's rate (dsd_vocode_ragged): its lengths and valid tiles instead of dsd_set_lengths'
+// rg: the ragged batch whose (batch, T) frames the GEMM runs over, at the GEMM's rate - the launch then covers only the tiles
+// that hold valid frames - or nullptr for a dense launch.  A GEMM is ragged exactly when its caller passes a grid.
 GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, long b_bstride, int b_rstride, int batch,
-                   int T, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false,
-                   const VocRagStage* vr = nullptr) {
+                   int T, const RaggedGrid* rg, int stage, int epi, int dil, bool generic_only = false, bool rs_pair = false) {
     GemmCall c;
     memset(&c.p, 0, sizeof(c.p));
     GemmP& p = c.p;
@@ -1376,18 +1375,13 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
     p.taps = g.taps;
     p.HL = gemm_halo(g.taps, dil);
     p.in_scale = 1.f;
-    // ragged batches: only a convolution along time can carry an item's padded frames into its valid ones, so only the
-    // k-tap GEMMs over the utterances' (B, T) frames mask their input (not the 1x1s, not the step-embedding MLPs)
-    const bool ragged = vr || (h->use_cg && !h->lens_host.empty() && batch == h->B && T == h->T);
-    p.lens = vr ? vr->lens : (ragged && g.taps > 1) ? h->lens_dev.p : nullptr;
     c.stage = stage;
     c.taps = g.taps;
     c.epi = epi;
     c.batch = batch;
     // tile width: 64 frames when that still fills the chip twice over, else 32
     const int mtiles = g.pairC > 0 ? (g.pairC + 31) / 32 : (g.M + 63) / 64;
-    // (a ragged vocoder batch: counted over its valid tiles, the shape B lone calls of similar length would take)
-    const long wg64 = (vr ? (long)vr->ncg[2] : (long)batch * ((T + 63) / 64)) * mtiles;
+    const long wg64 = (rg && rg->nb_by_valid_tiles ? (long)rg->count[2] : (long)batch * ((T + 63) / 64)) * mtiles;
     c.nb = wg64 >= 512 ? 2 : 1;
     // a conv on the generic path keeps all input channels resident: 64-frame tiles only while that fits in LDS
     // (the second test: the row stride's rounding can add 24 frames, not 16 - K = 368 at a halo of 12 passes the first and
@@ -1414,23 +1408,18 @@ GemmCall make_gemm(const dsd_handle* h, const PackedGemm& g, const float* Bsrc, 
         if (ok && !generic_only && (small || (wg32 <= 768 && load16 < load32))) c.nb = 0;
     }
     const int BN = c.nb == 0 ? 16 : 32 * c.nb;
-    p.tiles_per_b = (T + BN - 1) / BN;
-    if (ragged) {       // the launch covers only the tiles that hold valid frames (lists built by prepare_ragged)
-        p.cgmap = vr ? vr->cg[c.nb] : h->cg_dev[c.nb].p;
-        p.ncg = vr ? vr->ncg[c.nb] : h->cg_n[c.nb];
-    }
+    const long nft = fill_tiles(p, rg, batch, T, BN);
+    if (rg && !rg->mask_every_gemm && g.taps == 1) p.lens = nullptr;       // the masking policy (RaggedGrid)
     const int S = gemm_row_stride(BN, p.HL);
     p.S = S;
     p.mtiles = mtiles;
     const int w4 = (BN + 2 * p.HL) / 4;
     p.inv_mtiles = 1.0f / (float)mtiles;
-    p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
     p.inv_w4 = 1.0f / (float)w4;
     p.lpr_shift = 3;
     while ((1 << p.lpr_shift) < w4) ++p.lpr_shift;
     {   // L2 blocking of the work order for GEMMs with many row tiles (GemmP::gm_shift): groups of 8 row tiles
         constexpr int shift = 3;
-        const long nft = ragged ? (long)p.ncg : (long)batch * p.tiles_per_b;
         if (mtiles >= (2 << shift) && mtiles % (1 << shift) == 0 && nft * mtiles >= 2048 && (nft << shift) < (1L << 22)) {
             p.gm_shift = shift;
             p.per_group = (int)(nft << shift);
@@ -1512,14 +1501,6 @@ struct DenoisePlan {
     }
 };
 
-// valid frame tiles of `bn` frames in the batch (ragged: tiles that hold valid frames, = the length of the valid-tile list)
-inline long tiles_at(const dsd_handle* h, int bn) {
-    if (h->lens_host.empty()) return (long)h->B * ((h->T + bn - 1) / bn);
-    long tiles = 0;
-    for (int v : h->lens_host) tiles += (v + bn - 1) / bn;
-    return tiles;
-}
-
 // Cost of the two-launch path over `tiles` 32-frame tiles by rows per workgroup, in fused rounds (one round = 256 tiles on
 // wn_layer.hip, ~67 us at C = 256); RATIOS measured on one box at T = 1000 (profiles/r03_rows_sweep.txt):
 //   64 rows  (wn_rowsplit.hip up to ~110 tiles, the 64-frame-tile GEMM pair of gemm.hip above): 23.6 us at 64 tiles, 32.9 at 96,
@@ -1550,7 +1531,8 @@ bool wn_segments(const dsd_handle* h, std::vector<WnSeg>& segs) {
     const int max_dil = 1 << (std::min(h->cfg.dilation_cycle_length, L_of(h)) - 1);
     if (h->cfg.dilation_cycle_length < 1 || !wn_layer_supported(C, max_dil)) return false;
     const PathOpts& o = h->opts;
-    const long tiles = tiles_at(h, 32);
+    const RaggedGrid* rg = h->rag.grid();
+    const long tiles = tiles_at(rg, h->B, h->T, 32);
     if (tiles == 0 || tiles >= (1L << 22)) return false;
     const bool rs_ok = o.rowsplit != 0 && wn_rowsplit_supported(C, max_dil, h->Ts) && wn_rows_supported(C, max_dil, h->Ts);
     // split-bf16 mode: the fused segments run wn_layer_x3.hip, whose round takes ~0.55 of an fp32 round (bound by the weight
@@ -1564,26 +1546,13 @@ bool wn_segments(const dsd_handle* h, std::vector<WnSeg>& segs) {
     }
     // the fused kernel on 16-frame tiles (wn_layer16_kernel): a round of one tile per CU takes kRound16 of a 32-frame round (half the
     // MFMAs against the same 2 MB of weights per workgroup: profiles/r03_plan_sweep.txt); fp32 only, whole layers only
-    const long tiles16 = tiles_at(h, 16);
+    const long tiles16 = tiles_at(rg, h->B, h->T, 16);
     const bool f16_ok = !x3 && wn_layer16_supported(C, max_dil) && tiles16 < (1L << 22);
     if (o.fused16 == 1 && f16_ok) {                // forced
         segs.push_back({WN_FUSED, 16, 0, (int)tiles16, 0});
         return true;
     }
-    // index in the 16-frame tile order of the first 16-frame tile of 32-frame tile n (of the dense order / the valid-tile list)
-    auto map16 = [h](long n) -> long {
-        if (h->lens_host.empty()) {
-            const long tpb32 = (h->T + 31) / 32, tpb16 = (h->T + 15) / 16;
-            return (n / tpb32) * tpb16 + 2 * (n % tpb32);
-        }
-        long n32 = 0, n16 = 0;
-        for (int v : h->lens_host) {
-            const long t32 = (v + 31) / 32, t16 = (v + 15) / 16;
-            if (n < n32 + t32) return n16 + 2 * (n - n32);
-            n32 += t32; n16 += t16;
-        }
-        return n16;
-    };
+    auto map16 = [&](long n) { return rag_map16(rg, h->T, n); };
     if (o.wn_plan == 2 && rs_ok && o.fused_layer != 0) {
         // test hook: a mixed plan at any size - the first half of the tiles fused, the rest on the two-launch path
         const int nfh = (int)(tiles / 2);
@@ -1669,16 +1638,16 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
     const int B = h->B, T = h->T, C = C_of(h);
     if (is_wavenet(h)) {
         if (!wn_segments(h, pl.segs)) {
-            const bool ragged = !h->lens_host.empty();
+            const RaggedGrid* rg = h->rag.grid();
             for (int c = 0; c < std::min(h->cfg.dilation_cycle_length, L_of(h)); ++c) {
                 const int dil = 1 << c;
                 // 32-frame tiles on a grid of about one workgroup per CU (one utterance of ~1000 frames): the row-split pair
                 // of wn_rowsplit.hip - every weight block loaded once, compiler-counted waits - instead of the two GEMMs
                 const bool rs_ok = o.rowsplit != 0 && wn_rowsplit_supported(C, dil, h->Ts);
-                const GemmCall g = make_gemm(h, h->g_conv[c], nullptr, 0, h->Ts, B, T, ST_FILM, EP_GATE, dil, false, rs_ok);
+                const GemmCall g = make_gemm(h, h->g_conv[c], nullptr, 0, h->Ts, B, T, rg, ST_FILM, EP_GATE, dil, false, rs_ok);
                 // 48-frame tiles where they make a dense launch ONE round of workgroups and 32-frame tiles do not (T in
                 // (1024, 1536] at B = 1: 35-48 tiles of 32 frames = 280-384 workgroups for 256 CUs): 21.9 -> see DESIGN 4.2
-                const bool bn48 = rs_ok && !ragged && (long)B * ((T + 31) / 32) * 8 > 256 &&
+                const bool bn48 = rs_ok && !rg && (long)B * ((T + 31) / 32) * 8 > 256 &&
                                   (long)B * ((T + 47) / 48) * 8 <= 256;
                 pl.layer[c].rs_bn = rs_ok && ((g.nb == 1 && g.fast) || bn48) ? (bn48 ? 48 : 32) : 0;
                 pl.layer[c].rs_pair = rs_ok;
@@ -1687,7 +1656,7 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
         // skip projection -> output projection + solver update (-> the next evaluation's input projection) in one launch with
         // one workgroup per 32-frame tile.  DSD_EDGE: 0 = never (the three GEMMs of gemm.hip), 1 = on every grid, unset = by
         // grid size (tests/test_gpu_edge.py switches it between two handles of one process)
-        pl.edge = o.edge != 0 && wn_edge_supported(C, FM_of(h)) && (o.edge == 1 || tiles_at(h, 32) >= 128);
+        pl.edge = o.edge != 0 && wn_edge_supported(C, FM_of(h)) && (o.edge == 1 || tiles_at(h->rag.grid(), B, T, 32) >= 128);
         return pl;
     }
     // LYNXNet.  Batched grids: the two pointwise GEMMs with the whole K extent of a 32-frame tile resident in LDS
@@ -1695,7 +1664,7 @@ DenoisePlan plan_denoise(const dsd_handle* h) {
     // already fills the chip), pw2 only C / 512 (measured at C = 1024: slower at B = 2, +4 % at 3, +12 % at 4, +10 % at 8), so a
     // single utterance stays on the GEMM family
     const int inner = inner_of(h);
-    const long t32 = tiles_at(h, 32), t64 = tiles_at(h, 64);
+    const long t32 = tiles_at(h->rag.grid(), B, T, 32), t64 = tiles_at(h->rag.grid(), B, T, 64);
     const bool lx_ok = o.lynx_resident != 0 && lx_layer_supported(C, inner);
     const bool res1 = lx_ok && (o.lynx_resident == 1 || t32 * (2 * inner / 512) >= 192);
     const bool res2 = lx_ok && (o.lynx_resident == 1 || t32 * (C / 512) >= 192);
@@ -1751,15 +1720,15 @@ int run_step_tables(dsd_handle* h, int ncols, hipStream_t st) {
     const int C = C_of(h), Ns = h->Ns;
     hipError_t e = launch_sinemb(h->t_dev, ncols, Ns, h->blob.p + h->freqs_off, C, h->E, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "sinemb launch failed: %s", hipGetErrorString(e));
-    GemmCall g0 = make_gemm(h, h->g_emb0, h->E, 0, Ns, 1, ncols, ST_PLAIN, EP_BIAS_ACT, 0);
+    GemmCall g0 = make_gemm(h, h->g_emb0, h->E, 0, Ns, 1, ncols, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
     g0.p.act = h->emb_act; g0.p.out = h->Hd; g0.p.o_bstride = 0; g0.p.o_rstride = Ns;
     int rc = run_gemm(h, g0, st);
     if (rc) return rc;
-    GemmCall g1 = make_gemm(h, h->g_emb1, h->Hd, 0, Ns, 1, ncols, ST_PLAIN, EP_BIAS_ACT, 0);
+    GemmCall g1 = make_gemm(h, h->g_emb1, h->Hd, 0, Ns, 1, ncols, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
     g1.p.act = ACT_NONE; g1.p.out = h->E2; g1.p.o_rstride = Ns;
     rc = run_gemm(h, g1, st);
     if (rc) return rc;
-    GemmCall g2 = make_gemm(h, h->g_dproj, h->E2, 0, Ns, 1, ncols, ST_PLAIN, EP_BIAS_ACT, 0);
+    GemmCall g2 = make_gemm(h, h->g_dproj, h->E2, 0, Ns, 1, ncols, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
     g2.p.act = ACT_NONE; g2.p.out = h->D; g2.p.o_rstride = Ns;
     if ((rc = run_gemm(h, g2, st))) return rc;
     // ... and transposed: a layer's FiLM vector for one step is then C contiguous floats.  Read from D it is a gather of one
@@ -1841,7 +1810,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 const float* next_xin) {
     const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h), L = L_of(h);
     const long xs = (long)C * Ts, cps = (long)L * 2 * C * Ts;
-    const bool ragged = !h->lens_host.empty();
+    const RaggedGrid* rg = h->rag.grid();
     int rc;
     // What follows the layers is decided before they run: the edge kernel (wn_edge.hip, one workgroup per 32-frame tile) where the
     // plan has it and the sampler's terms fit it, else the GEMMs of gemm.hip - and only an evaluation that ends in those runs its
@@ -1850,7 +1819,6 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     bool edge = false;
     int edge_nwg = 0;
     if (pl.edge && nout >= 1 && nout <= kMaxOut) {
-        const int bnw = 32;
         WnEdgeP& p = ep;
         memset(&p, 0, sizeof(p));
         p.A1 = h->blob.p + h->g_tail1.a_off; p.b1 = h->blob.p + h->g_tail1.bias_off;
@@ -1858,7 +1826,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         p.A3 = h->blob.p + h->g_inproj.a_off; p.b3 = h->blob.p + h->g_inproj.bias_off;
         p.skip = h->skip; p.xh = h->xh; p.x_bstride = xs; p.Ts = Ts; p.T = T; p.FM = FM;
         p.in_scale = sqrtf((float)L);
-        p.tiles_per_b = (T + bnw - 1) / bnw; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        edge_nwg = (int)fill_tiles(p, rg, B, T, 32);
         p.nout = nout;
         edge = true;
         for (int i = 0; i < nout; ++i) {
@@ -1877,8 +1845,6 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         if (next_xin)
             for (int i = 0; i < nout; ++i)
                 if (lo[i].dst == next_xin) p.next_src = i;
-        edge_nwg = B * p.tiles_per_b;
-        if (ragged) { p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; edge_nwg = p.ncg; }
     }
     const bool folded = !edge && !h->g_outf.empty();
     const std::vector<PackedGemm>& outp = folded ? h->g_outf : h->g_outp;
@@ -1886,20 +1852,6 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     // bytes: the conv launch reads x and the hoisted conditioner projection and writes z (16 C), the out-proj launch
     // reads z, updates x and the skip sum (20 C); fused: x r/w, conditioner projection, skip r/w (24 C)
     const double fl_conv = 2.0 * 3 * C * 2 * C, fl_out = 2.0 * C * 2 * C;
-    auto seg_frames = [&](int bn, int t0, int nt) -> double {       // valid frames in tiles [t0, t0 + nt) at width bn
-        const int tpb = (T + bn - 1) / bn;
-        double fr = 0;
-        if (!ragged) {
-            for (int i = t0; i < t0 + nt; ++i) fr += std::min(bn, T - (i % tpb) * bn);
-        } else {
-            const int k = bn == 16 ? 0 : bn / 32;
-            for (int i = t0; i < t0 + nt; ++i) {
-                const int e = h->cg_host[k][i], b = e / tpb, ft = e - b * tpb;
-                fr += std::min(bn, h->lens_host[b] - ft * bn);
-            }
-        }
-        return fr;
-    };
     auto layer_params = [&](WnLayerP& p, int l, int bn) {
         memset(&p, 0, sizeof(p));
         p.Aconv = h->blob.p + h->g_conv[l].a_off;
@@ -1910,7 +1862,8 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         p.cp = h->cp + (long)l * 2 * C * Ts; p.cp_bstride = cps;
         film_of(h, l, film_col0, film_colb, p.film, p.film_cstride, p.film_col0, p.film_colb);
         p.dil = 1 << (l % h->cfg.dilation_cycle_length);
-        p.T = T; p.tiles_per_b = (T + bn - 1) / bn; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
+        p.T = T;
+        fill_tiles(p, rg, B, T, bn);
         p.first_layer = (l == 0);
     };
     // the row-split pair (rows per workgroup: 64 = wn_rowsplit.hip, else wn_rows.hip) on the tiles of `p`; class keys 200 + v / 300 + v
@@ -1933,7 +1886,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         const float* xi = h->xh;
         float* xo = h->z;
         std::vector<double> seg_fr(pl.segs.size());
-        for (size_t k = 0; k < pl.segs.size(); ++k) seg_fr[k] = seg_frames(pl.segs[k].bn, pl.segs[k].t0, pl.segs[k].nt);
+        for (size_t k = 0; k < pl.segs.size(); ++k) seg_fr[k] = tile_frames(rg, T, pl.segs[k].bn, pl.segs[k].t0, pl.segs[k].nt);
         for (int l = 0; l < L; ++l) {
             for (size_t k = 0; k < pl.segs.size(); ++k) {
                 const WnSeg& sg = pl.segs[k];
@@ -1942,7 +1895,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 layer_params(p, l, sg.bn);
                 p.xin = xi; p.xout = xo; p.z = h->hbuf;
                 p.tile0 = sg.t0; p.ntiles = sg.nt;
-                if (ragged) { p.lens = h->lens_dev.p; p.cgmap = h->cg_dev[sg.bn == 16 ? 0 : 1].p + sg.t0; p.ncg = sg.nt; }
+                if (rg) { p.cgmap += sg.t0; p.ncg = sg.nt; }      // the segment's slice of the list (item-major order: build_ragged)
                 const int vkey = (int)k * 4 + (p.dil > 8 ? 2 : 0) + (sg.bn == 16 ? 1 : 0);
                 if (sg.kind == WN_FUSED_X3) {
                     p.Aconv = h->blob.p + h->x3_conv[l];
@@ -1961,7 +1914,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
             xo = (xo == h->z) ? h->xh : h->z;
         }
     } else {
-        const double fr_all = ragged ? seg_frames(32, 0, h->cg_n[1]) : (double)B * T;
+        const double fr_all = valid_frames(rg, B, T);
         for (int l = 0; l < L; ++l) {
             const int dil = 1 << (l % h->cfg.dilation_cycle_length);
             const auto& form = pl.layer[l % h->cfg.dilation_cycle_length];
@@ -1969,25 +1922,23 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
                 WnLayerP p;
                 layer_params(p, l, form.rs_bn);
                 p.xin = h->xh; p.xout = h->xh; p.z = h->z;
-                if (ragged) { p.lens = h->lens_dev.p; p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
                 if ((rc = rowsplit(p, l, form.rs_bn, 64, (form.rs_bn == 48 ? 1 : 0) + (dil > 8 ? 2 : 0), fr_all))) return rc;
                 continue;
             }
-            GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, ST_FILM, EP_GATE, dil, false, form.rs_pair);
+            GemmCall g = make_gemm(h, h->g_conv[l], h->xh, xs, Ts, B, T, rg, ST_FILM, EP_GATE, dil, false, form.rs_pair);
             film_of(h, l, film_col0, film_colb, g.p.film, g.p.film_cstride, g.p.film_col0, g.p.film_colb);
             g.p.aux = h->cp + (long)l * 2 * C * Ts; g.p.aux_bstride = cps; g.p.aux_rstride = Ts;
             g.p.out = h->z; g.p.o_bstride = xs; g.p.o_rstride = Ts;
             if ((rc = timed_launch(h, 400 + (dil > 8 ? 2 : 0), fl_conv * fr_all, 16.0 * C * fr_all, "WaveNet conv GEMM", [&] { return run_gemm(h, g, st); })))
                 return rc;
-            GemmCall o = make_gemm(h, outp[l], h->z, xs, Ts, B, T, ST_PLAIN, EP_RESSKIP, 0);
+            GemmCall o = make_gemm(h, outp[l], h->z, xs, Ts, B, T, rg, ST_PLAIN, EP_RESSKIP, 0);
             o.p.C = C; o.p.x = h->xh; o.p.skip = h->skip; o.p.first_layer = (l == 0);
             o.p.o_bstride = xs; o.p.o_rstride = Ts;
             if ((rc = timed_launch(h, 500, fl_out * fr_all, 20.0 * C * fr_all, "WaveNet out-proj GEMM", [&] { return run_gemm(h, o, st); }))) return rc;
         }
     }
     if (edge) {
-        double fr_all = (double)B * T;
-        if (ragged) { fr_all = 0; for (int v : h->lens_host) fr_all += v; }
+        const double fr_all = valid_frames(rg, B, T);
         if ((rc = timed_launch(h, 700, 2.0 * (C * C + 2.0 * C * FM) * fr_all, 4.0 * (2 * C + 3 * FM) * fr_all, "WaveNet edge-kernel",
                                [&] { return launch_wn_edge(ep, C, 2, edge_nwg, st); })))
             return rc;
@@ -1997,12 +1948,12 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     // the GEMMs of gemm.hip.  Folded layers left relu's argument in the skip rows: the output projection stages max(skip, 0)
     // itself (ST_RELU) and hbuf is not written
     if (!folded) {
-        GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, ST_SCALE, EP_BIAS_ACT, 0);
+        GemmCall t1 = make_gemm(h, h->g_tail1, h->skip, xs, Ts, B, T, rg, ST_SCALE, EP_BIAS_ACT, 0);
         t1.p.in_scale = sqrtf((float)L);      // staged value is DIVIDED by in_scale (wavenet.py:96)
         t1.p.act = ACT_RELU; t1.p.out = h->hbuf; t1.p.o_bstride = xs; t1.p.o_rstride = Ts;
         if ((rc = run_gemm(h, t1, st))) return rc;
     }
-    GemmCall t2 = make_gemm(h, h->g_out, folded ? h->skip : h->hbuf, xs, Ts, B, T, folded ? ST_RELU : ST_PLAIN, EP_LINCOMB, 0);
+    GemmCall t2 = make_gemm(h, h->g_out, folded ? h->skip : h->hbuf, xs, Ts, B, T, rg, folded ? ST_RELU : ST_PLAIN, EP_LINCOMB, 0);
     t2.p.nout = nout;
     for (int i = 0; i < nout; ++i) t2.p.lo[i] = lo[i];
     t2.p.o_bstride = (long)FM * Ts; t2.p.o_rstride = Ts;
@@ -2013,7 +1964,7 @@ int run_wavenet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
 int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_colb, const LinOut* lo, int nout, hipStream_t st) {
     const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h), L = L_of(h), inner = inner_of(h);
     const long xs = (long)C * Ts, us = (long)inner * Ts;
-    const bool ragged = !h->lens_host.empty();
+    const RaggedGrid* rg = h->rag.grid();
     const int ln_tiles = (C + 63) / 64;
     int rc;
     // LayerNorm statistics of the next GEMM's input: merged from the producer's per-tile partials by a small kernel
@@ -2023,16 +1974,12 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
     // algorithmic work per valid frame of the two pointwise GEMMs: pw1 C -> 2 inner (reads x_in, writes the
     // SwiGLU product), pw2 inner -> C (reads the depthwise conv's output, the residual stream and the next layer's hoisted
     // conditioner projection, writes x and x_in)
-    double fr = (double)B * T;
-    if (ragged) { fr = 0; for (int v : h->lens_host) fr += v; }
+    const double fr = valid_frames(rg, B, T);
     const double fl1 = 2.0 * C * 2 * inner * fr, by1 = 4.0 * (C + inner) * fr, fl2 = 2.0 * inner * C * fr, by2 = 4.0 * (inner + 4 * C) * fr;
-    auto widen = [&](LxLayerP& q, int ncb) {              // the tile bookkeeping of a launch on 64-frame tiles
-        if (ncb != 4) return;
-        q.tiles_per_b = (T + 63) / 64;
-        q.inv_tiles_per_b = 1.0f / (float)q.tiles_per_b;
+    auto set_tiles = [&](LxLayerP& q, int bn) {           // the tile bookkeeping of a launch on bn-frame tiles
+        const long n = fill_tiles(q, rg, B, T, bn);
         q.nft = B * q.tiles_per_b;
-        if (ragged) { q.cgmap = h->cg_dev[2].p; q.ncg = h->cg_n[2]; }
-        q.inv_nft = 1.0f / (float)std::max(1, ragged ? q.ncg : q.nft);
+        q.inv_nft = 1.0f / (float)std::max(1L, n);
     };
     const PathOpts& o = h->opts;
     for (int l = 0; l < L; ++l) {
@@ -2043,10 +1990,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         p.A2 = h->blob.p + h->g_pw2[l].a_off; p.bias2 = h->blob.p + h->g_pw2[l].bias_off;
         p.xin = h->xin; p.stats = h->stats; p.u = h->ubuf; p.v = h->vbuf; p.x = h->xh;
         p.x_bstride = xs; p.u_bstride = us; p.inner = inner; p.Ts = Ts; p.T = T;
-        p.tiles_per_b = (T + 31) / 32; p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-        p.nft = B * p.tiles_per_b;
-        if (ragged) { p.cgmap = h->cg_dev[1].p; p.ncg = h->cg_n[1]; }
-        p.inv_nft = 1.0f / (float)std::max(1, ragged ? p.ncg : p.nft);
+        set_tiles(p, 32);
         p.strong = h->cfg.strong_cond;
         p.lnpart = h->lnpart; p.lnpart_ts = Ts; p.ln_tiles = ln_tiles; p.ln_rows = true_channels(h);
         p.lnpart_in = h->lnpart;        // (read by pw1 before pw2 of this layer replaces it with the next layer's partials)
@@ -2060,32 +2004,32 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         if (pl.pw1 == LX_X3) {
             LxLayerP q = p;
             q.A1 = h->blob.p + h->x3_conv[l];
-            widen(q, pl.x3_ncb1);
+            if (pl.x3_ncb1 == 4) set_tiles(q, 64);
             rc = timed_launch(h, 650 + (pl.x3_ncb1 == 4 ? 1 : 0), fl1, by1, "LYNXNet pw1", [&] { return launch_lx_x3(q, 0, C, pl.x3_ncb1, st); });
         } else if (pl.pw1 == LX_RESIDENT) {
             rc = timed_launch(h, 600, fl1, by1, "LYNXNet pw1", [&] { return launch_lx_layer(p, 0, C, o.lynx_pw1p, h->cus, st); });
         } else {
-            GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_SWIGLU, 0);
+            GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, rg, ST_LN, EP_SWIGLU, 0);
             g.p.ln_stats = h->stats; g.p.ln_ts = Ts;
             g.p.out = h->ubuf; g.p.o_bstride = us; g.p.o_rstride = Ts;
             rc = timed_launch(h, 630, fl1, by1, "LYNXNet pw1 GEMM", [&] { return run_gemm(h, g, st); });
         }
         if (rc) return rc;
-        rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, ragged ? h->lens_dev.p : nullptr, h->blob.p + h->dw_w[l],
+        rc = launch_rc(h, launch_dwconv(h->ubuf, h->vbuf, us, Ts, inner, B, T, rg ? rg->lens : nullptr, h->blob.p + h->dw_w[l],
                                         h->blob.p + h->dw_b[l], h->cfg.kernel_size, h->cfg.activation,
                                         h->dw_prelu[l] == SIZE_MAX ? nullptr : h->blob.p + h->dw_prelu[l], st), "dwconv");
         if (rc) return rc;
         if (pl.pw2 == LX_X3) {
             LxLayerP q = p;
             q.A2 = h->blob.p + h->x3_out[l];
-            widen(q, pl.x3_ncb2);
+            if (pl.x3_ncb2 == 4) set_tiles(q, 64);
             rc = timed_launch(h, 660 + (pl.x3_ncb2 == 4 ? 1 : 0), fl2, by2, "LYNXNet pw2 (bf16x3)", [&] { return launch_lx_x3(q, 1, C, pl.x3_ncb2, st); });
         } else if (pl.pw2 == LX_RESIDENT) {
             rc = timed_launch(h, 610, fl2, by2, "LYNXNet pw2", [&] { return launch_lx_layer(p, 1, C, o.lynx_pw1p, h->cus, st); });
         } else if (pl.pw2 == LX_PW2Q) {     // 128 rows per workgroup, C / 128 workgroups per frame tile (lynx_layer.hip, lx_pw2q_kernel)
             rc = timed_launch(h, 615, fl2, by2, "LYNXNet pw2 (128-row)", [&] { return launch_lx_pw2q(p, C, st); });
         } else {
-            GemmCall g = make_gemm(h, h->g_pw2[l], h->vbuf, us, Ts, B, T, ST_PLAIN, EP_LYNX_NEXT, 0);
+            GemmCall g = make_gemm(h, h->g_pw2[l], h->vbuf, us, Ts, B, T, rg, ST_PLAIN, EP_LYNX_NEXT, 0);
             g.p.act = ACT_NONE;
             g.p.aux = h->xh; g.p.aux_bstride = xs; g.p.aux_rstride = Ts;
             lynx_next(h, g.p, next, film_col0, film_colb);
@@ -2093,7 +2037,7 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
         }
         if (rc) return rc;
     }
-    GemmCall f = make_gemm(h, h->g_out, h->xh, xs, Ts, B, T, ST_LN, EP_LINCOMB, 0);
+    GemmCall f = make_gemm(h, h->g_out, h->xh, xs, Ts, B, T, rg, ST_LN, EP_LINCOMB, 0);
     if ((rc = ln_merge())) return rc;
     f.p.ln_stats = h->stats; f.p.ln_ts = Ts;
     f.p.nout = nout;
@@ -2107,7 +2051,6 @@ int run_lynxnet(dsd_handle* h, const DenoisePlan& pl, int film_col0, int film_co
 int run_backbone(dsd_handle* h, const DenoisePlan& pl, const float* xin_state, int film_col0, int film_colb, const LinOut* lo,
                  int nout, hipStream_t st, const float* next_xin = nullptr) {
     const int B = h->B, T = h->T, Ts = h->Ts, C = C_of(h), FM = FM_of(h);
-    RaggedScope ragged_scope(h);
     if (h->timing) {      // one empty bracket per evaluation calibrates what a hipEvent pair itself costs
         ++h->timing_evals;
         if (h->cal_used == h->cal_pool.size()) {
@@ -2125,7 +2068,8 @@ int run_backbone(dsd_handle* h, const DenoisePlan& pl, const float* xin_state, i
     const bool inproj_done = !lynx && h->edge_xh_src != nullptr && h->edge_xh_src == xin_state;
     h->edge_xh_src = nullptr;
     if (!inproj_done) {   // input projection (+ReLU for WaveNet, wavenet.py:86-88; GELU unless strong_cond for LYNXNet, lynxnet.py:141-143)
-        GemmCall g = make_gemm(h, h->g_inproj, xin_state, (long)FM * Ts, Ts, B, T, ST_PLAIN, lynx ? EP_LYNX_NEXT : EP_BIAS_ACT, 0);
+        GemmCall g = make_gemm(h, h->g_inproj, xin_state, (long)FM * Ts, Ts, B, T, h->rag.grid(), ST_PLAIN,
+                               lynx ? EP_LYNX_NEXT : EP_BIAS_ACT, 0);
         g.p.act = lynx ? (h->cfg.strong_cond ? ACT_NONE : ACT_GELU) : ACT_RELU;
         g.p.out = h->xh; g.p.o_bstride = (long)C * Ts; g.p.o_rstride = Ts;
         if (lynx) lynx_next(h, g.p, 0, film_col0, film_colb);
@@ -2303,7 +2247,7 @@ int dsd_prepare_cond(dsd_handle* h, const float* cond, int32_t B, int32_t T, int
     const int H = h->cfg.hidden_size, Ts = h->Ts, L = L_of(h), R = cp_rows(h);
     hipError_t e = launch_pack(cond, stride_b, stride_h, stride_t, h->cond_i, B, H, T, Ts, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "pack(cond) launch failed: %s", hipGetErrorString(e));
-    GemmCall g = make_gemm(h, h->g_cp, h->cond_i, (long)H * Ts, Ts, B, T, ST_PLAIN, EP_BIAS_ACT, 0);
+    GemmCall g = make_gemm(h, h->g_cp, h->cond_i, (long)H * Ts, Ts, B, T, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
     g.p.act = ACT_NONE;
     g.p.out = h->cp; g.p.o_bstride = (long)L * R * Ts; g.p.o_rstride = Ts;
     rc = run_gemm(h, g, st);
@@ -2393,12 +2337,12 @@ static int run_fs2_layers(dsd_handle* h, int H, int NL, int heads, int ffn_ks, i
     for (int l = 0; l < NL; ++l) {      // EncSALayer.forward  (common_layers.py:236-268)
         ENC_OK(launch_enc_layernorm(h->e_x, h->e_y, blob + h->e_ln1g[l], blob + h->e_ln1b[l], nullptr, H, B, L, Ls, 1e-5f, st),
                "layer_norm1");
-        GemmCall q = make_gemm(h, h->g_qkv[l], h->e_y, xs, Ls, B, L, ST_PLAIN, EP_BIAS_ACT, 0);
+        GemmCall q = make_gemm(h, h->g_qkv[l], h->e_y, xs, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
         q.p.act = ACT_NONE; q.p.out = h->e_qkv; q.p.o_bstride = 3 * xs; q.p.o_rstride = Ls;
         if ((rc = run_gemm(h, q, st))) return rc;
         if (h->e_pos == DSD_POS_ROPE) ENC_OK(launch_enc_rope(h->e_qkv, blob + h->e_freqs, H, H / heads, B, L, Ls, st), "rope");
         ENC_OK(launch_enc_attention(h->e_qkv, h->e_nonpad, h->e_y, H, heads, B, L, Ls, st), "attention");
-        GemmCall o = make_gemm(h, h->g_oproj[l], h->e_y, xs, Ls, B, L, ST_PLAIN, EP_BIAS_RES, 0);
+        GemmCall o = make_gemm(h, h->g_oproj[l], h->e_y, xs, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_RES, 0);
         o.p.aux = h->e_x; o.p.aux_bstride = xs; o.p.aux_rstride = Ls;
         o.p.out = h->e_x; o.p.o_bstride = xs; o.p.o_rstride = Ls;
         if ((rc = run_gemm(h, o, st))) return rc;
@@ -2409,12 +2353,12 @@ static int run_fs2_layers(dsd_handle* h, int H, int NL, int heads, int ffn_ks, i
         // SwiGLU: Conv1d(H, 8H, k), then rows [0, 4H) *= silu(rows [4H, 8H)) in place (common_layers.py:107-117)
         const int fa = h->e_ffn_act;
         const long ms = (fa == DSD_FFN_SWIGLU ? 8 : 4) * xs;
-        GemmCall f1 = make_gemm(h, h->g_ffn1[l], h->e_y, xs, Ls, B, L, ST_PLAIN, EP_BIAS_ACT, 1, ffn_ks > 1);
+        GemmCall f1 = make_gemm(h, h->g_ffn1[l], h->e_y, xs, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_ACT, 1, ffn_ks > 1);
         f1.p.act = fa == DSD_FFN_GELU ? ACT_GELU : fa == DSD_FFN_RELU ? ACT_RELU : fa == DSD_FFN_SWISH ? ACT_SILU : ACT_NONE;
         f1.p.out = h->e_mid; f1.p.o_bstride = ms; f1.p.o_rstride = Ls;
         if ((rc = run_gemm(h, f1, st))) return rc;
         if (fa == DSD_FFN_SWIGLU) ENC_OK(launch_enc_swiglu(h->e_mid, 4 * H, ms, B, L, Ls, st), "swiglu");
-        GemmCall f2 = make_gemm(h, h->g_ffn2[l], h->e_mid, ms, Ls, B, L, ST_PLAIN, EP_BIAS_RES, 0);
+        GemmCall f2 = make_gemm(h, h->g_ffn2[l], h->e_mid, ms, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_RES, 0);
         f2.p.aux = h->e_x; f2.p.aux_bstride = xs; f2.p.aux_rstride = Ls;
         f2.p.out = h->e_x; f2.p.o_bstride = xs; f2.p.o_rstride = Ls;
         if ((rc = run_gemm(h, f2, st))) return rc;
@@ -2561,7 +2505,7 @@ int dsd_token_encode(dsd_handle* h, const float* embed, const uint8_t* padding_m
     const float* res = h->e_y;
     int Ho = H;
     if (t.out_dims > 0) {      // MelodyEncoder.out_proj (variance_encoder.py:147)
-        GemmCall o = make_gemm(h, h->g_tout, h->e_y, (long)H * Ls, Ls, B, L, ST_PLAIN, EP_BIAS_ACT, 0);
+        GemmCall o = make_gemm(h, h->g_tout, h->e_y, (long)H * Ls, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_ACT, 0);
         o.p.act = ACT_NONE; o.p.out = h->e_mid; o.p.o_bstride = (long)t.out_dims * Ls; o.p.o_rstride = Ls;
         if ((rc = run_gemm(h, o, st))) return rc;
         res = h->e_mid;
@@ -2591,7 +2535,7 @@ int dsd_predict_dur(dsd_handle* h, const float* dur_cond, const uint8_t* padding
     const float* cur = h->d_in;
     int cin = H;
     for (int l = 0; l < t.dur_layers; ++l) {      // Conv1d -> ReLU -> LayerNorm(channels, eps 1e-12) -> * mask  (tts_modules.py:124-127)
-        GemmCall g = make_gemm(h, h->g_dconv[l], cur, (long)cin * Ls, Ls, B, L, ST_PLAIN, EP_BIAS_ACT, 1, t.dur_kernel_size > 1);
+        GemmCall g = make_gemm(h, h->g_dconv[l], cur, (long)cin * Ls, Ls, B, L, nullptr, ST_PLAIN, EP_BIAS_ACT, 1, t.dur_kernel_size > 1);
         g.p.act = ACT_RELU; g.p.out = h->d_a; g.p.o_bstride = (long)Cd * Ls; g.p.o_rstride = Ls;
         if ((rc = run_gemm(h, g, st))) return rc;
         ENC_OK(launch_enc_layernorm(h->d_a, h->d_b, blob + h->d_lng[l], blob + h->d_lnb[l], h->e_nonpad, Cd, B, L, Ls, 1e-12f, st),
@@ -2633,7 +2577,7 @@ int dsd_cond_assemble(const dsd_assemble_args* args, float* out, void* stream) {
 }
 
 static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float* out, const float* res, int B, int C,
-                     int T, int Ts, int dil, float slope_in, int act, hipStream_t st, const VocRagStage* vr = nullptr) {
+                     int T, int Ts, int dil, float slope_in, int act, const RaggedGrid* rg, hipStream_t st) {
     TConvP p;
     memset(&p, 0, sizeof(p));
     p.W = h->blob.p + pt.w_off;
@@ -2648,10 +2592,7 @@ static int run_tconv(dsd_handle* h, const PackedTConv& pt, const float* x, float
     p.SP = SP;
     p.slope_in = slope_in; p.act = act; p.co_real = pt.co_real;
     p.lds_bytes = tconv_lds_bytes(pt.ci, pt.co, pt.taps, SP);
-    if (vr) {
-        p.lens = vr->lens; p.cgmap = vr->tc; p.ncg = vr->ntc;
-        p.tiles = (T + 255) / 256;
-    }
+    fill_tiles(p, rg, B, T, 256);
     if (p.lds_bytes > 160 * 1024) return fail(h, DSD_EINVAL, "few-channel conv needs %d bytes of LDS", p.lds_bytes);
     hipError_t e = launch_tconv(p, pt.ci, pt.co, B, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "tconv launch failed: %s", hipGetErrorString(e));
@@ -2743,18 +2684,17 @@ namespace {
 // when the images fit in LDS and that still gives every CU a workgroup, else 32 - the result does not depend on it.  Returns
 // DSD_OK with *ran = false where the launch is outside the kernel's 32-bit addressing: the caller runs the fp32 GEMM.
 int run_voc_x3(dsd_handle* h, size_t stream, const PackedGemm& g, const float* x, const float* res, float* out, int B, int C,
-               int T, int Ts, int dil, float slope_in, float slope_out, const VocRagStage* vr, hipStream_t st, bool* ran) {
+               int T, int Ts, int dil, float slope_in, float slope_out, const RaggedGrid* rg, hipStream_t st, bool* ran) {
     *ran = false;
     int ncb = voc_x3_max_ncb(C, g.taps, dil);
     if (stream == SIZE_MAX || ncb == 0 || (long)C * Ts * 4 >= (1L << 31) - (1L << 20)) return DSD_OK;
-    const long t64 = vr ? (long)vr->ncg[2] : (long)B * ((T + 63) / 64);
+    const long t64 = tiles_at(rg, B, T, 64);
     const int xw = h->opts.x3_wide;                      // DSD_X3_WIDE: 0 never 64-frame tiles, 1 wherever they fit
     if (ncb == 4 && (xw == 0 || (xw != 1 && t64 < h->cus))) ncb = 2;
     const int BN = 16 * ncb;
     VocX3P p;
     memset(&p, 0, sizeof(p));
-    p.tiles_per_b = (T + BN - 1) / BN;
-    const long ntiles = vr ? (long)vr->ncg[ncb / 2] : (long)B * p.tiles_per_b;
+    const long ntiles = fill_tiles(p, rg, B, T, BN);
     if ((long)B * p.tiles_per_b >= (1L << 22)) return DSD_OK;
     p.W = h->blob.p + stream;
     p.bias = h->blob.p + g.bias_off;
@@ -2766,12 +2706,8 @@ int run_voc_x3(dsd_handle* h, size_t stream, const PackedGemm& g, const float* x
     p.nfq = (BN + 2 * p.HL) / 4;
     p.inv_nfq = 1.0f / (float)p.nfq;
     p.slope_in = slope_in; p.slope_out = slope_out;
-    p.inv_tiles_per_b = 1.0f / (float)p.tiles_per_b;
-    if (vr) {
-        p.lens = vr->lens; p.cgmap = vr->cg[ncb / 2]; p.ncg = vr->ncg[ncb / 2];
-    }
-    const double frames = vr ? (double)vr->valid : (double)B * T;
-    const int rc = timed_launch(h, 900 + 4 * voc_x3_mbw(C) + ncb + (vr ? 1 : 0), 2.0 * C * C * g.taps * frames,
+    const double frames = valid_frames(rg, B, T);
+    const int rc = timed_launch(h, 900 + 4 * voc_x3_mbw(C) + ncb + (rg ? 1 : 0), 2.0 * C * C * g.taps * frames,
                                 4.0 * C * frames * (res ? 3 : 2), "vocoder split-bf16 conv",
                                 [&] { return launch_voc_x3(p, ncb, (int)ntiles, st); });
     if (rc) return rc;
@@ -2780,60 +2716,17 @@ int run_voc_x3(dsd_handle* h, size_t stream, const PackedGemm& g, const float* x
     return DSD_OK;
 }
 
-// dsd_vocode_ragged's bookkeeping: item lengths at every rate and the lists of tiles that hold valid frames - for the GEMMs
-// at 32 / 64 frames (the vocoder's convolutions run on the generic path or on voc_x3.hip, never on 16-frame tiles) and for tconv.hip at 256 -
-// in one device block, copied on the caller's stream; kept while B, T and the lengths stay the same
+// dsd_vocode_ragged's bookkeeping: item lengths and valid-tile lists at every rate of the generator (rate i = after i upsamplings)
+// - for the GEMMs and voc_x3.hip at 32 / 64 frames (the vocoder's convolutions never run on 16-frame tiles; the count at 16 is
+// there for make_gemm's tile-width choice) and for tconv.hip at 256 - with the vocoder policies (RaggedGrid); kept while B, T
+// and the lengths stay the same
 int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipStream_t st) {
-    const dsd_vocoder_config& v = h->vcfg;
-    std::vector<int> key = {B, T};
-    key.insert(key.end(), lengths, lengths + B);
-    if (h->vr_dev.p && key == h->vr_key) return DSD_OK;
-    const int NU = v.n_ups;
-    std::vector<VocRagStage> st_(NU + 1);
-    std::vector<int>& host = h->vr_host;
-    host.clear();
-    std::vector<size_t> off_lens(NU + 1), off_cg[2], off_tc(NU + 1);
-    off_cg[0].resize(NU + 1);
-    off_cg[1].resize(NU + 1);
-    long mul = 1;
-    for (int i = 0; i <= NU; ++i) {
-        VocRagStage& r = st_[i];
-        r.T = (int)(T * mul);
-        off_lens[i] = host.size();
-        for (int b = 0; b < B; ++b) {
-            host.push_back((int)(lengths[b] * mul));
-            r.valid += lengths[b] * mul;
-        }
-        for (int k = 0; k < 3; ++k) {       // tile counts at 16 / 32 / 64 frames (the GEMM's tile-width choice reads them)
-            const int BN = 16 << k;
-            for (int b = 0; b < B; ++b) r.ncg[k] += (int)((lengths[b] * mul + BN - 1) / BN);
-        }
-        for (int k = 1; k < 3; ++k) {
-            const int BN = 16 << k, tiles = (r.T + BN - 1) / BN;
-            off_cg[k - 1][i] = host.size();
-            for (int b = 0; b < B; ++b)
-                for (long ft = 0; ft * BN < lengths[b] * mul; ++ft) host.push_back(b * tiles + (int)ft);
-        }
-        off_tc[i] = host.size();
-        const int tiles = (r.T + 255) / 256;
-        for (int b = 0; b < B; ++b)
-            for (long ft = 0; ft * 256 < lengths[b] * mul; ++ft) host.push_back(b * tiles + (int)ft);
-        r.ntc = (int)(host.size() - off_tc[i]);
-        if (i < NU) mul *= v.upsample_rates[i];
+    if (!h->vrag.built_for(lengths, B, T)) {
+        std::vector<long> mult = {1};
+        for (int i = 0; i < h->vcfg.n_ups; ++i) mult.push_back(mult.back() * h->vcfg.upsample_rates[i]);
+        h->vrag.build(lengths, B, T, RAG_W32 | RAG_W64 | RAG_W256, mult, true, true);
     }
-    if (int rc = h->vr_dev.reserve(h, host.size(), "dsd_vocode_ragged")) return rc;
-    h->vr_key.clear();          // stale until the copy is queued
-    if (hipMemcpyAsync(h->vr_dev.p, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail(h, DSD_EHIP, "dsd_vocode_ragged: copy of the tile lists failed");
-    for (int i = 0; i <= NU; ++i) {
-        st_[i].lens = h->vr_dev.p + off_lens[i];
-        st_[i].cg[1] = h->vr_dev.p + off_cg[0][i];
-        st_[i].cg[2] = h->vr_dev.p + off_cg[1][i];
-        st_[i].tc = h->vr_dev.p + off_tc[i];
-    }
-    h->vr_st = st_;
-    h->vr_key = key;
-    return DSD_OK;
+    return upload_ragged(h, h->vrag, "dsd_vocode_ragged", st);
 }
 
 // dsd_vocode and dsd_vocode_ragged (lengths != nullptr: item b is computed as if alone at T = lengths[b])
@@ -2892,7 +2785,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     h->v_x3_ran = false;
     if (lengths && (rc = prepare_voc_ragged(h, B, T, lengths, st))) return rc;
     // per rate: nullptr (dense) or the ragged batch's lengths and tiles
-    auto rag = [&](int i) -> const VocRagStage* { return lengths ? &h->vr_st[i] : nullptr; };
+    auto rag = [&](int i) -> const RaggedGrid* { return lengths ? h->vrag.grid(i) : nullptr; };
     const float* blob = h->blob.p;
     hipError_t er;
 #define VOC_OK(expr, what)                                                                        \
@@ -2912,8 +2805,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     // conv_pre  (models.py:227, 267)
     VOC_OK(launch_pack(mel, stride_b, stride_m, stride_t, h->v_mel, B, v.num_mels, T, Ts0, st), "pack(mel)");
     {
-        GemmCall g = make_gemm(h, h->v_pre, h->v_mel, (long)v.num_mels * Ts0, Ts0, B, T, ST_PLAIN, EP_BIAS_ACT, 1, true, false,
-                               rag(0));
+        GemmCall g = make_gemm(h, h->v_pre, h->v_mel, (long)v.num_mels * Ts0, Ts0, B, T, rag(0), ST_PLAIN, EP_BIAS_ACT, 1, true);
         g.p.act = ACT_NONE; g.p.out = h->v_pre_out; g.p.o_bstride = (long)C0 * Ts0; g.p.o_rstride = Ts0;
         if ((rc = run_gemm(h, g, st))) return rc;
     }
@@ -2931,7 +2823,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         float* acc = h->v_buf[4 * i + 3];
         const long xs = (long)ch * Tsq;
         {   // leaky_relu -> ConvTranspose1d  (models.py:271-272)
-            GemmCall g = make_gemm(h, h->v_ups[i], cur, (long)cur_c * Tsi, Tsi, B, Tin, ST_LRELU, EP_SCATTER, 1, true, false, rag(i));
+            GemmCall g = make_gemm(h, h->v_ups[i], cur, (long)cur_c * Tsi, Tsi, B, Tin, rag(i), ST_LRELU, EP_SCATTER, 1, true);
             g.p.in_scale = 0.1f; g.p.C = ch; g.p.up = u;
             g.p.out = x; g.p.o_bstride = xs; g.p.o_rstride = Tsq;
             if ((rc = run_gemm(h, g, st))) return rc;
@@ -2964,11 +2856,11 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                 const int dil = v.resblock_dilation_sizes[j][d];
                 if (!tv.empty()) {          // 16 / 32 channels: time-major convolutions (tconv.hip)
                     if (v.resblock == 1) {
-                        if ((rc = run_tconv(h, tv[2 * d], src, t1, nullptr, B, ch, Tq, Tsq, dil, 0.1f, ACT_LRELU, st, rag(i + 1)))) return rc;
-                        if ((rc = run_tconv(h, tv[2 * d + 1], t1, r, src, B, ch, Tq, Tsq, 1, 1.f, ACT_NONE, st, rag(i + 1)))) return rc;
+                        if ((rc = run_tconv(h, tv[2 * d], src, t1, nullptr, B, ch, Tq, Tsq, dil, 0.1f, ACT_LRELU, rag(i + 1), st))) return rc;
+                        if ((rc = run_tconv(h, tv[2 * d + 1], t1, r, src, B, ch, Tq, Tsq, 1, 1.f, ACT_NONE, rag(i + 1), st))) return rc;
                     } else {
                         float* dst = src == x ? r : t1;
-                        if ((rc = run_tconv(h, tv[d], src, dst, src, B, ch, Tq, Tsq, dil, 0.1f, ACT_NONE, st, rag(i + 1)))) return rc;
+                        if ((rc = run_tconv(h, tv[d], src, dst, src, B, ch, Tq, Tsq, dil, 0.1f, ACT_NONE, rag(i + 1), st))) return rc;
                         if (dst == t1) {
                             float* tmp = r; r = t1; t1 = tmp;
                         }
@@ -2978,16 +2870,14 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                 if (v.resblock == 1) {
                     if ((rc = x3(2 * d, cv[2 * d], src, nullptr, t1, dil, 0.1f, 0.1f, &ran))) return rc;
                     if (!ran) {
-                        GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, dil, true, false,
-                                                rag(i + 1));
+                        GemmCall c1 = make_gemm(h, cv[2 * d], src, xs, Tsq, B, Tq, rag(i + 1), ST_LRELU, EP_BIAS_ACT, dil, true);
                         c1.p.in_scale = 0.1f; c1.p.act = ACT_LRELU;
                         c1.p.out = t1; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
                         if ((rc = run_gemm(h, c1, st))) return rc;
                     }
                     if ((rc = x3(2 * d + 1, cv[2 * d + 1], t1, src, r, 1, 1.f, 1.f, &ran))) return rc;
                     if (ran) continue;
-                    GemmCall c2 = make_gemm(h, cv[2 * d + 1], t1, xs, Tsq, B, Tq, ST_PLAIN, EP_BIAS_RES, 1, true, false,
-                                            rag(i + 1));
+                    GemmCall c2 = make_gemm(h, cv[2 * d + 1], t1, xs, Tsq, B, Tq, rag(i + 1), ST_PLAIN, EP_BIAS_RES, 1, true);
                     c2.p.aux = src; c2.p.aux_bstride = xs; c2.p.aux_rstride = Tsq;
                     c2.p.out = r; c2.p.o_bstride = xs; c2.p.o_rstride = Tsq;
                     if ((rc = run_gemm(h, c2, st))) return rc;
@@ -2997,8 +2887,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
                     float* dst = (src == x || src == t1) ? r : t1;
                     if ((rc = x3(d, cv[d], src, src, dst, dil, 0.1f, 1.f, &ran))) return rc;
                     if (!ran) {
-                        GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, ST_LRELU, EP_BIAS_RES, dil, true, false,
-                                                rag(i + 1));
+                        GemmCall c1 = make_gemm(h, cv[d], src, xs, Tsq, B, Tq, rag(i + 1), ST_LRELU, EP_BIAS_RES, dil, true);
                         c1.p.in_scale = 0.1f;
                         c1.p.aux = src; c1.p.aux_bstride = xs; c1.p.aux_rstride = Tsq;
                         c1.p.out = dst; c1.p.o_bstride = xs; c1.p.o_rstride = Tsq;
@@ -3017,9 +2906,9 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
     {   // leaky_relu (default slope 0.01) -> conv_post -> tanh  (models.py:287-289)
         const int ch = voc_stage_channels(v, NU - 1), Tq = (int)len[NU], Tsq = lts[NU];
         if (h->v_postt.valid()) {
-            if ((rc = run_tconv(h, h->v_postt, cur, h->v_wav, nullptr, B, ch, Tq, Tsq, 1, 0.01f, ACT_TANH, st, rag(NU)))) return rc;
+            if ((rc = run_tconv(h, h->v_postt, cur, h->v_wav, nullptr, B, ch, Tq, Tsq, 1, 0.01f, ACT_TANH, rag(NU), st))) return rc;
         } else {
-            GemmCall g = make_gemm(h, h->v_post, cur, (long)ch * Tsq, Tsq, B, Tq, ST_LRELU, EP_BIAS_ACT, 1, true, false, rag(NU));
+            GemmCall g = make_gemm(h, h->v_post, cur, (long)ch * Tsq, Tsq, B, Tq, rag(NU), ST_LRELU, EP_BIAS_ACT, 1, true);
             g.p.in_scale = 0.01f; g.p.act = ACT_TANH;
             g.p.out = h->v_wav; g.p.o_bstride = Tsq; g.p.o_rstride = Tsq;
             if ((rc = run_gemm(h, g, st))) return rc;
@@ -3058,34 +2947,34 @@ int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_workspace(h, B, T, st))) return rc;
     if ((rc = check_lens(h, "dsd_aux_decode", B, T, st))) return rc;
-    RaggedScope ragged_scope(h);
+    const RaggedGrid* rg = h->rag.grid();
     const int H = h->cfg.hidden_size, Ts = h->Ts, L = L_of(h), C = C_of(h), M = FM_of(h);
     const long xs = (long)C * Ts, us = (long)4 * C * Ts;
     hipError_t e = launch_pack(cond, stride_b, stride_h, stride_t, h->cond_i, B, H, T, Ts, st);
     if (e != hipSuccess) return fail(h, DSD_EHIP, "pack(cond) launch failed: %s", hipGetErrorString(e));
     {   // inconv: Conv1d(H, C, k, padding=(k-1)//2)   convnext.py:63-66,80
-        GemmCall g = make_gemm(h, h->g_ain, h->cond_i, (long)H * Ts, Ts, B, T, ST_PLAIN, EP_BIAS_ACT, 1);
+        GemmCall g = make_gemm(h, h->g_ain, h->cond_i, (long)H * Ts, Ts, B, T, rg, ST_PLAIN, EP_BIAS_ACT, 1);
         g.p.act = ACT_NONE; g.p.out = h->xh; g.p.o_bstride = xs; g.p.o_rstride = Ts;
         if ((rc = run_gemm(h, g, st))) return rc;
     }
     for (int l = 0; l < L; ++l) {      // ConvNeXtBlock.forward   convnext.py:40-56
-        e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, h->lens_host.empty() ? nullptr : h->lens_dev.p,
+        e = launch_dwconv(h->xh, h->xin, xs, Ts, C, B, T, rg ? rg->lens : nullptr,
                           h->blob.p + h->dw_w[l], h->blob.p + h->dw_b[l], 7, 3, nullptr, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "dwconv launch failed: %s", hipGetErrorString(e));
         // (statistics only, over the caller's channels: rows beyond them are zero padding, pad_weights)
         e = launch_lynx_pre(h->xin, nullptr, nullptr, 0, nullptr, 0, 0, 0, xs, Ts, true_channels(h), B, T, 0, h->stats, Ts, 1e-6f, st);
         if (e != hipSuccess) return fail(h, DSD_EHIP, "LayerNorm stats launch failed: %s", hipGetErrorString(e));
-        GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, ST_LN, EP_BIAS_ACT, 0);
+        GemmCall g = make_gemm(h, h->g_pw1[l], h->xin, xs, Ts, B, T, rg, ST_LN, EP_BIAS_ACT, 0);
         g.p.ln_stats = h->stats; g.p.ln_ts = Ts;
         g.p.act = ACT_GELU; g.p.out = h->ubuf; g.p.o_bstride = us; g.p.o_rstride = Ts;
         if ((rc = run_gemm(h, g, st))) return rc;
-        GemmCall o = make_gemm(h, h->g_pw2[l], h->ubuf, us, Ts, B, T, ST_PLAIN, EP_BIAS_RES, 0);
+        GemmCall o = make_gemm(h, h->g_pw2[l], h->ubuf, us, Ts, B, T, rg, ST_PLAIN, EP_BIAS_RES, 0);
         o.p.aux = h->xh; o.p.aux_bstride = xs; o.p.aux_rstride = Ts;
         o.p.out = h->xh; o.p.o_bstride = xs; o.p.o_rstride = Ts;
         if ((rc = run_gemm(h, o, st))) return rc;
     }
     {   // outconv: Conv1d(C, M, k)   convnext.py:73-76,83
-        GemmCall g = make_gemm(h, h->g_aout, h->xh, xs, Ts, B, T, ST_PLAIN, EP_BIAS_ACT, 1);
+        GemmCall g = make_gemm(h, h->g_aout, h->xh, xs, Ts, B, T, rg, ST_PLAIN, EP_BIAS_ACT, 1);
         g.p.act = ACT_NONE; g.p.out = h->io_out; g.p.o_bstride = (long)M * Ts; g.p.o_rstride = Ts;
         if ((rc = run_gemm(h, g, st))) return rc;
     }
@@ -3216,8 +3105,8 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
         key.append((const char*)&T, sizeof(T));
         key.append((const char*)&h->opts, sizeof(PathOpts));      // the path switches: a graph is ONE set of launch choices
         key.append((const char*)&h->precision, sizeof(int));
-        key.push_back(h->lens_host.empty() ? 'd' : 'r');       // dense / ragged: other kernels, and grids that follow
-        for (int v : h->lens_host) key.append((const char*)&v, sizeof(v));      // the lengths (baked into the launches)
+        key.push_back(h->rag.active ? 'r' : 'd');       // dense / ragged: other kernels, and grids that follow
+        if (h->rag.active) key.append((const char*)h->rag.lengths(), sizeof(int) * B);      // the lengths (baked into the launches)
         auto it = h->graphs.find(key);
         if (it == h->graphs.end() && (flags & DSD_SAMPLE_GRAPH_LAZY) && !h->graph_seen.count(key)) {
             // DSD_SAMPLE_GRAPH_LAZY, first sight of this (program, batch shape): run it eagerly; the graph is built when the
@@ -3280,21 +3169,16 @@ int dsd_set_lengths(dsd_handle* h, const int32_t* lengths, int32_t B, void* stre
     if (!h) return DSD_EINVAL;
     if (int rc = enter(h, "dsd_set_lengths", K_DENOISER | K_AUX)) return rc;        // the kinds that take ragged batches
     if (!lengths) {             // back to dense batches
-        h->lens_host.clear();
+        h->rag.active = false;
         return DSD_OK;
     }
     if (B < 1) return fail(h, DSD_EINVAL, "dsd_set_lengths: B must be positive (%d)", B);
     for (int b = 0; b < B; ++b)
         if (lengths[b] < 0) return fail(h, DSD_EINVAL, "dsd_set_lengths: lengths[%d] = %d is negative", b, lengths[b]);
-    HIP_OK(h, hipSetDevice(h->cfg.device));
-    if ((size_t)B > h->lens_dev.cap) {
-        if (int rc = h->lens_dev.reserve(h, (size_t)B, "dsd_set_lengths")) return rc;
-        destroy_graphs(h);      // cached graphs captured the old pointer
-    }
-    h->lens_host.assign(lengths, lengths + B);
-    h->cg_T = -1;               // the valid-tile lists follow the lengths
-    // stream-ordered behind earlier launches that still read the old values
-    HIP_OK(h, hipMemcpyAsync(h->lens_dev.p, h->lens_host.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice, (hipStream_t)stream));
+    // copied now; the block goes to the device on the stream of the next call that launches on it (check_lens), behind whatever
+    // that stream still runs on the old values
+    if (h->rag.built_for(lengths, B, h->T)) h->rag.active = true;
+    else build_lengths(h, lengths, B, h->T);
     return DSD_OK;
 }
 
@@ -3326,7 +3210,7 @@ int dsd_get_stats(const dsd_handle* h, dsd_stats* out) {
         // layer forms apart by "+ 3" / "+ 1", so the count keeps that meaning
         const DenoisePlan pl = h->arena.p ? plan_denoise(h) : DenoisePlan();
         out->layer_launches = pl.segs.empty() ? 2 : 0;
-        if (pl.segs.empty()) out->split_tiles = (int32_t)tiles_at(h, 32);
+        if (pl.segs.empty()) out->split_tiles = (int32_t)tiles_at(h->rag.grid(), h->B, h->T, 32);
         for (const WnSeg& sg : pl.segs) {
             out->layer_launches += sg.kind == WN_ROWSPLIT ? 2 : 1;
             (sg.kind == WN_ROWSPLIT ? out->split_tiles : out->fused_tiles) += sg.nt;

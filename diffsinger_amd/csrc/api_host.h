@@ -18,6 +18,7 @@
 
 #include "../../include/dsdenoise.h"
 #include "dsd_internal.h"
+#include "ragged_tiles.h"
 
 using namespace dsd;
 
@@ -93,15 +94,35 @@ struct GraphEntry {
     hipGraphExec_t exec = nullptr;
 };
 
-// dsd_vocode_ragged: one rate of the generator (stage i = after i upsamplings), all pointers into dsd_handle::vr_dev
-struct VocRagStage {
-    int T = 0;                          // padded length of the batch at this rate
-    const int* lens = nullptr;          // [B] item lengths at this rate
-    long valid = 0;                     // their sum
-    const int* cg[3] = {};              // GEMM column groups (item, frame tile) with valid frames, 16 / 32 / 64-frame tiles
-    int ncg[3] = {};
-    const int* tc = nullptr;            // tconv.hip's 256-frame tiles with valid frames
-    int ntc = 0;
+// A ragged batch's host block, its copy on the device and the key both were built for: build_ragged's output for (B, T, lengths)
+// at every rate of `mult`, and the grids over it.  build() is host work only; upload_ragged (api.hip) puts the block on the
+// device before the first launch that reads it - on the caller's stream, outside any capture - and destroys the cached graphs
+// when the block had to move.  The same key always gives the same offsets, so while the block stays where it is a graph
+// captured for a key finds its lists at the addresses and with the contents it was captured with.
+struct RaggedOwner {
+    std::vector<int> key;               // {B, T, lengths...} of `host` (empty: nothing built)
+    std::vector<int> host;
+    DevBuf<int> dev;
+    size_t dense = 0;                   // what `dev` reserves: the block of this (B, T) with every item T long
+    bool on_device = false;             // `dev` holds `host`
+    bool active = false;                // the denoiser side: dsd_set_lengths gave lengths (NULL clears it, the block stays)
+    std::vector<RaggedGrid> grids;      // per rate; upload_ragged points them at the device copy
+    const RaggedGrid* grid(size_t rate = 0) const { return active ? &grids[rate] : nullptr; }
+    const int* lengths() const { return key.data() + 2; }
+    bool built_for(const int* lengths, int B, int T) const {
+        return key.size() == (size_t)B + 2 && key[0] == B && key[1] == T && std::equal(lengths, lengths + B, key.begin() + 2);
+    }
+    // `lengths` may be this owner's own (a rebuild at another T)
+    void build(const int* lengths, int B, int T, unsigned widths, const std::vector<long>& mult, bool nb_by_valid_tiles,
+               bool mask_every_gemm) {
+        std::vector<int> k = {B, T};
+        k.insert(k.end(), lengths, lengths + B);
+        key.swap(k);
+        dense = build_ragged(this->lengths(), B, T, widths, mult, host, grids);
+        for (RaggedGrid& g : grids) { g.nb_by_valid_tiles = nb_by_valid_tiles; g.mask_every_gemm = mask_every_gemm; }
+        on_device = false;
+        active = true;
+    }
 };
 
 // dsd_mel_analyze: per handle, the filterbank on the device and the DFT bases of the (N', W') sizes met so far
@@ -181,10 +202,8 @@ struct dsd_handle {
     DevBuf<float> v_arena;
     std::vector<float*> v_buf;                       // per stage: x, t1, r, acc
     float *v_mel = nullptr, *v_pre_out = nullptr, *v_har = nullptr, *v_phase = nullptr, *v_wav = nullptr;
-    // ragged vocoder batches: per-rate lengths and valid-tile lists (one device block, rebuilt when B, T or the lengths change)
-    std::vector<int> vr_key, vr_host;
-    DevBuf<int> vr_dev;
-    std::vector<VocRagStage> vr_st;
+    // ragged vocoder batches (dsd_vocode_ragged): lengths and valid-tile lists at every rate of the generator
+    RaggedOwner vrag;
     // mel analysis (dsd_mel_create): the config, the filterbank's packed non-zero runs and the device blocks of dsd_mel_analyze
     MelState* mel = nullptr;
     // RMVPE pitch extraction (dsd_rmvpe_create): config, packed weights, its own mel front end, workspace
@@ -221,15 +240,8 @@ struct dsd_handle {
     float *xin = nullptr, *ubuf = nullptr, *vbuf = nullptr, *stats = nullptr, *lnpart = nullptr;
     float *io_in = nullptr, *io_out = nullptr;
     bool cond_ready = false;
-    // ragged batches (dsd_set_lengths): per-item valid lengths on the device, nullptr = dense
-    DevBuf<int> lens_dev;
-    std::vector<int> lens_host;
-    // ... and, per tile width (16 / 32 / 64 frames), the list of column groups (item, frame tile) with valid frames
-    DevBuf<int> cg_dev[3];
-    int cg_n[3] = {0, 0, 0};
-    std::vector<int> cg_host[3];
-    int cg_T = -1;                  // the T the lists were built for (-1: stale)
-    bool use_cg = false;            // set around the launch sequences that may skip padded tiles
+    // ragged batches of the denoisers and the aux decoder (dsd_set_lengths): lengths and valid-tile lists; grid() == nullptr = dense
+    RaggedOwner rag;
     // sampler state buffers
     DevBuf<float> state;
     int state_nbufs = 0;
