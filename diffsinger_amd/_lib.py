@@ -52,6 +52,8 @@ EXPORTS = [
     "dsd_diffuse", "dsd_masked_loss", "dsd_curve_stats", "dsd_dur_score",
     "dsd_model_open", "dsd_model_close", "dsd_model_count", "dsd_model_find", "dsd_model_section", "dsd_model_config",
     "dsd_model_tensor", "dsd_model_meta_at", "dsd_model_meta", "dsd_model_create",
+    "dsd_variance_open", "dsd_variance_close", "dsd_variance_info", "dsd_variance_backbone", "dsd_variance_encode",
+    "dsd_variance_dur", "dsd_variance_pitch_cond", "dsd_variance_cond", "dsd_variance_pitch_post", "dsd_variance_post",
 ]
 DSD_API_VERSION = 10
 DSD_EINVAL, DSD_ESTATE, DSD_EHIP, DSD_ENOMEM, DSD_ENOTFOUND, DSD_EIO = -1, -2, -3, -4, -5, -6
@@ -59,6 +61,7 @@ DSD_MODEL_FORMAT_VERSION, DSD_MODEL_MAX_SECTIONS, DSD_MODEL_MAX_TENSORS, DSD_MOD
 DSD_MODEL_MAX_NAME, DSD_MODEL_ALIGN = 255, 64
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
+DSD_VARIANCE_TABLES, DSD_VAR_PITCH, DSD_VAR_VARIANCES, DSD_VAR_MAX_CURVES = 10, 0, 1, 4
 EMBED_FLAGS = {"energy": 1, "breathiness": 2, "voicing": 4, "tension": 8, "key_shift": 16, "speed": 32}
 
 
@@ -177,11 +180,50 @@ class DsdModelTensorInfo(C.Structure):
                 ("data", C.POINTER(C.c_float))]
 
 
+class DsdVarianceConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("hidden_size", C.c_int32), ("vocab_size", C.c_int32), ("num_lang", C.c_int32),
+                ("num_spk", C.c_int32), ("predict_dur", C.c_int32), ("predict_pitch", C.c_int32),
+                ("use_melody_encoder", C.c_int32), ("use_glide_embed", C.c_int32), ("use_lang_id", C.c_int32),
+                ("use_spk_id", C.c_int32), ("variances", C.c_uint32), ("melody_hidden_size", C.c_int32),
+                ("glide_rows", C.c_int32), ("glide_embed_scale", C.c_float), ("smooth_width", C.c_int32),
+                ("pitch_repeat_bins", C.c_int32), ("pitd_norm_min", C.c_float), ("pitd_norm_max", C.c_float),
+                ("pitd_clip_min", C.c_float), ("pitd_clip_max", C.c_float), ("var_repeat_bins", C.c_int32),
+                ("var_norm_min", C.c_float * 4), ("var_norm_max", C.c_float * 4), ("var_clamp_min", C.c_float * 4),
+                ("var_clamp_max", C.c_float * 4), ("var_no_clamp", C.c_int32 * 4), ("diffusion_type", C.c_int32),
+                ("timesteps", C.c_int32), ("k_step", C.c_int32), ("time_scale_factor", C.c_float)]
+
+
+class DsdVarianceEncodeArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("W", C.c_int32), ("tokens", C.c_void_p),
+                ("word_div", C.c_void_p), ("word_dur", C.c_void_p), ("ph_dur", C.c_void_p), ("languages", C.c_void_p),
+                ("encoder_out", C.c_void_p), ("x_masks", C.c_void_p), ("ph2word", C.c_void_p)]
+
+
+class DsdVarianceDurArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("encoder_out", C.c_void_p),
+                ("x_masks", C.c_void_p), ("ph_midi", C.c_void_p), ("spk_embed", C.c_void_p), ("spk_rows", C.c_int32),
+                ("ph_dur_pred", C.c_void_p)]
+
+
+class DsdVariancePitchCondArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("N", C.c_int32), ("T", C.c_int32),
+                ("encoder_out", C.c_void_p), ("ph_dur", C.c_void_p), ("note_midi", C.c_void_p), ("note_rest", C.c_void_p),
+                ("note_dur", C.c_void_p), ("note_glide", C.c_void_p), ("pitch", C.c_void_p), ("expr", C.c_void_p),
+                ("retake", C.c_void_p), ("spk_embed", C.c_void_p), ("spk_rows", C.c_int32),
+                ("lengths", C.POINTER(C.c_int32)), ("pitch_cond", C.c_void_p), ("base_pitch", C.c_void_p)]
+
+
+class DsdVarianceCondArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("encoder_out", C.c_void_p),
+                ("ph_dur", C.c_void_p), ("pitch", C.c_void_p), ("curves", C.c_void_p * 4), ("retake", C.c_void_p),
+                ("spk_embed", C.c_void_p), ("spk_rows", C.c_int32), ("variance_cond", C.c_void_p)]
+
+
 # the config struct of each handle kind (the DSD_* enum), and the create call dsd_model_create makes for it
 KIND_CONFIGS = {0: DsdConfig, 1: DsdConfig, 2: DsdConfig, 3: DsdEncoderConfig, 4: DsdVocoderConfig, 5: DsdTokenEncoderConfig,
-                6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig}
+                6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig, 10: DsdVarianceConfig}      # 9 is not assigned
 KIND_NAMES = {0: "wavenet", 1: "lynxnet", 2: "aux_convnext", 3: "fs2_acoustic", 4: "nsf_hifigan", 5: "fs2_tokens", 6: "mel",
-              7: "rmvpe", 8: "hnsep_vr"}
+              7: "rmvpe", 8: "hnsep_vr", 10: "variance_tables"}
 
 
 class DsdTerm(C.Structure):
@@ -317,6 +359,17 @@ def _load():
     lib.dsd_model_meta.argtypes = [vp, C.c_char_p]
     lib.dsd_model_meta.restype = C.c_char_p
     lib.dsd_model_create.argtypes = [vp, i32, i32, C.POINTER(vp)]
+    lib.dsd_variance_open.argtypes = [vp, C.c_char_p, i32, C.POINTER(vp)]
+    lib.dsd_variance_close.argtypes = [vp]
+    lib.dsd_variance_close.restype = None
+    lib.dsd_variance_info.argtypes = [vp, C.POINTER(DsdVarianceConfig)]
+    lib.dsd_variance_backbone.argtypes = [vp, i32, C.POINTER(vp)]
+    lib.dsd_variance_encode.argtypes = [vp, C.POINTER(DsdVarianceEncodeArgs), vp]
+    lib.dsd_variance_dur.argtypes = [vp, C.POINTER(DsdVarianceDurArgs), vp]
+    lib.dsd_variance_pitch_cond.argtypes = [vp, C.POINTER(DsdVariancePitchCondArgs), vp]
+    lib.dsd_variance_cond.argtypes = [vp, C.POINTER(DsdVarianceCondArgs), vp]
+    lib.dsd_variance_pitch_post.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.dsd_variance_post.argtypes = [vp, vp, i32, i32, C.POINTER(vp), vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

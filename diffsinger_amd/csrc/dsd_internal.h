@@ -471,6 +471,56 @@ struct FrameCurveP {
 hipError_t launch_length_regulate(const long long* dur, int B, int L, int T, long long* mel2x, hipStream_t st);
 hipError_t launch_frame_curve(const FrameCurveP& p, int items, hipStream_t st);
 
+// stage_kernels.hip: the index and per-frame scalar work of the variance twin's stages (dsd_variance_*), between the
+// length regulator and the assemble kernel.  Plain launches on tiny grids; every output is a workspace block of the object.
+struct StageEncodeP {               // forward_linguistic_encoder_word / _phoneme
+    const long long* tokens;        // [B][L]
+    const long long* ph2word;       // [B][L], or nullptr: the phoneme form
+    const long long* word_dur;      // [B][W]
+    const long long* ph_dur;        // [B][L] (phoneme form)
+    const long long* languages;     // [B][L] or nullptr
+    const float* mask;              // [vocab] 0 / 1
+    int L, W, vocab;
+    long long* onset;               // [B][L]
+    long long* lang;                // [B][L]
+    float* dur_f;                   // [B][L]
+    unsigned char* x_masks;         // [B][L]
+};
+struct StageNoteP {                 // MelodyEncoder.forward's terms
+    const float* note_midi;         // [B][N]
+    const unsigned char* note_rest;
+    const long long* note_dur;
+    const long long* note_glide;    // or nullptr (zeros)
+    int N;
+    float scale;                    // sqrt(melody hidden size)
+    float *midi_s, *keep_s, *dur_f; // [B][N] each
+    long long* glide;               // [B][N]
+    unsigned char* pad;             // [B][N]: note_midi < 0
+};
+struct StageFrameP {                // per-frame scalars of the two condition stages, and the speaker gather's index
+    int T, V;                       // V > 0: the variance form
+    const float* expr;              // [B][T] or nullptr        (pitch form)
+    const unsigned char* retake;    // [B][T] or [B][T][V]
+    const float* curves[4];         // [B][T] each              (variance form)
+    float *e, *one_minus_e;         // [B][T]                   (pitch form)
+    float *keep[4], *kept[4];       // [B][T] each: !retake, curve * !retake
+    long long* spk_idx;             // [B][T]: t (spk_iota) or 0; nullptr: not wanted
+    int spk_iota;
+};
+struct StagePostP {
+    const float* sample;            // [B][F][T][M]
+    const float* base;              // [B][T] or nullptr
+    float* out[4];                  // [B][T] per curve
+    int F, T, M;
+    float lo[4], hi[4];
+    int clamp[4];
+};
+hipError_t launch_stage_encode(const StageEncodeP& p, int B, hipStream_t st);
+hipError_t launch_stage_iota(long long* iota, long long* spk_idx, int spk_iota, int B, int L, hipStream_t st);
+hipError_t launch_stage_notes(const StageNoteP& p, int B, hipStream_t st);
+hipError_t launch_stage_frames(const StageFrameP& p, int B, hipStream_t st);
+hipError_t launch_stage_post(const StagePostP& p, int B, hipStream_t st);
+
 // noise_kernels.hip: seeded draws (dsd_noise_fill).  A NoiseP launch covers up to kNoiseItems batch items starting at item
 // b0; their seeds travel in the kernel arguments, so the entry owns no device memory and never synchronises.
 constexpr int kNoiseItems = 64;

@@ -67,6 +67,9 @@ extern "C" int dsd_model_create(const dsd_model_file* f, int32_t section, int32_
     dsd_model_section_info info;
     int rc = dsd_model_section(f, section, &info);
     if (rc != DSD_OK) return fail(nullptr, rc, "%s: %s", who, std::string(dsd_last_error(nullptr)).c_str());
+    if (info.kind == DSD_VARIANCE_TABLES)
+        return fail(nullptr, DSD_EINVAL, "%s: section \"%s\" holds the variance model's tables, not a handle: open the model with dsd_variance_open",
+                    who, info.name);
     AnyConfig cfg;
     memset(&cfg, 0, sizeof(cfg));
     if (info.config_size < 0 || (size_t)info.config_size > sizeof(cfg))

@@ -101,6 +101,8 @@ const KindInfo kKinds[] = {
     {"a mel analysis section", "dsd_mel_config", (uint32_t)sizeof(dsd_mel_config)},
     {"an RMVPE pitch extractor", "dsd_rmvpe_config", (uint32_t)sizeof(dsd_rmvpe_config)},
     {"a harmonic-noise separator", "dsd_hnsep_config", (uint32_t)sizeof(dsd_hnsep_config)},
+    {nullptr, nullptr, 0},          // 9 is not assigned
+    {"the variance model's tables", "dsd_variance_config", (uint32_t)sizeof(dsd_variance_config)},
 };
 const uint32_t kNumKinds = (uint32_t)(sizeof(kKinds) / sizeof(kKinds[0]));
 
@@ -205,7 +207,9 @@ int check_section(dsd_model_file& f, uint32_t i) {
     if (int rc = check_name(f, name_off, rd32(s + SEC_NAME_LEN), what)) return rc;
     const char* sname = f.str(name_off);
     const uint32_t kind = rd32(s + SEC_KIND);
-    if (kind >= kNumKinds) return fail(nullptr, DSD_EINVAL, "%s: section \"%s\": unknown kind %u (the DSD_* kinds are 0 .. %u)", WHO, sname, kind, kNumKinds - 1);
+    if (kind >= kNumKinds || !kKinds[kind].what)
+        return fail(nullptr, DSD_EINVAL, "%s: section \"%s\": unknown kind %u (the DSD_* kinds are 0 .. %d and %d)", WHO, sname, kind,
+                    (int)DSD_HNSEP_VR, (int)DSD_VARIANCE_TABLES);
     const KindInfo& K = kKinds[kind];
     const uint32_t cfg_size = rd32(s + SEC_CONFIG_SIZE);
     if (cfg_size != K.cfg_size)

@@ -10,7 +10,9 @@ the raw handle of dsd_model_create.
 acoustic encoder, the token encoders of variance.py, the vocoder Generator, pitch.RMVPE, hnsep.HnSep, the mel STFT - and
 gives the section its native handle is made of: the config of `_config()`, the tensors of `_native_state()` plus
 `_extra_weights()` in fp32.  `attach(module, file, section, device)` is the way back: the wrapper then runs on a handle
-made from the file, and uploads nothing itself.
+made from the file, and uploads nothing itself.  `variance_sections(prefix, model)` gives the sections of a staged variance
+twin (`deploy.DiffSingerVarianceDeploy`) as dsd_variance_open looks for them: its embedding tables and constants in a
+section of their own kind, and the inner handles' sections.
 """
 from __future__ import annotations
 
@@ -29,8 +31,8 @@ HEADER_BYTES, DIRECTORY_END = 32, 64        # the CRC covers [HEADER_BYTES, file
 SECTION_BYTES, TENSOR_BYTES, META_BYTES = 40, 64, 32
 
 Section = namedtuple("Section", "name kind cfg tensors")
-"""name: str; kind: the DSD_* enum (0 .. 8); cfg: the kind's ctypes config struct (or its bytes); tensors: an ordered
-mapping name -> array (anything numpy or torch, written as fp32)."""
+"""name: str; kind: the DSD_* enum (0 .. 8) or DSD_VARIANCE_TABLES (10); cfg: the kind's ctypes config struct (or its
+bytes); tensors: an ordered mapping name -> array (anything numpy or torch, written as fp32)."""
 SectionInfo = namedtuple("SectionInfo", "name kind config_size n_tensors total_floats")
 
 
@@ -178,6 +180,83 @@ def section_of(name, module):
     """The section a wrapper's native handle is made of (its `device` field 0: a file does not say where it runs)."""
     cfg = _zero_device(_module_config(module))
     return Section(name, _kind_of(cfg), cfg, _module_tensors(module))
+
+
+def _backbone_of(predictor):
+    return predictor.denoise_fn if hasattr(predictor, "denoise_fn") else predictor.velocity_fn
+
+
+def variance_config(model):
+    """The dsd_variance_config of a `deploy.DiffSingerVarianceDeploy` (include/dsdenoise.h): every constant its stages read
+    from hparams or from the predictors, so that a C caller has none in its source."""
+    from .hparams import hparams
+    c = _lib.DsdVarianceConfig()
+    c.struct_size = C.sizeof(c)
+    fs2 = model.fs2
+    c.hidden_size, c.vocab_size = model.hidden_size, fs2.txt_embed.num_embeddings
+    c.predict_dur, c.predict_pitch = int(bool(model.predict_dur)), int(bool(model.predict_pitch))
+    c.use_lang_id = int(hasattr(fs2, "lang_embed"))
+    c.num_lang = fs2.lang_embed.num_embeddings - 1 if c.use_lang_id else 0
+    c.use_spk_id = int(bool(model.use_spk_id))
+    c.num_spk = model.spk_embed.num_embeddings if c.use_spk_id else 0
+    for name in model.variance_prediction_list:
+        c.variances |= _lib.EMBED_FLAGS[name]
+    if c.predict_pitch:
+        c.use_melody_encoder = int(bool(model.use_melody_encoder))
+        if c.use_melody_encoder:
+            me = model.melody_encoder
+            c.melody_hidden_size = me._hidden
+            c.use_glide_embed = int(bool(me.use_glide_embed))
+            if c.use_glide_embed:
+                c.glide_rows, c.glide_embed_scale = me.note_glide_embed.num_embeddings, float(me.glide_embed_scale)
+        k = round(hparams['midi_smooth_width'] * hparams['audio_sample_rate'] / hparams['hop_size'])
+        if not 1 <= k <= 255:
+            raise ValueError(f"midi smoothing kernel of {k} frames is outside [1, 255]")
+        p = model.pitch_predictor
+        c.smooth_width, c.pitch_repeat_bins = k, p.repeat_bins
+        c.pitd_norm_min, c.pitd_norm_max, c.pitd_clip_min, c.pitd_clip_max = p.vmin, p.vmax, p.cmin, p.cmax
+    if c.variances:
+        p = model.variance_predictor
+        c.var_repeat_bins = p.repeat_bins
+        lo, hi = p.spec_min.reshape(-1).tolist(), p.spec_max.reshape(-1).tolist()
+        for i, name in enumerate(model.variance_prediction_list):
+            slot = list(_lib.EMBED_FLAGS).index(name)
+            c.var_norm_min[slot], c.var_norm_max[slot] = lo[i], hi[i]
+            if p.clamps[i] is None:
+                c.var_no_clamp[slot] = 1
+            else:
+                c.var_clamp_min[slot], c.var_clamp_max[slot] = p.clamps[i]
+    c.diffusion_type = _lib.DSD_DIFFUSE_REFLOW if model.diffusion_type == 'reflow' else _lib.DSD_DIFFUSE_DDPM
+    c.timesteps = int(hparams.get('timesteps') or 0)
+    c.k_step = int(hparams.get('K_step') or c.timesteps)
+    c.time_scale_factor = float(hparams.get('time_scale_factor') or 0)
+    return c
+
+
+def variance_sections(prefix, model):
+    """The sections dsd_variance_open looks for under `prefix`, for a `deploy.DiffSingerVarianceDeploy`: `<prefix>.tables`
+    (kind DSD_VARIANCE_TABLES: the embedding tables under the wrapper's own state_dict names, the mask of its
+    `cross_lingual_token_idx` and the smoothing taps of its `build_smooth_op`), `<prefix>.fs2`, `<prefix>.melody`, `<prefix>.pitch` and `<prefix>.variances`."""
+    cfg = variance_config(model)
+    sd = model.state_dict()
+    inner = ("fs2.encoder.", "fs2.dur_predictor.", "melody_encoder.encoder.", "melody_encoder.out_proj.", "pitch_predictor.",
+             "variance_predictor.")
+    tensors = OrderedDict((k, _as_f32(v)) for k, v in sd.items() if not k.startswith(inner))
+    mask = np.zeros(cfg.vocab_size, dtype="<f4")
+    idx = np.asarray(model.cross_lingual_token_idx.cpu().numpy(), dtype=np.int64)
+    mask[idx[(idx >= 0) & (idx < cfg.vocab_size)]] = 1.0
+    tensors["cross_lingual_mask"] = mask
+    if cfg.predict_pitch:       # build_smooth_op's taps as this host's torch computes them: the reference's export bakes them in too
+        from .deploy import smooth_kernel
+        tensors["smooth_taps"] = _as_f32(smooth_kernel(cfg.smooth_width))
+    out = [Section(prefix + ".tables", _lib.DSD_VARIANCE_TABLES, cfg, tensors), section_of(prefix + ".fs2", model.fs2)]
+    if cfg.use_melody_encoder:
+        out.append(section_of(prefix + ".melody", model.melody_encoder))
+    if cfg.predict_pitch:
+        out.append(section_of(prefix + ".pitch", _backbone_of(model.pitch_predictor)))
+    if cfg.variances:
+        out.append(section_of(prefix + ".variances", _backbone_of(model.variance_predictor)))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the C reader

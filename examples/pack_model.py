@@ -3,12 +3,16 @@
 (include/dsdenoise.h: dsd_model_open, dsd_model_create; examples/c_abi_model.c reads one).
 
     python examples/pack_model.py checkpoints/my_exp nsf_hifigan/model.ckpt -o my_voice.dsdm [--ckpt 160000]
+                                  [--variance checkpoints/my_variance_exp [--variance-prefix var] [--variance-ckpt N]]
 
 checkpoints/my_exp holds what a training run leaves there: config.yaml, model_ckpt_steps_<N>.ckpt, dictionary-<lang>.txt
 (or dictionary.txt); config.json lies beside the vocoder checkpoint.  Sections written: "encoder" (the FastSpeech2
 acoustic encoder), "denoiser" (the WaveNet / LYNXNet backbone), "aux_decoder" (with shallow diffusion), "vocoder", "mel"
 (the analysis that matches the vocoder).  Metadata: what a caller needs besides weights - the diffusion schedule's sizes,
 spec_min / spec_max, hop size, sample rate, the phoneme list - as plain strings (numbers in decimal, lists space-separated).
+`--variance` adds a variance experiment (the same layout) under a prefix, as dsd_variance_open looks for it
+(examples/c_abi_variance.c drives one): "<prefix>.tables" - the embedding tables of the staged twin, its constants and the
+mask of the dictionary's cross-lingual phonemes - and "<prefix>.fs2", ".melody", ".pitch", ".variances", the inner handles.
 Needs no GPU: the wrappers are built on the CPU and only their parameters are read.
 """
 import argparse
@@ -24,12 +28,27 @@ def _numbers(values):
     return " ".join(repr(float(v)) for v in values)
 
 
+def variance_sections(exp, prefix, ckpt_steps):
+    """the sections of a variance experiment's staged twin; hparams are the variance experiment's afterwards"""
+    from diffsinger_amd.deploy import DiffSingerVarianceDeploy
+    load_config(exp / "config.yaml", overrides=dict(infer=True, work_dir=str(exp)))
+    dictionary = harness.load_phoneme_dictionary()
+    cross = sorted({dictionary.encode_one(p) for p in dictionary.cross_lingual_phonemes})
+    model = DiffSingerVarianceDeploy(len(dictionary), cross_lingual_token_idx=cross).eval()
+    ckpt = harness.load_ckpt(model, exp, ckpt_steps=ckpt_steps, prefix_in_ckpt="model", strict=True)
+    print(f"| variance model: {ckpt} ({len(cross)} cross-lingual tokens)")
+    return modelfile.variance_sections(prefix, model)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("exp", type=pathlib.Path, help="experiment (work) directory")
     ap.add_argument("vocoder", type=pathlib.Path, help="NSF-HiFiGAN generator checkpoint (config.json beside it)")
     ap.add_argument("-o", "--out", type=pathlib.Path, required=True)
     ap.add_argument("--ckpt", type=int, default=None, help="checkpoint step (default: the latest)")
+    ap.add_argument("--variance", type=pathlib.Path, default=None, help="variance experiment (work) directory")
+    ap.add_argument("--variance-prefix", default="var", help="section name prefix of the variance model (default: var)")
+    ap.add_argument("--variance-ckpt", type=int, default=None, help="variance checkpoint step (default: the latest)")
     args = ap.parse_args()
 
     load_config(args.exp / "config.yaml", overrides=dict(infer=True, work_dir=str(args.exp)))
@@ -64,6 +83,8 @@ def main():
         "use_shallow_diffusion": str(int(bool(model.use_shallow_diffusion))),
         "phonemes": dictionary.decode(range(1, len(dictionary))),         # id order, ids from 1 (0 = padding)
     }
+    if args.variance is not None:
+        sections += variance_sections(args.variance, args.variance_prefix, args.variance_ckpt)
     size = modelfile.write(args.out, sections, meta)
     with modelfile.open(args.out) as f:          # the C reader has the last word
         for s in f.sections:

@@ -63,6 +63,8 @@ enum { DSD_BACKBONE_WAVENET = 0, DSD_BACKBONE_LYNXNET = 1,
        /* modules/hnsep/vr/nets.py:72  CascadedNet (VR harmonic-noise separator, is_complex=True) and the variance curves
           built on it; created with dsd_hnsep_create */
        DSD_HNSEP_VR = 8 };
+/* A model file has one more section kind, DSD_VARIANCE_TABLES = 10 (the variance model's embedding tables: not a handle,
+   see dsd_variance_open).  9 is not assigned, and a model file reader refuses it as unknown. */
 /* modules/backbones/lynxnet.py:38-42  activation_classes */
 enum { DSD_ACT_PRELU = 0, DSD_ACT_SILU = 1, DSD_ACT_RELU = 2 };
 
@@ -1228,7 +1230,7 @@ typedef struct dsd_model_file dsd_model_file;
 
 typedef struct dsd_model_section_info {
     const char* name;
-    int32_t kind;            /* DSD_BACKBONE_WAVENET .. DSD_HNSEP_VR                                     */
+    int32_t kind;            /* DSD_BACKBONE_WAVENET .. DSD_HNSEP_VR, or DSD_VARIANCE_TABLES             */
     int32_t config_size;     /* sizeof the kind's config struct: what dsd_model_config copies            */
     int32_t n_tensors;
     int64_t total_floats;    /* the sum of the tensors' counts                                           */
@@ -1267,6 +1269,185 @@ const char* dsd_model_meta(const dsd_model_file* f, const char* key);
  * the section, the tensor where one was being loaded, and that call's own message.
  */
 int dsd_model_create(const dsd_model_file* f, int32_t section, int32_t device, dsd_handle** out);
+
+/* ------------------------------------------------------------------------------------------
+ * The variance model's staged twin on one model file: DiffSingerVarianceONNX (deployment/modules/toplevel.py:132-302) and
+ * FastSpeech2VarianceONNX (deployment/modules/fastspeech2.py:133-184) stage by stage, for a process without Python.  One
+ * object owns the embedding tables the stages read and the model's inner handles (the token encoders and the two
+ * denoisers); every stage but the sampler is one call here.  The sampler stage stays dsd_prepare_cond + dsd_program_build +
+ * dsd_sample on the handles dsd_variance_backbone lends out.
+ *
+ * A section of kind DSD_VARIANCE_TABLES holds a dsd_variance_config and, in fp32 under the wrapper's state_dict names,
+ *   fs2.txt_embed.weight [vocab_size, H]                        always
+ *   cross_lingual_mask [vocab_size]                             always; 1 where the token is in cross_lingual_token_idx, else
+ *                                                               0; all zeros switches the language embedding off
+ *   fs2.lang_embed.weight [num_lang + 1, H]                     use_lang_id
+ *   fs2.onset_embed.weight [2, H], fs2.word_dur_embed.{weight [H, 1], bias [H]}, fs2.midi_embed.weight [128, H]   predict_dur
+ *   fs2.ph_dur_embed.{weight [H, 1], bias [H]}                  not predict_dur
+ *   spk_embed.weight [num_spk, H]                               use_spk_id (no stage reads it: the caller mixes from it)
+ *   melody_encoder.note_midi_embed.{weight [Hm, 1], bias [Hm]}, melody_encoder.note_dur_embed.{weight, bias}       use_melody_encoder
+ *   melody_encoder.note_glide_embed.weight [glide_rows, Hm]     use_glide_embed
+ *   pitch_retake_embed.weight [2, H]                            predict_pitch
+ *   smooth_taps [smooth_width]                                  predict_pitch, optional: the K taps of build_smooth_op as the
+ *                                                               exporter's torch computed them (the reference bakes its own
+ *                                                               into the exported graph in the same way)
+ *                                                               for K >= 2 every tap finite and their sum within 1e-4 of 1
+ *   delta_pitch_embed.{weight [H, 1], bias [H]}                 predict_pitch with a melody encoder
+ *   base_pitch_embed.{weight [H, 1], bias [H]}                  predict_pitch without one
+ *   pitch_embed.{weight [H, 1], bias [H]}, variance_embeds.<name>.{weight [H, 1], bias [H]}                        variances != 0
+ * Kind 9 is not assigned: a reader refuses it as unknown.  The format version stays 1; a reader from before this kind
+ * refuses such a section by its kind.  dsd_model_create answers DSD_EINVAL for the kind (use dsd_variance_open).
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_VARIANCE_TABLES 10
+#define DSD_VAR_PITCH 0          /* dsd_variance_backbone: the pitch predictor's denoiser                  */
+#define DSD_VAR_VARIANCES 1      /* ... and the multi-variance predictor's                                  */
+#define DSD_VAR_MAX_CURVES 4     /* energy, breathiness, voicing, tension (param_adaptor.py:10)              */
+
+typedef struct dsd_variance_config {
+    int32_t struct_size;         /* sizeof(dsd_variance_config)                                              */
+    int32_t hidden_size;         /* hparams['hidden_size']                                                   */
+    int32_t vocab_size;
+    int32_t num_lang;            /* lang_embed has num_lang + 1 rows                                         */
+    int32_t num_spk;
+    int32_t predict_dur;         /* 0/1: the word form of the encoder and the duration predictor             */
+    int32_t predict_pitch;       /* 0/1                                                                      */
+    int32_t use_melody_encoder;  /* 0/1; needs predict_pitch                                                 */
+    int32_t use_glide_embed;     /* 0/1; needs use_melody_encoder                                            */
+    int32_t use_lang_id;         /* 0/1                                                                      */
+    int32_t use_spk_id;          /* 0/1                                                                      */
+    uint32_t variances;          /* DSD_EMBED_ENERGY .. DSD_EMBED_TENSION: the predicted variances; their order in every
+                                    argument below is the order of the bits (VARIANCE_CHECKLIST)             */
+    int32_t melody_hidden_size;  /* melody_encoder_args.hidden_size (0 without a melody encoder)            */
+    int32_t glide_rows;          /* len(glide_types) + 1 (0 without a glide table)                           */
+    float glide_embed_scale;
+    int32_t smooth_width;        /* K = round(midi_smooth_width * audio_sample_rate / hop_size), 1 .. 255    */
+    int32_t pitch_repeat_bins;   /* pitch_prediction_args.repeat_bins                                        */
+    float pitd_norm_min, pitd_norm_max, pitd_clip_min, pitd_clip_max;
+    int32_t var_repeat_bins;     /* total_repeat_bins / the number of predicted variances                    */
+    /* indexed by the variance's place in the checklist (0 energy .. 3 tension), read where its bit is set   */
+    float var_norm_min[DSD_VAR_MAX_CURVES], var_norm_max[DSD_VAR_MAX_CURVES];
+    float var_clamp_min[DSD_VAR_MAX_CURVES], var_clamp_max[DSD_VAR_MAX_CURVES];
+    int32_t var_no_clamp[DSD_VAR_MAX_CURVES];    /* 1: the curve is not clamped                              */
+    int32_t diffusion_type;      /* DSD_DIFFUSE_DDPM / DSD_DIFFUSE_REFLOW                                    */
+    int32_t timesteps, k_step;
+    float time_scale_factor;
+} dsd_variance_config;
+
+typedef struct dsd_variance dsd_variance;        /* opaque; not a dsd_handle */
+
+/*
+ * Replaces: DiffSingerVarianceONNX.__init__ + load_state_dict + build_smooth_op (toplevel.py:133-194).
+ * Finds `<prefix>.tables` (kind DSD_VARIANCE_TABLES), `<prefix>.fs2` and - with a melody encoder - `<prefix>.melody` (kind
+ * DSD_ENC_FS2_TOKENS), `<prefix>.pitch` (predict_pitch) and `<prefix>.variances` (variances != 0; kinds 0 or 1).  Host checks
+ * come first, so a file that is refused touches no device: the tables against their config (a missing tensor, one the
+ * flags exclude and a wrong shape are DSD_EINVAL naming the tensor), every flag 0/1, smooth_width in [1, 255], and each
+ * inner config against the tables' (a mismatch names both fields).  Then the inner handles are made by dsd_model_create,
+ * the tables are uploaded once, and the K smoothing taps are taken from `smooth_taps` where the section has it.  Where it has
+ * not, they are computed on the host: sin(pi * linspace(0, 1, K)) with the fp32 argument, each sine rounded from double,
+ * divided by their sum (added in double, rounded once) - within 2^-20 of torch's own, whose CPU sine is accurate to one ulp
+ * and whose sum order follows the host's vector width, so that no C code gives torch's bits for every K.  K = 1 is 0 / 0 = NaN,
+ * as in the reference.  On any failure everything built so far is released and *out = NULL.
+ */
+int dsd_variance_open(const dsd_model_file* f, const char* prefix, int32_t device, dsd_variance** out);
+void dsd_variance_close(dsd_variance* v);            /* NULL is fine */
+/* the tables' config as stored (hparams the stages and the caller's dsd_sampler_spec / out_scale / out_shift need) */
+int dsd_variance_info(const dsd_variance* v, dsd_variance_config* out);
+/* which: DSD_VAR_PITCH / DSD_VAR_VARIANCES.  *out is borrowed: it lives until dsd_variance_close, never dsd_destroy it.
+   DSD_EINVAL for a predictor the model does not have. */
+int dsd_variance_backbone(const dsd_variance* v, int32_t which, dsd_handle** out);
+
+/*
+ * The stage calls.  Every pointer but `lengths` is device memory; int64 where the twin takes LongTensors, bytes for its
+ * bool tensors (non-zero = true).  Each call checks all of its arguments on the host before the first launch, reads nothing
+ * back, and allocates only when a size grows past what the object's workspace holds: a second call at the same sizes
+ * allocates nothing and may be captured in a HIP graph.  DSD_EINVAL: a NULL object, args or required pointer; a wrong
+ * struct_size; B < 1; L, W or N outside [1, 2048]; T < 1; a stage the model does not have; a word-form input on a
+ * phoneme-form model or the reverse; `languages` missing on a model whose mask has a set entry; `spk_embed` on a model
+ * without use_spk_id; spk_rows that is neither 1 nor the stage's length; a lengths entry outside [0, T].  An index outside
+ * its table reads as zeros (dsd_cond_assemble); that is the caller's contract, not checked.  Each stage keeps ONE workspace
+ * per object, on the object's device (every call makes that device current in the calling thread): two calls of the same
+ * stage on one object must not run concurrently, neither from two threads nor on two streams; use one object per stream.
+ */
+/* Replaces: forward_linguistic_encoder_word / _phoneme (fastspeech2.py:145-176). */
+typedef struct dsd_variance_encode_args {
+    int32_t struct_size;
+    int32_t B, L, W;              /* W words: the word form (predict_dur); 0: the phoneme form                 */
+    const int64_t* tokens;        /* [B, L]                                                                    */
+    const int64_t* word_div;      /* [B, W] phonemes per word   (word form)                                    */
+    const int64_t* word_dur;      /* [B, W] frames per word     (word form)                                    */
+    const int64_t* ph_dur;        /* [B, L] frames per phoneme  (phoneme form)                                 */
+    const int64_t* languages;     /* [B, L] or NULL                                                            */
+    float* encoder_out;           /* [B, L, H]                                                                 */
+    uint8_t* x_masks;             /* [B, L]: tokens == 0                                                       */
+    int64_t* ph2word;             /* [B, L] or NULL: the word form's length-regulated word index, if wanted
+                                     (DSD_EINVAL on a phoneme-form model, which has none)                    */
+} dsd_variance_encode_args;
+int dsd_variance_encode(dsd_variance* v, const dsd_variance_encode_args* args, void* stream);
+
+/* Replaces: forward_dur_predictor (fastspeech2.py:178-184). */
+typedef struct dsd_variance_dur_args {
+    int32_t struct_size;
+    int32_t B, L;
+    const float* encoder_out;     /* [B, L, H]                                                                 */
+    const uint8_t* x_masks;       /* [B, L]                                                                    */
+    const int64_t* ph_midi;       /* [B, L]                                                                    */
+    const float* spk_embed;       /* [B, spk_rows, H] or NULL                                                  */
+    int32_t spk_rows;             /* 1 or L                                                                    */
+    float* ph_dur_pred;           /* [B, L]                                                                    */
+} dsd_variance_dur_args;
+int dsd_variance_dur(dsd_variance* v, const dsd_variance_dur_args* args, void* stream);
+
+/* Replaces: forward_pitch_preprocess (toplevel.py:224-261) with MelodyEncoder.forward (variance_encoder.py:130-148). */
+typedef struct dsd_variance_pitch_cond_args {
+    int32_t struct_size;
+    int32_t B, L, N, T;
+    const float* encoder_out;     /* [B, L, H]                                                                 */
+    const int64_t* ph_dur;        /* [B, L]                                                                    */
+    const float* note_midi;       /* [B, N]; < 0: a padding note                                               */
+    const uint8_t* note_rest;     /* [B, N]; read with a melody encoder                                        */
+    const int64_t* note_dur;      /* [B, N]                                                                    */
+    const int64_t* note_glide;    /* [B, N] or NULL (= zeros)                                                  */
+    const float* pitch;           /* [B, T]                                                                    */
+    const float* expr;            /* [B, T] or NULL (= 1)                                                      */
+    const uint8_t* retake;        /* [B, T]                                                                    */
+    const float* spk_embed;       /* [B, spk_rows, H] or NULL                                                  */
+    int32_t spk_rows;             /* 1 or T                                                                    */
+    const int32_t* lengths;       /* HOST, [B] frame counts in [0, T], or NULL: see dsd_frame_curve            */
+    float* pitch_cond;            /* [B, T, H]                                                                 */
+    float* base_pitch;            /* [B, T]                                                                    */
+} dsd_variance_pitch_cond_args;
+int dsd_variance_pitch_cond(dsd_variance* v, const dsd_variance_pitch_cond_args* args, void* stream);
+
+/* Replaces: forward_variance_preprocess (toplevel.py:273-290). */
+typedef struct dsd_variance_cond_args {
+    int32_t struct_size;
+    int32_t B, L, T;
+    const float* encoder_out;     /* [B, L, H]                                                                 */
+    const int64_t* ph_dur;        /* [B, L]                                                                    */
+    const float* pitch;           /* [B, T]                                                                    */
+    const float* curves[DSD_VAR_MAX_CURVES];     /* [B, T] each: the first V entries, V predicted variances in order */
+    const uint8_t* retake;        /* [B, T, V]                                                                 */
+    const float* spk_embed;       /* [B, spk_rows, H] or NULL                                                  */
+    int32_t spk_rows;             /* 1 or T                                                                    */
+    float* variance_cond;         /* [B, T, H]                                                                 */
+} dsd_variance_cond_args;
+int dsd_variance_cond(dsd_variance* v, const dsd_variance_cond_args* args, void* stream);
+
+/*
+ * Replaces: forward_pitch_postprocess (toplevel.py:269-271) with PitchDiffusionONNX.denorm_spec's mean over the bins
+ * (deployment/modules/diffusion.py:185-190) and clamp_spec.  sample [B, T, M] as dsd_sample(..., DSD_SAMPLE_TRANSPOSE) writes
+ * it with the caller's out_scale / out_shift (M = pitch_repeat_bins): pitch_pred[b, t] = clamp(mean_m sample[b, t, m],
+ * pitd_clip_min, pitd_clip_max) + base_pitch[b, t].  The bins are added lane-wise (lane l takes m = l, l + 64, ...) and then
+ * across the wave by halving strides 32, 16, .. 1; the sum is divided by M.
+ */
+int dsd_variance_pitch_post(dsd_variance* v, const float* sample, const float* base_pitch, int32_t B, int32_t T,
+                            float* pitch_pred, void* stream);
+/*
+ * Replaces: forward_variance_postprocess (toplevel.py:296-302) with MultiVarianceDiffusionONNX.denorm_spec's mean
+ * (diffusion.py:217-222).  sample [B, V, T, M] ([B, T, M] for V = 1), M = var_repeat_bins: curves_out[i][b, t] =
+ * clamp(mean_m sample[b, i, t, m]) for the first V entries, each [B, T]; a variance with var_no_clamp is not clamped.
+ */
+int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T, float* const* curves_out, void* stream);
 
 #ifdef __cplusplus
 }

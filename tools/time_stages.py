@@ -4,7 +4,13 @@ B = 1, T = 1000 (no melody encoder, so the stage is the duration-to-frame work a
 written with the torch ops the `.ds` harness uses for it today on the same GPU - the searchsorted length regulator (which reads
 the frame total back), gather, replicate pad + conv1d, the retake blend, embedding lookups and broadcast adds.  Both are expected to be bound by
 launches, not by arithmetic.  Device-event times, warm-up, median of several repeats; GPU box only.  Prints one JSON line;
-`--out FILE` also writes it there."""
+`--out FILE` also writes it there.
+
+`--variance`: instead, every non-sampler stage of the variance twin at the sizes of a configs/variance.yaml segment (hidden
+256, 120 tokens, 60 notes, `--frames` frames, B = 1 and 8), the Python twin's stage (`deploy.DiffSingerVarianceDeploy`) and
+the C stage (`dsd_variance_*` through `cvariance.Variance`, on a model file packed from the same weights) in this one process
+on the same inputs.  Per stage and batch size: device-event time of one call, and the host time one
+call takes to issue (wall clock over back-to-back calls, the device drained before and after).  One JSON line."""
 import argparse
 import json
 import os
@@ -28,6 +34,7 @@ ap.add_argument("--repeats", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--frames", type=int, default=1000)
 ap.add_argument("--out")
+ap.add_argument("--variance", action="store_true")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "time_stages.py needs the MI355X"
 
@@ -45,6 +52,91 @@ def timed(fn):
         times.append(a.elapsed_time(b))
     return statistics.median(times)
 
+
+def host_ms(fn, calls=20):
+    """wall-clock time to issue one call: `calls` back-to-back, the device idle before the first and drained after the last"""
+    import time
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        fn()
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    return (t1 - t0) / calls * 1e3
+
+
+def variance_stages():
+    import tempfile
+    from diffsinger_amd import cvariance, modelfile
+    hp = dict(dc.BASE_HP)
+    hp.update(dc.VARIANCE_HP, hidden_size=256, enc_layers=4, predict_dur=True, predict_pitch=True, use_melody_encoder=True,
+              use_glide_embed=True, predict_energy=True, predict_breathiness=True, use_spk_id=True, num_spk=4, use_lang_id=True,
+              num_lang=2, diffusion_type="reflow", melody_encoder_args=dict(hidden_size=128, enc_layers=4),
+              dur_prediction_args=dict(dc.VARIANCE_HP["dur_prediction_args"], hidden_size=512, num_layers=5),
+              pitch_prediction_args=dict(dc.VARIANCE_HP["pitch_prediction_args"], repeat_bins=64),
+              variances_prediction_args=dict(dc.VARIANCE_HP["variances_prediction_args"], total_repeat_bins=48))
+    hparams.clear()
+    hparams.update(hp, infer=True)
+    vocab, n_ph, n_word, n_note, t_len, h = 60, 120, 40, 60, args.frames, 256
+    torch.manual_seed(2450)
+    model = deploy.DiffSingerVarianceDeploy(vocab, cross_lingual_token_idx=list(range(2, vocab, 3))).cuda().eval()
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "variance.dsdm")
+        modelfile.write(path, modelfile.variance_sections("var", model))
+        with modelfile.open(path) as f:
+            v = cvariance.Variance(f, "var", "cuda")
+    rng = np.random.default_rng(2451)
+    names = v.names
+    res = {"T": t_len, "tokens": n_ph, "words": n_word, "notes": n_note, "hidden": h, "K": int(v.cfg.smooth_width), "stages": {}}
+    for bsz in (1, 8):
+        def ints(lo, hi, shape):
+            return torch.from_numpy(rng.integers(lo, hi, shape).astype(np.int64)).cuda()
+
+        def split(total, parts):
+            return torch.from_numpy(np.stack([rng.multinomial(total, np.ones(parts) / parts) for _ in range(bsz)])).cuda()
+        tokens, languages, ph_midi = ints(1, vocab, (bsz, n_ph)), ints(1, 3, (bsz, n_ph)), ints(40, 80, (bsz, n_ph))
+        word_div, ph_dur, note_dur = split(n_ph, n_word), split(t_len, n_ph), split(t_len, n_note)
+        word_dur = ints(10, 40, (bsz, n_word))
+        note_midi = torch.from_numpy(rng.uniform(48, 72, (bsz, n_note)).astype(np.float32)).cuda()
+        note_rest, note_glide = torch.rand(bsz, n_note, device="cuda") < 0.2, ints(0, 3, (bsz, n_note))
+        pitch = torch.from_numpy((60 + rng.normal(0, 3, (bsz, t_len))).astype(np.float32)).cuda()
+        expr, retake = torch.rand(bsz, t_len, device="cuda"), torch.rand(bsz, t_len, device="cuda") < 0.5
+        spk = torch.randn(bsz, 1, h, device="cuda")
+        curves = {n: torch.from_numpy(rng.uniform(-60, -10, (bsz, t_len)).astype(np.float32)).cuda() for n in names}
+        var_retake = torch.rand(bsz, t_len, len(names), device="cuda") < 0.5
+        raw_pitch = torch.randn(bsz, t_len, v.cfg.pitch_repeat_bins, device="cuda")
+        raw_var = torch.randn(bsz, len(names), t_len, v.cfg.var_repeat_bins, device="cuda") * 30 - 40
+        enc, masks = v.encode(tokens, word_div=word_div, word_dur=word_dur, languages=languages)
+        _, base = v.pitch_cond(enc, ph_dur, note_midi, note_rest, note_dur, note_glide=note_glide, pitch=pitch, expr=expr, retake=retake,
+                               spk_embed=spk)
+        note = dict(note_midi=note_midi, note_rest=note_rest, note_dur=note_dur, note_glide=note_glide, pitch=pitch, expr=expr,
+                    retake=retake, spk_embed=spk)
+        pairs = {
+            "encode": (lambda: model.forward_linguistic_encoder_word(tokens, word_div, word_dur, languages=languages),
+                       lambda: v.encode(tokens, word_div=word_div, word_dur=word_dur, languages=languages)),
+            "dur": (lambda: model.forward_dur_predictor(enc, masks, ph_midi, spk_embed=spk), lambda: v.dur(enc, masks, ph_midi, spk_embed=spk)),
+            "pitch_cond": (lambda: model.forward_pitch_preprocess(enc, ph_dur, **note), lambda: v.pitch_cond(enc, ph_dur, **note)),
+            "cond": (lambda: model.forward_variance_preprocess(enc, ph_dur, pitch, variances=curves, retake=var_retake, spk_embed=spk),
+                     lambda: v.cond(enc, ph_dur, pitch, curves, var_retake, spk_embed=spk)),
+            "pitch_post": (lambda: model.forward_pitch_postprocess(raw_pitch.mean(-1), base), lambda: v.pitch_post(raw_pitch, base)),
+            "post": (lambda: model.forward_variance_postprocess(raw_var.mean(-1)), lambda: v.post(raw_var)),
+        }
+        for stage, (twin, c_call) in pairs.items():
+            res["stages"][f"{stage}_b{bsz}"] = {"python_device_ms": timed(twin), "c_device_ms": timed(c_call),
+                                                "python_host_ms": host_ms(twin), "c_host_ms": host_ms(c_call)}
+    v.close()
+    return res
+
+
+if args.variance:
+    with torch.no_grad():
+        line = json.dumps(variance_stages())
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0)
 
 hp = dict(dc.BASE_HP)
 hp.update(dc.VARIANCE_HP, hidden_size=256, predict_pitch=True, diffusion_type="reflow")
