@@ -54,6 +54,8 @@ EXPORTS = [
     "dsd_model_tensor", "dsd_model_meta_at", "dsd_model_meta", "dsd_model_create",
     "dsd_variance_open", "dsd_variance_close", "dsd_variance_info", "dsd_variance_backbone", "dsd_variance_encode",
     "dsd_variance_dur", "dsd_variance_pitch_cond", "dsd_variance_cond", "dsd_variance_pitch_post", "dsd_variance_post",
+    "dsd_acoustic_open", "dsd_acoustic_close", "dsd_acoustic_info", "dsd_acoustic_handle", "dsd_acoustic_condition",
+    "dsd_acoustic_plan", "dsd_acoustic_start", "dsd_acoustic_sample",
 ]
 DSD_API_VERSION = 10
 DSD_EINVAL, DSD_ESTATE, DSD_EHIP, DSD_ENOMEM, DSD_ENOTFOUND, DSD_EIO = -1, -2, -3, -4, -5, -6
@@ -62,6 +64,8 @@ DSD_MODEL_MAX_NAME, DSD_MODEL_ALIGN = 255, 64
 POS_ROPE, POS_REL, POS_NONE, POS_SIN = 0, 1, 2, 3       # DSD_POS_*
 FFN_ACTS = {"gelu": 0, "relu": 1, "swish": 2, "swiglu": 3}    # DSD_FFN_* (TransformerFFNLayer, common_layers.py:126-136)
 DSD_VARIANCE_TABLES, DSD_VAR_PITCH, DSD_VAR_VARIANCES, DSD_VAR_MAX_CURVES = 10, 0, 1, 4
+DSD_ACOUSTIC_TABLES, DSD_AC_FS2, DSD_AC_AUX, DSD_AC_DENOISER, DSD_AC_PITCH_BINS = 11, 0, 1, 2, 300
+DSD_AC_START_NOISE, DSD_AC_START_MIX, DSD_AC_START_SOURCE = 0, 1, 2
 EMBED_FLAGS = {"energy": 1, "breathiness": 2, "voicing": 4, "tension": 8, "key_shift": 16, "speed": 32}
 
 
@@ -219,11 +223,33 @@ class DsdVarianceCondArgs(C.Structure):
                 ("spk_embed", C.c_void_p), ("spk_rows", C.c_int32), ("variance_cond", C.c_void_p)]
 
 
+class DsdAcousticConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("hidden_size", C.c_int32), ("vocab_size", C.c_int32), ("out_dims", C.c_int32),
+                ("num_lang", C.c_int32), ("num_spk", C.c_int32), ("use_lang_id", C.c_int32), ("use_spk_id", C.c_int32),
+                ("embed_flags", C.c_uint32), ("f0_discrete", C.c_int32), ("use_shallow_diffusion", C.c_int32),
+                ("shift_min", C.c_float), ("shift_max", C.c_float), ("speed_min", C.c_float), ("speed_max", C.c_float),
+                ("mel_base_e", C.c_int32), ("diffusion_type", C.c_int32), ("timesteps", C.c_int32), ("k_step", C.c_int32),
+                ("schedule_type", C.c_int32), ("max_beta", C.c_double), ("t_start", C.c_float), ("time_scale_factor", C.c_float)]
+
+
+class DsdAcousticConditionArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("tokens", C.c_void_p),
+                ("durations", C.c_void_p), ("f0", C.c_void_p), ("curves", C.c_void_p * 4), ("gender", C.c_void_p),
+                ("velocity", C.c_void_p), ("spk_embed", C.c_void_p), ("spk_rows", C.c_int32), ("languages", C.c_void_p),
+                ("condition", C.c_void_p), ("aux_mel", C.c_void_p), ("f0_coarse", C.c_void_p)]
+
+
+class DsdAcousticPlan(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("start", C.c_int32), ("t_max", C.c_int32), ("speedup", C.c_int32), ("t_start", C.c_float),
+                ("n_step_noise", C.c_int32), ("src_scale", C.c_float), ("noise_scale", C.c_float), ("steps", C.c_int32)]
+
+
 # the config struct of each handle kind (the DSD_* enum), and the create call dsd_model_create makes for it
 KIND_CONFIGS = {0: DsdConfig, 1: DsdConfig, 2: DsdConfig, 3: DsdEncoderConfig, 4: DsdVocoderConfig, 5: DsdTokenEncoderConfig,
-                6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig, 10: DsdVarianceConfig}      # 9 is not assigned
+                6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig, 10: DsdVarianceConfig,       # 9 is not assigned
+                11: DsdAcousticConfig}
 KIND_NAMES = {0: "wavenet", 1: "lynxnet", 2: "aux_convnext", 3: "fs2_acoustic", 4: "nsf_hifigan", 5: "fs2_tokens", 6: "mel",
-              7: "rmvpe", 8: "hnsep_vr", 10: "variance_tables"}
+              7: "rmvpe", 8: "hnsep_vr", 10: "variance_tables", 11: "acoustic_tables"}
 
 
 class DsdTerm(C.Structure):
@@ -370,6 +396,15 @@ def _load():
     lib.dsd_variance_cond.argtypes = [vp, C.POINTER(DsdVarianceCondArgs), vp]
     lib.dsd_variance_pitch_post.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.dsd_variance_post.argtypes = [vp, vp, i32, i32, C.POINTER(vp), vp]
+    lib.dsd_acoustic_open.argtypes = [vp, C.c_char_p, i32, C.POINTER(vp)]
+    lib.dsd_acoustic_close.argtypes = [vp]
+    lib.dsd_acoustic_close.restype = None
+    lib.dsd_acoustic_info.argtypes = [vp, C.POINTER(DsdAcousticConfig)]
+    lib.dsd_acoustic_handle.argtypes = [vp, i32, C.POINTER(vp)]
+    lib.dsd_acoustic_condition.argtypes = [vp, C.POINTER(DsdAcousticConditionArgs), vp]
+    lib.dsd_acoustic_plan.argtypes = [C.POINTER(DsdAcousticConfig), C.c_float, i32, C.POINTER(DsdAcousticPlan)]
+    lib.dsd_acoustic_start.argtypes = [vp, C.POINTER(DsdAcousticPlan), vp, vp, i32, i32, vp, vp]
+    lib.dsd_acoustic_sample.argtypes = [vp, C.POINTER(DsdAcousticPlan), vp, vp, vp, i32, i32, C.c_uint32, vp, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

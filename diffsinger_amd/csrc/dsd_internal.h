@@ -521,6 +521,41 @@ hipError_t launch_stage_notes(const StageNoteP& p, int B, hipStream_t st);
 hipError_t launch_stage_frames(const StageFrameP& p, int B, hipStream_t st);
 hipError_t launch_stage_post(const StagePostP& p, int B, hipStream_t st);
 
+// acoustic_kernels.hip: the per-token and per-frame work of the acoustic twin's condition stage (dsd_acoustic_condition),
+// the samplers' start state and the mel base.  Plain launches; every output but x and mel is a workspace block of the object.
+struct AcTokensP {
+    const long long* tokens;        // [B][L]
+    const long long* durations;     // [B][L]
+    const long long* languages;     // [B][L], or nullptr: lang = 0
+    const float* mask;              // [vocab] 0 / 1
+    int L, vocab;
+    long long* dur_m;               // [B][L]: durations * (tokens > 0)
+    long long* lang;                // [B][L], or nullptr: the model has no lang_embed
+};
+struct AcFramesP {
+    const long long* mel2ph;        // [B][T]
+    const float* f0;                // [B][T]
+    const float* gender;            // [B][T]; read when key_shift is wanted and there is no frozen value
+    const float* velocity;          // [B][T] or nullptr (speed = 1)
+    const float* frozen_key_shift;  // device, 1 value, or nullptr
+    int T;
+    float shift_max, shift_min_abs, speed_min, speed_max;
+    float inv_700, coarse_a, coarse_b;      // f0_to_coarse's constants, rounded to fp32 as torch rounds Python scalars
+    float* f0_m;                    // [B][T]: f0 * (mel2ph > 0)
+    float* f0_enc;                  // [B][T] or nullptr: what the encoder takes - f0_m, or zeros with `coarse`
+    float* key_shift;               // [B][T] or nullptr
+    float* speed;                   // [B][T] or nullptr
+    long long* iota;                // [B][T] or nullptr: t
+    long long* coarse;              // [B][T] or nullptr: f0_to_coarse(f0_m)
+    long long* coarse_out;          // the caller's copy of it, or nullptr
+};
+hipError_t launch_ac_tokens(const AcTokensP& p, int B, hipStream_t st);
+hipError_t launch_ac_frames(const AcFramesP& p, int B, hipStream_t st);
+// source [B][T][M] -> x [B][1][M][T] = (source - mid[m]) / k[m]; with `noise` ([B][1][M][T]): src_scale * that + noise_scale * noise
+hipError_t launch_ac_source(const float* source, const float* noise, const float* k, const float* mid, float src_scale, float noise_scale,
+                            int B, int M, int T, float* x, hipStream_t st);
+hipError_t launch_ac_mel_base(float* mel, long n, float scale, hipStream_t st);
+
 // noise_kernels.hip: seeded draws (dsd_noise_fill).  A NoiseP launch covers up to kNoiseItems batch items starting at item
 // b0; their seeds travel in the kernel arguments, so the entry owns no device memory and never synchronises.
 constexpr int kNoiseItems = 64;

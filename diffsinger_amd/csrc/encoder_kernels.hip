@@ -11,7 +11,16 @@ namespace dsd {
 
 // ---------------------------------------------------------------------------------------------
 // mel2ph_to_dur (tts_modules.py:344-350): dur[b][k] = #{t : mel2ph[b][t] == k + 1}.  Integer atomics: exact.
+// The counters are cleared by a kernel, not by hipMemsetAsync: in a captured graph whose memset node follows a kernel node
+// (mel2ph from dsd_length_regulate in the same capture, as forward_fs2_aux and dsd_acoustic_condition run them) the first
+// replay gave the eager run's condition and every later one another, on the MI355X; with the kernel every replay gives it
+// (tests/test_gpu_cacoustic.py, the captured chain).  dsd_encode alone, its memset the graph's first node, replayed either way.
 // ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void enc_dur_clear_kernel(int* __restrict__ dur, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dur[i] = 0;
+}
+
 __global__ void enc_dur_kernel(const long long* __restrict__ mel2ph, int T, int L, int* __restrict__ dur) {
     const int b = blockIdx.y;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -400,7 +409,9 @@ hipError_t launch_assemble(const AssembleArgs& a, float* out, hipStream_t st) {
 }
 
 hipError_t launch_enc_dur(const long long* mel2ph, int B, int T, int L, int* dur, hipStream_t st) {
-    hipError_t e = hipMemsetAsync(dur, 0, sizeof(int) * (size_t)B * L, st);
+    const int n = B * L;        // B * 2048 at the most (dsd_encode's limits)
+    hipLaunchKernelGGL(enc_dur_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dur, n);
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(enc_dur_kernel, dim3((T + 255) / 256, B), dim3(256), 0, st, mel2ph, T, L, dur);
     return hipGetLastError();

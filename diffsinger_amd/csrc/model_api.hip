@@ -70,6 +70,9 @@ extern "C" int dsd_model_create(const dsd_model_file* f, int32_t section, int32_
     if (info.kind == DSD_VARIANCE_TABLES)
         return fail(nullptr, DSD_EINVAL, "%s: section \"%s\" holds the variance model's tables, not a handle: open the model with dsd_variance_open",
                     who, info.name);
+    if (info.kind == DSD_ACOUSTIC_TABLES)
+        return fail(nullptr, DSD_EINVAL, "%s: section \"%s\" holds the acoustic model's tables, not a handle: use dsd_acoustic_open",
+                    who, info.name);
     AnyConfig cfg;
     memset(&cfg, 0, sizeof(cfg));
     if (info.config_size < 0 || (size_t)info.config_size > sizeof(cfg))

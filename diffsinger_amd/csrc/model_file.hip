@@ -103,6 +103,7 @@ const KindInfo kKinds[] = {
     {"a harmonic-noise separator", "dsd_hnsep_config", (uint32_t)sizeof(dsd_hnsep_config)},
     {nullptr, nullptr, 0},          // 9 is not assigned
     {"the variance model's tables", "dsd_variance_config", (uint32_t)sizeof(dsd_variance_config)},
+    {"the acoustic model's tables", "dsd_acoustic_config", (uint32_t)sizeof(dsd_acoustic_config)},
 };
 const uint32_t kNumKinds = (uint32_t)(sizeof(kKinds) / sizeof(kKinds[0]));
 
@@ -208,8 +209,8 @@ int check_section(dsd_model_file& f, uint32_t i) {
     const char* sname = f.str(name_off);
     const uint32_t kind = rd32(s + SEC_KIND);
     if (kind >= kNumKinds || !kKinds[kind].what)
-        return fail(nullptr, DSD_EINVAL, "%s: section \"%s\": unknown kind %u (the DSD_* kinds are 0 .. %d and %d)", WHO, sname, kind,
-                    (int)DSD_HNSEP_VR, (int)DSD_VARIANCE_TABLES);
+        return fail(nullptr, DSD_EINVAL, "%s: section \"%s\": unknown kind %u (the DSD_* kinds are 0 .. %d, %d and %d)", WHO, sname, kind,
+                    (int)DSD_HNSEP_VR, (int)DSD_VARIANCE_TABLES, (int)DSD_ACOUSTIC_TABLES);
     const KindInfo& K = kKinds[kind];
     const uint32_t cfg_size = rd32(s + SEC_CONFIG_SIZE);
     if (cfg_size != K.cfg_size)

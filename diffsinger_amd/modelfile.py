@@ -12,7 +12,8 @@ gives the section its native handle is made of: the config of `_config()`, the t
 `_extra_weights()` in fp32.  `attach(module, file, section, device)` is the way back: the wrapper then runs on a handle
 made from the file, and uploads nothing itself.  `variance_sections(prefix, model)` gives the sections of a staged variance
 twin (`deploy.DiffSingerVarianceDeploy`) as dsd_variance_open looks for them: its embedding tables and constants in a
-section of their own kind, and the inner handles' sections.
+section of their own kind, and the inner handles' sections; `acoustic_sections(prefix, model)` does
+the same for a staged acoustic twin (`deploy.DiffSingerAcousticDeploy`) and dsd_acoustic_open (section 4p).
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ HEADER_BYTES, DIRECTORY_END = 32, 64        # the CRC covers [HEADER_BYTES, file
 SECTION_BYTES, TENSOR_BYTES, META_BYTES = 40, 64, 32
 
 Section = namedtuple("Section", "name kind cfg tensors")
-"""name: str; kind: the DSD_* enum (0 .. 8) or DSD_VARIANCE_TABLES (10); cfg: the kind's ctypes config struct (or its
+"""name: str; kind: the DSD_* enum (0 .. 8), DSD_VARIANCE_TABLES (10) or DSD_ACOUSTIC_TABLES (11); cfg: the kind's ctypes config struct (or its
 bytes); tensors: an ordered mapping name -> array (anything numpy or torch, written as fp32)."""
 SectionInfo = namedtuple("SectionInfo", "name kind config_size n_tensors total_floats")
 
@@ -256,6 +257,74 @@ def variance_sections(prefix, model):
         out.append(section_of(prefix + ".pitch", _backbone_of(model.pitch_predictor)))
     if cfg.variances:
         out.append(section_of(prefix + ".variances", _backbone_of(model.variance_predictor)))
+    return out
+
+
+def acoustic_config(model):
+    """The dsd_acoustic_config of a `deploy.DiffSingerAcousticDeploy` (include/dsdenoise.h): every constant its stages and
+    its sampler plan read from hparams or from the wrapper, so that a C caller has none in its source."""
+    import inspect
+    from . import cprogram, schedule
+    c = _lib.DsdAcousticConfig()
+    c.struct_size = C.sizeof(c)
+    fs2, diff = model.fs2, model.diffusion
+    c.hidden_size, c.vocab_size, c.out_dims = fs2._hidden, fs2.vocab_size, diff.out_dims
+    c.use_lang_id, c.num_lang = int(bool(fs2.use_lang_id)), fs2.num_lang
+    c.use_spk_id, c.num_spk = int(bool(fs2.use_spk_id)), fs2.num_spk
+    c.embed_flags = fs2._config(0).embed_flags
+    c.f0_discrete = int(model.f0_embed_type == 'discrete')
+    c.use_shallow_diffusion = int(bool(model.use_shallow_diffusion))
+    if fs2.use_key_shift_embed:
+        c.shift_min, c.shift_max = float(model.shift_min), float(model.shift_max)
+    if fs2.use_speed_embed:
+        c.speed_min, c.speed_max = float(model.speed_min), float(model.speed_max)
+    c.mel_base_e = int(model.mel_base == 'e')
+    if model.diffusion_type == 'reflow':
+        c.diffusion_type = _lib.DSD_DIFFUSE_REFLOW
+        c.t_start, c.time_scale_factor = float(diff.t_start), float(diff.time_scale_factor)
+    else:
+        from .hparams import hparams
+        c.diffusion_type = _lib.DSD_DIFFUSE_DDPM
+        c.timesteps, c.k_step = int(diff.timesteps), int(diff.k_step)
+        kind = hparams['schedule_type']
+        c.schedule_type = _lib.SCHEDULE_IDS[kind]
+        # the wrapper's constructor calls the schedule function with its default max_beta; the buffers are persistent, so a
+        # checkpoint may carry another schedule - which a config of (schedule_type, max_beta) cannot describe
+        c.max_beta = float(inspect.signature(schedule.linear_beta_schedule).parameters['max_beta'].default)
+        mine = cprogram.tables(kind, c.timesteps, c.max_beta)
+        for name in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "betas"):
+            if getattr(mine, name).tobytes() != getattr(diff, name).detach().cpu().numpy().tobytes():
+                raise ValueError(f"the model's `{name}` buffer is not the {kind} schedule of {c.timesteps} steps (max_beta {c.max_beta}): "
+                                 "a checkpoint with a schedule of its own cannot be packed as an acoustic twin")
+    return c
+
+
+def acoustic_sections(prefix, model):
+    """The sections dsd_acoustic_open looks for under `prefix`, for a `deploy.DiffSingerAcousticDeploy`: `<prefix>.tables`
+    (kind DSD_ACOUSTIC_TABLES: the mask of its `cross_lingual_token_idx`, spec_min / spec_max broadcast to the mel bins, the
+    discrete f0 embedding and the two `frozen_*` tensors where the model has them), `<prefix>.fs2`, `<prefix>.aux` (with shallow
+    diffusion) and `<prefix>.denoiser`."""
+    cfg = acoustic_config(model)
+    tensors = OrderedDict()
+    mask = np.zeros(cfg.vocab_size, dtype="<f4")
+    idx = np.asarray(model.cross_lingual_token_idx.cpu().numpy(), dtype=np.int64)
+    mask[idx[(idx >= 0) & (idx < cfg.vocab_size)]] = 1.0
+    tensors["cross_lingual_mask"] = mask
+    for name in ("spec_min", "spec_max"):
+        v = _as_f32(getattr(model.diffusion, name)).reshape(-1)
+        if v.size not in (1, cfg.out_dims):
+            raise ValueError(f"{name} has {v.size} values for {cfg.out_dims} mel bins")
+        tensors[name] = np.array(np.broadcast_to(v, (cfg.out_dims,)))      # a copy: the caller may edit it
+    if cfg.f0_discrete:
+        tensors["fs2.pitch_embed.weight"] = _as_f32(model.fs2.pitch_embed.weight)
+    for name in ("frozen_spk_embed", "frozen_key_shift"):
+        v = model._frozen(name)
+        if v is not None:
+            tensors[name] = np.ascontiguousarray(_as_f32(v).reshape(-1))
+    out = [Section(prefix + ".tables", _lib.DSD_ACOUSTIC_TABLES, cfg, tensors), section_of(prefix + ".fs2", model.fs2)]
+    if cfg.use_shallow_diffusion:
+        out.append(section_of(prefix + ".aux", model.aux_decoder.decoder))
+    out.append(section_of(prefix + ".denoiser", _backbone_of(model.diffusion)))
     return out
 
 

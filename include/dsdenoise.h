@@ -64,7 +64,8 @@ enum { DSD_BACKBONE_WAVENET = 0, DSD_BACKBONE_LYNXNET = 1,
           built on it; created with dsd_hnsep_create */
        DSD_HNSEP_VR = 8 };
 /* A model file has one more section kind, DSD_VARIANCE_TABLES = 10 (the variance model's embedding tables: not a handle,
-   see dsd_variance_open).  9 is not assigned, and a model file reader refuses it as unknown. */
+   see dsd_variance_open).  9 is not assigned, and a model file reader refuses it as unknown.  DSD_ACOUSTIC_TABLES = 11 is
+   the acoustic model's counterpart (see dsd_acoustic_open). */
 /* modules/backbones/lynxnet.py:38-42  activation_classes */
 enum { DSD_ACT_PRELU = 0, DSD_ACT_SILU = 1, DSD_ACT_RELU = 2 };
 
@@ -1448,6 +1449,166 @@ int dsd_variance_pitch_post(dsd_variance* v, const float* sample, const float* b
  * clamp(mean_m sample[b, i, t, m]) for the first V entries, each [B, T]; a variance with var_no_clamp is not clamped.
  */
 int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T, float* const* curves_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The acoustic model's staged twin on one model file: DiffSingerAcousticONNX (deployment/modules/toplevel.py:20-103) with
+ * FastSpeech2AcousticONNX.forward (deployment/modules/fastspeech2.py:43-130) as its first stage and GaussianDiffusionONNX /
+ * RectifiedFlowONNX (deployment/modules/diffusion.py:105-161, rectified_flow.py:37-68) as its second, for a process without
+ * Python: phonemes, durations and f0 in, mel out.  One object owns the inner handles (the acoustic encoder, the aux decoder
+ * of shallow diffusion, the denoiser), the constants the stages read and the sampler programs it has built.
+ *
+ * A section of kind DSD_ACOUSTIC_TABLES holds a dsd_acoustic_config and, in fp32,
+ *   cross_lingual_mask [vocab_size]        always; 1 where the token is in cross_lingual_token_idx, else 0; all zeros
+ *                                          switches the language embedding off (every token then takes lang_embed's row 0)
+ *   spec_min [out_dims], spec_max [out_dims]   always (the writer broadcasts a scalar); spec_max[m] > spec_min[m]
+ *   fs2.pitch_embed.weight [300, H]        f0_discrete: the Embedding over f0_to_coarse (fastspeech2.py:54-57)
+ *   frozen_spk_embed [H]                   optional, needs use_spk_id: takes the place of the caller's spk_embed
+ *   frozen_key_shift [1]                   optional, needs DSD_EMBED_KEY_SHIFT: takes the place of the gender curve
+ * The format version stays 1 and DSD_API_VERSION stays 10: the kind is an addition, as DSD_VARIANCE_TABLES was.
+ * dsd_model_create answers DSD_EINVAL for the kind (use dsd_acoustic_open).
+ * ------------------------------------------------------------------------------------------ */
+#define DSD_ACOUSTIC_TABLES 11
+#define DSD_AC_FS2 0             /* dsd_acoustic_handle: the acoustic encoder (dsd_encode)                 */
+#define DSD_AC_AUX 1             /* ... the aux decoder of shallow diffusion (dsd_aux_decode)              */
+#define DSD_AC_DENOISER 2        /* ... the denoiser (dsd_prepare_cond / dsd_sample)                       */
+#define DSD_AC_PITCH_BINS 300    /* rows of the discrete f0 embedding                                      */
+
+typedef struct dsd_acoustic_config {
+    int32_t struct_size;         /* sizeof(dsd_acoustic_config)                                              */
+    int32_t hidden_size;         /* hparams['hidden_size']                                                   */
+    int32_t vocab_size;
+    int32_t out_dims;            /* M mel bins                                                               */
+    int32_t num_lang;            /* lang_embed has num_lang + 1 rows (0 without use_lang_id)                 */
+    int32_t num_spk;             /* 0 without use_spk_id                                                     */
+    int32_t use_lang_id;         /* 0/1: the encoder has a lang_embed                                        */
+    int32_t use_spk_id;          /* 0/1                                                                      */
+    uint32_t embed_flags;        /* DSD_EMBED_*: the variance, key-shift and speed embeddings of the encoder */
+    int32_t f0_discrete;         /* 0/1: f0_embed_type == 'discrete'                                         */
+    int32_t use_shallow_diffusion;   /* 0/1: the model has an aux decoder                                    */
+    float shift_min, shift_max;  /* augmentation_args.random_pitch_shifting.range (read with the key-shift bit)  */
+    float speed_min, speed_max;  /* augmentation_args.random_time_stretching.range (read with the speed bit)     */
+    int32_t mel_base_e;          /* 0/1; 0: the sampler stage multiplies its mel by 2.30259 (log10 -> ln)    */
+    int32_t diffusion_type;      /* DSD_DIFFUSE_DDPM / DSD_DIFFUSE_REFLOW                                    */
+    int32_t timesteps, k_step;   /* DDPM; k_step == timesteps without shallow diffusion                      */
+    int32_t schedule_type;       /* DSD_SCHEDULE_LINEAR / _COSINE (DDPM)                                     */
+    double max_beta;             /* the linear schedule's max_beta as the wrapper built its tables (DDPM)    */
+    float t_start;               /* hparams['T_start'] (reflow; 0 without shallow diffusion)                 */
+    float time_scale_factor;     /* hparams['time_scale_factor'] (reflow)                                    */
+} dsd_acoustic_config;
+
+typedef struct dsd_acoustic dsd_acoustic;        /* opaque; not a dsd_handle */
+
+/*
+ * Replaces: DiffSingerAcousticONNX.__init__ + load_state_dict (toplevel.py:20-53).
+ * Finds `<prefix>.tables` (kind DSD_ACOUSTIC_TABLES), `<prefix>.fs2` (DSD_ENC_FS2_ACOUSTIC), `<prefix>.aux` (DSD_AUX_CONVNEXT,
+ * with use_shallow_diffusion) and `<prefix>.denoiser` (kind 0 or 1).  Host checks come first, so a file that is refused
+ * touches no device: the tables against their config (a missing tensor, one the config excludes and a wrong shape are
+ * DSD_EINVAL naming the tensor), every flag 0/1, every mask value 0/1, spec_max[m] > spec_min[m], shift_min <= 0 <= shift_max,
+ * 0 < speed_min <= speed_max, and each inner config against the tables' (encoder hidden_size, vocab_size, embed_flags,
+ * num_spk, num_lang; denoiser in_dims == out_dims, n_feats == 1, hidden_size; aux decoder in_dims, n_feats, hidden_size; a
+ * mismatch names both fields).  Then the inner handles are made by dsd_model_create and the constants - k = (spec_max -
+ * spec_min) / 2 and mid = (spec_max + spec_min) / 2, formed in fp32 - are uploaded once.  On any failure everything built
+ * so far is released and *out = NULL.
+ */
+int dsd_acoustic_open(const dsd_model_file* f, const char* prefix, int32_t device, dsd_acoustic** out);
+void dsd_acoustic_close(dsd_acoustic* a);            /* NULL is fine */
+/* the tables' config as stored */
+int dsd_acoustic_info(const dsd_acoustic* a, dsd_acoustic_config* out);
+/* which: DSD_AC_FS2 / DSD_AC_AUX / DSD_AC_DENOISER.  *out is borrowed: it lives until dsd_acoustic_close, never dsd_destroy
+   it.  DSD_EINVAL for DSD_AC_AUX on a model without shallow diffusion. */
+int dsd_acoustic_handle(const dsd_acoustic* a, int32_t which, dsd_handle** out);
+
+/*
+ * The stage calls follow dsd_variance_*'s conventions: every pointer is device memory unless marked HOST; each call checks
+ * all of its arguments on the host before the first launch, reads nothing back, keeps ONE workspace per stage per object on
+ * the object's device (made current by every call) that only grows - a second call at the same sizes allocates nothing and
+ * may be captured in a HIP graph.  Use one object per stream.
+ *
+ * Replaces: forward_fs2_aux (toplevel.py:61-81) with FastSpeech2AcousticONNX.forward (fastspeech2.py:59-130), in this
+ * order: durations * (tokens > 0); mel2ph = dsd_length_regulate; f0 * (mel2ph > 0); languages * mask[tokens] (zeros when the
+ * model has a lang_embed and the mask is all zeros); the key shift - frozen_key_shift broadcast where the file has it, else
+ * with g = clip(gender, -1, 1) and m = g < 0: g * ((1 - m) * shift_max + m * |shift_min|), each product and sum rounded to
+ * fp32 on its own; the speed clip(velocity, speed_min, speed_max), 1 for a NULL velocity; frozen_spk_embed in place of
+ * spk_embed where the file has it; dsd_encode on the encoder handle; with f0_discrete, condition +
+ * pitch_embed.weight[f0_to_coarse(f0)] by dsd_cond_assemble (the encoder's own pitch term is stored as zeros and sees f0 = 0);
+ * dsd_aux_decode last, with the denorm x * k + mid.
+ * DSD_EINVAL: what dsd_variance_* refuses of this kind (NULL object, args or required pointer, struct_size, B < 1, L outside
+ * [1, 2048], T < 1, spk_embed on a model without use_spk_id or missing on one with it and no frozen_spk_embed, spk_rows
+ * neither 1 nor T); gender NULL where it is read; a curve NULL for a set DSD_EMBED_ENERGY .. _TENSION bit or given for a
+ * cleared one; gender / velocity given on a model without the embedding; aux_mel on a model without an aux decoder, or
+ * NULL on one with it; languages NULL while the mask has a set entry (and the model a lang_embed).
+ */
+typedef struct dsd_acoustic_condition_args {
+    int32_t struct_size;
+    int32_t B, L, T;
+    const int64_t* tokens;        /* [B, L]; 0 = padding                                                       */
+    const int64_t* durations;     /* [B, L] frames per phoneme; every item's total is at most T                */
+    const float* f0;              /* [B, T] Hz                                                                 */
+    const float* curves[4];       /* [B, T] each, by the order of the DSD_EMBED_ENERGY .. _TENSION bits; NULL where clear */
+    const float* gender;          /* [B, T] or NULL                                                            */
+    const float* velocity;        /* [B, T] or NULL (= 1)                                                      */
+    const float* spk_embed;       /* [B, spk_rows, H] or NULL                                                  */
+    int32_t spk_rows;             /* 1 or T                                                                    */
+    const int64_t* languages;     /* [B, L] or NULL                                                            */
+    float* condition;             /* [B, T, H]                                                                 */
+    float* aux_mel;               /* [B, T, M]: exactly when the model has shallow diffusion                   */
+    int64_t* f0_coarse;           /* [B, T] or NULL: f0_to_coarse(f0 * (mel2ph > 0)), if wanted; f0_discrete only */
+} dsd_acoustic_condition_args;
+int dsd_acoustic_condition(dsd_acoustic* a, const dsd_acoustic_condition_args* args, void* stream);
+
+/*
+ * Replaces: how GaussianDiffusionONNX.forward (diffusion.py:105-131) and RectifiedFlowONNX.forward (rectified_flow.py:
+ * 37-57) turn the runtime inputs `depth` and `steps` into a start state and a loop.  Host only, and on a config, not an
+ * object: it runs without a GPU.  depth < 0: no shallow source (forward_diffusion / forward_reflow).
+ *   DDPM    (t_max, speedup) = dsd_onnx_ddpm_plan on the factors of `timesteps`.  start: NOISE without a source or when
+ *           t_max >= timesteps; MIX for 0 < t_max < timesteps with src_scale = sqrt_alphas_cumprod[t_max - 1] and noise_scale
+ *           = sqrt_one_minus_alphas_cumprod[t_max - 1] of dsd_ddpm_tables_fill(schedule_type, timesteps, max_beta); SOURCE at
+ *           t_max == 0.  n_step_noise = t_max when speedup == 1 (the ancestral sampler), else 0 (DDIM).
+ *   reflow  t_start = max(fp32(1 - depth), fp32(T_start)) with a source, 0 without.  NOISE for t_start <= 0, SOURCE for
+ *           t_start >= 1, else MIX with src_scale = t_start and noise_scale = fp32(1.0 - (double)t_start).  t_max, speedup
+ *           and n_step_noise are 0.
+ * NOISE has src_scale 0 and noise_scale 1, SOURCE 1 and 0.  DSD_EINVAL: a NULL argument, a wrong cfg->struct_size, an
+ * unknown diffusion_type, a NaN depth, steps < 1 on DDPM, and whatever dsd_onnx_ddpm_plan / dsd_ddpm_tables_fill refuse.
+ */
+#define DSD_AC_START_NOISE 0
+#define DSD_AC_START_MIX 1
+#define DSD_AC_START_SOURCE 2
+typedef struct dsd_acoustic_plan_t {
+    int32_t mode;                 /* DSD_DIFFUSE_DDPM / DSD_DIFFUSE_REFLOW                                      */
+    int32_t start;                /* DSD_AC_START_*                                                            */
+    int32_t t_max, speedup;       /* DDPM                                                                      */
+    float t_start;                /* reflow                                                                    */
+    int32_t n_step_noise;         /* [B, 1, M, T] tensors dsd_acoustic_sample reads from step_noise            */
+    float src_scale, noise_scale;
+    int32_t steps;                /* as given: reflow's euler steps                                            */
+} dsd_acoustic_plan_t;
+int dsd_acoustic_plan(const dsd_acoustic_config* cfg, float depth, int32_t steps, dsd_acoustic_plan_t* out);
+
+/*
+ * Replaces: the start state of GaussianDiffusionONNX.forward (diffusion.py:117-129: norm_spec, q_sample) and
+ * RectifiedFlowONNX.forward (rectified_flow.py:45-56).  SOURCE or MIX: x[b, 0, m, t] = src_scale * ((source[b, t, m] - mid[m])
+ * / k[m]) + noise_scale * noise[b, 0, m, t] - a correctly rounded division, both products and the sum rounded on their own;
+ * SOURCE, and MIX with noise == NULL, write the normalised, transposed source alone (after the latter the caller mixes
+ * seeded noise in place: dsd_noise_fill with src = x, src_scale, scale = noise_scale).  NOISE copies noise to x.  x must not
+ * overlap source or noise.  DSD_EINVAL: a NULL object, plan or x, B < 1, T < 1, B * M * T > 2^31 - 1, an unknown plan->start,
+ * source NULL for SOURCE / MIX, noise NULL for NOISE.
+ */
+int dsd_acoustic_start(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const float* source, const float* noise, int32_t B,
+                       int32_t T, float* x, void* stream);
+
+/*
+ * Replaces: the loop and denorm_spec of GaussianDiffusionONNX.forward (diffusion.py:131-161) / RectifiedFlowONNX.forward
+ * (rectified_flow.py:58-68), and ensure_mel_base (toplevel.py:55-59).  dsd_prepare_cond on the denoiser with the [B, T, H]
+ * strides; the plan's program from dsd_program_build - DDIM at (t_max, speedup), the ancestral sampler in chunks of 50 steps
+ * with step_noise consumed in order, DSD_SAMPLER_RF_EULER_ONNX for reflow, the empty program at t_max == 0, t_start >= 1 or
+ * (reflow) steps < 1 - cached on the object per plan (at most 32, then the cache is cleared); dsd_sample with
+ * DSD_SAMPLE_TRANSPOSE | flags, out_scale = k, out_shift = mid; with mel_base_e == 0 one more launch multiplies mel in place
+ * by fp32(2.30259).  flags: DSD_SAMPLE_GRAPH / DSD_SAMPLE_GRAPH_LAZY (not inside a capture of the caller's own).
+ * DSD_EINVAL: a NULL object, plan, condition, x or mel, B < 1, T < 1, a plan whose mode is not the model's or whose fields
+ * are out of range, step_noise NULL with n_step_noise > 0, a flag other than the two.
+ */
+int dsd_acoustic_sample(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const float* condition, const float* x,
+                        const float* step_noise, int32_t B, int32_t T, uint32_t flags, float* mel, void* stream);
 
 #ifdef __cplusplus
 }

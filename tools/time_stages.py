@@ -10,7 +10,13 @@ launches, not by arithmetic.  Device-event times, warm-up, median of several rep
 256, 120 tokens, 60 notes, `--frames` frames, B = 1 and 8), the Python twin's stage (`deploy.DiffSingerVarianceDeploy`) and
 the C stage (`dsd_variance_*` through `cvariance.Variance`, on a model file packed from the same weights) in this one process
 on the same inputs.  Per stage and batch size: device-event time of one call, and the host time one
-call takes to issue (wall clock over back-to-back calls, the device drained before and after).  One JSON line."""
+call takes to issue (wall clock over back-to-back calls, the device drained before and after).  One JSON line.
+
+`--acoustic`: the same for the acoustic twin at the sizes of a configs/acoustic.yaml segment (hidden
+256, 128 mel bins, 120 tokens, `--frames` frames, B = 1 and 8, shallow DDPM with every embedding): `condition`
+(forward_fs2_aux against dsd_acoustic_condition), `start` (the twin's norm_spec + q_sample against dsd_acoustic_start) and
+`sample` (forward_shallow_diffusion at depth 0.4 in 10 steps against dsd_acoustic_sample), `deploy.DiffSingerAcousticDeploy`
+against `cacoustic.Acoustic` on a model file packed from the same weights, in this one process."""
 import argparse
 import json
 import os
@@ -35,6 +41,7 @@ ap.add_argument("--warmup", type=int, default=10)
 ap.add_argument("--frames", type=int, default=1000)
 ap.add_argument("--out")
 ap.add_argument("--variance", action="store_true")
+ap.add_argument("--acoustic", action="store_true")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "time_stages.py needs the MI355X"
 
@@ -129,9 +136,65 @@ def variance_stages():
     return res
 
 
-if args.variance:
+def acoustic_stages():
+    import tempfile
+    from diffsinger_amd import _lib, cacoustic, modelfile
+    from diffsinger_amd.diffusion import _to_bfmt
+    graph_flags = _lib.DSD_SAMPLE_GRAPH | _lib.DSD_SAMPLE_GRAPH_LAZY
+    vocab, n_ph, t_len, h, m = 60, 120, args.frames, 256, 128
+    hp = dict(dc.BASE_HP)
+    hp.update(dc.ACOUSTIC_HP, hidden_size=256, enc_layers=4, use_shallow_diffusion=True, diffusion_type="ddpm", K_step=400,
+              use_key_shift_embed=True, use_speed_embed=True, use_energy_embed=True, use_breathiness_embed=True, use_spk_id=True,
+              num_spk=4, use_lang_id=True, num_lang=2, spec_min=[-12.0], spec_max=[0.0],
+              backbone_args=dict(num_layers=20, num_channels=256, dilation_cycle_length=4),
+              shallow_diffusion_args=dict(dc.ACOUSTIC_HP["shallow_diffusion_args"],
+                                          aux_decoder_args=dict(num_channels=512, num_layers=6, kernel_size=7, dropout_rate=0.1)))
+    hparams.clear()
+    hparams.update(hp, infer=True)
+    torch.manual_seed(2460)
+    model = deploy.DiffSingerAcousticDeploy(vocab, m, cross_lingual_token_idx=list(range(2, vocab, 3))).cuda().eval()
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "acoustic.dsdm")
+        modelfile.write(path, modelfile.acoustic_sections("ac", model))
+        with modelfile.open(path) as f:
+            a = cacoustic.Acoustic(f, "ac", "cuda")
+    rng = np.random.default_rng(2461)
+    depth, steps = 0.4, 10
+    plan = a.plan(depth, steps)
+    res = {"T": t_len, "tokens": n_ph, "hidden": h, "mel_bins": m, "depth": depth, "steps": steps, "t_max": int(plan.t_max),
+           "speedup": int(plan.speedup), "stages": {}}
+    diff = model.diffusion
+    k, mid = (diff.spec_max - diff.spec_min) / 2., (diff.spec_max + diff.spec_min) / 2.
+    for bsz in (1, 8):
+        def f32(lo, hi, shape):
+            return torch.from_numpy(rng.uniform(lo, hi, shape).astype(np.float32)).cuda()
+        tokens = torch.from_numpy(rng.integers(1, vocab, (bsz, n_ph)).astype(np.int64)).cuda()
+        languages = torch.from_numpy(rng.integers(1, 3, (bsz, n_ph)).astype(np.int64)).cuda()
+        durations = torch.from_numpy(np.stack([rng.multinomial(t_len, np.ones(n_ph) / n_ph) for _ in range(bsz)])).cuda()
+        f0 = f32(110, 440, (bsz, t_len))
+        curves = dict(energy=f32(-60, -10, (bsz, t_len)), breathiness=f32(-60, -10, (bsz, t_len)))
+        kw = dict(gender=f32(-1.2, 1.2, (bsz, t_len)), velocity=f32(0.4, 2.2, (bsz, t_len)), spk_embed=torch.randn(bsz, 1, h, device="cuda"),
+                  languages=languages)
+        noise = torch.randn(bsz, 1, m, t_len, device="cuda")
+        cond, aux = a.condition(tokens, durations, f0, curves, **kw)
+        x = a.start(plan, source=aux, noise=noise)
+        depth_t = torch.tensor(depth, dtype=torch.float32)
+        pairs = {
+            "condition": (lambda: model.forward_fs2_aux(tokens, durations, f0, curves, **kw), lambda: a.condition(tokens, durations, f0, curves, **kw)),
+            "start": (lambda: diff._start_state(plan.t_max, _to_bfmt((aux - mid) / k, 1), noise, bsz, aux.device),
+                      lambda: a.start(plan, source=aux, noise=noise)),
+            "sample": (lambda: model.forward_shallow_diffusion(cond, aux, depth_t, steps, noise=noise), lambda: a.sample(plan, cond, x, flags=graph_flags)),     # the twin's own graph policy ("lazy")
+        }
+        for stage, (twin, c_call) in pairs.items():
+            res["stages"][f"{stage}_b{bsz}"] = {"python_device_ms": timed(twin), "c_device_ms": timed(c_call),
+                                                "python_host_ms": host_ms(twin), "c_host_ms": host_ms(c_call)}
+    a.close()
+    return res
+
+
+if args.variance or args.acoustic:
     with torch.no_grad():
-        line = json.dumps(variance_stages())
+        line = json.dumps(variance_stages() if args.variance else acoustic_stages())
     print(line)
     if args.out:
         with open(args.out, "w") as f:
