@@ -21,6 +21,7 @@ DSD_SAMPLE_GRAPH_LAZY = 4
 BACKBONE_IDS = {"wavenet": 0, "lynxnet": 1}
 AUX_CONVNEXT = 2
 DSD_NOISE_NORMAL, DSD_NOISE_UNIFORM = 0, 1
+DSD_DOMAIN_X_T, DSD_DOMAIN_STEP, DSD_DOMAIN_VOC_SOURCE, DSD_DOMAIN_VOC_PRE, DSD_DOMAIN_VOC_PHASE = 1, 2, 3, 4, 5
 DSD_TRACK_F64, DSD_TRACK_F32, DSD_TRACK_PCM = 0, 1, 2
 DSD_SCORE_WORKSPACE_BYTES = 65536
 DSD_CURVE_MAX, DSD_CURVE_CHUNK = 32, 256
@@ -56,6 +57,7 @@ EXPORTS = [
     "dsd_variance_dur", "dsd_variance_pitch_cond", "dsd_variance_cond", "dsd_variance_pitch_post", "dsd_variance_post",
     "dsd_acoustic_open", "dsd_acoustic_close", "dsd_acoustic_info", "dsd_acoustic_handle", "dsd_acoustic_condition",
     "dsd_acoustic_plan", "dsd_acoustic_start", "dsd_acoustic_sample",
+    "dsd_acoustic_set_lengths", "dsd_acoustic_spk_mix", "dsd_variance_spk_mix", "dsd_vocode_seeded",
 ]
 DSD_API_VERSION = 10
 DSD_EINVAL, DSD_ESTATE, DSD_EHIP, DSD_ENOMEM, DSD_ENOTFOUND, DSD_EIO = -1, -2, -3, -4, -5, -6
@@ -244,6 +246,17 @@ class DsdAcousticPlan(C.Structure):
                 ("n_step_noise", C.c_int32), ("src_scale", C.c_float), ("noise_scale", C.c_float), ("steps", C.c_int32)]
 
 
+class DsdSpkMixArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("N", C.c_int32),
+                ("ids", C.POINTER(C.c_int32)), ("values", C.c_void_p), ("normalize", C.c_int32), ("out", C.c_void_p)]
+
+
+class DsdVocodeSeededArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("vocoder", C.c_void_p), ("mel", C.c_void_p),
+                ("stride_b", C.c_int64), ("stride_m", C.c_int64), ("stride_t", C.c_int64), ("lengths", C.POINTER(C.c_int32)),
+                ("f0", C.c_void_p), ("seeds", C.POINTER(C.c_uint64)), ("wav_out", C.c_void_p)]
+
+
 # the config struct of each handle kind (the DSD_* enum), and the create call dsd_model_create makes for it
 KIND_CONFIGS = {0: DsdConfig, 1: DsdConfig, 2: DsdConfig, 3: DsdEncoderConfig, 4: DsdVocoderConfig, 5: DsdTokenEncoderConfig,
                 6: DsdMelConfig, 7: DsdRmvpeConfig, 8: DsdHnsepConfig, 10: DsdVarianceConfig,       # 9 is not assigned
@@ -405,6 +418,10 @@ def _load():
     lib.dsd_acoustic_plan.argtypes = [C.POINTER(DsdAcousticConfig), C.c_float, i32, C.POINTER(DsdAcousticPlan)]
     lib.dsd_acoustic_start.argtypes = [vp, C.POINTER(DsdAcousticPlan), vp, vp, i32, i32, vp, vp]
     lib.dsd_acoustic_sample.argtypes = [vp, C.POINTER(DsdAcousticPlan), vp, vp, vp, i32, i32, C.c_uint32, vp, vp]
+    lib.dsd_acoustic_set_lengths.argtypes = [vp, C.POINTER(C.c_int32), i32, vp]
+    lib.dsd_acoustic_spk_mix.argtypes = [vp, C.POINTER(DsdSpkMixArgs), vp]
+    lib.dsd_variance_spk_mix.argtypes = [vp, C.POINTER(DsdSpkMixArgs), vp]
+    lib.dsd_vocode_seeded.argtypes = [C.POINTER(DsdVocodeSeededArgs), vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

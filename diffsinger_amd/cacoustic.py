@@ -29,6 +29,21 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _spk_mix(entry, name, obj, device, hidden, ids, values, normalize, out):
+    """dsd_acoustic_spk_mix / dsd_variance_spk_mix on `obj`; the shapes go to the library as given, which refuses what it refuses"""
+    ids = [[int(i) for i in row] for row in (ids.tolist() if torch.is_tensor(ids) else ids)]
+    values = _as(values, torch.float32, device)
+    bsz, rows, n = values.shape
+    if len(ids) != bsz or any(len(row) != n for row in ids):
+        raise ValueError(f"ids: [{bsz}, {n}] ints expected")
+    if out is None:
+        out = torch.empty((bsz, rows, hidden), device=device, dtype=torch.float32)
+    flat = (C.c_int32 * max(1, bsz * n))(*[i for row in ids for i in row])
+    a = _lib.DsdSpkMixArgs(C.sizeof(_lib.DsdSpkMixArgs), bsz, rows, n, flat, _ptr(values), int(bool(normalize)), _ptr(out))
+    _lib.check(None, entry(obj, C.byref(a), _stream(device)), name)
+    return out
+
+
 def plan(cfg, depth, steps):
     """dsd_acoustic_plan on a `_lib.DsdAcousticConfig`: depth None = no shallow source -> `_lib.DsdAcousticPlan`"""
     out = _lib.DsdAcousticPlan()
@@ -74,6 +89,20 @@ class Acoustic:
         hp = C.c_void_p()
         _lib.check(None, _lib.lib().dsd_acoustic_handle(self._a, int(which), C.byref(hp)), "dsd_acoustic_handle")
         return hp
+
+    def set_lengths(self, lengths):
+        """dsd_acoustic_set_lengths: B frame counts for the following condition / start / sample calls, or None for dense batches"""
+        if lengths is None:
+            arr, n = None, 0
+        else:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            arr, n = (C.c_int32 * max(1, len(lens)))(*lens), len(lens)
+        _lib.check(None, _lib.lib().dsd_acoustic_set_lengths(self._a, arr, n, _stream(self.device)), "dsd_acoustic_set_lengths")
+
+    def spk_mix(self, ids, values, normalize=False, out=None):
+        """dsd_acoustic_spk_mix: ids [B, N] ints (host), values [B, rows, N] -> [B, rows, H], what `condition` takes as spk_embed"""
+        return _spk_mix(_lib.lib().dsd_acoustic_spk_mix, "dsd_acoustic_spk_mix", self._a, self.device, self.cfg.hidden_size, ids,
+                        values, normalize, out)
 
     # ---- stages ------------------------------------------------------------------------------------------
     def condition(self, tokens, durations, f0, variances=None, gender=None, velocity=None, spk_embed=None, languages=None,

@@ -22,6 +22,10 @@ struct dsd_acoustic {
     // one workspace per stage, grown on demand: a call at sizes already met allocates nothing, and a graph captured over a
     // stage stays valid until that stage is called with larger sizes
     DevBuf<char> ws_cond, ws_sample;
+    // dsd_acoustic_set_lengths: the lengths the stage calls check their (B, T) against; the inner handles hold their own copies
+    bool ragged = false;
+    std::vector<int32_t> lengths;
+    SpkMixIds spk_ids;                  // dsd_acoustic_spk_mix's ids on the device
     void drop_programs() {
         for (auto& kv : programs)
             for (dsd_program* p : kv.second) dsd_program_free(p);
@@ -79,6 +83,18 @@ int check_sizes(const char* who, int B, int L, int T) {
     if (L != -1 && (L < 1 || L > kRegulateMaxTokens)) return fail(nullptr, DSD_EINVAL, "%s: L = %d outside [1, %d]", who, L, kRegulateMaxTokens);
     if (T < 1) return fail(nullptr, DSD_EINVAL, "%s: T = %d must be positive", who, T);
     if ((int64_t)B * T > INT32_MAX) return fail(nullptr, DSD_EINVAL, "%s: B * T = %lld exceeds 2^31 - 1", who, (long long)B * T);
+    return DSD_OK;
+}
+
+// dsd_set_lengths' rules for the stage calls, checked by the object itself: dsd_acoustic_start and a condition stage without an
+// aux decoder reach no inner handle that would
+int check_lengths(const dsd_acoustic* a, const char* who, int B, int T) {
+    if (!a->ragged) return DSD_OK;
+    if ((int)a->lengths.size() != B)
+        return fail(nullptr, DSD_ESTATE, "%s: dsd_acoustic_set_lengths gave %d lengths but this call runs a batch of %d", who,
+                    (int)a->lengths.size(), B);
+    for (int b = 0; b < B; ++b)
+        if (a->lengths[(size_t)b] > T) return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d exceeds T = %d", who, b, a->lengths[(size_t)b], T);
     return DSD_OK;
 }
 
@@ -286,6 +302,7 @@ int dsd_acoustic_condition(dsd_acoustic* a, const dsd_acoustic_condition_args* g
     const dsd_acoustic_config& c = a->cfg;
     if (!g->tokens || !g->durations || !g->f0 || !g->condition) return fail(nullptr, DSD_EINVAL, "%s: NULL tokens, durations, f0 or condition", who);
     if (int rc = check_sizes(who, g->B, g->L, g->T)) return rc;
+    if (int rc = check_lengths(a, who, g->B, g->T)) return rc;
     for (int i = 0; i < 4; ++i) {
         const bool set = (c.embed_flags >> i) & 1u;
         if (set && !g->curves[i]) return fail(nullptr, DSD_EINVAL, "%s: NULL curves[%d] (%s), which the model embeds", who, i, kCurveNames[i]);
@@ -388,6 +405,7 @@ int dsd_acoustic_start(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const f
     if (!a) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
     if (!plan || !x) return fail(nullptr, DSD_EINVAL, "%s: NULL plan or x", who);
     if (int rc = check_sizes(who, B, -1, T)) return rc;
+    if (int rc = check_lengths(a, who, B, T)) return rc;
     const int M = a->cfg.out_dims;
     if ((int64_t)B * T * M > INT32_MAX) return fail(nullptr, DSD_EINVAL, "%s: B * M * T = %lld exceeds 2^31 - 1", who, (long long)B * T * M);
     if (plan->start != DSD_AC_START_NOISE && plan->start != DSD_AC_START_MIX && plan->start != DSD_AC_START_SOURCE)
@@ -412,6 +430,7 @@ int dsd_acoustic_sample(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const 
     if (!a) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
     if (!plan || !condition || !x || !mel) return fail(nullptr, DSD_EINVAL, "%s: NULL plan, condition, x or mel", who);
     if (int rc = check_sizes(who, B, -1, T)) return rc;
+    if (int rc = check_lengths(a, who, B, T)) return rc;
     const dsd_acoustic_config& c = a->cfg;
     const int M = c.out_dims, H = c.hidden_size;
     if ((int64_t)B * T * M > INT32_MAX) return fail(nullptr, DSD_EINVAL, "%s: B * M * T = %lld exceeds 2^31 - 1", who, (long long)B * T * M);
@@ -464,6 +483,34 @@ int dsd_acoustic_sample(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const 
     }
     if (!c.mel_base_e) LAUNCH_OK(who, launch_ac_mel_base(mel, (long)n, 2.30259f, (hipStream_t)stream), "the mel base kernel");
     return DSD_OK;
+}
+
+int dsd_acoustic_set_lengths(dsd_acoustic* a, const int32_t* lengths, int32_t B, void* stream) {
+    const char* who = "dsd_acoustic_set_lengths";
+    if (!a) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
+    if (lengths) {      // everything dsd_set_lengths would refuse, first: the two handles are then set both, or neither
+        if (B < 1 || B > kMaxItems) return fail(nullptr, DSD_EINVAL, "%s: B = %d outside [1, %d]", who, B, kMaxItems);
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 0) return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d is negative", who, b, lengths[b]);
+    }
+    if (a->aux) HANDLE_OK(who, a->aux, dsd_set_lengths(a->aux, lengths, B, stream), "the aux decoder");
+    HANDLE_OK(who, a->denoiser, dsd_set_lengths(a->denoiser, lengths, B, stream), "the denoiser");
+    a->ragged = lengths != nullptr;
+    if (lengths) a->lengths.assign(lengths, lengths + B);
+    else a->lengths.clear();
+    return DSD_OK;
+}
+
+int dsd_acoustic_spk_mix(dsd_acoustic* a, const dsd_spk_mix_args* args, void* stream) {
+    const char* who = "dsd_acoustic_spk_mix";
+    if (!a) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
+    const dsd_acoustic_config& c = a->cfg;
+    const char* why_not = nullptr;
+    if (!c.use_spk_id) why_not = "the model has no speaker embedding (use_spk_id = 0)";
+    else if (a->frozen_spk) why_not = "the model's speaker is frozen (frozen_spk_embed): there is nothing to mix";
+    else if (a->fs2->e_spk == SIZE_MAX) why_not = "the encoder holds no spk_embed.weight";
+    const float* table = why_not ? nullptr : a->fs2->blob.p + a->fs2->e_spk;      // the table the encoder handle holds
+    return spk_mix_run(who, args, table, why_not ? why_not : "", c.num_spk, c.hidden_size, a->device, a->spk_ids, stream);
 }
 
 }  // extern "C"

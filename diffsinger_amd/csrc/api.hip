@@ -2729,16 +2729,22 @@ int prepare_voc_ragged(dsd_handle* h, int B, int T, const int32_t* lengths, hipS
     return upload_ragged(h, h->vrag, "dsd_vocode_ragged", st);
 }
 
-// dsd_vocode and dsd_vocode_ragged (lengths != nullptr: item b is computed as if alone at T = lengths[b])
+// dsd_vocode, dsd_vocode_ragged (lengths != nullptr: item b is computed as if alone at T = lengths[b]) and dsd_vocode_seeded
+// (seeded: rand_ini, noise and pre_noise are not read; the kernels that would read them draw from seeds[b] instead)
 int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
                 int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
-                const float* pre_noise, float* wav_out, void* stream) {
+                const float* pre_noise, float* wav_out, void* stream, bool seeded = false, const uint64_t* seeds = nullptr) {
     if (!h || !mel || !f0 || !wav_out) return fail(h, DSD_EINVAL, "%s: null argument", who);
     if (int rc = enter(h, who, K_VOC, ENTER_WEIGHTS | ENTER_LAUNCH)) return rc;
-    if (!h->vcfg.mini_nsf && (!rand_ini || !noise))
-        return fail(h, DSD_EINVAL, "%s: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)", who);
-    if (h->vcfg.noise_sigma > 0.f && !pre_noise)
-        return fail(h, DSD_EINVAL, "%s: pre_noise is required when noise_sigma > 0 (models.py:272-273)", who);
+    if (seeded) {
+        if (!seeds && (!h->vcfg.mini_nsf || h->vcfg.noise_sigma > 0.f))
+            return fail(h, DSD_EINVAL, "%s: null seeds, but the generator draws (a SineGen source, or noise_sigma > 0)", who);
+    } else {
+        if (!h->vcfg.mini_nsf && (!rand_ini || !noise))
+            return fail(h, DSD_EINVAL, "%s: rand_ini and noise are required (the SineGen source draws them, models.py:145,165)", who);
+        if (h->vcfg.noise_sigma > 0.f && !pre_noise)
+            return fail(h, DSD_EINVAL, "%s: pre_noise is required when noise_sigma > 0 (models.py:272-273)", who);
+    }
     if (B < 1 || T < 1) return fail(h, DSD_EINVAL, "%s: B and T must be positive (B=%d, T=%d)", who, B, T);
     if (stride_t != 1 && stride_m != 1)
         return fail(h, DSD_EINVAL, "%s: mel must be contiguous along T ([B,M,T]) or along M ([B,T,M])", who);
@@ -2766,6 +2772,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         };
         const size_t o_mel = take((size_t)B * v.num_mels * Ts0), o_pre = take((size_t)B * C0 * Ts0);
         const size_t o_har = take((size_t)B * lts[NU]), o_ph = take((size_t)B * T), o_wav = take((size_t)B * lts[NU]);
+        const size_t o_ini = take((size_t)B * 16);      // dsd_vocode_seeded's initial phases [B][harmonic_num + 1 <= 16]
         std::vector<size_t> ob;
         for (int i = 0; i < NU; ++i) {
             const size_t n = (size_t)B * voc_stage_channels(v, i) * lts[i + 1];
@@ -2778,6 +2785,7 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         if (hipMemsetAsync(a, 0, off * sizeof(float), st) != hipSuccess) return fail(h, DSD_EHIP, "hipMemset(vocoder workspace) failed");
         h->vB = B; h->vT = T;
         h->v_mel = a + o_mel; h->v_pre_out = a + o_pre; h->v_har = a + o_har; h->v_phase = a + o_ph; h->v_wav = a + o_wav;
+        h->v_ini = a + o_ini;
         h->v_buf.clear();
         for (size_t o : ob) h->v_buf.push_back(a + o);
     }
@@ -2797,6 +2805,23 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         const int src_upp = (int)(src_len / T);
         VOC_OK(launch_voc_fast_source(f0, B, T, src_upp, (float)v.sampling_rate / (float)voc_upp(v, 2), h->v_phase, lts[NU],
                                       h->v_har, st, lengths ? rag(0)->lens : nullptr), "source");
+    } else if (seeded) {
+        // the initial phases: dsd_noise_fill's uniform rows, one per item (ragged) or one shared from seeds[0] (dense), into the
+        // workspace; then the source kernel that draws its own normals
+        const int dim = v.harmonic_num + 1, n_ini = lengths ? B : 1;
+        NoiseP np;
+        memset(&np, 0, sizeof(np));
+        np.out = h->v_ini; np.scale = 1.f; np.src_scale = 1.f; np.domain = kVocPhaseDomain;
+        np.n = 1; np.B = n_ini; np.rows = 1; np.cols = dim; np.kind = DSD_NOISE_UNIFORM;
+        for (int b0 = 0; b0 < n_ini; b0 += kNoiseItems) {
+            const int items = std::min(kNoiseItems, n_ini - b0);
+            np.b0 = b0;
+            for (int b = 0; b < items; ++b) np.seed[b] = seeds[b0 + b];
+            VOC_OK(launch_noise_fill(np, items, st), "initial phases");
+        }
+        VOC_OK(launch_voc_source_seeded(f0, h->v_ini, (const unsigned long long*)seeds, blob + h->v_linw, blob + h->v_linb, B, T,
+                                        (int)upp, dim, (float)v.sampling_rate, 0.1f, 0.003f, h->v_phase, lts[NU], h->v_har, st,
+                                        lengths ? rag(0)->lens : nullptr), "seeded source");
     } else {
         VOC_OK(launch_voc_source(f0, rand_ini, noise, blob + h->v_linw, blob + h->v_linb, B, T, (int)upp, v.harmonic_num + 1,
                                  (float)v.sampling_rate, 0.1f, 0.003f, h->v_phase, lts[NU], h->v_har, st,
@@ -2809,9 +2834,13 @@ int vocode_impl(const char* who, dsd_handle* h, const float* mel, int32_t B, int
         g.p.act = ACT_NONE; g.p.out = h->v_pre_out; g.p.o_bstride = (long)C0 * Ts0; g.p.o_rstride = Ts0;
         if ((rc = run_gemm(h, g, st))) return rc;
     }
-    if (v.noise_sigma > 0.f)      // x += noise_sigma * randn_like(x)  (models.py:272-273)
+    if (v.noise_sigma > 0.f && seeded) {
+        VOC_OK(launch_voc_add_noise_seeded(h->v_pre_out, (const unsigned long long*)seeds, B, C0, T, Ts0, v.noise_sigma, st,
+                                           lengths ? rag(0)->lens : nullptr), "seeded pre-noise");
+    } else if (v.noise_sigma > 0.f) {   // x += noise_sigma * randn_like(x)  (models.py:272-273)
         VOC_OK(launch_voc_add_noise(h->v_pre_out, pre_noise, B, C0, T, Ts0, v.noise_sigma, st, lengths ? rag(0)->lens : nullptr),
                "pre-noise");
+    }
     const float* cur = h->v_pre_out;
     int cur_c = C0;
     for (int i = 0; i < NU; ++i) {
@@ -2934,6 +2963,14 @@ int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int
     if (!lengths) return fail(h, DSD_EINVAL, "dsd_vocode_ragged: null lengths");
     return vocode_impl("dsd_vocode_ragged", h, mel, B, T, stride_b, stride_m, stride_t, lengths, f0, rand_ini, noise,
                        pre_noise, wav_out, stream);
+}
+
+int dsd_vocode_seeded(const dsd_vocode_seeded_args* g, void* stream) {
+    const char* who = "dsd_vocode_seeded";
+    if (!g) return fail(nullptr, DSD_EINVAL, "%s: null args", who);
+    if (g->struct_size != (int32_t)sizeof(*g)) return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(*g));
+    return vocode_impl(who, g->vocoder, g->mel, g->B, g->T, g->stride_b, g->stride_m, g->stride_t, g->lengths, g->f0, nullptr, nullptr,
+                       nullptr, g->wav_out, stream, true, g->seeds);
 }
 
 int dsd_aux_decode(dsd_handle* h, const float* cond, int32_t B, int32_t T, int64_t stride_b, int64_t stride_h,

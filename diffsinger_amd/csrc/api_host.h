@@ -202,6 +202,7 @@ struct dsd_handle {
     DevBuf<float> v_arena;
     std::vector<float*> v_buf;                       // per stage: x, t1, r, acc
     float *v_mel = nullptr, *v_pre_out = nullptr, *v_har = nullptr, *v_phase = nullptr, *v_wav = nullptr;
+    float* v_ini = nullptr;             // dsd_vocode_seeded: the initial phases it draws, [B][harmonic_num + 1]
     // ragged vocoder batches (dsd_vocode_ragged): lengths and valid-tile lists at every rate of the generator
     RaggedOwner vrag;
     // mel analysis (dsd_mel_create): the config, the filterbank's packed non-zero runs and the device blocks of dsd_mel_analyze
@@ -375,6 +376,39 @@ void bn_scale_shift(const dsd_handle* h, const std::string& p, int C, std::vecto
 inline bool ends_with(const std::string& s, const char* suffix) {
     const size_t n = strlen(suffix);
     return s.size() >= n && s.compare(s.size() - n, n, suffix) == 0;
+}
+
+// What dsd_acoustic_spk_mix and dsd_variance_spk_mix share: every check on the host, then the ids into the object's own device
+// block on the caller's stream and the one launch of spk_mix_kernels.hip.  `table` is nullptr for a model that has none to mix
+// (`why_not` then says why: no use_spk_id, or a frozen_spk_embed).
+struct SpkMixIds {
+    std::vector<int> host;
+    DevBuf<int> dev;
+};
+inline int spk_mix_run(const char* who, const dsd_spk_mix_args* g, const float* table, const char* why_not, int num_spk, int H,
+                       int device, SpkMixIds& ids, void* stream) {
+    if (!g) return fail(nullptr, DSD_EINVAL, "%s: NULL args", who);
+    if (g->struct_size != (int32_t)sizeof(*g)) return fail(nullptr, DSD_EINVAL, "%s: struct_size %d != %zu", who, g->struct_size, sizeof(*g));
+    if (!table) return fail(nullptr, DSD_EINVAL, "%s: %s", who, why_not);
+    if (!g->ids || !g->values || !g->out) return fail(nullptr, DSD_EINVAL, "%s: NULL ids, values or out", who);
+    if (g->B < 1 || g->B > 65535) return fail(nullptr, DSD_EINVAL, "%s: B = %d outside [1, 65535]", who, g->B);
+    if (g->rows < 1 || g->N < 1) return fail(nullptr, DSD_EINVAL, "%s: rows = %d and N = %d must be positive", who, g->rows, g->N);
+    if ((int64_t)g->B * g->rows * std::max(g->N, H) > INT32_MAX || (int64_t)g->B * g->N > INT32_MAX)
+        return fail(nullptr, DSD_EINVAL, "%s: [%d, %d, max(N = %d, H = %d)] holds more than 2^31 - 1 elements", who, g->B, g->rows, g->N, H);
+    const size_t n = (size_t)g->B * g->N;
+    for (size_t i = 0; i < n; ++i)
+        if (g->ids[i] < 0 || g->ids[i] >= num_spk)
+            return fail(nullptr, DSD_EINVAL, "%s: ids[%zu] = %d outside [0, num_spk = %d)", who, i, g->ids[i], num_spk);
+    HIP_OK(nullptr, hipSetDevice(device));
+    ids.host.assign(g->ids, g->ids + n);
+    if (int rc = ids.dev.reserve(nullptr, n, who)) return rc;
+    HIP_OK(nullptr, hipMemcpyAsync(ids.dev.p, ids.host.data(), n * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
+    SpkMixP p;
+    p.table = table; p.ids = ids.dev.p; p.values = g->values; p.out = g->out;
+    p.rows = g->rows; p.N = g->N; p.H = H; p.normalize = g->normalize != 0; p.lanes = 0;
+    const hipError_t e = launch_spk_mix(p, g->B, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(nullptr, DSD_EHIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return DSD_OK;
 }
 
 // mel analysis (mel_api.hip); RMVPE's front end runs it with a filterbank and geometry of its own

@@ -556,6 +556,17 @@ hipError_t launch_ac_source(const float* source, const float* noise, const float
                             int B, int M, int T, float* x, hipStream_t st);
 hipError_t launch_ac_mel_base(float* mel, long n, float scale, hipStream_t st);
 
+// spk_mix_kernels.hip: out[b][r][:] = sum_n w[b][r][n] * table[ids[b][n]][:] (dsd_acoustic_spk_mix, dsd_variance_spk_mix)
+struct SpkMixP {
+    const float* table;             // [num_spk][H]
+    const int* ids;                 // device [B][N], each a row of `table` (the host entry has checked them)
+    const float* values;            // [B][rows][N]
+    float* out;                     // [B][rows][H]
+    int rows, N, H, normalize;
+    int lanes;                      // the launcher's: lanes per row, a power of two <= 256
+};
+hipError_t launch_spk_mix(SpkMixP p, int B, hipStream_t st);
+
 // noise_kernels.hip: seeded draws (dsd_noise_fill).  A NoiseP launch covers up to kNoiseItems batch items starting at item
 // b0; their seeds travel in the kernel arguments, so the entry owns no device memory and never synchronises.
 constexpr int kNoiseItems = 64;
@@ -568,6 +579,19 @@ struct NoiseP {
     unsigned long long seed[kNoiseItems];
 };
 hipError_t launch_noise_fill(const NoiseP& p, int items, hipStream_t st);
+// vocoder_kernels.hip, the seeded forms (dsd_vocode_seeded): the source and pre-noise kernels draw what dsd_noise_fill would have
+// written under these domains (include/dsdenoise.h: DSD_DOMAIN_VOC_*), stream 0, scale 1.  Seeds as in NoiseP: by value, up to
+// kNoiseItems items from b0 per launch.  `seeds` is a HOST array of B values.
+constexpr unsigned kVocSourceDomain = 3, kVocPreDomain = 4, kVocPhaseDomain = 5;
+struct VocSeedP {
+    int b0;
+    unsigned long long seed[kNoiseItems];
+};
+hipError_t launch_voc_source_seeded(const float* f0, const float* rand_ini, const unsigned long long* seeds, const float* lin_w,
+                                    const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp,
+                                    float noise_std, float* acc_tmp, int Tsu, float* har, hipStream_t st, const int* lens);
+hipError_t launch_voc_add_noise_seeded(float* x, const unsigned long long* seeds, int B, int C, int T, int Ts, float sigma,
+                                       hipStream_t st, const int* lens);
 
 // score_kernels.hip: validation scoring (dsd_diffuse, dsd_masked_loss, dsd_curve_stats, dsd_dur_score).  The reductions
 // sum doubles in an order fixed by the element count alone (include/dsdenoise.h, "the rounding rule"): workgroup g of

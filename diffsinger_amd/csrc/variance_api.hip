@@ -21,6 +21,7 @@ struct dsd_variance {
     // one workspace per stage, grown on demand: a call at sizes already met allocates nothing, and a graph captured over a
     // stage stays valid until that stage is called with larger sizes
     DevBuf<char> ws_encode, ws_dur, ws_pitch, ws_cond;
+    SpkMixIds spk_ids;                  // dsd_variance_spk_mix's ids on the device
     const float* tab(int j) const { return tables.p + off[(size_t)j]; }
     ~dsd_variance() {
         for (dsd_handle* h : {fs2, melody, pitch, variances})
@@ -498,6 +499,14 @@ int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T
     HIP_OK(nullptr, hipSetDevice(v->device));
     LAUNCH_OK(who, launch_stage_post(p, B, (hipStream_t)stream), "the post kernel");
     return DSD_OK;
+}
+
+int dsd_variance_spk_mix(dsd_variance* v, const dsd_spk_mix_args* args, void* stream) {
+    const char* who = "dsd_variance_spk_mix";
+    if (!v) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
+    const bool has = v->cfg.use_spk_id && v->ix.spk >= 0;
+    return spk_mix_run(who, args, has ? v->tab(v->ix.spk) : nullptr, "the model has no speaker embedding (use_spk_id = 0)",
+                       v->cfg.num_spk, v->cfg.hidden_size, v->device, v->spk_ids, stream);
 }
 
 }  // extern "C"

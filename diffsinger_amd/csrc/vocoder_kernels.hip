@@ -278,6 +278,115 @@ hipError_t launch_voc_add_noise(float* x, const float* noise, int B, int C, int 
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// The seeded forms (dsd_vocode_seeded): the draws of voc_source_kernel and voc_add_noise_kernel made where they are used, so
+// neither noise [B, T*upp, dim] nor pre_noise [B, C0, T] exists in memory.  Element (row, col) under an item's seed is the one
+// dsd_noise_fill writes (noise_kernels.hip: counter (col >> 2, row, 0, domain), scale 1), and the arithmetic around it is the
+// unseeded kernels' line for line, so the waveform is bit for bit the one of fill-then-vocode.  A launch covers up to
+// kNoiseItems items from sd.b0; their seeds travel in the kernel arguments.
+// ---------------------------------------------------------------------------------------------
+template <int RAG>
+__global__ void voc_source_seeded_kernel(const float* __restrict__ f0, const float* __restrict__ acc,
+                                         const float* __restrict__ rand_ini, const float* __restrict__ lin_w,
+                                         const float* __restrict__ lin_b, int T, int upp, int dim, float sr, float sine_amp,
+                                         float noise_std, int Tsu, float* __restrict__ har, const int* __restrict__ lens,
+                                         const VocSeedP sd) {
+    const int b = sd.b0 + blockIdx.y;
+    const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;       // sample index within the utterance: the draw's row
+    if (s >= (long)(RAG ? lens[b] : T) * upp) return;
+    if (RAG) rand_ini += (long)b * dim;
+    const int t = (int)(s / upp), n = (int)(s - (long)t * upp);
+    const float f = f0[(long)b * T + t];
+    float rad = f / sr * (float)(n + 1);
+    if (t > 0) rad += acc[(long)b * T + t - 1];
+    const float uv = f > 0.f ? 1.f : 0.f;
+    const float namp = uv * noise_std + (1.f - uv) * sine_amp / 3.f;
+    const unsigned long long seed = sd.seed[blockIdx.y];
+    float m = 0.f;
+    for (int d0 = 0; d0 < dim; d0 += 4) {           // one Philox block per four harmonics, the last part-used
+        const dsd_u32x4 w = philox4x32_10(dsd_u32x4{(unsigned)d0 >> 2, (unsigned)s, 0u, kVocSourceDomain}, (unsigned)seed,
+                                          (unsigned)(seed >> 32));
+        float nz[4];
+        philox_normal2(w.x, w.y, nz[0], nz[1]);
+        philox_normal2(w.z, w.w, nz[2], nz[3]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = d0 + i;
+            if (d < dim) {
+                float r = rad * (float)(d + 1);
+                r += (d == 0) ? 0.f : rand_ini[d];
+                const float sine = sinf(6.283185307179586f * r) * sine_amp;
+                m += (sine * uv + namp * nz[i]) * lin_w[d];
+            }
+        }
+    }
+    har[(long)b * Tsu + s] = tanhf(m + lin_b[0]);
+}
+
+// x[row][t] += sigma * z(row = channel, col = t): one thread = one Philox block = four consecutive frames of one channel
+template <int RAG>
+__global__ void voc_add_noise_seeded_kernel(float* __restrict__ x, int T, int Ts, float sigma, const int* __restrict__ lens,
+                                            const VocSeedP sd) {
+    const int b = sd.b0 + blockIdx.z;
+    const int Tb = RAG ? lens[b] : T;
+    const int t0 = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
+    if (t0 >= Tb) return;
+    const unsigned long long seed = sd.seed[blockIdx.z];
+    const dsd_u32x4 w = philox4x32_10(dsd_u32x4{(unsigned)t0 >> 2, blockIdx.y, 0u, kVocPreDomain}, (unsigned)seed,
+                                      (unsigned)(seed >> 32));
+    float z[4];
+    philox_normal2(w.x, w.y, z[0], z[1]);
+    philox_normal2(w.z, w.w, z[2], z[3]);
+    float* xr = x + ((long)b * gridDim.y + blockIdx.y) * Ts + t0;
+    if (t0 + 4 <= Tb && (Ts & 3) == 0 && ((uintptr_t)x & 15) == 0) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(xr);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] += sigma * z[i];
+        *reinterpret_cast<f32x4*>(xr) = v;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (t0 + i < Tb) xr[i] += sigma * z[i];
+    }
+}
+
+hipError_t launch_voc_source_seeded(const float* f0, const float* rand_ini, const unsigned long long* seeds, const float* lin_w,
+                                    const float* lin_b, int B, int T, int upp, int dim, float sr, float sine_amp,
+                                    float noise_std, float* acc_tmp, int Tsu, float* har, hipStream_t st, const int* lens) {
+    if (dim > VOC_MAXDIM) return hipErrorInvalidValue;
+    const long n = (long)T * upp;
+    if (lens) hipLaunchKernelGGL(voc_phase_kernel<1>, dim3(B), dim3(256), 0, st, f0, T, sr, upp, acc_tmp, lens);
+    else hipLaunchKernelGGL(voc_phase_kernel<0>, dim3(B), dim3(256), 0, st, f0, T, sr, upp, acc_tmp, nullptr);
+    VocSeedP sd;
+    for (int b0 = 0; b0 < B; b0 += kNoiseItems) {
+        const int items = std::min(kNoiseItems, B - b0);
+        sd.b0 = b0;
+        for (int b = 0; b < kNoiseItems; ++b) sd.seed[b] = b < items ? seeds[b0 + b] : 0ull;
+        const dim3 grid((unsigned)((n + 255) / 256), items);
+        if (lens)
+            hipLaunchKernelGGL(voc_source_seeded_kernel<1>, grid, dim3(256), 0, st, f0, acc_tmp, rand_ini, lin_w, lin_b, T, upp,
+                               dim, sr, sine_amp, noise_std, Tsu, har, lens, sd);
+        else
+            hipLaunchKernelGGL(voc_source_seeded_kernel<0>, grid, dim3(256), 0, st, f0, acc_tmp, rand_ini, lin_w, lin_b, T, upp,
+                               dim, sr, sine_amp, noise_std, Tsu, har, nullptr, sd);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_voc_add_noise_seeded(float* x, const unsigned long long* seeds, int B, int C, int T, int Ts, float sigma,
+                                       hipStream_t st, const int* lens) {
+    VocSeedP sd;
+    for (int b0 = 0; b0 < B; b0 += kNoiseItems) {
+        const int items = std::min(kNoiseItems, B - b0);
+        sd.b0 = b0;
+        for (int b = 0; b < kNoiseItems; ++b) sd.seed[b] = b < items ? seeds[b0 + b] : 0ull;
+        const dim3 grid(((T + 3) / 4 + 255) / 256, C, items);
+        if (lens) hipLaunchKernelGGL(voc_add_noise_seeded_kernel<1>, grid, dim3(256), 0, st, x, T, Ts, sigma, lens, sd);
+        else hipLaunchKernelGGL(voc_add_noise_seeded_kernel<0>, grid, dim3(256), 0, st, x, T, Ts, sigma, nullptr, sd);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_voc_accum(float* acc, const float* r, long n, int first, float div, hipStream_t st) {
     hipLaunchKernelGGL(voc_accum_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, acc, r, n, first, div);
     return hipGetLastError();

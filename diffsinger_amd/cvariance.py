@@ -72,6 +72,13 @@ class Variance:
         _lib.check(None, _lib.lib().dsd_variance_backbone(self._v, int(which), C.byref(hp)), "dsd_variance_backbone")
         return hp
 
+    def spk_mix(self, ids, values, normalize=False, out=None):
+        """dsd_variance_spk_mix: ids [B, N] ints (host), values [B, rows, N] -> [B, rows, H], what `dur` (rows 1 or L) and
+        `pitch_cond` / `cond` (rows 1 or T) take as spk_embed"""
+        from .cacoustic import _spk_mix
+        return _spk_mix(_lib.lib().dsd_variance_spk_mix, "dsd_variance_spk_mix", self._v, self.device, self.cfg.hidden_size, ids,
+                        values, normalize, out)
+
     # ---- stages ------------------------------------------------------------------------------------------
     def encode(self, tokens, word_div=None, word_dur=None, ph_dur=None, languages=None, want_ph2word=False):
         """-> encoder_out [B, L, H], x_masks [B, L] bool (, ph2word [B, L])"""

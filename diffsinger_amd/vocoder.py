@@ -10,6 +10,9 @@ reproducibility, or - `forward(x, f0, seed=...)` - drawn by the library's counte
 `mini_nsf: true` generators (fastsinegen source, `source_conv`) have no random draws.
 `forward(x, f0, lengths=[...])` vocodes a zero-padded batch of segments in one ragged call (dsd_vocode_ragged): item b
 comes out as the segment alone at T = lengths[b] would, draws included.
+`forward_seeded(x, f0, seeds, lengths=None)` binds dsd_vocode_seeded, the entry a C caller uses: the same waveform as
+`forward(..., seed=seeds)` bit for bit, with the draws made inside the kernels that use them; `forward` itself stays on the
+fill-then-vocode path.
 Inference only; no CPU path.
 """
 from __future__ import annotations
@@ -208,6 +211,39 @@ class Generator(_NativeBackbone):
                                                  C.c_void_p(stream)), "dsd_vocode")
         return out
 
+
+    def forward_seeded(self, x, f0, seeds, lengths=None):
+        """dsd_vocode_seeded: `forward(x, f0, lengths=lengths, seed=seeds)` bit for bit, with the draws made inside the kernels
+        that use them - no noise [B, T * upp, dim] or pre_noise [B, C0, T] tensor exists.  seeds: one int or B ints (None only
+        for a generator that draws nothing); a dense call takes its one row of initial phases from the first."""
+        if x.dim() != 3 or x.shape[1] != self.num_mels or tuple(f0.shape) != (x.shape[0], x.shape[2]):
+            raise ValueError(f"x [B, {self.num_mels}, T] and f0 [B, T] expected; got {tuple(x.shape)}, {tuple(f0.shape)}")
+        dev = x.device
+        handle = self.native_handle(dev)
+        b, _, t = x.shape
+        x = x.detach().to(torch.float32)
+        sb, sm, st_ = x.stride()
+        if st_ != 1 and sm != 1:
+            x = x.contiguous()
+            sb, sm, st_ = x.stride()
+        f0 = f0.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out = torch.empty((b, 1, t * self.upp), device=dev, dtype=torch.float32)
+        seeds_c = None if seeds is None else (C.c_uint64 * max(1, b))(*seeded.as_seeds(seeds, b))
+        lens_c = None
+        if lengths is not None:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(lens) != b:
+                raise ValueError(f"lengths: {b} values expected; got {len(lens)}")
+            lens_c = (C.c_int32 * max(1, b))(*lens)
+        a = _lib.DsdVocodeSeededArgs(C.sizeof(_lib.DsdVocodeSeededArgs), b, t, handle, C.c_void_p(x.data_ptr()), sb, sm, st_, lens_c,
+                                     C.c_void_p(f0.data_ptr()), seeds_c, C.c_void_p(out.data_ptr()))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(handle, _lib.lib().dsd_vocode_seeded(C.byref(a), C.c_void_p(stream)), "dsd_vocode_seeded")
+        if lengths is not None:
+            for i, n in enumerate(lens):        # as forward(lengths=): the library leaves the samples past an item's end unspecified
+                if n < t:
+                    out[i, :, n * self.upp:] = 0
+        return out
 
     def draw(self, t_len, device):
         """The random draws of a lone `forward` over `t_len` frames, made as it makes them (same calls, same order):

@@ -453,6 +453,11 @@ int dsd_curve_resample(int32_t device, const dsd_curve* curves, int32_t n_curves
  * out (and src) are 16-byte aligned, scalar stores otherwise.  DSD_EINVAL before any device work for a NULL spec, out or
  * seeds, a wrong struct_size, an unknown kind, n, B, rows or cols below 1, or more than 2^31 - 1 elements.
  * ------------------------------------------------------------------------------------------ */
+#define DSD_DOMAIN_X_T 1         /* the domains above that a renderer draws under, by name                 */
+#define DSD_DOMAIN_STEP 2
+#define DSD_DOMAIN_VOC_SOURCE 3
+#define DSD_DOMAIN_VOC_PRE 4
+#define DSD_DOMAIN_VOC_PHASE 5
 #define DSD_NOISE_NORMAL 0
 #define DSD_NOISE_UNIFORM 1
 typedef struct dsd_noise_spec {
@@ -537,6 +542,36 @@ int dsd_vocode(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t st
 int dsd_vocode_ragged(dsd_handle* h, const float* mel, int32_t B, int32_t T, int64_t stride_b, int64_t stride_m,
                       int64_t stride_t, const int32_t* lengths, const float* f0, const float* rand_ini, const float* noise,
                       const float* pre_noise, float* wav_out, void* stream);
+/*
+ * The vocoder with its draws made where they are used.  Replaces: the three dsd_noise_fill calls of Generator._seeded_draws
+ * (diffsinger_amd/vocoder.py) plus dsd_vocode / dsd_vocode_ragged, i.e. torch.rand / torch.randn_like of models.py:145, 165
+ * and 273 under per-item seeds.  The result is bit for bit the waveform dsd_vocode_ragged (lengths != NULL) or dsd_vocode
+ * (lengths == NULL) gives at the same (B, T, lengths) when its inputs come from dsd_noise_fill at stream 0, scale 1:
+ *   rand_ini   DSD_NOISE_UNIFORM, DSD_DOMAIN_VOC_PHASE, rows 1, cols harmonic_num + 1: a ragged call draws one row per item
+ *              from seeds[b], a dense call one shared row from seeds[0] (as the reference draws one per call)
+ *   noise      DSD_NOISE_NORMAL, DSD_DOMAIN_VOC_SOURCE, rows T * prod(upsample_rates), cols harmonic_num + 1, seeds[b]
+ *   pre_noise  DSD_NOISE_NORMAL, DSD_DOMAIN_VOC_PRE, rows upsample_initial_channel, cols T, seeds[b]; only with noise_sigma > 0
+ * but neither noise nor pre_noise is ever written: the source kernel draws its sample row's Philox blocks and the pre-noise
+ * kernel four frames per block, and the only draw kept is rand_ini, [B, harmonic_num + 1] in the handle's workspace.  An
+ * element of a draw does not depend on T or B, so item b of a ragged call comes out as it does alone with seeds[b].
+ * The seeds travel in the launch arguments, 64 items per launch: the call reads nothing back and can be captured after a
+ * first call at the same sizes.  The handle sits inside the struct; the entry check and the errors are dsd_vocode's and
+ * land on that handle (a handle of another kind: DSD_ESTATE).  DSD_EINVAL: NULL args, a wrong struct_size (both without a
+ * device), NULL vocoder, mel, f0 or wav_out, B < 1, T < 1, a length outside [1, T], both strides non-unit, and NULL seeds
+ * unless the generator draws nothing (mini_nsf with noise_sigma == 0).
+ */
+typedef struct dsd_vocode_seeded_args {
+    int32_t struct_size;
+    int32_t B, T;
+    dsd_handle* vocoder;
+    const float* mel;          /* as dsd_vocode's, with its strides                                             */
+    int64_t stride_b, stride_m, stride_t;
+    const int32_t* lengths;    /* HOST [B] in [1, T], or NULL for a dense batch                                 */
+    const float* f0;           /* [B, T]                                                                        */
+    const uint64_t* seeds;     /* HOST [B]; may be NULL only for a generator that draws nothing                 */
+    float* wav_out;            /* [B, T * prod(upsample_rates)]                                                 */
+} dsd_vocode_seeded_args;
+int dsd_vocode_seeded(const dsd_vocode_seeded_args* args, void* stream);
 
 /*
  * Ragged batches.  The reference runs one utterance per call (inference/ds_acoustic.py:214-271), because padding a batch
@@ -1450,6 +1485,31 @@ int dsd_variance_pitch_post(dsd_variance* v, const float* sample, const float* b
  */
 int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T, float* const* curves_out, void* stream);
 
+/*
+ * Speaker mixes on the device.  Replaces: `torch.sum(spk_embed(ids) * values, dim=2)` of the inference front ends
+ * (inference/ds_acoustic.py:191-197, inference/ds_variance.py:315-326), for a caller who cannot read `spk_embed.weight` out
+ * of the file.  out[b, r, h] = sum over n = 0 .. N-1, in that order, of w[b, r, n] * table[ids[b, n], h]; each product and
+ * each sum is rounded to fp32 on its own (no fused multiply-add).  w = values, or with normalize: values / s, a correctly
+ * rounded division by s = values[b, r, 0] + values[b, r, 1] + ... in index order.  Nothing is read back: negative
+ * proportions and a zero sum are the caller's to exclude, and IEEE arithmetic gives what it gives (a zero sum: inf or NaN).
+ * A padding speaker is an id with value 0.  `out` is what the stage calls take as spk_embed with spk_rows = rows.
+ * One launch: lanes run along H (16 bytes per lane where H % 4 == 0 and table and out are 16-byte aligned), and all lanes of
+ * a (b, r) row read its weights at one address per step.  The ids travel to the device in the object's own small buffer,
+ * stream-ordered (use one object per stream).
+ * DSD_EINVAL, with nothing launched: a NULL object, args or pointer, a wrong struct_size, a model without use_spk_id or
+ * with a frozen_spk_embed (the acoustic twin), B, rows or N below 1, an id outside [0, num_spk).
+ * The variance entry reads the tables section's spk_embed.weight; rows is 1, L (dsd_variance_dur) or T.
+ */
+typedef struct dsd_spk_mix_args {
+    int32_t struct_size;
+    int32_t B, rows, N;        /* rows: 1 or the stage's length; N >= 1                                         */
+    const int32_t* ids;        /* HOST [B, N], each in [0, num_spk)                                             */
+    const float* values;       /* device [B, rows, N]                                                           */
+    int32_t normalize;         /* 0/1: 1 divides each value by its row's sum                                    */
+    float* out;                /* device [B, rows, H]                                                           */
+} dsd_spk_mix_args;
+int dsd_variance_spk_mix(dsd_variance* v, const dsd_spk_mix_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The acoustic model's staged twin on one model file: DiffSingerAcousticONNX (deployment/modules/toplevel.py:20-103) with
  * FastSpeech2AcousticONNX.forward (deployment/modules/fastspeech2.py:43-130) as its first stage and GaussianDiffusionONNX /
@@ -1609,6 +1669,23 @@ int dsd_acoustic_start(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const f
  */
 int dsd_acoustic_sample(dsd_acoustic* a, const dsd_acoustic_plan_t* plan, const float* condition, const float* x,
                         const float* step_noise, int32_t B, int32_t T, uint32_t flags, float* mel, void* stream);
+
+/*
+ * Ragged lengths through the acoustic object.  Replaces: the one-utterance-per-call loop of inference/ds_acoustic.py:214-271
+ * for a C caller, as dsd_set_lengths does for a handle.  lengths: HOST array of B values, copied; NULL restores dense
+ * batches.  It applies to the following dsd_acoustic_condition / _start / _sample calls at batch size B until changed: item
+ * b of a padded batch comes out as the same item run alone through the same calls at T = lengths[b] - condition, aux mel and
+ * mel over t < lengths[b]; outputs at t >= lengths[b] are unspecified.  The encoder gives this by itself (its frames do not
+ * mix along time); the aux decoder and the denoiser get it from dsd_set_lengths on the inner handles, which this call sets
+ * both or, on a refusal, neither.  The object touches the inner handles' lengths only inside this call: a caller who set
+ * lengths on a borrowed handle and never calls this keeps that behaviour.  Works with DSD_SAMPLE_GRAPH / _GRAPH_LAZY (the
+ * graph key holds the lengths), with the chunked ancestral sampler, and with dsd_noise_fill in place on x (element (m, t) of
+ * x_T does not depend on T).  DSD_EINVAL: a NULL object, B < 1, a negative length; then, from the stage calls: a length above
+ * that call's T (DSD_EINVAL) and a call at another B (DSD_ESTATE).
+ */
+int dsd_acoustic_set_lengths(dsd_acoustic* a, const int32_t* lengths, int32_t B, void* stream);
+/* dsd_spk_mix_args (above dsd_variance_spk_mix) on the table the encoder handle holds; rows is 1 or T */
+int dsd_acoustic_spk_mix(dsd_acoustic* a, const dsd_spk_mix_args* args, void* stream);
 
 #ifdef __cplusplus
 }
