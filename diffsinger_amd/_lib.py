@@ -58,6 +58,7 @@ EXPORTS = [
     "dsd_acoustic_open", "dsd_acoustic_close", "dsd_acoustic_info", "dsd_acoustic_handle", "dsd_acoustic_condition",
     "dsd_acoustic_plan", "dsd_acoustic_start", "dsd_acoustic_sample",
     "dsd_acoustic_set_lengths", "dsd_acoustic_spk_mix", "dsd_variance_spk_mix", "dsd_vocode_seeded",
+    "dsd_word_dur", "dsd_group_midi", "dsd_rhythm_align", "dsd_variance_set_lengths",
 ]
 DSD_API_VERSION = 10
 DSD_EINVAL, DSD_ESTATE, DSD_EHIP, DSD_ENOMEM, DSD_ENOTFOUND, DSD_EIO = -1, -2, -3, -4, -5, -6
@@ -246,6 +247,23 @@ class DsdAcousticPlan(C.Structure):
                 ("n_step_noise", C.c_int32), ("src_scale", C.c_float), ("noise_scale", C.c_float), ("steps", C.c_int32)]
 
 
+class DsdWordDurArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("N", C.c_int32), ("W", C.c_int32), ("dur", C.c_void_p),
+                ("index", C.c_void_p), ("slur", C.c_void_p), ("totals", C.POINTER(C.c_int64)), ("word_dur", C.c_void_p),
+                ("index_out", C.c_void_p)]
+
+
+class DsdGroupMidiArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("Nn", C.c_int32), ("G", C.c_int32), ("L", C.c_int32), ("T", C.c_int32),
+                ("note_midi", C.c_void_p), ("note_dur", C.c_void_p), ("group_dur", C.c_void_p), ("ph2word", C.c_void_p),
+                ("midi", C.c_void_p)]
+
+
+class DsdRhythmAlignArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("L", C.c_int32), ("W", C.c_int32), ("ph_dur_pred", C.c_void_p),
+                ("ph2word", C.c_void_p), ("word_dur", C.c_void_p), ("ph_dur", C.c_void_p)]
+
+
 class DsdSpkMixArgs(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("B", C.c_int32), ("rows", C.c_int32), ("N", C.c_int32),
                 ("ids", C.POINTER(C.c_int32)), ("values", C.c_void_p), ("normalize", C.c_int32), ("out", C.c_void_p)]
@@ -422,6 +440,10 @@ def _load():
     lib.dsd_acoustic_spk_mix.argtypes = [vp, C.POINTER(DsdSpkMixArgs), vp]
     lib.dsd_variance_spk_mix.argtypes = [vp, C.POINTER(DsdSpkMixArgs), vp]
     lib.dsd_vocode_seeded.argtypes = [C.POINTER(DsdVocodeSeededArgs), vp]
+    lib.dsd_word_dur.argtypes = [i32, C.POINTER(DsdWordDurArgs), vp]
+    lib.dsd_group_midi.argtypes = [i32, C.POINTER(DsdGroupMidiArgs), vp]
+    lib.dsd_rhythm_align.argtypes = [i32, C.POINTER(DsdRhythmAlignArgs), vp]
+    lib.dsd_variance_set_lengths.argtypes = [vp, C.POINTER(C.c_int32), i32, vp]
     lib.dsd_get_stats.argtypes = [vp, C.POINTER(DsdStats)]
     lib.dsd_kernel_timing.argtypes = [vp, i32]
     lib.dsd_set_precision.argtypes = [vp, i32]

@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdsdenoise.so")
-SOURCES = ["gemm.hip", "wn_layer.hip", "wn_layer_x3.hip", "wn_rowsplit.hip", "wn_rows.hip", "wn_edge.hip", "lynx_layer.hip", "lynx_x3.hip", "aux_kernels.hip", "encoder_kernels.hip", "vocoder_kernels.hip", "tconv.hip", "voc_x3.hip", "mel_kernels.hip", "rmvpe_kernels.hip", "hnsep_kernels.hip", "frames_kernels.hip", "curve_kernels.hip", "noise_kernels.hip", "track_kernels.hip", "score_kernels.hip", "stage_kernels.hip", "acoustic_kernels.hip", "spk_mix_kernels.hip", "api.hip", "mel_api.hip", "rmvpe_api.hip", "hnsep_api.hip", "frames_api.hip", "curve_api.hip", "noise_api.hip", "program_api.hip", "track_api.hip", "score_api.hip", "model_file.hip", "model_api.hip", "variance_tables.hip", "variance_api.hip", "acoustic_tables.hip", "acoustic_api.hip"]
-HEADERS = [os.path.join(CSRC, "dsd_internal.h"), os.path.join(CSRC, "api_host.h"), os.path.join(CSRC, "dsd_device.h"), os.path.join(CSRC, "curve_params.h"), os.path.join(CSRC, "ragged_tiles.h"), os.path.join(CSRC, "variance_tables.h"), os.path.join(CSRC, "acoustic_tables.h"), os.path.join(os.path.dirname(HERE), "include", "dsdenoise.h")]
+SOURCES = ["gemm.hip", "wn_layer.hip", "wn_layer_x3.hip", "wn_rowsplit.hip", "wn_rows.hip", "wn_edge.hip", "lynx_layer.hip", "lynx_x3.hip", "aux_kernels.hip", "encoder_kernels.hip", "vocoder_kernels.hip", "tconv.hip", "voc_x3.hip", "mel_kernels.hip", "rmvpe_kernels.hip", "hnsep_kernels.hip", "frames_kernels.hip", "curve_kernels.hip", "noise_kernels.hip", "track_kernels.hip", "score_kernels.hip", "stage_kernels.hip", "acoustic_kernels.hip", "spk_mix_kernels.hip", "words_kernels.hip", "api.hip", "mel_api.hip", "rmvpe_api.hip", "hnsep_api.hip", "frames_api.hip", "curve_api.hip", "noise_api.hip", "program_api.hip", "track_api.hip", "score_api.hip", "model_file.hip", "model_api.hip", "variance_tables.hip", "variance_api.hip", "acoustic_tables.hip", "acoustic_api.hip", "words_api.hip"]
+HEADERS = [os.path.join(CSRC, "dsd_internal.h"), os.path.join(CSRC, "api_host.h"), os.path.join(CSRC, "dsd_device.h"), os.path.join(CSRC, "curve_params.h"), os.path.join(CSRC, "words_params.h"), os.path.join(CSRC, "ragged_tiles.h"), os.path.join(CSRC, "variance_tables.h"), os.path.join(CSRC, "acoustic_tables.h"), os.path.join(os.path.dirname(HERE), "include", "dsdenoise.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 FILE_FLAGS = {}           # per-file extra flags (none needed today; tools/check_resources.py and the stamp tools honour them)

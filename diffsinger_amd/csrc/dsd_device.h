@@ -228,6 +228,47 @@ __device__ __forceinline__ void philox_normal2(unsigned w0, unsigned w1, float& 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The prefix sum of one row of at most 8 * 256 counts by a workgroup of 256 lanes (frames_kernels.hip, words_kernels.hip):
+// cum[i] = min(value(0) + .. + value(i), cap) for i < n.  Each lane sums `per` contiguous values, the 256 lane totals are
+// scanned through `part` (256 ints), and the lane adds what stands before it.  value(i) must lie in [0, cap]: every partial
+// sum then saturates at cap, so nothing overflows, and a sum that has reached cap stays there.  Ends on a barrier: every
+// lane may read all of cum afterwards.  `cum` and `part` are LDS; all 256 lanes must call.
+// ---------------------------------------------------------------------------------------------
+template <typename Value>
+__device__ __forceinline__ void block_prefix_capped(int* cum, int* part, int n, int cap, Value&& value) {
+    const int tid = threadIdx.x;
+    const int per = (n + 255) / 256;                       // <= 8 contiguous values per lane
+    const int lo = min(tid * per, n), hi = min(lo + per, n);
+    int run = 0;
+    for (int i = lo; i < hi; ++i) {
+        run = (int)min((long long)run + value(i), (long long)cap);
+        cum[i] = run;
+    }
+    part[tid] = run;
+    __syncthreads();
+    for (int s = 1; s < 256; s <<= 1) {                    // inclusive scan of the 256 lane totals
+        const int add = tid >= s ? part[tid - s] : 0;
+        __syncthreads();
+        part[tid] = (int)min((long long)part[tid] + add, (long long)cap);
+        __syncthreads();
+    }
+    const int before = tid ? part[tid - 1] : 0;
+    for (int i = lo; i < hi; ++i) cum[i] = (int)min((long long)cum[i] + before, (long long)cap);
+    __syncthreads();
+}
+// the owner of frame p under such sums: the first i in [0, n) with cum[i] > p, or n (a zero count repeats its predecessor's
+// sum and is never the first)
+__device__ __forceinline__ int first_above(const int* cum, int n, int p) {
+    int a = 0, z = n;
+    while (a < z) {
+        const int m = (a + z) >> 1;
+        if (cum[m] > p) z = m;
+        else a = m + 1;
+    }
+    return a;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Diagnostic builds only (-DDSD_STAMPS; tools/stamp_*.py): thread 0 of workgroups < 4096 writes a clock into `elem` of its
 // file's stamp array, between scheduling barriers that keep the stamp at its place in the schedule.  No output value depends
 // on a stamp.  DSD_STAMP_AT: s_memtime (shader clock); DSD_STAMP_WITH(elem, __builtin_amdgcn_s_memrealtime): 100 MHz wall clock.

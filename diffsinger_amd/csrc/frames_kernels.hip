@@ -21,33 +21,13 @@ __global__ __launch_bounds__(256) void length_regulate_kernel(const long long* _
     __shared__ int part[256];
     const int b = blockIdx.x, tid = threadIdx.x;
     const long long* d = dur + (long)b * L;
-    const int per = (L + 255) / 256;                       // <= 8 contiguous tokens per lane
-    const int lo = min(tid * per, L), hi = min(lo + per, L);
-    int run = 0;
-    for (int i = lo; i < hi; ++i) {
+    block_prefix_capped(cum, part, L, T, [&](int i) {
         const long long v = d[i];
-        run = (int)min((long long)run + (v > 0 ? min(v, (long long)T) : 0ll), (long long)T);
-        cum[i] = run;
-    }
-    part[tid] = run;
-    __syncthreads();
-    for (int s = 1; s < 256; s <<= 1) {                    // inclusive scan of the 256 lane totals
-        const int add = tid >= s ? part[tid - s] : 0;
-        __syncthreads();
-        part[tid] = min(part[tid] + add, T);
-        __syncthreads();
-    }
-    const int before = tid ? part[tid - 1] : 0;
-    for (int i = lo; i < hi; ++i) cum[i] = min(cum[i] + before, T);
-    __syncthreads();
+        return v > 0 ? min(v, (long long)T) : 0ll;
+    });
     long long* out = mel2x + (long)b * T;
     for (int p = tid; p < T; p += 256) {
-        int a = 0, z = L;                                  // first i in [0, L) with cum[i] > p, or L
-        while (a < z) {
-            const int m = (a + z) >> 1;
-            if (cum[m] > p) z = m;
-            else a = m + 1;
-        }
+        const int a = first_above(cum, L, p);
         out[p] = a < L ? a + 1 : 0;
     }
 }

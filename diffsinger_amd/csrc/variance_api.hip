@@ -22,6 +22,10 @@ struct dsd_variance {
     // stage stays valid until that stage is called with larger sizes
     DevBuf<char> ws_encode, ws_dur, ws_pitch, ws_cond;
     SpkMixIds spk_ids;                  // dsd_variance_spk_mix's ids on the device
+    // dsd_variance_set_lengths: the lengths the frame-level stage calls check their (B, T) against and dsd_frame_curve takes;
+    // the two denoisers hold their own copies
+    bool ragged = false;
+    std::vector<int32_t> lengths;
     const float* tab(int j) const { return tables.p + off[(size_t)j]; }
     ~dsd_variance() {
         for (dsd_handle* h : {fs2, melody, pitch, variances})
@@ -99,6 +103,17 @@ void add_term(dsd_assemble_args& a, const float* s, const float* vec) {
 // the speaker gather of deploy.py's _spk_gather: [B, rows, H] at index t (rows == len > 1) or 0
 void add_spk(dsd_assemble_args& a, const float* spk_embed, int rows, int H, const int64_t* spk_idx) {
     add_gather(a, spk_embed, (int64_t)rows * H, rows, spk_idx, 0, 1.0f);
+}
+
+// dsd_set_lengths' rules for the frame-level stage calls, checked by the object itself: none of them reaches a denoiser that would
+int check_lengths(const dsd_variance* v, const char* who, int B, int T) {
+    if (!v->ragged) return DSD_OK;
+    if ((int)v->lengths.size() != B)
+        return fail(nullptr, DSD_ESTATE, "%s: dsd_variance_set_lengths gave %d lengths but this call runs a batch of %d", who,
+                    (int)v->lengths.size(), B);
+    for (int b = 0; b < B; ++b)
+        if (v->lengths[(size_t)b] > T) return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d exceeds T = %d", who, b, v->lengths[(size_t)b], T);
+    return DSD_OK;
 }
 
 int section_of(const dsd_model_file* f, const std::string& name, const char* who, bool tables, dsd_model_section_info* info) {
@@ -340,6 +355,13 @@ int dsd_variance_pitch_cond(dsd_variance* v, const dsd_variance_pitch_cond_args*
         for (int b = 0; b < a->B; ++b)
             if (a->lengths[b] < 0 || a->lengths[b] > a->T)
                 return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d outside [0, T = %d]", who, b, a->lengths[b], a->T);
+    if (int rc = check_lengths(v, who, a->B, a->T)) return rc;
+    if (v->ragged && a->lengths)
+        for (int b = 0; b < a->B; ++b)
+            if (a->lengths[b] != v->lengths[(size_t)b])
+                return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d, but dsd_variance_set_lengths gave %d", who, b, a->lengths[b],
+                            v->lengths[(size_t)b]);
+    const int32_t* lengths = v->ragged ? v->lengths.data() : a->lengths;
     const int B = a->B, L = a->L, N = a->N, T = a->T, H = c.hidden_size, Hm = c.melody_hidden_size;
     const size_t nt = (size_t)B * T, nn = (size_t)B * N;
     HIP_OK(nullptr, hipSetDevice(v->device));       // before the workspace is sized: it lives on the object's device
@@ -394,7 +416,7 @@ int dsd_variance_pitch_cond(dsd_variance* v, const dsd_variance_pitch_cond_args*
         float* base = mel ? a->base_pitch : other_a;
         float* blend = mel ? other_a : a->base_pitch;
         float* delta = other_b;
-        LIB_OK(who, dsd_frame_curve(v->device, a->note_midi, mel2note, a->pitch, a->retake, B, N, T, a->lengths, v->taps, c.smooth_width, base,
+        LIB_OK(who, dsd_frame_curve(v->device, a->note_midi, mel2note, a->pitch, a->retake, B, N, T, lengths, v->taps, c.smooth_width, base,
                                     blend, delta, stream), "the base pitch");
         dsd_assemble_args as;
         init_assemble(as, v, B, T, H);
@@ -422,6 +444,7 @@ int dsd_variance_cond(dsd_variance* v, const dsd_variance_cond_args* a, void* st
         if (!a->curves[i]) return fail(nullptr, DSD_EINVAL, "%s: NULL curves[%d] (%s)", who, i, kVarianceNames[v->var_slot[i]]);
     if (int rc = check_sizes(who, a->B, a->L, -1, -1, a->T)) return rc;
     if (int rc = check_spk(who, v, a->spk_embed, a->spk_rows, a->T, "T")) return rc;
+    if (int rc = check_lengths(v, who, a->B, a->T)) return rc;
     const int B = a->B, L = a->L, T = a->T, H = c.hidden_size, V = v->n_var;
     const size_t nt = (size_t)B * T;
     HIP_OK(nullptr, hipSetDevice(v->device));       // before the workspace is sized: it lives on the object's device
@@ -468,6 +491,7 @@ int dsd_variance_pitch_post(dsd_variance* v, const float* sample, const float* b
     if (!v->cfg.predict_pitch) return fail(nullptr, DSD_EINVAL, "%s: the model has no pitch predictor (predict_pitch = 0)", who);
     if (!sample || !base_pitch || !pitch_pred) return fail(nullptr, DSD_EINVAL, "%s: NULL sample, base_pitch or pitch_pred", who);
     if (int rc = check_sizes(who, B, -1, -1, -1, T)) return rc;
+    if (int rc = check_lengths(v, who, B, T)) return rc;
     StagePostP p;
     memset(&p, 0, sizeof(p));
     p.sample = sample; p.base = base_pitch; p.out[0] = pitch_pred;
@@ -487,6 +511,7 @@ int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T
         if (!curves_out[i]) return fail(nullptr, DSD_EINVAL, "%s: NULL curves_out[%d] (%s)", who, i, kVarianceNames[v->var_slot[i]]);
     if (int rc = check_sizes(who, B, -1, -1, -1, T)) return rc;
     if ((int64_t)B * T * v->n_var > INT32_MAX) return fail(nullptr, DSD_EINVAL, "%s: B * V * T exceeds 2^31 - 1", who);
+    if (int rc = check_lengths(v, who, B, T)) return rc;
     StagePostP p;
     memset(&p, 0, sizeof(p));
     p.sample = sample; p.base = nullptr;
@@ -498,6 +523,22 @@ int dsd_variance_post(dsd_variance* v, const float* sample, int32_t B, int32_t T
     }
     HIP_OK(nullptr, hipSetDevice(v->device));
     LAUNCH_OK(who, launch_stage_post(p, B, (hipStream_t)stream), "the post kernel");
+    return DSD_OK;
+}
+
+int dsd_variance_set_lengths(dsd_variance* v, const int32_t* lengths, int32_t B, void* stream) {
+    const char* who = "dsd_variance_set_lengths";
+    if (!v) return fail(nullptr, DSD_EINVAL, "%s: NULL object", who);
+    if (lengths) {      // everything dsd_set_lengths would refuse, first: the two denoisers are then set both, or neither
+        if (B < 1 || B > kMaxItems) return fail(nullptr, DSD_EINVAL, "%s: B = %d outside [1, %d]", who, B, kMaxItems);
+        for (int b = 0; b < B; ++b)
+            if (lengths[b] < 0) return fail(nullptr, DSD_EINVAL, "%s: lengths[%d] = %d is negative", who, b, lengths[b]);
+    }
+    if (v->pitch) HANDLE_OK(who, v->pitch, dsd_set_lengths(v->pitch, lengths, B, stream), "the pitch predictor");
+    if (v->variances) HANDLE_OK(who, v->variances, dsd_set_lengths(v->variances, lengths, B, stream), "the variance predictor");
+    v->ragged = lengths != nullptr;
+    if (lengths) v->lengths.assign(lengths, lengths + B);
+    else v->lengths.clear();
     return DSD_OK;
 }
 

@@ -79,6 +79,16 @@ class Variance:
         return _spk_mix(_lib.lib().dsd_variance_spk_mix, "dsd_variance_spk_mix", self._v, self.device, self.cfg.hidden_size, ids,
                         values, normalize, out)
 
+    def set_lengths(self, lengths):
+        """dsd_variance_set_lengths: B frame counts for the following pitch_cond / cond / post calls and both denoisers, or
+        None for dense batches"""
+        if lengths is None:
+            arr, n = None, 0
+        else:
+            lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            arr, n = (C.c_int32 * len(lens))(*lens), len(lens)
+        _lib.check(None, _lib.lib().dsd_variance_set_lengths(self._v, arr, n, _stream(self.device)), "dsd_variance_set_lengths")
+
     # ---- stages ------------------------------------------------------------------------------------------
     def encode(self, tokens, word_div=None, word_dur=None, ph_dur=None, languages=None, want_ph2word=False):
         """-> encoder_out [B, L, H], x_masks [B, L] bool (, ph2word [B, L])"""

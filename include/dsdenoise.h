@@ -1687,6 +1687,97 @@ int dsd_acoustic_set_lengths(dsd_acoustic* a, const int32_t* lengths, int32_t B,
 /* dsd_spk_mix_args (above dsd_variance_spk_mix) on the table the encoder handle holds; rows is 1 or T */
 int dsd_acoustic_spk_mix(dsd_acoustic* a, const dsd_spk_mix_args* args, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The variance front end's score algebra: what stands between a score and the inputs of dsd_variance_encode / _dur
+ * (word_dur, ph_midi), and between dsd_variance_dur's prediction and the integer durations every later stage takes.
+ * Three handle-free entries in the style of dsd_length_regulate: `device` is the HIP device index; every array is on the
+ * device but the ones marked HOST; every argument is checked on the host before the first launch; nothing is read back, no
+ * device memory is kept, and each call can be captured in a HIP graph.  B lies in [1, 65535]; every token, word or note
+ * count in [1, 2048].  DSD_EINVAL, with nothing launched: NULL args or a NULL required pointer, a wrong struct_size, a size
+ * outside those ranges, and what each entry names below.  DSD_API_VERSION stays 10: the entries are additions.
+ * ------------------------------------------------------------------------------------------ */
+/*
+ * Replaces: word_dur from ph_num / ph_dur or from note_slur / note_dur, and its alignment to the notes' frames
+ * (inference/ds_variance.py:185-206).
+ *   index[i]        = the given index (the front end's ph2word: 1-based, 0 for a padding phone), or with `slur` the
+ *                     inclusive count of the non-slur notes up to and including note i: cumsum(~is_slur).  A leading slur
+ *                     has index 0 and is dropped, as by the reference's [:, 1:].  A padding note carries slur = 1, dur = 0.
+ *   word_dur[w - 1] = the sum of dur[i] over index[i] == w; an index outside [1, W] adds nothing.  int64 arithmetic:
+ *                     exact in any order (the reference's scatter_add).
+ * With `totals` the words are aligned to the item's frame count as :202-205 does through mel2word: with
+ * c[w] = min(word_dur[0] + .. + word_dur[w], totals[b]) the durations become c[w] - c[w - 1] (what a cut mel2word counts),
+ * and where the sum is smaller than totals[b] the last word with a non-zero duration takes the rest (the padding with
+ * mel2word's last value).  An item whose words are all zero stays all zero.  Exactly one of index and slur is given; a
+ * total outside [0, 2^31 - 1] is DSD_EINVAL.  Negative durations are the caller's to exclude.
+ */
+typedef struct dsd_word_dur_args {
+    int32_t struct_size;
+    int32_t B, N, W;              /* N phones (index) or notes (slur); W words                                 */
+    const int64_t* dur;           /* [B, N] frames per phone or note                                           */
+    const int64_t* index;         /* [B, N], or NULL                                                           */
+    const uint8_t* slur;          /* [B, N] bytes (non-zero = slur), or NULL                                   */
+    const int64_t* totals;        /* HOST [B] frame counts, or NULL: no alignment                              */
+    int64_t* word_dur;            /* [B, W]                                                                    */
+    int64_t* index_out;           /* [B, N] or NULL: the index itself, if wanted                               */
+} dsd_word_dur_args;
+int dsd_word_dur(int32_t device, const dsd_word_dur_args* args, void* stream);
+/*
+ * Replaces: the `midi` input of the variance model, the rounded per-phone or per-word mean of the frame MIDI curve
+ * (inference/ds_variance.py:219-241).  Frames belong to notes (note_dur) and to groups (group_dur: ph_dur, or the aligned
+ * word_dur) exactly as dsd_length_regulate assigns them at this T: a zero duration owns no frame, and a frame at or past a
+ * row's total belongs to nothing - the frame MIDI there is 0, the F.pad(note_midi, [1, 0]) row.  For group g with
+ * n = group_dur[g] and its frames' MIDI values m_0, m_1, .. in frame order,
+ *   sum = ((0.0f + m_0 / (float)n) + m_1 / (float)n) + ..      every division and addition rounded to fp32 on its own
+ *   r[g] = (int64)rintf(sum)                                   half to even, as torch.round; 0 for a group with no frame
+ * which is torch's CPU scatter_add of frame_midi / mel2dur, bit for bit.  Without ph2word, midi [B, G] = r.  With it the
+ * groups are words and midi [B, L] is gathered: midi[b, i] = r[ph2word[b, i] - 1], 0 for an index outside [1, G].
+ * One lane walks a group's frames (the sum is one dependent chain by definition): the cost is T additions at most.
+ * note_midi holds the rests already filled (:138-145).  L is 0 without ph2word; T < 1 is DSD_EINVAL.
+ */
+typedef struct dsd_group_midi_args {
+    int32_t struct_size;
+    int32_t B, Nn, G, L, T;       /* Nn notes, G groups, L phones (0 without ph2word), T frames                */
+    const float* note_midi;       /* [B, Nn]                                                                   */
+    const int64_t* note_dur;      /* [B, Nn]                                                                   */
+    const int64_t* group_dur;     /* [B, G]                                                                    */
+    const int64_t* ph2word;       /* [B, L] or NULL                                                            */
+    int64_t* midi;                /* [B, L] with ph2word, else [B, G]                                          */
+} dsd_group_midi_args;
+int dsd_group_midi(int32_t device, const dsd_group_midi_args* args, void* stream);
+/*
+ * Replaces: RhythmRegulator.forward with its default eps = 1e-5 (modules/fastspeech/tts_modules.py:250-275), called on the
+ * duration predictor's output at inference/ds_variance.py:339.
+ *   d[i]     = ph_dur_pred[i] * (ph2word[i] > 0)
+ *   s[w]     = the fp32 sum of d[i] over ph2word[i] == w, in index order from 0.0f (torch's CPU scatter_add)
+ *   alpha[w] = (float)word_dur[w - 1] / max(s[w], 1e-5f),  alpha[0] = 0
+ *   ph_dur[i] = (int64)rintf(d[i] * alpha[ph2word[i]])      half to even
+ * defined for ph2word in any order, not only the non-decreasing one dsd_length_regulate makes.  An index outside [0, W]
+ * adds nothing and gets duration 0.
+ */
+typedef struct dsd_rhythm_align_args {
+    int32_t struct_size;
+    int32_t B, L, W;
+    const float* ph_dur_pred;     /* [B, L]                                                                    */
+    const int64_t* ph2word;       /* [B, L]                                                                    */
+    const int64_t* word_dur;      /* [B, W]                                                                    */
+    int64_t* ph_dur;              /* [B, L]                                                                    */
+} dsd_rhythm_align_args;
+int dsd_rhythm_align(int32_t device, const dsd_rhythm_align_args* args, void* stream);
+
+/*
+ * Ragged lengths through the variance object: the twin of dsd_acoustic_set_lengths.  Replaces: the one-segment-per-call loop
+ * of inference/ds_variance.py:344-360 for a C caller.  lengths: HOST array of B frame counts, copied; NULL restores dense
+ * batches bit for bit.  Everything dsd_set_lengths would refuse is checked first (B outside [1, 65535], a negative length:
+ * DSD_EINVAL); then dsd_set_lengths runs on each denoiser the model has, so both are set, or neither.  The object keeps its
+ * own copy and checks the (B, T) of the following dsd_variance_pitch_cond / _cond / _pitch_post / _post calls against it:
+ * another B is DSD_ESTATE, a length above T is DSD_EINVAL.  dsd_variance_pitch_cond with args->lengths == NULL then takes
+ * the object's copy for dsd_frame_curve; a non-NULL args->lengths that differs from the copy is DSD_EINVAL.  The token-level
+ * stages need nothing (their padding is tokens == 0).  Item b of a padded batch comes out as the same item run alone at
+ * T = lengths[b]; outputs at or past lengths[b] are whatever the padded computation gives: read lengths[b] frames.
+ * Without this call no stage changes.
+ */
+int dsd_variance_set_lengths(dsd_variance* v, const int32_t* lengths, int32_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
