@@ -3056,10 +3056,12 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
     int rc = enter(h, "dsd_sample", K_DENOISER, ENTER_LAUNCH);       // weights: as dsd_denoise
     if (rc) return rc;
     if (!h->cond_ready) return fail(h, DSD_ESTATE, "dsd_sample: call dsd_prepare_cond first");
-    if (prog->n_bufs < 1 || prog->n_bufs > 64 || prog->n_evals < 0 || (prog->n_evals > 0 && !prog->evals))
-        return fail(h, DSD_EINVAL, "dsd_sample: malformed program");
-    if (prog->result_buf < 0 || prog->result_buf >= prog->n_bufs) return fail(h, DSD_EINVAL, "dsd_sample: bad result_buf");
-    if (prog->n_noise > 0 && !noise) return fail(h, DSD_EINVAL, "dsd_sample: program references noise but noise == NULL");
+    if (prog->n_bufs < 1 || prog->n_bufs > 64) return fail(h, DSD_EINVAL, "dsd_sample: bad n_bufs %d (1..64)", prog->n_bufs);
+    if (prog->n_evals < 0) return fail(h, DSD_EINVAL, "dsd_sample: bad n_evals %d", prog->n_evals);
+    if (prog->n_evals > 0 && !prog->evals) return fail(h, DSD_EINVAL, "dsd_sample: evals == NULL with n_evals %d", prog->n_evals);
+    if (prog->result_buf < 0 || prog->result_buf >= prog->n_bufs)
+        return fail(h, DSD_EINVAL, "dsd_sample: bad result_buf %d", prog->result_buf);
+    if (prog->n_noise > 0 && !noise) return fail(h, DSD_EINVAL, "dsd_sample: program references noise (n_noise %d) but noise == NULL", prog->n_noise);
     hipStream_t st = (hipStream_t)stream;
     const int B = h->B, T = h->T, Ts = h->Ts, FM = FM_of(h);
     // validate the program before anything is launched
@@ -3070,7 +3072,11 @@ int dsd_sample(dsd_handle* h, const dsd_program* prog, const float* x_init, cons
         for (int o = 0; o < ev.n_out; ++o) {
             const dsd_lincomb& lc = ev.out[o];
             if (lc.dst < 0 || lc.dst >= prog->n_bufs) return fail(h, DSD_EINVAL, "eval %d out %d: bad dst %d", i, o, lc.dst);
-            if (lc.n_terms < 1 || lc.n_terms > DSD_MAX_TERMS) return fail(h, DSD_EINVAL, "eval %d out %d: bad n_terms", i, o);
+            // (the outputs of one evaluation are stored in no promised order: two of them into one buffer have no defined result)
+            for (int o2 = 0; o2 < o; ++o2)
+                if (ev.out[o2].dst == lc.dst)
+                    return fail(h, DSD_EINVAL, "eval %d out %d: duplicate dst %d (also out %d)", i, o, lc.dst, o2);
+            if (lc.n_terms < 1 || lc.n_terms > DSD_MAX_TERMS) return fail(h, DSD_EINVAL, "eval %d out %d: bad n_terms %d", i, o, lc.n_terms);
             for (int k = 0; k < lc.n_terms; ++k) {
                 const int s = lc.terms[k].src;
                 const bool ok = (s >= 0 && s < prog->n_bufs) || s == DSD_SRC_MODEL ||

@@ -749,8 +749,12 @@ typedef struct dsd_term {
     float coef;
 } dsd_term;
 
+/* One output of an evaluation.  All outputs of an evaluation read the buffers as they were BEFORE it, so a destination may be
+ * a source of the same or of another output (a swap is two outputs).  The outputs of one evaluation must have DISTINCT
+ * destinations: they are stored in no promised order, so dsd_sample refuses a duplicate dst with DSD_EINVAL.  A source may be
+ * listed more than once in one combination (the model output included); the terms are summed. */
 typedef struct dsd_lincomb {
-    int32_t dst;      /* state buffer id */
+    int32_t dst;      /* state buffer id; distinct among the outputs of one evaluation */
     int32_t n_terms;  /* 1..DSD_MAX_TERMS */
     dsd_term terms[DSD_MAX_TERMS];
 } dsd_lincomb;
@@ -762,8 +766,12 @@ typedef struct dsd_eval {
     dsd_lincomb out[DSD_MAX_OUT];
 } dsd_eval;
 
+/* Buffer 0 holds x_init on entry.  Every OTHER buffer is undefined on entry - it holds whatever the handle's previous call
+ * left there (the buffers are cleared only when they are allocated) - so a program reads a buffer other than 0, as x_buf or as
+ * a source, only after an earlier evaluation has written it.  dsd_sample checks the ranges below (DSD_EINVAL, before anything
+ * is launched), not this order. */
 typedef struct dsd_program {
-    int32_t n_bufs;          /* number of state buffers (each [B, F*M, T]); buffer 0 = x_T on entry */
+    int32_t n_bufs;          /* number of state buffers, 1..64 (each [B, F*M, T]); buffer 0 = x_T on entry, the rest undefined */
     int32_t result_buf;      /* buffer holding the sample after the last evaluation */
     int32_t n_evals;
     int32_t n_noise;         /* number of injected [B,F,M,T] noise tensors referenced by terms */

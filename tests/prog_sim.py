@@ -7,8 +7,10 @@ from diffsinger_amd import schedule
 F32 = np.float32
 
 
-def run_program(prog, model, x_init, cond, noise=None):
-    """model(x[B,F,M,T], t[B] float32, cond) -> [B,F,M,T]; returns the result buffer [B,F,M,T]."""
+def run_program(prog, model, x_init, cond, noise=None, all_bufs=False):
+    """model(x[B,F,M,T], t[B] float32, cond) -> [B,F,M,T]; returns the result buffer [B,F,M,T], or with all_bufs the list of
+    all n_bufs buffers as the last evaluation left them (a buffer the program never wrote, other than 0, is zeros here and
+    undefined in the library)."""
     bufs = [np.zeros_like(x_init, dtype=F32) for _ in range(prog.n_bufs)]
     bufs[0] = np.asarray(x_init, dtype=F32).copy()
     bsz = x_init.shape[0]
@@ -28,7 +30,7 @@ def run_program(prog, model, x_init, cond, noise=None):
             new.append((dst, acc))
         for dst, acc in new:
             bufs[dst] = acc
-    return bufs[prog.result_buf]
+    return bufs if all_bufs else bufs[prog.result_buf]
 
 
 def finish(x, spec_min=-12.0, spec_max=0.0):
