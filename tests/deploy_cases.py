@@ -88,10 +88,10 @@ VAR_CASES = OrderedDict(
 VOCAB = 12
 
 
-def variance_hparams(tag):
+def variance_hparams(tag, cases=None):
     hp = dict(BASE_HP)
     hp.update(VARIANCE_HP)
-    hp.update(VAR_CASES[tag]["hp"])
+    hp.update((cases or VAR_CASES)[tag]["hp"])
     return hp
 
 
@@ -109,9 +109,10 @@ def _split(rng, total, parts):
     return (rng.multinomial(total - floor * parts, np.ones(parts) / parts) + floor).astype(np.int64)
 
 
-def variance_inputs(tag):
-    """Seeded stage inputs of a variance case: a dict of numpy arrays (B = 1)."""
-    c, hp = VAR_CASES[tag], variance_hparams(tag)
+def variance_inputs(tag, cases=None):
+    """Seeded stage inputs of a variance case: a dict of numpy arrays (B = 1).  `cases`: another table of the same form
+    (tests/twin_config_cases.py), VAR_CASES when left out."""
+    c, hp = (cases or VAR_CASES)[tag], variance_hparams(tag, cases)
     rng = np.random.Generator(np.random.PCG64(c["seed"]))
     n_ph, n_word, t_len = c["n_ph"], c["n_word"], c["t_len"]
     out = dict(tokens=rng.integers(1, VOCAB, (1, n_ph)).astype(np.int64))
@@ -127,7 +128,7 @@ def variance_inputs(tag):
     if hp["use_lang_id"]:
         out["languages"] = rng.integers(1, hp["num_lang"] + 1, (1, n_ph)).astype(np.int64)
     if hp["use_spk_id"]:
-        out["spk_embed"] = rng.standard_normal((1, 1, HIDDEN)).astype(np.float32)
+        out["spk_embed"] = rng.standard_normal((1, 1, hp["hidden_size"])).astype(np.float32)
     out["pitch"] = (60.0 + 6.0 * np.sin(np.arange(t_len)[None] / 5.0) + rng.normal(0, 0.5, (1, t_len))).astype(np.float32)
     if hp["predict_pitch"]:
         n_note = c["n_note"]
@@ -153,9 +154,9 @@ def variance_inputs(tag):
     return out
 
 
-def variance_noise_shapes(tag):
+def variance_noise_shapes(tag, cases=None):
     """x_T shapes of the case's samplers, in the order the stages draw them: pitch first, then the variances."""
-    c, hp = VAR_CASES[tag], variance_hparams(tag)
+    c, hp = (cases or VAR_CASES)[tag], variance_hparams(tag, cases)
     shapes = {}
     if hp["predict_pitch"] and c["steps"]:
         shapes["pitch"] = (1, 1, hp["pitch_prediction_args"]["repeat_bins"], c["t_len"])

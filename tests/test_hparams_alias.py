@@ -33,8 +33,11 @@ def test_every_module_follows_the_reference_dict(monkeypatch):
             assert m.hparams is ref, m.__name__
         ref["K_step_infer"] = 123               # a later mutation by the host (scripts/infer.py --depth) is seen everywhere
         assert d.hparams["K_step_infer"] == 123 and t.hparams.get("use_shallow_diffusion") is True
-    finally:        # back to the package's own dict for the other tests
-        for m in readers:
-            m.hparams = old
+    finally:        # back to the package's own dict for the other tests: every module the call rebound, not only `readers`
+        for name, m in list(sys.modules.items()):       # (deploy.py, imported by an earlier test, would otherwise stay on `ref`)
+            if m is not None and (name == "diffsinger_amd" or name.startswith("diffsinger_amd.")) and getattr(m, "hparams", None) is ref:
+                m.hparams = old
         old.clear()
         old.update(saved)
+    for m in readers:
+        assert m.hparams is old, m.__name__
