@@ -31,13 +31,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import kernel_ledger_cases as lc  # noqa: E402
+import poison_cases as pz  # noqa: E402
 import vocoder_config_cases as vcc  # noqa: E402
 import vocoder_x3_cases as vx3  # noqa: E402
-from diffsinger_amd import _lib, synth  # noqa: E402
-from gpu_util import check, dev, make_backbone, rel_err, set_hp  # noqa: E402
+from diffsinger_amd import _lib  # noqa: E402
+from gpu_util import check, rel_err, set_hp  # noqa: E402
 from oracle import aux_decoder as oa  # noqa: E402
 from oracle import backbones as ob  # noqa: E402
-from test_gpu_aux_decoder import TOL_AUX, make_adaptor  # noqa: E402
+from test_gpu_aux_decoder import TOL_AUX  # noqa: E402
 from test_gpu_config_sweep import TOL_NFE  # noqa: E402
 from test_gpu_first_capture import SWITCHES  # noqa: E402
 from test_gpu_vocoder_x3 import TOL as TOL_VOCODER_X3  # noqa: E402
@@ -75,57 +76,42 @@ def _ran(ledger):
 
 
 # ------------------------------------------------------------------------------------------------ handles, shared by cases
-_handles = {}
+_handles = {}       # poison_cases.handle_key -> poison_cases.Handle
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release():
     yield
     for h in _handles.values():
-        h = h[0] if isinstance(h, tuple) else h
-        getattr(h, "decoder", h).release_native()
+        pz.release(h)
     _handles.clear()
 
 
-def _backbone(net):
-    if net not in _handles:
-        kind, in_dims, n_feats, args, seed = lc.NETS[net]
-        _handles[net] = make_backbone(kind, in_dims, n_feats, args, seed)
-    return _handles[net]
-
-
-def _vocoder(module, tag):
-    if (module, tag) not in _handles:
-        from diffsinger_amd.vocoder import Generator
-        g = Generator(module.config(tag))
-        g.load_state_dict({k: torch.from_numpy(v) for k, v in module.weights(tag).items()}, strict=True)
-        _handles[(module, tag)] = g.cuda().eval()
-    return _handles[(module, tag)]
+def _handle(case):
+    key = pz.handle_key(case)
+    if key not in _handles:
+        _handles[key] = pz.make_handle(case)
+    return _handles[key]
 
 
 # ------------------------------------------------------------------------------------------------ one call of each family
+# (poison_cases.py has the inputs, the handles and the call itself: test_gpu_poison.py runs the same calls)
 def run_backbone(case, reset):
     net_name, bsz, t_len, lengths = case.spec
     kind, in_dims, n_feats, args, _ = lc.NETS[net_name]
-    net, params = _backbone(net_name)
-    x = synth.synth_normal((bsz, n_feats, in_dims, t_len), 21)
-    cond = synth.synth_normal((bsz, 256, t_len), 22)
-    t = ((np.arange(bsz) * 173.25 + 7.5) % 1000.0).astype(np.float32)         # diffusion steps: [0, 1000)
+    h = _handle(case)
+    net, params = h.net, h.params
+    i = pz.clean(case)
+    x, t, cond = i["x"], i["t"], i["cond"]
     if kind == "wavenet":
         fwd = lambda xx, tt, cc: ob.wavenet_forward(params, xx, tt, cc, dilation_cycle_length=args["dilation_cycle_length"])  # noqa: E731
     else:
         fwd = lambda xx, tt, cc: ob.lynxnet_forward(params, xx, tt, cc, activation=args["activation"], strong_cond=args["strong_cond"])  # noqa: E731
-    xd, td, cd = dev(x), dev(t), dev(cond)
     net.set_precision(case.precision)
     try:
-        with torch.no_grad():
-            if lengths is not None:         # the tiles the ragged call skips hold this call's values
-                net.set_lengths(None, xd.device)
-                net(xd, td, cd)
-            net.set_lengths(lengths, xd.device)
-            torch.cuda.synchronize()
-            reset()
-            out = net(xd, td, cd).cpu().numpy()
+        if lengths is not None:         # the tiles the ragged call skips hold this call's values
+            pz.call(h, i)
+        out = pz.call(h, i, lengths, reset).cpu().numpy()
         if any("_x3_" in t for t in case.targets) or case.precision == "f32":     # (bf16x3 without a split-bf16 kernel on the
             assert net.stats()["precision"] == (1 if case.precision == "bf16x3" else 0), net.stats()      # plan reports fp32)
         if lengths is None:
@@ -134,30 +120,20 @@ def run_backbone(case, reset):
             for b, n in enumerate(lengths):
                 check(out[b:b + 1, :, :, :n], fwd(x[b:b + 1, :, :, :n], t[b:b + 1], cond[b:b + 1, :, :n]), TOL_NFE, what=(case.id, b))
     finally:
-        net.set_lengths(None, xd.device)
         net.set_precision("f32")
 
 
 def run_vocoder(case, reset):
     which, tag, bsz, t_len, lengths = case.spec
-    module = vcc if which == "configs" else vx3
+    module = pz.voc_module(which)
     x3 = case.precision == "bf16x3"
-    gen = _vocoder(module, tag)
-    upp = int(np.prod(module.config(tag)["upsample_rates"]))
-
-    def call(i, lens=None):
-        with torch.no_grad():
-            out = gen(dev(i["mel"]), dev(i["f0"]), lengths=lens, rand_ini=dev(i["rand_ini"]), noise=dev(i["noise"]),
-                      pre_noise=dev(i["pre_noise"]))
-        torch.cuda.synchronize()
-        return out
-
+    h = _handle(case)
+    gen, upp = h.net, h.upp
     gen.set_precision(case.precision)
     try:
-        i = module.inputs(tag, bsz, t_len)
+        i = pz.clean(case)
         if lengths is None:
-            reset()
-            got = call(i)
+            got = pz.call(h, i, None, reset)
             assert tuple(got.shape) == (bsz, 1, t_len * upp)
             if which == "configs":          # test_gpu_vocoder_configs.py: the case's bound in fp32, TOL in split-bf16
                 # (a shape vocoder_config_cases.FLOORS does not list: TOL itself, which bound() never goes below)
@@ -167,11 +143,10 @@ def run_vocoder(case, reset):
                 assert rel_err(got, vx3.reference(tag, bsz, t_len)) < TOL_VOCODER_X3, case.id
         else:
             own = lengths != "cases"        # "cases": the module's ragged lengths, whose references the suite shares
-            lens = list(lengths if own else module.RAGGED_LENGTHS)
+            lens = pz.grid(case)[2]
             assert bsz == len(lens) and (which == "configs" if own else t_len == module.RAGGED_T and (which == "configs" or tag == vx3.RAGGED_LAYOUT))
-            call(i)
-            reset()
-            got = call(dict(i, rand_ini=np.repeat(i["rand_ini"][None], bsz, 0)), lens)      # one row of phases per item
+            pz.call(h, i)
+            got = pz.call(h, i, lens, reset)
             for b, n in enumerate(lens):
                 if own:
                     want = vcc.oracle(tag, vcc.item_inputs(tag, bsz, t_len, b, n), np.float64)
@@ -186,20 +161,14 @@ def run_vocoder(case, reset):
 
 def run_aux(case, reset):
     net_name, bsz, t_len, lengths = case.spec
-    hsz, m, c, nl, ks, wseed = lc.AUX_NETS[net_name]
-    rng = np.random.Generator(np.random.PCG64(5))
-    smin, smax = (-12.0 + rng.random(m)).astype(np.float32), rng.random(m).astype(np.float32)
-    if net_name not in _handles:
-        _handles[net_name] = make_adaptor(hsz, m, c, nl, ks, wseed, smin, smax)
-    a, params = _handles[net_name]
-    cond = synth.synth_normal((bsz, t_len, hsz), 900 + t_len)
-    cd = dev(cond)
-    with torch.no_grad():
-        if lengths is not None:
-            a(cd, infer=True)
-        torch.cuda.synchronize()
-        reset()
-        got = a(cd, infer=True, lengths=lengths).cpu().numpy()
+    m = lc.AUX_NETS[net_name][1]
+    h = _handle(case)
+    params, smin, smax = h.params, h.smin, h.smax
+    i = pz.clean(case)
+    cond = i["cond"]
+    if lengths is not None:
+        pz.call(h, i)
+    got = pz.call(h, i, lengths, reset).cpu().numpy()
     if lengths is None:
         assert rel_err(got, oa.aux_adaptor_forward(params, cond, m, 1, smin, smax, infer=True)) < TOL_AUX, case.id
     else:
